@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the trim + pileup + call hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--depth D] [--strong]
+    python bench.py --gpus N --steps K --warmup W [--depth D] [--strong] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the whole hot path over one synthetic batch that is already resident
 in HBM: reset the device table, run the trim + pileup kernels over every read of the batch
@@ -19,19 +19,32 @@ depth: 29,903 nt synthetic genome, ARTIC-style 98-amplicon primer scheme, 150 bp
       over the ranks and every rank holds a full-size batch of its own range (the job is N x D deep)
   --strong (BASELINE config 4): ONE job of depth D; its coordinate-sorted reads are cut into N
       contiguous slices of equal base counts (parallel.shard_bounds), rank r processes slice r, and
-      rank 0 asserts that the all-reduced table is bit-identical to the table of the whole job
-      processed on one GPU.
+      with --full, rank 0 asserts that the all-reduced table is bit-identical to the table of the
+      whole job processed on one GPU.
 Either way the counts are stitched with one all-reduce of the 7 x 29,903 uint32 device table.
 
 Prints ONE JSON line on rank 0 (see the driver contract), including
   roofline:     algorithmic bytes of the CIGAR-scan pass / its HIP-event duration vs 8 TB/s.  The
                 scan pass is what amp_process_batch_device launches: k_fast (simple reads), k_tile<LIST>
                 (the other reads, straight from the fast kernel's per-block lists), k_deferred_heavy
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the line.
+Everything else runs behind the timed region only with --full:
+  roofline:     the pass alone on the whole chip (kernel_ms_alone, frac_alone, fast_kernel_ms_alone) and the
+                measured copy ceiling (peak_measured, frac_of_measured, frac_alone_of_measured)
   cpu_baseline: the C restatement in oracle/ timed on this host's cores on the same batch, plus the
-                pure-Python restatement on a 100 k-read subsample
+                pure-Python restatement on a 100 k-read subsample; its first pass checks the GPU result
   e2e:          file-to-file rates outside the timed region (host pointers, BAM -> calls, BAM -> BAM)
   extra:        BASELINE configs 3 (100k x depth, 19.9 M reads) and 5 (8.0 M mixed 75-300 bp reads), each as ONE launch behind
                 the timed region: duration of the scan pass alone, roofline fraction, oracle assertion
+  strong_check: (--strong) the bit-identity check above
+Without --full those keys are null.
+
+--dump-outputs DIR writes what the last timed step handed its caller, as float64 .npy files (bytes of text as
+float32), about 25 MB at the default depth: the count table (counts, ins_tally), the consensus string and the VCF
+body of the calls, and for a fixed seeded sample of 2^18 reads their trimmed positions, CIGAR lengths, reference
+lengths, trim flags, statuses and trimmed CIGAR words.  The inputs are seeded, so two builds run with the same
+arguments can be compared file for file.
 """
 import argparse
 import json
@@ -51,6 +64,31 @@ SCAN_KERNELS = {0: "scan pass: k_fast (k_fast5 for reads of more than 152 bases,
                 6: "scan pass: k_fast6 + k_tile<LIST> + k_deferred_heavy", 7: "scan pass: k_fast7 + k_tile<LIST> + k_deferred_heavy",
                 2: "scan pass: k_tile + k_deferred_heavy",
                 3: "scan pass: k_trim + k_scan + k_tile<SPLIT> + k_deferred_heavy", 1: "k_reads_lane"}
+DUMP_READ_SAMPLE = 1 << 18        # reads of the last step whose per-read outputs --dump-outputs writes
+DUMP_SEED = 20251016
+
+
+def dump_outputs(out_dir, batch, out, table, G, consensus, vcf_body):
+    """--dump-outputs: the last timed step's results (see the module docstring), integers as float64 (exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    tab = table.cpu().numpy().view(np.uint32)
+    arrays = {"counts": tab[:G * 6].reshape(G, 6), "ins_tally": tab[G * 6:],
+              "consensus": np.frombuffer(consensus.encode("ascii"), np.uint8).astype(np.float32),
+              "vcf": np.frombuffer(vcf_body.encode("ascii"), np.uint8).astype(np.float32)}
+    n = batch.n
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_READ_SAMPLE), replace=False))
+    idx_t = torch.from_numpy(idx).to(out["new_pos"].device)
+    arrays["read_index"] = idx
+    for k in ("new_pos", "new_ncig", "ref_len", "trim_flags", "status"):
+        arrays[k] = out[k].index_select(0, idx_t).cpu().numpy()
+    # read i's trimmed CIGAR is new_ncig[i] words from new_cig[cig_off[i] + 3 i] (include/amplihip.h); sampled reads in order
+    ncig = arrays["new_ncig"].astype(np.int64)
+    start = batch.cig_off32.index_select(0, idx_t).cpu().numpy().astype(np.int64) + 3 * idx
+    first = np.repeat(start - (np.cumsum(ncig) - ncig), ncig)
+    words = out["new_cig"].cpu().numpy().view(np.uint32)
+    arrays["new_cig"] = words[first + np.arange(int(ncig.sum()), dtype=np.int64)]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def main():
@@ -61,11 +99,11 @@ def main():
     os.dup2(2, 1)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200, help="timed steps (200 x 0.23 ms: with eight steps in flight a 20-step region is two and a half pipeline depths long and its fill and drain cost 10 %: 0.248 ms per step at 20, 0.226 at 200, 0.223 at 1000)")
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (200 x 0.23 ms: with eight steps in flight a 20-step region is two and a half pipeline depths long and its fill and drain cost 10 %%: 0.248 ms per step at 20, 0.226 at 200, 0.223 at 1000)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--depth", type=int, default=10000, help="mean coverage (10000 -> 1,993,533 reads): per GPU, or of the whole job with --strong")
     ap.add_argument("--strong", action="store_true", help="BASELINE config 4: one job of --depth partitioned over the ranks (strong scaling)")
-    ap.add_argument("--cpu-passes", type=int, default=0, help="passes of the CPU baseline over the batch (0 = as many as fit ~10 s; -1 = skip the CPU legs)")
+    ap.add_argument("--cpu-passes", type=int, default=0, help="passes of the CPU baseline over the batch (with --full; 0 = as many as fit ~10 s; -1 = skip the CPU legs)")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (0 = chosen per batch by the library)")
     ap.add_argument("--no-pipeline", action="store_true", help="one step at a time (default: eight steps in flight over eight streams)")
     ap.add_argument("--in-flight", type=int, default=8, help="steps in flight (each has its own engine, table and outputs)")
@@ -75,6 +113,9 @@ def main():
     ap.add_argument("--streams", type=int, default=8, help="HIP streams the steps in flight are dealt over (1: the GPU runs step after step; 2+: the next step's reads start on the CUs the last blocks of this step's reads have left)")
     ap.add_argument("--cu-share", type=int, default=0, help="size each step's scan pass for 1 / N of the CUs (0 = 2 when the steps are dealt over several streams, else 1)")
     ap.add_argument("--no-comm-overlap", action="store_true", help="multi-rank runs: all-reduce on the work stream, in front of the step's calls (default: on its own stream, under the next step's reads)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--full", action="store_true", help="also run the legs behind the timed region: the pass alone and the copy ceiling (roofline), "
+                    "cpu_baseline with its oracle check, e2e, extra and the --strong check (each can still be skipped by its own option)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -271,46 +312,50 @@ def main():
     eng, table, out_t = last["slot"].eng, last["slot"].table, last["slot"].out
     batch = last["slot"].batch           # (the checks and the byte counts below are those of the LAST step's own batch)
     rd = last["slot"].rd
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, out_t, table, G, last["consensus"], last["call"].vcf_text("SYN_REF"))
     # outside the timed region: the same launches with nothing else on the GPU (the pipelined steps above
     # overlap them with the previous step's small kernels and with the next scan, which stretches their
     # own duration while shortening the step)
     solo_pass, solo_fast = [], []
-    eng.set_cu_share(1)                  # alone, the pass has the whole chip
-    for it in range(11):                 # three untimed passes on the new grid, five timed, three with the first kernel timed on its own
-        eng.set_timing(it >= 8)          # (timing the first kernel of the pass on its own costs an idle gap)
-        with torch.cuda.stream(last["slot"].stream):
-            eng.reset()
-            eng.process_device(rd, 0, last["slot"].dev_out)
-            eng.sync()
-        t, s = eng.last_kernel_ms()
-        if it >= 3:
-            (solo_pass if it < 8 else solo_fast).append(t if it < 8 else s)
-    eng.set_timing(False)
-    eng.set_cu_share(cu_share)
-    if dist is not None:     # leave the engine with the reduced table again (the check below and the calls use it)
-        with torch.cuda.stream(last["slot"].stream):
-            parallel.allreduce_table(dist, table)
-        torch.cuda.synchronize()
+    if args.full:
+        eng.set_cu_share(1)                  # alone, the pass has the whole chip
+        for it in range(11):                 # three untimed passes on the new grid, five timed, three with the first kernel timed on its own
+            eng.set_timing(it >= 8)          # (timing the first kernel of the pass on its own costs an idle gap)
+            with torch.cuda.stream(last["slot"].stream):
+                eng.reset()
+                eng.process_device(rd, 0, last["slot"].dev_out)
+                eng.sync()
+            t, s = eng.last_kernel_ms()
+            if it >= 3:
+                (solo_pass if it < 8 else solo_fast).append(t if it < 8 else s)
+        eng.set_timing(False)
+        eng.set_cu_share(cu_share)
+        if dist is not None:     # leave the engine with the reduced table again (the check below and the calls use it)
+            with torch.cuda.stream(last["slot"].stream):
+                parallel.allreduce_table(dist, table)
+            torch.cuda.synchronize()
 
     # ---- the box's own stream ceiling (report against the spec peak AND a measured copy): 1 GiB copied device to device,
     # bytes read + bytes written over the HIP-event time of the copies
     peak_measured = None
-    try:
-        src_t = torch.empty(1 << 28, dtype=torch.float32, device=dev).normal_()
-        dst_t = torch.empty_like(src_t)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(3):
-            dst_t.copy_(src_t)
-        ev0.record()
-        for _ in range(10):
-            dst_t.copy_(src_t)
-        ev1.record()
-        torch.cuda.synchronize()
-        peak_measured = 2.0 * src_t.numel() * 4 * 10 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
-        del src_t, dst_t
-        torch.cuda.empty_cache()
-    except Exception:
-        peak_measured = None
+    if args.full:
+        try:
+            src_t = torch.empty(1 << 28, dtype=torch.float32, device=dev).normal_()
+            dst_t = torch.empty_like(src_t)
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for _ in range(3):
+                dst_t.copy_(src_t)
+            ev0.record()
+            for _ in range(10):
+                dst_t.copy_(src_t)
+            ev1.record()
+            torch.cuda.synchronize()
+            peak_measured = 2.0 * src_t.numel() * 4 * 10 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
+            del src_t, dst_t
+            torch.cuda.empty_cache()
+        except Exception:
+            peak_measured = None
     # ---- accounting (outside the timed region) ------------------------------------------------
     n_out = int(out_t["new_ncig"].sum().item())
     n_err = int((out_t["status"] != 0).sum().item())
@@ -320,7 +365,7 @@ def main():
     n_cig_in = int(batch.cig_off32[-1].item() - batch.cig_off32[0].item())
     alg_bytes = n_reads * (16 + (L + 1) // 2 + L + 8) + 4 * n_cig_in + 4 * n_out + 6 * G * 4 + 2 * G * 4
     k_ms = float(np.mean(pass_ms))
-    k_solo = float(np.mean(solo_pass))
+    k_solo = float(np.mean(solo_pass)) if solo_pass else None
     # one stream: the pass's own HIP-event duration inside the timed region; several: the region's pass rate (see roofline.note)
     k_rate_ms = k_ms if len(work_streams) == 1 else elapsed / args.steps * 1e3
     traffic = None
@@ -329,7 +374,7 @@ def main():
         traffic = json.load(open(tf)).get("depth%d_variant%d" % (args.depth, args.variant or 4))
 
     strong_check = None
-    if args.strong and rank == 0:
+    if args.full and args.strong and rank == 0:
         # bit-identity of the stitched table with the whole job on ONE GPU (A:896-915 is an order-free integer sum)
         one = Slot(whole)
         one.eng.set_cu_share(1)
@@ -344,7 +389,7 @@ def main():
         one.eng.close()
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_passes >= 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_passes >= 0:
         from concurrent.futures import ThreadPoolExecutor
         from oracle import oracle
         hb = batch.to_host()
@@ -401,7 +446,7 @@ def main():
             pass
 
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         try:
             from tools import e2e_legs
             e2e = e2e_legs.measure(batch, genome, primers, ref_seq, dev)
@@ -411,7 +456,7 @@ def main():
     # ---- the other single-GPU configs of BASELINE.json, each as ONE launch checked against the oracle (outside the timed
     # region; the driver's one run then carries their roofline figures too) ---------------------------------------------
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra and not args.strong and args.depth == 10000:
+    if args.full and rank == 0 and world == 1 and not args.no_extra and not args.strong and args.depth == 10000:
         extra = {}
         try:
             from concurrent.futures import ThreadPoolExecutor
@@ -501,12 +546,12 @@ def main():
                          "frac": round(alg_bytes / (k_rate_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5), "traffic": traffic,
                          "peak_measured": round(peak_measured, 1) if peak_measured else None,
                          "frac_of_measured": round(alg_bytes / (k_rate_ms * 1e-3) / 1e9 / peak_measured, 5) if peak_measured else None,
-                         "frac_alone_of_measured": round(alg_bytes / k_solo / 1e6 / peak_measured, 5) if peak_measured else None,
+                         "frac_alone_of_measured": round(alg_bytes / k_solo / 1e6 / peak_measured, 5) if peak_measured and k_solo else None,
                          "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": round(k_rate_ms, 5),
                          "kernel_ms_event_span": round(k_ms, 5),
-                         "kernel_ms_alone": round(k_solo, 5),
-                         "frac_alone": round(alg_bytes / k_solo / 1e6 / HBM_PEAK_GBS, 5),
-                         "fast_kernel_ms_alone": round(float(np.mean(solo_fast)), 5),
+                         "kernel_ms_alone": round(k_solo, 5) if k_solo else None,
+                         "frac_alone": round(alg_bytes / k_solo / 1e6 / HBM_PEAK_GBS, 5) if k_solo else None,
+                         "fast_kernel_ms_alone": round(float(np.mean(solo_fast)), 5) if solo_fast else None,
                          "note": ("kernel_ms / achieved / frac: the timed region deals its steps over %d HIP streams, so the scan passes of "
                                   "consecutive steps overlap (the next one starts on the CUs the last blocks of this one have left) and "
                                   "the HIP-event span of one pass (kernel_ms_event_span) covers time it shares with its neighbours; the "
@@ -521,7 +566,8 @@ def main():
                                     "fast_kernel_ms_alone: the first kernel of the pass alone (k_fast for variant 4). " % cu_share)
                                  + "peak_measured: a 1 GiB device-to-device copy on this box (read + written bytes per second), frac_of_measured / "
                                    "frac_alone_of_measured: the same two fractions against it.  traffic: HBM bytes per launch from the rocprofv3 "
-                                   "counter passes committed under profiles/ (a constant of the profile, not measured in this run: counters need the profiler)"},
+                                   "counter passes committed under profiles/ (a constant of the profile, not measured in this run: counters need the profiler).  "
+                                   "The *_alone and *_measured figures take runs of their own and are null without --full."},
             "cpu_baseline": cpu,
             "e2e": e2e,
             "extra": extra,
