@@ -22,6 +22,11 @@
 //   * results are stored in the tile they belong to (no one-tile deferral, no packed `pending' registers)
 // Reads it does not take (other CIGARs, QUAL '*', more than F5_MAXLEN bases, rows that do not fit the staging buffer)
 // go on the block's list for the general pass, exactly as in variant 4.
+//
+// The tile loop (f5_tiles) is shared with k_fast7 (amp_fast7.hpp).  What a tile holds comes from a TILE SOURCE: which reads
+// (and the ticket pipeline that hands tiles to the waves), how their rows are staged, which pieces a lane owns, and how the
+// next tile's bases are pulled into L2.  k_fast5's source, F5Run below, cuts tiles of 64 consecutive reads and stages one
+// contiguous run; amp_fast7.hpp's cuts them from lists binned by read length and gathers rows.
 #pragma once
 
 #include "amp_fast.hpp"
@@ -30,10 +35,17 @@
 namespace amp {
 
 #ifndef AMP_F5_ADD64
-#define AMP_F5_ADD64 1      // 64-bit counter adds where a build's replica count allows them (the eight-wave build)
+#define AMP_F5_ADD64 1      // 64-bit counter adds where a build's replica count allows them (k_fast5's eight-wave build, k_fast7)
 #endif
 #ifndef AMP_F5_ABL
 #define AMP_F5_ABL 0      // development builds: parts of the kernel switched off to count the rest's instructions (results are wrong on purpose)
+#endif
+// development builds (-DAMP_F7_STAMPS): shader cycles a wave spends in the two waits of a turn, in the piece loops and in all of its
+// turns, summed over the waves into ctr[8 ..], turns into ctr[6] (tools/time_config5.py prints them)
+#ifdef AMP_F7_STAMPS
+#define F5_T(k) do { const unsigned long long f5_n = __builtin_amdgcn_s_memtime(); f5_t[k] += f5_n - f5_prev; f5_prev = f5_n; } while (0)
+#else
+#define F5_T(k) do { } while (0)
 #endif
 constexpr int F5_NP = 20;                 // 16-base pieces of the longest read taken
 constexpr int F5_MAXLEN = 304;            // F5_NP pieces cover it from 8 bases before its start
@@ -69,9 +81,53 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_readlane((int)t, 63);
 }
 
-template <int W, int F5_WAVES, int F5_QRUN, int F5_REP, int F5_PW>
-__global__ void __launch_bounds__(F5_WAVES * 64, 2)
-k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_ARGS)
+// minimum over the lanes of the wave (DPP row shifts and row broadcasts, no LDS traffic); the result is uniform
+__device__ __forceinline__ int32_t wave_min_i32(int32_t x) {
+    int32_t t = x, u;
+    const int32_t big = 0x7FFFFFFF;
+    u = __builtin_amdgcn_update_dpp(big, t, 0x111, 0xF, 0xF, false); t = u < t ? u : t;      // row_shr:1
+    u = __builtin_amdgcn_update_dpp(big, t, 0x112, 0xF, 0xF, false); t = u < t ? u : t;      // row_shr:2
+    u = __builtin_amdgcn_update_dpp(big, t, 0x114, 0xF, 0xF, false); t = u < t ? u : t;      // row_shr:4
+    u = __builtin_amdgcn_update_dpp(big, t, 0x118, 0xF, 0xF, false); t = u < t ? u : t;      // row_shr:8
+    u = __builtin_amdgcn_update_dpp(big, t, 0x142, 0xA, 0xF, false); t = u < t ? u : t;      // row_bcast:15 into rows 1 and 3
+    u = __builtin_amdgcn_update_dpp(big, t, 0x143, 0xC, 0xF, false); t = u < t ? u : t;      // row_bcast:31 into rows 2 and 3
+    return __builtin_amdgcn_readlane(t, 63);
+}
+
+// ---- what the tile loop and a tile source share --------------------------------------------------------------------------
+struct F5Hdr { int32_t pos, tlen; uint32_t lseq, flag, c0, c1, o8; };      // a lane's header words as loaded
+// ... and as kept: lf = l_seq (saturated at 0xFFFF) | paired << 16 | reverse << 17 | the template-length test of A:452 << 18 |
+// number of CIGAR ops (saturated at 7) << 19 | lane holds a read of the block << 22; idx: the read, where the source keeps it
+struct F5HdrP { int32_t pos; uint32_t lf, c0, o8, idx;
+    __device__ uint32_t lseq() const { return lf & 0xFFFFu; }
+    __device__ uint32_t nops() const { return (lf >> 19) & 7u; }
+    __device__ uint32_t flag() const { return ((lf >> 16) & 1u) | (((lf >> 17) & 1u) << 4); }
+    __device__ bool isize_flag() const { return (lf >> 18) & 1u; }
+    __device__ bool valid() const { return (lf >> 22) & 1u; } };
+// the block and the lane, as a source sees them
+struct F5Blk { amp_dev_reads rd; int64_t rb, re; int wave, lane; int32_t rpb; };
+
+// The tile loop.  Src, the tile source, provides
+//   WAVES, QCAP, SCAP      waves of the block; bytes of a wave's quality / packed-base staging buffer
+//   SLOTS, AHEAD           piece slots of a lane; slots whose packed bases are read together ahead of their adds
+//   SORTED                 a tile's reads are in the order of the batch (its first lane has its least position)
+//   Geo                    a tile's geometry as the lane sees it: np pieces from piece pbase() of its read, quality row at
+//                          `row', packed-base row at srow(); mine(): the lane stores the read's results; pair(): (uniform) two
+//                          lanes per read, merged by DPP; past(): a piece number outside every range of the lane
+//   clear, prologue        its LDS words zeroed (thread 0), the block's tiles found (after the block's window is cleared)
+//   start, take, next_hdr, rotate, n_tb, tk0, tk1, kR
+//                          the ticket pipeline: a tile's ticket; kR: the key of the tile whose header is loading
+//   load_hdr, valid, idx, index   a lane's header by key; the read it holds
+//   geometry, stage, prefetch, touch   a tile's geometry; LDS-DMA of its rows; L2 prefetch of its bases; registers of loads
+//                          of its own that the wait at the top of the loop has to cover
+// (F_ARGS by name: a kernel hands its arguments on)
+#define F_ARGS_FWD a_pos, a_min_quality, a_flag, a_window, a_tlen, a_do_trim, a_lseq, a_do_count, a_cig_off32, a_ref_len, a_cig, a_max_primer_len, \
+    a_seq_off8, reads_per_block, a_seq, a_epoch, a_qual, pad1, a_min_start, pad2, a_max_end, pad3, a_new_pos, pad4, a_new_ncig, pad5, a_new_cig, pad6, \
+    a_o_ref_len, pad7, a_trim_flags, pad8, a_status, pad9, counts, pad10, a_ev, pad11, a_ctr, pad12, a_ins_at, pad13, glist, pad14, gcnt, pad15, \
+    a_n_reads, pad17, read_base, pad18, a_ev_cap
+template <int W, int F5_REP, int F5_PW, class Src>
+__device__ __forceinline__ void f5_tiles(Src ts, F_ARGS) {
+    constexpr int F5_WAVES = Src::WAVES, F5_SLOTS = Src::SLOTS, F5_AHEAD = Src::AHEAD;
     const KParams P{a_min_quality, a_window, a_do_trim, a_do_count, a_ref_len, a_max_primer_len, a_min_start, a_max_end, (uint32_t)a_epoch};
     const amp_dev_reads rd{a_n_reads, a_pos, a_flag, a_tlen, a_lseq, a_cig_off32, a_cig, a_seq_off8, a_seq, a_qual, 0, 0};
     const DevOut out{a_new_pos, a_new_ncig, a_new_cig, a_o_ref_len, a_trim_flags, a_status};
@@ -82,7 +138,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
     constexpr bool F5_ADD64 = AMP_F5_ADD64 && F5_REP % 2 == 0 && F5_REPW % 2 == 1;
     constexpr int F5_NREP = F5_ADD64 ? F5_REP / 2 : F5_REP;               // replicas a lane can be sent to
     constexpr int F5_FLUSH = 255 / (((16 + F5_NREP - 1) / F5_NREP) * 4);      // (lanes go to replicas in groups of four: so many of them add into one array at most)
-    constexpr int F5_QB = F5_PAD + F5_QRUN + 2 * F5_PAD, F5_SB = F5_PAD + F5_QRUN / 2 + F5_PAD;      // (a row's last piece is read with the 8 bytes behind it: up to 23 bytes past the run)
+    constexpr int F5_QB = F5_PAD + Src::QCAP + 2 * F5_PAD, F5_SB = F5_PAD + Src::SCAP + F5_PAD;      // (a row's last piece is read with the 8 bytes behind it: up to 23 bytes past the run)
     __shared__ uint4 s_q[F5_WAVES][F5_QB / 16];                       // per wave: the tile's quality bytes
     __shared__ uint4 s_s[F5_WAVES][F5_SB / 16];                       // per wave: the tile's packed bases
     __shared__ __attribute__((aligned(8))) uint32_t s_pwin[F5_WAVES][F5_REP * F5_REPW];           // per wave: packed counters, byte c of a word = base c (A C G T)
@@ -100,7 +156,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
     // every nibble of the base staging buffer starts as a valid code (the bytes in front of a run are read by the
     // lanes whose pieces start 8 bases early, and are never written again)
     for (int i = lane; i < F5_SB / 4; i += 64) ((lds_u32 *)s_s[wave])[i] = 0x11111111u;
-    if (tid == 0) { s_ticket = 0; s_gcur = 0; }
+    if (tid == 0) { s_ticket = 0; s_gcur = 0; ts.clear(); }
     if (tid == 0 && blockIdx.x == 0) { eb.ctr[26] = 0ull; eb.ctr[27] = 0ull; eb.ctr[28] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
     int32_t bw_base = rb < n ? rd.pos[rb] : 0;
     bw_base = (bw_base < 16 ? 0 : bw_base - 16) & ~15;
@@ -111,7 +167,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
     const uint32_t thr = mqc * (uint32_t)W;
     const uint32_t mqb = (uint32_t)mq * 0x01010101u;             // mq <= 128 (the host sends other runs to the general kernel)
     const uint32_t G = (uint32_t)P.ref_len;
-    const uint32_t n_tb = re > rb ? (uint32_t)((re - rb + 63) / 64) : 0u;
+    ts.prologue(F5Blk{rd, rb, re, wave, lane, reads_per_block}, glist, (lds_u32 *)&s_gcur);
     auto take_ticket = [&]() {
         uint32_t t = 0;
         if (lane == 0) t = __hip_atomic_fetch_add((lds_u32 *)&s_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -167,32 +223,14 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         if ((uint32_t)lane < ev_left && (long long)(ev_base + (unsigned)lane) < eb.cap) ev_list[ev_base + (unsigned)lane] = amp_ins_event{-1, 0u, 0, 0};
     };
 
-    struct Hdr { int32_t pos, tlen; uint32_t lseq, flag, c0, c1, o8; };      // as loaded
-    // ... and as kept: lf = l_seq (saturated at 0xFFFF) | paired << 16 | reverse << 17 | the template-length test of A:452 << 18 |
-    // number of CIGAR ops (saturated at 7) << 19 | lane holds a read of the block << 22
-    struct HdrP { int32_t pos; uint32_t lf, c0, o8;
-        __device__ uint32_t lseq() const { return lf & 0xFFFFu; }
-        __device__ uint32_t nops() const { return (lf >> 19) & 7u; }
-        __device__ uint32_t flag() const { return ((lf >> 16) & 1u) | (((lf >> 17) & 1u) << 4); }
-        __device__ bool isize_flag() const { return (lf >> 18) & 1u; }
-        __device__ bool valid() const { return (lf >> 22) & 1u; } };
-    auto load_hdr = [&](int64_t t0) {
-        Hdr h{0, 0, 0u, 0u, 0u, 0u, 0u};
-        const int64_t i = t0 + lane;
-        if (i < re) {
-            h.pos = rd.pos[i]; h.flag = rd.flag[i]; h.tlen = rd.tlen[i]; h.lseq = rd.lseq[i];
-            h.c0 = rd.cig_off32[i]; h.c1 = rd.cig_off32[i + 1]; h.o8 = rd.seq_off8[i];
-        }
-        return h;
-    };
-    auto pack_hdr = [&](const Hdr &h, int64_t t0) {
+    auto pack_hdr = [&](const F5Hdr &h, const auto &key) {
         const uint32_t nn = h.c1 - h.c0, at = (uint32_t)(h.tlen < 0 ? -(int64_t)h.tlen : (int64_t)h.tlen);
         const bool isz = ((int64_t)at - P.max_primer_len) > (int64_t)h.lseq;                                  // A:452
-        return HdrP{h.pos, (h.lseq > 0xFFFFu ? 0xFFFFu : h.lseq) | ((h.flag & 1u) << 16) | (((h.flag >> 4) & 1u) << 17) | ((isz ? 1u : 0u) << 18) |
-                               ((nn > 7u ? 7u : nn) << 19) | ((t0 + lane < re ? 1u : 0u) << 22), h.c0, h.o8};
+        return F5HdrP{h.pos, (h.lseq > 0xFFFFu ? 0xFFFFu : h.lseq) | ((h.flag & 1u) << 16) | (((h.flag >> 4) & 1u) << 17) | ((isz ? 1u : 0u) << 18) |
+                                 ((nn > 7u ? 7u : nn) << 19) | ((ts.valid(key) ? 1u : 0u) << 22), h.c0, h.o8, ts.idx(key)};
     };
     struct Cg { uint32_t w[5]; };
-    auto load_cig = [&](const HdrP &h) {
+    auto load_cig = [&](const F5HdrP &h) {
         Cg c{{0u, 0u, 0u, 0u, 0u}};
         const uint32_t nops = h.nops();
         if (nops >= 1u && nops <= 5u) {
@@ -201,30 +239,8 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         }
         return c;
     };
-    // the tile's run: the bytes of its leading reads that fit the staging buffer (64 reads of up to 152 bases always do)
-    struct Geo { uint32_t np, row, Tq, m0; int ntake; bool solo, fastq; };
-    auto geometry = [&](const HdrP &h) {
-        Geo g;
-        const bool valid = h.valid();
-        const uint32_t hl = h.lseq();
-        const bool shortq = valid && hl >= 1u && hl <= (uint32_t)F5_MAXLEN;
-        g.np = shortq ? (hl + phi_lane + 15u) >> 4 : 1u;
-        g.m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)h.o8);
-        g.row = (h.o8 - g.m0) * 8u;
-        const uint32_t nch = (hl + 7u) >> 3;
-        // a row is read as pieces of 16 bytes plus the 8 bytes behind them: up to 24 bytes past the read's own padded bytes
-        const bool fits = valid && h.o8 >= g.m0 && (h.o8 - g.m0) <= (uint32_t)(F5_QRUN / 8) && g.row + 8u * nch <= (uint32_t)F5_QRUN;
-        const unsigned long long fitmask = __ballot(fits);
-        g.ntake = fitmask == ~0ull ? 64 : __builtin_ctzll(~fitmask);
-        g.solo = g.ntake == 0;
-        if (g.solo) g.ntake = 1;
-        g.Tq = g.solo ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)(g.row + 8u * nch), g.ntake - 1);
-        g.fastq = lane < g.ntake && !g.solo && shortq;
-        if (!g.fastq) { g.row = 0u; g.np = 1u; }
-        return g;
-    };
     struct Shape { Bf s; bool ok; int32_t refspan; };
-    auto shape_of = [&](const HdrP &h, const Cg &c, bool fastq) {
+    auto shape_of = [&](const F5HdrP &h, const Cg &c, bool fastq) {
         Shape r;
         bool ok;
         r.s = bf_from_words5((int)h.nops(), c.w[0], c.w[1], c.w[2], c.w[3], c.w[4], (int32_t)h.lseq(), F_MAXINS, F_MAXDEL, ok);
@@ -233,21 +249,11 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         return r;
     };
     struct Tabs { int32_t L, R; };
-    auto load_tabs = [&](const HdrP &h, const Shape &sh) {
+    auto load_tabs = [&](const F5HdrP &h, const Shape &sh) {
         Tabs t{-1, -1};
         const bool in_ref = ((uint32_t)h.pos < G) & ((uint32_t)(h.pos + sh.refspan - 1) < G);
         if (sh.ok & (P.do_trim != 0) & in_ref) { t.L = P.max_end[h.pos]; t.R = P.min_start[h.pos + sh.refspan - 1]; }
         return t;
-    };
-    // LDS-DMA of a run: lane l moves bytes [1024 s + 16 l, + 16) to the same offset of the staging buffer; lanes past the
-    // run re-read its end, lanes past the buffer do nothing
-    auto issue_run = [&](const uint8_t *run, uint32_t nbytes, lds_u8 *stage, int cap) {
-        const uint32_t last = nbytes ? (nbytes - 1u) & ~15u : 0u;
-#pragma unroll
-        for (int sl = 0; sl < (cap + 1023) / 1024; ++sl) {
-            uint32_t off = (uint32_t)(sl * 1024 + lane * 16);
-            if (sl * 1024 + 1024 <= cap || (int)off < cap) dma16(run + (off < last ? off : last), stage + sl * 1024);
-        }
     };
 
     uint32_t pw_lim = 0;
@@ -257,51 +263,58 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         while (__builtin_amdgcn_s_memtime() < t_end) __builtin_amdgcn_s_sleep(8);
     }
     // ---- prologue: three tiles' headers; CIGAR words of the first two; the first tile's qualities and table entries -----------
-    uint32_t tk0 = take_ticket(), tk1 = take_ticket(), tk2 = take_ticket();
-    int64_t i0 = rb + 64 * (int64_t)tk0, i1 = rb + 64 * (int64_t)tk1, i2 = rb + 64 * (int64_t)tk2;
-    HdrP h0, h1;
-    Hdr hR;
+    ts.start(take_ticket);
+    F5HdrP h0, h1;
+    F5Hdr hR;
     {
-        const Hdr a = load_hdr(i0), b = load_hdr(i1);
-        hR = load_hdr(i2);
-        h0 = pack_hdr(a, i0); h1 = pack_hdr(b, i1);
+        const F5Hdr a = ts.load_hdr(ts.k0), b = ts.load_hdr(ts.k1);
+        hR = ts.load_hdr(ts.kR);
+        h0 = pack_hdr(a, ts.k0); h1 = pack_hdr(b, ts.k1);
     }
     Cg cN = load_cig(h1);
-    Geo g0 = geometry(h0);
+    typename Src::Geo g0 = ts.geometry(h0, ts.tk0, phi_lane);
     Shape sh0;
     {
         const Cg c = load_cig(h0);
-        issue_run(rd.qual + (int64_t)g0.m0 * 8, g0.Tq, qst, F5_QRUN);
+        ts.stage(h0, g0, false, qst);
         sh0 = shape_of(h0, c, g0.fastq);
     }
     Tabs tb0 = load_tabs(h0, sh0);
     uint32_t pfA = 0u, pfB = 0u;                   // (L2 prefetch of the next tile's bases: see below)
-    while (tk0 < n_tb) {
+#ifdef AMP_F7_STAMPS
+    unsigned long long f5_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, f5_prev = __builtin_amdgcn_s_memtime();
+    uint32_t f5_turns = 0;
+#endif
+    while (ts.tk0 < ts.n_tb) {
         // ---- everything issued a phase or more ago has arrived: this tile's qualities and table entries, the next tile's
         // CIGAR words, the header of the tile behind it -------------------------------------------------------------------
+        F5_T(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        F5_T(1);
         asm volatile("" : : "v"(pfA), "v"(pfB));
         // (every register a load of the last turn -- or of the prologue -- wrote is touched HERE, where nothing is in flight: left to its
         // own devices the compiler waits at the first use, behind the issue of this tile's bases, and the wave sits out their latency)
         asm volatile("" : : "v"(tb0.L), "v"(tb0.R), "v"(cN.w[0]), "v"(cN.w[1]), "v"(cN.w[2]), "v"(cN.w[3]), "v"(cN.w[4]));
         asm volatile("" : : "v"(hR.pos), "v"(hR.tlen), "v"(hR.lseq), "v"(hR.flag), "v"(hR.c0), "v"(hR.c1), "v"(hR.o8));
-        const HdrP h = h0;
-        const Geo g = g0;
+        ts.touch();
+        const F5HdrP h = h0;
+        const typename Src::Geo g = g0;
         const Shape shp = sh0;
         const Tabs tA = tb0;
-        const Geo g1 = geometry(h1);
+        const typename Src::Geo g1 = ts.geometry(h1, ts.tk1, phi_lane);
         const Shape sh1 = shape_of(h1, cN, g1.fastq);
-        const HdrP h2 = pack_hdr(hR, i2);
+        const F5HdrP h2 = pack_hdr(hR, ts.kR);
         // this tile's packed bases start moving (their buffer was in use until the end of the last tile)
-        issue_run(rd.seq + (int64_t)g.m0 * 4, g.Tq >> 1, sst, F5_QRUN / 2);
-        const int64_t i = i0 + lane;
+        ts.stage(h, g, true, sst);
+        const int64_t i = ts.index(h);
+        const bool pair = g.pair(), mine = g.mine();              // (pair: uniform; mine: the lane that stores the read's results)
         const int32_t pos = h.pos;
         const uint32_t lseq = h.lseq(), flag = h.flag(), c0 = h.c0, o8 = h.o8;
         const uint32_t np = g.np, phi = g.fastq ? phi_lane : 0u;
         const bool fastq = g.fastq;
         // ---- the wave's packed window: fold and re-anchor when the tile has moved on, or before a byte could overflow
         {
-            const int32_t first_pos = __builtin_amdgcn_readfirstlane(pos);
+            const int32_t first_pos = Src::SORTED ? __builtin_amdgcn_readfirstlane(pos) : wave_min_i32(fastq ? pos : 0x7FFFFFFF);
             const int32_t want = (first_pos < 16 ? 0 : first_pos - 16) & ~15;
             if (pw_tiles >= F5_FLUSH || want < pw_base || want - pw_base >= 64) {
                 if (pw_tiles) fold();
@@ -331,34 +344,40 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         bf_quality_window(s, (int32_t)lseq, lo, qlen);
         lo = scan ? lo + (int32_t)phi : 0; qlen = scan ? qlen : 0;
         const int32_t hi = lo + qlen;
-        // ---- pass over the qualities: slot k of the lane is piece (k + rot) mod np of its read.  Per piece: 16 failing-window
-        // bits (bit b: the W-byte window starting at base b of the piece sums to less than W * min_quality), of which the
-        // first / last inside [lo, hi - W] give the first failing window start (forward) / last failing window end
+        // ---- pass over the qualities: slot k of the lane is piece pbase + (k + rot) mod np of its read.  Per piece: 16
+        // failing-window bits (bit b: the W-byte window starting at base b of the piece sums to less than W * min_quality), of
+        // which the first / last inside [lo, hi - W] give the first failing window start (forward) / last failing window end
         // (reverse); and 16 good-quality bits, kept as ok[k] for the counting phase ------------------------------------------
-        const uint32_t rot = (uint32_t)lane % np;
+        F5_T(4);
+        const uint32_t rot = ((uint32_t)lane >> (pair ? 1 : 0)) % np;
+        const uint32_t pbase = g.pbase();
         const uint32_t live = wave_or_u32((1u << np) - 1u);                    // bit k: some lane of the tile has a piece in slot k
         const int32_t lrow = (int32_t)g.row - (int32_t)phi;                    // >= -8: the pad in front of the run
         const lds_u8 *const lq = qst + g.row;                                  // the read's qualities in the staging buffer
-        uint32_t fo[F5_NP];
+        uint32_t fo[F5_SLOTS];
         int32_t ffmin = 0x7FFFFFFF, lemax = -1;
         // (the 24 bytes of slot k + 1 are asked for before slot k is worked on: a slot's LDS round trip lies under its predecessor's work)
         auto piece_bytes = [&](int k, amp_u32x2 &a, amp_u32x2 &b, amp_u32x2 &c) {
             uint32_t p = (uint32_t)k + rot;
             p = p >= np ? p - np : p;
-            const lds_u8 *src = qst + lrow + (int32_t)(((uint32_t)k < np ? p : np - 1u) * 16u);
+            const lds_u8 *src = qst + lrow + (int32_t)((pbase + ((uint32_t)k < np ? p : np - 1u)) * 16u);
             a = *(const lds_u32x2 *)src; b = *(const lds_u32x2 *)(src + 8); c = *(const lds_u32x2 *)(src + 16);
+        };
+        // the piece of slot k (past(): the lane has no piece there)
+        auto piece_of = [&](int k) -> uint32_t {
+            uint32_t p = (uint32_t)k + rot;
+            p = p >= np ? p - np : p;
+            return (uint32_t)k < np ? pbase + p : g.past();
         };
         amp_u32x2 an, bn, cn;
         piece_bytes(0, an, bn, cn);
 #pragma unroll
-        for (int k = 0; k < F5_NP; ++k) {
+        for (int k = 0; k < F5_SLOTS; ++k) {
             fo[k] = 0u;
             if (!((live >> k) & 1u) || (AMP_F5_ABL & 1)) continue;             // (uniform)
             const amp_u32x2 a = an, b = bn, c = cn;
-            if (k + 1 < F5_NP) piece_bytes(k + 1, an, bn, cn);
-            uint32_t p = (uint32_t)k + rot;
-            p = p >= np ? p - np : p;
-            p = (uint32_t)k < np ? p : np;
+            if (k + 1 < F5_SLOTS) piece_bytes(k + 1, an, bn, cn);
+            const uint32_t p = piece_of(k);
             const uint4 q = make_uint4(a.x, a.y, b.x, b.y);
             fo[k] = ok_bits16(q, mqb);
             if (P.do_trim) {
@@ -369,6 +388,11 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
                 lemax = ((fail != 0u) & (e1 > lemax)) ? e1 : lemax;
             }
         }
+        if (pair) {      // (uniform) the two lanes of a read have looked at different pieces
+            const int32_t fo_ = __builtin_amdgcn_update_dpp(0, ffmin, 0xB1, 0xF, 0xF, true), lo_ = __builtin_amdgcn_update_dpp(0, lemax, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]
+            ffmin = fo_ < ffmin ? fo_ : ffmin; lemax = lo_ > lemax ? lo_ : lemax;
+        }
+        F5_T(5);
         const uint32_t fb = lq[0];                                             // 0xFF = QUAL '*'
         // ---- quality clip (A:589-686) --------------------------------------------------------------------------------
         int32_t iq = rev ? 0 : qlen;
@@ -398,7 +422,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         const bool stored = shaped & !nogo;
         const bool okres = stored & (terr == 0);
         const int32_t reflen = okres ? s.ref_len() : 0;
-        n_err += (stored & (terr != 0)) ? 1u : 0u;
+        n_err += (stored & mine & (terr != 0)) ? 1u : 0u;
         const bool counted = okres & (P.do_count != 0);
         // ---- what counting needs of the qualities besides the bits: the inserted bases' (A:730-748), and the good bits of
         // GROUP B = the 16 bases from the 8-aligned start of the second segment, for the piece that holds bases of both
@@ -417,12 +441,15 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
             okB = ok_bits16(make_uint4(a.x, a.y, b.x, b.y), mqb);
         }
         // ---- the tile's bases have arrived; the quality buffer is free: results out, the next tile's loads go out ------
+        F5_T(2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        F5_T(3);
         {
             // [S a][op m1][I|D k][op m2][S c], absent parts left out
             const uint32_t part[5] = {((uint32_t)s.a << 4) | OP_S, ((uint32_t)s.m1 << 4) | s.op, ((uint32_t)s.k << 4) | (s.kind == 1 ? OP_I : OP_D),
                                       ((uint32_t)s.m2 << 4) | s.op, ((uint32_t)s.c << 4) | OP_S};
-            const bool has[5] = {bool(okres & (s.a > 0)), bool(okres & (s.m1 > 0)), bool(okres & (s.kind != 0)), bool(okres & (s.kind != 0) & (s.m2 > 0)), bool(okres & (s.c > 0))};
+            const bool okm_ = okres & mine;
+            const bool has[5] = {bool(okm_ & (s.a > 0)), bool(okm_ & (s.m1 > 0)), bool(okm_ & (s.kind != 0)), bool(okm_ & (s.kind != 0) & (s.m2 > 0)), bool(okm_ & (s.c > 0))};
             uint32_t *home = out.new_cig + ((size_t)c0 + 3 * (size_t)i);
             uint32_t nc = 0;
 #pragma unroll
@@ -430,7 +457,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
                 if (has[t]) home[nc] = part[t];
                 nc += has[t] ? 1u : 0u;
             }
-            if (stored) {
+            if (stored & mine) {
                 if (out.new_pos) out.new_pos[i] = tpos;
                 if (out.new_ncig) out.new_ncig[i] = nc;
                 if (out.ref_len) out.ref_len[i] = reflen;
@@ -438,28 +465,20 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
                 if (out.status) out.status[i] = (uint8_t)terr;
             }
         }
-        const uint32_t tk3 = take_ticket();
-        const int64_t i3 = rb + 64 * (int64_t)tk3;
-        issue_run(rd.qual + (int64_t)g1.m0 * 8, g1.Tq, qst, F5_QRUN);
+        ts.take(take_ticket);
+        ts.stage(h1, g1, false, qst);
         tb0 = load_tabs(h1, sh1);
         cN = load_cig(h2);
-        hR = load_hdr(i3);
-        {
-            // the next tile's packed bases are pulled into L2 now (one dword of every 128-byte line; plain loads whose values
-            // are only "used" behind the wait at the top of the loop): their LDS-DMA can only be issued when this tile's bases
-            // have been counted, a third of a tile before they are needed
-            const uint32_t nb = g1.Tq >> 1;
-            const uint32_t off = (uint32_t)lane * 128u;
-            const uint8_t *sb = rd.seq + (int64_t)g1.m0 * 4;
-            pfA = *(const uint32_t *)(sb + (off < nb ? off : 0u));
-            if (F5_QRUN / 2 > 8192) pfB = *(const uint32_t *)(sb + (off + 8192u < nb ? off + 8192u : 0u));
-        }
+        hR = ts.next_hdr();
+        // the next tile's packed bases are pulled into L2 now (plain loads whose values are only "used" behind the wait at the top of
+        // the loop): their LDS-DMA can only be issued when this tile's bases have been counted, a third of a tile before they are needed
+        ts.prefetch(h1, g1, pfA, pfB);
         // pad nibbles of the staged rows (a row is padded to 8 bases) become a valid code: the test for codes outside
         // A C G T looks at whole pieces
         {
-            const uint32_t e = fastq ? lseq & 7u : 0u;                        // bases of the row's last group of 8 (0: the group is full)
+            const uint32_t e = (fastq & mine) ? lseq & 7u : 0u;                // bases of the row's last group of 8 (0: the group is full)
             if (e) {
-                lds_u32 *w = (lds_u32 *)(sst + (g.row >> 1) + 4u * (lseq >> 3));
+                lds_u32 *w = (lds_u32 *)(sst + g.srow() + 4u * (lseq >> 3));
                 // nibble i of the group sits in byte i >> 1, high nibble first
                 const uint32_t x = *w, xs = ((x & 0x0F0F0F0Fu) << 4) | ((x >> 4) & 0x0F0F0F0Fu);      // nibble i at bit 4 i
                 const uint32_t keep = (1u << (4u * e)) - 1u;
@@ -476,7 +495,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         const int32_t pos2 = tpos + s.m1 + s.kD();                                 // reference position of the second segment
         bool bad_extra = false;
         // deletion: '-' at each of its positions (A:714-715), through the block's window
-        if (two & (s.kind == 2) & !(AMP_F5_ABL & 4)) {
+        if (two & mine & (s.kind == 2) & !(AMP_F5_ABL & 4)) {
             for (int32_t j = 0; j < s.k; ++j) {
                 const int32_t r = tpos + s.m1 + j;
                 const uint32_t d = (uint32_t)(r - bw_base);
@@ -487,7 +506,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         }
         // insertion (A:730-748): one event per maximal run of good-quality inserted bases
         {
-            uint32_t runs = (AMP_F5_ABL & 4) ? 0u : good & ~(good << 1);                              // first base of every run
+            uint32_t runs = (AMP_F5_ABL & 4) || !mine ? 0u : good & ~(good << 1);                     // first base of every run
             const unsigned long long em = __ballot(runs != 0u);
             if (em) {
                 const uint32_t total = (uint32_t)__popcll(em);
@@ -529,16 +548,32 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
                 ev_base += total; ev_left -= total;
             }
         }
+        F5_T(6);
         uint32_t redo = 0;                        // pieces (slots) the careful loop has to do; bit F5_NP = group B
         // group B: the part of the second segment that shares a piece with the first
         const int32_t jstar = (qb1 - 1) & ~15;                       // the piece that holds the first segment's last base
-        const bool has_b = two & (jstar + 16 > qa2) & (qb2 > qa2);
+        const bool has_b = two & mine & (jstar + 16 > qa2) & (qb2 > qa2);
         const int32_t xbe = qb2 < jstar + 16 ? qb2 : jstar + 16;
         const int32_t jb = g_b + (int32_t)phi;
         // The bases go into the wave's packed window, F_PW positions from pw_base; a tile whose reads lie further apart (the
         // step from one pile of reads to the next) is counted in PASSES: fold, re-anchor at the first lane left.
         const int32_t end_pos = two ? pos2 + s.m2 : tpos + s.m1;                   // one past the last counted position
-        const lds_u8 *const lsrow = sst + (int32_t)(g.row >> 1) - (int32_t)(phi >> 1);
+        const lds_u8 *const lsrow = sst + (int32_t)g.srow() - (int32_t)(phi >> 1);
+        // The packed bases of F5_AHEAD slots are read before their adds: LDS operations of a wave complete in order, so a read
+        // behind the sixteen adds of a piece waits for every one of them (the compiler cannot see the adds and waits with
+        // lgkmcnt(0)); read piece by piece, the counting loop drained the LDS queue once per slot.  When they are all of the
+        // lane's slots (ten at most: two lanes per long read), they are read once, before the first pass.
+        uint2 sqv[F5_AHEAD];
+        auto read_ahead = [&](int c) {
+#pragma unroll
+            for (int j = 0; j < F5_AHEAD; ++j) {
+                uint32_t p = (uint32_t)(c + j) + rot;
+                p = p >= np ? p - np : p;
+                const lds_u8 *sp = lsrow + (pbase + ((uint32_t)(c + j) < np ? p : np - 1u)) * 8u;
+                sqv[j] = make_uint2(*(const lds_u32 *)sp, *(const lds_u32 *)(sp + 4));
+            }
+        };
+        if (F5_AHEAD == F5_SLOTS) read_ahead(0);
         bool todo = counted;
         for (bool first_pass = true;; first_pass = false) {
             const unsigned long long tm = __ballot(todo);
@@ -556,32 +591,22 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
             const int32_t a1 = now ? qa1 : 0, b1 = now ? qb1 : 0, a2 = now ? qa2 : 0, b2 = now ? qb2 : 0;
             const int32_t dbase1 = tpos - pw_base - qa1, dbase2 = pos2 - pw_base - qa2;
             if (__ballot(has_b & now)) {
-                const lds_u8 *sp = sst + (g.row >> 1) + (uint32_t)(g_b >> 1);
+                const lds_u8 *sp = sst + g.srow() + (uint32_t)(g_b >> 1);
                 const uint2 sq = make_uint2(*(const lds_u32 *)sp, *(const lds_u32 *)(sp + 4));
                 const uint32_t mB = (has_b & now) ? okB & range_bits16(qa2 - jb, xbe - jb) : 0u;
                 redo |= count5(sq, mB, dbase2 + jb, lim16) << F5_NP;
             }
-            // The packed bases of FIVE pieces are read before their adds: LDS operations of a wave complete in order, so a read behind
-            // the sixteen adds of a piece waits for every one of them (the compiler cannot see the adds and waits with lgkmcnt(0)); read
-            // piece by piece the loop drained the LDS queue once per slot (amp_fast7.hpp, whose lanes have ten pieces at most, reads all)
 #pragma unroll
-            for (int c = 0; c < F5_NP; c += 5) {
-                if (!((live >> c) & 1u) || (AMP_F5_ABL & 2)) continue;      // (uniform; the live slots are the low ones)
-                uint2 sqv[5];
-#pragma unroll
-                for (int j = 0; j < 5; ++j) {
-                    uint32_t p = (uint32_t)(c + j) + rot;
-                    p = p >= np ? p - np : p;
-                    const lds_u8 *sp = lsrow + ((uint32_t)(c + j) < np ? p : np - 1u) * 8u;
-                    sqv[j] = make_uint2(*(const lds_u32 *)sp, *(const lds_u32 *)(sp + 4));
+            for (int c = 0; c < F5_SLOTS; c += F5_AHEAD) {
+                if (F5_AHEAD < F5_SLOTS) {
+                    if (!((live >> c) & 1u) || (AMP_F5_ABL & 2)) continue;      // (uniform; the live slots are the low ones)
+                    read_ahead(c);
                 }
 #pragma unroll
-                for (int j = 0; j < 5; ++j) {
+                for (int j = 0; j < F5_AHEAD; ++j) {
                     const int k = c + j;
-                    if (!((live >> k) & 1u)) continue;
-                    uint32_t p = (uint32_t)k + rot;
-                    p = p >= np ? p - np : p;
-                    p = (uint32_t)k < np ? p : np;
+                    if (!((live >> k) & 1u) || (AMP_F5_ABL & 2)) continue;
+                    const uint32_t p = piece_of(k);
                     const int32_t j0 = (int32_t)(p * 16u);
                     const bool second = j0 >= qb1;                              // a piece behind the first segment belongs to the second
                     const uint32_t rng = range_bits16((second ? a2 : a1) - j0, (second ? b2 : b1) - j0);
@@ -590,6 +615,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
             }
             todo = todo & !now;
         }
+        F5_T(7);
         bool want_status = bad_extra;
         if (__ballot(redo != 0u)) {
             // careful loop (rare): bases of the flagged pieces one by one, straight from memory into the 32-bit counters
@@ -612,7 +638,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
                 for (int k = 0; k < F5_NP; ++k) {
                     if (!((redo >> k) & 1u)) continue;
                     uint32_t p = (uint32_t)k + rot;
-                    p = p >= np ? p - np : p;
+                    p = pbase + (p >= np ? p - np : p);
                     const int32_t j0 = (int32_t)(p * 16u) - (int32_t)phi;
                     const bool second = j0 + (int32_t)phi >= qb1;
                     const int32_t sa = second ? a2 : a1, sb_ = second ? b2 : b1;
@@ -623,8 +649,9 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         }
         // ---- hand-over to the general pass: the block's segment of the list -----------------------------------------------
         {
+            if (pair) want_status |= __builtin_amdgcn_update_dpp(0, (int)want_status, 0xB1, 0xF, 0xF, true) != 0;      // (either lane of the read)
             const bool status_only = !general & counted & want_status;        // a base could not be counted: exact status wanted
-            const bool has = general | status_only;
+            const bool has = (general | status_only) & mine;
             const unsigned long long m = __ballot(has);
             if (m) {
                 uint32_t base = 0;
@@ -635,11 +662,17 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
         }
         // ---- next tile ------------------------------------------------------------------------------------------------
         h0 = h1; h1 = h2; g0 = g1; sh0 = sh1;
-        i0 = i1; i1 = i2; i2 = i3; tk0 = tk1; tk1 = tk2; tk2 = tk3;
+        ts.rotate();
+#ifdef AMP_F7_STAMPS
+        ++f5_turns;
+#endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // (the loads issued for a tile that does not exist)
+#ifdef AMP_F7_STAMPS
+    if (lane == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&ctr[8 + k], f5_t[k]); atomicAdd(&ctr[6], (unsigned long long)f5_turns); }
+#endif
     pad_events();
-    if (pw_tiles && n_tb) fold();
+    if (pw_tiles && ts.n_tb) fold();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
     for (int i = tid; i < F_BPL * F_BW; i += F5_WAVES * 64) {
@@ -658,6 +691,97 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
     if (tid == 0) { gcnt[blockIdx.x] = s_gcur; if (s_gcur) eb.ctr[29] = (unsigned long long)P.epoch; }      // (every block writes the same value)
 }
 
+// k_fast5's tile source: 64 consecutive reads of the block a tile, a lane each; their rows are one contiguous run of the batch,
+// staged as far as the run fits the staging buffer (QRUN bytes of qualities)
+template <int WAVES_, int QRUN>
+struct F5Run {
+    static constexpr int WAVES = WAVES_, QCAP = QRUN, SCAP = QRUN / 2;
+    static constexpr int SLOTS = F5_NP, AHEAD = 5;
+    static constexpr bool SORTED = true;
+    // the tile's run: the bytes of its leading reads that fit the staging buffer (64 reads of up to 152 bases always do)
+    struct Geo { uint32_t np, row, Tq, m0; int ntake; bool solo, fastq;
+        __device__ uint32_t pbase() const { return 0u; }
+        __device__ uint32_t srow() const { return row >> 1; }
+        __device__ bool mine() const { return true; }
+        __device__ bool pair() const { return false; }
+        __device__ uint32_t past() const { return np; } };      // (np pieces cover the read)
+    F5Blk b;
+    uint32_t n_tb, tk0, tk1, tk2, tk3;
+    int64_t k0, k1, kR, k3;                   // the first reads of the current tile, of the next, of the one whose header is loading, of the one behind
+    __device__ void clear() const {}
+    __device__ void prologue(const F5Blk &blk, uint32_t *, lds_u32 *) {
+        b = blk;
+        n_tb = b.re > b.rb ? (uint32_t)((b.re - b.rb + 63) / 64) : 0u;
+    }
+    template <class T> __device__ void start(T ticket) {
+        tk0 = ticket(); tk1 = ticket(); tk2 = ticket();
+        k0 = b.rb + 64 * (int64_t)tk0; k1 = b.rb + 64 * (int64_t)tk1; kR = b.rb + 64 * (int64_t)tk2;
+    }
+    template <class T> __device__ void take(T ticket) { tk3 = ticket(); k3 = b.rb + 64 * (int64_t)tk3; }
+    __device__ F5Hdr next_hdr() const { return load_hdr(k3); }
+    __device__ void rotate() { k0 = k1; k1 = kR; kR = k3; tk0 = tk1; tk1 = tk2; tk2 = tk3; }
+    __device__ void touch() const {}
+    __device__ bool valid(int64_t t0) const { return t0 + b.lane < b.re; }
+    __device__ uint32_t idx(int64_t) const { return 0u; }
+    __device__ int64_t index(const F5HdrP &) const { return k0 + b.lane; }
+    __device__ F5Hdr load_hdr(int64_t t0) const {
+        F5Hdr h{0, 0, 0u, 0u, 0u, 0u, 0u};
+        const int64_t i = t0 + b.lane;
+        if (i < b.re) {
+            h.pos = b.rd.pos[i]; h.flag = b.rd.flag[i]; h.tlen = b.rd.tlen[i]; h.lseq = b.rd.lseq[i];
+            h.c0 = b.rd.cig_off32[i]; h.c1 = b.rd.cig_off32[i + 1]; h.o8 = b.rd.seq_off8[i];
+        }
+        return h;
+    }
+    __device__ Geo geometry(const F5HdrP &h, uint32_t, uint32_t phi_lane) const {
+        Geo g;
+        const bool valid = h.valid();
+        const uint32_t hl = h.lseq();
+        const bool shortq = valid && hl >= 1u && hl <= (uint32_t)F5_MAXLEN;
+        g.np = shortq ? (hl + phi_lane + 15u) >> 4 : 1u;
+        g.m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)h.o8);
+        g.row = (h.o8 - g.m0) * 8u;
+        const uint32_t nch = (hl + 7u) >> 3;
+        // a row is read as pieces of 16 bytes plus the 8 bytes behind them: up to 24 bytes past the read's own padded bytes
+        const bool fits = valid && h.o8 >= g.m0 && (h.o8 - g.m0) <= (uint32_t)(QRUN / 8) && g.row + 8u * nch <= (uint32_t)QRUN;
+        const unsigned long long fitmask = __ballot(fits);
+        g.ntake = fitmask == ~0ull ? 64 : __builtin_ctzll(~fitmask);
+        g.solo = g.ntake == 0;
+        if (g.solo) g.ntake = 1;
+        g.Tq = g.solo ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)(g.row + 8u * nch), g.ntake - 1);
+        g.fastq = b.lane < g.ntake && !g.solo && shortq;
+        if (!g.fastq) { g.row = 0u; g.np = 1u; }
+        return g;
+    }
+    // LDS-DMA of a run: lane l moves bytes [1024 s + 16 l, + 16) to the same offset of the staging buffer; lanes past the
+    // run re-read its end, lanes past the buffer do nothing
+    __device__ void stage(const F5HdrP &, const Geo &g, bool bases, lds_u8 *stage) const {
+        const uint8_t *run = bases ? b.rd.seq + (int64_t)g.m0 * 4 : b.rd.qual + (int64_t)g.m0 * 8;
+        const uint32_t nbytes = bases ? g.Tq >> 1 : g.Tq;
+        const int cap = bases ? QRUN / 2 : QRUN;
+        const uint32_t last = nbytes ? (nbytes - 1u) & ~15u : 0u;
+#pragma unroll
+        for (int sl = 0; sl < (cap + 1023) / 1024; ++sl) {
+            uint32_t off = (uint32_t)(sl * 1024 + b.lane * 16);
+            if (sl * 1024 + 1024 <= cap || (int)off < cap) dma16(run + (off < last ? off : last), stage + sl * 1024);
+        }
+    }
+    // one dword of every 128-byte line of the run's packed bases
+    __device__ void prefetch(const F5HdrP &, const Geo &g1, uint32_t &pfA, uint32_t &pfB) const {
+        const uint32_t nb = g1.Tq >> 1;
+        const uint32_t off = (uint32_t)b.lane * 128u;
+        const uint8_t *sb = b.rd.seq + (int64_t)g1.m0 * 4;
+        pfA = *(const uint32_t *)(sb + (off < nb ? off : 0u));
+        if (QRUN / 2 > 8192) pfB = *(const uint32_t *)(sb + (off + 8192u < nb ? off + 8192u : 0u));
+    }
+};
+
+template <int W, int F5_WAVES, int F5_QRUN, int F5_REP, int F5_PW>
+__global__ void __launch_bounds__(F5_WAVES * 64, 2)
+k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_ARGS)
+    f5_tiles<W, F5_REP, F5_PW>(F5Run<F5_WAVES, F5_QRUN>{}, F_ARGS_FWD);
+}
+
 struct Fast5Cfg { int waves, qrun; };
 // which build: by the mean padded read length of the batch (bases, a multiple of 8 per read)
 static inline Fast5Cfg fast5_cfg(int64_t n_reads, int64_t n_bases_padded, int window) {
@@ -666,10 +790,11 @@ static inline Fast5Cfg fast5_cfg(int64_t n_reads, int64_t n_bases_padded, int wi
     if (mean_pad <= 192) return Fast5Cfg{6, 13312};
     return Fast5Cfg{4, 19456};
 }
-static inline FastGrid fast5_grid(int64_t n_reads, int n_cu, const Fast5Cfg &cf) {
+// grid of k_fast5 / k_fast7 with so many waves per block
+static inline FastGrid fast5_grid(int64_t n_reads, int n_cu, int waves) {
     int64_t rpb = (n_reads + (int64_t)n_cu - 1) / (int64_t)n_cu;
     rpb = ((rpb + 63) / 64) * 64;
-    if (rpb < 2 * cf.waves * 64) rpb = 2 * cf.waves * 64;
+    if (rpb < 2 * waves * 64) rpb = 2 * waves * 64;
     return FastGrid{(n_reads + rpb - 1) / rpb, rpb};
 }
 

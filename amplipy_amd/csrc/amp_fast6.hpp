@@ -157,19 +157,6 @@ __device__ __forceinline__ void f6_count16(const uint2 &m, uint32_t wb, uint32_t
     f6_add8<8>(wb, se1, so1, one);
 }
 
-// minimum over the lanes of the wave (DPP row shifts and row broadcasts, no LDS traffic); the result is uniform
-__device__ __forceinline__ int32_t wave_min_i32(int32_t x) {
-    int32_t t = x, u;
-    const int32_t big = 0x7FFFFFFF;
-    u = __builtin_amdgcn_update_dpp(big, t, 0x111, 0xF, 0xF, false); t = u < t ? u : t;      // row_shr:1
-    u = __builtin_amdgcn_update_dpp(big, t, 0x112, 0xF, 0xF, false); t = u < t ? u : t;      // row_shr:2
-    u = __builtin_amdgcn_update_dpp(big, t, 0x114, 0xF, 0xF, false); t = u < t ? u : t;      // row_shr:4
-    u = __builtin_amdgcn_update_dpp(big, t, 0x118, 0xF, 0xF, false); t = u < t ? u : t;      // row_shr:8
-    u = __builtin_amdgcn_update_dpp(big, t, 0x142, 0xA, 0xF, false); t = u < t ? u : t;      // row_bcast:15 into rows 1 and 3
-    u = __builtin_amdgcn_update_dpp(big, t, 0x143, 0xC, 0xF, false); t = u < t ? u : t;      // row_bcast:31 into rows 2 and 3
-    return __builtin_amdgcn_readlane(t, 63);
-}
-
 // phase stamps of development builds (-DAMP_F6_STAMPS: cycles per phase summed over the waves into ctr[8 ..], turns into ctr[6]); the
 // shipped library has none
 #ifdef AMP_F6_WAITSTAMPS

@@ -1,6 +1,6 @@
-// amp_fast7.hpp -- the fast kernel for batches of MIXED read lengths (variant 7): k_fast5's tile code (amp_fast5.hpp) driven
-// by per-block lists of reads binned by length, so that a tile's piece loops run to the length of ITS reads and no lane is
-// spent on a read that goes to the general pass.  CDNA4 / gfx950.
+// amp_fast7.hpp -- the fast kernel for batches of MIXED read lengths (variant 7): the second generation's tile loop
+// (f5_tiles, amp_fast5.hpp) driven by per-block lists of reads binned by length, so that a tile's piece loops run to the
+// length of ITS reads and no lane is spent on a read that goes to the general pass.  CDNA4 / gfx950.
 //
 // What k_fast5 does on BASELINE config 5 (75-300 bp reads, 40 % of them for the general pass): a tile is 64 CONSECUTIVE
 // reads, its loops run to the longest of them (300 bases in practically every tile) and 43 % of its lanes hold reads it
@@ -14,33 +14,17 @@
 //     and the piece loops are half as long.  Both lanes compute the read's trims (same inputs, same result); the first
 //     failing window is the minimum over the pair; results, indel extras and hand-overs are lane 2r's.
 // A tile's rows are gathered by LDS-DMA into a row-major image with a stride per bin (a multiple of 16 bytes: lane l of
-// instruction s moves image bytes [1024 s + 16 l, + 16), which lie in ONE row); everything behind the staging buffers is
-// amp_fast5.hpp's code with a lane's first piece (`pbase`) added to its piece numbers.
+// instruction s moves image bytes [1024 s + 16 l, + 16), which lie in ONE row).  This file holds that tile source, F7Lists;
+// everything behind the staging buffers is the shared tile loop, which sees a lane's first piece (`pbase') and whether it
+// stores its read's results (`mine').
 #pragma once
 
 #include "amp_fast5.hpp"
-#include "amp_fast6.hpp"
 
 namespace amp {
 
-#ifndef AMP_F7_ADD64
-#define AMP_F7_ADD64 1      // 64-bit counter adds (count_piece5q): two replicas of two arrays each
-#endif
 #ifndef AMP_F7_ABL
-#define AMP_F7_ABL 0
-#endif
-// development builds (-DAMP_F7_STAMPS): shader cycles a wave spends in the two waits of a turn, in the piece loops and in all of its
-// turns, summed over the waves into ctr[8 ..], turns into ctr[6] (tools/time_config5.py prints them)
-#ifdef AMP_F7_STAMPS
-#define F7_T(k) do { const unsigned long long f7_n = __builtin_amdgcn_s_memtime(); f7_t[k] += f7_n - f7_prev; f7_prev = f7_n; } while (0)
-#else
-#define F7_T(k) do { } while (0)
-#endif
-#ifndef AMP_F7_LAYOUT
-#define AMP_F7_LAYOUT 0
-#endif
-#ifndef AMP_F7_SKEW
-#define AMP_F7_SKEW 1
+#define AMP_F7_ABL 0      // development builds: bit 2 no gather, bit 4 no tiles (the lists only); results are wrong on purpose
 #endif
 #ifndef AMP_F7_REPS
 #define AMP_F7_REPS 4
@@ -55,20 +39,13 @@ namespace amp {
 #ifndef AMP_F7_PWIN
 #define AMP_F7_PWIN 400                   // a read of 304 bases + 16 positions in front + the spread of a tile's starts
 #endif
-#if AMP_F7_LAYOUT == 1                  // (experiment: six waves, reads of up to 208 bases one lane each)
-constexpr int F7_WAVES = 6;
-constexpr int F7_QCAP = 13312;            // 64 x 208, 32 x 304
-constexpr int F7_SCAP = 7168;             // 64 x 112
-constexpr uint32_t F7_B2MAX = 208u, F7_PAIRBIN = 3u, F7_B2MAGIC = 20648882u;
-#else
 constexpr int F7_WAVES = AMP_F7_NWAVES;
 constexpr int F7_QCAP = 9728;             // bytes of a tile's quality image (64 x 144, 32 x 304)
 constexpr int F7_SCAP = 5120;             // ... of its packed-base image (64 x 80, 32 x 160)
 constexpr uint32_t F7_B2MAX = 224u, F7_PAIRBIN = 2u, F7_B2MAGIC = 19173962u;      // bin 2: reads of up to so many bases; bins from here on hold two lanes per read; ceil(2^32 / F7_B2MAX)
-#endif
 constexpr int F7_REP = AMP_F7_REPS, F7_PW = AMP_F7_PWIN;    // packed window: replicas, positions
 constexpr int F7_NBIN = 4;
-constexpr int F7_SLOTS = AMP_F7_LAYOUT == 1 ? 14 : 10;      // pieces of a LANE at most (a read of more than 144 bases has two lanes)
+constexpr int F7_SLOTS = 10;              // pieces of a LANE at most (a read of more than 144 bases has two lanes)
 
 // one of four 16-bit / 32-bit constants by a bin number (shifts of packed words: a chain of selects becomes a table in scratch
 // memory, and every load from it makes the wave wait for all of its loads in flight)
@@ -82,241 +59,142 @@ __device__ __forceinline__ uint32_t f7_pick32(uint32_t b, uint32_t v0, uint32_t 
 }
 __device__ __forceinline__ uint32_t f7_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
-template <int W>
-__global__ void __launch_bounds__(F7_WAVES * 64, 2)
-k_fast7(F_ARGS, int32_t pad19, uint32_t *clist) {      // (individual arguments, like k_fast: see the note at F_ARGS)
-    constexpr int F5_WAVES = F7_WAVES, F5_REP = F7_REP, F5_PW = F7_PW;
-    const KParams P{a_min_quality, a_window, a_do_trim, a_do_count, a_ref_len, a_max_primer_len, a_min_start, a_max_end, (uint32_t)a_epoch};
-    const amp_dev_reads rd{a_n_reads, a_pos, a_flag, a_tlen, a_lseq, a_cig_off32, a_cig, a_seq_off8, a_seq, a_qual, 0, 0};
-    const DevOut out{a_new_pos, a_new_ncig, a_new_cig, a_o_ref_len, a_trim_flags, a_status};
-    const EventBuf eb{a_ev, a_ctr, a_ins_at, a_ev_cap};
-    constexpr int F5_REPW = F5_PW + AMP_F7_SKEW;        // words of a replica of the wave's packed window (replica r is skewed by r banks)
-    // 64-bit adds (count_piece5q, amp_fast.hpp): a replica is two arrays, for pieces that start on an even / odd window offset; needs an
-    // even number of arrays and an odd number of words in each
-    constexpr bool F5_ADD64 = AMP_F7_ADD64 && F5_REP % 2 == 0 && F5_REPW % 2 == 1;
-    constexpr int F5_NREP = F5_ADD64 ? F5_REP / 2 : F5_REP;               // replicas a lane can be sent to
-    constexpr int F5_FLUSH = 255 / (((16 + F5_NREP - 1) / F5_NREP) * 4);      // (lanes go to replicas in groups of four: so many of them add into one array at most)
-    constexpr int F5_QB = F5_PAD + F7_QCAP + 2 * F5_PAD, F5_SB = F5_PAD + F7_SCAP + F5_PAD;      // (a row's last piece is read with the 8 bytes behind it: up to 23 bytes past the image)
-    __shared__ uint4 s_q[F5_WAVES][F5_QB / 16];                       // per wave: the tile's quality bytes
-    __shared__ uint4 s_s[F5_WAVES][F5_SB / 16];                       // per wave: the tile's packed bases
-    __shared__ __attribute__((aligned(8))) uint32_t s_pwin[F5_WAVES][F5_REP * F5_REPW];           // per wave: packed counters, byte c of a word = base c (A C G T)
-    __shared__ uint32_t s_bwin[F_BPL * F_BW];                         // the block's window, 32-bit counters
-    __shared__ uint32_t s_ticket, s_gcur, s_nb[F7_NBIN];
-    unsigned long long *const ctr = eb.ctr;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t n = rd.n_reads;
-    const int64_t rb = (int64_t)blockIdx.x * reads_per_block;
-    const int64_t re = rb + reads_per_block < n ? rb + reads_per_block : n;
-    lds_u32 *const bwin = (lds_u32 *)s_bwin;
-    lds_u32 *const pwin = (lds_u32 *)s_pwin[wave];
-    for (int i = tid; i < F_BPL * F_BW; i += F5_WAVES * 64) bwin[i] = 0;
-    for (int i = lane; i < F5_REP * F5_REPW; i += 64) pwin[i] = 0;
-    // every nibble of the base staging buffer starts as a valid code (the bytes in front of a run are read by the
-    // lanes whose pieces start 8 bases early, and are never written again)
-    for (int i = lane; i < F5_SB / 4; i += 64) ((lds_u32 *)s_s[wave])[i] = 0x11111111u;
-    if (tid == 0) { s_ticket = 0; s_gcur = 0; s_nb[0] = 0; s_nb[1] = 0; s_nb[2] = 0; s_nb[3] = 0; }
-    if (tid == 0 && blockIdx.x == 0) { eb.ctr[26] = 0ull; eb.ctr[27] = 0ull; eb.ctr[28] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
-    int32_t bw_base = rb < n ? rd.pos[rb] : 0;
-    bw_base = (bw_base < 16 ? 0 : bw_base - 16) & ~15;
-    __syncthreads();
-
-    const int32_t mq = P.min_quality;
-    const uint32_t mqc = (uint32_t)(mq > 256 ? 256 : mq);
-    const uint32_t thr = mqc * (uint32_t)W;
-    const uint32_t mqb = (uint32_t)mq * 0x01010101u;             // mq <= 128 (the host sends other runs to the general kernel)
-    const uint32_t G = (uint32_t)P.ref_len;
-    const uint32_t q_tot8 = rd.seq_off8[n];                          // rows end here (units of 8 bases): 16 bytes of slack behind
-    // ---- bins: the block's reads by length (A:426-753 do not care about the order of reads).  The block's segment of clist is
-    // two stretches of reads_per_block entries: bins 0 / 1 fill the first from its front / back, bins 2 / 3 the second; reads
-    // that cannot have the closed-form shape go on the general list at once.  (The order inside a list is the order in which
-    // the waves' groups of 64 reads arrive: a tile does not rely on it.)
-    uint32_t *const seg = clist + 2 * rb;
-    {
-        constexpr int R = 4;                                       // groups of 64 reads whose loads are in flight together
-        for (int64_t g0 = rb + (int64_t)wave * 64; g0 < re; g0 += (int64_t)R * F7_WAVES * 64) {
-            uint32_t c0[R], c1[R], ls[R], wf[R], wl[R];
+// k_fast7's tile source (see the head of the file).  A key is a lane's list entry: its read, 0xFFFFFFFF for none.
+struct F7Lists {
+    static constexpr int WAVES = F7_WAVES, QCAP = F7_QCAP, SCAP = F7_SCAP;
+    static constexpr int SLOTS = F7_SLOTS, AHEAD = F7_SLOTS;
+    static constexpr bool SORTED = false;       // (a list is not strictly in the order of the batch)
+    // row = offset of the lane's row in the quality image (the packed bases' image has rows at brow), np = pieces of the LANE,
+    // first = its first piece, half = the second lane of a pair
+    struct Geo { uint32_t np, first, row, brow, bin; bool half, fastq;
+        __device__ uint32_t pbase() const { return first; }
+        __device__ uint32_t srow() const { return brow; }
+        __device__ bool mine() const { return !half; }
+        __device__ bool pair() const { return bin >= F7_PAIRBIN; }
+        __device__ uint32_t past() const { return 4096u; } };      // (np lies on the partner's pieces)
+    uint32_t *clist;                          // 2 * grid * rpb words of scratch (the blocks' lists)
+    lds_u32 *nb;                              // the lengths of the block's four lists
+    F5Blk b;
+    uint32_t *seg;
+    uint32_t q_tot8, nb0, nb1, nb2, nb3, t1, t2, t3, n_tb;
+    uint32_t tk0, tk1, tk2, tk3, tk4;         // (tickets run four tiles ahead: the list entries of tile t + 4 are asked for while
+    uint32_t k0, k1, kR, kN;                  //  tile t is computed, the headers of t + 3)
+    __device__ void clear() const { nb[0] = 0; nb[1] = 0; nb[2] = 0; nb[3] = 0; }
+    __device__ void prologue(const F5Blk &blk, uint32_t *glist, lds_u32 *gcur) {
+        b = blk;
+        const int64_t rb = b.rb, re = b.re;
+        const int lane = b.lane;
+        q_tot8 = b.rd.seq_off8[b.rd.n_reads];      // rows end here (units of 8 bases): 16 bytes of slack behind
+        // ---- bins: the block's reads by length (A:426-753 do not care about the order of reads).  The block's segment of clist is
+        // two stretches of reads_per_block entries: bins 0 / 1 fill the first from its front / back, bins 2 / 3 the second; reads
+        // that cannot have the closed-form shape go on the general list at once.  (The order inside a list is the order in which
+        // the waves' groups of 64 reads arrive: a tile does not rely on it.)
+        seg = clist + 2 * rb;
+        {
+            constexpr int R = 4;                                       // groups of 64 reads whose loads are in flight together
+            for (int64_t g0 = rb + (int64_t)b.wave * 64; g0 < re; g0 += (int64_t)R * F7_WAVES * 64) {
+                uint32_t c0[R], c1[R], ls[R], wf[R], wl[R];
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int64_t i = g0 + (int64_t)r * F7_WAVES * 64 + lane;
-                const int64_t ic = i < re ? i : rb;
-                c0[r] = rd.cig_off32[ic]; c1[r] = rd.cig_off32[ic + 1]; ls[r] = rd.lseq[ic];
-            }
+                for (int r = 0; r < R; ++r) {
+                    const int64_t i = g0 + (int64_t)r * F7_WAVES * 64 + lane;
+                    const int64_t ic = i < re ? i : rb;
+                    c0[r] = b.rd.cig_off32[ic]; c1[r] = b.rd.cig_off32[ic + 1]; ls[r] = b.rd.lseq[ic];
+                }
 #pragma unroll
-            for (int r = 0; r < R; ++r) {      // first and last CIGAR word of the reads with four or five ops: such a shape needs soft clips
-                const uint32_t nops = c1[r] - c0[r];
-                const bool want = nops == 4u || nops == 5u;
-                wf[r] = want ? rd.cig[c0[r]] : 4u; wl[r] = want ? rd.cig[c1[r] - 1u] : 4u;
-            }
+                for (int r = 0; r < R; ++r) {      // first and last CIGAR word of the reads with four or five ops: such a shape needs soft clips
+                    const uint32_t nops = c1[r] - c0[r];
+                    const bool want = nops == 4u || nops == 5u;
+                    wf[r] = want ? b.rd.cig[c0[r]] : 4u; wl[r] = want ? b.rd.cig[c1[r] - 1u] : 4u;
+                }
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int64_t i = g0 + (int64_t)r * F7_WAVES * 64 + lane;
-                const bool valid = i < re;
-                const uint32_t nops = c1[r] - c0[r];
-                const bool sf = (wf[r] & 15u) == OP_S, sl = (wl[r] & 15u) == OP_S;
-                const bool cand = ls[r] >= 1u && ls[r] <= (uint32_t)F5_MAXLEN && nops >= 1u && nops <= 5u && (nops < 4u || (nops == 4u ? (sf | sl) : (sf & sl)));
-                const uint32_t cls = !valid ? 5u : !cand ? 4u : ls[r] <= 80u ? 0u : ls[r] <= 144u ? 1u : ls[r] <= F7_B2MAX ? 2u : 3u;
+                for (int r = 0; r < R; ++r) {
+                    const int64_t i = g0 + (int64_t)r * F7_WAVES * 64 + lane;
+                    const bool valid = i < re;
+                    const uint32_t nops = c1[r] - c0[r];
+                    const bool sf = (wf[r] & 15u) == OP_S, sl = (wl[r] & 15u) == OP_S;
+                    const bool cand = ls[r] >= 1u && ls[r] <= (uint32_t)F5_MAXLEN && nops >= 1u && nops <= 5u && (nops < 4u || (nops == 4u ? (sf | sl) : (sf & sl)));
+                    const uint32_t cls = !valid ? 5u : !cand ? 4u : ls[r] <= 80u ? 0u : ls[r] <= 144u ? 1u : ls[r] <= F7_B2MAX ? 2u : 3u;
 #pragma unroll
-                for (uint32_t c = 0; c < 5u; ++c) {
-                    const unsigned long long m = __ballot(cls == c);
-                    if (!m) continue;
-                    uint32_t base = 0;
-                    if (lane == 0) base = __hip_atomic_fetch_add(c == 4u ? (lds_u32 *)&s_gcur : (lds_u32 *)&s_nb[c], (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                    const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                    if (cls == c) {
-                        if (c == 4u) glist[(size_t)rb + at] = (uint32_t)i;
-                        else seg[(c >> 1) * (uint32_t)reads_per_block + ((c & 1u) ? (uint32_t)reads_per_block - 1u - at : at)] = (uint32_t)i;
+                    for (uint32_t c = 0; c < 5u; ++c) {
+                        const unsigned long long m = __ballot(cls == c);
+                        if (!m) continue;
+                        uint32_t base = 0;
+                        if (lane == 0) base = __hip_atomic_fetch_add(c == 4u ? gcur : &nb[c], (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                        const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                        if (cls == c) {
+                            if (c == 4u) glist[(size_t)rb + at] = (uint32_t)i;
+                            else seg[(c >> 1) * (uint32_t)b.rpb + ((c & 1u) ? (uint32_t)b.rpb - 1u - at : at)] = (uint32_t)i;
+                        }
                     }
                 }
             }
         }
+        __syncthreads();
+        // tiles, longest bin first: tiles [0, t3) of bin 3, [t3, t2) of bin 2 (32 reads each), [t2, t1) of bin 1, [t1, n_tb) of bin 0
+        nb0 = nb[0]; nb1 = nb[1]; nb2 = nb[2]; nb3 = nb[3];
+        t3 = (nb3 + 31u) >> 5; t2 = t3 + ((nb2 + 31u) >> 5); t1 = t2 + ((nb1 + 63u) >> 6); n_tb = (AMP_F7_ABL & 4) ? 0u : t1 + ((nb0 + 63u) >> 6);
     }
-    __syncthreads();
-    // tiles, longest bin first: tiles [0, t3) of bin 3, [t3, t2) of bin 2 (32 reads each), [t2, t1) of bin 1, [t1, n_tb) of bin 0
-    const uint32_t nb0 = s_nb[0], nb1 = s_nb[1], nb2 = s_nb[2], nb3 = s_nb[3];
-    const uint32_t t3 = (nb3 + 31u) >> 5, t2 = t3 + (F7_PAIRBIN <= 2u ? (nb2 + 31u) >> 5 : (nb2 + 63u) >> 6), t1 = t2 + ((nb1 + 63u) >> 6), n_tb = (AMP_F7_ABL & 4) ? 0u : t1 + ((nb0 + 63u) >> 6);
-    auto take_ticket = [&]() {
-        uint32_t t = 0;
-        if (lane == 0) t = __hip_atomic_fetch_add((lds_u32 *)&s_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-    };
-    uint32_t n_err = 0;
-    // bank plan: lane l works on piece (k + l) mod np in step k, starts its pieces 8 bases early when bit 1 of l is
-    // set and adds into replica (l >> 2) & 3 (replica r is skewed by r banks)
-    const uint32_t rep = (F5_REP & (F5_REP - 1)) ? ((uint32_t)lane >> 2) % (uint32_t)F5_REP : ((uint32_t)lane >> 2) & (uint32_t)(F5_REP - 1);
-    const uint32_t phi_lane = ((uint32_t)lane >> 1) & 1u ? 8u : 0u;
-    const uint32_t wrep = (uint32_t)(uintptr_t)((lds_u8 *)pwin + (F5_ADD64 ? (rep % (uint32_t)F5_NREP) * (uint32_t)(2 * F5_REPW * 4) : rep * (uint32_t)(F5_REPW * 4)));
-    auto count5 = [&](const uint2 &sq_, uint32_t m_, int32_t d0_, int32_t lim_) -> uint32_t {
-        if constexpr (F5_ADD64) return count_piece5q(sq_, m_, d0_, lim_, wrep, (uint32_t)(F5_REPW * 4));
-        else return count_piece5(sq_, m_, d0_, lim_, wrep);
-    };
-    lds_u8 *const qst = (lds_u8 *)s_q[wave] + F5_PAD;
-    lds_u8 *const sst = (lds_u8 *)s_s[wave] + F5_PAD;
-    int32_t pw_base = 0;
-    int pw_tiles = F5_FLUSH;
-    const unsigned ev_shard = blockIdx.x & (EV_SHARDS - 1);
-    amp_ins_event *const ev_list = eb.ev + (size_t)ev_shard * (size_t)eb.cap;
-    unsigned long long ev_base = 0;
-    uint32_t ev_left = 0;
-
-    // folds the wave's packed window into the block's 32-bit window (or the global table) and clears it
-    auto fold = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the adds of the counting phase are invisible to the compiler's wait counts)
-        wave_sync();
-#pragma unroll 1
-        for (int idx = lane; idx < F5_PW; idx += 64) {
-            uint32_t ag = 0, ct = 0;                                 // A | G << 16, C | T << 16
-#pragma unroll
-            for (int r = 0; r < F5_REP; ++r) {
-                const uint32_t w = pwin[r * F5_REPW + idx];
-                pwin[r * F5_REPW + idx] = 0;
-                ag += w & 0x00FF00FFu; ct += (w >> 8) & 0x00FF00FFu;
-            }
-            if (ag | ct) {
-                const int32_t p = pw_base + idx;
-                const uint32_t d = (uint32_t)(p - bw_base);
-                const uint32_t c4[4] = {ag & 0xFFFFu, ct & 0xFFFFu, ag >> 16, ct >> 16};
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (!c4[c]) continue;
-                    if (d < (uint32_t)F_BW) lds_add(bwin + c * F_BW + d, c4[c]);
-                    else if ((uint32_t)p < G) atomicAdd(&counts[(size_t)p * AMP_NSYM + c], c4[c]);
-                }
-            }
-        }
-        wave_sync();
-    };
-    auto pad_events = [&]() {
-        if ((uint32_t)lane < ev_left && (long long)(ev_base + (unsigned)lane) < eb.cap) ev_list[ev_base + (unsigned)lane] = amp_ins_event{-1, 0u, 0, 0};
-    };
-
-    struct Hdr { int32_t pos, tlen; uint32_t lseq, flag, c0, c1, o8; };      // as loaded
-    // ... and as kept: lf = l_seq (saturated at 0xFFFF) | paired << 16 | reverse << 17 | the template-length test of A:452 << 18 |
-    // number of CIGAR ops (saturated at 7) << 19 | lane holds a read of the block << 22
-    struct HdrP { int32_t pos; uint32_t lf, c0, o8, idx;      // idx: the read (a lane without one points at the block's first read)
-        __device__ uint32_t lseq() const { return lf & 0xFFFFu; }
-        __device__ uint32_t nops() const { return (lf >> 19) & 7u; }
-        __device__ uint32_t flag() const { return ((lf >> 16) & 1u) | (((lf >> 17) & 1u) << 4); }
-        __device__ bool isize_flag() const { return (lf >> 18) & 1u; }
-        __device__ bool valid() const { return (lf >> 22) & 1u; } };
-    // tile tk: its bin, and the list entry of the lane (read index; 0xFFFFFFFF = none).  Tiles of bins 2 and 3 hold 32 reads,
-    // two lanes each.
-    auto bin_of = [&](uint32_t tk) -> uint32_t { return 3u - (tk >= t3 ? 1u : 0u) - (tk >= t2 ? 1u : 0u) - (tk >= t1 ? 1u : 0u); };
-    auto entry_of = [&](uint32_t tk) -> uint32_t {
-        const uint32_t b = bin_of(tk);
-        const uint32_t first = f7_pick32(b, t1, t2, t3, 0u), cnt = f7_pick32(b, nb0, nb1, nb2, nb3);      // (by value: a select between captured variables is a select between their addresses, and puts them in scratch memory)
+    // tile tk: its bin, and the list entry of the lane.  Tiles of bins 2 and 3 hold 32 reads, two lanes each.
+    __device__ uint32_t bin_of(uint32_t tk) const { return 3u - (tk >= t3 ? 1u : 0u) - (tk >= t2 ? 1u : 0u) - (tk >= t1 ? 1u : 0u); }
+    __device__ uint32_t entry_of(uint32_t tk) const {
+        const uint32_t b_ = bin_of(tk);
+        const uint32_t first = f7_pick32(b_, t1, t2, t3, 0u), cnt = f7_pick32(b_, nb0, nb1, nb2, nb3);      // (by value: a select between captured variables is a select between their addresses, and puts them in scratch memory)
         const uint32_t ln = f7_lane();
-        const uint32_t j = b >= F7_PAIRBIN ? (tk - first) * 32u + (ln >> 1) : (tk - first) * 64u + ln;
+        const uint32_t j = b_ >= F7_PAIRBIN ? (tk - first) * 32u + (ln >> 1) : (tk - first) * 64u + ln;
         const bool valid = tk < n_tb && j < cnt;
-        const uint32_t at = (b >> 1) * (uint32_t)reads_per_block + ((b & 1u) ? (uint32_t)reads_per_block - 1u - j : j);
+        const uint32_t at = (b_ >> 1) * (uint32_t)b.rpb + ((b_ & 1u) ? (uint32_t)b.rpb - 1u - j : j);
         const uint32_t e = seg[valid ? at : 0u];
         return valid ? e : 0xFFFFFFFFu;
-    };
-    auto load_hdr = [&](uint32_t ent) {
-        const int64_t i = ent == 0xFFFFFFFFu ? rb : (int64_t)ent;
-        Hdr h;
-        h.pos = rd.pos[i]; h.flag = rd.flag[i]; h.tlen = rd.tlen[i]; h.lseq = rd.lseq[i];
-        h.c0 = rd.cig_off32[i]; h.c1 = rd.cig_off32[i + 1]; h.o8 = rd.seq_off8[i];
+    }
+    template <class T> __device__ void start(T ticket) {
+        tk0 = ticket(); tk1 = ticket(); tk2 = ticket(); tk3 = ticket();
+        k0 = entry_of(tk0); k1 = entry_of(tk1);
+        kR = entry_of(tk2); kN = entry_of(tk3);
+    }
+    template <class T> __device__ void take(T ticket) { tk4 = ticket(); }
+    __device__ F5Hdr next_hdr() {
+        const F5Hdr h = load_hdr(kN);           // (kN arrived before the wait at the top of this turn)
+        kR = kN;
+        kN = entry_of(tk4);
         return h;
-    };
-    auto pack_hdr = [&](const Hdr &h, uint32_t ent) {
-        const uint32_t nn = h.c1 - h.c0, at = (uint32_t)(h.tlen < 0 ? -(int64_t)h.tlen : (int64_t)h.tlen);
-        const bool isz = ((int64_t)at - P.max_primer_len) > (int64_t)h.lseq;                                  // A:452
-        const bool valid = ent != 0xFFFFFFFFu;
-        return HdrP{h.pos, (h.lseq > 0xFFFFu ? 0xFFFFu : h.lseq) | ((h.flag & 1u) << 16) | (((h.flag >> 4) & 1u) << 17) | ((isz ? 1u : 0u) << 18) |
-                               ((nn > 7u ? 7u : nn) << 19) | ((valid ? 1u : 0u) << 22), h.c0, h.o8, valid ? ent : (uint32_t)rb};
-    };
-    struct Cg { uint32_t w[5]; };
-    auto load_cig = [&](const HdrP &h) {
-        Cg c{{0u, 0u, 0u, 0u, 0u}};
-        const uint32_t nops = h.nops();
-        if (nops >= 1u && nops <= 5u) {
-#pragma unroll
-            for (uint32_t k = 0; k < 5u; ++k) c.w[k] = rd.cig[h.c0 + (k < nops ? k : 0u)];
-        }
-        return c;
-    };
-    // a tile's geometry: row = offset of the lane's row in the quality image (the packed bases' image has rows of srow bytes),
-    // np = pieces of the LANE, pbase = its first piece, half = the second lane of a pair
-    struct Geo { uint32_t np, pbase, row, srow, bin; bool half, fastq; };
-    auto geometry = [&](const HdrP &h, uint32_t tk) {
+    }
+    __device__ void rotate() { tk0 = tk1; tk1 = tk2; tk2 = tk3; tk3 = tk4; }
+    __device__ void touch() const { asm volatile("" : : "v"(kN), "v"(kR)); }
+    __device__ bool valid(uint32_t ent) const { return ent != 0xFFFFFFFFu; }
+    __device__ uint32_t idx(uint32_t ent) const { return valid(ent) ? ent : (uint32_t)b.rb; }      // (a lane without a read points at the block's first)
+    __device__ int64_t index(const F5HdrP &h) const { return (int64_t)h.idx; }
+    __device__ F5Hdr load_hdr(uint32_t ent) const {
+        const int64_t i = ent == 0xFFFFFFFFu ? b.rb : (int64_t)ent;
+        F5Hdr h;
+        h.pos = b.rd.pos[i]; h.flag = b.rd.flag[i]; h.tlen = b.rd.tlen[i]; h.lseq = b.rd.lseq[i];
+        h.c0 = b.rd.cig_off32[i]; h.c1 = b.rd.cig_off32[i + 1]; h.o8 = b.rd.seq_off8[i];
+        return h;
+    }
+    __device__ Geo geometry(const F5HdrP &h, uint32_t tk, uint32_t phi_lane) const {
         Geo g;
         g.bin = bin_of(tk);
         const bool pair = g.bin >= F7_PAIRBIN;
         const uint32_t qs = f7_pick16(g.bin, 80u, 144u, F7_B2MAX, 304u);
         const uint32_t ss = f7_pick16(g.bin, 48u, 80u, 112u, 160u);
         const uint32_t na = 8u + (g.bin & 1u) * 2u;                 // pieces of a pair's first lane (bin 2: 8, bin 3: 10)
-        const uint32_t r = pair ? (uint32_t)lane >> 1 : (uint32_t)lane;
-        g.half = pair && (lane & 1);
+        const uint32_t r = pair ? (uint32_t)b.lane >> 1 : (uint32_t)b.lane;
+        g.half = pair && (b.lane & 1);
         g.fastq = h.valid();
-        const uint32_t npt = (h.lseq() + phi_lane + 15u) >> 4;      // pieces of the read (bins 2 / 3: more than na, by their lengths)
+        const uint32_t npt = (h.lseq() + phi_lane + 15u) >> 4;    // pieces of the read (bins 2 / 3: more than na, by their lengths)
         g.np = !g.fastq ? 1u : !pair ? npt : g.half ? npt - na : na;
-        g.pbase = g.half && g.fastq ? na : 0u;
+        g.first = g.half && g.fastq ? na : 0u;
         g.row = g.fastq ? r * qs : 0u;
-        g.srow = g.fastq ? r * ss : 0u;
+        g.brow = g.fastq ? r * ss : 0u;
         return g;
-    };
-    struct Shape { Bf s; bool ok; int32_t refspan; };
-    auto shape_of = [&](const HdrP &h, const Cg &c, bool fastq) {
-        Shape r;
-        bool ok;
-        r.s = bf_from_words5((int)h.nops(), c.w[0], c.w[1], c.w[2], c.w[3], c.w[4], (int32_t)h.lseq(), F_MAXINS, F_MAXDEL, ok);
-        r.ok = ok & fastq;
-        r.refspan = r.ok ? r.s.m1 + r.s.m2 + r.s.kD() : 1;
-        return r;
-    };
-    struct Tabs { int32_t L, R; };
-    auto load_tabs = [&](const HdrP &h, const Shape &sh) {
-        Tabs t{-1, -1};
-        const bool in_ref = ((uint32_t)h.pos < G) & ((uint32_t)(h.pos + sh.refspan - 1) < G);
-        if (sh.ok & (P.do_trim != 0) & in_ref) { t.L = P.max_end[h.pos]; t.R = P.min_start[h.pos + sh.refspan - 1]; }
-        return t;
-    };
+    }
     // LDS-DMA of a tile's rows: lane l of instruction s moves bytes [1024 s + 16 l, + 16) of the row-major image; they belong
     // to ONE row (strides are multiples of 16), whose address comes from the lane that holds the row.  unit = bytes per 8
     // bases (8: qualities, 4: packed bases).  Bytes of a row behind the end of the batch's buffer are fetched from its end
     // (16 bytes of slack); they lie behind the read's own bytes.
-    auto issue_rows = [&](const uint8_t *base, uint32_t unit, const HdrP &h, uint32_t bin, bool bases, lds_u8 *stage) {
+    __device__ void stage(const F5HdrP &h, const Geo &g, bool bases, lds_u8 *stage) const {
+        const uint8_t *const base = bases ? b.rd.seq : b.rd.qual;
+        const uint32_t unit = bases ? 4u : 8u, bin = g.bin;
         const bool pair = bin >= F7_PAIRBIN;
         const uint32_t stride = bases ? f7_pick16(bin, 48u, 80u, 112u, 160u) : f7_pick16(bin, 80u, 144u, F7_B2MAX, 304u);
         const uint32_t magic = bases ? f7_pick32(bin, 89478486u, 53687092u, 38347923u, 26843546u)
@@ -342,448 +220,22 @@ k_fast7(F_ARGS, int32_t pad19, uint32_t *clist) {      // (individual arguments,
             const uint32_t lim = (q_tot8 - o8v[sl]) * unit;
             if (off0 < nbytes) dma16(base + (int64_t)o8v[sl] * unit + (wv[sl] < lim ? wv[sl] : lim), stage + sl * 1024);      // (lanes past the image: the staging buffer ends there)
         }
-    };
-
-    uint32_t pw_lim = 0;
-
-    if (AMP_F_STAGGER > 0) {       // (wave w starts w steps late, as in k_fast)
-        const unsigned long long t_end = __builtin_amdgcn_s_memtime() + (unsigned long long)AMP_F_STAGGER * (unsigned)wave;
-        while (__builtin_amdgcn_s_memtime() < t_end) __builtin_amdgcn_s_sleep(8);
     }
-    // ---- prologue: three tiles' headers; CIGAR words of the first two; the first tile's qualities and table entries -----------
-    // (tickets run four tiles ahead: the list entries of tile t + 4 are asked for while tile t is computed, the headers of t + 3)
-    uint32_t tk0 = take_ticket(), tk1 = take_ticket(), tk2 = take_ticket(), tk3 = take_ticket();
-    HdrP h0, h1;
-    Hdr hR;
-    uint32_t eR, eN;                               // list entries of the tile whose header is in hR / of the tile behind it
-    {
-        const uint32_t e0 = entry_of(tk0), e1 = entry_of(tk1);
-        eR = entry_of(tk2); eN = entry_of(tk3);
-        const Hdr a = load_hdr(e0), b = load_hdr(e1);
-        hR = load_hdr(eR);
-        h0 = pack_hdr(a, e0); h1 = pack_hdr(b, e1);
+    // the 128-byte lines of the lane's row (a pair shares them out)
+    __device__ void prefetch(const F5HdrP &h1, const Geo &g1, uint32_t &pfA, uint32_t &pfB) const {
+        const uint32_t lim = (q_tot8 - h1.o8) * 4u;
+        const uint32_t off = g1.half ? 128u : 0u;
+        const uint8_t *sb = b.rd.seq + (int64_t)h1.o8 * 4;
+        pfA = *(const uint32_t *)(sb + (off < lim ? off : 0u));
+        pfB = *(const uint32_t *)(sb + (off + 64u < lim ? off + 64u : 0u));
     }
-    Cg cN = load_cig(h1);
-    Geo g0 = geometry(h0, tk0);
-    Shape sh0;
-    {
-        const Cg c = load_cig(h0);
-        issue_rows(rd.qual, 8u, h0, g0.bin, false, qst);
-        sh0 = shape_of(h0, c, g0.fastq);
-    }
-    Tabs tb0 = load_tabs(h0, sh0);
-    uint32_t pfA = 0u, pfB = 0u;                   // (L2 prefetch of the next tile's bases: see below)
-#ifdef AMP_F7_STAMPS
-    unsigned long long f7_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, f7_prev = __builtin_amdgcn_s_memtime();
-    uint32_t f7_turns = 0;
-#endif
-    while (tk0 < n_tb) {
-        // ---- everything issued a phase or more ago has arrived: this tile's qualities and table entries, the next tile's
-        // CIGAR words, the header of the tile behind it -------------------------------------------------------------------
-        F7_T(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        F7_T(1);
-        asm volatile("" : : "v"(pfA), "v"(pfB));
-        // (every register a load of the last turn -- or of the prologue -- wrote is touched HERE, where nothing is in flight: left to its
-        // own devices the compiler waits at the first use, behind the issue of this tile's bases, and the wave sits out their latency)
-        asm volatile("" : : "v"(tb0.L), "v"(tb0.R), "v"(cN.w[0]), "v"(cN.w[1]), "v"(cN.w[2]), "v"(cN.w[3]), "v"(cN.w[4]));
-        asm volatile("" : : "v"(hR.pos), "v"(hR.tlen), "v"(hR.lseq), "v"(hR.flag), "v"(hR.c0), "v"(hR.c1), "v"(hR.o8), "v"(eN), "v"(eR));
-        const HdrP h = h0;
-        const Geo g = g0;
-        const Shape shp = sh0;
-        const Tabs tA = tb0;
-        const Geo g1 = geometry(h1, tk1);
-        const Shape sh1 = shape_of(h1, cN, g1.fastq);
-        const HdrP h2 = pack_hdr(hR, eR);
-        // this tile's packed bases start moving (their buffer was in use until the end of the last tile)
-        issue_rows(rd.seq, 4u, h, g.bin, true, sst);
-        const int64_t i = (int64_t)h.idx;
-        const bool pair = g.bin >= F7_PAIRBIN, mine = !g.half;                // (pair: uniform; mine: the lane that stores the read's results)
-        const int32_t pos = h.pos;
-        const uint32_t lseq = h.lseq(), flag = h.flag(), c0 = h.c0, o8 = h.o8;
-        const uint32_t np = g.np, phi = g.fastq ? phi_lane : 0u;
-        const bool fastq = g.fastq;
-        // ---- the wave's packed window: fold and re-anchor when the tile has moved on, or before a byte could overflow
-        {
-            const int32_t first_pos = wave_min_i32(fastq ? pos : 0x7FFFFFFF);      // (a list is not strictly in the order of the batch)
-            const int32_t want = (first_pos < 16 ? 0 : first_pos - 16) & ~15;
-            if (pw_tiles >= F5_FLUSH || want < pw_base || want - pw_base >= 64) {
-                if (pw_tiles) fold();
-                pw_base = want; pw_tiles = 0;
-            }
-            ++pw_tiles;
-        }
-        pw_lim = (int64_t)G - pw_base >= (int64_t)F5_PW ? (uint32_t)F5_PW : (uint32_t)(G > (uint32_t)pw_base ? G - (uint32_t)pw_base : 0u);
-        // ---- primer clips in closed form (A:450-558), branch-free (amp_bf.hpp) --------------------------------------
-        const bool shaped = shp.ok;
-        const bool in_ref = ((uint32_t)pos < G) & ((uint32_t)(pos + shp.refspan - 1) < G);      // A:450-451
-        const bool rev = (flag & 0x10u) != 0;
-        const bool trim = shaped & (P.do_trim != 0);
-        const int terr = (trim & !in_ref) ? AMP_RS_INDEX_REF : 0;
-        const bool use = trim & in_ref;
-        int32_t tpos = pos;
-        uint32_t tflags = 0u;
-        Bf s = shp.s;
-        {
-            int32_t p2 = pos; uint32_t f2 = 0u;
-            const Bf sp = bf_trim_primers(s, p2, f2, flag, h.isize_flag(), (int32_t)lseq, tA.L, tA.R);
-            if (!(AMP_F5_ABL & 16)) { s = bf_pick(use, sp, s); tpos = use ? p2 : pos; tflags = use ? f2 : 0u; }
-        }
-        const bool scan = use & !s.punt;
-        // aligned-quality window [lo, hi) in PIECE coordinates (query index + phi)
-        int32_t lo, qlen;
-        bf_quality_window(s, (int32_t)lseq, lo, qlen);
-        lo = scan ? lo + (int32_t)phi : 0; qlen = scan ? qlen : 0;
-        const int32_t hi = lo + qlen;
-        // ---- pass over the qualities: slot k of the lane is piece (k + rot) mod np of its read.  Per piece: 16 failing-window
-        // bits (bit b: the W-byte window starting at base b of the piece sums to less than W * min_quality), of which the
-        // first / last inside [lo, hi - W] give the first failing window start (forward) / last failing window end
-        // (reverse); and 16 good-quality bits, kept as ok[k] for the counting phase ------------------------------------------
-        F7_T(4);
-        const uint32_t rot = ((uint32_t)lane >> (pair ? 1 : 0)) % np;
-        const uint32_t pbase = g.pbase;
-        const uint32_t live = wave_or_u32((1u << np) - 1u);                    // bit k: some lane of the tile has a piece in slot k
-        const int32_t lrow = (int32_t)g.row - (int32_t)phi;                    // >= -8: the pad in front of the run
-        const lds_u8 *const lq = qst + g.row;                                  // the read's qualities in the staging buffer
-        uint32_t fo[F7_SLOTS];
-        int32_t ffmin = 0x7FFFFFFF, lemax = -1;
-        // (the 24 bytes of slot k + 1 are asked for before slot k is worked on: a slot's LDS round trip lies under its predecessor's work)
-        auto piece_bytes = [&](int k, amp_u32x2 &a, amp_u32x2 &b, amp_u32x2 &c) {
-            uint32_t p = (uint32_t)k + rot;
-            p = p >= np ? p - np : p;
-            const lds_u8 *src = qst + lrow + (int32_t)((pbase + ((uint32_t)k < np ? p : np - 1u)) * 16u);
-            a = *(const lds_u32x2 *)src; b = *(const lds_u32x2 *)(src + 8); c = *(const lds_u32x2 *)(src + 16);
-        };
-        amp_u32x2 an, bn, cn;
-        piece_bytes(0, an, bn, cn);
-#pragma unroll
-        for (int k = 0; k < F7_SLOTS; ++k) {
-            fo[k] = 0u;
-            if (!((live >> k) & 1u) || (AMP_F5_ABL & 1)) continue;             // (uniform)
-            const amp_u32x2 a = an, b = bn, c = cn;
-            if (k + 1 < F7_SLOTS) piece_bytes(k + 1, an, bn, cn);
-            uint32_t p = (uint32_t)k + rot;
-            p = p >= np ? p - np : p;
-            p = (uint32_t)k < np ? pbase + p : 4096u;                          // (a slot the lane has no piece for: outside every range)
-            const uint4 q = make_uint4(a.x, a.y, b.x, b.y);
-            fo[k] = ok_bits16(q, mqb);
-            if (P.do_trim) {
-                const int32_t j0 = (int32_t)(p * 16u);
-                const uint32_t fail = piece_fail_bits<W>(q, make_uint2(c.x, c.y), thr) & range_bits16(lo - j0, hi - W - j0 + 1);      // window starts j0+b must lie in [lo, hi - W]
-                const int32_t f1 = j0 + (__builtin_ffs((int)fail) - 1), e1 = j0 + (31 - __builtin_clz(fail)) + W;
-                ffmin = ((fail != 0u) & (f1 < ffmin)) ? f1 : ffmin;
-                lemax = ((fail != 0u) & (e1 > lemax)) ? e1 : lemax;
-            }
-        }
-        if (pair) {      // (uniform) the two lanes of a read have looked at different pieces
-            const int32_t fo_ = __builtin_amdgcn_update_dpp(0, ffmin, 0xB1, 0xF, 0xF, true), lo_ = __builtin_amdgcn_update_dpp(0, lemax, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]
-            ffmin = fo_ < ffmin ? fo_ : ffmin; lemax = lo_ > lemax ? lo_ : lemax;
-        }
-        F7_T(5);
-        const uint32_t fb = lq[0];                                             // 0xFF = QUAL '*'
-        // ---- quality clip (A:589-686) --------------------------------------------------------------------------------
-        int32_t iq = rev ? 0 : qlen;
-        {
-            // the shrinking windows at the 3' end decide when no full window failed (A:575-576, A:637-638)
-            int32_t acc = 0;
-            const int32_t kmax = qlen < W - 1 ? qlen : W - 1;
-            const int32_t qlo = lo - (int32_t)phi, qhi = hi - (int32_t)phi;            // query indices
-#pragma unroll
-            for (int32_t k = 1; k <= W - 1; ++k) {
-                const bool on = k <= kmax;
-                const int32_t idx = on ? (rev ? qlo + k - 1 : qhi - k) : 0;
-                acc += on ? (int32_t)lq[idx] : 0;
-                iq = (on & ((int64_t)acc < (int64_t)mq * k)) ? (rev ? k : qlen - k) : iq;
-            }
-            iq = (!rev & (ffmin != 0x7FFFFFFF)) ? ffmin - lo : iq;
-            iq = (rev & (lemax >= 0)) ? lemax - lo : iq;
-        }
-        {
-            uint32_t f2 = tflags;
-            const Bf sq_ = bf_trim_quality(s, tpos, f2, rev, iq, qlen);
-            if (!(AMP_F5_ABL & 16)) { s = bf_pick(scan, sq_, s); tflags = scan ? f2 : tflags; }
-        }
-        // ---- results ---------------------------------------------------------------------------------------------------
-        const bool nogo = ((fb & 0xFFu) == 0xFFu) | (s.punt != 0u);               // QUAL '*': the generic code reports it (A:561-562, A:718); a shape the closed forms leave
-        const bool general = h.valid() & (!shaped | nogo);                       // (a lane whose bytes did not fit the run included)
-        const bool stored = shaped & !nogo;
-        const bool okres = stored & (terr == 0);
-        const int32_t reflen = okres ? s.ref_len() : 0;
-        n_err += (stored & mine & (terr != 0)) ? 1u : 0u;
-        const bool counted = okres & (P.do_count != 0);
-        // ---- what counting needs of the qualities besides the bits: the inserted bases' (A:730-748), and the good bits of
-        // GROUP B = the 16 bases from the 8-aligned start of the second segment, for the piece that holds bases of both
-        // segments of an indel read (its second part is counted on its own) --------------------------------------------
-        const bool two = counted & (s.kind != 0);
-        const int32_t q_seg2 = s.a + s.m1 + s.kI();
-        const int32_t g_b = two ? q_seg2 & ~7 : 0;
-        uint32_t good = 0, okB = 0;
-        if (__ballot(two)) {
-            if (two & (s.kind == 1)) {
-                uint32_t m = 0;
-                for (int32_t j = 0; j < s.k; ++j) m |= ((int32_t)lq[s.a + s.m1 + j] >= mq ? 1u : 0u) << j;      // (a clip may have taken the first inserted bases)
-                good = m;
-            }
-            const amp_u32x2 a = *(const lds_u32x2 *)(lq + g_b), b = *(const lds_u32x2 *)(lq + g_b + 8);
-            okB = ok_bits16(make_uint4(a.x, a.y, b.x, b.y), mqb);
-        }
-        // ---- the tile's bases have arrived; the quality buffer is free: results out, the next tile's loads go out ------
-        F7_T(2);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        F7_T(3);
-        {
-            // [S a][op m1][I|D k][op m2][S c], absent parts left out
-            const uint32_t part[5] = {((uint32_t)s.a << 4) | OP_S, ((uint32_t)s.m1 << 4) | s.op, ((uint32_t)s.k << 4) | (s.kind == 1 ? OP_I : OP_D),
-                                      ((uint32_t)s.m2 << 4) | s.op, ((uint32_t)s.c << 4) | OP_S};
-            const bool okm_ = okres & mine;
-            const bool has[5] = {bool(okm_ & (s.a > 0)), bool(okm_ & (s.m1 > 0)), bool(okm_ & (s.kind != 0)), bool(okm_ & (s.kind != 0) & (s.m2 > 0)), bool(okm_ & (s.c > 0))};
-            uint32_t *home = out.new_cig + ((size_t)c0 + 3 * (size_t)i);
-            uint32_t nc = 0;
-#pragma unroll
-            for (int t = 0; t < 5; ++t) {
-                if (has[t]) home[nc] = part[t];
-                nc += has[t] ? 1u : 0u;
-            }
-            if (stored & mine) {
-                if (out.new_pos) out.new_pos[i] = tpos;
-                if (out.new_ncig) out.new_ncig[i] = nc;
-                if (out.ref_len) out.ref_len[i] = reflen;
-                if (out.trim_flags) out.trim_flags[i] = (uint8_t)(terr ? 0u : tflags);
-                if (out.status) out.status[i] = (uint8_t)terr;
-            }
-        }
-        const uint32_t tk4 = take_ticket();
-        issue_rows(rd.qual, 8u, h1, g1.bin, false, qst);
-        tb0 = load_tabs(h1, sh1);
-        cN = load_cig(h2);
-        hR = load_hdr(eN);                         // (eN arrived before the wait at the top of this turn)
-        eR = eN;
-        eN = entry_of(tk4);
-        {
-            // the next tile's packed bases are pulled into L2 now (the 128-byte lines of the lane's row -- a pair shares them out;
-            // plain loads whose values are only "used" behind the wait at the top of the loop): their LDS-DMA can only be issued
-            // when this tile's bases have been counted, a third of a tile before they are needed
-            const uint32_t lim = (q_tot8 - h1.o8) * 4u;
-            const uint32_t off = g1.half ? 128u : 0u;
-            const uint8_t *sb = rd.seq + (int64_t)h1.o8 * 4;
-            pfA = *(const uint32_t *)(sb + (off < lim ? off : 0u));
-            pfB = *(const uint32_t *)(sb + (off + 64u < lim ? off + 64u : 0u));
-        }
-        // pad nibbles of the staged rows (a row is padded to 8 bases) become a valid code: the test for codes outside
-        // A C G T looks at whole pieces
-        {
-            const uint32_t e = (fastq & mine) ? lseq & 7u : 0u;                // bases of the row's last group of 8 (0: the group is full)
-            if (e) {
-                lds_u32 *w = (lds_u32 *)(sst + g.srow + 4u * (lseq >> 3));
-                // nibble i of the group sits in byte i >> 1, high nibble first
-                const uint32_t x = *w, xs = ((x & 0x0F0F0F0Fu) << 4) | ((x >> 4) & 0x0F0F0F0Fu);      // nibble i at bit 4 i
-                const uint32_t keep = (1u << (4u * e)) - 1u;
-                const uint32_t ys = (xs & keep) | (0x11111111u & ~keep);
-                *w = ((ys & 0x0F0F0F0Fu) << 4) | ((ys >> 4) & 0x0F0F0F0Fu);
-            }
-        }
-        wave_sync();
+};
 
-        // ---- counting (A:709-753): the counted query ranges [qa1, qb1) and [qa2, qb2) in piece coordinates, the window
-        // offset of piece coordinate 0 for each of them ------------------------------------------------------------------
-        const int32_t qa1 = counted ? s.a + (int32_t)phi : 0, qb1 = counted ? qa1 + s.m1 : 0;
-        const int32_t qa2 = two ? qb1 + s.kI() : qb1, qb2 = two ? qa2 + s.m2 : qa2;
-        const int32_t pos2 = tpos + s.m1 + s.kD();                                 // reference position of the second segment
-        bool bad_extra = false;
-        // deletion: '-' at each of its positions (A:714-715), through the block's window
-        if (two & mine & (s.kind == 2) & !(AMP_F5_ABL & 4)) {
-            for (int32_t j = 0; j < s.k; ++j) {
-                const int32_t r = tpos + s.m1 + j;
-                const uint32_t d = (uint32_t)(r - bw_base);
-                if ((uint32_t)r >= G) bad_extra = true;
-                else if (d < (uint32_t)F_BW) lds_add_nt(bwin + 4 * F_BW + d, 1u);
-                else atomicAdd(&counts[(size_t)r * AMP_NSYM + 5], 1u);
-            }
-        }
-        // insertion (A:730-748): one event per maximal run of good-quality inserted bases
-        {
-            uint32_t runs = (AMP_F5_ABL & 4) || !mine ? 0u : good & ~(good << 1);                     // first base of every run
-            const unsigned long long em = __ballot(runs != 0u);
-            if (em) {
-                const uint32_t total = (uint32_t)__popcll(em);
-                if (total > ev_left) {
-                    pad_events();
-                    unsigned long long nb = 0;
-                    if (lane == 0) nb = atomicAdd(&ctr[16 + ev_shard], (unsigned long long)F_EVGRAN);
-                    ev_base = __shfl(nb, 0); ev_left = F_EVGRAN;
-                }
-                if (runs) {
-                    const int32_t q0 = s.a + s.m1, r2 = tpos + s.m1, ref_end = tpos + s.m1 + s.m2;
-                    const unsigned long long slot = ev_base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
-                    const uint32_t rid = (uint32_t)(read_base + (uint64_t)i);
-                    bool firstrun = true;
-                    while (runs) {
-                        const int32_t js = __builtin_ctz(runs);
-                        runs &= runs - 1u;
-                        const int32_t je = js + __builtin_ctz(~(good >> js));
-                        int32_t elo, ehi;
-                        if (je == s.k && s.m2 > 0 && r2 == 0) py_slice(q0 + js, q0 + je + 1, (int32_t)lseq, elo, ehi);   // A:735-736
-                        else py_slice(q0 + js - 1, q0 + je, (int32_t)lseq, elo, ehi);              // A:738
-                        int32_t ins_pos = je == s.k ? r2 : ref_end;                                // A:742 / A:739-740
-                        ins_pos = ins_pos - 1 > 0 ? ins_pos - 1 : 0;                               // A:744
-                        const bool inside = (uint32_t)ins_pos < G;
-                        if (!inside) bad_extra = true;
-                        if (firstrun) {
-                            if ((long long)slot < eb.cap) ev_list[slot] = inside ? amp_ins_event{ins_pos, rid, elo, ehi} : amp_ins_event{-1, 0u, 0, 0};
-                            if (inside) {
-                                const uint32_t d = (uint32_t)(ins_pos - bw_base);
-                                if (d < (uint32_t)F_BW) lds_add_nt(bwin + 5 * F_BW + d, 1u);
-                                else atomicAdd(&eb.ins_at[ins_pos], 1u);
-                            }
-                        } else if (inside) {
-                            eb.record(ins_pos, rid, elo, ehi);
-                        }
-                        firstrun = false;
-                    }
-                }
-                ev_base += total; ev_left -= total;
-            }
-        }
-        F7_T(6);
-        uint32_t redo = 0;                        // pieces (slots) the careful loop has to do; bit F5_NP = group B
-        // group B: the part of the second segment that shares a piece with the first
-        const int32_t jstar = (qb1 - 1) & ~15;                       // the piece that holds the first segment's last base
-        const bool has_b = two & mine & (jstar + 16 > qa2) & (qb2 > qa2);
-        const int32_t xbe = qb2 < jstar + 16 ? qb2 : jstar + 16;
-        const int32_t jb = g_b + (int32_t)phi;
-        // The bases go into the wave's packed window, F_PW positions from pw_base; a tile whose reads lie further apart (the
-        // step from one pile of reads to the next) is counted in PASSES: fold, re-anchor at the first lane left.
-        const int32_t end_pos = two ? pos2 + s.m2 : tpos + s.m1;                   // one past the last counted position
-        const lds_u8 *const lsrow = sst + (int32_t)g.srow - (int32_t)(phi >> 1);
-        // The packed bases of all of the lane's pieces are read BEFORE the first add: LDS operations of a wave complete in order, so a read
-        // behind the sixteen adds of a piece waits for every one of them (the compiler cannot see the adds and waits with lgkmcnt(0)):
-        // read piece by piece, the counting loop drained the LDS queue once per slot.
-        uint2 sqv[F7_SLOTS];
-#pragma unroll
-        for (int k = 0; k < F7_SLOTS; ++k) {
-            uint32_t p = (uint32_t)k + rot;
-            p = p >= np ? p - np : p;
-            const lds_u8 *sp = lsrow + (pbase + ((uint32_t)k < np ? p : np - 1u)) * 8u;
-            sqv[k] = make_uint2(*(const lds_u32 *)sp, *(const lds_u32 *)(sp + 4));
-        }
-        bool todo = counted;
-        for (bool first_pass = true;; first_pass = false) {
-            const unsigned long long tm = __ballot(todo);
-            if (!tm) break;
-            const int lead = __builtin_ctzll(tm);
-            if (!first_pass) {
-                fold();
-                const int32_t lead_pos = __builtin_amdgcn_readlane(pos, lead);
-                pw_base = (lead_pos < 16 ? 0 : lead_pos - 16) & ~15; pw_tiles = 1;
-                pw_lim = (int64_t)G - pw_base >= (int64_t)F5_PW ? (uint32_t)F5_PW : (uint32_t)(G > (uint32_t)pw_base ? G - (uint32_t)pw_base : 0u);
-            }
-            const int32_t lim16 = (int32_t)pw_lim - 16;
-            const bool fits = (tpos - pw_base >= 16) & (end_pos - pw_base + 16 <= (int32_t)pw_lim);
-            const bool now = todo & (fits | (lane == lead));
-            const int32_t a1 = now ? qa1 : 0, b1 = now ? qb1 : 0, a2 = now ? qa2 : 0, b2 = now ? qb2 : 0;
-            const int32_t dbase1 = tpos - pw_base - qa1, dbase2 = pos2 - pw_base - qa2;
-            if (__ballot(has_b & now)) {
-                const lds_u8 *sp = sst + g.srow + (uint32_t)(g_b >> 1);
-                const uint2 sq = make_uint2(*(const lds_u32 *)sp, *(const lds_u32 *)(sp + 4));
-                const uint32_t mB = (has_b & now) ? okB & range_bits16(qa2 - jb, xbe - jb) : 0u;
-                redo |= count5(sq, mB, dbase2 + jb, lim16) << F5_NP;
-            }
-#pragma unroll
-            for (int k = 0; k < F7_SLOTS; ++k) {
-                if (!((live >> k) & 1u) || (AMP_F5_ABL & 2)) continue;
-                uint32_t p = (uint32_t)k + rot;
-                p = p >= np ? p - np : p;
-                p = (uint32_t)k < np ? pbase + p : 4096u;
-                const int32_t j0 = (int32_t)(p * 16u);
-                const bool second = j0 >= qb1;                              // a piece behind the first segment belongs to the second
-                const uint2 sq = sqv[k];
-                const uint32_t rng = range_bits16((second ? a2 : a1) - j0, (second ? b2 : b1) - j0);
-                redo |= count5(sq, fo[k] & rng, (second ? dbase2 : dbase1) + j0, lim16) << k;
-            }
-            todo = todo & !now;
-        }
-        F7_T(7);
-        bool want_status = bad_extra;
-        if (__ballot(redo != 0u)) {
-            // careful loop (rare): bases of the flagged pieces one by one, straight from memory into the 32-bit counters
-            if (redo) {
-                const uint8_t *qrow = rd.qual + (int64_t)o8 * 8;
-                const uint8_t *srow = rd.seq + (int64_t)o8 * 4;
-                const int32_t a1 = qa1 - (int32_t)phi, b1 = qb1 - (int32_t)phi, a2 = qa2 - (int32_t)phi, b2 = qb2 - (int32_t)phi;   // query indices
-                auto careful = [&](int32_t x0, int32_t x1, int32_t qa_q, int32_t rp0) {
-                    for (int32_t q = x0; q < x1; ++q) {
-                        if ((int32_t)qrow[q] < mq) continue;
-                        const uint32_t sb = srow[q >> 1];
-                        const uint32_t col = col_of_code((q & 1) ? (sb & 15u) : (sb >> 4));
-                        const int32_t rp = rp0 + (q - qa_q);
-                        const uint32_t d = (uint32_t)(rp - bw_base);
-                        if (col > 4u || (uint32_t)rp >= G) want_status = true;
-                        else if (d < (uint32_t)F_BW && col < (uint32_t)F_NPL) lds_add_nt(bwin + col * F_BW + d, 1u);
-                        else atomicAdd(&counts[(size_t)rp * AMP_NSYM + col], 1u);
-                    }
-                };
-                for (int k = 0; k < F5_NP; ++k) {
-                    if (!((redo >> k) & 1u)) continue;
-                    uint32_t p = (uint32_t)k + rot;
-                    p = pbase + (p >= np ? p - np : p);
-                    const int32_t j0 = (int32_t)(p * 16u) - (int32_t)phi;
-                    const bool second = j0 + (int32_t)phi >= qb1;
-                    const int32_t sa = second ? a2 : a1, sb_ = second ? b2 : b1;
-                    careful(j0 < sa ? sa : j0, j0 + 16 < sb_ ? j0 + 16 : sb_, sa, second ? pos2 : tpos);
-                }
-                if ((redo >> F5_NP) & 1u) careful(a2, xbe - (int32_t)phi, a2, pos2);
-            }
-        }
-        // ---- hand-over to the general pass: the block's segment of the list -----------------------------------------------
-        {
-            if (pair) want_status |= __builtin_amdgcn_update_dpp(0, (int)want_status, 0xB1, 0xF, 0xF, true) != 0;      // (either lane of the read)
-            const bool status_only = !general & counted & want_status;        // a base could not be counted: exact status wanted
-            const bool has = (general | status_only) & mine;
-            const unsigned long long m = __ballot(has);
-            if (m) {
-                uint32_t base = 0;
-                if (lane == 0) base = __hip_atomic_fetch_add((lds_u32 *)&s_gcur, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                if (has) glist[(size_t)rb + base + __popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)i | (status_only ? GL_STATUS_ONLY : 0u);
-            }
-        }
-        // ---- next tile ------------------------------------------------------------------------------------------------
-        h0 = h1; h1 = h2; g0 = g1; sh0 = sh1;
-        tk0 = tk1; tk1 = tk2; tk2 = tk3; tk3 = tk4;
-#ifdef AMP_F7_STAMPS
-        ++f7_turns;
-#endif
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // (the loads issued for a tile that does not exist)
-#ifdef AMP_F7_STAMPS
-    if (lane == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&ctr[8 + k], f7_t[k]); atomicAdd(&ctr[6], (unsigned long long)f7_turns); }
-#endif
-    pad_events();
-    if (pw_tiles && n_tb) fold();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int i = tid; i < F_BPL * F_BW; i += F5_WAVES * 64) {
-        const uint32_t v = bwin[i];
-        if (v) {
-            const int pl = i / F_BW, d = i - pl * F_BW;
-            const uint32_t p = (uint32_t)(bw_base + d);
-            if (p < G) {
-                if (pl < F_NPL) atomicAdd(&counts[(size_t)p * AMP_NSYM + pl], v);
-                else if (pl == 4) atomicAdd(&counts[(size_t)p * AMP_NSYM + 5], v);      // '-'
-                else atomicAdd(&eb.ins_at[p], v);
-            }
-        }
-    }
-    if (n_err) atomicAdd(&ctr[2], (unsigned long long)n_err);
-    if (tid == 0) { gcnt[blockIdx.x] = s_gcur; if (s_gcur) eb.ctr[29] = (unsigned long long)P.epoch; }      // (every block writes the same value)
-}
-
-
-static inline FastGrid fast7_grid(int64_t n_reads, int n_cu) {
-    int64_t rpb = (n_reads + (int64_t)n_cu - 1) / (int64_t)n_cu;
-    rpb = ((rpb + 63) / 64) * 64;
-    if (rpb < 2 * F7_WAVES * 64) rpb = 2 * F7_WAVES * 64;
-    return FastGrid{(n_reads + rpb - 1) / rpb, rpb};
+template <int W>
+__global__ void __launch_bounds__(F7_WAVES * 64, 2)
+k_fast7(F_ARGS, int32_t pad19, uint32_t *clist) {      // (individual arguments, like k_fast: see the note at F_ARGS)
+    __shared__ uint32_t s_nb[F7_NBIN];
+    f5_tiles<W, F7_REP, F7_PW>(F7Lists{clist, (lds_u32 *)s_nb}, F_ARGS_FWD);
 }
 
 // clist: 2 * grid * rpb words of scratch (the blocks' bin lists)

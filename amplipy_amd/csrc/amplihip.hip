@@ -1109,7 +1109,7 @@ static int launch_reads(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base,
     const int variant = kv >= 5 ? 4 : kv;          // (5 and 6 differ from 4 in the fast kernel only)
     const TileGrid tg = tile_grid(n, c->n_cu);
     const int fast_cus = std::max(1, c->n_cu / c->cu_share);
-    const FastGrid fg = kv == 7 ? fast7_grid(n, fast_cus) : kv == 6 ? fast6_grid(n, fast_cus) : kv == 5 ? fast5_grid(n, fast_cus, f5) : fast_grid(n, fast_cus);
+    const FastGrid fg = kv == 7 ? fast5_grid(n, fast_cus, F7_WAVES) : kv == 6 ? fast6_grid(n, fast_cus) : kv == 5 ? fast5_grid(n, fast_cus, f5.waves) : fast_grid(n, fast_cus);
     // scratch: [CIGAR ping-pong slots][deferred list][list counts, debug words][variant 3 hand-over][outputs the caller
     // did not ask for but the second pass reads][variant 4: per-block lists, their counts, the dense list, geometry]
     // general pass of variant 4: at most four blocks per CU (its list is usually a tenth of the batch; blocks without

@@ -427,7 +427,7 @@ def test_function_level_seams_replay_the_named_cases():
     assert tot == 10 and [a[2] for a in alleles] == ["T", "AT", "A", "-"] and alleles[0][1] == 0.3
 
 
-@pytest.mark.parametrize("seed,mq,w,off,lmin,lmax", [(61, 20, 4, 0, 160, 304), (62, 20, 4, 1, 100, 200), (63, 10, 4, 0, 240, 304), (64, 30, 3, 2, 60, 304), (65, 20, 4, 0, 250, 250)])
+@pytest.mark.parametrize("seed,mq,w,off,lmin,lmax", [(61, 20, 4, 0, 160, 304), (62, 20, 4, 1, 100, 200), (63, 10, 4, 0, 240, 304), (64, 30, 3, 2, 60, 304), (65, 20, 4, 0, 250, 250), (66, 20, 7, 1, 160, 304), (67, 20, 6, 0, 100, 304)])
 def test_reads_of_up_to_304_bases_with_one_indel(runner, seed, mq, w, off, lmin, lmax):
     """The second-generation fast kernel (amp_fast5.hpp, branch-free closed forms of amp_bf.hpp) takes reads of up to 304
     bases and runs in three builds chosen by the batch's mean padded read length (runs of 9.7 / 13.3 / 19.5 KB per tile,
@@ -488,7 +488,7 @@ def test_reads_of_up_to_304_bases_with_one_indel(runner, seed, mq, w, off, lmin,
         assert left < 0.1 * good2.n, (left, good2.n)
 
 
-@pytest.mark.parametrize("seed,mq,w,off", [(41, 20, 4, 0), (42, 10, 1, 2), (43, 30, 8, 1), (44, 0, 3, 0), (45, 25, 6, 3), (46, 20, 2, 0)])
+@pytest.mark.parametrize("seed,mq,w,off", [(41, 20, 4, 0), (42, 10, 1, 2), (43, 30, 8, 1), (44, 0, 3, 0), (45, 25, 6, 3), (46, 20, 2, 0), (47, 20, 7, 2)])
 def test_short_reads_with_one_indel(runner, seed, mq, w, off):
     """The shapes the fast kernel does in closed form (amp_fast.hpp / Cig2 in amp_read.hpp): reads of up to 152 bases with one
     match op or two around ONE insertion / deletion, with or without soft clips at the ends, dense primer tables so that the clips of A:450-558 and A:589-686 often

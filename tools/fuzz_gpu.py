@@ -18,7 +18,7 @@ runners = {v: GpuRunner(variant=v) for v in (1, 2, 3, 4, 5, 6, 7)}
 t0 = time.time(); n_cmp = 0
 for seed in range(first, first + count):
     rng = np.random.default_rng(seed)
-    mq = int(rng.choice([0, 2, 13, 20, 30, 41])); w = int(rng.choice([1, 2, 3, 4, 5, 8, 9, 30])); off = int(rng.integers(0, 8))
+    mq = int(rng.choice([0, 2, 13, 20, 30, 41])); w = int(rng.choice([1, 2, 3, 4, 5, 6, 7, 8, 9, 30])); off = int(rng.integers(0, 8))
     mn, mx, mpl = oracle.find_overlapping_primers(g.size, pr, off)
     kind = seed % 4
     if kind == 0:
