@@ -120,7 +120,7 @@ def native_parts(input_fn, rank=0, world=1, part_bytes=None):
     return per_rank * world, per_rank * rank, per_rank * (rank + 1)
 
 
-def open_native_bam(input_fn, output_fn, rank=0, world=1):
+def open_native_bam(input_fn, output_fn, rank=0, world=1, device=0):
     """(NativeInput, BamWriter or None) when the native codec can serve this run: BAM file in, and BAM file
     (or nothing) out.  None otherwise (SAM text, stdin / stdout): the Python codec handles those.
     Same checks and messages as open_alignment_files."""
@@ -136,8 +136,10 @@ def open_native_bam(input_fn, output_fn, rank=0, world=1):
         from . import bam_native
         first = src.first_part()
         hdr = bamio.Header(first.header_text, first.references).with_amplipy_pg(VERSION, " ".join(sys.argv))
-        # zlib's default level like htslib; AMPLIPY_BAM_LEVEL=1 trades file size for speed
-        writer = bam_native.BamWriter(output_fn, hdr.text, first, level=int(os.environ.get("AMPLIPY_BAM_LEVEL", "-1")))
+        # zlib's default level like htslib; AMPLIPY_BAM_LEVEL=1 trades file size for speed; AMPLIPY_GPU_DEFLATE=1 hands the blocks'
+        # DEFLATE streams to the HIP encoder on this rank's device
+        writer = bam_native.BamWriter(output_fn, hdr.text, first, level=int(os.environ.get("AMPLIPY_BAM_LEVEL", "-1")),
+                                      gpu_deflate=os.environ.get("AMPLIPY_GPU_DEFLATE", "0") not in ("", "0"), device=device)
     return src, writer
 
 
@@ -364,7 +366,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if run_trim:
             print_log("Input untrimmed SAM/BAM: %s" % untrimmed_reads_fn)
             print_log("Output trimmed SAM/BAM: %s" % trimmed_reads_fn)
-            native = open_native_bam(untrimmed_reads_fn, trimmed_reads_fn, rank, world)
+            native = open_native_bam(untrimmed_reads_fn, trimmed_reads_fn, rank, world, device)
             if native is None:
                 reader, writer = open_alignment_files(untrimmed_reads_fn, trimmed_reads_fn)
         else:

@@ -16,7 +16,10 @@ EXPORTS = [
     "ampbam_version", "ampbam_strerror", "ampbam_open", "ampbam_close", "ampbam_last_error", "ampbam_n_records",
     "ampbam_header_text", "ampbam_n_refs", "ampbam_ref", "ampbam_decode", "ampbam_writer_open", "ampbam_write_rows",
     "ampbam_writer_close", "ampbam_writer_header_bytes", "ampbam_write_batch", "ampbam_open_range", "ampbam_open_range_at", "ampbam_part_range", "ampbam_crc32", "ampbam_inflate_raw",
+    "ampbam_writer_set_deflater", "ampbam_writer_deflater_stats",
 ]
+# ampbam_deflate_fn of include/ampbam.h
+DEFLATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_uint32))
 _LIB = None
 
 
@@ -46,6 +49,8 @@ def load():
         L.ampbam_crc32.argtypes = [C.c_void_p, C.c_int64]
         L.ampbam_close.restype = None
         L.ampbam_close.argtypes = [C.c_void_p]
+        L.ampbam_writer_set_deflater.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ampbam_writer_deflater_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -127,9 +132,13 @@ class BamFile:
 class BamWriter:
     """Writes rows of decoded batches of ``src`` with new positions / CIGARs (AmpliPy.py:911)."""
 
-    def __init__(self, path, header_text, src, level=-1, threads=0):
+    def __init__(self, path, header_text, src, level=-1, threads=0, gpu_deflate=False, device=0):
+        """gpu_deflate: the blocks' DEFLATE streams come from the HIP encoder of libamplihip on ``device`` (amp_deflate_blocks; the
+        header's blocks, and any block the device hands back, from the host codec at ``level``).  The library must load and the
+        device must be there: asking for it without one is an error, not a silent host run."""
         self.L = load()
         self.src = src
+        self._deflater = None
         h = C.c_void_p()
         text = header_text.encode("ascii")
         rc = self.L.ampbam_writer_open(os.fsencode(path), text, C.c_int64(len(text)), src.h, C.c_int(level), C.c_int(threads), C.byref(h))
@@ -139,6 +148,28 @@ class BamWriter:
         self.L.ampbam_writer_header_bytes.restype = C.c_int64
         self.path = path
         self.header_bytes = int(self.L.ampbam_writer_header_bytes(h))      # the header has BGZF blocks of its own: their size in the file
+        if gpu_deflate:
+            from . import lib
+            G = lib.load()
+            if G.amp_device_count() <= int(device):
+                self.close()
+                raise AmpBamError("gpu_deflate: no GPU device %d" % int(device))
+            # the C function itself is the callback (no Python in the flush path); `user` is the device number
+            self._deflater = (C.cast(G.amp_deflate_blocks_cb, C.c_void_p), C.c_int32(int(device)))
+            self.set_deflater(self._deflater[0], C.byref(self._deflater[1]))
+
+    def set_deflater(self, fn, user=None):
+        """ampbam_writer_set_deflater: ``fn`` an ampbam_deflate_fn (a DEFLATE_FN object, which the caller keeps alive, or the address
+        of a C function) or None."""
+        rc = self.L.ampbam_writer_set_deflater(self.h, fn, user)
+        if rc:
+            raise AmpBamError("set_deflater: %s" % self.L.ampbam_strerror(rc).decode())
+
+    def deflater_stats(self):
+        """(blocks whose stream came from the deflater, blocks the codec compressed itself although one was set, failed calls)."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self.L.ampbam_writer_deflater_stats(self.h, C.byref(a), C.byref(b), C.byref(c))
+        return int(a.value), int(b.value), int(c.value)
 
     def write_rows(self, src, src_index, keep, new_pos, new_ncig, new_cig_off, new_cig):
         """Rows of a batch decoded from ``src`` (the input file, or the piece of it the batch came from; None: the file the

@@ -318,6 +318,9 @@ struct ampbam_writer {
     Bytes pend;                             // uncompressed bytes not yet written (no zero fill on growth)
     Bytes comp;                             // compressed blocks of one flush, at a fixed stride
     int64_t header_bytes = 0;               // compressed bytes of the header's own blocks
+    ampbam_deflate_fn deflater = nullptr;   // ampbam_writer_set_deflater: another encoder for the blocks' DEFLATE streams
+    void *deflater_user = nullptr;
+    int64_t blocks_external = 0, blocks_fallback = 0, deflater_failed = 0;
     std::string err;
 };
 
@@ -828,15 +831,34 @@ static int flush_blocks(ampbam_writer *w, bool all) {
     if (!w->comp.resize(nblk * STRIDE)) return AMPBAM_ENOMEM;
     std::vector<uint32_t> out_len(nblk, 0);
     std::atomic<int> bad{0};
+    const size_t room = STRIDE - 18 - 8;
+    // a deflater that was set gets all blocks of the flush in one call; ext_len[k] != 0: block k's stream is in place
+    std::vector<uint32_t> ext_len;
+    if (w->deflater) {
+        ext_len.assign(nblk, 0);
+        const int64_t n_in = (int64_t)std::min(w->pend.size(), nblk * BS);
+        const size_t ext_room = 65536 - 26;               // what a BGZF block can hold
+        if (w->deflater(w->deflater_user, w->pend.data(), n_in, (int32_t)BS, w->comp.data() + 18, (int64_t)STRIDE, (int32_t)ext_room, ext_len.data()) != 0) {
+            std::fill(ext_len.begin(), ext_len.end(), 0u);
+            ++w->deflater_failed;
+        }
+        for (size_t k = 0; k < nblk; ++k) {
+            if (ext_len[k] > ext_room) ext_len[k] = 0;
+            if (ext_len[k]) ++w->blocks_external; else ++w->blocks_fallback;
+        }
+    }
     const int64_t grain = 4;
     parallel_for(w->n_threads, ((int64_t)nblk + grain - 1) / grain, [&](int64_t ch) {
-        void *lc = libdeflate().ok ? libdeflate().alloc_c(w->level < 0 ? 6 : (w->level == 0 ? 1 : w->level)) : nullptr;
+        bool own = ext_len.empty();                       // does this chunk of blocks need the codec's own encoder?
+        for (int64_t k = ch * grain; !own && k < std::min<int64_t>((int64_t)nblk, (ch + 1) * grain); ++k) own = ext_len[(size_t)k] == 0;
+        void *lc = own && libdeflate().ok ? libdeflate().alloc_c(w->level < 0 ? 6 : (w->level == 0 ? 1 : w->level)) : nullptr;
         for (int64_t k = ch * grain; k < std::min<int64_t>((int64_t)nblk, (ch + 1) * grain); ++k) {
             const size_t off = (size_t)k * BS, len = std::min(BS, w->pend.size() - off);
             uint8_t *o = w->comp.data() + (size_t)k * STRIDE;
-            const size_t room = STRIDE - 18 - 8;
             size_t clen = 0;
-            if (lc) {
+            if (!ext_len.empty() && ext_len[(size_t)k]) {
+                clen = ext_len[(size_t)k];
+            } else if (lc) {
                 clen = libdeflate().compress(lc, w->pend.data() + off, len, o + 18, room);
             } else {
                 z_stream zs;
@@ -900,6 +922,20 @@ int ampbam_writer_open(const char *path, const char *header_text, int64_t header
 }
 
 int64_t ampbam_writer_header_bytes(const ampbam_writer *w) { return w ? w->header_bytes : -1; }
+
+int ampbam_writer_set_deflater(ampbam_writer *w, ampbam_deflate_fn fn, void *user) {
+    if (!w) return AMPBAM_EINVAL;
+    w->deflater = fn; w->deflater_user = fn ? user : nullptr;
+    return AMPBAM_OK;
+}
+
+int ampbam_writer_deflater_stats(const ampbam_writer *w, int64_t *blocks_external, int64_t *blocks_fallback, int64_t *failed_calls) {
+    if (!w) return AMPBAM_EINVAL;
+    if (blocks_external) *blocks_external = w->blocks_external;
+    if (blocks_fallback) *blocks_fallback = w->blocks_fallback;
+    if (failed_calls) *failed_calls = w->deflater_failed;
+    return AMPBAM_OK;
+}
 
 int ampbam_write_rows(ampbam_writer *w, const ampbam_file *src, int64_t n_rows, const int64_t *src_index,
                       const uint8_t *keep, const int32_t *new_pos, const uint32_t *new_ncig,

@@ -129,6 +129,19 @@ int64_t ampbam_writer_header_bytes(const ampbam_writer *w);
 int ampbam_write_batch(ampbam_writer *w, int64_t n, const int32_t *pos, const uint16_t *flag, const int32_t *tlen, const uint32_t *lseq,
                        const uint64_t *cig_off, const uint32_t *cig, const uint64_t *seq_off, const uint8_t *seq, const uint8_t *qual,
                        uint64_t name_base);
+/* Another DEFLATE encoder for the writer's blocks (a GPU's, say: amp_deflate_blocks_cb of include/amplihip.h has this signature;
+ * this library itself stays free of GPU code).  From now on every flush calls fn ONCE for all its blocks: n_bytes of `in` are
+ * ceil(n_bytes / block_bytes) chunks of block_bytes (the last may be shorter); chunk k's complete raw DEFLATE stream (RFC 1951)
+ * goes to out + k * out_stride, at most out_room bytes, its length to out_len[k].  CRC-32, BGZF header and trailer stay with
+ * the writer's threads.  A block whose out_len is 0 or larger than out_room, and every block of a call that returns non-zero,
+ * is compressed by the codec itself as before (counted: ampbam_writer_deflater_stats), so a failing encoder costs time, never
+ * the file.  fn == NULL: the codec's own encoder again.  Without this call the writer's bytes are what they always were. */
+typedef int (*ampbam_deflate_fn)(void *user, const uint8_t *in, int64_t n_bytes, int32_t block_bytes,
+                                 uint8_t *out, int64_t out_stride, int32_t out_room, uint32_t *out_len);
+int ampbam_writer_set_deflater(ampbam_writer *w, ampbam_deflate_fn fn, void *user);
+/* Blocks written so far with a stream of the deflater / by the codec itself although a deflater was set / calls of the
+ * deflater that returned non-zero (any pointer may be NULL). */
+int ampbam_writer_deflater_stats(const ampbam_writer *w, int64_t *blocks_external, int64_t *blocks_fallback, int64_t *failed_calls);
 /* Flushes, writes the BGZF end-of-file block, closes the file and frees the writer. */
 int ampbam_writer_close(ampbam_writer *w);
 

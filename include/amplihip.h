@@ -358,6 +358,28 @@ int amp_call_compact_begin(amp_ctx *ctx, const amp_call_params *params);
 int amp_event_strings(amp_ctx *ctx, const amp_dev_reads *reads, uint64_t read_base, int64_t n_events,
                       const amp_ins_event *events, const uint64_t *off, uint8_t *text);
 
+/* ---- DEFLATE of BGZF blocks (the writer's opt-in device codec) ----------
+ * n = ceil(n_bytes / block_bytes) consecutive chunks of block_bytes (1..0xFF00; the last may be shorter) of `in` become n
+ * complete raw DEFLATE streams (RFC 1951, one final block each, dynamic Huffman codes or stored): chunk k's stream at
+ * out + k * out_stride, its length in out_len[k].  Nothing is written beyond out + k * out_stride + out_room; a chunk
+ * whose stream does not fit out_room -- not even as a stored block of chunk + 5 bytes -- gets out_len[k] = 0 and the caller
+ * compresses it some other way.  Framing (gzip / BGZF header, CRC-32, ISIZE) is the caller's.
+ * Needs no amp_ctx: the device's stream and staging buffers of this entry point belong to the library, are made on first
+ * use and kept for the process.  Calls for one device are serialised inside; a call may run on any thread, also while
+ * another thread is inside amp_process_batch (a stream of its own, no synchronisation of the device).
+ * in / out / out_len are host memory; n_bytes == 0 is no chunk and AMP_OK. */
+int amp_deflate_blocks(int device, const uint8_t *in, int64_t n_bytes, int32_t block_bytes,
+                       uint8_t *out, int64_t out_stride, int32_t out_room, uint32_t *out_len);
+/* The same on device memory, enqueued on `stream` (a hipStream_t; NULL: the library's stream of that device) without waiting:
+ * the kernel alone.  Any alignment of in, out and out_stride works. */
+int amp_deflate_blocks_device(int device, const uint8_t *in, int64_t n_bytes, int32_t block_bytes,
+                              uint8_t *out, int64_t out_stride, int32_t out_room, uint32_t *out_len, void *stream);
+/* Waits for the library's DEFLATE stream of `device` (what a NULL stream above runs on). */
+int amp_deflate_sync(int device);
+/* Signature of ampbam_writer_set_deflater (include/ampbam.h): `user` points to an int32_t holding the device. */
+int amp_deflate_blocks_cb(void *user, const uint8_t *in, int64_t n_bytes, int32_t block_bytes,
+                          uint8_t *out, int64_t out_stride, int32_t out_room, uint32_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,506 @@
+"""The opt-in device DEFLATE encoder of the BAM writer: amp_deflate_blocks (amplipy_amd/csrc/amp_deflate.hip), the hook of the host
+codec that takes it (ampbam_writer_set_deflater), BamWriter(gpu_deflate=True) and AMPLIPY_GPU_DEFLATE=1 of the command line.
+The hook's fallback tests and the run of the encoder's phases on the host need no GPU; everything else does."""
+import ctypes as C
+import gzip
+import os
+import struct
+import subprocess
+import sys
+import zlib
+
+import numpy as np
+import pytest
+
+from amplipy_amd import bam_native, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BS = 0xFF00
+GUARD = 96
+PATTERN = 0xA5
+
+
+# ---- plumbing -----------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def scheme():
+    g = synth.make_genome()
+    primers, amps = synth.make_artic_scheme()
+    return g, primers, amps
+
+
+def _seed_file(tmp_path, batch, g):
+    """A tiny BAM of the Python codec that lends its header and reference dictionary."""
+    from tools.e2e_legs import write_bam
+    seed = str(tmp_path / "seed.bam")
+    write_bam(seed, batch.slice(0, 8), g.size)
+    return bam_native.BamFile(seed)
+
+
+def _synthetic_bam(tmp_path, scheme, n_reads, name="in.bam", seed=42, **writer_args):
+    g, _, amps = scheme
+    b = synth.make_amplicon_batch(g, amps, n_reads, seed=seed)
+    sf = _seed_file(tmp_path, b, g)
+    path = str(tmp_path / name)
+    w = bam_native.BamWriter(path, sf.header_text, sf, **writer_args)
+    w.write_batch(b)
+    stats = w.deflater_stats()
+    w.close(); sf.close()
+    return path, stats
+
+
+def _members(path):
+    """[(offset, block size, compressed bytes, crc, isize)] of a BGZF file, with the format checks of SAMv1 4.1."""
+    raw = open(path, "rb").read()
+    out, off = [], 0
+    while off < len(raw):
+        id1, id2, cm, flg, _mt, _xfl, _os, xlen = struct.unpack_from("<BBBBIBBH", raw, off)
+        assert (id1, id2, cm, flg, xlen) == (31, 139, 8, 4, 6)
+        assert raw[off + 12:off + 16] == b"BC\x02\x00"
+        bsize = struct.unpack_from("<H", raw, off + 16)[0] + 1
+        assert bsize <= 65536 and off + bsize <= len(raw)
+        crc, isize = struct.unpack_from("<II", raw, off + bsize - 8)
+        out.append((off, bsize, raw[off + 18:off + bsize - 8], crc, isize))
+        off += bsize
+    assert off == len(raw)
+    return raw, out
+
+
+def _check_bgzf(path):
+    """Every member inflates to ISIZE bytes with the CRC it states, the file ends with the EOF block; returns the inflated bytes."""
+    raw, mem = _members(path)
+    assert raw.endswith(bam_native.BGZF_EOF)
+    data = bytearray()
+    for _off, _bsize, cdata, crc, isize in mem:
+        d = zlib.decompressobj(-15)
+        block = d.decompress(cdata)
+        assert d.eof and d.unused_data == b"" and len(block) == isize and zlib.crc32(block) == crc
+        data += block
+    assert bytes(data) == gzip.open(path).read()          # readable as concatenated gzip members
+    return bytes(data)
+
+
+def _deflate_blocks(data, block_bytes=BS, room=65536 - 26, device=0, hostsim=None):
+    """amp_deflate_blocks on ``data``: (rc, [stream or None per chunk]); the guard bytes behind every room and the bytes behind
+    every stream must be untouched.  hostsim: the library of the kernel's phases compiled for the host instead."""
+    if hostsim is None:
+        from amplipy_amd import lib
+        L = lib.load()
+        L.amp_deflate_blocks.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        call = lambda *a: L.amp_deflate_blocks(device, *a)
+    else:
+        hostsim.ampdf_hostsim_blocks.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        call = hostsim.ampdf_hostsim_blocks
+    n = len(data)
+    nb = (n + block_bytes - 1) // block_bytes
+    stride = room + GUARD
+    src = np.frombuffer(data, np.uint8) if n else np.zeros(1, np.uint8)
+    out = np.full(max(nb, 1) * stride, PATTERN, np.uint8)
+    lens = np.full(max(nb, 1), 0xFFFFFFFF, np.uint32)
+    rc = call(src.ctypes.data, n, block_bytes, out.ctypes.data, stride, room, lens.ctypes.data)
+    streams = []
+    for k in range(nb):
+        ln = int(lens[k])
+        assert ln <= room, "chunk %d: length %d beyond the room %d" % (k, ln, room)
+        assert (out[k * stride + ln:(k + 1) * stride] == PATTERN).all(), "chunk %d: bytes behind the stream / the room were written" % k
+        streams.append(out[k * stride:k * stride + ln].tobytes() if ln else None)
+    if nb == 0:
+        assert (out == PATTERN).all() and int(lens[0]) == 0xFFFFFFFF
+    return rc, streams
+
+
+def _check_streams(data, streams, block_bytes=BS, allow_none=False):
+    """Every stream inflates, with zlib and with the codec's own decoder, to exactly its chunk and ends at its last byte."""
+    A = bam_native.load()
+    assert len(streams) == (len(data) + block_bytes - 1) // block_bytes
+    for k, s in enumerate(streams):
+        chunk = data[k * block_bytes:(k + 1) * block_bytes]
+        if s is None:
+            assert allow_none, "chunk %d was handed back (out_len 0) although a stored block fits" % k
+            continue
+        d = zlib.decompressobj(-15)
+        got = d.decompress(s)
+        assert d.eof and d.unused_data == b"" and d.unconsumed_tail == b"", "chunk %d: the stream does not end at its last byte" % k
+        assert got == chunk, "chunk %d: zlib inflates other bytes" % k
+        back = C.create_string_buffer(max(len(chunk), 1))
+        assert A.ampbam_inflate_raw(s, len(s), back, len(chunk)) == 0, "chunk %d: the codec's own inflate refuses the stream" % k
+        assert back.raw[:len(chunk)] == chunk
+        if len(s) > 1:                                     # ... and not one byte earlier
+            assert A.ampbam_inflate_raw(s, len(s) - 1, back, len(chunk)) != 0
+
+
+@pytest.fixture(scope="module")
+def bam_image(tmp_path_factory, scheme):
+    """The inflated bytes of a synthetic BAM of 40,000 reads."""
+    path, _ = _synthetic_bam(tmp_path_factory.mktemp("img"), scheme, 40000, level=1)
+    return gzip.open(path).read()
+
+
+def _fibonacci_bytes():
+    """Byte values with Fibonacci frequencies, shuffled: their Huffman tree is 21 deep, so the 15-bit limit has to act."""
+    f = [1, 1]
+    while sum(f) + f[-1] + f[-2] <= BS:
+        f.append(f[-1] + f[-2])
+    vals = np.concatenate([np.full(c, (7 * i + 3) & 0xFF, np.uint8) for i, c in enumerate(f)])
+    np.random.default_rng(1).shuffle(vals)
+    return vals.tobytes()
+
+
+# ---- 1. block level --------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_blocks_of_a_bam_image_round_trip(bam_image):
+    rc, streams = _deflate_blocks(bam_image)
+    assert rc == 0
+    _check_streams(bam_image, streams)
+    total = sum(len(s) for s in streams)
+    print("BAM image: %d bytes -> %d bytes of DEFLATE streams (%.2f x)" % (len(bam_image), total, len(bam_image) / total))
+    assert total < len(bam_image) / 2, "the streams of BAM records are stored or Huffman-only"
+    assert all(s[0] & 7 == 5 for s in streams), "a block of BAM records must be one final block with dynamic codes"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,data", [
+    ("zeros", bytes(3 * BS)),
+    ("one byte", b"Q"),
+    ("short last chunk", bytes(range(256)) * 300 + b"tail"),
+    ("two bytes over", b"ACGT" * (BS // 4) + b"xy"),
+    ("runs", b"a" * 1000 + b"ab" * 700 + b"\x00" * 40000 + b"I" * 258 + b"J" + b"I" * 259 + b"abc" * 5000 + b"z" * 70000),
+    ("fibonacci frequencies", _fibonacci_bytes()),
+    ("text", b"".join(b"read%07d\tACGTACGTTTGACCA\tIIIIIIIIIIIIIII\n" % (i * 7919 % 100000) for i in range(6000))),
+])
+def test_blocks_round_trip(name, data):
+    rc, streams = _deflate_blocks(data)
+    assert rc == 0
+    _check_streams(data, streams)
+    if name in ("zeros", "runs"):
+        assert sum(len(s) for s in streams) < len(data) // 50, "long runs must become long matches"
+
+
+@pytest.mark.gpu
+def test_empty_input_is_no_block():
+    rc, streams = _deflate_blocks(b"")
+    assert rc == 0 and streams == []
+
+
+@pytest.mark.gpu
+def test_incompressible_chunks_are_stored_or_handed_back():
+    data = os.urandom(65536)
+    rc, streams = _deflate_blocks(data)                        # a stored block of 0xFF00 + 5 bytes fits a BGZF block
+    assert rc == 0
+    _check_streams(data, streams)
+    assert len(streams[0]) == BS + 5 and streams[0][0] == 1
+    rc, streams = _deflate_blocks(data, room=4096)             # ... and here it does not: the caller is told so
+    assert rc == 0
+    assert streams[0] is None
+    _check_streams(data, streams, allow_none=True)
+    rc, streams = _deflate_blocks(bytes(BS) + data[:1000], room=600)    # a room that only compressible chunks fit
+    assert rc == 0 and streams[0] is not None and streams[1] is None
+    _check_streams(bytes(BS) + data[:1000], streams, allow_none=True)
+
+
+@pytest.mark.gpu
+def test_random_block_sizes(bam_image):
+    rng = np.random.default_rng(5)
+    sizes = [1, 2, 3, 4, 5, 123, 124, 125, 247, 248, BS - 1, BS] + [int(x) for x in rng.integers(1, BS + 1, size=8)]
+    for bs in sizes:
+        n = min(len(bam_image), max(300, min(24 * bs, 1 << 20)) if bs > 5 else 64 + bs)
+        at = int(rng.integers(0, len(bam_image) - n))
+        data = bam_image[at:at + n]
+        rc, streams = _deflate_blocks(data, block_bytes=bs)
+        assert rc == 0, "block size %d" % bs
+        _check_streams(data, streams, block_bytes=bs)
+
+
+@pytest.mark.gpu
+def test_bad_arguments_are_refused():
+    from amplipy_amd import lib
+    L = lib.load()
+    L.amp_deflate_blocks.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    buf = np.zeros(256, np.uint8); lens = np.zeros(4, np.uint32)
+    assert L.amp_deflate_blocks(0, buf.ctypes.data, 100, BS + 1, buf.ctypes.data, 128, 128, lens.ctypes.data) == -1
+    assert L.amp_deflate_blocks(0, buf.ctypes.data, 100, 0, buf.ctypes.data, 128, 128, lens.ctypes.data) == -1
+    assert L.amp_deflate_blocks(0, buf.ctypes.data, 100, 100, buf.ctypes.data, 64, 128, lens.ctypes.data) == -1     # stride < room
+    assert L.amp_deflate_blocks(0, None, 100, 100, buf.ctypes.data, 128, 128, lens.ctypes.data) == -1
+    assert L.amp_deflate_blocks(99, buf.ctypes.data, 100, 100, buf.ctypes.data, 128, 128, lens.ctypes.data) == -1
+
+
+@pytest.mark.gpu
+def test_device_entry_matches_the_host_entry(bam_image):
+    """amp_deflate_blocks_device on torch tensors (what the timing tool times) gives the streams of the host-pointer entry."""
+    import torch
+    from amplipy_amd import lib
+    L = lib.load()
+    L.amp_deflate_blocks_device.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+    data = bam_image[77:77 + 20 * BS + 999]                     # an odd start: the chunks are not dword-aligned
+    room, stride = 65536 - 26, 65536
+    nb = (len(data) + BS - 1) // BS
+    whole = torch.frombuffer(bytearray(bam_image[:77 + len(data)]), dtype=torch.uint8).cuda()
+    d_out = torch.full((nb * stride,), PATTERN, dtype=torch.uint8, device="cuda")
+    d_len = torch.zeros(nb, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    assert L.amp_deflate_blocks_device(0, whole.data_ptr() + 77, len(data), BS, d_out.data_ptr(), stride, room, d_len.data_ptr(), None) == 0
+    assert L.amp_deflate_sync(0) == 0
+    out = d_out.cpu().numpy(); lens = d_len.cpu().numpy()
+    rc, ref = _deflate_blocks(data)
+    assert rc == 0
+    for k in range(nb):
+        assert out[k * stride:k * stride + int(lens[k])].tobytes() == ref[k]
+        assert (out[k * stride + int(lens[k]):(k + 1) * stride] == PATTERN).all()
+    _check_streams(data, ref)
+
+
+# ---- 2. whole file ---------------------------------------------------------------------------------------------------------------
+def _trim_rows(tmp_path, scheme, n_reads, **writer_args):
+    """Rows of a synthetic BAM re-written with new positions and CIGARs through write_rows (every row kept, its CIGAR turned into
+    one soft clip + one match: what the writer does with a trimmed record, without the GPU engine)."""
+    inp, _ = _synthetic_bam(tmp_path, scheme, n_reads, name="src.bam", level=1)
+    src = bam_native.BamFile(inp)
+    b, _ = src.decode(0, src.n_records)
+    n = b.n
+    keep = np.ones(n, np.uint8); keep[::7] = 0
+    new_ncig = np.full(n, 2, np.uint32)
+    new_cig = np.empty(2 * n, np.uint32)
+    new_cig[0::2] = (3 << 4) | 4
+    new_cig[1::2] = ((b.lseq.astype(np.uint32) - 3) << 4) | 0
+    off = (2 * np.arange(n)).astype(np.uint64)
+    outs = {}
+    for tag, args in writer_args.items():
+        path = str(tmp_path / ("out_%s.bam" % tag))
+        w = bam_native.BamWriter(path, src.header_text, src, **args)
+        for lo in range(0, n, 9000):                          # several flushes
+            hi = min(n, lo + 9000)
+            w.write_rows(None, b.src_index[lo:hi], keep[lo:hi], b.pos[lo:hi] + 3, new_ncig[lo:hi], off[lo:hi], new_cig)
+        stats = w.deflater_stats()
+        hb = w.header_bytes
+        w.close()
+        outs[tag] = (path, stats, hb)
+    src.close()
+    return outs
+
+
+@pytest.mark.gpu
+def test_whole_file_written_with_gpu_deflate(tmp_path, scheme):
+    from tests.test_format_spec import spec_parse_bam
+    outs = _trim_rows(tmp_path, scheme, 40000, gpu=dict(gpu_deflate=True), host=dict(gpu_deflate=False))
+    (gpu, stats, _), (host, hstats, _) = outs["gpu"], outs["host"]
+    assert hstats == (0, 0, 0)
+    assert stats[0] > 100 and stats[1] == 0 and stats[2] == 0, "blocks (device, host, failed calls) = %r" % (stats,)
+    img = _check_bgzf(gpu)
+    assert img == _check_bgzf(host), "the inflated file differs from the host codec's"
+    f = bam_native.BamFile(gpu)
+    text, refs, recs = spec_parse_bam(gpu)
+    assert f.n_records == len(recs) and f.n_records > 30000
+    f.close()
+    assert spec_parse_bam(host) == (text, refs, recs)
+    # the device's streams really are in the file: they are not the host codec's bytes
+    assert open(gpu, "rb").read() != open(host, "rb").read()
+
+
+# ---- 3. command line ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_cli_with_and_without_gpu_deflate(tmp_path, scheme):
+    g, primers, _ = scheme
+    inp, _ = _synthetic_bam(tmp_path, scheme, 60000, level=1)
+    ref = tmp_path / "ref.fas"; ref.write_text(">SYN_REF\n" + synth.genome_string(g) + "\n")
+    bed = tmp_path / "p.bed"; bed.write_text("".join("SYN_REF\t%d\t%d\tp%d\n" % (s, e, i) for i, (s, e, _) in enumerate(primers)))
+    outs = {}
+    for tag, val in (("host", None), ("gpu", "1")):
+        env = dict(os.environ); env.pop("AMPLIPY_GPU_DEFLATE", None)
+        env["AMPLIPY_PART_BYTES"] = str(1 << 20)               # several pieces: several flushes next to the read pass
+        env["PYTHONPATH"] = ROOT + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
+        if val:
+            env["AMPLIPY_GPU_DEFLATE"] = val
+        # the same command line in a directory of its own (the @PG line of the trimmed BAM records the command)
+        cwd = tmp_path / tag; cwd.mkdir()
+        r = subprocess.run([sys.executable, "-m", "amplipy_amd", "aio", "-i", inp, "-p", str(bed), "-r", str(ref), "-ot", "t.bam", "-ov", "v.vcf", "-oc", "c.fas"],
+                           cwd=str(cwd), env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs[tag] = {k: str(cwd / fn) for k, fn in (("t", "t.bam"), ("v", "v.vcf"), ("c", "c.fas"))}
+    a, b = _check_bgzf(outs["host"]["t"]), _check_bgzf(outs["gpu"]["t"])
+    assert len(a) > 1 << 20 and a == b
+    assert open(outs["host"]["v"], "rb").read() == open(outs["gpu"]["v"], "rb").read()
+    assert open(outs["host"]["c"], "rb").read() == open(outs["gpu"]["c"], "rb").read()
+    assert open(outs["host"]["t"], "rb").read() != open(outs["gpu"]["t"], "rb").read(), "the switch changed nothing in the file"
+
+
+# ---- 4. multi-rank join ------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_stitch_of_gpu_deflated_parts(tmp_path, scheme):
+    g, _, amps = scheme
+    b = synth.make_amplicon_batch(g, amps, 30000, seed=9)
+    sf = _seed_file(tmp_path, b, g)
+    whole = str(tmp_path / "whole.bam")
+    w = bam_native.BamWriter(whole, sf.header_text, sf, gpu_deflate=True); w.write_batch(b); w.close()
+    parts = []
+    for k, (lo, hi) in enumerate(((0, 13000), (13000, 30000))):
+        path = str(tmp_path / ("part%d.bam" % k))
+        w = bam_native.BamWriter(path, sf.header_text, sf, gpu_deflate=True)
+        w.write_batch(b.slice(lo, hi), name_base=lo)
+        assert w.deflater_stats()[0] > 0
+        raw_hdr = w.header_bytes
+        w.close()
+        # header_bytes is where the header's own blocks end: a member starts there, and what is in front inflates to the header alone
+        offs = [m[0] for m in _members(path)[1]]
+        assert raw_hdr in offs
+        parts.append((path, raw_hdr))
+    sf.close()
+    joined = str(tmp_path / "joined.bam")
+    bam_native.stitch_bam_parts(joined, parts)
+    assert _check_bgzf(joined) == _check_bgzf(whole)
+    f = bam_native.BamFile(joined); assert f.n_records == 30000; f.close()
+
+
+# ---- 5. the hook, without a GPU ------------------------------------------------------------------------------------------------------
+def _hook_file(tmp_path, scheme, tag, fn, snap=lambda: None):
+    """Returns (path, the writer's deflater statistics just before close, snap() at that moment): close flushes once more."""
+    g, _, amps = scheme
+    b = synth.make_amplicon_batch(g, amps, 6000, seed=3)
+    sf = _seed_file(tmp_path, b, g)
+    path = str(tmp_path / ("%s.bam" % tag))
+    w = bam_native.BamWriter(path, sf.header_text, sf, level=1)
+    cb = bam_native.DEFLATE_FN(fn) if fn is not None else None
+    if cb is not None:
+        w.set_deflater(cb, None)
+    for lo in range(0, b.n, 2500):
+        w.write_batch(b.slice(lo, min(b.n, lo + 2500)), name_base=lo)
+    stats, at_stats = w.deflater_stats(), snap()
+    w.close(); sf.close()
+    return path, stats, at_stats
+
+
+def test_hook_falls_back_when_the_deflater_fails(tmp_path, scheme):
+    calls = []
+
+    def failing(user, inp, n_bytes, block_bytes, out, stride, room, out_len):
+        calls.append(n_bytes)
+        return -1
+    plain, pstats, _ = _hook_file(tmp_path, scheme, "plain", None)
+    path, stats, n_calls = _hook_file(tmp_path, scheme, "failing", failing, lambda: len(calls))
+    assert pstats == (0, 0, 0)
+    assert n_calls and len(calls) == n_calls + 1 and stats[0] == 0 and stats[1] > 0 and stats[2] == n_calls
+    assert open(path, "rb").read() == open(plain, "rb").read()     # the codec's own encoder wrote every block: the same file
+    _check_bgzf(path)
+
+
+def test_hook_takes_streams_and_compresses_the_blocks_it_is_not_given(tmp_path, scheme):
+    seen = {"blocks": 0, "given": 0, "oversize": 0, "args": set()}
+
+    def every_second(user, inp, n_bytes, block_bytes, out, stride, room, out_len):
+        seen["args"].add((block_bytes, room, stride >= room))
+        nb = (n_bytes + block_bytes - 1) // block_bytes
+        for k in range(nb):
+            chunk = C.string_at(inp + k * block_bytes, min(block_bytes, n_bytes - k * block_bytes))
+            seen["blocks"] += 1
+            if k % 2:
+                out_len[k] = 0
+            elif k % 4 == 2:
+                out_len[k] = room + 1                            # a length that does not fit: the block is the codec's too
+                seen["oversize"] += 1
+            else:
+                co = zlib.compressobj(9, zlib.DEFLATED, -15)
+                s = co.compress(chunk) + co.flush()
+                C.memmove(out + k * stride, s, len(s))
+                out_len[k] = len(s)
+                seen["given"] += 1
+        return 0
+    plain, _, _ = _hook_file(tmp_path, scheme, "plain", None)
+    path, stats, at_stats = _hook_file(tmp_path, scheme, "second", every_second, lambda: (seen["given"], seen["blocks"] - seen["given"], 0))
+    assert seen["given"] > 0 and seen["oversize"] > 0
+    assert seen["args"] == {(BS, 65536 - 26, True)}
+    assert stats == at_stats
+    img = _check_bgzf(path)
+    assert img == _check_bgzf(plain)
+    # the hook's streams really land in the file: the members it supplied hold zlib level 9's bytes
+    raw, mem = _members(path)
+    data_members = [m for m in mem if m[4]]
+    hits = 0
+    for _off, _bsize, cdata, _crc, isize in data_members:
+        co = zlib.compressobj(9, zlib.DEFLATED, -15)
+        block = zlib.decompress(cdata, -15)
+        hits += (co.compress(block) + co.flush()) == cdata
+    assert hits >= seen["given"]
+    f = bam_native.BamFile(path); assert f.n_records == 6000; f.close()
+
+
+def test_hook_can_be_taken_out_again(tmp_path, scheme):
+    g, _, amps = scheme
+    b = synth.make_amplicon_batch(g, amps, 3000, seed=4)
+    sf = _seed_file(tmp_path, b, g)
+
+    def never(user, inp, n_bytes, block_bytes, out, stride, room, out_len):
+        raise AssertionError("called after it was taken out")
+    cb = bam_native.DEFLATE_FN(never)
+    path = str(tmp_path / "out.bam")
+    w = bam_native.BamWriter(path, sf.header_text, sf, level=1)
+    w.set_deflater(cb, None)
+    w.set_deflater(None, None)
+    w.write_batch(b)
+    assert w.deflater_stats() == (0, 0, 0)
+    w.close(); sf.close()
+    _check_bgzf(path)
+
+
+# ---- the encoder's phases on the host ------------------------------------------------------------------------------------------------
+def test_encoder_phases_on_the_host(tmp_path, scheme):
+    """amp_deflate.hip's phase functions compile for the host too (-DAMPDF_HOSTSIM: thread after thread, phase after phase): the
+    streams they give there pass the block-level checks, so the encoder's logic is tested where there is no GPU."""
+    import shutil
+    from amplipy_amd import build
+    so = str(tmp_path / "libampdf_hostsim.so")
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-Wno-unused-function", "-DAMPDF_HOSTSIM",
+                           "-o", so, os.path.join(build.CSRC, "amp_deflate.hip")])
+    sim = C.CDLL(so)
+    path, _ = _synthetic_bam(tmp_path, scheme, 6000, level=1)
+    image = gzip.open(path).read()
+    cases = [(image, BS), (image[5:300000], 12345), (bytes(2 * BS + 17), BS), (b"Q", BS), (_fibonacci_bytes(), BS), (os.urandom(70000), BS),
+             (b"a" * 1000 + b"ab" * 700 + b"I" * 258 + b"J" + b"I" * 259 + b"abc" * 5000, 777), (image[:2000], 3)]
+    for data, bs in cases:
+        rc, streams = _deflate_blocks(data, block_bytes=bs, hostsim=sim)
+        assert rc == 0
+        _check_streams(data, streams, block_bytes=bs)
+    rc, streams = _deflate_blocks(image, hostsim=sim)
+    total = sum(len(s) for s in streams)
+    assert total < len(image) / 4 and all(s[0] & 7 == 5 for s in streams)
+    rc, streams = _deflate_blocks(os.urandom(BS), room=4096, hostsim=sim)
+    assert rc == 0 and streams == [None]
+
+
+@pytest.mark.gpu
+def test_device_streams_are_the_host_phases_streams(tmp_path, bam_image):
+    """... and the device gives exactly those streams: nothing in them depends on how the threads were scheduled."""
+    import shutil
+    from amplipy_amd import build
+    so = str(tmp_path / "libampdf_hostsim.so")
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-Wno-unused-function", "-DAMPDF_HOSTSIM",
+                           "-o", so, os.path.join(build.CSRC, "amp_deflate.hip")])
+    data = bam_image[:40 * BS + 321]
+    assert _deflate_blocks(data)[1] == _deflate_blocks(data, hostsim=C.CDLL(so))[1]
+
+
+# ---- 6. size -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_file_size_against_the_host_codec(tmp_path, scheme, capsys):
+    """Gate: the GPU file is at most 1.10 x the host codec's level-1 file of the same inflated bytes.  The ratio against the shipped
+    level (-1) is printed, not gated.  Measured on an MI355X, 40,000 synthetic reads (10.9 MB inflated), S1 from libdeflate:
+    the figures are in DESIGN.md section 9."""
+    gpu, stats = _synthetic_bam(tmp_path, scheme, 40000, name="gpu.bam", gpu_deflate=True)
+    s1, _ = _synthetic_bam(tmp_path, scheme, 40000, name="s1.bam", gpu_deflate=False, level=1)
+    s6, _ = _synthetic_bam(tmp_path, scheme, 40000, name="s6.bam", gpu_deflate=False, level=-1)
+    img = _check_bgzf(gpu)
+    assert img == _check_bgzf(s1) == _check_bgzf(s6)
+    try:
+        C.CDLL("libdeflate.so.0"); provider = "libdeflate"
+    except OSError:
+        try:
+            C.CDLL("libdeflate.so"); provider = "libdeflate"
+        except OSError:
+            provider = "zlib"
+    if os.environ.get("AMPBAM_ZLIB"):
+        provider = "zlib"
+    G, S1, S6 = (os.path.getsize(p) for p in (gpu, s1, s6))
+    with capsys.disabled():
+        print("\ngpu deflate size: inflated %d, GPU %d (%.2f x), S1 %d (%.2f x, %s level 1), S6 %d (%.2f x); GPU / S1 = %.3f, GPU / S6 = %.3f; blocks %r"
+              % (len(img), G, len(img) / G, S1, len(img) / S1, provider, S6, len(img) / S6, G / S1, G / S6, stats))
+    assert stats[0] > 100 and stats[1] == 0 and stats[2] == 0
+    assert G <= 1.10 * S1, "GPU file %d bytes, host level 1 %d bytes: %.3f x" % (G, S1, G / S1)
