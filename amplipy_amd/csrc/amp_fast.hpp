@@ -38,13 +38,10 @@
 
 namespace amp {
 
-#ifndef AMP_F_WAVES
-#define AMP_F_WAVES 8
-#endif
 #ifndef AMP_F_LDSPAD
 #define AMP_F_LDSPAD 0
 #endif
-constexpr int F_WAVES = AMP_F_WAVES;  // waves per block (one block per CU: LDS)
+// (F_WAVES, F_EVGRAN and fast_grid: amp_plan.hpp)
 #ifndef AMP_F4_LEAN
 #define AMP_F4_LEAN 1    // counting from 16 good-quality bits per piece with the lean piece code below (count_piece5); 0: round 2's fast_count_piece
 #endif
@@ -72,23 +69,9 @@ constexpr int F_NPL = 4;              // its base planes: A C G T (a counted N g
 constexpr int F_BPL = 6;              // ... followed by '-' (deletions) and the insertion-event tally
 constexpr int F_MAXINS = 8;           // longest insertion / deletion of a read the fast path takes
 constexpr int F_MAXDEL = 16;
-constexpr uint32_t F_EVGRAN = 64;     // event-list slots a wave reserves at a time
 constexpr int F_STAGE = 10240;        // bytes of a wave's staging buffer = the longest run of quality bytes a tile may span
 constexpr int F_PAD = 16;             // bytes in front of the staged run (rows that start 8 bases early)
 constexpr int F_FLUSH = 15;           // tiles between two folds of a packed window (16 increments per counter and tile at most)
-
-struct FastGrid { int64_t grid, rpb; };
-static inline FastGrid fast_grid(int64_t n_reads, int n_cu) {
-#ifndef AMP_F_BPC
-#define AMP_F_BPC 1
-#endif
-    // AMP_F_BPC blocks per CU (one is resident): a block owns a contiguous range of whole tiles of 64 reads, which its
-    // waves take one by one (at least two tiles per wave)
-    int64_t rpb = (n_reads + AMP_F_BPC * (int64_t)n_cu - 1) / (AMP_F_BPC * (int64_t)n_cu);
-    rpb = ((rpb + 63) / 64) * 64;
-    if (rpb < 2 * F_WAVES * 64) rpb = 2 * F_WAVES * 64;
-    return FastGrid{(n_reads + rpb - 1) / rpb, rpb};
-}
 
 // per-byte flag (bit 7) "quality >= mq" of four qualities, for mq <= 128 (mqb = mq in every byte); the host sends
 // runs with a larger min_quality to the general kernel
@@ -362,10 +345,10 @@ __device__ __forceinline__ uint32_t range_bits16(int32_t klo, int32_t khi) {
 #define F_STAMP_DECL unsigned long long f_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, f_prev = __builtin_amdgcn_s_memtime(); const unsigned long long f_k0 = f_prev, f_w0 = wall_clock64(); unsigned long long f_ep[3] = {0, 0, 0}, f_epw[2] = {0, 0}; uint32_t f_glob = 0
 #define F_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0xC07F); unsigned long long f_n = __builtin_amdgcn_s_memtime(); f_t[k] += f_n - f_prev; f_prev = f_n; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define F_STAMP_VM(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0x0070); unsigned long long f_n = __builtin_amdgcn_s_memtime(); f_t[k] += f_n - f_prev; f_prev = f_n; __builtin_amdgcn_sched_barrier(0); } while (0)
-#define F_STAMP_OUT do { f_t[0] = __builtin_amdgcn_s_memtime() - f_k0; const unsigned long long f_w1 = wall_clock64(); f_t[7] = f_w1 - f_w0; if (lane == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&ctr[8 + k], f_t[k]); \
-    atomicMax(&ctr[4], f_t[7]); atomicMax(&ctr[5], ~f_t[7]); atomicMax(&ctr[6], ~f_w0); atomicMax(&ctr[7], f_w1); \
+#define F_STAMP_OUT do { f_t[0] = __builtin_amdgcn_s_memtime() - f_k0; const unsigned long long f_w1 = wall_clock64(); f_t[7] = f_w1 - f_w0; if (lane == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&ctr[CTR_PHASE0 + k], f_t[k]); \
+    atomicMax(&ctr[CTR_STAMP0], f_t[7]); atomicMax(&ctr[CTR_STAMP0 + 1], ~f_t[7]); atomicMax(&ctr[CTR_STAMP0 + 2], ~f_w0); atomicMax(&ctr[CTR_STAMP0 + 3], f_w1); \
     if (f_dbg && wave == 0) { uint32_t *f_o = f_dbg + blockIdx.x * 8; f_o[0] = (uint32_t)f_t[7]; f_o[1] = (uint32_t)f_w0; for (int k = 1; k < 7; ++k) f_o[1 + k] = (uint32_t)(f_t[k] >> 4); } \
-    if (f_dbg) { uint32_t *f_o = f_dbg + 2048 + (blockIdx.x * F_WAVES + wave) * 6; f_o[0] = (uint32_t)((f_t[1] + f_t[2] + f_t[3] + f_t[4] + f_t[5] + f_t[6]) >> 4); f_o[1] = (uint32_t)(f_epw[0] - f_w0); f_o[2] = (uint32_t)(f_epw[1] - f_epw[0]); f_o[3] = (uint32_t)(f_ep[0] - f_epw[1]); f_o[4] = (uint32_t)(f_ep[1] - f_ep[0]); f_o[5] = (uint32_t)(f_ep[2] - f_ep[1]); } } } while (0)
+    if (f_dbg) { uint32_t *f_o = f_dbg + F_DBG_WAVE0 + (blockIdx.x * F_WAVES + wave) * F_DBG_WAVEWORDS; f_o[0] = (uint32_t)((f_t[1] + f_t[2] + f_t[3] + f_t[4] + f_t[5] + f_t[6]) >> 4); f_o[1] = (uint32_t)(f_epw[0] - f_w0); f_o[2] = (uint32_t)(f_epw[1] - f_epw[0]); f_o[3] = (uint32_t)(f_ep[0] - f_epw[1]); f_o[4] = (uint32_t)(f_ep[1] - f_ep[0]); f_o[5] = (uint32_t)(f_ep[2] - f_ep[1]); } } } while (0)
 #else
 #define F_DBG_PARAM
 #define F_DBG_ARG(x)
@@ -432,7 +415,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
     for (int i = lane; i < F_REP * F_REPW; i += 64) pwin[i] = 0;
     if (lane < F_PAD / 4) ((lds_u32 *)s_stage[wave])[lane] = 0x11111111u;      // (the bytes in front of a staged run are read as bases by the lanes whose pieces start 8 bases early)
     if (tid == 0) { s_ticket = 0; s_gcur = 0; }
-    if (tid == 0 && blockIdx.x == 0) { eb.ctr[26] = 0ull; eb.ctr[27] = 0ull; eb.ctr[28] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
+    if (tid == 0 && blockIdx.x == 0) { eb.ctr[CTR_LONG_N] = 0ull; eb.ctr[CTR_LONG_TICKET] = 0ull; eb.ctr[CTR_GEN_LEFT] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
     // the block's window: anchored 16 positions left of its first read (sorted input: nothing of this block starts
     // left of that read)
     int32_t bw_base = rb < n ? rd.pos[rb] : 0;
@@ -958,7 +941,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
                 if (total > ev_left) {
                     pad_events();
                     unsigned long long nb = 0;
-                    if (lane == 0) nb = atomicAdd(&ctr[16 + ev_shard], (unsigned long long)F_EVGRAN);
+                    if (lane == 0) nb = atomicAdd(&ctr[CTR_EV_SHARD0 + ev_shard], (unsigned long long)F_EVGRAN);
                     ev_base = __shfl(nb, 0); ev_left = F_EVGRAN;
                 }
                 if (runs) {
@@ -1130,9 +1113,9 @@ k_fast(F_ARGS F_DBG_PARAM) {
             }
         }
     }
-    if (n_err) atomicAdd(&ctr[2], n_err);
+    if (n_err) atomicAdd(&ctr[CTR_ERROR_READS], n_err);
     F_STAMP_OUT;
-    if (tid == 0) { gcnt[blockIdx.x] = s_gcur; if (s_gcur) eb.ctr[29] = (unsigned long long)P.epoch; }      // (every block writes the same value)
+    if (tid == 0) { gcnt[blockIdx.x] = s_gcur; if (s_gcur) eb.ctr[CTR_EPOCH] = (unsigned long long)P.epoch; }      // (every block writes the same value)
 }
 
 // Dense list of the reads the fast kernel handed over + the geometry of the general pass.  Block b places the
@@ -1177,9 +1160,9 @@ k_gcompact(const uint32_t *__restrict__ glist, const uint32_t *__restrict__ gcnt
         const bool promote = (unsigned long long)n_strict * 4ull >= (unsigned long long)cnt * 3ull;
         const uint32_t total = promote ? n_elig : n_strict;
         const auto is_long = [&](uint32_t k) -> bool { const uint32_t kd = kind(k); return kd == 1u || (promote && kd == 2u); };
-        if (tid == 0 && cnt > total) atomicAdd(&ctr[28], (unsigned long long)(cnt - total));      // entries left to the tile kernel
+        if (tid == 0 && cnt > total) atomicAdd(&ctr[CTR_GEN_LEFT], (unsigned long long)(cnt - total));      // entries left to the tile kernel
         if (total) {                                   // (uniform over the block)
-            if (tid == 0) s_lbase = (uint32_t)atomicAdd(&ctr[26], (unsigned long long)total);
+            if (tid == 0) s_lbase = (uint32_t)atomicAdd(&ctr[CTR_LONG_N], (unsigned long long)total);
             uint32_t run = 0;
             for (uint32_t k0 = 0; k0 < cnt; k0 += 256) {
                 const uint32_t k = k0 + tid;
@@ -1206,7 +1189,7 @@ k_gcompact(const uint32_t *__restrict__ glist, const uint32_t *__restrict__ gcnt
         tpb = ((tpb + T_WAVES - 1) / T_WAVES) * T_WAVES;
         if (tpb < (uint32_t)T_WAVES) tpb = T_WAVES;
         geo->n_list = n_list; geo->tpb = tpb; geo->n_seg = (tiles + tpb - 1) / tpb; geo->live_counted = long_max_ops ? 1u : 0u;
-        ctr[7] = n_list;                          // (amp_debug_counters: reads of the last batch that took the general pass)
+        ctr[CTR_GEN_LIST_N] = n_list;                          // (amp_debug_counters: reads of the last batch that took the general pass)
     }
 }
 

@@ -41,7 +41,7 @@ namespace amp {
 #define AMP_F5_ABL 0      // development builds: parts of the kernel switched off to count the rest's instructions (results are wrong on purpose)
 #endif
 // development builds (-DAMP_F7_STAMPS): shader cycles a wave spends in the two waits of a turn, in the piece loops and in all of its
-// turns, summed over the waves into ctr[8 ..], turns into ctr[6] (tools/time_config5.py prints them)
+// turns, summed over the waves into ctr[CTR_PHASE0 ..], turns into ctr[CTR_STAMP0 + 2] (tools/time_config5.py prints them)
 #ifdef AMP_F7_STAMPS
 #define F5_T(k) do { const unsigned long long f5_n = __builtin_amdgcn_s_memtime(); f5_t[k] += f5_n - f5_prev; f5_prev = f5_n; } while (0)
 #else
@@ -157,7 +157,7 @@ __device__ __forceinline__ void f5_tiles(Src ts, F_ARGS) {
     // lanes whose pieces start 8 bases early, and are never written again)
     for (int i = lane; i < F5_SB / 4; i += 64) ((lds_u32 *)s_s[wave])[i] = 0x11111111u;
     if (tid == 0) { s_ticket = 0; s_gcur = 0; ts.clear(); }
-    if (tid == 0 && blockIdx.x == 0) { eb.ctr[26] = 0ull; eb.ctr[27] = 0ull; eb.ctr[28] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
+    if (tid == 0 && blockIdx.x == 0) { eb.ctr[CTR_LONG_N] = 0ull; eb.ctr[CTR_LONG_TICKET] = 0ull; eb.ctr[CTR_GEN_LEFT] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
     int32_t bw_base = rb < n ? rd.pos[rb] : 0;
     bw_base = (bw_base < 16 ? 0 : bw_base - 16) & ~15;
     __syncthreads();
@@ -513,7 +513,7 @@ __device__ __forceinline__ void f5_tiles(Src ts, F_ARGS) {
                 if (total > ev_left) {
                     pad_events();
                     unsigned long long nb = 0;
-                    if (lane == 0) nb = atomicAdd(&ctr[16 + ev_shard], (unsigned long long)F_EVGRAN);
+                    if (lane == 0) nb = atomicAdd(&ctr[CTR_EV_SHARD0 + ev_shard], (unsigned long long)F_EVGRAN);
                     ev_base = __shfl(nb, 0); ev_left = F_EVGRAN;
                 }
                 if (runs) {
@@ -669,7 +669,7 @@ __device__ __forceinline__ void f5_tiles(Src ts, F_ARGS) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // (the loads issued for a tile that does not exist)
 #ifdef AMP_F7_STAMPS
-    if (lane == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&ctr[8 + k], f5_t[k]); atomicAdd(&ctr[6], (unsigned long long)f5_turns); }
+    if (lane == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&ctr[CTR_PHASE0 + k], f5_t[k]); atomicAdd(&ctr[CTR_STAMP0 + 2], (unsigned long long)f5_turns); }
 #endif
     pad_events();
     if (pw_tiles && ts.n_tb) fold();
@@ -687,8 +687,8 @@ __device__ __forceinline__ void f5_tiles(Src ts, F_ARGS) {
             }
         }
     }
-    if (n_err) atomicAdd(&ctr[2], (unsigned long long)n_err);
-    if (tid == 0) { gcnt[blockIdx.x] = s_gcur; if (s_gcur) eb.ctr[29] = (unsigned long long)P.epoch; }      // (every block writes the same value)
+    if (n_err) atomicAdd(&ctr[CTR_ERROR_READS], (unsigned long long)n_err);
+    if (tid == 0) { gcnt[blockIdx.x] = s_gcur; if (s_gcur) eb.ctr[CTR_EPOCH] = (unsigned long long)P.epoch; }      // (every block writes the same value)
 }
 
 // k_fast5's tile source: 64 consecutive reads of the block a tile, a lane each; their rows are one contiguous run of the batch,
@@ -782,22 +782,7 @@ k_fast5(F_ARGS) {      // (individual arguments, like k_fast: see the note at F_
     f5_tiles<W, F5_REP, F5_PW>(F5Run<F5_WAVES, F5_QRUN>{}, F_ARGS_FWD);
 }
 
-struct Fast5Cfg { int waves, qrun; };
-// which build: by the mean padded read length of the batch (bases, a multiple of 8 per read)
-static inline Fast5Cfg fast5_cfg(int64_t n_reads, int64_t n_bases_padded, int window) {
-    const int64_t mean_pad = n_reads > 0 ? (n_bases_padded + n_reads - 1) / n_reads : 0;
-    if (mean_pad <= 152 || window != 4) return Fast5Cfg{8, 9728};          // (the other two are built for the default window only)
-    if (mean_pad <= 192) return Fast5Cfg{6, 13312};
-    return Fast5Cfg{4, 19456};
-}
-// grid of k_fast5 / k_fast7 with so many waves per block
-static inline FastGrid fast5_grid(int64_t n_reads, int n_cu, int waves) {
-    int64_t rpb = (n_reads + (int64_t)n_cu - 1) / (int64_t)n_cu;
-    rpb = ((rpb + 63) / 64) * 64;
-    if (rpb < 2 * waves * 64) rpb = 2 * waves * 64;
-    return FastGrid{(n_reads + rpb - 1) / rpb, rpb};
-}
-
+// (which build a batch takes and its grid: fast5_cfg, fast5_grid in amp_plan.hpp)
 static inline int fast5_launch(const KParams &P, const amp_dev_reads &rd, uint64_t read_base, const DevOut &out, uint32_t *counts,
                                const EventBuf &eb, uint32_t *glist, uint32_t *gcnt, const FastGrid &fg, const Fast5Cfg &cf, hipStream_t stream) {
     const unsigned g = (unsigned)fg.grid;

@@ -50,7 +50,7 @@ namespace amp {
 #ifndef AMP_F6_ABL
 #define AMP_F6_ABL 0
 #endif
-constexpr int F6_WAVES = 8;
+// (F6_WAVES and fast6_grid: amp_plan.hpp)
 constexpr int F6_NP = 10;                  // 16-base pieces of a row
 constexpr int F6_MAXLEN = 16 * F6_NP;      // longest read taken
 constexpr int F6_QB = 1024 * F6_NP;        // bytes of a wave's quality image (10 instructions x 64 lanes x 16 bytes)
@@ -157,13 +157,13 @@ __device__ __forceinline__ void f6_count16(const uint2 &m, uint32_t wb, uint32_t
     f6_add8<8>(wb, se1, so1, one);
 }
 
-// phase stamps of development builds (-DAMP_F6_STAMPS: cycles per phase summed over the waves into ctr[8 ..], turns into ctr[6]); the
+// phase stamps of development builds (-DAMP_F6_STAMPS: cycles per phase summed over the waves into ctr[CTR_PHASE0 ..], turns into ctr[CTR_STAMP0 + 2]); the
 // shipped library has none
 #ifdef AMP_F6_WAITSTAMPS
 #define F6_WS_DECL unsigned long long f6_w[4] = {0, 0, 0, 0}, f6_wt = 0; unsigned long long f6_wn = 0
 #define F6_WS_BEGIN do { __builtin_amdgcn_s_waitcnt(0xC07F); f6_wt = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); } while (0)
 #define F6_WS_END(k) do { const unsigned long long f6_n = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); f6_w[k] += f6_n - f6_wt; f6_wt = f6_n; } while (0)
-#define F6_WS_OUT do { if (lane == 0) { for (int k = 0; k < 4; ++k) atomicAdd(&ctr[8 + k], f6_w[k]); atomicAdd(&ctr[6], f6_wn); } } while (0)
+#define F6_WS_OUT do { if (lane == 0) { for (int k = 0; k < 4; ++k) atomicAdd(&ctr[CTR_PHASE0 + k], f6_w[k]); atomicAdd(&ctr[CTR_STAMP0 + 2], f6_wn); } } while (0)
 #else
 #define F6_WS_DECL
 #define F6_WS_BEGIN
@@ -173,7 +173,7 @@ __device__ __forceinline__ void f6_count16(const uint2 &m, uint32_t wb, uint32_t
 #ifdef AMP_F6_STAMPS
 #define F6_STAMP_DECL unsigned long long f6_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, f6_prev = __builtin_amdgcn_s_memtime(); unsigned long long f6_turns = 0
 #define F6_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0xC07F); const unsigned long long f6_n = __builtin_amdgcn_s_memtime(); f6_t[k] += f6_n - f6_prev; f6_prev = f6_n; __builtin_amdgcn_sched_barrier(0); } while (0)
-#define F6_STAMP_OUT do { if (lane == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&ctr[8 + k], f6_t[k]); atomicAdd(&ctr[6], f6_turns); } } while (0)
+#define F6_STAMP_OUT do { if (lane == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&ctr[CTR_PHASE0 + k], f6_t[k]); atomicAdd(&ctr[CTR_STAMP0 + 2], f6_turns); } } while (0)
 #define F6_TURN ++f6_turns
 #else
 #define F6_STAMP_DECL
@@ -230,7 +230,7 @@ k_fast6(F6_PARAMS) {
     for (int i = tid; i < F_BPL * F6_BW; i += F6_WAVES * 64) bwin[i] = 0;
     for (int i = lane; i < F6_REP * F6_REPW; i += 64) pwin[i] = 0;
     if (tid == 0) { s_ticket = 0; s_gcur = 0; s_n[0] = 0; s_n[1] = 0; }
-    if (tid == 0 && blockIdx.x == 0) { eb.ctr[26] = 0ull; eb.ctr[27] = 0ull; eb.ctr[28] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
+    if (tid == 0 && blockIdx.x == 0) { eb.ctr[CTR_LONG_N] = 0ull; eb.ctr[CTR_LONG_TICKET] = 0ull; eb.ctr[CTR_GEN_LEFT] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
     int32_t bw_base = rb < n ? rd.pos[rb] : 0;
     bw_base = (bw_base < 16 ? 0 : bw_base - 16) & ~15;
     __syncthreads();
@@ -750,7 +750,7 @@ k_fast6(F6_PARAMS) {
                 if (total > ev_left) {
                     pad_events();
                     unsigned long long nb = 0;
-                    if (lane == 0) nb = atomicAdd(&ctr[16 + ev_shard], (unsigned long long)F_EVGRAN);
+                    if (lane == 0) nb = atomicAdd(&ctr[CTR_EV_SHARD0 + ev_shard], (unsigned long long)F_EVGRAN);
                     ev_base = __shfl(nb, 0); ev_left = F_EVGRAN;
                 }
                 if (runs) {
@@ -904,17 +904,10 @@ k_fast6(F6_PARAMS) {
             }
         }
     }
-    if (n_err) atomicAdd(&ctr[2], n_err);
+    if (n_err) atomicAdd(&ctr[CTR_ERROR_READS], n_err);
     F6_STAMP_OUT;
     F6_WS_OUT;
-    if (tid == 0) { gcnt[blockIdx.x] = s_gcur; if (s_gcur) eb.ctr[29] = (unsigned long long)P.epoch; }      // (every block writes the same value)
-}
-
-static inline FastGrid fast6_grid(int64_t n_reads, int n_cu) {
-    int64_t rpb = (n_reads + (int64_t)n_cu - 1) / (int64_t)n_cu;
-    rpb = ((rpb + 63) / 64) * 64;
-    if (rpb < 2 * F6_WAVES * 64) rpb = 2 * F6_WAVES * 64;
-    return FastGrid{(n_reads + rpb - 1) / rpb, rpb};
+    if (tid == 0) { gcnt[blockIdx.x] = s_gcur; if (s_gcur) eb.ctr[CTR_EPOCH] = (unsigned long long)P.epoch; }      // (every block writes the same value)
 }
 
 static inline int fast6_launch(const KParams &P, const amp_dev_reads &rd, uint64_t read_base, const DevOut &out, uint32_t *counts,

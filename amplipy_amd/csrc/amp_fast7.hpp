@@ -32,14 +32,10 @@ namespace amp {
 // Waves per block, replicas and width of a wave's packed window: the LDS holds 8 waves with 2 replicas, 7 with 4 or 6 with 5.  The
 // counting adds are bound by LDS bank conflicts (14.5 LDS cycles per instruction with two replicas, 12 of them conflicts), so
 // replicas buy more than the eighth wave: config 5 takes 1.69 ms with 8 x 2, 1.34 with 7 x 4, 1.43 / 1.42 with 6 x 4 / 6 x 5, 1.52
-// with 5 x 8 (profiles/r04_config5_ablations.txt)
-#ifndef AMP_F7_NWAVES
-#define AMP_F7_NWAVES 7
-#endif
+// with 5 x 8 (profiles/r04_config5_ablations.txt).  (AMP_F7_NWAVES / F7_WAVES are defined in amp_plan.hpp: the host sizes the grid with them.)
 #ifndef AMP_F7_PWIN
 #define AMP_F7_PWIN 400                   // a read of 304 bases + 16 positions in front + the spread of a tile's starts
 #endif
-constexpr int F7_WAVES = AMP_F7_NWAVES;
 constexpr int F7_QCAP = 9728;             // bytes of a tile's quality image (64 x 144, 32 x 304)
 constexpr int F7_SCAP = 5120;             // ... of its packed-base image (64 x 80, 32 x 160)
 constexpr uint32_t F7_B2MAX = 224u, F7_PAIRBIN = 2u, F7_B2MAGIC = 19173962u;      // bin 2: reads of up to so many bases; bins from here on hold two lanes per read; ceil(2^32 / F7_B2MAX)

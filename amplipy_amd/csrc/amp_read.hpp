@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/amplihip.h"
+#include "amp_plan.hpp"
 
 #define AMP_HD __host__ __device__ __forceinline__
 
@@ -31,7 +32,7 @@ struct KParams {
     int32_t min_quality, window, do_trim, do_count;
     int32_t ref_len, max_primer_len;
     const int32_t *min_start, *max_end;  // -1 = None; valid when do_trim
-    uint32_t epoch = 0;                  // number of the launch (a fast kernel that hands reads to the general pass leaves it in ctr[29]: the pass
+    uint32_t epoch = 0;                  // number of the launch (a fast kernel that hands reads to the general pass leaves it in ctr[CTR_EPOCH]: the pass
                                          // after a launch without such reads ends at its first instruction instead of adding up 256 list lengths)
 };
 
@@ -47,16 +48,40 @@ struct DevOut {
 
 // Where insertion events go: the event list (bounded by cap; the cursor keeps counting so the
 // host can detect a short reservation) and the per-position event tally used by calling.
-constexpr int EV_SHARDS = 8;     // event cursors: ctr[16 .. 16+EV_SHARDS)
+constexpr int EV_SHARDS = 8;     // event cursors: ctr[CTR_EV_SHARD0 .. CTR_EV_SHARD0 + EV_SHARDS)
+// The ctx's device counters (EventBuf::ctr, 64-bit words).  amp_ctx_create and amp_reset clear all of them; no slot moves:
+// amp_debug_counters hands the first CTR_DEBUG_WORDS out by index.  Where one slot has two names its users cannot meet.
+enum : int {
+    // [0] and [3] are written by no kernel: amp_debug_counters fills them on the host (heavy / all deferred reads of the last batch)
+    CTR_EVENT_BOUND = 1,      // k_event_bound adds a batch's bound on insertion events; launch_reads clears it before and reads it after
+    CTR_ERROR_READS = 2,      // every read kernel adds its reads with a non-zero status; read by amp_error_reads
+    CTR_CALL_RELEVANT = 4,    // k_call counts the insertion-relevant positions; amp_call_positions clears it before and reads it after
+    CTR_STAMP0 = 4,           // [4, 8): clocks of a stamping kernel (block durations, waits, turns).  -DAMP_DEV / stamp builds only, which
+                              // clear them in front of the stamped launch: a stamped run gives up CTR_CALL_RELEVANT's and CTR_GEN_LIST_N's
+                              // values between two launches, the shipped library has no stamps
+    CTR_GEN_LIST_N = 7,       // reads of the last batch that took the general pass: k_gcompact or k_tile<LIST> stores it (amp_debug_counters [7])
+    CTR_PHASE0 = 8,           // [8, 16): per-phase cycle sums of a stamping kernel (k_tile: six, then the slowest block and the block count)
+    CTR_DEBUG_WORDS = 16,     // amp_debug_counters copies [0, 16)
+    CTR_EV_SHARD0 = 16,       // [16, 24): the event list's cursors, one per shard; every kernel that records events adds, the drain calls clear them
+    CTR_HEAVY_FLAG = 24,      // the tile kernel sets it when it deferred a read to the heavy pass, which leaves at once otherwise (sticky until amp_reset)
+    CTR_LONG_N = 26,          // k_long's list length, added up by k_gcompact ...
+    CTR_LONG_TICKET = 27,     // ... the chunk ticket its blocks draw from ...
+    CTR_GEN_LEFT = 28,        // ... and the list entries left to the tile kernel (k_gcompact adds, k_long adds the reads it hands back).
+                              // Block 0 of the fast kernel clears the three at the start of every variant-4 batch
+    CTR_EPOCH = 29,           // KParams::epoch of the last fast kernel that handed a read to the general pass (any of its blocks stores it)
+    CTR_WORDS = 32,
+};
+static_assert(CTR_STAMP0 + 4 == CTR_PHASE0 && CTR_PHASE0 + 8 == CTR_EV_SHARD0, "the stamps fill [4, 16)");
+static_assert(CTR_EV_SHARD0 + EV_SHARDS <= CTR_HEAVY_FLAG && CTR_EPOCH < CTR_WORDS, "the shard cursors and the slots above them fit the counters");
 struct EventBuf {
     amp_ins_event *ev;         // EV_SHARDS regions of `cap` events each
-    unsigned long long *ctr;   // [1] bound, [2] error reads, [3] deferred reads, [16+s] events of shard s
+    unsigned long long *ctr;   // [CTR_WORDS], see the enum above
     uint32_t *ins_at;          // [ref_len]
     long long cap;             // per shard
     // One cursor per shard (block id modulo EV_SHARDS): a single hot counter serialises the chip.
     __device__ void record(int32_t pos, uint32_t read, int32_t lo, int32_t hi) const {
         const unsigned s = blockIdx.x & (EV_SHARDS - 1);
-        unsigned long long idx = atomicAdd(&ctr[16 + s], 1ull);
+        unsigned long long idx = atomicAdd(&ctr[CTR_EV_SHARD0 + s], 1ull);
         if ((long long)idx < cap) ev[(size_t)s * (size_t)cap + idx] = amp_ins_event{pos, read, lo, hi};
         atomicAdd(&ins_at[pos], 1u);
     }

@@ -36,10 +36,8 @@
 
 namespace amp {
 
-constexpr int TILE = 64;          // reads per wave tile
-constexpr int T_WAVES = 8;        // waves per block (two blocks per CU)
+// (TILE, T_WAVES, T_MAXOPS, DEFER_INDEX_MASK, GL_MAXSEG and tile_grid: amp_plan.hpp, the host plans with them)
 constexpr int T_W = 512;          // reference positions covered by the LDS window
-constexpr int T_MAXOPS = 18;      // CIGAR ops per read held in LDS as 16-bit words (input ops <= T_MAXOPS-3, lengths sum < 4096)
 constexpr int T_MAPCAP = T_MAXOPS * TILE * 2;   // chunk-map bytes = the spare CIGAR buffer
 constexpr int T_SEGCAP = 192;     // match-op segments per tile
 constexpr int T_UNROLL = 3;       // chunks per lane whose loads are issued before any of them is processed (P2)
@@ -57,17 +55,12 @@ typedef __attribute__((address_space(3))) amp_u32x4 lds_u32x4;
 // entries of the deferred list: read index | kind
 constexpr uint32_t DEFER_STATUS_ONLY = 0x80000000u;   // counted by the tile kernel; only the exact status is missing
 constexpr uint32_t DEFER_INDELS = 0x40000000u;        // match bases counted by the tile kernel; deletions / insertion events missing
-constexpr uint32_t DEFER_INDEX_MASK = 0x3FFFFFFFu;
 
 // The general pass of variant 4 (amp_fast.hpp) runs this kernel over a LIST of reads: entries are read index | kind
 constexpr uint32_t GL_STATUS_ONLY = 0x80000000u;   // counted by the fast kernel; a base could not be counted: exact status wanted
 constexpr uint32_t GL_LONG = 0x40000000u;          // tens of CIGAR ops: taken by k_long (amp_wave.hpp), not a row of this pass
 constexpr uint32_t GL_INDEX_MASK = 0x3FFFFFFFu;
-// Where k_tile<LIST> finds its list when k_gcompact has not packed it (the common case: one launch less per batch).  The fast
-// kernel leaves one list segment per block (entries [b * rpb, b * rpb + gcnt[b]) of glist); a block of the tile kernel sums
-// the counts itself (a KB from L2), derives the geometry k_gcompact would have written, and finds entry li of the virtual
-// dense list by a binary search over the prefix sums.
-constexpr int GL_MAXSEG = 256;
+// Where k_tile<LIST> finds its list when k_gcompact has not packed it (GL_MAXSEG, amp_plan.hpp)
 struct ListSrc {
     const uint32_t *glist, *gcnt;   // null: the list is dense (rlist)
     int n_gseg, rpb;
@@ -79,7 +72,7 @@ struct GenGeo {            // geometry of the general pass, decided on the devic
     uint32_t n_list;       // entries of the dense list
     uint32_t tpb;          // tiles per block of k_tile<LIST>
     uint32_t n_seg;        // its blocks that have tiles
-    uint32_t live_counted; // 1: ctr[28] holds the entries not flagged GL_LONG (k_long's batches); the tile kernel leaves at once when there are none
+    uint32_t live_counted; // 1: ctr[CTR_GEN_LEFT] holds the entries not flagged GL_LONG (k_long's batches); the tile kernel leaves at once when there are none
 };
 
 // per-read state words kept in LDS for the chunk lanes
@@ -591,12 +584,12 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const bool direct = LIST && ls.glist != nullptr;
     uint32_t n_list_direct = 0;
-    if (direct && (uint32_t)ctr[29] != P.epoch) {
+    if (direct && (uint32_t)ctr[CTR_EPOCH] != P.epoch) {
         // no block of this launch's fast kernel handed a read over: an empty pass (what the code below finds out after adding up the
         // list lengths of all blocks; the batches of an amplicon run are like this nine times in ten)
         if (blockIdx.x == 0 && tid == 0) {
             ls.geo_out->n_list = 0u; ls.geo_out->tpb = (uint32_t)T_WAVES; ls.geo_out->n_seg = 0u; ls.geo_out->live_counted = 0u;
-            ctr[7] = 0ull;
+            ctr[CTR_GEN_LIST_N] = 0ull;
         }
         if (tid == 0) { dcnt[blockIdx.x] = 0; dcnt[5 * dcnt_stride + 64 + blockIdx.x] = 0; }
         return;
@@ -620,7 +613,7 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
         tiles_per_block = (int)tpb;
         if (blockIdx.x == 0 && tid == 0) {
             ls.geo_out->n_list = n_list_direct; ls.geo_out->tpb = tpb; ls.geo_out->n_seg = (tiles + tpb - 1) / tpb; ls.geo_out->live_counted = 0u;
-            ctr[7] = n_list_direct;                   // (amp_debug_counters: reads of the last batch that took the general pass)
+            ctr[CTR_GEN_LIST_N] = n_list_direct;                   // (amp_debug_counters: reads of the last batch that took the general pass)
         }
     } else if (LIST) tiles_per_block = (int)geo->tpb;
     const int64_t n = direct ? (int64_t)n_list_direct : LIST ? (int64_t)geo->n_list : rd.n_reads;
@@ -634,7 +627,7 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
     const int64_t n_tiles = (n + TILE - 1) / TILE;
     const int64_t tile_begin = (int64_t)blockIdx.x * tiles_per_block;
     const int64_t tile_end = tile_begin + tiles_per_block < n_tiles ? tile_begin + tiles_per_block : n_tiles;
-    if (tile_begin >= tile_end || (LIST && !direct && geo->live_counted && ctr[28] == 0ull)) {
+    if (tile_begin >= tile_end || (LIST && !direct && geo->live_counted && ctr[CTR_GEN_LEFT] == 0ull)) {
         if (threadIdx.x == 0) { dcnt[blockIdx.x] = 0; dcnt[5 * dcnt_stride + 64 + blockIdx.x] = 0; }
         return;
     }
@@ -943,7 +936,7 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
             if (nev) {
                 const unsigned shard = blockIdx.x & (EV_SHARDS - 1);
                 unsigned long long eb0 = 0;
-                if (lane == 0) eb0 = atomicAdd(&eb.ctr[16 + shard], (unsigned long long)nev);
+                if (lane == 0) eb0 = atomicAdd(&eb.ctr[CTR_EV_SHARD0 + shard], (unsigned long long)nev);
                 eb0 = __shfl(eb0, 0);
                 for (uint32_t k = (uint32_t)lane; k < nev; k += 64u)
                     if ((long long)(eb0 + k) < eb.cap)
@@ -1004,40 +997,27 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
             }
         }
     }
-    if (n_err) atomicAdd(&ctr[2], n_err);
+    if (n_err) atomicAdd(&ctr[CTR_ERROR_READS], n_err);
     if (tid == 0) {
         dcnt[blockIdx.x] = L.dcount; dcnt[5 * dcnt_stride + 64 + blockIdx.x] = L.dcount2;
-        if (L.dcount2) atomicOr(&ctr[24], 1ull);        // tells the heavy pass that it has something to do at all (sticky until amp_reset)
+        if (L.dcount2) atomicOr(&ctr[CTR_HEAVY_FLAG], 1ull);        // tells the heavy pass that it has something to do at all (sticky until amp_reset)
         // (no per-block atomic on a shared counter here: thousands of blocks on one address serialise;
         //  amp_debug_counters sums the per-block list counts instead)
     }
     if (stamps && lane == 0) {
-        for (int k = 0; k < 6; ++k) atomicAdd(&ctr[8 + k], tacc[k]);
-        atomicAdd(&ctr[6], t_loopend - t_kernel0);      // time a wave spends in its tile loop
-        atomicAdd(&ctr[7], t_barrier - t_loopend);      // ... waiting for the slowest wave of its block
-        atomicAdd(&ctr[15], 1ull);
+        for (int k = 0; k < 6; ++k) atomicAdd(&ctr[CTR_PHASE0 + k], tacc[k]);
+        atomicAdd(&ctr[CTR_STAMP0 + 2], t_loopend - t_kernel0);      // time a wave spends in its tile loop
+        atomicAdd(&ctr[CTR_STAMP0 + 3], t_barrier - t_loopend);      // ... waiting for the slowest wave of its block
+        atomicAdd(&ctr[CTR_PHASE0 + 7], 1ull);
         if (tid == 0) {
             const unsigned long long dur = __builtin_amdgcn_s_memtime() - t_kernel0;
-            atomicMax(&ctr[14], (dur << 16) | (unsigned long long)(blockIdx.x & 0xFFFF));            // slowest block and its id
-            atomicMax(&ctr[5], ((0xFFFFFFFFFFFFull - dur) << 16) | (unsigned long long)(blockIdx.x & 0xFFFF));   // fastest block
-            atomicAdd(&ctr[4], dur);
+            atomicMax(&ctr[CTR_PHASE0 + 6], (dur << 16) | (unsigned long long)(blockIdx.x & 0xFFFF));            // slowest block and its id
+            atomicMax(&ctr[CTR_STAMP0 + 1], ((0xFFFFFFFFFFFFull - dur) << 16) | (unsigned long long)(blockIdx.x & 0xFFFF));   // fastest block
+            atomicAdd(&ctr[CTR_STAMP0], dur);
             dcnt[dcnt_stride + 64 + blockIdx.x * 4 + 0] = (uint32_t)dur; dcnt[dcnt_stride + 64 + blockIdx.x * 4 + 1] = bs_rebase;
         }
         if (lane == 0) { atomicAdd(&dcnt[dcnt_stride + 64 + blockIdx.x * 4 + 2], bs_c2); atomicAdd(&dcnt[dcnt_stride + 64 + blockIdx.x * 4 + 3], bs_c4); }
     }
-}
-
-// Geometry shared by the tile kernel and the second pass: block b owns tiles [b*tpb, (b+1)*tpb).
-struct TileGrid { int64_t grid, tpb; };
-static inline TileGrid tile_grid(int64_t n_reads, int n_cu) {
-    const int64_t n_tiles = (n_reads + TILE - 1) / TILE;
-    // 32 blocks per CU: two are resident, the rest are handed out as CUs free up, which evens out the
-    // (measured) speed differences between blocks and XCDs.  Measured on 19.9 M reads: 8 blocks per CU
-    // 3.45 ms, 16: 3.20, 32: 3.15, 64: 3.13, one tile per wave (the minimum): 3.34.
-    int64_t tpb = (n_tiles + 32 * (int64_t)n_cu - 1) / (32 * (int64_t)n_cu);
-    tpb = ((tpb + T_WAVES - 1) / T_WAVES) * T_WAVES;   // whole super-tiles per block
-    if (tpb < T_WAVES) tpb = T_WAVES;
-    return TileGrid{(n_tiles + tpb - 1) / tpb, tpb};
 }
 
 static inline int tile_launch(const KParams &P, const amp_dev_reads &rd, uint64_t read_base, const DevOut &out,

@@ -334,7 +334,7 @@ __device__ __forceinline__ void wv_flush_events(const EventBuf &eb, lds_u32 *ev,
     if (n == 0u) return;
     const unsigned shard = blockIdx.x & (EV_SHARDS - 1);
     unsigned long long b0 = 0ull;
-    if (lane == 0) b0 = atomicAdd(&eb.ctr[16 + shard], (unsigned long long)n);
+    if (lane == 0) b0 = atomicAdd(&eb.ctr[CTR_EV_SHARD0 + shard], (unsigned long long)n);
     b0 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(b0 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)b0);
     for (uint32_t k = (uint32_t)lane; k < n; k += 64u)
         if ((long long)(b0 + k) < eb.cap)
@@ -365,7 +365,7 @@ __device__ __forceinline__ void wv_flush_events_granule(const EventBuf &eb, lds_
     wave_sync();
     if (lane == 0) *nev = 0u;
     wave_sync();
-    if (more && lane == 0) gran = atomicAdd(&eb.ctr[16 + shard], (unsigned long long)cap);
+    if (more && lane == 0) gran = atomicAdd(&eb.ctr[CTR_EV_SHARD0 + shard], (unsigned long long)cap);
 }
 
 // One read on one wave: trims (A:426-687), outputs, counts (A:690-753).  x, y, z: the wave's three LDS rows of WV_MAXOPS
@@ -681,7 +681,7 @@ __device__ bool wave_read(const KParams &P, const amp_dev_reads &rd, int64_t i, 
     }
     if (lane == 0) {
         if (out.status) out.status[i] = (uint8_t)err;
-        if (err) atomicAdd(&eb.ctr[2], 1ull);
+        if (err) atomicAdd(&eb.ctr[CTR_ERROR_READS], 1ull);
     }
     wave_sync();
     return true;
@@ -701,9 +701,7 @@ __device__ bool wave_read(const KParams &P, const amp_dev_reads &rd, int64_t i, 
 // cursor that the wave waits for; waves taking every 16th read of the chunk wait 19 % longer at the chunk's barrier than
 // with the LDS ticket; a block that walks a contiguous 1/256 of the list with a moving window has fewer barriers but ran
 // 0.76-2.2 ms from launch to launch.)
-constexpr int L_WAVES = 12;
-constexpr int L_MAXOPS = 160;        // words per CIGAR row: reads of up to L_MAXOPS - 4 ops (more: the heavy pass's wave path, 508)
-constexpr int L_EVCAP = 64;          // events staged per wave
+// (L_WAVES, L_MAXOPS, L_EVCAP: amp_plan.hpp)
 constexpr int L_CHUNK = 128;         // most list entries a block takes at a time
 constexpr uint32_t L_WIN = 1024;     // reference positions of the block's window
 constexpr uint32_t L_PITCH = L_WIN + L_WIN / 64;   // words per plane (skewed: see WaveSink)
@@ -722,7 +720,7 @@ k_long(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
        const uint32_t *__restrict__ llist, const uint32_t *__restrict__ lpos, uint32_t *dense) {
     __shared__ __attribute__((aligned(16))) LongLds L;
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint32_t n_long = (uint32_t)eb.ctr[26];            // left by k_gcompact
+    const uint32_t n_long = (uint32_t)eb.ctr[CTR_LONG_N];            // left by k_gcompact
     if (n_long == 0u) return;
     for (uint32_t w = (uint32_t)tid; w < (AMP_NSYM + 1) * L_PITCH; w += L_WAVES * 64) L.win[w] = 0u;
     if (lane == 0) L.nev[wave] = 0u;
@@ -738,12 +736,12 @@ k_long(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
     const uint32_t n_bigc = (uint32_t)(((unsigned long long)n_long * 3ull / 4ull) / big), rest0 = n_bigc * big;
     const uint32_t n_chunk = n_bigc + (n_long - rest0 + small - 1u) / small;
     unsigned long long gran = 0ull;                          // the wave's granule of the event list (lane 0)
-    if (lane == 0) gran = atomicAdd(&eb.ctr[16 + (blockIdx.x & (EV_SHARDS - 1))], (unsigned long long)L_EVCAP);
+    if (lane == 0) gran = atomicAdd(&eb.ctr[CTR_EV_SHARD0 + (blockIdx.x & (EV_SHARDS - 1))], (unsigned long long)L_EVCAP);
     unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (;;) {
         __syncthreads();
         if (tid == 0) {
-            const uint32_t c = (uint32_t)atomicAdd(&eb.ctr[27], 1ull);
+            const uint32_t c = (uint32_t)atomicAdd(&eb.ctr[CTR_LONG_TICKET], 1ull);
             L.chunk = c; L.ticket = 0u;
             if (c < n_chunk) { const int32_t p = rd.pos[llist[c < n_bigc ? c * big : rest0 + (c - n_bigc) * small]]; L.base = (p < 0 ? 0 : p) & ~31; }
         }
@@ -769,7 +767,7 @@ k_long(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
             if (kn < k1) { in = (int64_t)llist[kn]; hn = wv_header_load(rd, in, lane); }      // lands while this read is worked on
             WaveSink ws{(lds_u32 *)L.win, base, L_WIN, L_PITCH, 6u, (uint32_t)AMP_NSYM, counts, eb, (uint32_t)(read_base + (uint64_t)i), wev, wn, (uint32_t)L_EVCAP};
             if (!wave_read(P, rd, i, hdr, out, ws, eb, row, row + L_MAXOPS, row + 2 * L_MAXOPS, wq, L_MAXOPS - 4, lane, tacc)) {
-                if (lane == 0) { dense[lpos[k]] &= ~GL_LONG; atomicAdd(&eb.ctr[28], 1ull); }
+                if (lane == 0) { dense[lpos[k]] &= ~GL_LONG; atomicAdd(&eb.ctr[CTR_GEN_LEFT], 1ull); }
             }
             // (a read of this kind records about ten events; one that overflows the stage records the rest one by one)
             if (*wn > (uint32_t)L_EVCAP - 24u) wv_flush_events_granule(eb, wev, wn, (uint32_t)L_EVCAP, lane, gran, true);
@@ -788,7 +786,7 @@ k_long(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
     }
     wv_flush_events_granule(eb, wev, wn, (uint32_t)L_EVCAP, lane, gran, false);
 #ifdef AMP_WV_STAMPS
-    if (lane == 0) for (int k = 0; k < 8; ++k) atomicAdd(&eb.ctr[8 + k], tacc[k]);
+    if (lane == 0) for (int k = 0; k < 8; ++k) atomicAdd(&eb.ctr[CTR_PHASE0 + k], tacc[k]);
 #endif
 }
 

@@ -68,7 +68,7 @@ struct amp_ctx {
     DBuf events;                  // amp_ins_event[EV_SHARDS][ev_cap]
     int64_t ev_cap = 0;           // per shard
     bool ev_reserved = false;     // caller sized the buffer: skip the bound pre-pass
-    unsigned long long *d_ctr = nullptr;  // [0] events recorded, [1] event bound, [2] error reads, [3] deferred reads
+    unsigned long long *d_ctr = nullptr;  // [CTR_WORDS] device counters (the enum next to EventBuf, amp_read.hpp)
     uint32_t *d_ins_at = nullptr;         // [ref_len] insertion events per reference position
     uint8_t *d_ref = nullptr;             // [ref_len] reference sequence, ASCII (amp_set_reference)
     bool have_ref = false;
@@ -142,27 +142,30 @@ struct Guard {  // make the ctx's device current for the duration of a call
 // kernels shared by both variants
 // ---------------------------------------------------------------------------------------
 
-// Upper bound on the insertion events a batch can record: every event starts on its own
+// Upper bound on the insertion events a read can record: every event starts on its own
 // (q, None) aligned pair inside [query_alignment_start, query_alignment_end), i.e. on a base
-// of an I / P / inner-S op.  Trimming only turns such bases into clips, never creates them.
+// of an I / P / inner-S op of the INPUT CIGAR, ops [c0, c1) of cig.  Trimming only turns such bases into clips,
+// never creates them.  The event list is reserved by this bound and the heavy pass cuts a read's slice of it by the same.
+__device__ __forceinline__ unsigned long long ins_event_bound(const uint32_t *__restrict__ cig, uint32_t c0, uint32_t c1) {
+    unsigned long long lead = 0, all = 0, trail = 0;
+    bool in_lead = true;
+    for (uint32_t k = c0; k < c1; ++k) {
+        uint32_t v = cig[k], op = v & 15u, len = v >> 4;
+        if (op == OP_H) continue;
+        if (op == OP_S) { all += len; trail += len; if (in_lead) lead += len; }
+        else { in_lead = false; trail = 0; if (op == OP_I || op == OP_P) all += len; }
+    }
+    return all - lead - (in_lead ? 0 : trail);
+}
+
+// ... of a batch, added to ctr[CTR_EVENT_BOUND]
 __global__ void k_event_bound(int64_t n, const uint32_t *__restrict__ cig_off, const uint32_t *__restrict__ cig,
                               unsigned long long *ctr) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long b = 0;
-    if (i < n) {
-        uint32_t c0 = cig_off[i], c1 = cig_off[i + 1];
-        unsigned long long lead = 0, all = 0, trail = 0;
-        bool in_lead = true;
-        for (uint32_t k = c0; k < c1; ++k) {
-            uint32_t v = cig[k], op = v & 15u, len = v >> 4;
-            if (op == OP_H) continue;
-            if (op == OP_S) { all += len; trail += len; if (in_lead) lead += len; }
-            else { in_lead = false; trail = 0; if (op == OP_I || op == OP_P) all += len; }
-        }
-        b = all - lead - (in_lead ? 0 : trail);
-    }
+    if (i < n) b = ins_event_bound(cig, cig_off[i], cig_off[i + 1]);
     for (int o = 32; o > 0; o >>= 1) b += __shfl_down(b, o);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&ctr[1], b);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&ctr[CTR_EVENT_BOUND], b);
 }
 
 struct DevSink {
@@ -232,7 +235,7 @@ __device__ void flush_staged_events(const EventBuf &eb, const uint32_t *s_ev, ui
     __syncthreads();
     const uint32_t nev = *s_nev < D_EVCAP ? *s_nev : D_EVCAP;
     const unsigned shard = blockIdx.x & (EV_SHARDS - 1);
-    if (threadIdx.x == 0 && nev) *s_evbase = atomicAdd(&eb.ctr[16 + shard], (unsigned long long)nev);
+    if (threadIdx.x == 0 && nev) *s_evbase = atomicAdd(&eb.ctr[CTR_EV_SHARD0 + shard], (unsigned long long)nev);
     __syncthreads();
     if (nev) {
         const unsigned long long eb0 = *s_evbase;
@@ -285,47 +288,8 @@ __device__ __forceinline__ bool is_home(const LdsCig256 &, const uint32_t *) { r
 // two CIGAR buffers the trims ping-pong between (global slots, or LDS columns when the read fits);
 // the final CIGAR always lands in the read's output slot.  status_only: the tile kernel already
 // counted this read and only needs to know which error comes first in pair order.
-template <class CB, class Sink>
-__device__ void process_read_body(const KParams &P, const amp_dev_reads &rd, int64_t i, const DevOut &out, Sink &sink,
-                                  const EventBuf &eb, bool status_only, CB cur, CB tmp, uint32_t *home, uint32_t c0, int n) {
-    for (int k = 0; k < n; ++k) cur.set(k, rd.cig[c0 + k]);
-    const int32_t lseq = (int32_t)rd.lseq[i];
-    const int64_t boff = (int64_t)rd.seq_off8[i] * 8;
-    const uint8_t *qual = rd.qual + boff;
-    const bool have_qual = lseq > 0 && qual[0] != 0xFF;
-    TrimState st{rd.pos[i], n, 0u, 0};
-    if (P.do_trim) trim_read_serial(P, st, rd.flag[i], rd.tlen[i], lseq, qual, have_qual, cur, tmp);
-    if (!st.err && !is_home(cur, home))
-        for (int k = 0; k < st.n; ++k) home[k] = cur.get(k);
-    int err = st.err;
-    if (!err && P.do_count) {
-        if (status_only) {
-            NullSink ns;
-            err = count_read_walk(P, cur, st.n, st.pos, lseq, ReadBytesCached{rd.seq, boff, qual}, have_qual, ns);
-        } else {
-            err = count_read_walk(P, cur, st.n, st.pos, lseq, ReadBytesCached{rd.seq, boff, qual}, have_qual, sink);
-        }
-    }
-    if (out.new_pos) out.new_pos[i] = st.pos;
-    if (out.new_ncig) out.new_ncig[i] = st.err ? 0u : (uint32_t)st.n;
-    if (out.ref_len) out.ref_len[i] = st.err ? 0 : reference_length(cur, st.n);
-    if (out.trim_flags) out.trim_flags[i] = st.err ? (uint8_t)0 : (uint8_t)st.flags;
-    if (out.status) out.status[i] = (uint8_t)err;
-    if (err) atomicAdd(&eb.ctr[2], 1ull);
-}
-
-// CIGAR ping-pong in global memory (any length)
-__device__ void process_read_serial(const KParams &P, const amp_dev_reads &rd, int64_t i, uint64_t read_base, const DevOut &out,
-                                    uint32_t *scratch, uint32_t *counts, const EventBuf &eb, bool status_only) {
-    const uint32_t c0 = rd.cig_off32[i];
-    const int n = (int)(rd.cig_off32[i + 1] - c0);
-    const size_t slot = (size_t)c0 + 3 * (size_t)i;
-    DevSink sink{counts, eb, (uint32_t)(read_base + (uint64_t)i)};
-    process_read_body(P, rd, i, out, sink, eb, status_only, CigBuf<1>{out.new_cig + slot}, CigBuf<1>{scratch + slot},
-                      out.new_cig + slot, c0, n);
-}
-
-// Second-pass treatment of a read the tile kernel could not hold (more CIGAR ops than its LDS
+// COOP = false: the exact serial walk counts the read (returns false).
+// COOP = true: the second-pass treatment of a read the tile kernel could not hold (more CIGAR ops than its LDS
 // column): serial trim with both CIGAR buffers in LDS columns -- or, for CIGARs of more than D_MAXOPS - 3 ops
 // (Nanopore-like reads), ping-pong between the read's output slot and the scratch slot in global memory --, then
 //   * regular trimmed CIGAR (clips at the ends, body of M/=/X/I/D/N): deletions / insertion events by
@@ -334,10 +298,10 @@ __device__ void process_read_serial(const KParams &P, const amp_dev_reads &rd, i
 //   * anything else: the exact serial walk.
 constexpr int D_MAXOPS = 19;      // (with the rest of HeavyLds this lets two blocks share a CU's 160 KB)
 static_assert(4 * (3 * WV_MAXOPS + WV_STASH_WORDS) <= 2 * D_MAXOPS * 256 && 4 * WV_EVCAP <= 512 && WV_QSTASH <= 528, "the wave path's rows and event stages alias the columns / the block's stage");
-template <class CB, class Sink>
-__device__ bool process_read_full(const KParams &P, const amp_dev_reads &rd, int64_t i, const DevOut &out, Sink &sink,
-                                  const EventBuf &eb, bool status_only, CB &cur, CB &tmp, uint32_t c0, int n,
-                                  int &n_final, int32_t &pos_final) {
+template <bool COOP, class CB, class Sink>
+__device__ bool process_read(const KParams &P, const amp_dev_reads &rd, int64_t i, const DevOut &out, Sink &sink,
+                             const EventBuf &eb, bool status_only, CB &cur, CB &tmp, uint32_t c0, int n,
+                             int &n_final, int32_t &pos_final) {
     uint32_t *const home = out.new_cig + (size_t)c0 + 3 * (size_t)i;
     for (int k = 0; k < n; ++k) cur.set(k, rd.cig[c0 + k]);
     const int32_t lseq = (int32_t)rd.lseq[i];
@@ -354,6 +318,8 @@ __device__ bool process_read_full(const KParams &P, const amp_dev_reads &rd, int
         NullSink ns;
         if (status_only) {
             err = count_read_walk(P, cur, st.n, st.pos, lseq, ReadBytesCached{rd.seq, boff, qual}, have_qual, ns);
+        } else if constexpr (!COOP) {
+            err = count_read_walk(P, cur, st.n, st.pos, lseq, ReadBytesCached{rd.seq, boff, qual}, have_qual, sink);
         } else {
             bool regular, plain;
             int nseg, e1 = 0, e2 = 0;
@@ -375,7 +341,7 @@ __device__ bool process_read_full(const KParams &P, const amp_dev_reads &rd, int
     if (out.ref_len) out.ref_len[i] = st.err ? 0 : reference_length(cur, st.n);
     if (out.trim_flags) out.trim_flags[i] = st.err ? (uint8_t)0 : (uint8_t)st.flags;
     if (out.status) out.status[i] = (uint8_t)err;
-    if (err) atomicAdd(&eb.ctr[2], 1ull);
+    if (err) atomicAdd(&eb.ctr[CTR_ERROR_READS], 1ull);
     n_final = st.n; pos_final = st.pos;
     return coop;
 }
@@ -423,7 +389,7 @@ __device__ void count_match_coop(const KParams &P, const amp_dev_reads &rd, int6
         NullSink ns;
         const int err = count_read_walk(P, cig, n, pos, lseq, ReadBytesCached{rd.seq, boff, qual}, true, ns);
         if (out.status) out.status[i] = (uint8_t)err;
-        if (err) atomicAdd(&eb.ctr[2], 1ull);
+        if (err) atomicAdd(&eb.ctr[CTR_ERROR_READS], 1ull);
     }
 }
 
@@ -433,7 +399,12 @@ __global__ void __launch_bounds__(256)
 k_reads_lane(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *scratch, uint32_t *counts, EventBuf eb) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rd.n_reads) return;
-    process_read_serial(P, rd, i, read_base, out, scratch, counts, eb, false);
+    const uint32_t c0 = rd.cig_off32[i];
+    const size_t slot = (size_t)c0 + 3 * (size_t)i;
+    DevSink sink{counts, eb, (uint32_t)(read_base + (uint64_t)i)};
+    CigBuf<1> cur{out.new_cig + slot}, tmp{scratch + slot};      // CIGAR ping-pong in global memory (any length)
+    int nf; int32_t pf;
+    process_read<false>(P, rd, i, out, sink, eb, false, cur, tmp, c0, (int)(rd.cig_off32[i + 1] - c0), nf, pf);
 }
 
 // Deletions / reference skips and insertion events of a read whose match bases the tile kernel
@@ -556,7 +527,7 @@ __device__ __forceinline__ void heavy_pass(HeavyLds &L, const KParams &P, const 
                 if (n + 3 <= D_MAXOPS) {
                     LdsCig256 cur{(lds_u32 *)s_cig + threadIdx.x}, tmp{(lds_u32 *)s_cig + D_MAXOPS * 256 + threadIdx.x};
                     int nf; int32_t pf;
-                    if (process_read_full(P, rd, i, out, sink, eb, status_only, cur, tmp, c0, n, nf, pf)) {
+                    if (process_read<true>(P, rd, i, out, sink, eb, status_only, cur, tmp, c0, n, nf, pf)) {
                         // cooperative entry: read, final ops | column of the lane that trimmed it << 22 | buffer B << 30, start
                         const uint32_t slot = atomicAdd(&s_ncoop, 1u) - done;
                         const uint32_t in_b = cur.p != (lds_u32 *)s_cig + threadIdx.x;
@@ -569,32 +540,20 @@ __device__ __forceinline__ void heavy_pass(HeavyLds &L, const KParams &P, const 
                     L.lng[atomicAdd(&L.nlong, 1u)] = (uint32_t)i;
                 } else {
                     // longer CIGARs ping-pong in global memory; counts go through the block's window and the
-                    // events into a slice of the list reserved once for the read: its bound is the number of
-                    // bases on (q, None) pairs, i.e. of I / P / inner-S ops of the INPUT CIGAR (trimming only
-                    // turns such bases into clips)
+                    // events into a slice of the list reserved once for the read, of ins_event_bound slots
                     const size_t slot = (size_t)c0 + 3 * (size_t)i;
                     uint32_t bound = 0;
-                    if (!status_only && P.do_count) {
-                        uint32_t lead = 0, all = 0, trail = 0;
-                        bool in_lead = true;
-                        for (int k = 0; k < n; ++k) {
-                            const uint32_t v = rd.cig[c0 + k], op = v & 15u, len = v >> 4;
-                            if (op == OP_H) continue;
-                            if (op == OP_S) { all += len; trail += len; if (in_lead) lead += len; }
-                            else { in_lead = false; trail = 0; if (op == OP_I || op == OP_P) all += len; }
-                        }
-                        bound = all - lead - (in_lead ? 0u : trail);
-                    }
+                    if (!status_only && P.do_count) bound = (uint32_t)ins_event_bound(rd.cig, c0, c0 + (uint32_t)n);
                     const unsigned shard = blockIdx.x & (EV_SHARDS - 1);
                     unsigned long long base0 = 0;
-                    if (bound) base0 = atomicAdd(&eb.ctr[16 + shard], (unsigned long long)bound);
+                    if (bound) base0 = atomicAdd(&eb.ctr[CTR_EV_SHARD0 + shard], (unsigned long long)bound);
                     const bool fits = bound && (long long)(base0 + bound) <= eb.cap;
                     SliceSink ss{sink, eb.ev + (size_t)shard * (size_t)eb.cap + base0, fits ? bound : 0u, 0u};
                     // the trim runs on this lane; a regular result leaves only its indels here (skip-ahead walk) and
                     // hands the match bases to a group of lanes, which reads the final CIGAR from the output slot
                     CigBuf<1> cur{out.new_cig + slot}, tmp{scratch + slot};
                     int nf; int32_t pf;
-                    if (process_read_full(P, rd, i, out, ss, eb, status_only, cur, tmp, c0, n, nf, pf)) {
+                    if (process_read<true>(P, rd, i, out, ss, eb, status_only, cur, tmp, c0, n, nf, pf)) {
                         const uint32_t cslot = atomicAdd(&s_ncoop, 1u) - done;
                         s_coop[cslot * 3] = (uint32_t)i;
                         s_coop[cslot * 3 + 1] = ((uint32_t)nf & 0x3FFFFFu) | (1u << 31);      // bit 31: the CIGAR is in global memory
@@ -645,8 +604,9 @@ __device__ __forceinline__ void heavy_pass(HeavyLds &L, const KParams &P, const 
                 const uint32_t c0 = rd.cig_off32[i];
                 const size_t slot = (size_t)c0 + 3 * (size_t)i;
                 WinSink sink{(lds_u32 *)s_win, base, counts, eb, (uint32_t)(read_base + (uint64_t)i), (lds_u32 *)s_ev, (lds_u32 *)&s_nev};
-                process_read_body(P, rd, i, out, sink, eb, false, CigBuf<1>{out.new_cig + slot}, CigBuf<1>{scratch + slot},
-                                  out.new_cig + slot, c0, (int)(rd.cig_off32[i + 1] - c0));
+                CigBuf<1> cur{out.new_cig + slot}, tmp{scratch + slot};
+                int nf; int32_t pf;
+                process_read<false>(P, rd, i, out, sink, eb, false, cur, tmp, c0, (int)(rd.cig_off32[i + 1] - c0), nf, pf);
             }
             flush_staged_events(eb, s_ev, &s_nev, &s_evbase);
             if (threadIdx.x == 0) { L.nlong = 0; L.nslow = 0; }
@@ -673,7 +633,7 @@ k_deferred_heavy(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, ui
                  EventBuf eb, const uint32_t *dlist, const uint32_t *dcnt, long long tiles_per_block, long long n_seg,
                  const GenGeo *geo, long long dcnt_stride, const uint32_t *segfirst) {
     __shared__ HeavyLds L;
-    if (__hip_atomic_load(&eb.ctr[24], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull) return;   // set by the tile kernel
+    if (__hip_atomic_load(&eb.ctr[CTR_HEAVY_FLAG], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull) return;   // set by the tile kernel
     if (geo) { tiles_per_block = (long long)geo->tpb; n_seg = (long long)geo->n_seg; }
     heavy_pass<true>(L, P, rd, read_base, out, scratch, counts, eb, dlist, dcnt, tiles_per_block, n_seg, dcnt_stride, segfirst);
     __syncthreads();
@@ -934,10 +894,10 @@ int amp_ctx_create(amp_ctx **out, int device, int32_t ref_len) {
     c->d_ins_at = c->d_counts + (size_t)ref_len * AMP_NSYM;
     if (hipMalloc((void **)&c->d_min_start, (size_t)ref_len * 4) != hipSuccess) return fail(AMP_ENOMEM);
     if (hipMalloc((void **)&c->d_max_end, (size_t)ref_len * 4) != hipSuccess) return fail(AMP_ENOMEM);
-    if (hipMalloc((void **)&c->d_ctr, 32 * sizeof(unsigned long long)) != hipSuccess) return fail(AMP_ENOMEM);
+    if (hipMalloc((void **)&c->d_ctr, CTR_WORDS * sizeof(unsigned long long)) != hipSuccess) return fail(AMP_ENOMEM);
     if (hipMalloc((void **)&c->d_ref, (size_t)ref_len) != hipSuccess) return fail(AMP_ENOMEM);
     if (hipMemsetAsync(c->d_counts, 0, cb, c->stream) != hipSuccess) return fail(AMP_EHIP);
-    if (hipMemsetAsync(c->d_ctr, 0, 32 * sizeof(unsigned long long), c->stream) != hipSuccess) return fail(AMP_EHIP);
+    if (hipMemsetAsync(c->d_ctr, 0, CTR_WORDS * sizeof(unsigned long long), c->stream) != hipSuccess) return fail(AMP_EHIP);
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreate(&c->ev2) != hipSuccess || hipEventCreate(&c->ev3) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_call, hipEventDisableTiming) != hipSuccess) return fail(AMP_EHIP);
@@ -1024,8 +984,7 @@ int amp_set_kernel_variant(amp_ctx *c, int variant) {  // 1 = lane-per-read kern
 
 int amp_fast_path_active(amp_ctx *c) {
     if (!c) return AMP_EINVAL;
-    const int kv = c->kernel_variant;
-    return ((kv == 0 || kv >= 4) && c->window <= 8 && c->min_quality <= 128) ? 1 : 0;
+    return fast_path_active(c->kernel_variant, c->window, c->min_quality) ? 1 : 0;
 }
 
 int amp_last_kernel_variant(amp_ctx *c) {
@@ -1060,114 +1019,83 @@ int amp_sync(amp_ctx *c) {
     return AMP_OK;
 }
 
-// Launches the read kernels for a device-resident batch on the ctx stream.
+// The batch of the last amp_process_batch call: its device copy is still in the ctx's staging buffers.
+static amp_dev_reads staged_reads(const amp_ctx *c) {
+    return amp_dev_reads{c->staged_n, c->s_pos.as<int32_t>(), c->s_flag.as<uint16_t>(), c->s_tlen.as<int32_t>(), c->s_lseq.as<uint32_t>(),
+                         c->s_cigoff.as<uint32_t>(), c->s_cig.as<uint32_t>(), c->s_seqoff.as<uint32_t>(), c->s_seq.as<uint8_t>(),
+                         c->s_qual.as<uint8_t>(), c->staged_ncig, c->staged_nbases};
+}
+
+// Launches the read kernels for a device-resident batch on the ctx stream: plan (amp_plan.hpp: which kernels, their grids,
+// the scratch layout), reserve events, size the scratch buffer, turn the plan's offsets into pointers, launch.
 static int launch_reads(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base, const amp_trim_out *o) {
     if (c->do_trim && !c->have_primers) return AMP_ESTATE;
     const int64_t n = rd->n_reads;
     c->timed = false;
     c->call_pending = false;       // (calls begun earlier are for the table as it was)
     if (n == 0) return AMP_OK;
+    DevOut out{o ? o->new_pos : nullptr, o ? o->new_ncig : nullptr, o ? o->new_cig : nullptr, o ? o->ref_len : nullptr,
+               o ? o->trim_flags : nullptr, o ? o->status : nullptr};
+    ReadPlan pl;
+    if (!plan_reads(PlanIn{n, rd->n_cig, rd->n_bases_padded, c->window, c->min_quality, c->kernel_variant, c->n_cu, c->cu_share,
+                           out.new_pos != nullptr, out.new_ncig != nullptr, out.new_cig != nullptr}, pl)) {
+        snprintf(c->err, sizeof(c->err), "a batch holds at most %u reads", DEFER_INDEX_MASK); return AMP_EINVAL;
+    }
+    const int kv = pl.kv, variant = pl.variant;
+    const TileGrid &tg = pl.tg;
+    const FastGrid &fg = pl.fg;
     // event capacity
     if (c->do_count && !c->ev_reserved) {
-        unsigned long long h[32];
-        HIPCHK(c, hipMemsetAsync(&c->d_ctr[1], 0, sizeof(unsigned long long), c->stream));
+        unsigned long long h[CTR_WORDS];
+        HIPCHK(c, hipMemsetAsync(&c->d_ctr[CTR_EVENT_BOUND], 0, sizeof(unsigned long long), c->stream));
         k_event_bound<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(n, rd->cig_off32, rd->cig, c->d_ctr);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(h, c->d_ctr, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         unsigned long long mx = 0;
-        for (int s = 0; s < EV_SHARDS; ++s) mx = std::max(mx, h[16 + s]);
-        // any shard may receive every new event; the fast kernel reserves list slots a granule at a time (a refill
-        // leaves fewer slots unused than the tile that caused it needs, plus one open granule per wave at the end)
-        const FastGrid fgb = fast_grid(n, std::max(1, c->n_cu / c->cu_share));
-        // (k_long's waves own granules too: amp_wave.hpp)
-        const int64_t need = (int64_t)(mx + 2 * h[1]) + fgb.grid * F_WAVES * (int64_t)F_EVGRAN + 2 * (int64_t)c->n_cu * L_WAVES * L_EVCAP;
+        for (int s = 0; s < EV_SHARDS; ++s) mx = std::max(mx, h[CTR_EV_SHARD0 + s]);
+        // what the fullest shard holds + twice the batch's bound + the granules its waves leave open (ReadPlan::ev_fixed)
+        const int64_t need = (int64_t)(mx + 2 * h[CTR_EVENT_BOUND]) + pl.ev_fixed;
         if (need > c->ev_cap) HIPCHK(c, grow_events(c, std::max<int64_t>(need, c->ev_cap + c->ev_cap / 2)));
     }
     KParams P{c->min_quality, c->window, c->do_trim, c->do_count, c->ref_len, c->max_primer_len, c->d_min_start, c->d_max_end, ++c->epoch};
-    if (n > 0x7FFFFFFFll) return AMP_EINVAL;
-    const size_t slots = (size_t)rd->n_cig + 3 * (size_t)n;
-    DevOut out{o ? o->new_pos : nullptr, o ? o->new_ncig : nullptr, o ? o->new_cig : nullptr, o ? o->ref_len : nullptr,
-               o ? o->trim_flags : nullptr, o ? o->status : nullptr};
-    if (n > (int64_t)DEFER_INDEX_MASK) return AMP_EINVAL;
-    // windows wider than a chunk take the serial scan of the general kernel, and the fast kernel's byte-parallel
-    // quality test is written for min_quality <= 128: no fast pass for such runs
-    // the fast kernel by the batch: its first generation (amp_fast.hpp) keeps a read in registers and is the quicker one for
-    // reads of up to 152 bases; the second (amp_fast5.hpp) consumes reads from LDS and takes them up to 304 bases (200 and
-    // 250 bp runs: 1.5 x and 1.3 x the first generation, which hands such reads to the general pass)
-    const Fast5Cfg f5 = fast5_cfg(n, rd->n_bases_padded, c->window);
-    // (a window of 8 makes the first-generation kernel spill 39 registers: 0.354 ms on the bench batch against 0.296 for the second;
-    //  windows 5-7 are its own: 0.253 / 0.269 ms at windows of 6 / 7 against 0.277 / 0.280 -- a window of 7 spills 15 registers since the
-    //  64-bit adds took four fixed ones, and is still the quicker of the two)
-    // (batches of long reads with many CIGAR ops -- three a read and more: soft clips and indels everywhere, BASELINE config 5 --
-    //  take the list-driven build of the second generation, amp_fast7.hpp: its tiles hold reads of one length class and none of
-    //  the reads that go to the general pass; on batches of uniform long reads it is the slower one, 0.49 against 0.37 ms at 250 bp)
-    const bool mixed = f5.waves != 8 && rd->n_cig >= 3 * n;
-    const int kv0 = c->kernel_variant == 0 ? (mixed ? 7 : (f5.waves == 8 && c->window != 8) ? 4 : 5) : c->kernel_variant;
-    const int kv1 = (kv0 >= 4 && (c->window > 8 || c->min_quality > 128)) ? 2 : kv0;
-    const int kv = (kv1 == 6 && c->min_quality < 1) ? 4 : kv1;      // (the third generation tells a masked base by its zeroed code: with min_quality 0 the pad bases of a row would count as kept)
-    const int variant = kv >= 5 ? 4 : kv;          // (5 and 6 differ from 4 in the fast kernel only)
-    const TileGrid tg = tile_grid(n, c->n_cu);
-    const int fast_cus = std::max(1, c->n_cu / c->cu_share);
-    const FastGrid fg = kv == 7 ? fast5_grid(n, fast_cus, F7_WAVES) : kv == 6 ? fast6_grid(n, fast_cus) : kv == 5 ? fast5_grid(n, fast_cus, f5.waves) : fast_grid(n, fast_cus);
-    // scratch: [CIGAR ping-pong slots][deferred list][list counts, debug words][variant 3 hand-over][outputs the caller
-    // did not ask for but the second pass reads][variant 4: per-block lists, their counts, the dense list, geometry]
-    // general pass of variant 4: at most four blocks per CU (its list is usually a tenth of the batch; blocks without
-    // tiles would still have to be placed on a CU one after the other), tiles per block decided on the device
-    const int64_t gen_grid = std::min<int64_t>(std::min<int64_t>(tg.grid, 4 * (int64_t)c->n_cu), 1024);      // (1024: the words of segfirst, one per block)
-    const int64_t n_tiles_max = (n + TILE - 1) / TILE;
-    const int64_t gen_tpb_max = (((n_tiles_max + gen_grid - 1) / gen_grid + T_WAVES - 1) / T_WAVES) * T_WAVES;
-    const size_t dlist_words = std::max(((size_t)tg.grid + 1) * (size_t)tg.tpb, (size_t)(n_tiles_max + gen_tpb_max + T_WAVES)) * TILE;
-    // a batch of reads with many CIGAR ops (eight a read on average: Nanopore-like) gets k_long (amp_wave.hpp) for them; the
-    // results do not depend on this choice
-    const bool long_kernel = variant == 4 && rd->n_cig >= 8 * n;
-    const size_t fast_words = variant == 4 ? (size_t)fg.grid * (size_t)fg.rpb + (size_t)fg.grid * F_WAVES + (size_t)n + 64 + 1024 + (long_kernel ? 2 * (size_t)n : 0) + (kv == 6 ? (size_t)fg.grid * (size_t)fg.rpb : kv == 7 ? 2 * (size_t)fg.grid * (size_t)fg.rpb : 0) : 0;
-    HIPCHK(c, c->scratch.ensure((slots * (out.new_cig ? 1 : 2) + (size_t)n * 7 + (size_t)tg.grid * 6 + 64 + dlist_words + fast_words) * 4));
-    uint32_t *scr = c->scratch.as<uint32_t>();
-    uint32_t *dlist = scr + slots;                                   // one segment of tpb*64 entries per tile-kernel block
-    uint32_t *dcnt = dlist + dlist_words;                             // entries used in each segment
-    uint32_t *extra = dcnt + tg.grid * 6 + 64;           // [grid] light counts | 64 | [4*grid] debug | [grid] heavy counts
-    SplitDesc sd{(int32_t *)extra, extra + n, extra + 2 * n, extra + 3 * n};      // variant 3 hand-over arrays
-    extra += 4 * n;
+    HIPCHK(c, c->scratch.ensure(pl.total_words * 4));
+    uint32_t *const scr = c->scratch.as<uint32_t>();
+    const auto at = [scr](const Region &r) { return scr + r.off; };
+    uint32_t *const dlist = at(pl.dlist), *const dcnt = at(pl.dcnt);
     c->dbg_dcnt = dcnt; c->dbg_grid = (int)tg.grid;
 #ifdef AMP_DEV
     if (c->phases & 0x100u) HIPCHK(c, hipMemsetAsync(dcnt, 0, ((size_t)tg.grid * 5 + 64) * 4, c->stream));
 #endif
-    if (!out.new_pos) { out.new_pos = (int32_t *)extra; }
-    extra += n;
-    if (!out.new_ncig) { out.new_ncig = extra; }
-    extra += n;
-    if (!out.new_cig) { out.new_cig = extra; extra += slots; }
-    uint32_t *glist = extra, *gcnt = glist + (size_t)fg.grid * (size_t)fg.rpb, *gdense = gcnt + fg.grid * F_WAVES;
-    GenGeo *geo = (GenGeo *)(gdense + ((n + 3) & ~(int64_t)3));
+    if (!out.new_pos) out.new_pos = (int32_t *)at(pl.new_pos);
+    if (!out.new_ncig) out.new_ncig = at(pl.new_ncig);
+    if (!out.new_cig) out.new_cig = at(pl.new_cig);
     const EventBuf eb{c->events.as<amp_ins_event>(), c->d_ctr, c->d_ins_at, (long long)c->ev_cap};
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (variant == 1) {
         HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-        k_reads_lane<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(P, *rd, read_base, out, scr, c->d_counts, eb);
+        k_reads_lane<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(P, *rd, read_base, out, at(pl.pingpong), c->d_counts, eb);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(c->ev2, c->stream));
     } else if (variant == 4) {
         // fast pass over the simple reads, then the general tile kernel over the list of the others
         const SplitDesc none{nullptr, nullptr, nullptr, nullptr};
+        uint32_t *const glist = at(pl.glist), *const gcnt = at(pl.gcnt), *const gdense = at(pl.gdense), *const clist = at(pl.clist);
+        uint32_t *const segfirst = at(pl.segfirst), *const llist = at(pl.llist), *const lpos = at(pl.lpos);
+        GenGeo *const geo = (GenGeo *)at(pl.geo);
+        const bool long_kernel = pl.long_kernel, direct = pl.direct;
         if (c->split_timing) HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-        uint32_t *segfirst0 = (uint32_t *)geo + 4;
-        uint32_t *clist = segfirst0 + 1024 + (long_kernel ? 2 * (size_t)n : 0);      // (variant 6) the blocks' class lists
         if ((kv == 7 ? fast7_launch(P, *rd, read_base, out, c->d_counts, eb, glist, gcnt, clist, fg, c->stream)
              : kv == 6 ? fast6_launch(P, *rd, read_base, out, c->d_counts, eb, glist, gcnt, clist, fg, c->stream)
-             : kv == 5 ? fast5_launch(P, *rd, read_base, out, c->d_counts, eb, glist, gcnt, fg, f5, c->stream)
+             : kv == 5 ? fast5_launch(P, *rd, read_base, out, c->d_counts, eb, glist, gcnt, fg, pl.f5, c->stream)
                      : fast_launch(P, *rd, read_base, out, c->d_counts, eb, glist, gcnt, fg, c->stream, dcnt + tg.grid + 64)) != 0) {
             snprintf(c->err, sizeof(c->err), "fast kernel launch failed"); return AMP_EHIP;
         }
         if (c->split_timing) HIPCHK(c, hipEventRecord(c->ev2, c->stream));
-        uint32_t *segfirst = (uint32_t *)geo + 4, *llist = segfirst + 1024, *lpos = llist + n;
-        // the list stays in the fast kernel's per-block segments and the tile kernel indexes them itself -- one launch less --
-        // unless k_long needs the dense list (to flag its reads in) or the fast kernel ran more blocks than the tile kernel's table holds
-        const bool direct = !long_kernel && fg.grid <= GL_MAXSEG;
-        const ListSrc ls{direct ? glist : nullptr, direct ? gcnt : nullptr, (int)fg.grid, (int)fg.rpb, (uint32_t)gen_grid, segfirst, geo};
-        // (ctr[26..28] -- k_long's list length, its chunk ticket, the entries left to the tile kernel -- are zeroed by the fast kernel)
+        const ListSrc ls{direct ? glist : nullptr, direct ? gcnt : nullptr, (int)fg.grid, (int)fg.rpb, (uint32_t)pl.gen_grid, segfirst, geo};
+        // (ctr[CTR_LONG_N], [CTR_LONG_TICKET], [CTR_GEN_LEFT] are zeroed by the fast kernel)
         if (!direct) {
-            k_gcompact<<<(unsigned)fg.grid, 256, 0, c->stream>>>(glist, gcnt, (int)fg.rpb, n, gdense, geo, (uint32_t)gen_grid, c->d_ctr,
+            k_gcompact<<<(unsigned)fg.grid, 256, 0, c->stream>>>(glist, gcnt, (int)fg.rpb, n, gdense, geo, (uint32_t)pl.gen_grid, c->d_ctr,
                                                                   rd->cig_off32, llist, lpos, long_kernel ? L_MAXOPS - 4 : 0);
             HIPCHK(c, hipGetLastError());
         }
@@ -1177,28 +1105,30 @@ static int launch_reads(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base,
         }
 #ifdef AMP_DEV
         if (c->phases & 0x100u) {           // stamps of the general pass alone: the fast kernel's are dropped
-            HIPCHK(c, hipMemsetAsync(&c->d_ctr[4], 0, 12 * sizeof(unsigned long long), c->stream));
-            k_tile<true, false, true><<<(unsigned)gen_grid, T_WAVES * 64, 0, c->stream>>>(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, 0, none,
+            HIPCHK(c, hipMemsetAsync(&c->d_ctr[CTR_STAMP0], 0, (CTR_EV_SHARD0 - CTR_STAMP0) * sizeof(unsigned long long), c->stream));
+            k_tile<true, false, true><<<(unsigned)pl.gen_grid, T_WAVES * 64, 0, c->stream>>>(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, 0, none,
                                                                                        direct ? nullptr : gdense, geo, (uint32_t)tg.grid, ls AMP_PHASES_ARG(c->phases));
         } else
 #endif
-        k_tile<false, false, true><<<(unsigned)gen_grid, T_WAVES * 64, 0, c->stream>>>(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, 0, none,
+        k_tile<false, false, true><<<(unsigned)pl.gen_grid, T_WAVES * 64, 0, c->stream>>>(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, 0, none,
                                                                                     direct ? nullptr : gdense, geo, (uint32_t)tg.grid, ls AMP_PHASES_ARG(c->phases));
         HIPCHK(c, hipGetLastError());
         // (the tile kernel does the indels of regular reads itself and raises the heavy pass's flag: k_deferred_light, round 1's
         // second-pass kernel for them, is no longer launched)
-        k_deferred_heavy<<<(unsigned)std::min<int64_t>(tg.grid, 2 * (int64_t)c->n_cu), 256, 0, c->stream>>>(
-            P, *rd, read_base, out, scr, c->d_counts, eb, dlist, dcnt, 0, 0, geo, (long long)tg.grid, segfirst);
+        k_deferred_heavy<<<(unsigned)pl.heavy_grid, 256, 0, c->stream>>>(
+            P, *rd, read_base, out, at(pl.pingpong), c->d_counts, eb, dlist, dcnt, 0, 0, geo, (long long)tg.grid, segfirst);
         HIPCHK(c, hipGetLastError());
     } else {
         HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+        uint32_t *const sp = at(pl.split);      // variant 3 hand-over arrays
+        const SplitDesc sd{(int32_t *)sp, sp + n, sp + 2 * n, sp + 3 * n};
         int rc = variant == 3
                      ? split_launch(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, c->n_cu, c->phases, sd, c->stream)
                      : tile_launch(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, c->n_cu, c->phases, c->stream);
         if (rc != 0) { snprintf(c->err, sizeof(c->err), "tile kernel launch failed: %s", hipGetErrorString((hipError_t)rc)); return AMP_EHIP; }
         HIPCHK(c, hipEventRecord(c->ev2, c->stream));
-        k_deferred_heavy<<<(unsigned)std::min<int64_t>(tg.grid, 2 * (int64_t)c->n_cu), 256, 0, c->stream>>>(
-            P, *rd, read_base, out, scr, c->d_counts, eb, dlist, dcnt, (long long)tg.tpb, (long long)tg.grid, nullptr, (long long)tg.grid, nullptr);
+        k_deferred_heavy<<<(unsigned)pl.heavy_grid, 256, 0, c->stream>>>(
+            P, *rd, read_base, out, at(pl.pingpong), c->d_counts, eb, dlist, dcnt, (long long)tg.tpb, (long long)tg.grid, nullptr, (long long)tg.grid, nullptr);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(c->ev3, c->stream));
@@ -1246,12 +1176,10 @@ int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const 
     HIPCHK(c, c->o_pos.ensure((size_t)n * 4)); HIPCHK(c, c->o_ncig.ensure((size_t)n * 4));
     HIPCHK(c, c->o_cig.ensure(slots * 4)); HIPCHK(c, c->o_reflen.ensure((size_t)n * 4));
     HIPCHK(c, c->o_flags.ensure((size_t)n)); HIPCHK(c, c->o_status.ensure((size_t)n));
-    amp_dev_reads rd{n, c->s_pos.as<int32_t>(), c->s_flag.as<uint16_t>(), c->s_tlen.as<int32_t>(), c->s_lseq.as<uint32_t>(),
-                     c->s_cigoff.as<uint32_t>(), c->s_cig.as<uint32_t>(), c->s_seqoff.as<uint32_t>(), c->s_seq.as<uint8_t>(),
-                     c->s_qual.as<uint8_t>(), (int64_t)n_cig, (int64_t)n_bases};
+    c->staged_n = n; c->staged_ncig = (int64_t)n_cig; c->staged_nbases = (int64_t)n_bases;
+    const amp_dev_reads rd = staged_reads(c);
     amp_trim_out dout{c->o_pos.as<int32_t>(), c->o_ncig.as<uint32_t>(), c->o_cig.as<uint32_t>(), c->o_reflen.as<int32_t>(),
                       c->o_flags.as<uint8_t>(), c->o_status.as<uint8_t>()};
-    c->staged_n = n; c->staged_ncig = (int64_t)n_cig; c->staged_nbases = (int64_t)n_bases;
     int rc = launch_reads(c, &rd, read_base, &dout);
     if (rc != AMP_OK) return rc;
     if (out) {
@@ -1307,7 +1235,7 @@ int amp_get_ins_events(amp_ctx *c, int64_t *n, amp_ins_event *buf, int64_t cap) 
     if (!c || !n) return AMP_EINVAL;
     Guard g(c);
     unsigned long long h[EV_SHARDS];
-    HIPCHK(c, hipMemcpyAsync(h, &c->d_ctr[16], sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h, &c->d_ctr[CTR_EV_SHARD0], sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int64_t total = 0;
     bool dropped = false;
@@ -1337,7 +1265,7 @@ int amp_drain_ins_events(amp_ctx *c, int64_t *n, amp_ins_event *buf, int64_t cap
     const int rc = amp_get_ins_events(c, n, buf, cap);
     if (rc != AMP_OK || !buf) return rc;
     Guard g(c);
-    HIPCHK(c, hipMemsetAsync(&c->d_ctr[16], 0, EV_SHARDS * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->d_ctr[CTR_EV_SHARD0], 0, EV_SHARDS * sizeof(unsigned long long), c->stream));
     return AMP_OK;
 }
 
@@ -1345,7 +1273,7 @@ int amp_aggregate_ins_events(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
     if (!c || !n_runs) return AMP_EINVAL;
     Guard g(c);
     unsigned long long h[EV_SHARDS];
-    HIPCHK(c, hipMemcpyAsync(h, &c->d_ctr[16], sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h, &c->d_ctr[CTR_EV_SHARD0], sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int64_t total = 0;
     for (int s = 0; s < EV_SHARDS; ++s) { if ((int64_t)h[s] > c->ev_cap) return AMP_EOVERFLOW; total += (int64_t)h[s]; }
@@ -1353,11 +1281,9 @@ int amp_aggregate_ins_events(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
     if (!buf) return AMP_OK;
     if (total > cap) return AMP_EOVERFLOW;
     amp_dev_reads staged;
-    if (!rd) {           // the batch of the last amp_process_batch call: its device copy is still in the ctx's staging buffers
+    if (!rd) {
         if (c->staged_n < 0) return AMP_ESTATE;
-        staged = amp_dev_reads{c->staged_n, c->s_pos.as<int32_t>(), c->s_flag.as<uint16_t>(), c->s_tlen.as<int32_t>(), c->s_lseq.as<uint32_t>(),
-                               c->s_cigoff.as<uint32_t>(), c->s_cig.as<uint32_t>(), c->s_seqoff.as<uint32_t>(), c->s_seq.as<uint8_t>(),
-                               c->s_qual.as<uint8_t>(), c->staged_ncig, c->staged_nbases};
+        staged = staged_reads(c);
         rd = &staged;
     }
     int64_t n_ev = 0, nr = 0;
@@ -1372,7 +1298,7 @@ int amp_aggregate_ins_events(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     *n_runs = nr;
-    if (drain) HIPCHK(c, hipMemsetAsync(&c->d_ctr[16], 0, EV_SHARDS * sizeof(unsigned long long), c->stream));
+    if (drain) HIPCHK(c, hipMemsetAsync(&c->d_ctr[CTR_EV_SHARD0], 0, EV_SHARDS * sizeof(unsigned long long), c->stream));
     return AMP_OK;
 }
 
@@ -1389,7 +1315,7 @@ int amp_debug_blocks(amp_ctx *c, uint32_t *out, int cap_blocks, int *n_blocks) {
 int amp_debug_counters(amp_ctx *c, uint64_t *out16) {  // raw device counters (development aid)
     if (!c || !out16) return AMP_EINVAL;
     Guard g(c);
-    HIPCHK(c, hipMemcpyAsync(out16, c->d_ctr, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out16, c->d_ctr, CTR_DEBUG_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->kernel_variant != 1 && c->dbg_dcnt && c->dbg_grid > 0) {      // [3]: deferred reads of the LAST batch, from the per-block list counts
         std::vector<uint32_t> h((size_t)c->dbg_grid * 6 + 64);
@@ -1407,7 +1333,7 @@ int amp_error_reads(amp_ctx *c, int64_t *n) {  // reads with a non-zero status s
     if (!c || !n) return AMP_EINVAL;
     Guard g(c);
     unsigned long long h = 0;
-    HIPCHK(c, hipMemcpyAsync(&h, &c->d_ctr[2], sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&h, &c->d_ctr[CTR_ERROR_READS], sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *n = (int64_t)h;
     return AMP_OK;
@@ -1419,7 +1345,8 @@ int amp_reset(amp_ctx *c) {
     c->call_pending = false;
     // one small kernel for the table and the counters (two hipMemsetAsync calls are three fill kernels of 5 us each)
     const size_t words = (size_t)c->ref_len * AMP_DEV_COLS;
-    k_reset<<<(unsigned)((words + 64 + 1023) / 1024), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, 64);
+    constexpr size_t ctr_words = 2 * CTR_WORDS;      // the 64-bit counters as the 32-bit words k_reset writes
+    k_reset<<<(unsigned)((words + ctr_words + 1023) / 1024), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, ctr_words);
     HIPCHK(c, hipGetLastError());
     return AMP_OK;
 }
@@ -1469,13 +1396,13 @@ int amp_call_positions(amp_ctx *c, const amp_call_params *pr, amp_pos_call *out,
     Guard g(c);
     const int32_t G = c->ref_len;
     HIPCHK(c, c->call_buf.ensure((size_t)G * sizeof(amp_pos_call)));
-    HIPCHK(c, hipMemsetAsync(&c->d_ctr[4], 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->d_ctr[CTR_CALL_RELEVANT], 0, sizeof(unsigned long long), c->stream));
     k_call<<<(unsigned)((G + 255) / 256), 256, 0, c->stream>>>(c->d_counts, c->d_ins_at, c->d_ref, G, *pr,
-                                                              c->call_buf.as<amp_pos_call>(), &c->d_ctr[4], nullptr);
+                                                              c->call_buf.as<amp_pos_call>(), &c->d_ctr[CTR_CALL_RELEVANT], nullptr);
     HIPCHK(c, hipGetLastError());
     unsigned long long nr = 0;
     HIPCHK(c, hipMemcpyAsync(out, c->call_buf.p, (size_t)G * sizeof(amp_pos_call), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&nr, &c->d_ctr[4], sizeof(nr), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&nr, &c->d_ctr[CTR_CALL_RELEVANT], sizeof(nr), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (n_relevant) *n_relevant = (int64_t)nr;
     return AMP_OK;
@@ -1627,11 +1554,9 @@ int amp_event_strings(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base, i
     if (!c || n_ev < 0 || (n_ev && (!ev || !off || !text))) return AMP_EINVAL;
     if (n_ev == 0) return AMP_OK;
     amp_dev_reads staged;
-    if (!rd) {           // the batch of the last amp_process_batch call: its device copy is still in the ctx's staging buffers
+    if (!rd) {
         if (c->staged_n < 0) return AMP_ESTATE;
-        staged = amp_dev_reads{c->staged_n, c->s_pos.as<int32_t>(), c->s_flag.as<uint16_t>(), c->s_tlen.as<int32_t>(), c->s_lseq.as<uint32_t>(),
-                               c->s_cigoff.as<uint32_t>(), c->s_cig.as<uint32_t>(), c->s_seqoff.as<uint32_t>(), c->s_seq.as<uint8_t>(),
-                               c->s_qual.as<uint8_t>(), c->staged_ncig, c->staged_nbases};
+        staged = staged_reads(c);
         rd = &staged;
     }
     for (int64_t e = 0; e < n_ev; ++e) {

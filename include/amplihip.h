@@ -249,7 +249,8 @@ int amp_debug_blocks(amp_ctx *ctx, uint32_t *out, int cap_blocks, int *n_blocks)
  * events of a batch plus 64 slots per wave of the fast kernel (8 per CU) and of the many-op kernel (24 per CU): waves
  * reserve list slots 64 at a time and leave some unused (read-out drops them). */
 int amp_reserve_events(amp_ctx *ctx, int64_t cap);
-/* 0 (default) = chosen per batch between 4, 5 and 7 by its mean padded read length (up to 152: 4), the window (8: 5) and its mean number
+/* 0 (default) = chosen per batch between 4, 5 and 7 by its mean padded read length (up to 152: 4), the window (8: 5; any other than the
+ * default of 4: 4 whatever the length, the builds for longer reads exist for that window only) and its mean number
  * of CIGAR ops (long reads with three ops a read and more: 7).  4 = the fast kernel (closed-form trim +
  * pileup of reads with one match op or one insertion / deletion of up to 152 bases, every byte loaded once) followed by the
  * general pass over the reads it hands over; 5 = its second generation (reads consumed from LDS staging buffers,
@@ -258,7 +259,8 @@ int amp_reserve_events(amp_ctx *ctx, int64_t cap);
  * per-block lists of reads binned by length (tiles of one length class, two lanes per read of more than 144 bases, reads for the
  * general pass never in a tile: amp_fast7.hpp; for batches of mixed read lengths); 2 = the fused tile kernel over every read; 1 = one-lane-per-read
  * kernels and 3 = the tile kernel's work cut into three kernels -- 1 to 3 are kept for on-GPU A/B checks (all give
- * identical results).  Runs with window > 8 or min_quality > 128 use variant 2 whatever is set. */
+ * identical results).  Runs with window > 8 or min_quality > 128 use variant 2 whichever of 0 and 4 to 7 is set, runs with
+ * min_quality 0 variant 4 where 6 is set. */
 int amp_set_kernel_variant(amp_ctx *ctx, int variant);
 /* 1 when runs with the ctx's current parameters take a fast kernel (window 1..8, min_quality <= 128, variant 0 / 4 / 5 / 6 / 7), 0 when
  * every read takes the general tile kernel (same results, about 1.5 x the time); negative on a bad ctx.  Informational: lets a

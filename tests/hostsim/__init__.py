@@ -14,7 +14,7 @@ def lib():
     if _LIB is None:
         so = os.path.join(_HERE, "libhostsim.so")
         src = os.path.join(_HERE, "hostsim.hip")
-        hdrs = [os.path.join(_HERE, "..", "..", "amplipy_amd", "csrc", h) for h in ("amp_read.hpp", "amp_bf.hpp")]
+        hdrs = [os.path.join(_HERE, "..", "..", "amplipy_amd", "csrc", h) for h in ("amp_read.hpp", "amp_bf.hpp", "amp_plan.hpp")]
         if not os.path.isfile(so) or os.path.getmtime(so) < max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in hdrs]):
             subprocess.check_call(["hipcc", "-O1", "-fPIC", "-shared", "--offload-arch=gfx950", "-o", so, src])
         _LIB = C.CDLL(so)
