@@ -226,6 +226,51 @@ def bam_native_error(msg):
     return bam_native.AmpBamError(msg)
 
 
+def gpu_sam_wanted(gpu_sam=None):
+    """The opt-in switch of the device codec for SAM text: run_amplipy(gpu_sam=...) or AMPLIPY_GPU_SAM=1."""
+    return bool(gpu_sam) if gpu_sam is not None else os.environ.get("AMPLIPY_GPU_SAM", "0") not in ("", "0")
+
+
+def open_native_sam(input_fn, output_fn):
+    """(SamTextInput, Header, AlignmentWriter or None, binary output or None, device_ok) when the device codec for SAM text can serve
+    this run (sam_native): stdin or an existing .sam file in, and stdout, a new .sam file or nothing out.
+    None otherwise: the Python codec handles those.  Same checks and messages as open_alignment_files (what it would refuse
+    is left to it).  device_ok False: the header is one the device's name table cannot take (more than 64 @SQ lines, a name
+    that is not plain text) -- every chunk of the run then goes through the Python codec."""
+    import io
+    from . import sam_native
+    if input_fn is None:
+        return None
+    from_stdin = input_fn.lower() == "stdin"
+    if from_stdin:
+        if not hasattr(sys.stdin, "buffer"):
+            return None
+    elif not isfile(input_fn) or _reads_mode(input_fn, False) != "r":
+        return None
+    to_stdout = output_fn is not None and output_fn.lower() == "stdout"
+    if to_stdout and not hasattr(sys.stdout, "buffer"):
+        return None
+    if output_fn is not None and not to_stdout and (isfile(output_fn) or not output_fn.lower().endswith(".sam")):
+        return None
+    src = sam_native.SamTextInput("-" if from_stdin else input_fn)
+    text = src.header_text()
+    hdr = bamio.Header(text, bamio._refs_from_text(text))
+    names = [n for n, _ in hdr.refs]
+    device_ok = src.header_is_plain() and len(names) <= sam_native.MAX_REFS and sum(len(n) for n in names) <= sam_native.MAX_REF_BYTES \
+        and all(n not in ("", "*", "=") and all(33 <= ord(c) < 127 for c in n) for n in names)
+    writer = outb = None
+    if output_fn is not None:
+        out_hdr = hdr.with_amplipy_pg(VERSION, " ".join(sys.argv))
+        if to_stdout:
+            outt, outb = sys.stdout, sys.stdout.buffer
+        else:
+            outb = open(output_fn, "wb")
+            outt = io.TextIOWrapper(outb, write_through=True)       # (what open(output_fn, "w") is made of)
+        writer = bamio.AlignmentWriter(None, "w", out_hdr, fileobj=outt)
+        outt.flush()
+    return src, hdr, writer, outb, device_ok
+
+
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
@@ -274,18 +319,19 @@ def _raise_for_status(status):
     raise exc("read rejected by the engine: %s (the reference raises %s here)" % (abi.READ_STATUS_NAMES[int(status)], exc.__name__))
 
 
-def _store_events(eng, ins_store, read_base):
+def _store_events(eng, ins_store, read_base, dev_reads=None):
     """A batch's insertion alleles (A:730-748) into the store: the device sorts the batch's events by (position, allele) and
     run-length encodes them (amp_aggregate_ins_events), the text of one representative per allele is gathered on
-    the device from the copy of the batch that eng.process() left there (A:736-738), and the event list starts over."""
-    runs = eng.aggregate_events(read_base=read_base, drain=True)
+    the device from the copy of the batch that eng.process() left there (A:736-738; dev_reads: from that device batch instead),
+    and the event list starts over."""
+    runs = eng.aggregate_events(dev_reads=dev_reads, read_base=read_base, drain=True)
     if runs.size == 0:
         return
     rows = np.zeros(runs.size, abi.INS_EVENT_DTYPE)
     for f in ("ref_pos", "q_from", "q_to"):
         rows[f] = runs[f]
     rows["read"] = (runs["read"].astype(np.int64) - (read_base & 0xFFFFFFFF)) & 0xFFFFFFFF     # read ids are 32-bit, relative to read_base modulo 2^32
-    length, blob = eng.event_text(rows, 0)
+    length, blob = eng.event_text(rows, 0, dev_reads=dev_reads)
     ins_store.add_text(runs["ref_pos"], length, blob, runs["count"])
 
 
@@ -293,8 +339,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 consensus_fn=None, primer_pos_offset=None, min_length=None, min_quality=None, sliding_window_width=None,
                 min_freq_consensus=None, min_freq_variants=None, min_depth_consensus=None, min_depth_variants=None,
                 unknown_symbol=None, include_no_primer=None, run_trim=False, run_variants=False, run_consensus=False,
-                device=None):
+                device=None, gpu_sam=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
+
+    gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
+    sam_native instead of the Python codec; one process only.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -360,19 +409,24 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    native = reader = writer = vcf = None
+    native = reader = writer = vcf = sam = None
     rank_error = None
+    use_sam = dist is None and gpu_sam_wanted(gpu_sam)
     try:
         if run_trim:
             print_log("Input untrimmed SAM/BAM: %s" % untrimmed_reads_fn)
             print_log("Output trimmed SAM/BAM: %s" % trimmed_reads_fn)
             native = open_native_bam(untrimmed_reads_fn, trimmed_reads_fn, rank, world, device)
-            if native is None:
+            if native is None and use_sam:
+                sam = open_native_sam(untrimmed_reads_fn, trimmed_reads_fn)
+            if native is None and sam is None:
                 reader, writer = open_alignment_files(untrimmed_reads_fn, trimmed_reads_fn)
         else:
             print_log("Input trimmed SAM/BAM: %s" % trimmed_reads_fn)
             native = open_native_bam(trimmed_reads_fn, None, rank, world)
-            if native is None:
+            if native is None and use_sam:
+                sam = open_native_sam(trimmed_reads_fn, None)
+            if native is None and sam is None:
                 reader, writer = open_alignment_files(trimmed_reads_fn, None)
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
@@ -505,6 +559,71 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if nwriter is not None and rank_error is None:
                 nwriter.close()
         seam = getattr(src, "seam", [None, None])
+    elif sam is not None:
+        # SAM text in (and SAM text or nothing out) with the switch on: chunks of whole lines are parsed, packed, trimmed / counted
+        # and, for a trimmed output, turned back into text on the device (sam_native; no per-read Python object).  A chunk
+        # with a line the device calls odd goes through the Python codec as below (same Rec / flush() code), then the next chunk
+        # is the device's again; rows stay in input order.
+        import io
+        from . import sam_native
+        src, sam_hdr, writer, outb, device_ok = sam
+        stats = sam_native.LAST_RUN_STATS
+        stats.update(device_chunks=0, python_chunks=0, records=0)
+        codec = None
+        py_reader = bamio.AlignmentReader.for_header(sam_hdr)
+        try:
+            if device_ok:
+                codec = sam_native.SamCodec(eng)
+                codec.set_references([n for n, _ in sam_hdr.refs])
+            for chunk in src:
+                info = codec.parse(chunk) if codec is not None else None
+                if info is None or info.first_odd_line >= 0:
+                    stats["python_chunks"] += 1
+                    for rec in py_reader.records_of(io.TextIOWrapper(io.BytesIO(chunk))):
+                        s_i = n_seen
+                        n_seen += 1
+                        if s_i % PROGRESS_NUM_READS == 0 and s_i != 0:
+                            print_log("Processed %d reads..." % s_i)
+                        if (rec.flag & 4) or rec.cigar is None:            # AmpliPy.py:902
+                            continue
+                        pending.append(rec)
+                        if len(pending) >= BATCH_READS:
+                            flush()
+                    flush()
+                    if writer is not None:
+                        writer._f.flush()
+                    continue
+                stats["device_chunks"] += 1
+                count = int(info.n_records)
+                for k_ in range(n_seen + (-n_seen) % PROGRESS_NUM_READS, n_seen + count, PROGRESS_NUM_READS):
+                    if k_:
+                        print_log("Processed %d reads..." % k_)
+                n_seen += count
+                if count:
+                    s_i = n_seen - 1
+                if info.n_rows == 0:
+                    continue
+                n_bases += int(info.n_bases)
+                bad_row, bad_status = codec.process(read_base)
+                if run_trim and writer is not None:
+                    text, _ = codec.format(min_length, include_no_primer)       # AmpliPy.py:910-911
+                    outb.write(text)
+                if bad_row >= 0:                  # the rows in front of it are written (A:907-911)
+                    _raise_for_status(bad_status)
+                if do_count:
+                    _store_events(eng, ins_store, read_base, dev_reads=codec.dev_reads())
+                read_base += int(info.n_rows)
+            stats["records"] = n_seen
+            print_log("SAM text codec: %d chunks on the device, %d through the Python codec" % (stats["device_chunks"], stats["python_chunks"]))
+        finally:
+            if writer is not None:
+                writer._f.flush()
+                outb.flush()
+                if outb is not getattr(sys.stdout, "buffer", None):
+                    outb.close()
+            if codec is not None:
+                codec.close()
+            src.close()
     else:
         seam = [None, None]
         try:

@@ -276,10 +276,23 @@ class AlignmentReader:
             o += l_seq
             yield Rec(qname, flag, ref_id, pos, mapq, cig, nref, npos, tlen, seq, qual, aux_bam=b[o:])
 
+    @classmethod
+    def for_header(cls, header):
+        """A text-mode reader without a file: records_of() on lines that come from elsewhere (sam_native hands it the lines of
+        a chunk the device codec passed on)."""
+        self = cls.__new__(cls)
+        self.path = None; self.mode = "r"; self._f = None; self._first = None
+        self.header = header
+        self._ref_index = {n: i for i, (n, _) in enumerate(header.refs)}
+        return self
+
     def _iter_sam(self):
         import itertools
-        src = itertools.chain([self._first], self._f) if self._first is not None else iter(())
-        for line in src:
+        return self.records_of(itertools.chain([self._first], self._f) if self._first is not None else iter(()))
+
+    def records_of(self, lines):
+        """Rec objects of an iterable of decoded lines (text mode: default encoding, universal newlines)."""
+        for line in lines:
             f = line.rstrip("\r\n").split("\t")
             if len(f) < 11:
                 continue
@@ -292,7 +305,7 @@ class AlignmentReader:
                       int(f[8]), seq, qual, aux_sam=f[11:])
 
     def close(self):
-        if self._f is not sys.stdin:
+        if self._f is not None and self._f is not sys.stdin:
             self._f.close()
 
 
@@ -300,8 +313,9 @@ class AlignmentReader:
 # writers
 # ---------------------------------------------------------------------------------------------
 class AlignmentWriter:
-    def __init__(self, path, mode, header):
-        self.mode = mode; self.header = header
+    def __init__(self, path, mode, header, fileobj=None):
+        """fileobj (text mode only): an open text file to write to in place of ``path``; it is left open by close()."""
+        self.mode = mode; self.header = header; self._own = fileobj is None
         if mode == "wb":
             self._w = BgzfWriter(open(path, "wb"))
             text = header.text.encode("utf-8")
@@ -311,7 +325,7 @@ class AlignmentWriter:
                 out += struct.pack("<i", len(nb)) + nb + struct.pack("<i", ln)
             self._w.write(bytes(out))
         else:
-            self._f = sys.stdout if path == "-" else open(path, "w")
+            self._f = fileobj if fileobj is not None else (sys.stdout if path == "-" else open(path, "w"))
             self._f.write(header.text)
 
     def _ref_name(self, i):
@@ -351,5 +365,5 @@ class AlignmentWriter:
     def close(self):
         if self.mode == "wb":
             self._w.close()
-        elif self._f is not sys.stdout:
+        elif self._f is not sys.stdout and self._own:
             self._f.close()

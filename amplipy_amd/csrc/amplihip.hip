@@ -25,6 +25,7 @@
 #include "amp_fast7.hpp"
 #include "amp_wave.hpp"
 #include "amp_ins.hpp"
+#include "amp_sam.hpp"
 
 using namespace amp;
 
@@ -790,6 +791,12 @@ __global__ void k_event_strings(amp_dev_reads rd, uint64_t read_base, int64_t n_
     uint8_t *dst = text + off[e];
     for (int32_t q = ev[e].q_from; q < ev[e].q_to; ++q) *dst++ = (uint8_t)nt16[base_code(rd.seq, boff, q)];
 }
+
+// what amp_sam.hip (a translation unit of its own) needs to know of a ctx
+namespace amp {
+hipStream_t ctx_stream(const amp_ctx *c) { return c->stream; }
+int ctx_device(const amp_ctx *c) { return c->device; }
+}  // namespace amp
 
 // ---------------------------------------------------------------------------------------
 // library / context API

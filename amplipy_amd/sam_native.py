@@ -1,0 +1,230 @@
+"""SAM text through the device codec of libamplihip.so (amp_sam_*, amplipy_amd/csrc/amp_sam.hip).
+
+Opt-in (AMPLIPY_GPU_SAM=1 or run_amplipy(gpu_sam=True)): chunks of text go to the device, a packed batch is built there, the read
+pass runs on it and the kept lines of a trimmed output come back as text -- no per-read Python object.  A chunk with a line
+the device codec calls odd (one the Python codec might not give back byte for byte, or raises on) is handed to the Python codec
+of ``bamio`` instead, so whatever that does with the line still happens.
+
+``SamCodec`` binds the C entry points; it also drives the host twin of the kernels (the same lane functions compiled with
+-DAMPSAM_HOSTSIM, ``build_twin``), which is how the codec is checked without a GPU.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import io
+import os
+import queue
+import shutil
+import subprocess
+import sys
+import threading
+
+import numpy as np
+
+from . import abi
+from .batch import ReadBatch
+
+CHUNK_BYTES = 16 << 20             # text per device chunk (AMPLIPY_SAM_CHUNK_BYTES): see the sweep in DESIGN.md section 10
+MAX_REFS = 64                      # AMP_SAM_MAX_REFS / AMP_SAM_MAX_REF_BYTES of amplihip.h
+MAX_REF_BYTES = 4096
+N_STAGES = 10
+
+ODD_REASONS = {0: "NONE", 1: "BYTE", 2: "INT", 3: "RANGE", 4: "RNAME", 5: "RNEXT", 6: "CIGAR", 7: "CIGAR_LEN", 8: "EMPTY",
+               9: "QUAL_NO_SEQ", 10: "QUAL_LEN", 11: "QUAL_CHAR", 12: "LINES"}
+
+# chunks of the last run of run_amplipy that took this path: by the device, and by the Python codec (odd chunks)
+LAST_RUN_STATS = {"device_chunks": 0, "python_chunks": 0, "records": 0}
+
+
+class AmpSamInfo(C.Structure):
+    _fields_ = [("n_lines", C.c_int64), ("n_records", C.c_int64), ("n_rows", C.c_int64), ("n_cig", C.c_int64),
+                ("n_bases", C.c_int64), ("n_bases_padded", C.c_int64), ("first_odd_line", C.c_int64),
+                ("odd_reason", C.c_int32), ("reserved", C.c_int32)]
+
+
+def twin_sources():
+    here = os.path.dirname(os.path.abspath(__file__))
+    return os.path.join(here, "csrc", "amp_sam.hip"), os.path.join(here, "..", "include", "amplihip.h")
+
+
+def build_twin(out_path, sanitize=False, main_source=None):
+    """The kernels' lane functions and a driver that runs them lane after lane, compiled for the host (no HIP needed):
+    a shared library with the amp_sam_* entry points (amp_sam_twin_set_results in place of amp_sam_process), or, with
+    ``main_source``, a program around them.  sanitize: -fsanitize=address,undefined (host code only)."""
+    src, _ = twin_sources()
+    cmd = [shutil.which("g++") or "g++", "-x", "c++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
+           "-DAMPSAM_HOSTSIM"]
+    if sanitize:
+        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+    if main_source is None:
+        cmd += ["-fPIC", "-shared", "-o", out_path, src]
+    else:
+        cmd += ["-I", os.path.dirname(src), "-o", out_path, main_source]
+    subprocess.check_call(cmd)
+    return out_path
+
+
+class SamCodec:
+    """One amp_sam: on the device of ``engine`` (lib.Engine), or the host twin when ``twin`` is the path of its library."""
+
+    def __init__(self, engine=None, twin=None):
+        if twin is not None:
+            self.L = C.CDLL(twin); self.is_twin = True; ctx = None
+        else:
+            from . import lib
+            self.L = lib.load(); self.is_twin = False; ctx = engine.h
+        self.L.amp_sam_destroy.restype = None
+        self.L.amp_sam_destroy.argtypes = [C.c_void_p]
+        self.h = C.c_void_p()
+        self._chk(self.L.amp_sam_create(ctx, C.byref(self.h)), "amp_sam_create")
+        self.info = None
+        self._out = np.zeros(1 << 16, np.uint8)
+
+    def _chk(self, rc, where):
+        if rc:
+            from .lib import AmpliHipError
+            raise AmpliHipError(rc, where)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.amp_sam_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_references(self, names):
+        enc = [n.encode("ascii") for n in names]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        self._chk(self.L.amp_sam_set_references(self.h, C.c_int32(len(enc)), arr), "amp_sam_set_references")
+
+    def parse(self, text):
+        """amp_sam_parse on bytes (whole lines): AmpSamInfo."""
+        info = AmpSamInfo()
+        buf = (C.c_char * len(text)).from_buffer_copy(text) if isinstance(text, (bytearray, memoryview)) else text
+        self._chk(self.L.amp_sam_parse(self.h, buf, C.c_int64(len(text)), C.byref(info)), "amp_sam_parse")
+        self.info = info
+        return info
+
+    def dev_reads(self):
+        rd = abi.AmpDevReads()
+        self._chk(self.L.amp_sam_reads(self.h, C.byref(rd)), "amp_sam_reads")
+        return rd
+
+    def batch(self):
+        """The batch of the last parse as a host ReadBatch (src_index = the rows' records)."""
+        n, nc, nb = int(self.info.n_rows), int(self.info.n_cig), int(self.info.n_bases_padded)
+        a = dict(pos=np.zeros(n, np.int32), flag=np.zeros(n, np.uint16), tlen=np.zeros(n, np.int32), lseq=np.zeros(n, np.uint32),
+                 cig_off=np.zeros(n + 1, np.uint64), cig=np.zeros(nc, np.uint32), seq_off=np.zeros(n + 1, np.uint64),
+                 seq=np.zeros(nb // 2, np.uint8), qual=np.zeros(nb, np.uint8))
+        src = np.zeros(n, np.int64)
+        st = abi.AmpReads(n, *[abi.ptr(a[k]) for k in ("pos", "flag", "tlen", "lseq", "cig_off", "cig", "seq_off", "seq", "qual")])
+        self._chk(self.L.amp_sam_batch_to_host(self.h, C.byref(st), C.c_void_p(abi.ptr(src))), "amp_sam_batch_to_host")
+        return ReadBatch(a["pos"], a["flag"], a["tlen"], a["lseq"], a["cig_off"], a["cig"], a["seq_off"], a["seq"], a["qual"], src_index=src)
+
+    def process(self, read_base=0):
+        """amp_sam_process: (first row with a non-zero status or -1, that status)."""
+        bad = C.c_int64(-1); st = C.c_uint8(0)
+        self._chk(self.L.amp_sam_process(self.h, C.c_uint64(read_base), C.byref(bad), C.byref(st)), "amp_sam_process")
+        return int(bad.value), int(st.value)
+
+    def twin_set_results(self, res):
+        """(twin) the results the format stage works from: an abi.TrimResult-like of this batch's rows."""
+        bad = C.c_int64(-1); st = C.c_uint8(0)
+        arrs = [np.ascontiguousarray(x) for x in (res.new_pos, res.new_ncig, res.new_cig, res.ref_len, res.trim_flags, res.status)]
+        self._chk(self.L.amp_sam_twin_set_results(self.h, *[C.c_void_p(abi.ptr(x)) for x in arrs], C.byref(bad), C.byref(st)),
+                  "amp_sam_twin_set_results")
+        return int(bad.value), int(st.value)
+
+    def format(self, min_length, include_no_primer):
+        """amp_sam_format: (bytes of the kept lines, their number)."""
+        nb = C.c_int64(0); nr = C.c_int64(0)
+        for _ in range(2):
+            rc = self.L.amp_sam_format(self.h, C.c_int32(min_length), C.c_int32(1 if include_no_primer else 0),
+                                       C.c_void_p(abi.ptr(self._out)), C.c_int64(self._out.size), C.byref(nb), C.byref(nr))
+            if rc != -6:
+                break
+            self._out = np.zeros(int(nb.value) + (int(nb.value) >> 2) + 4096, np.uint8)
+        self._chk(rc, "amp_sam_format")
+        return self._out[:int(nb.value)].tobytes(), int(nr.value)
+
+    def stage_ms(self, on=True, read=True):
+        ms = (C.c_float * N_STAGES)(*([-1.0] * N_STAGES))
+        self._chk(self.L.amp_sam_stage_ms(self.h, C.c_int(1 if on else 0), ms if read else None), "amp_sam_stage_ms")
+        return [float(x) for x in ms]
+
+
+# ---- the run's input -----------------------------------------------------------------------------------------------------------
+def decode_text(raw):
+    """Bytes -> str the way the text-mode reader of bamio does it: default encoding, universal newlines."""
+    return io.TextIOWrapper(io.BytesIO(raw)).read()
+
+
+class SamTextInput:
+    """A SAM file or stdin read as bytes: the header lines, then chunks of about ``chunk_bytes`` cut behind their last newline
+    (a final line without one is completed), read one chunk ahead of the consumer on a helper thread."""
+
+    def __init__(self, path, chunk_bytes=None):
+        self.chunk_bytes = int(chunk_bytes or os.environ.get("AMPLIPY_SAM_CHUNK_BYTES", CHUNK_BYTES))
+        self._f = sys.stdin.buffer if path == "-" else open(path, "rb")
+        head = []
+        self._carry = b""
+        while True:
+            line = self._f.readline()
+            if not line:
+                break
+            if not line.startswith(b"@"):
+                self._carry = line
+                break
+            head.append(line)
+        self.header_raw = b"".join(head)
+
+    def header_is_plain(self):
+        """True when the header is ASCII with LF / CRLF line ends only: what the device path takes the @SQ names from."""
+        h = self.header_raw.replace(b"\r\n", b"\n")
+        return b"\r" not in h and all(c < 128 for c in h)
+
+    def header_text(self):
+        text = decode_text(self.header_raw)
+        return text if text.endswith("\n") or not text else text + "\n"
+
+    def _chunks(self):
+        buf = self._carry
+        self._carry = b""
+        while True:
+            more = self._f.read(self.chunk_bytes)
+            if not more:
+                break
+            buf += more
+            cut = buf.rfind(b"\n") + 1
+            if cut:
+                yield buf[:cut]
+                buf = buf[cut:]
+        if buf:
+            yield buf + b"\n"
+
+    def __iter__(self):
+        q = queue.Queue(maxsize=1)
+
+        def run():
+            try:
+                for c in self._chunks():
+                    q.put(c)
+                q.put(None)
+            except Exception as e:          # surfaced by the consumer
+                q.put(e)
+        threading.Thread(target=run, daemon=True).start()
+        while True:
+            c = q.get()
+            if c is None:
+                return
+            if isinstance(c, Exception):
+                raise c
+            yield c
+
+    def close(self):
+        if self._f is not sys.stdin.buffer:
+            self._f.close()

@@ -382,6 +382,70 @@ int amp_deflate_sync(int device);
 int amp_deflate_blocks_cb(void *user, const uint8_t *in, int64_t n_bytes, int32_t block_bytes,
                           uint8_t *out, int64_t out_stride, int32_t out_room, uint32_t *out_len);
 
+/* ---- SAM text on the device (opt-in codec of the command line: AMPLIPY_GPU_SAM=1) ----------------------
+ * The reference reads SAM text through pysam in front of its per-read loop and writes it with out_aln.write (AmpliPy.py:296-360,
+ * :896-915); the host mirror does that per line in Python (bamio.AlignmentReader._iter_sam, AlignmentWriter.write).  An amp_sam
+ * does it for chunks of whole lines on the device of its ctx: the text goes up once, a packed batch (amp_dev_reads) is built
+ * from it in HBM, amp_process_batch_device runs on that batch, and the kept lines of a trimmed output come back as text: the
+ * input line with POS and CIGAR replaced.  An amp_sam owns device text, line and field tables, the batch, its results and
+ * the output text; the buffers grow to the largest chunk and are reused -- nothing is freed while chunks of one size go
+ * through.  Not thread-safe; all work runs on the ctx stream.
+ *
+ * A line is ODD when the Python codec might not give it back byte for byte, or would raise on it; a chunk with an odd line
+ * is not processed here at all (amp_sam_process refuses it): the caller hands that chunk's text to the Python codec, so
+ * whatever that does with the line still happens.  Reasons, in the order a line is tested: */
+#define AMP_SAM_ODD_NONE 0
+#define AMP_SAM_ODD_BYTE 1         /* a byte >= 0x80, a NUL, a '\r' that is not the single byte in front of a '\n' (any line) */
+#define AMP_SAM_ODD_INT 2          /* FLAG POS MAPQ PNEXT TLEN not -?(0|[1-9][0-9]*), or "-0" */
+#define AMP_SAM_ODD_RANGE 3        /* ... outside FLAG 0..65535, POS / PNEXT 0..2^31-1, MAPQ 0..255, TLEN int32 */
+#define AMP_SAM_ODD_RNAME 4        /* RNAME neither '*' nor an @SQ name */
+#define AMP_SAM_ODD_RNEXT 5        /* RNEXT not '*', '=' behind a named RNAME, or an @SQ name other than RNAME */
+#define AMP_SAM_ODD_CIGAR 6        /* CIGAR neither '*' nor (\d+[MIDNSHP=XB])+ : parse_cigar raises ValueError */
+#define AMP_SAM_ODD_CIGAR_LEN 7    /* an op length of 2^28 or more, or one written with leading zeros */
+#define AMP_SAM_ODD_EMPTY 8        /* SEQ or QUAL empty */
+#define AMP_SAM_ODD_QUAL_NO_SEQ 9  /* QUAL given, SEQ '*' */
+#define AMP_SAM_ODD_QUAL_LEN 10    /* QUAL given, its length is not SEQ's */
+#define AMP_SAM_ODD_QUAL_CHAR 11   /* a QUAL character below '!' */
+#define AMP_SAM_ODD_LINES 12       /* more lines than the line tables hold (n_bytes / 64 + 1024): not SAM records */
+#define AMP_SAM_MAX_REFS 64        /* @SQ names the device table holds; a header with more keeps the run on the Python codec */
+#define AMP_SAM_MAX_REF_BYTES 4096 /* ... and their bytes */
+#define AMP_SAM_N_STAGES 10
+
+typedef struct amp_sam amp_sam;
+typedef struct amp_sam_info {
+    int64_t n_lines;         /* '\n' of the chunk */
+    int64_t n_records;       /* lines of 11 fields and more (what _iter_sam yields; fewer fields: skipped, not counted) */
+    int64_t n_rows;          /* records the loop does not skip (A:902): mapped, CIGAR not '*' */
+    int64_t n_cig, n_bases, n_bases_padded;     /* of the rows */
+    int64_t first_odd_line;  /* -1: none.  With an odd line the counts from n_rows on leave out the odd lines and mean nothing */
+    int32_t odd_reason, reserved;
+} amp_sam_info;
+int amp_sam_create(amp_ctx *ctx, amp_sam **out);
+void amp_sam_destroy(amp_sam *s);
+/* header.refs of bamio.AlignmentReader: the @SQ SN names in header order, once per run and before the first parse. */
+int amp_sam_set_references(amp_sam *s, int32_t n_ref, const char *const *names);
+/* bamio._iter_sam + ReadBatch.from_segments (pysam's parsing in front of A:896, the skip of A:902) for n_bytes < 1 GiB of host
+ * text that ends with '\n' (AMP_EINVAL otherwise; n_bytes 0: no line, AMP_OK).  Waits for the device once, for the sizes. */
+int amp_sam_parse(amp_sam *s, const uint8_t *text, int64_t n_bytes, amp_sam_info *info);
+/* The batch of the last parse: device pointers, valid until the next parse. */
+int amp_sam_reads(amp_sam *s, amp_dev_reads *out);
+/* The same batch copied into the host arrays dst points to (dst->n_reads must be n_rows; 64-bit offsets as in amp_reads) and
+ * the number of each row's record among the chunk's records (ReadBatch.src_index): tests and tools. */
+int amp_sam_batch_to_host(amp_sam *s, const amp_reads *dst, int64_t *src_index);
+/* A:896-915 for the chunk: amp_process_batch_device on the batch, the result arrays owned by s.  *first_bad_row = the first
+ * row whose status is not AMP_RS_OK and *its_status that status; -1 and 0 when there is none.  AMP_ESTATE for an odd chunk. */
+int amp_sam_process(amp_sam *s, uint64_t read_base, int64_t *first_bad_row, uint8_t *its_status);
+/* AlignmentWriter.write(r, pos=, cigar=) (out_aln.write, A:911) for every row in front of the first failing one that passes
+ * ref_len >= min_length and (trimmed at a primer or include_no_primer) (A:910): the input line with field 4 = new_pos + 1,
+ * field 6 = the new CIGAR, a '\r' before the '\n' dropped.  AMP_EOVERFLOW with *n_bytes = the size needed when cap is
+ * short; AMP_EINVAL before amp_sam_process. */
+int amp_sam_format(amp_sam *s, int32_t min_length, int32_t include_no_primer, uint8_t *out, int64_t cap, int64_t *n_bytes,
+                   int64_t *n_rows_written);
+/* Development aid: ms[AMP_SAM_N_STAGES] of the last chunk from HIP events on the ctx stream -- [0] copy up, [1] scan and
+ * ranks, [2] lines and tabs, [3] records and rows, [4] pack, [6] the read pass, [8] format kernels, [9] copy down ([5], [7]:
+ * host time between the calls).  on != 0 records the events from the next call on. */
+int amp_sam_stage_ms(amp_sam *s, int on, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
