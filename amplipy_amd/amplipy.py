@@ -231,6 +231,22 @@ def gpu_sam_wanted(gpu_sam=None):
     return bool(gpu_sam) if gpu_sam is not None else os.environ.get("AMPLIPY_GPU_SAM", "0") not in ("", "0")
 
 
+def gpu_bam_wanted(gpu_bam=None):
+    """The opt-in switch of the device codec for BAM input: run_amplipy(gpu_bam=...) or AMPLIPY_GPU_BAM=1."""
+    return bool(gpu_bam) if gpu_bam is not None else os.environ.get("AMPLIPY_GPU_BAM", "0") not in ("", "0")
+
+
+def open_device_bam(input_fn):
+    """A bam_device.DeviceBamInput when the device codec for BAM input can serve this run: an existing BAM
+    file in, no trimmed reads out.  None otherwise -- under the conditions open_native_bam serves: whatever else the input is,
+    the other codecs handle (and refuse) it as before."""
+    if input_fn is None or input_fn.lower() == "stdin" or not isfile(input_fn) or _reads_mode(input_fn, False) != "rb":
+        return None
+    if os.environ.get("AMPLIPY_PYTHON_BAM"):
+        return None
+    return input_fn
+
+
 def open_native_sam(input_fn, output_fn):
     """(SamTextInput, Header, AlignmentWriter or None, binary output or None, device_ok) when the device codec for SAM text can serve
     this run (sam_native): stdin or an existing .sam file in, and stdout, a new .sam file or nothing out.
@@ -339,11 +355,13 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 consensus_fn=None, primer_pos_offset=None, min_length=None, min_quality=None, sliding_window_width=None,
                 min_freq_consensus=None, min_freq_variants=None, min_depth_consensus=None, min_depth_variants=None,
                 unknown_symbol=None, include_no_primer=None, run_trim=False, run_variants=False, run_consensus=False,
-                device=None, gpu_sam=None):
+                device=None, gpu_sam=None, gpu_bam=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
     sam_native instead of the Python codec; one process only.
+    gpu_bam (default: AMPLIPY_GPU_BAM, off): a BAM file in and no trimmed reads out (variants, consensus) is inflated, indexed and
+    decoded on the device (bam_device) instead of by libampbam; one process only.  Runs that write trimmed reads keep libampbam.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -409,24 +427,30 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    native = reader = writer = vcf = sam = None
+    native = reader = writer = vcf = sam = bamdev = None
     rank_error = None
     use_sam = dist is None and gpu_sam_wanted(gpu_sam)
+    use_bam = dist is None and gpu_bam_wanted(gpu_bam)
     try:
         if run_trim:
             print_log("Input untrimmed SAM/BAM: %s" % untrimmed_reads_fn)
             print_log("Output trimmed SAM/BAM: %s" % trimmed_reads_fn)
             native = open_native_bam(untrimmed_reads_fn, trimmed_reads_fn, rank, world, device)
+            if native is not None and use_bam:
+                print_log("BAM device codec: this run writes trimmed reads, the host codec reads the input")
             if native is None and use_sam:
                 sam = open_native_sam(untrimmed_reads_fn, trimmed_reads_fn)
             if native is None and sam is None:
                 reader, writer = open_alignment_files(untrimmed_reads_fn, trimmed_reads_fn)
         else:
             print_log("Input trimmed SAM/BAM: %s" % trimmed_reads_fn)
-            native = open_native_bam(trimmed_reads_fn, None, rank, world)
-            if native is None and use_sam:
+            if use_bam:
+                bamdev = open_device_bam(trimmed_reads_fn)
+            if bamdev is None:
+                native = open_native_bam(trimmed_reads_fn, None, rank, world)
+            if native is None and bamdev is None and use_sam:
                 sam = open_native_sam(trimmed_reads_fn, None)
-            if native is None and sam is None:
+            if native is None and sam is None and bamdev is None:
                 reader, writer = open_alignment_files(trimmed_reads_fn, None)
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
@@ -559,6 +583,41 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if nwriter is not None and rank_error is None:
                 nwriter.close()
         seam = getattr(src, "seam", [None, None])
+    elif bamdev is not None:
+        # BAM in, no trimmed reads out, with the switch on: the compressed bytes of a piece of whole BGZF blocks go to the device,
+        # which inflates them, checks every block's CRC, indexes the records and decodes the rows into the packed batch
+        # (bam_device; the next piece is read and copied up while this one is there).  The read pass runs on that batch.
+        from . import bam_device
+        stats = bam_device.LAST_RUN_STATS
+        stats.update(pieces=0, blocks_device=0, blocks_host=0, index_rounds=0, waits=0, records=0, bytes_up=0, bytes_file=0)
+        refuse = os.environ.get("AMPLIPY_GPU_BAM_REFUSE_BLOCK") if os.environ.get("AMPLIPY_DEV") == "1" else None
+        codec = None
+        try:
+            src = bam_device.DeviceBamInput(bamdev)
+            codec = bam_device.BamCodec(eng)
+            for info, running in bam_device.walk(codec, src, refuse_block=int(refuse) if refuse else None):
+                stats.update(running)
+                count = int(info.n_records)
+                for k_ in range(n_seen + (-n_seen) % PROGRESS_NUM_READS, n_seen + count, PROGRESS_NUM_READS):
+                    if k_:
+                        print_log("Processed %d reads..." % k_)
+                n_seen += count
+                if count:
+                    s_i = n_seen - 1
+                if info.n_rows == 0:
+                    continue
+                n_bases += int(info.n_bases)
+                bad_row, bad_status = codec.process(read_base)
+                if bad_row >= 0:
+                    _raise_for_status(bad_status)
+                if do_count:
+                    _store_events(eng, ins_store, read_base, dev_reads=codec.dev_reads())
+                read_base += int(info.n_rows)
+            print_log("BAM device codec: %d pieces, %d blocks on the device, %d through the host codec, %d index rounds"
+                      % (stats["pieces"], stats["blocks_device"], stats["blocks_host"], stats["index_rounds"]))
+        finally:
+            if codec is not None:
+                codec.close()
     elif sam is not None:
         # SAM text in (and SAM text or nothing out) with the switch on: chunks of whole lines are parsed, packed, trimmed / counted
         # and, for a trimmed output, turned back into text on the device (sam_native; no per-read Python object).  A chunk

@@ -16,7 +16,7 @@ EXPORTS = [
     "ampbam_version", "ampbam_strerror", "ampbam_open", "ampbam_close", "ampbam_last_error", "ampbam_n_records",
     "ampbam_header_text", "ampbam_n_refs", "ampbam_ref", "ampbam_decode", "ampbam_writer_open", "ampbam_write_rows",
     "ampbam_writer_close", "ampbam_writer_header_bytes", "ampbam_write_batch", "ampbam_open_range", "ampbam_open_range_at", "ampbam_part_range", "ampbam_crc32", "ampbam_inflate_raw",
-    "ampbam_writer_set_deflater", "ampbam_writer_deflater_stats",
+    "ampbam_writer_set_deflater", "ampbam_writer_deflater_stats", "ampbam_block_table",
 ]
 # ampbam_deflate_fn of include/ampbam.h
 DEFLATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_uint32))
@@ -47,6 +47,8 @@ def load():
         L.ampbam_inflate_raw.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         L.ampbam_crc32.restype = C.c_uint32
         L.ampbam_crc32.argtypes = [C.c_void_p, C.c_int64]
+        L.ampbam_block_table.restype = C.c_int64
+        L.ampbam_block_table.argtypes = [C.c_char_p, C.c_void_p, C.c_int64]
         L.ampbam_close.restype = None
         L.ampbam_close.argtypes = [C.c_void_p]
         L.ampbam_writer_set_deflater.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -10,13 +10,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # translation units of libamplihip.so: the kernels + C ABI, and the insertion-event aggregation (its sort headers triple the
 # compile time of whatever includes them, so it is built -- and cached -- on its own), the DEFLATE encoder of the BAM writer, and
-# the codec for SAM text
-UNITS = ["amplihip.hip", "amp_ins.hip", "amp_deflate.hip", "amp_sam.hip"]
+# the codecs for SAM text and for BAM input
+UNITS = ["amplihip.hip", "amp_ins.hip", "amp_deflate.hip", "amp_sam.hip", "amp_bgzf.hip"]
 SRC = os.path.join(CSRC, "amplihip.hip")
 HEADERS = [os.path.join(_HERE, "..", "include", "amplihip.h")] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
 UNIT_DEPS = {"amplihip.hip": HEADERS, "amp_ins.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_ins.hpp")],
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
-             "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_sam.hpp")]}
+             "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_sam.hpp")],
+             "amp_bgzf.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_sam.hpp"), os.path.join(CSRC, "amp_bgzf.hpp")]}
 DEPS = [os.path.join(CSRC, u) for u in UNITS] + HEADERS
 OUT = os.path.join(_HERE, "libamplihip.so")
 OBJ_DIR = os.path.join(_HERE, "build")

@@ -798,6 +798,22 @@ int ampbam_open_range_at(const char *path, int n_threads, int part, int n_parts,
     return AMPBAM_OK;
 }
 
+int64_t ampbam_block_table(const char *path, uint64_t *table, int64_t cap) {
+    if (!path || cap < 0 || (cap && !table)) return AMPBAM_EINVAL;
+    MappedFile raw;
+    int rc = raw.map(path);
+    if (rc) return rc;
+    std::vector<Block> blocks;
+    size_t total = 0;
+    try { rc = block_table(raw, blocks, total); } catch (const std::bad_alloc &) { return AMPBAM_ENOMEM; }
+    if (rc) return rc;
+    if (blocks.empty()) return AMPBAM_EFORMAT;
+    for (size_t k = 0; k < blocks.size() && (int64_t)k < cap; ++k) {
+        table[4 * k] = blocks[k].in_off; table[4 * k + 1] = blocks[k].in_len; table[4 * k + 2] = blocks[k].out_len; table[4 * k + 3] = blocks[k].crc;
+    }
+    return (int64_t)blocks.size();
+}
+
 int ampbam_part_range(const ampbam_file *f, uint64_t *first, uint64_t *end) {
     if (!f || !first || !end) return AMPBAM_EINVAL;
     *first = f->part_first; *end = f->part_end;

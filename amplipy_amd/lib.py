@@ -31,6 +31,8 @@ EXPORTS = [
     "amp_deflate_blocks", "amp_deflate_blocks_device", "amp_deflate_sync", "amp_deflate_blocks_cb",
     "amp_sam_create", "amp_sam_destroy", "amp_sam_set_references", "amp_sam_parse", "amp_sam_reads", "amp_sam_batch_to_host",
     "amp_sam_process", "amp_sam_format", "amp_sam_stage_ms",
+    "amp_bam_create", "amp_bam_destroy", "amp_bam_feed", "amp_bam_dev_refuse", "amp_bam_refused", "amp_bam_patch_block", "amp_bam_reindex",
+    "amp_bam_reads", "amp_bam_batch_to_host", "amp_bam_image_to_host", "amp_bam_process", "amp_bam_stage_ms",
 ]
 
 

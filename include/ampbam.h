@@ -74,6 +74,11 @@ int ampbam_open_range_at(const char *path, int n_threads, int part, int n_parts,
 /* Offsets in the file's INFLATED stream of the part's first record and of the byte behind its last record (equal for a
  * part without records; 0 / 0 ... for a file opened with ampbam_open: header end / stream end are not tracked there). */
 int ampbam_part_range(const ampbam_file *f, uint64_t *first, uint64_t *end);
+/* The BGZF block table of a file, read from the 18-byte headers and 8-byte trailers alone (nothing is inflated): per block four
+ * values in table[4 * k ..] -- file offset and length of its raw DEFLATE stream, ISIZE, CRC-32.  Returns the number of blocks
+ * (at most cap of them are written; call with cap 0 for the size) or a negative ampbam_rc: what ampbam_open refuses in a
+ * block header it refuses here.  For readers that inflate elsewhere (the device codec of include/amplihip.h). */
+int64_t ampbam_block_table(const char *path, uint64_t *table, int64_t cap);
 void ampbam_close(ampbam_file *f);
 const char *ampbam_last_error(const ampbam_file *f);
 

@@ -446,6 +446,71 @@ int amp_sam_format(amp_sam *s, int32_t min_length, int32_t include_no_primer, ui
  * host time between the calls).  on != 0 records the events from the next call on. */
 int amp_sam_stage_ms(amp_sam *s, int on, float *ms);
 
+/* ---- BAM input on the device (opt-in codec of the command line: AMPLIPY_GPU_BAM=1) ---------------------
+ * The reference reads BAM through pysam (AmpliPy.py:296-324, :896) and skips unmapped reads and reads without a CIGAR (A:902);
+ * the host codec does it in libampbam: ampbam_open_range_at (BGZF inflate, CRC-32 of every block, record index) and
+ * ampbam_decode (the packed batch), after which the decoded batch is copied to the device.  An amp_bam takes the COMPRESSED
+ * bytes of a piece of the file -- whole BGZF blocks, with the block table libampbam reads from their headers and trailers
+ * (ampbam_block_table) -- and does the rest on the device of its ctx: every block's raw DEFLATE stream is inflated into the
+ * piece's image [carry | inflated blocks] (carry: the bytes of the last image behind its last complete record), every block's
+ * CRC-32 is compared with its trailer, the records are indexed from the KNOWN start of the first one, and the rows are
+ * decoded into an amp_dev_reads on which amp_process_batch_device runs where it lies.  The buffers belong to the amp_bam, grow
+ * to the largest piece and are not freed during a run.  Not thread-safe; all work runs on the ctx stream.
+ *
+ * A block the device refuses -- its stream breaks a rule of RFC 1951, does not end after exactly ISIZE bytes, or its CRC
+ * differs -- writes nothing outside its own range of the image and is handed back: the caller inflates it on the host
+ * (ampbam_inflate_raw / zlib, CRC checked), patches the bytes in and asks for the index again.  On a valid file no block is. */
+#define AMP_BAM_IMAGE_LIMIT (256ll << 20) /* bytes of an image: carry + the ISIZE sum of a piece.  A record is at most 2^27 + 4 bytes
+                                           * (a longer block_size is a format error), so pieces of up to 120 MiB inflated always fit */
+#define AMP_BAM_N_STAGES 7
+typedef struct amp_bam amp_bam;
+typedef struct amp_bam_block {   /* one BGZF block of a piece */
+    uint32_t in_off, in_len;     /* its raw DEFLATE stream in the piece's compressed bytes */
+    uint32_t out_len, crc;       /* ISIZE and CRC-32 of its trailer */
+} amp_bam_block;
+typedef struct amp_bam_info {
+    int64_t n_blocks, n_inflated;     /* of this piece: blocks, their ISIZE sum */
+    int64_t image_bytes, carry_in;    /* the image [carry | inflated]; bytes carried in from the piece before */
+    int64_t carry_out;                /* bytes behind the last complete record: they open the next image */
+    int64_t next_first;               /* > 0: the first record starts that many bytes behind this image (a header longer than a piece) */
+    int64_t n_records;                /* records that END in this image */
+    int64_t n_rows;                   /* ... that the loop does not skip (A:902) */
+    int64_t n_cig, n_bases, n_bases_padded;     /* of the rows */
+    int64_t n_refused;                /* blocks handed back; the counts above are 0 until they are patched and re-indexed */
+    int64_t index_rounds;             /* link / jump / settle rounds the index took (1: every guessed record start was right) */
+    int64_t waits;                    /* waits for the device this piece cost (1 on the ordinary path) */
+    int64_t bytes_up;                 /* host-to-device bytes of the piece: compressed bytes + block table */
+    int32_t bad_record, reserved;     /* a record with block_size < 32 or > 2^27, or a body longer than block_size: the `bad` of index_records */
+} amp_bam_info;
+int amp_bam_create(amp_ctx *ctx, amp_bam **out);
+void amp_bam_destroy(amp_bam *s);
+/* ampbam_open_range_at + ampbam_decode for a piece.  first_off >= 0: the first record starts at that offset of the inflated
+ * blocks and nothing is carried in (the file's first piece: the header's end); < 0: the image starts with the carry, whose first
+ * byte is a record's.  rec_base = records in front of this piece (src_index counts from it); n_ref = references of the header
+ * (the plausibility test of guessed record starts).  AMP_EOVERFLOW when the image would pass AMP_BAM_IMAGE_LIMIT. */
+int amp_bam_feed(amp_bam *s, const uint8_t *comp, int64_t n_comp, const amp_bam_block *blocks, int64_t n_blocks, int64_t first_off,
+                 int32_t n_ref, int64_t rec_base, amp_bam_info *info);
+/* Development aid: the next feed hands block k of its piece back although it inflates (the test of the host fallback). */
+int amp_bam_dev_refuse(amp_bam *s, int64_t k);
+/* The blocks the last feed handed back (piece-relative numbers), the host's bytes for one of them, and the index and decode
+ * again once all of them are patched. */
+int amp_bam_refused(amp_bam *s, int64_t *idx, int64_t cap, int64_t *n);
+int amp_bam_patch_block(amp_bam *s, int64_t k, const uint8_t *bytes, int64_t n_bytes);
+int amp_bam_reindex(amp_bam *s, amp_bam_info *info);
+/* The batch of the last feed (ampbam_decode's rows): device pointers, valid until the next feed. */
+int amp_bam_reads(amp_bam *s, amp_dev_reads *out);
+/* The same batch copied to host arrays (dst->n_reads must be n_rows; cig, seq and qual with their 16 bytes of slack) and each
+ * row's record number: tests and tools. */
+int amp_bam_batch_to_host(amp_bam *s, const amp_reads *dst, int64_t *src_index);
+/* The image of the last feed and the offsets of its records in it (either may be NULL): tests and tools.  Both stay on the
+ * device until the next feed -- what a device re-encoder of trimmed records would copy the unchanged parts from. */
+int amp_bam_image_to_host(amp_bam *s, uint8_t *image, int64_t image_cap, uint32_t *rec_off, int64_t rec_cap);
+/* A:896-915 for the piece: amp_process_batch_device on the batch, the result arrays owned by s (as amp_sam_process). */
+int amp_bam_process(amp_bam *s, uint64_t read_base, int64_t *first_bad_row, uint8_t *its_status);
+/* Development aid: ms[AMP_BAM_N_STAGES] of the last piece from HIP events on the ctx stream -- [0] copy up, [1] inflate, [2] CRC,
+ * [3] record index, [4] decode, [6] the read pass ([5]: the wait and host time between).  on != 0 records from the next call on. */
+int amp_bam_stage_ms(amp_bam *s, int on, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
