@@ -226,14 +226,19 @@ def bam_native_error(msg):
     return bam_native.AmpBamError(msg)
 
 
+def gpu_codec_wanted(arg, env_name):
+    """The opt-in switch of a device codec: the argument of run_amplipy when it is given, else the variable set to anything but 0."""
+    return bool(arg) if arg is not None else os.environ.get(env_name, "0") not in ("", "0")
+
+
 def gpu_sam_wanted(gpu_sam=None):
-    """The opt-in switch of the device codec for SAM text: run_amplipy(gpu_sam=...) or AMPLIPY_GPU_SAM=1."""
-    return bool(gpu_sam) if gpu_sam is not None else os.environ.get("AMPLIPY_GPU_SAM", "0") not in ("", "0")
+    """The device codec for SAM text: run_amplipy(gpu_sam=...) or AMPLIPY_GPU_SAM=1."""
+    return gpu_codec_wanted(gpu_sam, "AMPLIPY_GPU_SAM")
 
 
 def gpu_bam_wanted(gpu_bam=None):
-    """The opt-in switch of the device codec for BAM input: run_amplipy(gpu_bam=...) or AMPLIPY_GPU_BAM=1."""
-    return bool(gpu_bam) if gpu_bam is not None else os.environ.get("AMPLIPY_GPU_BAM", "0") not in ("", "0")
+    """The device codec for BAM input: run_amplipy(gpu_bam=...) or AMPLIPY_GPU_BAM=1."""
+    return gpu_codec_wanted(gpu_bam, "AMPLIPY_GPU_BAM")
 
 
 def open_device_bam(input_fn):
@@ -495,6 +500,34 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
 
     n_seen = 0                           # records this rank has gone through (all of them when there is one rank)
     n_bases = 0                          # ... and their bases (the measure the shares of a multi-rank run should be equal in: SURVEY 8e)
+
+    def progress(count):
+        """The progress lines of the next ``count`` records."""
+        for k_ in range(n_seen + (-n_seen) % PROGRESS_NUM_READS, n_seen + count, PROGRESS_NUM_READS):
+            if k_:
+                print_log("Processed %d reads..." % k_)
+
+    def device_piece(codec, info, emit=None):
+        """A piece or chunk whose batch a device codec has built (info: n_records, n_rows, n_bases): counted, through the read pass
+        where it lies, ``emit`` run on its results, its events stored."""
+        nonlocal n_seen, s_i, n_bases, read_base
+        count = int(info.n_records)
+        progress(count)
+        n_seen += count
+        if count:
+            s_i = n_seen - 1
+        if info.n_rows == 0:
+            return
+        n_bases += int(info.n_bases)
+        bad_row, bad_status = codec.process(read_base)
+        if emit is not None:
+            emit()
+        if bad_row >= 0:                  # the rows in front of it are written (A:907-911)
+            _raise_for_status(bad_status)
+        if do_count:
+            _store_events(eng, ins_store, read_base, dev_reads=codec.dev_reads())
+        read_base += int(info.n_rows)
+
     seam = [None, None]
     if rank_error is not None:
         pass                              # (nothing was opened: straight to the exchange)
@@ -530,9 +563,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 for first in range(0, piece.n_records, NATIVE_BATCH_READS):
                     count = min(NATIVE_BATCH_READS, piece.n_records - first)
                     batch, _ = piece.decode(first, count)
-                    for k_ in range(n_seen + (-n_seen) % PROGRESS_NUM_READS, n_seen + count, PROGRESS_NUM_READS):
-                        if k_:
-                            print_log("Processed %d reads..." % k_)
+                    progress(count)
                     n_seen += count
                     s_i = n_seen - 1
                     if batch.n == 0:
@@ -597,22 +628,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             codec = bam_device.BamCodec(eng)
             for info, running in bam_device.walk(codec, src, refuse_block=int(refuse) if refuse else None):
                 stats.update(running)
-                count = int(info.n_records)
-                for k_ in range(n_seen + (-n_seen) % PROGRESS_NUM_READS, n_seen + count, PROGRESS_NUM_READS):
-                    if k_:
-                        print_log("Processed %d reads..." % k_)
-                n_seen += count
-                if count:
-                    s_i = n_seen - 1
-                if info.n_rows == 0:
-                    continue
-                n_bases += int(info.n_bases)
-                bad_row, bad_status = codec.process(read_base)
-                if bad_row >= 0:
-                    _raise_for_status(bad_status)
-                if do_count:
-                    _store_events(eng, ins_store, read_base, dev_reads=codec.dev_reads())
-                read_base += int(info.n_rows)
+                device_piece(codec, info)
             print_log("BAM device codec: %d pieces, %d blocks on the device, %d through the host codec, %d index rounds"
                       % (stats["pieces"], stats["blocks_device"], stats["blocks_host"], stats["index_rounds"]))
         finally:
@@ -630,6 +646,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         stats.update(device_chunks=0, python_chunks=0, records=0)
         codec = None
         py_reader = bamio.AlignmentReader.for_header(sam_hdr)
+
+        def write_kept():
+            if run_trim and writer is not None:
+                text, _ = codec.format(min_length, include_no_primer)       # AmpliPy.py:910-911
+                outb.write(text)
         try:
             if device_ok:
                 codec = sam_native.SamCodec(eng)
@@ -653,25 +674,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                         writer._f.flush()
                     continue
                 stats["device_chunks"] += 1
-                count = int(info.n_records)
-                for k_ in range(n_seen + (-n_seen) % PROGRESS_NUM_READS, n_seen + count, PROGRESS_NUM_READS):
-                    if k_:
-                        print_log("Processed %d reads..." % k_)
-                n_seen += count
-                if count:
-                    s_i = n_seen - 1
-                if info.n_rows == 0:
-                    continue
-                n_bases += int(info.n_bases)
-                bad_row, bad_status = codec.process(read_base)
-                if run_trim and writer is not None:
-                    text, _ = codec.format(min_length, include_no_primer)       # AmpliPy.py:910-911
-                    outb.write(text)
-                if bad_row >= 0:                  # the rows in front of it are written (A:907-911)
-                    _raise_for_status(bad_status)
-                if do_count:
-                    _store_events(eng, ins_store, read_base, dev_reads=codec.dev_reads())
-                read_base += int(info.n_rows)
+                device_piece(codec, info, emit=write_kept)
             stats["records"] = n_seen
             print_log("SAM text codec: %d chunks on the device, %d through the Python codec" % (stats["device_chunks"], stats["python_chunks"]))
         finally:

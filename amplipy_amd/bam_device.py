@@ -12,17 +12,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import queue
-import shutil
 import struct
-import subprocess
-import threading
 import zlib
 
 import numpy as np
 
-from . import abi, bam_native
-from .batch import ReadBatch
+from . import abi, bam_native, devcodec
 
 # Compressed bytes of a piece (AMPLIPY_GPU_BAM_PIECE_BYTES).  A CU holds twelve decoders (13,344 bytes of LDS each), the chip
 # 3,072; a BGZF block of an amplicon BAM is 8-10 KB compressed, so 16 MB are about 1,800 blocks: one wave of work for more
@@ -58,17 +53,7 @@ def build_twin(out_path, sanitize=False, main_source=None):
     """The kernels' lane functions and a driver that runs them lane after lane, compiled for the host (no HIP needed): a shared
     library with the amp_bam_* entry points (without amp_bam_process), or, with ``main_source``, a program around the lane
     functions.  sanitize: -fsanitize=address,undefined (host code only)."""
-    src, _ = twin_sources()
-    cmd = [shutil.which("g++") or "g++", "-x", "c++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-           "-DAMPBGZF_HOSTSIM"]
-    if sanitize:
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
-    if main_source is None:
-        cmd += ["-fPIC", "-shared", "-o", out_path, src]
-    else:
-        cmd += ["-I", os.path.dirname(src), "-o", out_path, main_source]
-    subprocess.check_call(cmd)
-    return out_path
+    return devcodec.build_twin(twin_sources()[0], "AMPBGZF_HOSTSIM", out_path, sanitize, main_source)
 
 
 def format_error(path):
@@ -153,36 +138,11 @@ def cut_pieces(table, piece_bytes):
     return pieces
 
 
-class BamCodec:
+class BamCodec(devcodec.DeviceCodec):
     """One amp_bam: on the device of ``engine`` (lib.Engine), or the host twin when ``twin`` is the path of its library."""
 
     def __init__(self, engine=None, twin=None):
-        if twin is not None:
-            self.L = C.CDLL(twin); self.is_twin = True; ctx = None
-        else:
-            from . import lib
-            self.L = lib.load(); self.is_twin = False; ctx = engine.h
-        self.L.amp_bam_destroy.restype = None
-        self.L.amp_bam_destroy.argtypes = [C.c_void_p]
-        self.h = C.c_void_p()
-        self._chk(self.L.amp_bam_create(ctx, C.byref(self.h)), "amp_bam_create")
-        self.info = None
-
-    def _chk(self, rc, where):
-        if rc:
-            from .lib import AmpliHipError
-            raise AmpliHipError(rc, where)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.amp_bam_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__("amp_bam", N_STAGES, engine, twin)
 
     def feed(self, comp, blocks, first_off, n_ref, rec_base=0):
         """amp_bam_feed: comp = the piece's bytes (numpy uint8 or bytes), blocks = (n, 4) array of in_off (relative to comp), in_len,
@@ -231,26 +191,11 @@ class BamCodec:
         self.info = info
         return n
 
-    def dev_reads(self):
-        rd = abi.AmpDevReads()
-        self._chk(self.L.amp_bam_reads(self.h, C.byref(rd)), "amp_bam_reads")
-        return rd
-
     def batch(self, slack=False):
         """The batch of the last feed as a host ReadBatch (src_index = the rows' record numbers).  slack: (the batch, the 16 spare
         bytes behind cig, seq and qual as three arrays) -- the tests check that they are zero like ampbam_decode's."""
-        n, nc, nb = int(self.info.n_rows), int(self.info.n_cig), int(self.info.n_bases_padded)
-        a = dict(pos=np.zeros(n, np.int32), flag=np.zeros(n, np.uint16), tlen=np.zeros(n, np.int32), lseq=np.zeros(n, np.uint32),
-                 cig_off=np.zeros(n + 1, np.uint64), cig=np.full(nc + 4, 0xA5A5A5A5, np.uint32), seq_off=np.zeros(n + 1, np.uint64),
-                 seq=np.full(nb // 2 + 16, 0xA5, np.uint8), qual=np.full(nb + 16, 0xA5, np.uint8))
-        src = np.zeros(n, np.int64)
-        st = abi.AmpReads(n, *[abi.ptr(a[k]) for k in ("pos", "flag", "tlen", "lseq", "cig_off", "cig", "seq_off", "seq", "qual")])
-        self._chk(self.L.amp_bam_batch_to_host(self.h, C.byref(st), C.c_void_p(abi.ptr(src))), "amp_bam_batch_to_host")
-        tails = (a["cig"][nc:].copy(), a["seq"][nb // 2:].copy(), a["qual"][nb:].copy())
-        a["cig"] = a["cig"][:nc]; a["seq"] = a["seq"][:nb // 2]; a["qual"] = a["qual"][:nb]
-        if slack:
-            return ReadBatch(a["pos"], a["flag"], a["tlen"], a["lseq"], a["cig_off"], a["cig"], a["seq_off"], a["seq"], a["qual"], src_index=src), tails
-        return ReadBatch(a["pos"], a["flag"], a["tlen"], a["lseq"], a["cig_off"], a["cig"], a["seq_off"], a["seq"], a["qual"], src_index=src)
+        rb, tails = super().batch(slack=16)
+        return (rb, tails) if slack else rb
 
     def image(self):
         """(the image of the last feed, the offsets of its records in it)."""
@@ -259,17 +204,6 @@ class BamCodec:
         self._chk(self.L.amp_bam_image_to_host(self.h, C.c_void_p(abi.ptr(img)), C.c_int64(img.size), C.c_void_p(abi.ptr(off)), C.c_int64(off.size)),
                   "amp_bam_image_to_host")
         return img[:int(self.info.image_bytes)], off[:int(self.info.n_records)]
-
-    def process(self, read_base=0):
-        """amp_bam_process: (first row with a non-zero status or -1, that status)."""
-        bad = C.c_int64(-1); st = C.c_uint8(0)
-        self._chk(self.L.amp_bam_process(self.h, C.c_uint64(read_base), C.byref(bad), C.byref(st)), "amp_bam_process")
-        return int(bad.value), int(st.value)
-
-    def stage_ms(self, on=True, read=True):
-        ms = (C.c_float * N_STAGES)(*([-1.0] * N_STAGES))
-        self._chk(self.L.amp_bam_stage_ms(self.h, C.c_int(1 if on else 0), ms if read else None), "amp_bam_stage_ms")
-        return [float(x) for x in ms]
 
 
 class DeviceBamInput:
@@ -299,25 +233,7 @@ class DeviceBamInput:
                 yield comp, tab, lo, n + 1 == len(self.pieces)
 
     def __iter__(self):
-        q = queue.Queue(maxsize=1)
-
-        def run():
-            try:
-                for c in self._read():
-                    q.put(c)
-                q.put(None)
-            except Exception as e:          # surfaced by the consumer
-                q.put(e)
-        threading.Thread(target=run, daemon=True).start()
-        while True:
-            c = q.get()
-            if c is None:
-                return
-            if isinstance(c, Exception):
-                raise c
-            yield c
-
-
+        return devcodec.read_ahead(self._read())
 
 
 def walk(codec, src, refuse_block=None):

@@ -16,8 +16,8 @@ SRC = os.path.join(CSRC, "amplihip.hip")
 HEADERS = [os.path.join(_HERE, "..", "include", "amplihip.h")] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
 UNIT_DEPS = {"amplihip.hip": HEADERS, "amp_ins.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_ins.hpp")],
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
-             "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_sam.hpp")],
-             "amp_bgzf.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_sam.hpp"), os.path.join(CSRC, "amp_bgzf.hpp")]}
+             "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_codec.hpp")],
+             "amp_bgzf.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_codec.hpp"), os.path.join(CSRC, "amp_bgzf.hpp")]}
 DEPS = [os.path.join(CSRC, u) for u in UNITS] + HEADERS
 OUT = os.path.join(_HERE, "libamplihip.so")
 OBJ_DIR = os.path.join(_HERE, "build")

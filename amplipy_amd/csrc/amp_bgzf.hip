@@ -23,30 +23,16 @@
 //
 // The lane functions compile for the host as well (-DAMPBGZF_HOSTSIM: any C++ compiler, sanitizers included) and a driver runs
 // them lane after lane: the twin the CPU tests check against libampbam.
-#ifndef AMPBGZF_HOSTSIM
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-#define BGZ_HD __host__ __device__ __forceinline__
-#else
-#define BGZ_HD static inline
-#endif
-
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <new>
+// What surrounds the stages -- stream, copies, scan, events, the batch's way into the read pass -- is the shell of amp_codec.hpp.
 #include <vector>
 
-#include "../../include/amplihip.h"
+#include "amp_codec.hpp"
+#define BGZ_HD AMP_HD
 #include "amp_bgzf.hpp"
-#ifndef AMPBGZF_HOSTSIM
-#include "amp_sam.hpp"          // amp::ctx_stream, amp::ctx_device
-#endif
 
 namespace ampbgzf {
 
-enum { CTL_REFUSED = 0, CTL_SETTLED, CTL_BAD, CTL_ROUNDS, CTL_CARRY, CTL_NREC, CTL_NROWS, CTL_NCIG, CTL_NBASES, CTL_NSLOTS, CTL_FIRST_BAD,
+enum { CTL_REFUSED = 0, CTL_SETTLED, CTL_BAD, CTL_ROUNDS, CTL_CARRY, CTL_NREC, CTL_NROWS, CTL_NCIG, CTL_NBASES, CTL_NSLOTS,
        CTL_WORDS = 16 };
 enum { BAM_STRETCH = 4096, WAVE = 64, CHAIN = 64, BLIND_ROUNDS = 2 };
 enum { ST_RUN = 0, ST_END = 1, ST_BAD = 2 };
@@ -55,25 +41,19 @@ static const int64_t IMAGE_LIMIT = AMP_BAM_IMAGE_LIMIT;
 
 struct DevBlock { uint32_t in_off, in_len, out_off, out_len, crc; };
 
-// Every pointer of a piece: device memory in the library, host memory in the twin.
-struct Buf {
+// Every pointer of a piece: device memory in the library, host memory in the twin.  Buf is a kernel argument and its layout the
+// kernels' view of it: blocks, image and index, then the batch (amp_dev_reads: the shell's struct), then the counters.
+struct BufIndex {
     const uint8_t *comp; const DevBlock *blocks; uint8_t *verdict; int64_t n_blocks, force_refuse;
     uint8_t *img; int64_t n_img, carry_len, o0, t0, n_stretch, rec_cap, rec_base; int32_t n_ref;
     uint32_t *entry, *exit_, *cnt, *s_cnt, *ja, *jb; uint8_t *st, *reach;
     uint32_t *rec_off, *s_row, *s_ncig, *s_slots;
-    int32_t *pos; uint16_t *flag; int32_t *tlen; uint32_t *lseq, *cig_off32, *cig, *seq_off8; uint8_t *seq, *qual;
-    int64_t *src_index; uint32_t *row_seq;
-    unsigned long long *ctl;
-    const uint8_t *status;
 };
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define BAM_MIN64(p, v) atomicMin((unsigned long long *)(p), (unsigned long long)(v))
-#define BAM_ADD64(p, v) atomicAdd((unsigned long long *)(p), (unsigned long long)(v))
-#else
-#define BAM_MIN64(p, v) do { if ((unsigned long long)(v) < *(p)) *(p) = (unsigned long long)(v); } while (0)
-#define BAM_ADD64(p, v) do { *(p) += (unsigned long long)(v); } while (0)
-#endif
+struct Buf : BufIndex, ampcodec::Batch {
+    uint32_t *row_seq;
+    unsigned long long *ctl;
+    uint64_t spare;            // (the kernels' other arguments stay where they were when a pointer lay here)
+};
 
 // ---- inflate / crc: one wave per block ----------------------------------------------------------------------------------------
 BGZ_HD void lane_inflate(const Buf &b, int64_t k, Tables &T) {
@@ -84,7 +64,7 @@ BGZ_HD void lane_inflate(const Buf &b, int64_t k, Tables &T) {
 // `reg` = XOR of crc_lane over the 64 lanes
 BGZ_HD void lane_crc_verdict(const Buf &b, int64_t k, uint32_t reg) {
     if (b.verdict[k] == 0 && ((~reg) != b.blocks[k].crc || k == b.force_refuse)) b.verdict[k] = 2;
-    if (b.verdict[k]) BAM_ADD64(&b.ctl[CTL_REFUSED], 1);
+    if (b.verdict[k]) AMP_ADD64(&b.ctl[CTL_REFUSED], 1);
 }
 
 // ---- the record index -----------------------------------------------------------------------------------------------------------
@@ -190,7 +170,7 @@ BGZ_HD void lane_rows(const Buf &b, int64_t i) {
         for (uint32_t k = 0; k < n_cig; ++k) b.cig[c0 + k] = rd32(v + 4 * k);
         b.row_seq[r] = o + 4u + 32u + l_name + 4u * n_cig;
         b.src_index[r] = b.rec_base + i;
-        BAM_ADD64(&b.ctl[CTL_NBASES], l_seq);
+        AMP_ADD64(&b.ctl[CTL_NBASES], l_seq);
     }
     if (i == (int64_t)b.ctl[CTL_NREC] - 1) {
         const uint32_t nr = b.s_row[i] + (row ? 1u : 0u);
@@ -227,18 +207,12 @@ BGZ_HD void lane_slack(const Buf &b, int64_t) {               // 16 zeroed bytes
     for (int k = 0; k < 16; ++k) { b.seq[4 * ns + k] = 0; b.qual[8 * ns + k] = 0; }
 }
 
-BGZ_HD void lane_first_bad(const Buf &b, int64_t r) {
-    if (b.status[r]) BAM_MIN64(&b.ctl[CTL_FIRST_BAD], ((unsigned long long)r << 8) | b.status[r]);
-}
-
 // ---- layout -----------------------------------------------------------------------------------------------------------------------
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int64_t rec_cap_for(int64_t n_img) { return n_img / 37 + 2; }       // a record is 4 + 32 + a name of one byte at least
 // Carves `base` (NULL: sizes only) for images of up to cap bytes and n_blocks blocks; returns the bytes needed.
 static size_t carve(Buf &b, uint8_t *base, int64_t cap, int64_t cap_blocks) {
     const size_t n = (size_t)cap, S = n / BAM_STRETCH + 2, R = (size_t)rec_cap_for(cap);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up256(bytes); return p; };
+    ampcodec::Carver take{base};
     b.blocks = (const DevBlock *)take((size_t)cap_blocks * sizeof(DevBlock)); b.verdict = take((size_t)cap_blocks);
     uint32_t **per_stretch[] = {&b.entry, &b.exit_, &b.cnt, &b.s_cnt, &b.ja, &b.jb};
     for (uint32_t **p : per_stretch) *p = (uint32_t *)take(S * 4);
@@ -252,30 +226,25 @@ static size_t carve(Buf &b, uint8_t *base, int64_t cap, int64_t cap_blocks) {
     // (L + 1) / 2 + L bytes of them, so its ceil(L / 8) slots are at most L / 8 + 1
     b.cig = (uint32_t *)take((n / 4 + 8) * 4); b.seq = take((n / 8 + R) * 4 + 64); b.qual = take((n / 8 + R) * 8 + 64);
     b.ctl = (unsigned long long *)take(CTL_WORDS * 8);
-    return o;
+    return take.o;
 }
 
 }  // namespace ampbgzf
 
 using namespace ampbgzf;
+using namespace ampcodec;
 
-// ---- the two back ends ------------------------------------------------------------------------------------------------------------
+CODEC_FIRST_BAD_KERNEL(k_bam_first_bad)
 #ifndef AMPBGZF_HOSTSIM
-#define BAM_KERNEL(name, fn)                                                                                          \
-    __global__ void __launch_bounds__(256) name(Buf b, int64_t n, int ctl) {                                          \
-        if (ctl >= 0 && (int64_t)b.ctl[ctl] < n) n = (int64_t)b.ctl[ctl];                                             \
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) fn(b, i);     \
-    }
-BAM_KERNEL(k_bam_walk, lane_walk)
-BAM_KERNEL(k_bam_link, lane_link)
-BAM_KERNEL(k_bam_jump, lane_jump)
-BAM_KERNEL(k_bam_settle, lane_settle)
-BAM_KERNEL(k_bam_counts, lane_counts)
-BAM_KERNEL(k_bam_emit, lane_emit)
-BAM_KERNEL(k_bam_rows, lane_rows)
-BAM_KERNEL(k_bam_pack, lane_pack)
-BAM_KERNEL(k_bam_slack, lane_slack)
-BAM_KERNEL(k_bam_first_bad, lane_first_bad)
+CODEC_KERNEL(k_bam_walk, lane_walk)
+CODEC_KERNEL(k_bam_link, lane_link)
+CODEC_KERNEL(k_bam_jump, lane_jump)
+CODEC_KERNEL(k_bam_settle, lane_settle)
+CODEC_KERNEL(k_bam_counts, lane_counts)
+CODEC_KERNEL(k_bam_emit, lane_emit)
+CODEC_KERNEL(k_bam_rows, lane_rows)
+CODEC_KERNEL(k_bam_pack, lane_pack)
+CODEC_KERNEL(k_bam_slack, lane_slack)
 
 // One wave per BGZF block, its decoder's tables in LDS.  The decode of a stream is serial in its bit position: lane 0 runs it
 // (the branch is wave-uniform per instruction: the other lanes are masked off, not diverged into another path).
@@ -302,79 +271,33 @@ __global__ void __launch_bounds__(256) k_bgzf_crc(Buf b) {
 #endif
 
 struct amp_bam {
+    Shell sh;
     Buf b{};
-    int64_t cap_img = 0, cap_comp = 0, cap_carry = 0, cap_arena = 0, arena_img = 0, arena_blocks = 0;
+    size_t cap_img = 0, cap_comp = 0, cap_carry = 0, cap_arena = 0;
+    int64_t arena_img = 0, arena_blocks = 0;
     uint8_t *arena = nullptr, *img = nullptr, *comp = nullptr, *carry = nullptr;
     int64_t carry_len = 0;                            // bytes of the last image behind its last complete record, kept in `carry`
-    uint8_t *res = nullptr; size_t res_cap = 0;       // results of the read pass
-    int32_t *new_pos = nullptr; uint32_t *new_ncig = nullptr, *new_cig = nullptr; int32_t *ref_len = nullptr; uint8_t *trim_flags = nullptr, *status = nullptr;
+    Trim trim{};                                      // results of the read pass
     std::vector<DevBlock> h_blocks;
     std::vector<uint8_t> h_verdict;
     amp_bam_info info{};
     bool fed = false;
-    int64_t refused_left = 0, force_refuse = -1, waits = 0;
+    int64_t refused_left = 0, force_refuse = -1;
     unsigned long long h_ctl[CTL_WORDS];
-#ifndef AMPBGZF_HOSTSIM
-    amp_ctx *ctx = nullptr; int device = 0; hipStream_t stream = nullptr;
-    void *scan_tmp = nullptr; size_t scan_tmp_cap = 0;
-    hipEvent_t ev[AMP_BAM_N_STAGES + 1] = {};
-    bool timed = false;
-#endif
 };
 
 #ifndef AMPBGZF_HOSTSIM
-struct BamDevGuard {
-    int prev = -1;
-    explicit BamDevGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); }
-    ~BamDevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-#define BAM_GUARD(s) BamDevGuard guard__((s)->device)
-#define BAM_TRY(call) do { if ((call) != hipSuccess) return AMP_EHIP; } while (0)
-static int bam_alloc(amp_bam *, uint8_t **p, size_t bytes) { return hipMalloc((void **)p, bytes) == hipSuccess ? AMP_OK : AMP_ENOMEM; }
-static void bam_free(uint8_t *p) { if (p) (void)hipFree(p); }
-static int bam_up(amp_bam *s, void *dst, const void *src, size_t n) { return !n || hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s->stream) == hipSuccess ? AMP_OK : AMP_EHIP; }
-static int bam_down(amp_bam *s, void *dst, const void *src, size_t n) { return !n || hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s->stream) == hipSuccess ? AMP_OK : AMP_EHIP; }
-static int bam_d2d(amp_bam *s, void *dst, const void *src, size_t n) { return !n || hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, s->stream) == hipSuccess ? AMP_OK : AMP_EHIP; }
-static int bam_zero(amp_bam *s, void *p, int v, size_t n) { return !n || hipMemsetAsync(p, v, n, s->stream) == hipSuccess ? AMP_OK : AMP_EHIP; }
-static int bam_wait(amp_bam *s) { ++s->waits; return hipStreamSynchronize(s->stream) == hipSuccess ? AMP_OK : AMP_EHIP; }
-static unsigned bam_grid(int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : g > 4096 ? 4096 : g); }
-#define BAM_RUN(s, k, fn, n, cx) do { if ((n) > 0) { k<<<bam_grid(n), 256, 0, (s)->stream>>>((s)->b, (int64_t)(n), (cx)); if (hipGetLastError() != hipSuccess) return AMP_EHIP; } } while (0)
-template <class T> static int bam_scan(amp_bam *s, T *p, int64_t n) {      // exclusive sum in place
-    if (n <= 0) return AMP_OK;
-    size_t need = 0;
-    BAM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, p, p, (int)n, s->stream));
-    if (need > s->scan_tmp_cap) {
-        if (s->scan_tmp) { if (hipStreamSynchronize(s->stream) != hipSuccess) return AMP_EHIP; (void)hipFree(s->scan_tmp); s->scan_tmp = nullptr; s->scan_tmp_cap = 0; }
-        if (hipMalloc(&s->scan_tmp, 2 * need + 256) != hipSuccess) return AMP_ENOMEM;
-        s->scan_tmp_cap = 2 * need + 256;
-    }
-    size_t tb = s->scan_tmp_cap;
-    BAM_TRY(hipcub::DeviceScan::ExclusiveSum(s->scan_tmp, tb, p, p, (int)n, s->stream));
-    return AMP_OK;
-}
 static int bam_inflate_crc(amp_bam *s) {
     const int64_t nb = s->b.n_blocks;
     if (nb <= 0) return AMP_OK;
     // twelve decoders fit a CU's LDS: 256 x 12 workgroups are resident at once, a larger piece's blocks queue behind them
-    k_bgzf_inflate<<<(unsigned)(nb < 3072 ? nb : 3072), 64, 0, s->stream>>>(s->b);
+    k_bgzf_inflate<<<(unsigned)(nb < 3072 ? nb : 3072), 64, 0, s->sh.stream>>>(s->b);
     if (hipGetLastError() != hipSuccess) return AMP_EHIP;
-    if (s->timed) (void)hipEventRecord(s->ev[2], s->stream);
-    k_bgzf_crc<<<(unsigned)((nb + 3) / 4 < 4096 ? (nb + 3) / 4 : 4096), 256, 0, s->stream>>>(s->b);
+    codec_mark(s->sh, 2);
+    k_bgzf_crc<<<(unsigned)((nb + 3) / 4 < 4096 ? (nb + 3) / 4 : 4096), 256, 0, s->sh.stream>>>(s->b);
     return hipGetLastError() == hipSuccess ? AMP_OK : AMP_EHIP;
 }
-#define BAM_MARK(s, k) do { if ((s)->timed) (void)hipEventRecord((s)->ev[k], (s)->stream); } while (0)
 #else
-#define BAM_GUARD(s) (void)0
-static int bam_alloc(amp_bam *, uint8_t **p, size_t bytes) { *p = (uint8_t *)malloc(bytes ? bytes : 1); return *p ? AMP_OK : AMP_ENOMEM; }
-static void bam_free(uint8_t *p) { free(p); }
-static int bam_up(amp_bam *, void *dst, const void *src, size_t n) { if (n) memcpy(dst, src, n); return AMP_OK; }
-static int bam_down(amp_bam *, void *dst, const void *src, size_t n) { if (n) memcpy(dst, src, n); return AMP_OK; }
-static int bam_d2d(amp_bam *, void *dst, const void *src, size_t n) { if (n) memmove(dst, src, n); return AMP_OK; }
-static int bam_zero(amp_bam *, void *p, int v, size_t n) { if (n) memset(p, v, n); return AMP_OK; }
-static int bam_wait(amp_bam *s) { ++s->waits; return AMP_OK; }
-#define BAM_RUN(s, k, fn, n, cx) do { int64_t n__ = (int64_t)(n); if ((cx) >= 0 && (int64_t)(s)->b.ctl[(cx) < 0 ? 0 : (cx)] < n__) n__ = (int64_t)(s)->b.ctl[(cx) < 0 ? 0 : (cx)]; \
-                                       for (int64_t i__ = 0; i__ < n__; ++i__) fn((s)->b, i__); } while (0)
-template <class T> static int bam_scan(amp_bam *, T *p, int64_t n) { T a = 0; for (int64_t i = 0; i < n; ++i) { const T v = p[i]; p[i] = a; a += v; } return AMP_OK; }
 static int bam_inflate_crc(amp_bam *s) {
     static Tables T;
     static uint32_t tab[256];
@@ -388,30 +311,17 @@ static int bam_inflate_crc(amp_bam *s) {
     }
     return AMP_OK;
 }
-#define BAM_MARK(s, k) (void)0
 #endif
-#define BAM_OK(call) do { const int rc__ = (call); if (rc__) return rc__; } while (0)
-
-static int bam_grow(amp_bam *s, uint8_t **p, int64_t *cap, int64_t need) {
-    if (need <= *cap) return AMP_OK;
-    BAM_OK(bam_wait(s)); --s->waits;                   // (growth: the first piece, or a larger one; never on the steady path)
-    uint8_t *np = nullptr;
-    const int64_t ncap = need + need / 8 + 4096;
-    BAM_OK(bam_alloc(s, &np, (size_t)ncap));
-    bam_free(*p);
-    *p = np; *cap = ncap;
-    return AMP_OK;
-}
 
 static int bam_ensure(amp_bam *s, int64_t n_img, int64_t n_blocks, int64_t n_comp) {
-    BAM_OK(bam_grow(s, &s->img, &s->cap_img, n_img + 64));
-    BAM_OK(bam_grow(s, &s->comp, &s->cap_comp, n_comp + 64));
+    CODEC_OK(codec_grow(s->sh, &s->img, &s->cap_img, (size_t)n_img + 64));
+    CODEC_OK(codec_grow(s->sh, &s->comp, &s->cap_comp, (size_t)n_comp + 64));
     if (!s->arena || n_img > s->arena_img || n_blocks > s->arena_blocks) {      // pieces of a run have one size: grown once, then reused
         const int64_t ci = n_img > s->arena_img ? n_img + n_img / 8 + 4096 : s->arena_img;
         const int64_t cb = n_blocks > s->arena_blocks ? n_blocks + n_blocks / 8 + 64 : s->arena_blocks;
         Buf probe = s->b;
         const size_t need = carve(probe, nullptr, ci, cb);
-        BAM_OK(bam_grow(s, &s->arena, &s->cap_arena, (int64_t)need));
+        CODEC_OK(codec_grow(s->sh, &s->arena, &s->cap_arena, need));
         (void)carve(s->b, s->arena, ci, cb);
         s->arena_img = ci; s->arena_blocks = cb;
     }
@@ -423,13 +333,13 @@ static int bam_ensure(amp_bam *s, int64_t n_img, int64_t n_blocks, int64_t n_com
 static int bam_index_decode(amp_bam *s) {
     Buf &b = s->b;
     const int64_t S = b.n_stretch, R = b.rec_cap;
-    BAM_OK(bam_zero(s, &b.ctl[CTL_SETTLED], 0, (CTL_WORDS - CTL_SETTLED) * 8));
-    BAM_OK(bam_zero(s, b.cig_off32, 0, 4));
-    BAM_OK(bam_zero(s, b.seq_off8, 0, 4));
-    BAM_OK(bam_zero(s, b.s_row, 0, (size_t)R * 4));
-    BAM_OK(bam_zero(s, b.s_ncig, 0, (size_t)R * 4));
-    BAM_OK(bam_zero(s, b.s_slots, 0, (size_t)R * 4));
-    if (S > 0) BAM_RUN(s, k_bam_walk, lane_walk, S, -1);
+    CODEC_OK(codec_zero(s->sh, &b.ctl[CTL_SETTLED], 0, (CTL_WORDS - CTL_SETTLED) * 8));
+    CODEC_OK(codec_zero(s->sh, b.cig_off32, 0, 4));
+    CODEC_OK(codec_zero(s->sh, b.seq_off8, 0, 4));
+    CODEC_OK(codec_zero(s->sh, b.s_row, 0, (size_t)R * 4));
+    CODEC_OK(codec_zero(s->sh, b.s_ncig, 0, (size_t)R * 4));
+    CODEC_OK(codec_zero(s->sh, b.s_slots, 0, (size_t)R * 4));
+    if (S > 0) CODEC_RUN(s, k_bam_walk, lane_walk, S, -1);
     return AMP_OK;
 }
 static int bam_rounds(amp_bam *s, int rounds) {
@@ -439,12 +349,12 @@ static int bam_rounds(amp_bam *s, int rounds) {
     int K = 1;
     while ((1ll << K) < S) ++K;
     for (int r = 0; r < rounds; ++r) {
-        BAM_RUN(s, k_bam_link, lane_link, S, -1);
+        CODEC_RUN(s, k_bam_link, lane_link, S, -1);
         for (int k = 0; k <= K; ++k) {
-            BAM_RUN(s, k_bam_jump, lane_jump, S, -1);
+            CODEC_RUN(s, k_bam_jump, lane_jump, S, -1);
             uint32_t *t = b.ja; b.ja = b.jb; b.jb = t;
         }
-        BAM_RUN(s, k_bam_settle, lane_settle, S, -1);
+        CODEC_RUN(s, k_bam_settle, lane_settle, S, -1);
     }
     return AMP_OK;
 }
@@ -452,16 +362,16 @@ static int bam_decode(amp_bam *s) {
     Buf &b = s->b;
     const int64_t S = b.n_stretch, R = b.rec_cap;
     if (S > 0) {
-        BAM_RUN(s, k_bam_counts, lane_counts, S, -1);
-        BAM_OK(bam_scan(s, b.s_cnt, S));
-        BAM_RUN(s, k_bam_emit, lane_emit, S, -1);
-        BAM_OK(bam_scan(s, b.s_row, R));
-        BAM_OK(bam_scan(s, b.s_ncig, R));
-        BAM_OK(bam_scan(s, b.s_slots, R));
-        BAM_RUN(s, k_bam_rows, lane_rows, R, CTL_NREC);
-        BAM_RUN(s, k_bam_pack, lane_pack, b.n_img / 8 + R, CTL_NSLOTS);
+        CODEC_RUN(s, k_bam_counts, lane_counts, S, -1);
+        CODEC_OK(codec_scan(s->sh, b.s_cnt, S));
+        CODEC_RUN(s, k_bam_emit, lane_emit, S, -1);
+        CODEC_OK(codec_scan(s->sh, b.s_row, R));
+        CODEC_OK(codec_scan(s->sh, b.s_ncig, R));
+        CODEC_OK(codec_scan(s->sh, b.s_slots, R));
+        CODEC_RUN(s, k_bam_rows, lane_rows, R, CTL_NREC);
+        CODEC_RUN(s, k_bam_pack, lane_pack, b.n_img / 8 + R, CTL_NSLOTS);
     }
-    BAM_RUN(s, k_bam_slack, lane_slack, 1, -1);
+    CODEC_RUN(s, k_bam_slack, lane_slack, 1, -1);
     return AMP_OK;
 }
 
@@ -469,19 +379,19 @@ static int bam_decode(amp_bam *s) {
 static int bam_finish(amp_bam *s, amp_bam_info *info) {
     Buf &b = s->b;
     const unsigned long long *c = s->h_ctl;
-    BAM_OK(bam_rounds(s, BLIND_ROUNDS));
-    BAM_MARK(s, 4);
-    BAM_OK(bam_decode(s));
-    BAM_MARK(s, 5);
+    CODEC_OK(bam_rounds(s, BLIND_ROUNDS));
+    codec_mark(s->sh, 4);
+    CODEC_OK(bam_decode(s));
+    codec_mark(s->sh, 5);
     for (;;) {
-        BAM_OK(bam_down(s, s->h_ctl, b.ctl, CTL_WORDS * 8));
-        BAM_OK(bam_wait(s));
+        CODEC_OK(codec_down(s->sh, s->h_ctl, b.ctl, CTL_WORDS * 8));
+        CODEC_OK(codec_wait(s->sh));
         if (c[CTL_REFUSED] || c[CTL_SETTLED] || b.n_stretch <= 0) break;
-        BAM_OK(bam_rounds(s, BLIND_ROUNDS));                    // an index that has not settled: more rounds, another wait
-        BAM_OK(bam_decode(s));
+        CODEC_OK(bam_rounds(s, BLIND_ROUNDS));                    // an index that has not settled: more rounds, another wait
+        CODEC_OK(bam_decode(s));
     }
     amp_bam_info &I = s->info;
-    I.n_refused = (int64_t)c[CTL_REFUSED]; I.index_rounds = (int64_t)c[CTL_ROUNDS]; I.waits = s->waits;
+    I.n_refused = (int64_t)c[CTL_REFUSED]; I.index_rounds = (int64_t)c[CTL_ROUNDS]; I.waits = s->sh.waits;
     s->refused_left = I.n_refused;
     I.n_records = I.n_rows = I.n_cig = I.n_bases = I.n_bases_padded = 0; I.bad_record = 0;
     I.carry_out = 0; I.next_first = 0;
@@ -494,8 +404,8 @@ static int bam_finish(amp_bam *s, amp_bam_info *info) {
             I.n_bases = (int64_t)c[CTL_NBASES]; I.n_bases_padded = (int64_t)c[CTL_NSLOTS] * 8;
             I.carry_out = b.n_img - (int64_t)c[CTL_CARRY];
             // the tail behind the last complete record opens the next image (a device-to-device copy of less than one record)
-            BAM_OK(bam_grow(s, &s->carry, &s->cap_carry, I.carry_out + 64));
-            BAM_OK(bam_d2d(s, s->carry, b.img + (int64_t)c[CTL_CARRY], (size_t)I.carry_out));
+            CODEC_OK(codec_grow(s->sh, &s->carry, &s->cap_carry, (size_t)I.carry_out + 64));
+            CODEC_OK(codec_d2d(s->sh, s->carry, b.img + (int64_t)c[CTL_CARRY], (size_t)I.carry_out));
         }
         s->carry_len = I.carry_out;
     }
@@ -506,41 +416,23 @@ static int bam_finish(amp_bam *s, amp_bam_info *info) {
 extern "C" {
 
 // libampbam's reader of one run (ampbam_open_range_at + ampbam_decode; pysam's iteration at A:296-324, A:896, A:902)
-int amp_bam_create(amp_ctx *ctx, amp_bam **out) {
-    if (!out) return AMP_EINVAL;
-#ifndef AMPBGZF_HOSTSIM
-    if (!ctx) return AMP_EINVAL;
-#endif
-    amp_bam *s = new (std::nothrow) amp_bam();
-    if (!s) return AMP_ENOMEM;
-#ifndef AMPBGZF_HOSTSIM
-    s->ctx = ctx; s->device = amp::ctx_device(ctx); s->stream = amp::ctx_stream(ctx);
-    BAM_GUARD(s);
-    for (hipEvent_t &e : s->ev) if (hipEventCreate(&e) != hipSuccess) { delete s; return AMP_EHIP; }
-#endif
-    *out = s;
-    return AMP_OK;
-}
+int amp_bam_create(amp_ctx *ctx, amp_bam **out) { return codec_new(ctx, out, AMP_BAM_N_STAGES, k_bam_first_bad); }
 
 void amp_bam_destroy(amp_bam *s) {
     if (!s) return;
-    BAM_GUARD(s);
-    (void)bam_wait(s);
-    bam_free(s->arena); bam_free(s->img); bam_free(s->comp); bam_free(s->carry); bam_free(s->res);
-#ifndef AMPBGZF_HOSTSIM
-    if (s->scan_tmp) (void)hipFree(s->scan_tmp);
-    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
-#endif
-    delete s;
+    DevGuard guard(s->sh);
+    (void)codec_wait(s->sh);
+    codec_free(s->arena); codec_free(s->img); codec_free(s->comp); codec_free(s->carry);
+    codec_delete(s);
 }
 
 // ampbam_open_range_at for one piece of whole BGZF blocks: inflate, CRC, record index; and ampbam_decode of its records
 int amp_bam_feed(amp_bam *s, const uint8_t *comp, int64_t n_comp, const amp_bam_block *blocks, int64_t n_blocks, int64_t first_off,
                  int32_t n_ref, int64_t rec_base, amp_bam_info *info) {
     if (!s || !info || n_comp < 0 || n_blocks < 0 || (n_comp && !comp) || (n_blocks && !blocks) || n_ref < 0 || n_comp >= (1ll << 31)) return AMP_EINVAL;
-    BAM_GUARD(s);
+    DevGuard guard(s->sh);
     s->fed = false;
-    const int64_t waits0 = s->waits;
+    const int64_t waits0 = s->sh.waits;
     int64_t isize = 0;
     try { s->h_blocks.resize((size_t)n_blocks); s->h_verdict.assign((size_t)n_blocks, 0); } catch (const std::bad_alloc &) { return AMP_ENOMEM; }
     for (int64_t k = 0; k < n_blocks; ++k) {
@@ -553,7 +445,7 @@ int amp_bam_feed(amp_bam *s, const uint8_t *comp, int64_t n_comp, const amp_bam_
     const int64_t carry_len = first_off >= 0 ? 0 : s->carry_len;
     const int64_t n_img = carry_len + isize;
     if (n_img > IMAGE_LIMIT) return AMP_EOVERFLOW;
-    BAM_OK(bam_ensure(s, n_img > 0 ? n_img : 1, n_blocks > 0 ? n_blocks : 1, n_comp > 0 ? n_comp : 1));
+    CODEC_OK(bam_ensure(s, n_img > 0 ? n_img : 1, n_blocks > 0 ? n_blocks : 1, n_comp > 0 ? n_comp : 1));
     Buf &b = s->b;
     b.n_blocks = n_blocks; b.force_refuse = s->force_refuse; s->force_refuse = -1;
     b.n_img = n_img; b.carry_len = carry_len; b.o0 = first_off >= 0 ? first_off : 0; b.n_ref = n_ref; b.rec_base = rec_base;
@@ -562,18 +454,18 @@ int amp_bam_feed(amp_bam *s, const uint8_t *comp, int64_t n_comp, const amp_bam_
     z.n_blocks = n_blocks; z.n_inflated = isize; z.image_bytes = n_img; z.carry_in = carry_len;
     z.bytes_up = n_comp + n_blocks * (int64_t)sizeof(DevBlock);
     s->info = z;
-    BAM_MARK(s, 0);
-    BAM_OK(bam_up(s, (void *)b.comp, comp, (size_t)n_comp));
-    BAM_OK(bam_up(s, (void *)b.blocks, s->h_blocks.data(), (size_t)n_blocks * sizeof(DevBlock)));
-    BAM_OK(bam_d2d(s, b.img, s->carry, (size_t)carry_len));
-    BAM_OK(bam_zero(s, b.img + n_img, 0, 64));
-    BAM_OK(bam_zero(s, b.ctl, 0, CTL_WORDS * 8));
-    BAM_MARK(s, 1);
-    BAM_OK(bam_inflate_crc(s));
-    BAM_MARK(s, 3);
-    BAM_OK(bam_index_decode(s));
-    BAM_OK(bam_finish(s, nullptr));
-    s->info.waits = s->waits - waits0;
+    codec_mark(s->sh, 0);
+    CODEC_OK(codec_up(s->sh, (void *)b.comp, comp, (size_t)n_comp));
+    CODEC_OK(codec_up(s->sh, (void *)b.blocks, s->h_blocks.data(), (size_t)n_blocks * sizeof(DevBlock)));
+    CODEC_OK(codec_d2d(s->sh, b.img, s->carry, (size_t)carry_len));
+    CODEC_OK(codec_zero(s->sh, b.img + n_img, 0, 64));
+    CODEC_OK(codec_zero(s->sh, b.ctl, 0, CTL_WORDS * 8));
+    codec_mark(s->sh, 1);
+    CODEC_OK(bam_inflate_crc(s));
+    codec_mark(s->sh, 3);
+    CODEC_OK(bam_index_decode(s));
+    CODEC_OK(bam_finish(s, nullptr));
+    s->info.waits = s->sh.waits - waits0;
     *info = s->info;
     s->fed = true;
     return AMP_OK;
@@ -590,9 +482,9 @@ int amp_bam_dev_refuse(amp_bam *s, int64_t k) {
 int amp_bam_refused(amp_bam *s, int64_t *idx, int64_t cap, int64_t *n) {
     if (!s || !n || cap < 0 || (cap && !idx)) return AMP_EINVAL;
     if (!s->fed) return AMP_ESTATE;
-    BAM_GUARD(s);
-    BAM_OK(bam_down(s, s->h_verdict.data(), s->b.verdict, s->h_verdict.size()));
-    BAM_OK(bam_wait(s));
+    DevGuard guard(s->sh);
+    CODEC_OK(codec_down(s->sh, s->h_verdict.data(), s->b.verdict, s->h_verdict.size()));
+    CODEC_OK(codec_wait(s->sh));
     int64_t m = 0;
     for (size_t k = 0; k < s->h_verdict.size(); ++k) if (s->h_verdict[k]) { if (m < cap) idx[m] = (int64_t)k; ++m; }
     *n = m;
@@ -605,9 +497,9 @@ int amp_bam_patch_block(amp_bam *s, int64_t k, const uint8_t *bytes, int64_t n_b
     if (!s->fed || k >= (int64_t)s->h_blocks.size() || !s->h_verdict[(size_t)k]) return AMP_ESTATE;
     const DevBlock &blk = s->h_blocks[(size_t)k];
     if (n_bytes != (int64_t)blk.out_len) return AMP_EINVAL;
-    BAM_GUARD(s);
-    BAM_OK(bam_up(s, s->b.img + s->b.carry_len + blk.out_off, bytes, (size_t)n_bytes));
-    BAM_OK(bam_wait(s));
+    DevGuard guard(s->sh);
+    CODEC_OK(codec_up(s->sh, s->b.img + s->b.carry_len + blk.out_off, bytes, (size_t)n_bytes));
+    CODEC_OK(codec_wait(s->sh));
     s->h_verdict[(size_t)k] = 0;
     --s->refused_left;
     return AMP_OK;
@@ -617,12 +509,12 @@ int amp_bam_patch_block(amp_bam *s, int64_t k, const uint8_t *bytes, int64_t n_b
 int amp_bam_reindex(amp_bam *s, amp_bam_info *info) {
     if (!s || !info) return AMP_EINVAL;
     if (!s->fed || s->refused_left != 0) return AMP_ESTATE;
-    BAM_GUARD(s);
-    const int64_t waits0 = s->info.waits, w0 = s->waits;
-    BAM_OK(bam_zero(s, s->b.ctl, 0, CTL_WORDS * 8));
-    BAM_OK(bam_index_decode(s));
-    BAM_OK(bam_finish(s, nullptr));
-    s->info.waits = waits0 + (s->waits - w0);
+    DevGuard guard(s->sh);
+    const int64_t waits0 = s->info.waits, w0 = s->sh.waits;
+    CODEC_OK(codec_zero(s->sh, s->b.ctl, 0, CTL_WORDS * 8));
+    CODEC_OK(bam_index_decode(s));
+    CODEC_OK(bam_finish(s, nullptr));
+    s->info.waits = waits0 + (s->sh.waits - w0);
     *info = s->info;
     return AMP_OK;
 }
@@ -631,8 +523,7 @@ int amp_bam_reindex(amp_bam *s, amp_bam_info *info) {
 int amp_bam_reads(amp_bam *s, amp_dev_reads *out) {
     if (!s || !out) return AMP_EINVAL;
     if (!s->fed || s->info.n_refused) return AMP_ESTATE;
-    const Buf &b = s->b;
-    *out = amp_dev_reads{s->info.n_rows, b.pos, b.flag, b.tlen, b.lseq, b.cig_off32, b.cig, b.seq_off8, b.seq, b.qual, s->info.n_cig, s->info.n_bases_padded};
+    *out = codec_reads(s->b, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded);
     return AMP_OK;
 }
 
@@ -640,31 +531,7 @@ int amp_bam_reads(amp_bam *s, amp_dev_reads *out) {
 int amp_bam_batch_to_host(amp_bam *s, const amp_reads *dst, int64_t *src_index) {
     if (!s || !dst) return AMP_EINVAL;
     if (!s->fed || s->info.n_refused) return AMP_ESTATE;
-    const int64_t n = s->info.n_rows;
-    if (dst->n_reads != n) return AMP_EINVAL;
-    BAM_GUARD(s);
-    const Buf &b = s->b;
-    uint32_t *co = (uint32_t *)malloc(((size_t)n + 1) * 8);
-    if (!co) return AMP_ENOMEM;
-    uint32_t *so = co + n + 1;
-    int rc = AMP_OK;
-    if (dst->pos) rc = rc ? rc : bam_down(s, (void *)dst->pos, b.pos, (size_t)n * 4);
-    if (dst->flag) rc = rc ? rc : bam_down(s, (void *)dst->flag, b.flag, (size_t)n * 2);
-    if (dst->tlen) rc = rc ? rc : bam_down(s, (void *)dst->tlen, b.tlen, (size_t)n * 4);
-    if (dst->lseq) rc = rc ? rc : bam_down(s, (void *)dst->lseq, b.lseq, (size_t)n * 4);
-    if (dst->cig) rc = rc ? rc : bam_down(s, (void *)dst->cig, b.cig, (size_t)s->info.n_cig * 4 + 16);
-    if (dst->seq) rc = rc ? rc : bam_down(s, (void *)dst->seq, b.seq, (size_t)s->info.n_bases_padded / 2 + 16);
-    if (dst->qual) rc = rc ? rc : bam_down(s, (void *)dst->qual, b.qual, (size_t)s->info.n_bases_padded + 16);
-    if (src_index) rc = rc ? rc : bam_down(s, src_index, b.src_index, (size_t)n * 8);
-    rc = rc ? rc : bam_down(s, co, b.cig_off32, ((size_t)n + 1) * 4);
-    rc = rc ? rc : bam_down(s, so, b.seq_off8, ((size_t)n + 1) * 4);
-    rc = rc ? rc : bam_wait(s);
-    for (int64_t i = 0; !rc && i <= n; ++i) {
-        if (dst->cig_off) ((uint64_t *)dst->cig_off)[i] = co[i];
-        if (dst->seq_off) ((uint64_t *)dst->seq_off)[i] = (uint64_t)so[i] * 8;
-    }
-    free(co);
-    return rc;
+    return codec_batch_to_host(s->sh, s->b, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded, dst, src_index, 16);
 }
 
 // the image of the last feed ([carry | inflated blocks], image_bytes of them) and the offsets of its records: tests, tools, and
@@ -672,10 +539,10 @@ int amp_bam_batch_to_host(amp_bam *s, const amp_reads *dst, int64_t *src_index) 
 int amp_bam_image_to_host(amp_bam *s, uint8_t *image, int64_t image_cap, uint32_t *rec_off, int64_t rec_cap) {
     if (!s || image_cap < 0 || rec_cap < 0) return AMP_EINVAL;
     if (!s->fed) return AMP_ESTATE;
-    BAM_GUARD(s);
-    if (image) { if (image_cap < s->b.n_img) return AMP_EOVERFLOW; BAM_OK(bam_down(s, image, s->b.img, (size_t)s->b.n_img)); }
-    if (rec_off) { if (rec_cap < s->info.n_records) return AMP_EOVERFLOW; BAM_OK(bam_down(s, rec_off, s->b.rec_off, (size_t)s->info.n_records * 4)); }
-    return bam_wait(s);
+    DevGuard guard(s->sh);
+    if (image) { if (image_cap < s->b.n_img) return AMP_EOVERFLOW; CODEC_OK(codec_down(s->sh, image, s->b.img, (size_t)s->b.n_img)); }
+    if (rec_off) { if (rec_cap < s->info.n_records) return AMP_EOVERFLOW; CODEC_OK(codec_down(s->sh, rec_off, s->b.rec_off, (size_t)s->info.n_records * 4)); }
+    return codec_wait(s->sh);
 }
 
 #ifndef AMPBGZF_HOSTSIM
@@ -683,53 +550,11 @@ int amp_bam_image_to_host(amp_bam *s, uint8_t *image, int64_t image_cap, uint32_
 int amp_bam_process(amp_bam *s, uint64_t read_base, int64_t *first_bad_row, uint8_t *its_status) {
     if (!s) return AMP_EINVAL;
     if (!s->fed || s->info.n_refused || s->info.bad_record) return AMP_ESTATE;
-    BAM_GUARD(s);
-    const size_t n = (size_t)s->info.n_rows, nc = (size_t)s->info.n_cig + 3 * n;
-    const size_t need = 3 * up256(n * 4 + 4) + up256(nc * 4 + 4) + 2 * up256(n + 1);
-    if (need > s->res_cap) {
-        int64_t cap = (int64_t)s->res_cap;
-        BAM_OK(bam_grow(s, &s->res, &cap, (int64_t)need));
-        s->res_cap = (size_t)cap;
-    }
-    uint8_t *p = s->res;
-    s->new_pos = (int32_t *)p; p += up256(n * 4 + 4);
-    s->new_ncig = (uint32_t *)p; p += up256(n * 4 + 4);
-    s->ref_len = (int32_t *)p; p += up256(n * 4 + 4);
-    s->new_cig = (uint32_t *)p; p += up256(nc * 4 + 4);
-    s->trim_flags = p; p += up256(n + 1);
-    s->status = p;
-    Buf &b = s->b;
-    b.status = s->status;
-    BAM_MARK(s, 6);
-    if (n) {
-        amp_dev_reads rd;
-        BAM_OK(amp_bam_reads(s, &rd));
-        const amp_trim_out o{s->new_pos, s->new_ncig, s->new_cig, s->ref_len, s->trim_flags, s->status};
-        BAM_OK(amp_process_batch_device(s->ctx, &rd, read_base, &o));
-    }
-    BAM_MARK(s, 7);
-    BAM_OK(bam_zero(s, &b.ctl[CTL_FIRST_BAD], 0xFF, 8));
-    BAM_RUN(s, k_bam_first_bad, lane_first_bad, (int64_t)n, -1);
-    unsigned long long key = ~0ull;
-    BAM_OK(bam_down(s, &key, &b.ctl[CTL_FIRST_BAD], 8));
-    BAM_OK(bam_wait(s));
-    const bool any = key != ~0ull;
-    if (first_bad_row) *first_bad_row = any ? (int64_t)(key >> 8) : -1;
-    if (its_status) *its_status = any ? (uint8_t)(key & 255u) : 0;
-    return AMP_OK;
+    return codec_process(s->sh, s->b, s->trim, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded, read_base, 6, first_bad_row, its_status);
 }
 
 // milliseconds of the stages of the last feed / process on the ctx stream (HIP events); on != 0 switches the events on
-int amp_bam_stage_ms(amp_bam *s, int on, float *ms) {
-    if (!s) return AMP_EINVAL;
-    BAM_GUARD(s);
-    if (ms && s->timed) {
-        BAM_OK(bam_wait(s));
-        for (int k = 0; k < AMP_BAM_N_STAGES; ++k) if (hipEventElapsedTime(&ms[k], s->ev[k], s->ev[k + 1]) != hipSuccess) ms[k] = -1.f;
-    }
-    s->timed = on != 0;
-    return AMP_OK;
-}
+int amp_bam_stage_ms(amp_bam *s, int on, float *ms) { return s ? codec_stage_ms(s->sh, on, ms) : AMP_EINVAL; }
 #endif
 
 }  // extern "C"

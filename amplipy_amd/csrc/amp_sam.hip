@@ -23,34 +23,21 @@
 //
 // The same lane functions compile for the host (-DAMPSAM_HOSTSIM, no HIP headers needed: any C++ compiler, sanitizers
 // included) and a driver runs the stages lane after lane: the twin the CPU tests check against the Python codec.
-#ifndef AMPSAM_HOSTSIM
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-#define SAM_HD __host__ __device__ __forceinline__
-#else
-#define SAM_HD static inline
-#endif
-
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <new>
-
-#include "../../include/amplihip.h"
-#ifndef AMPSAM_HOSTSIM
-#include "amp_sam.hpp"
-#endif
+// What surrounds the stages -- stream, copies, scan, events, the batch's way into the read pass and back -- is the shell of
+// amp_codec.hpp.
+#include "amp_codec.hpp"
 
 namespace ampsam {
 
 enum { CTL_NLINES = 0, CTL_NREC, CTL_NROWS, CTL_NCIG, CTL_NBASES, CTL_NSLOTS, CTL_ODD, CTL_BADBYTE, CTL_FMT_BYTES, CTL_FMT_ROWS,
-       CTL_FIRST_BAD, CTL_WORDS = 16 };
+       CTL_WORDS = 16 };
 enum { FTABS = 11, WAVE = 64 };
 static const uint32_t QUAL_STAR = 0xFFFFFFFFu;
 
-// Every pointer of a chunk: device memory in the library, host memory in the twin.
-struct Buf {
+// Every pointer of a chunk: device memory in the library, host memory in the twin.  Buf is a kernel argument and its layout
+// the kernels' view of it: text and lines, the batch (amp_dev_reads: the shell's struct), the rows, the results of the read
+// pass (the shell's struct), format -- in this order.
+struct BufLines {
     const uint8_t *text; int64_t n_bytes, n_slots16, line_cap;
     uint32_t *mask;            // [n_slots16] newline bits | tab bits << 16
     uint32_t *lowmask;         // [n_slots16] bytes below '!' other than tab, newline and carriage return
@@ -61,32 +48,24 @@ struct Buf {
     uint32_t *ftab;            // [line_cap][FTABS]
     uint32_t *l_rec, *l_row, *l_ncig, *l_slots;      // per line: is a record, is a row, its CIGAR ops, its 8-base slots
     uint32_t *s_rec, *s_row, *s_ncig, *s_slots;      // their exclusive sums
-    // the batch (amp_dev_reads) and what format needs per row
-    int32_t *pos; uint16_t *flag; int32_t *tlen; uint32_t *lseq, *cig_off32, *cig, *seq_off8; uint8_t *seq, *qual;
-    int64_t *src_index; uint32_t *row_line, *row_seq, *row_qual;
+};
+struct BufRows {
+    uint32_t *row_line, *row_seq, *row_qual;       // what pack and format need per row
     // @SQ names
     const uint8_t *names; const uint32_t *ref_off; int32_t n_ref;
     unsigned long long *ctl;   // [CTL_WORDS]
-    // results of the read pass, format
-    const int32_t *new_pos; const uint32_t *new_ncig, *new_cig; const int32_t *ref_len; const uint8_t *trim_flags, *status;
+};
+struct Buf : BufLines, ampcodec::Batch, BufRows, ampcodec::Trim {
     uint32_t *out_off, *cig_tlen; uint8_t *out;
     int32_t min_length, include_no_primer; int64_t good_rows;
 };
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define SAM_MIN64(p, v) atomicMin((unsigned long long *)(p), (unsigned long long)(v))
-#define SAM_ADD64(p, v) atomicAdd((unsigned long long *)(p), (unsigned long long)(v))
-#else
-#define SAM_MIN64(p, v) do { if ((unsigned long long)(v) < *(p)) *(p) = (unsigned long long)(v); } while (0)
-#define SAM_ADD64(p, v) do { *(p) += (unsigned long long)(v); } while (0)
-#endif
-
-SAM_HD uint64_t load8(const uint8_t *p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
-SAM_HD void store8(uint8_t *p, uint64_t v) { __builtin_memcpy(p, &v, 8); }
-SAM_HD void odd(const Buf &b, int64_t line, int reason) { SAM_MIN64(&b.ctl[CTL_ODD], ((unsigned long long)line << 8) | (unsigned)reason); }
+AMP_HD uint64_t load8(const uint8_t *p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
+AMP_HD void store8(uint8_t *p, uint64_t v) { __builtin_memcpy(p, &v, 8); }
+AMP_HD void odd(const Buf &b, int64_t line, int reason) { AMP_MIN64(&b.ctl[CTL_ODD], ((unsigned long long)line << 8) | (unsigned)reason); }
 
 // ---- scan: lane = 16 bytes ---------------------------------------------------------------------------------------------
-SAM_HD void lane_scan(const Buf &b, int64_t j) {
+AMP_HD void lane_scan(const Buf &b, int64_t j) {
     const int64_t base = j * 16;
     uint32_t w[4];
     __builtin_memcpy(w, __builtin_assume_aligned(b.text + base, 16), 16);       // (the text buffer is 16-byte aligned and padded)
@@ -108,11 +87,11 @@ SAM_HD void lane_scan(const Buf &b, int64_t j) {
     b.lowmask[j] = low;
     b.rank[j] = (uint64_t)__builtin_popcount(nl) | ((uint64_t)__builtin_popcount(tab) << 32);
     b.lowrank[j] = (uint32_t)__builtin_popcount(low);
-    if (bad) SAM_MIN64(&b.ctl[CTL_BADBYTE], base + __builtin_ctz(bad));
+    if (bad) AMP_MIN64(&b.ctl[CTL_BADBYTE], base + __builtin_ctz(bad));
 }
 
 // ---- lines / tabs: lane = 16-byte slot, masks only ----------------------------------------------------------------------
-SAM_HD void lane_lines(const Buf &b, int64_t j) {
+AMP_HD void lane_lines(const Buf &b, int64_t j) {
     const uint32_t m = b.mask[j], tabm = m >> 16;
     uint32_t nl = m & 0xFFFFu;
     const uint64_t r = b.rank[j];
@@ -131,7 +110,7 @@ SAM_HD void lane_lines(const Buf &b, int64_t j) {
     if (j == b.n_slots16 - 1) b.ctl[CTL_NLINES] = line;
 }
 
-SAM_HD void lane_tabs(const Buf &b, int64_t j) {
+AMP_HD void lane_tabs(const Buf &b, int64_t j) {
     const uint32_t m = b.mask[j], nlm = m & 0xFFFFu;
     uint32_t tab = m >> 16;
     const uint64_t r = b.rank[j];
@@ -151,7 +130,7 @@ SAM_HD void lane_tabs(const Buf &b, int64_t j) {
 // ---- records: lane = line -------------------------------------------------------------------------------------------------
 struct Line { uint32_t start, end, ntab; };
 
-SAM_HD Line line_of(const Buf &b, int64_t i) {
+AMP_HD Line line_of(const Buf &b, int64_t i) {
     Line ln;
     ln.start = i ? b.nl_pos[i - 1] + 1u : 0u;
     ln.end = b.nl_pos[i];
@@ -161,13 +140,13 @@ SAM_HD Line line_of(const Buf &b, int64_t i) {
 }
 
 // field k (0..10) of a line with at least 10 tabs
-SAM_HD void field(const Buf &b, int64_t i, const Line &ln, int k, uint32_t &fs, uint32_t &fe) {
+AMP_HD void field(const Buf &b, int64_t i, const Line &ln, int k, uint32_t &fs, uint32_t &fe) {
     fs = k == 0 ? ln.start : b.ftab[(size_t)i * FTABS + k - 1] + 1u;
     fe = (k < 10 || ln.ntab >= FTABS) ? b.ftab[(size_t)i * FTABS + k] : ln.end;
 }
 
 // -?(0|[1-9][0-9]*) and not "-0" (int() reads it, str() does not give it back): 0 ok, 1 otherwise
-SAM_HD int parse_int(const uint8_t *t, uint32_t fs, uint32_t fe, int64_t &v) {
+AMP_HD int parse_int(const uint8_t *t, uint32_t fs, uint32_t fe, int64_t &v) {
     if (fe == fs) return 1;
     const bool neg = t[fs] == '-';
     uint32_t p = fs + (neg ? 1u : 0u);
@@ -184,7 +163,7 @@ SAM_HD int parse_int(const uint8_t *t, uint32_t fs, uint32_t fe, int64_t &v) {
 }
 
 // -2: '*', -1: not an @SQ name, else its number
-SAM_HD int name_id(const Buf &b, uint32_t fs, uint32_t fe) {
+AMP_HD int name_id(const Buf &b, uint32_t fs, uint32_t fe) {
     const uint32_t n = fe - fs;
     if (n == 1 && b.text[fs] == '*') return -2;
     for (int r = 0; r < b.n_ref; ++r) {
@@ -197,7 +176,7 @@ SAM_HD int name_id(const Buf &b, uint32_t fs, uint32_t fe) {
     return -1;
 }
 
-SAM_HD int cigar_op(uint32_t c) {
+AMP_HD int cigar_op(uint32_t c) {
     switch (c) {
         case 'M': return 0; case 'I': return 1; case 'D': return 2; case 'N': return 3; case 'S': return 4;
         case 'H': return 5; case 'P': return 6; case '=': return 7; case 'X': return 8; case 'B': return 9;
@@ -207,7 +186,7 @@ SAM_HD int cigar_op(uint32_t c) {
 
 // The CIGAR string: number of ops (0: '*'), -1 where parse_cigar would refuse it, -2 for an op length of 2^28 or more or one
 // written with leading zeros.  out != NULL: the BAM words.
-SAM_HD int cigar_scan(const uint8_t *t, uint32_t fs, uint32_t fe, uint32_t *out) {
+AMP_HD int cigar_scan(const uint8_t *t, uint32_t fs, uint32_t fe, uint32_t *out) {
     if (fe - fs == 1 && t[fs] == '*') return 0;
     if (fe == fs) return -1;
     int n = 0;
@@ -229,11 +208,11 @@ SAM_HD int cigar_scan(const uint8_t *t, uint32_t fs, uint32_t fe, uint32_t *out)
     return n;
 }
 
-SAM_HD uint32_t low_before(const Buf &b, uint32_t p) {
+AMP_HD uint32_t low_before(const Buf &b, uint32_t p) {
     return b.lowrank[p >> 4] + (uint32_t)__builtin_popcount(b.lowmask[p >> 4] & ((1u << (p & 15u)) - 1u));
 }
 
-SAM_HD void lane_records(const Buf &b, int64_t i) {
+AMP_HD void lane_records(const Buf &b, int64_t i) {
     uint32_t rec = 0, row = 0, ncig = 0, slots = 0;
     const int64_t n_lines = (int64_t)b.ctl[CTL_NLINES];
     if (i < n_lines) {
@@ -299,7 +278,7 @@ SAM_HD void lane_records(const Buf &b, int64_t i) {
 }
 
 // ---- rows: lane = line ----------------------------------------------------------------------------------------------------
-SAM_HD void lane_rows(const Buf &b, int64_t i) {
+AMP_HD void lane_rows(const Buf &b, int64_t i) {
     const int64_t n_lines = (int64_t)b.ctl[CTL_NLINES];
     const int64_t last = (n_lines < b.line_cap ? n_lines : b.line_cap) - 1;
     if (i > last) return;
@@ -321,7 +300,7 @@ SAM_HD void lane_rows(const Buf &b, int64_t i) {
         b.row_qual[r] = (fe - fs == 1 && t[fs] == '*') ? QUAL_STAR : fs;
         b.cig_off32[r] = b.s_ncig[i]; b.seq_off8[r] = b.s_slots[i];
         b.src_index[r] = (int64_t)b.s_rec[i]; b.row_line[r] = (uint32_t)i;
-        SAM_ADD64(&b.ctl[CTL_NBASES], L);
+        AMP_ADD64(&b.ctl[CTL_NBASES], L);
     }
     if (i == last) {
         const uint32_t n = b.s_row[i] + b.l_row[i];
@@ -333,7 +312,7 @@ SAM_HD void lane_rows(const Buf &b, int64_t i) {
 
 // ---- pack: lane = 8-base slot of the batch ----------------------------------------------------------------------------------
 // "=ACMGRSVTWYHKDBN" in both cases, any other byte 15: the letters a..p and q..z as nibbles of two constants
-SAM_HD uint32_t nt16(uint32_t c) {
+AMP_HD uint32_t nt16(uint32_t c) {
     if (c == '=') return 0;
     const uint32_t k = (c | 0x20u) - 'a';
     if (k < 16u) return (uint32_t)(0xFFF3FCFFB4FFD2E1ull >> (4 * k)) & 15u;
@@ -341,7 +320,7 @@ SAM_HD uint32_t nt16(uint32_t c) {
     return 15u;
 }
 
-SAM_HD void lane_pack(const Buf &b, int64_t s) {
+AMP_HD void lane_pack(const Buf &b, int64_t s) {
     const uint32_t n = (uint32_t)b.ctl[CTL_NROWS];
     uint32_t lo = 0, hi = n;                                  // the last row r with seq_off8[r] <= s (rows without bases own no slot)
     while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (b.seq_off8[mid] <= (uint32_t)s) lo = mid; else hi = mid; }
@@ -363,18 +342,18 @@ SAM_HD void lane_pack(const Buf &b, int64_t s) {
 }
 
 // ---- format -----------------------------------------------------------------------------------------------------------------
-SAM_HD uint32_t ndigits(uint64_t v) { uint32_t n = 1; while (v >= 10) { v /= 10; ++n; } return n; }
-SAM_HD uint32_t put_uint(uint8_t *p, uint64_t v) {
+AMP_HD uint32_t ndigits(uint64_t v) { uint32_t n = 1; while (v >= 10) { v /= 10; ++n; } return n; }
+AMP_HD uint32_t put_uint(uint8_t *p, uint64_t v) {
     const uint32_t n = ndigits(v);
     for (uint32_t k = n; k-- > 0;) { p[k] = (uint8_t)('0' + v % 10); v /= 10; }
     return n;
 }
-SAM_HD bool row_kept(const Buf &b, int64_t r) {                 // A:910, and nothing from the first failing read on (A:907-911)
+AMP_HD bool row_kept(const Buf &b, int64_t r) {                 // A:910, and nothing from the first failing read on (A:907-911)
     return r < b.good_rows && b.ref_len[r] >= b.min_length && ((b.trim_flags[r] & 3u) || b.include_no_primer);
 }
-SAM_HD const uint32_t *row_new_cig(const Buf &b, int64_t r) { return b.new_cig + b.cig_off32[r] + 3 * (size_t)r; }
+AMP_HD const uint32_t *row_new_cig(const Buf &b, int64_t r) { return b.new_cig + b.cig_off32[r] + 3 * (size_t)r; }
 
-SAM_HD void lane_fmt_len(const Buf &b, int64_t r) {
+AMP_HD void lane_fmt_len(const Buf &b, int64_t r) {
     uint32_t len = 0, ct = 0;
     if (row_kept(b, r)) {
         const int64_t i = b.row_line[r];
@@ -386,20 +365,20 @@ SAM_HD void lane_fmt_len(const Buf &b, int64_t r) {
         for (uint32_t k = 0; k < b.new_ncig[r]; ++k) ct += ndigits(w[k] >> 4) + 1u;
         const int64_t p1 = (int64_t)b.new_pos[r] + 1;
         len = (ln.end - ln.start) - (f3e - f3s) - (f5e - f5s) + ct + (p1 < 0 ? 1u + ndigits((uint64_t)-p1) : ndigits((uint64_t)p1)) + 1u;
-        SAM_ADD64(&b.ctl[CTL_FMT_ROWS], 1);
-        SAM_ADD64(&b.ctl[CTL_FMT_BYTES], len);
+        AMP_ADD64(&b.ctl[CTL_FMT_ROWS], 1);
+        AMP_ADD64(&b.ctl[CTL_FMT_BYTES], len);
     }
     b.out_off[r] = len; b.cig_tlen[r] = ct;
 }
 
 // n bytes by the 64 lanes of a wave, 8 per lane and step; the last n % 8 one per lane
-SAM_HD void wave_copy(uint8_t *dst, const uint8_t *src, uint32_t n, uint32_t lane) {
+AMP_HD void wave_copy(uint8_t *dst, const uint8_t *src, uint32_t n, uint32_t lane) {
     for (uint32_t o = lane * 8u; o + 8u <= n; o += WAVE * 8u) store8(dst + o, load8(src + o));
     const uint32_t tail = n & ~7u;
     if (tail + lane < n) dst[tail + lane] = src[tail + lane];
 }
 
-SAM_HD void lane_fmt_copy(const Buf &b, int64_t r, uint32_t lane) {
+AMP_HD void lane_fmt_copy(const Buf &b, int64_t r, uint32_t lane) {
     if (!row_kept(b, r)) return;
     const int64_t i = b.row_line[r];
     const Line ln = line_of(b, i);
@@ -430,19 +409,13 @@ SAM_HD void lane_fmt_copy(const Buf &b, int64_t r, uint32_t lane) {
     if (lane == 0) *d = '\n';
 }
 
-SAM_HD void lane_first_bad(const Buf &b, int64_t r) {
-    if (b.status[r]) SAM_MIN64(&b.ctl[CTL_FIRST_BAD], ((unsigned long long)r << 8) | b.status[r]);
-}
-
 // ---- layout of a chunk's memory ---------------------------------------------------------------------------------------------
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int64_t line_cap_for(int64_t n_bytes) { return n_bytes / 64 + 1024; }       // a record is far longer than 64 bytes; a chunk
                                                                                          // with more lines than this is odd (AMP_SAM_ODD_LINES)
 // Carves `base` (NULL: sizes only) for chunks of up to cap_bytes of text; returns the bytes needed.
 static size_t carve(Buf &b, uint8_t *base, int64_t cap_bytes) {
     const size_t n = (size_t)cap_bytes, S = n / 16 + 2, LC = (size_t)line_cap_for(cap_bytes);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { uint8_t *p = base ? base + o : nullptr; o += up256(bytes); return p; };
+    ampcodec::Carver take{base};
     b.text = take(n + 64);
     b.mask = (uint32_t *)take(S * 4); b.lowmask = (uint32_t *)take(S * 4); b.rank = (uint64_t *)take(S * 8); b.lowrank = (uint32_t *)take(S * 4);
     b.nl_pos = (uint32_t *)take(LC * 4); b.line_tab0 = (uint32_t *)take((LC + 1) * 4); b.ftab = (uint32_t *)take(LC * FTABS * 4);
@@ -456,162 +429,73 @@ static size_t carve(Buf &b, uint8_t *base, int64_t cap_bytes) {
     b.cig = (uint32_t *)take((n / 2 + 4) * 4); b.seq = take(n / 2 + 64); b.qual = take(n + 64);
     b.out_off = (uint32_t *)take((LC + 1) * 4); b.cig_tlen = (uint32_t *)take((LC + 1) * 4);
     b.ctl = (unsigned long long *)take(CTL_WORDS * 8);
-    return o;
+    return take.o;
 }
 
 }  // namespace ampsam
 
 using namespace ampsam;
+using namespace ampcodec;
 
-// ---- the two back ends: HIP kernels on the ctx stream, or plain loops -----------------------------------------------------------
 #ifndef AMPSAM_HOSTSIM
-#define SAM_KERNEL(name, fn)                                                                                          \
-    __global__ void __launch_bounds__(256) name(Buf b, int64_t n, int ctl) {                                          \
-        if (ctl >= 0 && (int64_t)b.ctl[ctl] < n) n = (int64_t)b.ctl[ctl];                                             \
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) fn(b, i);     \
-    }
-SAM_KERNEL(k_sam_scan, lane_scan)
-SAM_KERNEL(k_sam_lines, lane_lines)
-SAM_KERNEL(k_sam_tabs, lane_tabs)
-SAM_KERNEL(k_sam_records, lane_records)
-SAM_KERNEL(k_sam_rows, lane_rows)
-SAM_KERNEL(k_sam_pack, lane_pack)
-SAM_KERNEL(k_sam_fmt_len, lane_fmt_len)
-SAM_KERNEL(k_sam_first_bad, lane_first_bad)
+CODEC_KERNEL(k_sam_scan, lane_scan)
+CODEC_KERNEL(k_sam_lines, lane_lines)
+CODEC_KERNEL(k_sam_tabs, lane_tabs)
+CODEC_KERNEL(k_sam_records, lane_records)
+CODEC_KERNEL(k_sam_rows, lane_rows)
+CODEC_KERNEL(k_sam_pack, lane_pack)
+CODEC_KERNEL(k_sam_fmt_len, lane_fmt_len)
 __global__ void __launch_bounds__(256) k_sam_fmt_copy(Buf b, int64_t n_rows) {      // one wave per row
     const uint32_t lane = threadIdx.x & 63u;
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n_rows; r += (int64_t)gridDim.x * 4) lane_fmt_copy(b, r, lane);
 }
 #endif
+CODEC_FIRST_BAD_KERNEL(k_sam_first_bad)
 
 struct amp_sam {
+    Shell sh;
     Buf b{};
     int64_t cap_bytes = 0;
     uint8_t *arena = nullptr;
     uint8_t *names = nullptr; uint32_t *ref_off = nullptr; int32_t n_ref = -1;      // -1: amp_sam_set_references not called yet
-    uint8_t *res = nullptr; size_t res_cap = 0;       // results of the read pass
     uint8_t *out = nullptr; size_t out_cap = 0;       // output text
     amp_sam_info info{};
     bool parsed = false, processed = false;
     int64_t good_rows = 0;
     unsigned long long h_ctl[CTL_WORDS];
-#ifndef AMPSAM_HOSTSIM
-    amp_ctx *ctx = nullptr; int device = 0; hipStream_t stream = nullptr;
-    void *scan_tmp = nullptr; size_t scan_tmp_cap = 0;
-    hipEvent_t ev[AMP_SAM_N_STAGES + 1] = {};
-    bool timed = false;
-#endif
 };
-
-#ifndef AMPSAM_HOSTSIM
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); }
-    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-#define SAM_GUARD(s) DevGuard guard__((s)->device)
-#define SAM_TRY(call) do { if ((call) != hipSuccess) return AMP_EHIP; } while (0)
-static int sam_alloc(amp_sam *, uint8_t **p, size_t bytes) { return hipMalloc((void **)p, bytes) == hipSuccess ? AMP_OK : AMP_ENOMEM; }
-static void sam_free(uint8_t *p) { if (p) (void)hipFree(p); }
-static int sam_up(amp_sam *s, void *dst, const void *src, size_t n) { return !n || hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s->stream) == hipSuccess ? AMP_OK : AMP_EHIP; }
-static int sam_down(amp_sam *s, void *dst, const void *src, size_t n) { return !n || hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s->stream) == hipSuccess ? AMP_OK : AMP_EHIP; }
-static int sam_zero(amp_sam *s, void *p, int v, size_t n) { return hipMemsetAsync(p, v, n, s->stream) == hipSuccess ? AMP_OK : AMP_EHIP; }
-static int sam_wait(amp_sam *s) { return hipStreamSynchronize(s->stream) == hipSuccess ? AMP_OK : AMP_EHIP; }
-static unsigned sam_grid(int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : g > 4096 ? 4096 : g); }
-#define SAM_RUN(s, k, fn, n, cx) do { if ((n) > 0) { k<<<sam_grid(n), 256, 0, (s)->stream>>>((s)->b, (int64_t)(n), (cx)); if (hipGetLastError() != hipSuccess) return AMP_EHIP; } } while (0)
-static int sam_scan_tmp(amp_sam *s, size_t need) {
-    if (need <= s->scan_tmp_cap) return AMP_OK;
-    if (s->scan_tmp) { if (hipStreamSynchronize(s->stream) != hipSuccess) return AMP_EHIP; (void)hipFree(s->scan_tmp); s->scan_tmp = nullptr; s->scan_tmp_cap = 0; }
-    if (hipMalloc(&s->scan_tmp, need + 256) != hipSuccess) return AMP_ENOMEM;
-    s->scan_tmp_cap = need + 256;
-    return AMP_OK;
-}
-template <class T> static int sam_scan(amp_sam *s, T *p, int64_t n) {      // exclusive sum in place
-    if (n <= 0) return AMP_OK;
-    size_t need = 0;
-    SAM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, p, p, (int)n, s->stream));
-    const int rc = sam_scan_tmp(s, need);
-    if (rc) return rc;
-    size_t tb = s->scan_tmp_cap;
-    SAM_TRY(hipcub::DeviceScan::ExclusiveSum(s->scan_tmp, tb, p, p, (int)n, s->stream));
-    return AMP_OK;
-}
-#define SAM_MARK(s, k) do { if ((s)->timed) (void)hipEventRecord((s)->ev[k], (s)->stream); } while (0)
-#else
-#define SAM_GUARD(s) (void)0
-static int sam_alloc(amp_sam *, uint8_t **p, size_t bytes) { *p = (uint8_t *)malloc(bytes ? bytes : 1); return *p ? AMP_OK : AMP_ENOMEM; }
-static void sam_free(uint8_t *p) { free(p); }
-static int sam_up(amp_sam *, void *dst, const void *src, size_t n) { if (n) memcpy(dst, src, n); return AMP_OK; }
-static int sam_down(amp_sam *, void *dst, const void *src, size_t n) { if (n) memcpy(dst, src, n); return AMP_OK; }
-static int sam_zero(amp_sam *, void *p, int v, size_t n) { memset(p, v, n); return AMP_OK; }
-static int sam_wait(amp_sam *) { return AMP_OK; }
-#define SAM_RUN(s, k, fn, n, cx) do { int64_t n__ = (int64_t)(n); if ((cx) >= 0 && (int64_t)(s)->b.ctl[(cx) < 0 ? 0 : (cx)] < n__) n__ = (int64_t)(s)->b.ctl[(cx) < 0 ? 0 : (cx)]; \
-                                       for (int64_t i__ = 0; i__ < n__; ++i__) fn((s)->b, i__); } while (0)
-template <class T> static int sam_scan(amp_sam *, T *p, int64_t n) { T a = 0; for (int64_t i = 0; i < n; ++i) { const T v = p[i]; p[i] = a; a += v; } return AMP_OK; }
-#define SAM_MARK(s, k) (void)0
-#endif
-#define SAM_OK(call) do { const int rc__ = (call); if (rc__) return rc__; } while (0)
 
 static int sam_ensure(amp_sam *s, int64_t n_bytes) {
     if (n_bytes <= s->cap_bytes) return AMP_OK;
-    SAM_OK(sam_wait(s));
+    CODEC_OK(codec_sync(s->sh));
     const int64_t cap = n_bytes + n_bytes / 8 + 4096;           // chunks of a run have one size: grown once, then reused
     Buf nb = s->b;
     const size_t bytes = carve(nb, nullptr, cap);
     uint8_t *p = nullptr;
-    SAM_OK(sam_alloc(s, &p, bytes));
-    sam_free(s->arena);
+    CODEC_OK(codec_alloc(&p, bytes));
+    codec_free(s->arena);
     s->arena = p; s->cap_bytes = cap;
     (void)carve(s->b, p, cap);
-    return AMP_OK;
-}
-
-static int sam_grow(amp_sam *s, uint8_t **p, size_t *cap, size_t need) {
-    if (need <= *cap) return AMP_OK;
-    SAM_OK(sam_wait(s));
-    uint8_t *np = nullptr;
-    const size_t ncap = need + need / 4 + 4096;
-    SAM_OK(sam_alloc(s, &np, ncap));
-    sam_free(*p);
-    *p = np; *cap = ncap;
     return AMP_OK;
 }
 
 extern "C" {
 
 // bamio.AlignmentReader / AlignmentWriter of one run; A:296-360
-int amp_sam_create(amp_ctx *ctx, amp_sam **out) {
-    if (!out) return AMP_EINVAL;
-#ifndef AMPSAM_HOSTSIM
-    if (!ctx) return AMP_EINVAL;
-#endif
-    amp_sam *s = new (std::nothrow) amp_sam();
-    if (!s) return AMP_ENOMEM;
-#ifndef AMPSAM_HOSTSIM
-    s->ctx = ctx; s->device = amp::ctx_device(ctx); s->stream = amp::ctx_stream(ctx);
-    SAM_GUARD(s);
-    for (hipEvent_t &e : s->ev) if (hipEventCreate(&e) != hipSuccess) { delete s; return AMP_EHIP; }
-#endif
-    *out = s;
-    return AMP_OK;
-}
+int amp_sam_create(amp_ctx *ctx, amp_sam **out) { return codec_new(ctx, out, AMP_SAM_N_STAGES, k_sam_first_bad); }
 
 void amp_sam_destroy(amp_sam *s) {
     if (!s) return;
-    SAM_GUARD(s);
-    (void)sam_wait(s);
-    sam_free(s->arena); sam_free(s->names); sam_free((uint8_t *)s->ref_off); sam_free(s->res); sam_free(s->out);
-#ifndef AMPSAM_HOSTSIM
-    if (s->scan_tmp) (void)hipFree(s->scan_tmp);
-    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
-#endif
-    delete s;
+    DevGuard guard(s->sh);
+    (void)codec_wait(s->sh);
+    codec_free(s->arena); codec_free(s->names); codec_free(s->ref_off); codec_free(s->out);
+    codec_delete(s);
 }
 
 // the @SQ SN names in header order: header.refs of bamio.AlignmentReader (what RNAME / RNEXT are looked up in)
 int amp_sam_set_references(amp_sam *s, int32_t n_ref, const char *const *names) {
     if (!s || n_ref < 0 || n_ref > AMP_SAM_MAX_REFS || (n_ref && !names)) return AMP_EINVAL;
-    SAM_GUARD(s);
+    DevGuard guard(s->sh);
     uint32_t off[AMP_SAM_MAX_REFS + 1];
     size_t tot = 0;
     for (int32_t r = 0; r < n_ref; ++r) {
@@ -622,14 +506,14 @@ int amp_sam_set_references(amp_sam *s, int32_t n_ref, const char *const *names) 
     }
     off[n_ref] = (uint32_t)tot;
     if (!s->names) {
-        SAM_OK(sam_alloc(s, &s->names, AMP_SAM_MAX_REF_BYTES + 16));
-        SAM_OK(sam_alloc(s, (uint8_t **)&s->ref_off, sizeof(off)));
+        CODEC_OK(codec_alloc(&s->names, AMP_SAM_MAX_REF_BYTES + 16));
+        CODEC_OK(codec_alloc((uint8_t **)&s->ref_off, sizeof(off)));
     }
     uint8_t blob[AMP_SAM_MAX_REF_BYTES + 16];
     for (int32_t r = 0; r < n_ref; ++r) memcpy(blob + off[r], names[r], off[r + 1] - off[r]);
-    SAM_OK(sam_up(s, s->names, blob, tot));
-    SAM_OK(sam_up(s, s->ref_off, off, sizeof(uint32_t) * (size_t)(n_ref + 1)));
-    SAM_OK(sam_wait(s));
+    CODEC_OK(codec_up(s->sh, s->names, blob, tot));
+    CODEC_OK(codec_up(s->sh, s->ref_off, off, sizeof(uint32_t) * (size_t)(n_ref + 1)));
+    CODEC_OK(codec_wait(s->sh));
     s->n_ref = n_ref;
     return AMP_OK;
 }
@@ -639,44 +523,44 @@ int amp_sam_parse(amp_sam *s, const uint8_t *text, int64_t n_bytes, amp_sam_info
     if (!s || !info || n_bytes < 0 || n_bytes >= (1ll << 30) || (n_bytes && !text)) return AMP_EINVAL;
     if (n_bytes && text[n_bytes - 1] != '\n') return AMP_EINVAL;
     if (s->n_ref < 0) return AMP_ESTATE;
-    SAM_GUARD(s);
+    DevGuard guard(s->sh);
     s->parsed = s->processed = false;
     amp_sam_info z{};
     z.first_odd_line = -1;
     s->info = *info = z;
-    SAM_OK(sam_ensure(s, n_bytes > 0 ? n_bytes : 1));
+    CODEC_OK(sam_ensure(s, n_bytes > 0 ? n_bytes : 1));
     Buf &b = s->b;
     b.n_bytes = n_bytes; b.n_slots16 = (n_bytes + 15) / 16; b.line_cap = line_cap_for(n_bytes);
     b.names = s->names; b.ref_off = s->ref_off; b.n_ref = s->n_ref;
-    SAM_MARK(s, 0);
-    SAM_OK(sam_up(s, (void *)b.text, text, (size_t)n_bytes));
-    SAM_OK(sam_zero(s, (uint8_t *)b.text + n_bytes, 0, 48));
-    SAM_OK(sam_zero(s, b.ctl, 0, CTL_WORDS * 8));
-    SAM_OK(sam_zero(s, &b.ctl[CTL_ODD], 0xFF, 16));             // CTL_ODD, CTL_BADBYTE: minima
-    SAM_OK(sam_zero(s, b.cig_off32, 0, 4));
-    SAM_OK(sam_zero(s, b.seq_off8, 0, 4));
-    SAM_MARK(s, 1);
+    codec_mark(s->sh, 0);
+    CODEC_OK(codec_up(s->sh, (void *)b.text, text, (size_t)n_bytes));
+    CODEC_OK(codec_zero(s->sh, (uint8_t *)b.text + n_bytes, 0, 48));
+    CODEC_OK(codec_zero(s->sh, b.ctl, 0, CTL_WORDS * 8));
+    CODEC_OK(codec_zero(s->sh, &b.ctl[CTL_ODD], 0xFF, 16));             // CTL_ODD, CTL_BADBYTE: minima
+    CODEC_OK(codec_zero(s->sh, b.cig_off32, 0, 4));
+    CODEC_OK(codec_zero(s->sh, b.seq_off8, 0, 4));
+    codec_mark(s->sh, 1);
     if (n_bytes) {
         const int64_t S = b.n_slots16, LC = b.line_cap;
-        SAM_RUN(s, k_sam_scan, lane_scan, S, -1);
-        SAM_OK(sam_scan(s, b.rank, S));
-        SAM_OK(sam_scan(s, b.lowrank, S));
-        SAM_MARK(s, 2);
-        SAM_RUN(s, k_sam_lines, lane_lines, S, -1);
-        SAM_RUN(s, k_sam_tabs, lane_tabs, S, -1);
-        SAM_MARK(s, 3);
-        SAM_RUN(s, k_sam_records, lane_records, LC, -1);
-        SAM_OK(sam_scan(s, b.s_rec, LC));
-        SAM_OK(sam_scan(s, b.s_row, LC));
-        SAM_OK(sam_scan(s, b.s_ncig, LC));
-        SAM_OK(sam_scan(s, b.s_slots, LC));
-        SAM_RUN(s, k_sam_rows, lane_rows, LC, CTL_NLINES);
-        SAM_MARK(s, 4);
-        SAM_RUN(s, k_sam_pack, lane_pack, n_bytes / 8 + 1, CTL_NSLOTS);
-        SAM_MARK(s, 5);
+        CODEC_RUN(s, k_sam_scan, lane_scan, S, -1);
+        CODEC_OK(codec_scan(s->sh, b.rank, S));
+        CODEC_OK(codec_scan(s->sh, b.lowrank, S));
+        codec_mark(s->sh, 2);
+        CODEC_RUN(s, k_sam_lines, lane_lines, S, -1);
+        CODEC_RUN(s, k_sam_tabs, lane_tabs, S, -1);
+        codec_mark(s->sh, 3);
+        CODEC_RUN(s, k_sam_records, lane_records, LC, -1);
+        CODEC_OK(codec_scan(s->sh, b.s_rec, LC));
+        CODEC_OK(codec_scan(s->sh, b.s_row, LC));
+        CODEC_OK(codec_scan(s->sh, b.s_ncig, LC));
+        CODEC_OK(codec_scan(s->sh, b.s_slots, LC));
+        CODEC_RUN(s, k_sam_rows, lane_rows, LC, CTL_NLINES);
+        codec_mark(s->sh, 4);
+        CODEC_RUN(s, k_sam_pack, lane_pack, n_bytes / 8 + 1, CTL_NSLOTS);
+        codec_mark(s->sh, 5);
     }
-    SAM_OK(sam_down(s, s->h_ctl, b.ctl, CTL_WORDS * 8));
-    SAM_OK(sam_wait(s));
+    CODEC_OK(codec_down(s->sh, s->h_ctl, b.ctl, CTL_WORDS * 8));
+    CODEC_OK(codec_wait(s->sh));
     const unsigned long long *c = s->h_ctl;
     amp_sam_info &I = s->info;
     I.n_lines = (int64_t)c[CTL_NLINES]; I.n_records = (int64_t)c[CTL_NREC]; I.n_rows = (int64_t)c[CTL_NROWS];
@@ -692,8 +576,7 @@ int amp_sam_parse(amp_sam *s, const uint8_t *text, int64_t n_bytes, amp_sam_info
 int amp_sam_reads(amp_sam *s, amp_dev_reads *out) {
     if (!s || !out) return AMP_EINVAL;
     if (!s->parsed) return AMP_ESTATE;
-    const Buf &b = s->b;
-    *out = amp_dev_reads{s->info.n_rows, b.pos, b.flag, b.tlen, b.lseq, b.cig_off32, b.cig, b.seq_off8, b.seq, b.qual, s->info.n_cig, s->info.n_bases_padded};
+    *out = codec_reads(s->b, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded);
     return AMP_OK;
 }
 
@@ -701,60 +584,15 @@ int amp_sam_reads(amp_sam *s, amp_dev_reads *out) {
 int amp_sam_batch_to_host(amp_sam *s, const amp_reads *dst, int64_t *src_index) {
     if (!s || !dst) return AMP_EINVAL;
     if (!s->parsed) return AMP_ESTATE;
-    const int64_t n = s->info.n_rows;
-    if (dst->n_reads != n) return AMP_EINVAL;
-    SAM_GUARD(s);
-    const Buf &b = s->b;
-    uint32_t *co = (uint32_t *)malloc(((size_t)n + 1) * 8);
-    if (!co) return AMP_ENOMEM;
-    uint32_t *so = co + n + 1;
-    int rc = AMP_OK;
-    if (dst->pos) rc = rc ? rc : sam_down(s, (void *)dst->pos, b.pos, (size_t)n * 4);
-    if (dst->flag) rc = rc ? rc : sam_down(s, (void *)dst->flag, b.flag, (size_t)n * 2);
-    if (dst->tlen) rc = rc ? rc : sam_down(s, (void *)dst->tlen, b.tlen, (size_t)n * 4);
-    if (dst->lseq) rc = rc ? rc : sam_down(s, (void *)dst->lseq, b.lseq, (size_t)n * 4);
-    if (dst->cig) rc = rc ? rc : sam_down(s, (void *)dst->cig, b.cig, (size_t)s->info.n_cig * 4);
-    if (dst->seq) rc = rc ? rc : sam_down(s, (void *)dst->seq, b.seq, (size_t)s->info.n_bases_padded / 2);
-    if (dst->qual) rc = rc ? rc : sam_down(s, (void *)dst->qual, b.qual, (size_t)s->info.n_bases_padded);
-    if (src_index) rc = rc ? rc : sam_down(s, src_index, b.src_index, (size_t)n * 8);
-    rc = rc ? rc : sam_down(s, co, b.cig_off32, ((size_t)n + 1) * 4);
-    rc = rc ? rc : sam_down(s, so, b.seq_off8, ((size_t)n + 1) * 4);
-    rc = rc ? rc : sam_wait(s);
-    for (int64_t i = 0; !rc && i <= n; ++i) {
-        if (dst->cig_off) ((uint64_t *)dst->cig_off)[i] = co[i];
-        if (dst->seq_off) ((uint64_t *)dst->seq_off)[i] = (uint64_t)so[i] * 8;
-    }
-    free(co);
-    return rc;
+    return codec_batch_to_host(s->sh, s->b, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded, dst, src_index, 0);
 }
 
-static int sam_results_room(amp_sam *s) {
-    const size_t n = (size_t)s->info.n_rows, nc = (size_t)s->info.n_cig + 3 * n;
-    const size_t need = 3 * up256(n * 4 + 4) + up256(nc * 4 + 4) + 2 * up256(n + 1);
-    SAM_OK(sam_grow(s, &s->res, &s->res_cap, need));
-    uint8_t *p = s->res;
-    Buf &b = s->b;
-    b.new_pos = (int32_t *)p; p += up256(n * 4 + 4);
-    b.new_ncig = (uint32_t *)p; p += up256(n * 4 + 4);
-    b.ref_len = (int32_t *)p; p += up256(n * 4 + 4);
-    b.new_cig = (uint32_t *)p; p += up256(nc * 4 + 4);
-    b.trim_flags = p; p += up256(n + 1);
-    b.status = p;
-    return AMP_OK;
-}
-
-static int sam_first_bad(amp_sam *s, int64_t *first_bad_row, uint8_t *its_status) {
-    Buf &b = s->b;
-    SAM_OK(sam_zero(s, &b.ctl[CTL_FIRST_BAD], 0xFF, 8));
-    SAM_RUN(s, k_sam_first_bad, lane_first_bad, s->info.n_rows, -1);
-    unsigned long long key = ~0ull;
-    SAM_OK(sam_down(s, &key, &b.ctl[CTL_FIRST_BAD], 8));
-    SAM_OK(sam_wait(s));
-    const bool any = key != ~0ull;
-    s->good_rows = any ? (int64_t)(key >> 8) : s->info.n_rows;
-    if (first_bad_row) *first_bad_row = any ? (int64_t)(key >> 8) : -1;
-    if (its_status) *its_status = any ? (uint8_t)(key & 255u) : 0;
+// format writes nothing from the first failing row on
+static int sam_processed(amp_sam *s, int rc, int64_t bad, int64_t *first_bad_row) {
+    if (rc) return rc;
+    s->good_rows = bad >= 0 ? bad : s->info.n_rows;
     s->processed = true;
+    if (first_bad_row) *first_bad_row = bad;
     return AMP_OK;
 }
 
@@ -763,44 +601,28 @@ static int sam_first_bad(amp_sam *s, int64_t *first_bad_row, uint8_t *its_status
 int amp_sam_process(amp_sam *s, uint64_t read_base, int64_t *first_bad_row, uint8_t *its_status) {
     if (!s) return AMP_EINVAL;
     if (!s->parsed || s->info.first_odd_line >= 0) return AMP_ESTATE;
-    SAM_GUARD(s);
-    SAM_OK(sam_results_room(s));
-    const Buf &b = s->b;
-    SAM_MARK(s, 6);
-    if (s->info.n_rows) {
-        amp_dev_reads rd;
-        SAM_OK(amp_sam_reads(s, &rd));
-        const amp_trim_out o{(int32_t *)b.new_pos, (uint32_t *)b.new_ncig, (uint32_t *)b.new_cig, (int32_t *)b.ref_len, (uint8_t *)b.trim_flags, (uint8_t *)b.status};
-        SAM_OK(amp_process_batch_device(s->ctx, &rd, read_base, &o));
-    }
-    SAM_MARK(s, 7);
-    return sam_first_bad(s, first_bad_row, its_status);
+    int64_t bad = -1;
+    const int rc = codec_process(s->sh, s->b, s->b, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded, read_base, 6, &bad, its_status);
+    return sam_processed(s, rc, bad, first_bad_row);
 }
 
 // milliseconds of the stages of the last parse / process / format on the ctx stream (HIP events); on != 0 switches the events on
-int amp_sam_stage_ms(amp_sam *s, int on, float *ms) {
-    if (!s) return AMP_EINVAL;
-    SAM_GUARD(s);
-    if (ms && s->timed) {
-        SAM_OK(sam_wait(s));
-        for (int k = 0; k < AMP_SAM_N_STAGES; ++k) if (hipEventElapsedTime(&ms[k], s->ev[k], s->ev[k + 1]) != hipSuccess) ms[k] = -1.f;
-    }
-    s->timed = on != 0;
-    return AMP_OK;
-}
+int amp_sam_stage_ms(amp_sam *s, int on, float *ms) { return s ? codec_stage_ms(s->sh, on, ms) : AMP_EINVAL; }
 #else
 // the twin has no read pass: the test hands it the results the format stage is to work from
 int amp_sam_twin_set_results(amp_sam *s, const int32_t *new_pos, const uint32_t *new_ncig, const uint32_t *new_cig, const int32_t *ref_len,
                              const uint8_t *trim_flags, const uint8_t *status, int64_t *first_bad_row, uint8_t *its_status) {
     if (!s || !new_pos || !new_ncig || !new_cig || !ref_len || !trim_flags || !status) return AMP_EINVAL;
     if (!s->parsed || s->info.first_odd_line >= 0) return AMP_ESTATE;
-    SAM_OK(sam_results_room(s));
+    CODEC_OK(codec_results_room(s->sh, s->info.n_rows, s->info.n_cig, s->b));
     const Buf &b = s->b;
     const size_t n = (size_t)s->info.n_rows;
     memcpy((void *)b.new_pos, new_pos, n * 4); memcpy((void *)b.new_ncig, new_ncig, n * 4); memcpy((void *)b.ref_len, ref_len, n * 4);
     memcpy((void *)b.new_cig, new_cig, ((size_t)s->info.n_cig + 3 * n) * 4);
     memcpy((void *)b.trim_flags, trim_flags, n); memcpy((void *)b.status, status, n);
-    return sam_first_bad(s, first_bad_row, its_status);
+    int64_t bad = -1;
+    const int rc = codec_first_bad(s->sh, s->b, s->info.n_rows, &bad, its_status);
+    return sam_processed(s, rc, bad, first_bad_row);
 }
 #endif
 
@@ -808,35 +630,35 @@ int amp_sam_twin_set_results(amp_sam *s, const int32_t *new_pos, const uint32_t 
 int amp_sam_format(amp_sam *s, int32_t min_length, int32_t include_no_primer, uint8_t *out, int64_t cap, int64_t *n_bytes, int64_t *n_rows_written) {
     if (!s || !n_bytes || cap < 0 || (cap && !out)) return AMP_EINVAL;
     if (!s->parsed || !s->processed) return AMP_EINVAL;
-    SAM_GUARD(s);
+    DevGuard guard(s->sh);
     Buf &b = s->b;
     const int64_t n = s->info.n_rows;
     b.min_length = min_length; b.include_no_primer = include_no_primer ? 1 : 0; b.good_rows = s->good_rows;
-    SAM_MARK(s, 8);
-    SAM_OK(sam_zero(s, &b.ctl[CTL_FMT_BYTES], 0, 16));
-    SAM_RUN(s, k_sam_fmt_len, lane_fmt_len, n, -1);
-    SAM_OK(sam_scan(s, b.out_off, n));
+    codec_mark(s->sh, 8);
+    CODEC_OK(codec_zero(s->sh, &b.ctl[CTL_FMT_BYTES], 0, 16));
+    CODEC_RUN(s, k_sam_fmt_len, lane_fmt_len, n, -1);
+    CODEC_OK(codec_scan(s->sh, b.out_off, n));
     unsigned long long tot[2] = {0, 0};
-    SAM_OK(sam_down(s, tot, &b.ctl[CTL_FMT_BYTES], 16));
-    SAM_OK(sam_wait(s));
+    CODEC_OK(codec_down(s->sh, tot, &b.ctl[CTL_FMT_BYTES], 16));
+    CODEC_OK(codec_wait(s->sh));
     *n_bytes = (int64_t)tot[0];
     if (n_rows_written) *n_rows_written = (int64_t)tot[1];
     if ((int64_t)tot[0] > cap) return AMP_EOVERFLOW;
     if (tot[0] >= (1ull << 32)) return AMP_EOVERFLOW;
-    SAM_OK(sam_grow(s, &s->out, &s->out_cap, (size_t)tot[0] + 64));
+    CODEC_OK(codec_grow(s->sh, &s->out, &s->out_cap, (size_t)tot[0] + 64));
     b.out = s->out;
 #ifndef AMPSAM_HOSTSIM
     if (n > 0 && tot[0]) {
-        k_sam_fmt_copy<<<sam_grid(n * 64), 256, 0, s->stream>>>(b, n);
+        k_sam_fmt_copy<<<codec_grid(n * 64), 256, 0, s->sh.stream>>>(b, n);
         if (hipGetLastError() != hipSuccess) return AMP_EHIP;
     }
 #else
     for (int64_t r = 0; r < n; ++r) for (uint32_t lane = 0; lane < WAVE; ++lane) lane_fmt_copy(b, r, lane);
 #endif
-    SAM_MARK(s, 9);
-    SAM_OK(sam_down(s, out, s->out, (size_t)tot[0]));
-    SAM_MARK(s, 10);
-    return sam_wait(s);
+    codec_mark(s->sh, 9);
+    CODEC_OK(codec_down(s->sh, out, s->out, (size_t)tot[0]));
+    codec_mark(s->sh, 10);
+    return codec_wait(s->sh);
 }
 
 }  // extern "C"

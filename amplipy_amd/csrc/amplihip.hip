@@ -25,7 +25,8 @@
 #include "amp_fast7.hpp"
 #include "amp_wave.hpp"
 #include "amp_ins.hpp"
-#include "amp_sam.hpp"
+#define AMP_CODEC_CTX_ONLY
+#include "amp_codec.hpp"
 
 using namespace amp;
 
@@ -792,7 +793,7 @@ __global__ void k_event_strings(amp_dev_reads rd, uint64_t read_base, int64_t n_
     for (int32_t q = ev[e].q_from; q < ev[e].q_to; ++q) *dst++ = (uint8_t)nt16[base_code(rd.seq, boff, q)];
 }
 
-// what amp_sam.hip (a translation unit of its own) needs to know of a ctx
+// what the device codecs (translation units of their own: amp_codec.hpp) need to know of a ctx
 namespace amp {
 hipStream_t ctx_stream(const amp_ctx *c) { return c->stream; }
 int ctx_device(const amp_ctx *c) { return c->device; }

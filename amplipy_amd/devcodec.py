@@ -1,0 +1,124 @@
+"""What the device codecs of libamplihip.so share on the Python side (sam_native / amp_sam_*, bam_device / amp_bam_*; the C
+half is amplipy_amd/csrc/amp_codec.hpp): the binding of the entry points every codec has, the build of a host twin, and the
+thread that reads one piece ahead of the consumer."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import queue
+import shutil
+import subprocess
+import threading
+
+import numpy as np
+
+from . import abi
+from .batch import ReadBatch
+
+
+def build_twin(source, define, out_path, sanitize=False, main_source=None):
+    """``source``'s lane functions and a driver that runs them lane after lane, compiled for the host with -D``define`` (no HIP
+    needed): a shared library with the codec's entry points, or, with ``main_source``, a program around them.
+    sanitize: -fsanitize=address,undefined (host code only)."""
+    cmd = [shutil.which("g++") or "g++", "-x", "c++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
+           "-D" + define]
+    if sanitize:
+        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+    if main_source is None:
+        cmd += ["-fPIC", "-shared", "-o", out_path, source]
+    else:
+        cmd += ["-I", os.path.dirname(source), "-o", out_path, main_source]
+    subprocess.check_call(cmd)
+    return out_path
+
+
+def read_ahead(items):
+    """The items of ``items`` (an iterable), produced one ahead of the consumer on a helper thread; what it raises there is raised
+    here."""
+    q = queue.Queue(maxsize=1)
+
+    def run():
+        try:
+            for c in items:
+                q.put(c)
+            q.put(None)
+        except Exception as e:          # surfaced by the consumer
+            q.put(e)
+    threading.Thread(target=run, daemon=True).start()
+    while True:
+        c = q.get()
+        if c is None:
+            return
+        if isinstance(c, Exception):
+            raise c
+        yield c
+
+
+class DeviceCodec:
+    """One codec object of libamplihip.so (``prefix``: "amp_sam" / "amp_bam", with ``n_stages`` timed stages): on the device of
+    ``engine`` (lib.Engine), or the host twin when ``twin`` is the path of its library.  ``self.info`` = the info struct of
+    the last piece (n_rows, n_cig, n_bases_padded)."""
+
+    def __init__(self, prefix, n_stages, engine=None, twin=None):
+        if twin is not None:
+            self.L = C.CDLL(twin); self.is_twin = True; ctx = None
+        else:
+            from . import lib
+            self.L = lib.load(); self.is_twin = False; ctx = engine.h
+        self.prefix, self.n_stages = prefix, n_stages
+        self._fn("destroy").restype = None
+        self._fn("destroy").argtypes = [C.c_void_p]
+        self.h = C.c_void_p()
+        self._chk(self._fn("create")(ctx, C.byref(self.h)), prefix + "_create")
+        self.info = None
+
+    def _fn(self, name):
+        return getattr(self.L, "%s_%s" % (self.prefix, name))
+
+    def _chk(self, rc, where):
+        if rc:
+            from .lib import AmpliHipError
+            raise AmpliHipError(rc, where)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def dev_reads(self):
+        rd = abi.AmpDevReads()
+        self._chk(self._fn("reads")(self.h, C.byref(rd)), self.prefix + "_reads")
+        return rd
+
+    def batch(self, slack=0):
+        """(the batch of the last piece as a host ReadBatch with src_index = the rows' records, the ``slack`` spare bytes behind
+        cig, seq and qual as three arrays).  slack: what the codec's batch_to_host copies, 0 or 16."""
+        n, nc, nb = int(self.info.n_rows), int(self.info.n_cig), int(self.info.n_bases_padded)
+        sw, sb = slack // 4, slack
+        a = dict(pos=np.zeros(n, np.int32), flag=np.zeros(n, np.uint16), tlen=np.zeros(n, np.int32), lseq=np.zeros(n, np.uint32),
+                 cig_off=np.zeros(n + 1, np.uint64), cig=np.full(nc + sw, 0xA5A5A5A5, np.uint32), seq_off=np.zeros(n + 1, np.uint64),
+                 seq=np.full(nb // 2 + sb, 0xA5, np.uint8), qual=np.full(nb + sb, 0xA5, np.uint8))
+        src = np.zeros(n, np.int64)
+        st = abi.AmpReads(n, *[abi.ptr(a[k]) for k in ("pos", "flag", "tlen", "lseq", "cig_off", "cig", "seq_off", "seq", "qual")])
+        self._chk(self._fn("batch_to_host")(self.h, C.byref(st), C.c_void_p(abi.ptr(src))), self.prefix + "_batch_to_host")
+        tails = (a["cig"][nc:].copy(), a["seq"][nb // 2:].copy(), a["qual"][nb:].copy())
+        rb = ReadBatch(a["pos"], a["flag"], a["tlen"], a["lseq"], a["cig_off"], a["cig"][:nc], a["seq_off"], a["seq"][:nb // 2], a["qual"][:nb],
+                       src_index=src)
+        return rb, tails
+
+    def process(self, read_base=0):
+        """amp_*_process: (first row with a non-zero status or -1, that status)."""
+        bad = C.c_int64(-1); st = C.c_uint8(0)
+        self._chk(self._fn("process")(self.h, C.c_uint64(read_base), C.byref(bad), C.byref(st)), self.prefix + "_process")
+        return int(bad.value), int(st.value)
+
+    def stage_ms(self, on=True, read=True):
+        ms = (C.c_float * self.n_stages)(*([-1.0] * self.n_stages))
+        self._chk(self._fn("stage_ms")(self.h, C.c_int(1 if on else 0), ms if read else None), self.prefix + "_stage_ms")
+        return [float(x) for x in ms]

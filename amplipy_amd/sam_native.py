@@ -13,16 +13,11 @@ from __future__ import annotations
 import ctypes as C
 import io
 import os
-import queue
-import shutil
-import subprocess
 import sys
-import threading
 
 import numpy as np
 
-from . import abi
-from .batch import ReadBatch
+from . import abi, devcodec
 
 CHUNK_BYTES = 16 << 20             # text per device chunk (AMPLIPY_SAM_CHUNK_BYTES): see the sweep in DESIGN.md section 10
 MAX_REFS = 64                      # AMP_SAM_MAX_REFS / AMP_SAM_MAX_REF_BYTES of amplihip.h
@@ -51,50 +46,15 @@ def build_twin(out_path, sanitize=False, main_source=None):
     """The kernels' lane functions and a driver that runs them lane after lane, compiled for the host (no HIP needed):
     a shared library with the amp_sam_* entry points (amp_sam_twin_set_results in place of amp_sam_process), or, with
     ``main_source``, a program around them.  sanitize: -fsanitize=address,undefined (host code only)."""
-    src, _ = twin_sources()
-    cmd = [shutil.which("g++") or "g++", "-x", "c++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-           "-DAMPSAM_HOSTSIM"]
-    if sanitize:
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
-    if main_source is None:
-        cmd += ["-fPIC", "-shared", "-o", out_path, src]
-    else:
-        cmd += ["-I", os.path.dirname(src), "-o", out_path, main_source]
-    subprocess.check_call(cmd)
-    return out_path
+    return devcodec.build_twin(twin_sources()[0], "AMPSAM_HOSTSIM", out_path, sanitize, main_source)
 
 
-class SamCodec:
+class SamCodec(devcodec.DeviceCodec):
     """One amp_sam: on the device of ``engine`` (lib.Engine), or the host twin when ``twin`` is the path of its library."""
 
     def __init__(self, engine=None, twin=None):
-        if twin is not None:
-            self.L = C.CDLL(twin); self.is_twin = True; ctx = None
-        else:
-            from . import lib
-            self.L = lib.load(); self.is_twin = False; ctx = engine.h
-        self.L.amp_sam_destroy.restype = None
-        self.L.amp_sam_destroy.argtypes = [C.c_void_p]
-        self.h = C.c_void_p()
-        self._chk(self.L.amp_sam_create(ctx, C.byref(self.h)), "amp_sam_create")
-        self.info = None
+        super().__init__("amp_sam", N_STAGES, engine, twin)
         self._out = np.zeros(1 << 16, np.uint8)
-
-    def _chk(self, rc, where):
-        if rc:
-            from .lib import AmpliHipError
-            raise AmpliHipError(rc, where)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.amp_sam_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_references(self, names):
         enc = [n.encode("ascii") for n in names]
@@ -109,27 +69,9 @@ class SamCodec:
         self.info = info
         return info
 
-    def dev_reads(self):
-        rd = abi.AmpDevReads()
-        self._chk(self.L.amp_sam_reads(self.h, C.byref(rd)), "amp_sam_reads")
-        return rd
-
     def batch(self):
         """The batch of the last parse as a host ReadBatch (src_index = the rows' records)."""
-        n, nc, nb = int(self.info.n_rows), int(self.info.n_cig), int(self.info.n_bases_padded)
-        a = dict(pos=np.zeros(n, np.int32), flag=np.zeros(n, np.uint16), tlen=np.zeros(n, np.int32), lseq=np.zeros(n, np.uint32),
-                 cig_off=np.zeros(n + 1, np.uint64), cig=np.zeros(nc, np.uint32), seq_off=np.zeros(n + 1, np.uint64),
-                 seq=np.zeros(nb // 2, np.uint8), qual=np.zeros(nb, np.uint8))
-        src = np.zeros(n, np.int64)
-        st = abi.AmpReads(n, *[abi.ptr(a[k]) for k in ("pos", "flag", "tlen", "lseq", "cig_off", "cig", "seq_off", "seq", "qual")])
-        self._chk(self.L.amp_sam_batch_to_host(self.h, C.byref(st), C.c_void_p(abi.ptr(src))), "amp_sam_batch_to_host")
-        return ReadBatch(a["pos"], a["flag"], a["tlen"], a["lseq"], a["cig_off"], a["cig"], a["seq_off"], a["seq"], a["qual"], src_index=src)
-
-    def process(self, read_base=0):
-        """amp_sam_process: (first row with a non-zero status or -1, that status)."""
-        bad = C.c_int64(-1); st = C.c_uint8(0)
-        self._chk(self.L.amp_sam_process(self.h, C.c_uint64(read_base), C.byref(bad), C.byref(st)), "amp_sam_process")
-        return int(bad.value), int(st.value)
+        return super().batch(slack=0)[0]
 
     def twin_set_results(self, res):
         """(twin) the results the format stage works from: an abi.TrimResult-like of this batch's rows."""
@@ -150,11 +92,6 @@ class SamCodec:
             self._out = np.zeros(int(nb.value) + (int(nb.value) >> 2) + 4096, np.uint8)
         self._chk(rc, "amp_sam_format")
         return self._out[:int(nb.value)].tobytes(), int(nr.value)
-
-    def stage_ms(self, on=True, read=True):
-        ms = (C.c_float * N_STAGES)(*([-1.0] * N_STAGES))
-        self._chk(self.L.amp_sam_stage_ms(self.h, C.c_int(1 if on else 0), ms if read else None), "amp_sam_stage_ms")
-        return [float(x) for x in ms]
 
 
 # ---- the run's input -----------------------------------------------------------------------------------------------------------
@@ -207,23 +144,7 @@ class SamTextInput:
             yield buf + b"\n"
 
     def __iter__(self):
-        q = queue.Queue(maxsize=1)
-
-        def run():
-            try:
-                for c in self._chunks():
-                    q.put(c)
-                q.put(None)
-            except Exception as e:          # surfaced by the consumer
-                q.put(e)
-        threading.Thread(target=run, daemon=True).start()
-        while True:
-            c = q.get()
-            if c is None:
-                return
-            if isinstance(c, Exception):
-                raise c
-            yield c
+        return devcodec.read_ahead(self._chunks())
 
     def close(self):
         if self._f is not sys.stdin.buffer:
