@@ -252,6 +252,20 @@ def open_device_bam(input_fn):
     return input_fn
 
 
+def open_device_bam_write(input_fn, output_fn):
+    """(bam_device.DeviceBamInput, bam_device.DeviceBamOutput) when the device codec can serve a run that writes trimmed reads
+    (DESIGN.md section 12): an existing BAM file in and a new BAM file out, the conditions under which open_native_bam opens a
+    writer.  None otherwise: the host codec serves the run as before."""
+    if open_device_bam(input_fn) is None:
+        return None
+    if output_fn is None or output_fn.lower() == "stdout" or isfile(output_fn) or _reads_mode(output_fn, True) != "wb":
+        return None
+    from . import bam_device
+    src = bam_device.DeviceBamInput(input_fn)
+    hdr = bamio.Header(src.header_text, src.references).with_amplipy_pg(VERSION, " ".join(sys.argv))
+    return src, bam_device.DeviceBamOutput(output_fn, hdr.text, src.references, level=int(os.environ.get("AMPLIPY_BAM_LEVEL", "-1")))
+
+
 def open_native_sam(input_fn, output_fn):
     """(SamTextInput, Header, AlignmentWriter or None, binary output or None, device_ok) when the device codec for SAM text can serve
     this run (sam_native): stdin or an existing .sam file in, and stdout, a new .sam file or nothing out.
@@ -360,13 +374,15 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 consensus_fn=None, primer_pos_offset=None, min_length=None, min_quality=None, sliding_window_width=None,
                 min_freq_consensus=None, min_freq_variants=None, min_depth_consensus=None, min_depth_variants=None,
                 unknown_symbol=None, include_no_primer=None, run_trim=False, run_variants=False, run_consensus=False,
-                device=None, gpu_sam=None, gpu_bam=None):
+                device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
     sam_native instead of the Python codec; one process only.
     gpu_bam (default: AMPLIPY_GPU_BAM, off): a BAM file in and no trimmed reads out (variants, consensus) is inflated, indexed and
-    decoded on the device (bam_device) instead of by libampbam; one process only.  Runs that write trimmed reads keep libampbam.
+    decoded on the device (bam_device) instead of by libampbam; one process only.  Runs that write trimmed reads keep libampbam,
+    unless gpu_bam_write (default: AMPLIPY_GPU_BAM_WRITE, off) is on as well: a BAM file in and a new BAM file of trimmed reads out
+    (trim, aio) then stay on the device codec, which re-encodes, compresses and frames the kept records too.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -432,20 +448,25 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    native = reader = writer = vcf = sam = bamdev = None
+    native = reader = writer = vcf = sam = bamdev = bamdev_io = None
     rank_error = None
     use_sam = dist is None and gpu_sam_wanted(gpu_sam)
     use_bam = dist is None and gpu_bam_wanted(gpu_bam)
+    use_bam_write = use_bam and gpu_codec_wanted(gpu_bam_write, "AMPLIPY_GPU_BAM_WRITE")
     try:
         if run_trim:
             print_log("Input untrimmed SAM/BAM: %s" % untrimmed_reads_fn)
             print_log("Output trimmed SAM/BAM: %s" % trimmed_reads_fn)
-            native = open_native_bam(untrimmed_reads_fn, trimmed_reads_fn, rank, world, device)
+            if use_bam_write:
+                bamdev_io = open_device_bam_write(untrimmed_reads_fn, trimmed_reads_fn)
+                bamdev = untrimmed_reads_fn if bamdev_io is not None else None
+            if bamdev is None:
+                native = open_native_bam(untrimmed_reads_fn, trimmed_reads_fn, rank, world, device)
             if native is not None and use_bam:
                 print_log("BAM device codec: this run writes trimmed reads, the host codec reads the input")
-            if native is None and use_sam:
+            if native is None and bamdev is None and use_sam:
                 sam = open_native_sam(untrimmed_reads_fn, trimmed_reads_fn)
-            if native is None and sam is None:
+            if native is None and sam is None and bamdev is None:
                 reader, writer = open_alignment_files(untrimmed_reads_fn, trimmed_reads_fn)
         else:
             print_log("Input trimmed SAM/BAM: %s" % trimmed_reads_fn)
@@ -615,22 +636,49 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 nwriter.close()
         seam = getattr(src, "seam", [None, None])
     elif bamdev is not None:
-        # BAM in, no trimmed reads out, with the switch on: the compressed bytes of a piece of whole BGZF blocks go to the device,
-        # which inflates them, checks every block's CRC, indexes the records and decodes the rows into the packed batch
-        # (bam_device; the next piece is read and copied up while this one is there).  The read pass runs on that batch.
+        # BAM in with the switch on: the compressed bytes of a piece of whole BGZF blocks go to the device, which inflates them,
+        # checks every block's CRC, indexes the records and decodes the rows into the packed batch (bam_device; the next piece
+        # is read and copied up while this one is there).  The read pass runs on that batch.  A run that writes trimmed reads
+        # (both switches on) has the kept records of every piece re-encoded, compressed and framed there as well: the BGZF
+        # blocks of the trimmed BAM are all that comes back.
         from . import bam_device
         stats = bam_device.LAST_RUN_STATS
         stats.update(pieces=0, blocks_device=0, blocks_host=0, index_rounds=0, waits=0, records=0, bytes_up=0, bytes_file=0)
+        stats.update((k_, 0) for k_ in bam_device.OUT_STATS)
         refuse = os.environ.get("AMPLIPY_GPU_BAM_REFUSE_BLOCK") if os.environ.get("AMPLIPY_DEV") == "1" else None
         codec = None
+        out = None
+        running = None
+        emit = None
+        flushed = False
+        if bamdev_io is not None:
+            src, out = bamdev_io
+
+            def emit():
+                # ampbam_write_rows of the host path: the rows in front of a failing one are written (A:907-911), and whole blocks
+                # only -- the rest of the stream is flushed with the last piece, unless the run ends on a failing row (the host
+                # writer is not closed then either)
+                nonlocal flushed
+                flushed = running["pieces"] == len(src.pieces) and codec.first_bad < 0
+                out.encode(codec, running, min_length, include_no_primer, final=flushed)
         try:
-            src = bam_device.DeviceBamInput(bamdev)
+            if out is None:
+                src = bam_device.DeviceBamInput(bamdev)
             codec = bam_device.BamCodec(eng)
             for info, running in bam_device.walk(codec, src, refuse_block=int(refuse) if refuse else None):
-                stats.update(running)
-                device_piece(codec, info)
+                try:
+                    device_piece(codec, info, emit)
+                finally:
+                    stats.update(running)
+            if out is not None:
+                # header blocks and end-of-file block are the host codec's (a last piece without rows: the bare flush)
+                if not flushed:
+                    out.encode(codec, stats, min_length, include_no_primer, final=True)
+                out.close()
             print_log("BAM device codec: %d pieces, %d blocks on the device, %d through the host codec, %d index rounds"
-                      % (stats["pieces"], stats["blocks_device"], stats["blocks_host"], stats["index_rounds"]))
+                      % (stats["pieces"], stats["blocks_device"], stats["blocks_host"], stats["index_rounds"])
+                      + ("" if out is None else "; trimmed reads: %d blocks on the device, %d through the host codec, %d bytes down"
+                         % (stats["out_blocks_device"], stats["out_blocks_host"], stats["bytes_down"])))
         finally:
             if codec is not None:
                 codec.close()

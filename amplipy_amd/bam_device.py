@@ -1,7 +1,9 @@
-"""BAM input through the device codec of libamplihip.so (amp_bam_*, amplipy_amd/csrc/amp_bgzf.hip).
+"""BAM input through the device codec of libamplihip.so (amp_bam_*, amplipy_amd/csrc/amp_bgzf.hip), and
+trimmed BAM output from it (amp_bam_encode, amplipy_amd/csrc/amp_bamout.hip; section 12).
 
 Opt-in (AMPLIPY_GPU_BAM=1 or run_amplipy(gpu_bam=True)), for single-process runs that read an existing BAM file and write no
-trimmed reads: the file is walked in pieces of whole BGZF blocks, the COMPRESSED bytes of a piece and its block table go to
+trimmed reads -- or, with AMPLIPY_GPU_BAM_WRITE=1 / gpu_bam_write=True as well, a new trimmed BAM file, whose records are
+re-encoded, compressed and framed on the device too: the file is walked in pieces of whole BGZF blocks, the COMPRESSED bytes of a piece and its block table go to
 the device, and inflate, CRC check, record index and decode into the packed batch all happen there; the read pass runs on
 the batch where it lies.  A block the device refuses is inflated here (zlib), checked and patched in, and counted.
 
@@ -26,12 +28,16 @@ from . import abi, bam_native, devcodec
 PIECE_BYTES = 16 << 20
 IMAGE_LIMIT = 256 << 20            # AMP_BAM_IMAGE_LIMIT of amplihip.h
 PIECE_ISIZE_LIMIT = 120 << 20      # ISIZE sum of a piece: with a carry of at most one record (2^27 + 4 bytes) the image fits
-N_STAGES = 7
+N_STAGES = 12                      # AMP_BAM_N_STAGES
+OUT_BS = 0xFF00                    # uncompressed bytes of a BGZF block of the trimmed output (the host writer's)
 FORMAT_ERROR = -3                  # AMPBAM_EFORMAT
 
 # the last run of run_amplipy that took this path
 LAST_RUN_STATS = {"pieces": 0, "blocks_device": 0, "blocks_host": 0, "index_rounds": 0, "waits": 0, "records": 0,
-                  "bytes_up": 0, "bytes_file": 0}
+                  "bytes_up": 0, "bytes_file": 0,
+                  # a run that writes trimmed reads through amp_bam_encode (section 12)
+                  "out_blocks_device": 0, "out_blocks_host": 0, "out_rows": 0, "bytes_down": 0, "bytes_out_file": 0}
+OUT_STATS = ("out_blocks_device", "out_blocks_host", "out_rows", "bytes_down", "bytes_out_file")
 
 
 class AmpBamBlock(C.Structure):
@@ -44,9 +50,27 @@ class AmpBamInfo(C.Structure):
                                          "bytes_up")] + [("bad_record", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AmpBamOutInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_rows_written", "stream_bytes", "carry_in", "carry_out", "n_blocks", "file_bytes", "n_blocks_host",
+                                         "waits", "bytes_down")]
+
+
+# amp_bam_twin_deflate_fn of amp_bamout.hpp
+TWIN_DEFLATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_uint32))
+
+
 def twin_sources():
+    """amp_bgzf.hip (which includes amp_bamout.hip, the re-encoder's lanes and driver) and the lane functions' headers."""
     here = os.path.dirname(os.path.abspath(__file__))
-    return os.path.join(here, "csrc", "amp_bgzf.hip"), os.path.join(here, "csrc", "amp_bgzf.hpp")
+    return tuple(os.path.join(here, "csrc", f) for f in ("amp_bgzf.hip", "amp_bgzf.hpp", "amp_bamout.hip", "amp_bamout.hpp"))
+
+
+def bgzf_block(data, level=6):
+    """One BGZF block of ``data`` (at most 0xFF00 bytes) made on the host: zlib's stream, the framing of flush_blocks."""
+    co = zlib.compressobj(level, zlib.DEFLATED, -15)
+    comp = co.compress(data) + co.flush()
+    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(comp) + 25) + comp
+            + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
 
 
 def build_twin(out_path, sanitize=False, main_source=None):
@@ -197,6 +221,58 @@ class BamCodec(devcodec.DeviceCodec):
         rb, tails = super().batch(slack=16)
         return (rb, tails) if slack else rb
 
+    def set_trim(self, res, first_bad=-1):
+        """Twin only (it has no read pass): the results of the last feed's rows -- new_pos, new_ncig, new_cig (row r's words at
+        cig_off[r] + 3 r), ref_len, trim_flags as a lib.TrimResult holds them -- for the encode that follows."""
+        self._trim = [np.ascontiguousarray(a, t) for a, t in ((res.new_pos, np.int32), (res.new_ncig, np.uint32), (res.new_cig, np.uint32),
+                                                              (res.ref_len, np.int32), (res.trim_flags, np.uint8))]
+        self._chk(self.L.amp_bam_twin_set_trim(self.h, *[C.c_void_p(abi.ptr(a)) for a in self._trim], C.c_int64(first_bad)), "amp_bam_twin_set_trim")
+
+    def set_deflater(self, fn):
+        """Twin only: the DEFLATE encoder of its encodes -- the address of ampdf_hostsim_blocks (amp_deflate.hip's host phases), or a
+        TWIN_DEFLATE_FN object."""
+        self._deflater = fn
+        self._chk(self.L.amp_bam_twin_set_deflater(self.h, fn), "amp_bam_twin_set_deflater")
+
+    def guards_ok(self):
+        """Twin only: no encode so far wrote behind one of its buffers."""
+        return int(self.L.amp_bam_twin_guards(self.h)) == 0
+
+    def encode(self, min_length, include_no_primer, final=False):
+        """amp_bam_encode + amp_bam_encoded_to_host: (the BGZF blocks of this call as they go into the file, info).  The kept rows
+        of the last feed (A:910), behind what the call before left over; final: the last partial block too.  A block whose
+        stream did not fit comes down raw and is compressed here (info.n_blocks_host counts it; never on real data)."""
+        info = AmpBamOutInfo()
+        rc = self.L.amp_bam_encode(self.h, C.c_int32(int(min_length)), C.c_int32(1 if include_no_primer else 0), C.c_int32(1 if final else 0), C.byref(info))
+        if rc == -1:
+            raise bam_native.AmpBamError("write: %s" % bam_native.load().ampbam_strerror(-1).decode())      # (what ampbam_write_rows answers)
+        self._chk(rc, "amp_bam_encode")
+        self.out_info = info
+        out = np.empty(max(int(info.file_bytes), 1), np.uint8)
+        if info.file_bytes:
+            self._chk(self.L.amp_bam_encoded_to_host(self.h, C.c_void_p(abi.ptr(out)), C.c_int64(out.size)), "amp_bam_encoded_to_host")
+        out = out[:int(info.file_bytes)]
+        if info.n_blocks_host:
+            lens = np.zeros(int(info.n_blocks), np.uint32)
+            self._chk(self.L.amp_bam_encoded_blocks(self.h, C.c_void_p(abi.ptr(lens)), C.c_int64(lens.size)), "amp_bam_encoded_blocks")
+            enc = int(info.stream_bytes) - int(info.carry_out)
+            parts, at = [], 0
+            for k, n in enumerate(int(x) for x in lens):
+                if n:
+                    parts.append(out[at:at + n].tobytes()); at += n
+                else:
+                    parts.append(bgzf_block(self.stream(k * OUT_BS, min(OUT_BS, enc - k * OUT_BS)).tobytes()))
+                    info.bytes_down += min(OUT_BS, enc - k * OUT_BS)
+            out = np.frombuffer(b"".join(parts), np.uint8)
+        return out, info
+
+    def stream(self, start=0, n=None):
+        """Bytes [start, start + n) of the uncompressed stream [carry | new records] of the last encode (n None: to its end)."""
+        n = int(self.out_info.stream_bytes) - start if n is None else n
+        buf = np.zeros(max(n, 1), np.uint8)
+        self._chk(self.L.amp_bam_stream_to_host(self.h, C.c_int64(start), C.c_int64(n), C.c_void_p(abi.ptr(buf))), "amp_bam_stream_to_host")
+        return buf[:n]
+
     def image(self):
         """(the image of the last feed, the offsets of its records in it)."""
         img = np.zeros(max(int(self.info.image_bytes), 1), np.uint8)
@@ -242,6 +318,7 @@ def walk(codec, src, refuse_block=None):
     stats = the running totals (the keys of LAST_RUN_STATS).  refuse_block: development only -- that block of the file is
     treated as refused."""
     stats = dict(pieces=0, blocks_device=0, blocks_host=0, index_rounds=0, waits=0, records=0, bytes_up=0, bytes_file=src.file_bytes)
+    stats.update((k, 0) for k in OUT_STATS)
     n_ref = len(src.references)
     first = src.first_record
     for comp, tab, k_lo, last in src:
@@ -267,3 +344,27 @@ def walk(codec, src, refuse_block=None):
         stats["waits"] += int(info.waits)
         stats["records"] += int(info.n_records)
         yield info, stats
+
+
+class DeviceBamOutput:
+    """The trimmed BAM of a run whose reads an amp_bam holds (section 12): header blocks and end-of-file block from the host codec
+    (bam_native.BamWriter on the header alone), everything between them from ``codec.encode``.  ``stats``: the running totals of
+    ``walk``, whose output keys and waits are counted up here."""
+
+    def __init__(self, path, header_text, references, level=-1):
+        self.writer = bam_native.BamWriter(path, header_text, None, level=level, references=references)
+        self.path = path
+
+    def encode(self, codec, stats, min_length, include_no_primer, final=False):
+        blocks, info = codec.encode(min_length, include_no_primer, final)
+        self.writer.append_framed(blocks)
+        stats["out_blocks_device"] += int(info.n_blocks) - int(info.n_blocks_host)
+        stats["out_blocks_host"] += int(info.n_blocks_host)
+        stats["out_rows"] += int(info.n_rows_written)
+        stats["bytes_down"] += int(info.bytes_down)
+        stats["bytes_out_file"] += int(blocks.size)
+        stats["waits"] += int(info.waits)
+        return info
+
+    def close(self):
+        self.writer.close()

@@ -17,6 +17,7 @@ EXPORTS = [
     "ampbam_header_text", "ampbam_n_refs", "ampbam_ref", "ampbam_decode", "ampbam_writer_open", "ampbam_write_rows",
     "ampbam_writer_close", "ampbam_writer_header_bytes", "ampbam_write_batch", "ampbam_open_range", "ampbam_open_range_at", "ampbam_part_range", "ampbam_crc32", "ampbam_inflate_raw",
     "ampbam_writer_set_deflater", "ampbam_writer_deflater_stats", "ampbam_block_table",
+    "ampbam_writer_open_refs", "ampbam_writer_append_framed",
 ]
 # ampbam_deflate_fn of include/ampbam.h
 DEFLATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_uint32))
@@ -53,6 +54,7 @@ def load():
         L.ampbam_close.argtypes = [C.c_void_p]
         L.ampbam_writer_set_deflater.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ampbam_writer_deflater_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ampbam_writer_append_framed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         _LIB = L
     return _LIB
 
@@ -134,8 +136,10 @@ class BamFile:
 class BamWriter:
     """Writes rows of decoded batches of ``src`` with new positions / CIGARs (AmpliPy.py:911)."""
 
-    def __init__(self, path, header_text, src, level=-1, threads=0, gpu_deflate=False, device=0):
-        """gpu_deflate: the blocks' DEFLATE streams come from the HIP encoder of libamplihip on ``device`` (amp_deflate_blocks; the
+    def __init__(self, path, header_text, src, level=-1, threads=0, gpu_deflate=False, device=0, references=None):
+        """src None: the reference dictionary is ``references`` = [(name, length)] (ampbam_writer_open_refs: a caller that has no
+        BamFile of the input, the device codec of bam_device); write_rows then needs its ``src`` argument.
+        gpu_deflate: the blocks' DEFLATE streams come from the HIP encoder of libamplihip on ``device`` (amp_deflate_blocks; the
         header's blocks, and any block the device hands back, from the host codec at ``level``).  The library must load and the
         device must be there: asking for it without one is an error, not a silent host run."""
         self.L = load()
@@ -143,7 +147,14 @@ class BamWriter:
         self._deflater = None
         h = C.c_void_p()
         text = header_text.encode("ascii")
-        rc = self.L.ampbam_writer_open(os.fsencode(path), text, C.c_int64(len(text)), src.h, C.c_int(level), C.c_int(threads), C.byref(h))
+        if src is not None:
+            rc = self.L.ampbam_writer_open(os.fsencode(path), text, C.c_int64(len(text)), src.h, C.c_int(level), C.c_int(threads), C.byref(h))
+        else:
+            refs = list(references or [])
+            names = (C.c_char_p * max(len(refs), 1))(*[n.encode("ascii") for n, _ in refs])
+            lens = (C.c_int32 * max(len(refs), 1))(*[int(ln) for _, ln in refs])
+            rc = self.L.ampbam_writer_open_refs(os.fsencode(path), text, C.c_int64(len(text)), C.c_int32(len(refs)), names, lens,
+                                                C.c_int(level), C.c_int(threads), C.byref(h))
         if rc:
             raise AmpBamError("%s: %s" % (path, self.L.ampbam_strerror(rc).decode()))
         self.h = h
@@ -186,6 +197,14 @@ class BamWriter:
                                       C.c_void_p(new_cig.ctypes.data))
         if rc:
             raise AmpBamError("write: %s" % self.L.ampbam_strerror(rc).decode())
+
+    def append_framed(self, blocks):
+        """ampbam_writer_append_framed: complete BGZF blocks made elsewhere (bytes or a numpy uint8 array) go into the file as they
+        are.  Only while nothing of write_rows / write_batch is pending."""
+        buf = np.frombuffer(blocks, np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blocks, np.uint8)
+        rc = self.L.ampbam_writer_append_framed(self.h, C.c_void_p(buf.ctypes.data if buf.size else None), C.c_int64(buf.size))
+        if rc:
+            raise AmpBamError("append: %s" % self.L.ampbam_strerror(rc).decode())
 
     def write_batch(self, b, name_base=0):
         """The rows of a packed ReadBatch as NEW records named r<name_base + row> (ampbam_write_batch: files made from synthetic

@@ -10,15 +10,17 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # translation units of libamplihip.so: the kernels + C ABI, and the insertion-event aggregation (its sort headers triple the
 # compile time of whatever includes them, so it is built -- and cached -- on its own), the DEFLATE encoder of the BAM writer, and
-# the codecs for SAM text and for BAM input
+# the codecs for SAM text and for BAM (input, and trimmed records out)
 UNITS = ["amplihip.hip", "amp_ins.hip", "amp_deflate.hip", "amp_sam.hip", "amp_bgzf.hip"]
 SRC = os.path.join(CSRC, "amplihip.hip")
 HEADERS = [os.path.join(_HERE, "..", "include", "amplihip.h")] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
 UNIT_DEPS = {"amplihip.hip": HEADERS, "amp_ins.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_ins.hpp")],
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
              "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_codec.hpp")],
-             "amp_bgzf.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_codec.hpp"), os.path.join(CSRC, "amp_bgzf.hpp")]}
-DEPS = [os.path.join(CSRC, u) for u in UNITS] + HEADERS
+             # (amp_bamout.hip, the re-encoder of trimmed records, is part of amp_bgzf.hip's unit: it is included there)
+             "amp_bgzf.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in
+                              ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamout.hip")]}
+DEPS = [os.path.join(CSRC, u) for u in UNITS] + [os.path.join(CSRC, "amp_bamout.hip")] + HEADERS
 OUT = os.path.join(_HERE, "libamplihip.so")
 OBJ_DIR = os.path.join(_HERE, "build")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function"]

@@ -24,11 +24,13 @@
 // The lane functions compile for the host as well (-DAMPBGZF_HOSTSIM: any C++ compiler, sanitizers included) and a driver runs
 // them lane after lane: the twin the CPU tests check against libampbam.
 // What surrounds the stages -- stream, copies, scan, events, the batch's way into the read pass -- is the shell of amp_codec.hpp.
+#include <utility>
 #include <vector>
 
 #include "amp_codec.hpp"
 #define BGZ_HD AMP_HD
 #include "amp_bgzf.hpp"
+#include "amp_bamout.hpp"
 
 namespace ampbgzf {
 
@@ -53,6 +55,7 @@ struct Buf : BufIndex, ampcodec::Batch {
     uint32_t *row_seq;
     unsigned long long *ctl;
     uint64_t spare;            // (the kernels' other arguments stay where they were when a pointer lay here)
+    ampbamout::Out o;          // the re-encoder of trimmed records (amp_bamout.hip)
 };
 
 // ---- inflate / crc: one wave per block ----------------------------------------------------------------------------------------
@@ -284,6 +287,19 @@ struct amp_bam {
     bool fed = false;
     int64_t refused_left = 0, force_refuse = -1;
     unsigned long long h_ctl[CTL_WORDS];
+    // the re-encoder of trimmed records (amp_bamout.hip)
+    bool processed = false, encoded = false, out_ok = false;      // of the last feed: results are there; its rows were encoded
+    int64_t good_rows = 0;                            // rows in front of the first failing one
+    uint8_t *oarena = nullptr, *ocarry = nullptr;
+    size_t cap_oarena = 0, cap_ocarry = 0;
+    int64_t oarena_rows = 0, oarena_stream = 0, oarena_blocks = 0;
+    int64_t ocarry_len = 0;                           // bytes of the record stream behind its last whole 0xFF00-byte chunk, kept in `ocarry`
+    amp_bam_out_info oinfo{};
+    unsigned long long h_octl[ampbamout::OCTL_WORDS];
+#ifdef AMPBGZF_HOSTSIM
+    amp_bam_twin_deflate_fn twin_deflate = nullptr;
+    std::vector<std::pair<uint8_t *, size_t>> guards;     // the bytes behind the encoder's buffers, which nothing may write
+#endif
 };
 
 #ifndef AMPBGZF_HOSTSIM
@@ -422,7 +438,7 @@ void amp_bam_destroy(amp_bam *s) {
     if (!s) return;
     DevGuard guard(s->sh);
     (void)codec_wait(s->sh);
-    codec_free(s->arena); codec_free(s->img); codec_free(s->comp); codec_free(s->carry);
+    codec_free(s->arena); codec_free(s->img); codec_free(s->comp); codec_free(s->carry); codec_free(s->oarena); codec_free(s->ocarry);
     codec_delete(s);
 }
 
@@ -431,7 +447,7 @@ int amp_bam_feed(amp_bam *s, const uint8_t *comp, int64_t n_comp, const amp_bam_
                  int32_t n_ref, int64_t rec_base, amp_bam_info *info) {
     if (!s || !info || n_comp < 0 || n_blocks < 0 || (n_comp && !comp) || (n_blocks && !blocks) || n_ref < 0 || n_comp >= (1ll << 31)) return AMP_EINVAL;
     DevGuard guard(s->sh);
-    s->fed = false;
+    s->fed = s->processed = s->encoded = false;
     const int64_t waits0 = s->sh.waits;
     int64_t isize = 0;
     try { s->h_blocks.resize((size_t)n_blocks); s->h_verdict.assign((size_t)n_blocks, 0); } catch (const std::bad_alloc &) { return AMP_ENOMEM; }
@@ -550,11 +566,18 @@ int amp_bam_image_to_host(amp_bam *s, uint8_t *image, int64_t image_cap, uint32_
 int amp_bam_process(amp_bam *s, uint64_t read_base, int64_t *first_bad_row, uint8_t *its_status) {
     if (!s) return AMP_EINVAL;
     if (!s->fed || s->info.n_refused || s->info.bad_record) return AMP_ESTATE;
-    return codec_process(s->sh, s->b, s->trim, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded, read_base, 6, first_bad_row, its_status);
+    int64_t bad = -1;
+    CODEC_OK(codec_process(s->sh, s->b, s->trim, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded, read_base, 6, &bad, its_status));
+    s->good_rows = bad >= 0 ? bad : s->info.n_rows;
+    s->processed = true;
+    if (first_bad_row) *first_bad_row = bad;
+    return AMP_OK;
 }
 
-// milliseconds of the stages of the last feed / process on the ctx stream (HIP events); on != 0 switches the events on
+// milliseconds of the stages of the last feed / process / encode on the ctx stream (HIP events); on != 0 switches the events on
 int amp_bam_stage_ms(amp_bam *s, int on, float *ms) { return s ? codec_stage_ms(s->sh, on, ms) : AMP_EINVAL; }
 #endif
 
 }  // extern "C"
+
+#include "amp_bamout.hip"

@@ -86,6 +86,7 @@ struct Args {
     int32_t room;
     uint32_t *out_len;
     uint32_t *tokens;                                 // [gridDim.x][TOK_MAX][THREADS]
+    const unsigned long long *n_dev;                  // not NULL: n_bytes is read from here by the kernel (at most the n_bytes above)
 };
 
 #define AMPDF_FN __host__ __device__ static inline
@@ -529,6 +530,11 @@ __device__ static inline void run_phases(Shared &sh, const Args &a, int64_t blk)
 
 __global__ __launch_bounds__(THREADS) void k_deflate(Args a, int64_t n_blocks) {
     __shared__ Shared sh;
+    if (a.n_dev) {                                        // a byte count that only the device knows: the launch was sized for the most it can be
+        const int64_t n = (int64_t)*a.n_dev;
+        if (n < a.n_bytes) a.n_bytes = n;
+        n_blocks = (a.n_bytes + a.block_bytes - 1) / a.block_bytes;
+    }
     for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) run_phases<0>(sh, a, blk);
 }
 
@@ -628,13 +634,13 @@ static int ensure_tokens(DevState &st, int grid) {
 }
 
 static int launch(DevState &st, const uint8_t *d_in, int64_t n_bytes, int32_t block_bytes, uint8_t *d_out, int64_t stride, int32_t room,
-                  uint32_t *d_len, hipStream_t s) {
+                  uint32_t *d_len, hipStream_t s, const unsigned long long *n_dev = nullptr) {
     const int64_t nb = (n_bytes + block_bytes - 1) / block_bytes;
     if (nb == 0) return AMP_OK;
     const int grid = grid_for(st, nb);
     const int rc = ensure_tokens(st, grid);
     if (rc) return rc;
-    Args a{d_in, n_bytes, block_bytes, d_out, stride, room, d_len, st.d_tokens};
+    Args a{d_in, n_bytes, block_bytes, d_out, stride, room, d_len, st.d_tokens, n_dev};
     // launches share the token scratch: each waits for the one before it, on whatever stream that was
     if (st.tokens_used && hipStreamWaitEvent(s, st.tokens_free, 0) != hipSuccess) return AMP_EHIP;
     hipLaunchKernelGGL(k_deflate, dim3((unsigned)grid), dim3(THREADS), 0, s, a, nb);
@@ -676,8 +682,8 @@ static int init_state(DevState &st, int device) {
 
 extern "C" {
 
-int amp_deflate_blocks_device(int device, const uint8_t *d_in, int64_t n_bytes, int32_t block_bytes, uint8_t *d_out, int64_t out_stride,
-                              int32_t out_room, uint32_t *d_out_len, void *stream) {
+static int deflate_device(int device, const uint8_t *d_in, int64_t n_bytes, const unsigned long long *n_dev, int32_t block_bytes, uint8_t *d_out,
+                          int64_t out_stride, int32_t out_room, uint32_t *d_out_len, void *stream) {
     using namespace ampdf;
     if (n_bytes < 0 || block_bytes < 1 || block_bytes > BS_MAX || out_room < 0 || out_stride < out_room) return AMP_EINVAL;
     if (n_bytes == 0) return AMP_OK;
@@ -690,7 +696,18 @@ int amp_deflate_blocks_device(int device, const uint8_t *d_in, int64_t n_bytes, 
     if (!scope.ok) return AMP_EHIP;
     rc = init_state(*st, device);
     if (rc) return rc;
-    return launch(*st, d_in, n_bytes, block_bytes, d_out, out_stride, out_room, d_out_len, stream ? (hipStream_t)stream : st->stream);
+    return launch(*st, d_in, n_bytes, block_bytes, d_out, out_stride, out_room, d_out_len, stream ? (hipStream_t)stream : st->stream, n_dev);
+}
+
+int amp_deflate_blocks_device(int device, const uint8_t *d_in, int64_t n_bytes, int32_t block_bytes, uint8_t *d_out, int64_t out_stride,
+                              int32_t out_room, uint32_t *d_out_len, void *stream) {
+    return deflate_device(device, d_in, n_bytes, nullptr, block_bytes, d_out, out_stride, out_room, d_out_len, stream);
+}
+
+int amp_deflate_blocks_device_counted(int device, const uint8_t *d_in, const uint64_t *d_n_bytes, int64_t max_bytes, int32_t block_bytes,
+                                      uint8_t *d_out, int64_t out_stride, int32_t out_room, uint32_t *d_out_len, void *stream) {
+    if (!d_n_bytes) return AMP_EINVAL;
+    return deflate_device(device, d_in, max_bytes, (const unsigned long long *)d_n_bytes, block_bytes, d_out, out_stride, out_room, d_out_len, stream);
 }
 
 int amp_deflate_sync(int device) {

@@ -908,7 +908,20 @@ static int flush_blocks(ampbam_writer *w, bool all) {
 
 int ampbam_writer_open(const char *path, const char *header_text, int64_t header_len, const ampbam_file *like,
                        int level, int n_threads, ampbam_writer **out) {
-    if (!path || !out || header_len < 0 || (header_len && !header_text) || !like || level < -1 || level > 9) return AMPBAM_EINVAL;
+    if (!like) return AMPBAM_EINVAL;
+    std::vector<const char *> names;
+    std::vector<int32_t> lens;
+    try {
+        for (size_t r = 0; r < like->ref_names.size(); ++r) { names.push_back(like->ref_names[r].c_str()); lens.push_back((int32_t)like->ref_lens[r]); }
+    } catch (const std::bad_alloc &) { return AMPBAM_ENOMEM; }
+    return ampbam_writer_open_refs(path, header_text, header_len, (int32_t)names.size(), names.data(), lens.data(), level, n_threads, out);
+}
+
+int ampbam_writer_open_refs(const char *path, const char *header_text, int64_t header_len, int32_t n_ref, const char *const *ref_names,
+                            const int32_t *ref_lens, int level, int n_threads, ampbam_writer **out) {
+    if (!path || !out || header_len < 0 || (header_len && !header_text) || n_ref < 0 || (n_ref && (!ref_names || !ref_lens)) || level < -1 || level > 9)
+        return AMPBAM_EINVAL;
+    for (int32_t r = 0; r < n_ref; ++r) if (!ref_names[r]) return AMPBAM_EINVAL;
     *out = nullptr;
     ampbam_writer *w = new (std::nothrow) ampbam_writer();
     if (!w) return AMPBAM_ENOMEM;
@@ -920,12 +933,12 @@ int ampbam_writer_open(const char *path, const char *header_text, int64_t header
     bool okm = append(b, "BAM\1", 4);
     put32(t, (uint32_t)header_len); okm = okm && append(b, t, 4);
     okm = okm && append(b, header_text, (size_t)header_len);
-    put32(t, (uint32_t)like->ref_names.size()); okm = okm && append(b, t, 4);
-    for (size_t r = 0; okm && r < like->ref_names.size(); ++r) {
-        const std::string &nm = like->ref_names[r];
-        put32(t, (uint32_t)nm.size() + 1); okm = okm && append(b, t, 4);
-        okm = okm && append(b, nm.c_str(), nm.size() + 1);
-        put32(t, (uint32_t)like->ref_lens[r]); okm = okm && append(b, t, 4);
+    put32(t, (uint32_t)n_ref); okm = okm && append(b, t, 4);
+    for (int32_t r = 0; okm && r < n_ref; ++r) {
+        const size_t ln = std::strlen(ref_names[r]);
+        put32(t, (uint32_t)ln + 1); okm = okm && append(b, t, 4);
+        okm = okm && append(b, ref_names[r], ln + 1);
+        put32(t, (uint32_t)ref_lens[r]); okm = okm && append(b, t, 4);
     }
     if (!okm) { std::fclose(w->fp); delete w; return AMPBAM_ENOMEM; }
     // the header gets BGZF blocks of its own (htslib flushes behind it too): the files that the ranks of a multi-GPU run write can
@@ -938,6 +951,12 @@ int ampbam_writer_open(const char *path, const char *header_text, int64_t header
 }
 
 int64_t ampbam_writer_header_bytes(const ampbam_writer *w) { return w ? w->header_bytes : -1; }
+
+int ampbam_writer_append_framed(ampbam_writer *w, const void *blocks, int64_t n_bytes) {
+    if (!w || n_bytes < 0 || (n_bytes && !blocks) || w->pend.size() != 0) return AMPBAM_EINVAL;
+    if (n_bytes && std::fwrite(blocks, 1, (size_t)n_bytes, w->fp) != (size_t)n_bytes) return AMPBAM_EIO;
+    return AMPBAM_OK;
+}
 
 int ampbam_writer_set_deflater(ampbam_writer *w, ampbam_deflate_fn fn, void *user) {
     if (!w) return AMPBAM_EINVAL;

@@ -113,9 +113,10 @@ class DeviceCodec:
         return rb, tails
 
     def process(self, read_base=0):
-        """amp_*_process: (first row with a non-zero status or -1, that status)."""
+        """amp_*_process: (first row with a non-zero status or -1, that status); the row is kept in ``self.first_bad`` as well."""
         bad = C.c_int64(-1); st = C.c_uint8(0)
         self._chk(self._fn("process")(self.h, C.c_uint64(read_base), C.byref(bad), C.byref(st)), self.prefix + "_process")
+        self.first_bad = int(bad.value)
         return int(bad.value), int(st.value)
 
     def stage_ms(self, on=True, read=True):

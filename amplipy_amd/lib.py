@@ -28,11 +28,12 @@ EXPORTS = [
     "amp_reserve_events", "amp_set_kernel_variant", "amp_set_reference", "amp_call_positions",
     "amp_event_strings", "amp_debug_counters", "amp_call_compact", "amp_debug_blocks", "amp_call_compact_view", "amp_set_timing", "amp_call_compact_begin", "amp_coordinate_helpers", "amp_drain_ins_events", "amp_set_cu_share",
     "amp_aggregate_ins_events", "amp_fast_path_active", "amp_last_kernel_variant",
-    "amp_deflate_blocks", "amp_deflate_blocks_device", "amp_deflate_sync", "amp_deflate_blocks_cb",
+    "amp_deflate_blocks", "amp_deflate_blocks_device", "amp_deflate_blocks_device_counted", "amp_deflate_sync", "amp_deflate_blocks_cb",
     "amp_sam_create", "amp_sam_destroy", "amp_sam_set_references", "amp_sam_parse", "amp_sam_reads", "amp_sam_batch_to_host",
     "amp_sam_process", "amp_sam_format", "amp_sam_stage_ms",
     "amp_bam_create", "amp_bam_destroy", "amp_bam_feed", "amp_bam_dev_refuse", "amp_bam_refused", "amp_bam_patch_block", "amp_bam_reindex",
     "amp_bam_reads", "amp_bam_batch_to_host", "amp_bam_image_to_host", "amp_bam_process", "amp_bam_stage_ms",
+    "amp_bam_encode", "amp_bam_encoded_to_host", "amp_bam_encoded_blocks", "amp_bam_stream_to_host",
 ]
 
 

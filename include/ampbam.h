@@ -115,6 +115,15 @@ int ampbam_decode(ampbam_file *f, int64_t first, int64_t count, ampbam_batch *ou
  * (AmpliPy.py:343-346 copies the input's references).  level = zlib level 0..9 (-1: default). */
 int ampbam_writer_open(const char *path, const char *header_text, int64_t header_len, const ampbam_file *like,
                        int level, int n_threads, ampbam_writer **out);
+/* The same for a caller that has no ampbam_file of the input (one that inflates elsewhere: the device codec of
+ * include/amplihip.h): the reference dictionary as n_ref names (NUL-terminated) and lengths.  The file's bytes are those of
+ * ampbam_writer_open with a `like` of the same references. */
+int ampbam_writer_open_refs(const char *path, const char *header_text, int64_t header_len, int32_t n_ref, const char *const *ref_names,
+                            const int32_t *ref_lens, int level, int n_threads, ampbam_writer **out);
+/* Appends complete BGZF blocks made elsewhere (compressed, with header, CRC-32 and ISIZE) to the file as they are.  Valid only
+ * while the writer holds no pending bytes of its own -- right behind the open, or when every record has come this way --
+ * AMPBAM_EINVAL otherwise: blocks of the two sources would change places.  The end-of-file block stays ampbam_writer_close's. */
+int ampbam_writer_append_framed(ampbam_writer *w, const void *blocks, int64_t n_bytes);
 /* Appends rows of a decoded batch whose keep[i] != 0, re-encoded with a new position and CIGAR:
  * row i of the batch is record src_index[i] of `src`; its new CIGAR is new_ncig[i] words at
  * new_cig + new_cig_off[i].  block_size, bin (reg2bin of [pos, end)), n_cigar_op and pos change,

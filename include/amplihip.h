@@ -377,6 +377,10 @@ int amp_deflate_blocks(int device, const uint8_t *in, int64_t n_bytes, int32_t b
 int amp_deflate_blocks_device(int device, const uint8_t *in, int64_t n_bytes, int32_t block_bytes,
                               uint8_t *out, int64_t out_stride, int32_t out_room, uint32_t *out_len, void *stream);
 /* Waits for the library's DEFLATE stream of `device` (what a NULL stream above runs on). */
+/* The same when only the device knows the byte count: the kernel reads it from *d_n_bytes (device memory, written by earlier work
+ * on `stream`); max_bytes = the most it can be, which sizes the launch.  out_len[k] is written for the chunks of *d_n_bytes only. */
+int amp_deflate_blocks_device_counted(int device, const uint8_t *in, const uint64_t *d_n_bytes, int64_t max_bytes, int32_t block_bytes,
+                                      uint8_t *out, int64_t out_stride, int32_t out_room, uint32_t *out_len, void *stream);
 int amp_deflate_sync(int device);
 /* Signature of ampbam_writer_set_deflater (include/ampbam.h): `user` points to an int32_t holding the device. */
 int amp_deflate_blocks_cb(void *user, const uint8_t *in, int64_t n_bytes, int32_t block_bytes,
@@ -462,7 +466,7 @@ int amp_sam_stage_ms(amp_sam *s, int on, float *ms);
  * (ampbam_inflate_raw / zlib, CRC checked), patches the bytes in and asks for the index again.  On a valid file no block is. */
 #define AMP_BAM_IMAGE_LIMIT (256ll << 20) /* bytes of an image: carry + the ISIZE sum of a piece.  A record is at most 2^27 + 4 bytes
                                            * (a longer block_size is a format error), so pieces of up to 120 MiB inflated always fit */
-#define AMP_BAM_N_STAGES 7
+#define AMP_BAM_N_STAGES 12
 typedef struct amp_bam amp_bam;
 typedef struct amp_bam_block {   /* one BGZF block of a piece */
     uint32_t in_off, in_len;     /* its raw DEFLATE stream in the piece's compressed bytes */
@@ -503,13 +507,46 @@ int amp_bam_reads(amp_bam *s, amp_dev_reads *out);
  * row's record number: tests and tools. */
 int amp_bam_batch_to_host(amp_bam *s, const amp_reads *dst, int64_t *src_index);
 /* The image of the last feed and the offsets of its records in it (either may be NULL): tests and tools.  Both stay on the
- * device until the next feed -- what a device re-encoder of trimmed records would copy the unchanged parts from. */
+ * device until the next feed -- what amp_bam_encode copies the unchanged parts of trimmed records from. */
 int amp_bam_image_to_host(amp_bam *s, uint8_t *image, int64_t image_cap, uint32_t *rec_off, int64_t rec_cap);
 /* A:896-915 for the piece: amp_process_batch_device on the batch, the result arrays owned by s (as amp_sam_process). */
 int amp_bam_process(amp_bam *s, uint64_t read_base, int64_t *first_bad_row, uint8_t *its_status);
 /* Development aid: ms[AMP_BAM_N_STAGES] of the last piece from HIP events on the ctx stream -- [0] copy up, [1] inflate, [2] CRC,
- * [3] record index, [4] decode, [6] the read pass ([5]: the wait and host time between).  on != 0 records from the next call on. */
+ * [3] record index, [4] decode, [6] the read pass, [8] re-encode of trimmed records, [9] their DEFLATE, [10] CRC and framing,
+ * [11] copy down ([5], [7]: the waits and host time between the calls).  on != 0 records from the next call on. */
 int amp_bam_stage_ms(amp_bam *s, int on, float *ms);
+
+/* ---- trimmed BAM out of an amp_bam (opt-in: AMPLIPY_GPU_BAM_WRITE=1 with AMPLIPY_GPU_BAM=1) -------------
+ * The host codec writes trimmed reads with ampbam_write_rows (out_aln.write, AmpliPy.py:911), which copies the unchanged parts of
+ * a record from the piece's HOST image, and compresses 0xFF00-byte chunks of the record stream into BGZF blocks.  amp_bam_encode
+ * does both on the device, behind amp_bam_process, from the image, record offsets, batch and results the amp_bam holds: the
+ * kept rows of the last feed (A:910: ref_len >= min_length and (trimmed at a primer or include_no_primer), rows in front of the
+ * first failing one) are re-encoded -- the same bytes as ampbam_write_rows -- behind the bytes the call before left over, the
+ * whole 0xFF00-byte chunks of that stream are compressed (amp_deflate_blocks_device_counted), given CRC-32 and BGZF framing and
+ * gathered back to back; what is left (< 0xFF00 bytes) opens the next call's stream, so the blocks do not depend on how the
+ * file was cut into pieces.  final != 0 compresses the last partial chunk too.  A call without a fresh feed behind it (the rows
+ * of a feed are encoded once), or after a feed without rows, appends nothing: with final it is the bare flush.
+ * One wait per call.  AMP_EINVAL when a kept row's new CIGAR has more than 65,535 ops (ampbam_write_rows refuses the batch):
+ * nothing was appended.  AMP_ESTATE when the last feed has rows and amp_bam_process has not run on them.  The header's blocks
+ * and the end-of-file block stay the host codec's (ampbam_writer_open_refs / ampbam_writer_append_framed / ampbam_writer_close). */
+typedef struct amp_bam_out_info {
+    int64_t n_rows_written;    /* rows re-encoded by this call */
+    int64_t stream_bytes;      /* the call's uncompressed stream [carry_in | new records] */
+    int64_t carry_in, carry_out;   /* bytes taken over from the call before / left to the next one */
+    int64_t n_blocks;          /* BGZF blocks of this call */
+    int64_t file_bytes;        /* ... their bytes in the file: what amp_bam_encoded_to_host copies */
+    int64_t n_blocks_host;     /* blocks whose DEFLATE stream did not fit a BGZF block: not among file_bytes, the caller compresses them */
+    int64_t waits;             /* waits for the device this call cost (1) */
+    int64_t bytes_down;        /* device-to-host bytes: the counters and file_bytes */
+} amp_bam_out_info;
+int amp_bam_encode(amp_bam *s, int32_t min_length, int32_t include_no_primer, int32_t final, amp_bam_out_info *info);
+/* The framed blocks of the last encode back to back, file_bytes of them, to host memory. */
+int amp_bam_encoded_to_host(amp_bam *s, uint8_t *dst, int64_t cap);
+/* The size in the file of every block of the last encode (n_blocks values); 0 for a block handed to the host, whose chunk is
+ * bytes [k * 0xFF00, ...) of the stream. */
+int amp_bam_encoded_blocks(amp_bam *s, uint32_t *blk_len, int64_t cap);
+/* n bytes from offset `from` of the uncompressed stream of the last encode: tests, and the chunks of blocks handed to the host. */
+int amp_bam_stream_to_host(amp_bam *s, int64_t from, int64_t n, uint8_t *dst);
 
 #ifdef __cplusplus
 }
