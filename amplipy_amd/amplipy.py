@@ -266,12 +266,15 @@ def open_device_bam_write(input_fn, output_fn):
     return src, bam_device.DeviceBamOutput(output_fn, hdr.text, src.references, level=int(os.environ.get("AMPLIPY_BAM_LEVEL", "-1")))
 
 
-def open_native_sam(input_fn, output_fn):
-    """(SamTextInput, Header, AlignmentWriter or None, binary output or None, device_ok) when the device codec for SAM text can serve
-    this run (sam_native): stdin or an existing .sam file in, and stdout, a new .sam file or nothing out.
+def open_native_sam(input_fn, output_fn, bam_write=False):
+    """(SamTextInput, Header, AlignmentWriter or None, binary output or None, device_ok, DeviceBamOutput or None) when the device
+    codec for SAM text can serve this run (sam_native): stdin or an existing .sam file in, and stdout, a new
+    .sam file or nothing out -- or, with bam_write (both switches on, section 13), a new .bam file, whose header blocks and
+    end-of-file block a bam_device.DeviceBamOutput writes.
     None otherwise: the Python codec handles those.  Same checks and messages as open_alignment_files (what it would refuse
     is left to it).  device_ok False: the header is one the device's name table cannot take (more than 64 @SQ lines, a name
-    that is not plain text) -- every chunk of the run then goes through the Python codec."""
+    that is not plain text) -- every chunk of the run then goes through the Python codec, and a BAM output through its
+    writer, as with the switches off."""
     import io
     from . import sam_native
     if input_fn is None:
@@ -285,7 +288,8 @@ def open_native_sam(input_fn, output_fn):
     to_stdout = output_fn is not None and output_fn.lower() == "stdout"
     if to_stdout and not hasattr(sys.stdout, "buffer"):
         return None
-    if output_fn is not None and not to_stdout and (isfile(output_fn) or not output_fn.lower().endswith(".sam")):
+    to_bam = bool(bam_write) and output_fn is not None and not to_stdout and not isfile(output_fn) and output_fn.lower().endswith(".bam")
+    if output_fn is not None and not to_stdout and not to_bam and (isfile(output_fn) or not output_fn.lower().endswith(".sam")):
         return None
     src = sam_native.SamTextInput("-" if from_stdin else input_fn)
     text = src.header_text()
@@ -293,17 +297,23 @@ def open_native_sam(input_fn, output_fn):
     names = [n for n, _ in hdr.refs]
     device_ok = src.header_is_plain() and len(names) <= sam_native.MAX_REFS and sum(len(n) for n in names) <= sam_native.MAX_REF_BYTES \
         and all(n not in ("", "*", "=") and all(33 <= ord(c) < 127 for c in n) for n in names)
-    writer = outb = None
+    writer = outb = bam_out = None
     if output_fn is not None:
         out_hdr = hdr.with_amplipy_pg(VERSION, " ".join(sys.argv))
-        if to_stdout:
+        if to_bam and device_ok:
+            from . import bam_device
+            bam_out = bam_device.DeviceBamOutput(output_fn, out_hdr.text, hdr.refs, level=int(os.environ.get("AMPLIPY_BAM_LEVEL", "-1")))
+        elif to_bam:
+            writer = bamio.AlignmentWriter(output_fn, "wb", out_hdr)
+        elif to_stdout:
             outt, outb = sys.stdout, sys.stdout.buffer
         else:
             outb = open(output_fn, "wb")
             outt = io.TextIOWrapper(outb, write_through=True)       # (what open(output_fn, "w") is made of)
-        writer = bamio.AlignmentWriter(None, "w", out_hdr, fileobj=outt)
-        outt.flush()
-    return src, hdr, writer, outb, device_ok
+        if outb is not None:
+            writer = bamio.AlignmentWriter(None, "w", out_hdr, fileobj=outt)
+            outt.flush()
+    return src, hdr, writer, outb, device_ok, bam_out
 
 
 class VcfWriter:
@@ -378,7 +388,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
-    sam_native instead of the Python codec; one process only.
+    sam_native instead of the Python codec; one process only.  With gpu_bam_write on as well, SAM text in and a new BAM file of
+    trimmed reads out does too: records, compression and framing are made on the device.
     gpu_bam (default: AMPLIPY_GPU_BAM, off): a BAM file in and no trimmed reads out (variants, consensus) is inflated, indexed and
     decoded on the device (bam_device) instead of by libampbam; one process only.  Runs that write trimmed reads keep libampbam,
     unless gpu_bam_write (default: AMPLIPY_GPU_BAM_WRITE, off) is on as well: a BAM file in and a new BAM file of trimmed reads out
@@ -465,7 +476,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if native is not None and use_bam:
                 print_log("BAM device codec: this run writes trimmed reads, the host codec reads the input")
             if native is None and bamdev is None and use_sam:
-                sam = open_native_sam(untrimmed_reads_fn, trimmed_reads_fn)
+                sam = open_native_sam(untrimmed_reads_fn, trimmed_reads_fn, bam_write=gpu_codec_wanted(gpu_bam_write, "AMPLIPY_GPU_BAM_WRITE"))
             if native is None and sam is None and bamdev is None:
                 reader, writer = open_alignment_files(untrimmed_reads_fn, trimmed_reads_fn)
         else:
@@ -528,9 +539,10 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if k_:
                 print_log("Processed %d reads..." % k_)
 
-    def device_piece(codec, info, emit=None):
+    def device_piece(codec, info, emit=None, defer=False):
         """A piece or chunk whose batch a device codec has built (info: n_records, n_rows, n_bases): counted, through the read pass
-        where it lies, ``emit`` run on its results, its events stored."""
+        where it lies, ``emit`` run on its results, its events stored.  defer: the read pass is only enqueued, ``emit`` works from
+        the verdict where it lies and brings it down with its own wait (sam_native.SamCodec.encode)."""
         nonlocal n_seen, s_i, n_bases, read_base
         count = int(info.n_records)
         progress(count)
@@ -540,9 +552,14 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if info.n_rows == 0:
             return
         n_bases += int(info.n_bases)
-        bad_row, bad_status = codec.process(read_base)
-        if emit is not None:
+        if defer:
+            codec.process(read_base, defer=True)
             emit()
+            bad_row, bad_status = codec.verdict()
+        else:
+            bad_row, bad_status = codec.process(read_base)
+            if emit is not None:
+                emit()
         if bad_row >= 0:                  # the rows in front of it are written (A:907-911)
             _raise_for_status(bad_status)
         if do_count:
@@ -686,14 +703,36 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         # SAM text in (and SAM text or nothing out) with the switch on: chunks of whole lines are parsed, packed, trimmed / counted
         # and, for a trimmed output, turned back into text on the device (sam_native; no per-read Python object).  A chunk
         # with a line the device calls odd goes through the Python codec as below (same Rec / flush() code), then the next chunk
-        # is the device's again; rows stay in input order.
+        # is the device's again; rows stay in input order.  With both switches on and a new BAM file out (section 13) the kept
+        # rows of a device chunk become BAM records, DEFLATE streams and framed BGZF blocks there (one wait per chunk behind the
+        # parse's), and the records the Python codec makes of an odd chunk go up into the same stream: the file's blocks do not
+        # depend on which side encoded a chunk.
         import io
         from . import sam_native
-        src, sam_hdr, writer, outb, device_ok = sam
+        src, sam_hdr, writer, outb, device_ok, bam_out = sam
         stats = sam_native.LAST_RUN_STATS
         stats.update(device_chunks=0, python_chunks=0, records=0)
+        stats.update((k_, 0) for k_ in sam_native.OUT_STATS)
         codec = None
         py_reader = bamio.AlignmentReader.for_header(sam_hdr)
+        host_recs = []                    # record bytes the Python codec made of an odd chunk, on their way into the device's stream
+
+        class RecordSink:                 # what flush() writes kept records to on that way
+            @staticmethod
+            def write(r, pos=None, cigar=None):
+                host_recs.append(bamio.bam_record_bytes(r, r.pos if pos is None else pos, r.cigar if cigar is None else cigar))
+        if bam_out is not None:
+            writer = RecordSink
+
+        def encode_kept():                # AmpliPy.py:910-911: the rows in front of a failing one, whole blocks only
+            bam_out.encode(codec, stats, min_length, include_no_primer)
+            stats["encodes"] += 1
+
+        def send_host_recs(final=False):
+            if host_recs or final:
+                bam_out.encode_bytes(codec, stats, b"".join(host_recs), final=final)
+                stats["encodes"] += 1
+                del host_recs[:]
 
         def write_kept():
             if run_trim and writer is not None:
@@ -703,30 +742,48 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if device_ok:
                 codec = sam_native.SamCodec(eng)
                 codec.set_references([n for n, _ in sam_hdr.refs])
+                if bam_out is not None:
+                    codec.set_output(sam_native.OUT_BAM)
             for chunk in src:
                 info = codec.parse(chunk) if codec is not None else None
                 if info is None or info.first_odd_line >= 0:
                     stats["python_chunks"] += 1
-                    for rec in py_reader.records_of(io.TextIOWrapper(io.BytesIO(chunk))):
-                        s_i = n_seen
-                        n_seen += 1
-                        if s_i % PROGRESS_NUM_READS == 0 and s_i != 0:
-                            print_log("Processed %d reads..." % s_i)
-                        if (rec.flag & 4) or rec.cigar is None:            # AmpliPy.py:902
-                            continue
-                        pending.append(rec)
-                        if len(pending) >= BATCH_READS:
-                            flush()
-                    flush()
-                    if writer is not None:
+                    try:
+                        for rec in py_reader.records_of(io.TextIOWrapper(io.BytesIO(chunk))):
+                            s_i = n_seen
+                            n_seen += 1
+                            if s_i % PROGRESS_NUM_READS == 0 and s_i != 0:
+                                print_log("Processed %d reads..." % s_i)
+                            if (rec.flag & 4) or rec.cigar is None:            # AmpliPy.py:902
+                                continue
+                            pending.append(rec)
+                            if len(pending) >= BATCH_READS:
+                                flush()
+                        flush()
+                    finally:
+                        if bam_out is not None:
+                            send_host_recs()          # (on a failing read too: the rows in front of it were written)
+                    if outb is not None:
                         writer._f.flush()
                     continue
                 stats["device_chunks"] += 1
-                device_piece(codec, info, emit=write_kept)
+                if bam_out is not None:
+                    device_piece(codec, info, emit=encode_kept, defer=True)
+                else:
+                    device_piece(codec, info, emit=write_kept)
             stats["records"] = n_seen
-            print_log("SAM text codec: %d chunks on the device, %d through the Python codec" % (stats["device_chunks"], stats["python_chunks"]))
+            if bam_out is not None:
+                # the partial block, then the end-of-file block; not on a failing read (the Python codec does not close its
+                # writer then either).  The flush is a call of its own: a chunk's encode does not know the read pass's verdict
+                send_host_recs(final=True)
+                bam_out.close()
+            elif writer is not None and outb is None:
+                writer.close()                        # (a BAM output of a run whose header keeps it on the Python codec)
+            print_log("SAM text codec: %d chunks on the device, %d through the Python codec" % (stats["device_chunks"], stats["python_chunks"])
+                      + ("" if bam_out is None else "; trimmed reads went out as BAM blocks from the device: %d blocks on the device, %d "
+                         "through the host, %d bytes down" % (stats["out_blocks_device"], stats["out_blocks_host"], stats["bytes_down"])))
         finally:
-            if writer is not None:
+            if outb is not None:
                 writer._f.flush()
                 outb.flush()
                 if outb is not getattr(sys.stdout, "buffer", None):

@@ -29,7 +29,7 @@ PIECE_BYTES = 16 << 20
 IMAGE_LIMIT = 256 << 20            # AMP_BAM_IMAGE_LIMIT of amplihip.h
 PIECE_ISIZE_LIMIT = 120 << 20      # ISIZE sum of a piece: with a carry of at most one record (2^27 + 4 bytes) the image fits
 N_STAGES = 12                      # AMP_BAM_N_STAGES
-OUT_BS = 0xFF00                    # uncompressed bytes of a BGZF block of the trimmed output (the host writer's)
+OUT_BS = devcodec.OUT_BS
 FORMAT_ERROR = -3                  # AMPBAM_EFORMAT
 
 # the last run of run_amplipy that took this path
@@ -50,27 +50,13 @@ class AmpBamInfo(C.Structure):
                                          "bytes_up")] + [("bad_record", C.c_int32), ("reserved", C.c_int32)]
 
 
-class AmpBamOutInfo(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("n_rows_written", "stream_bytes", "carry_in", "carry_out", "n_blocks", "file_bytes", "n_blocks_host",
-                                         "waits", "bytes_down")]
-
-
-# amp_bam_twin_deflate_fn of amp_bamout.hpp
-TWIN_DEFLATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_uint32))
+AmpBamOutInfo, TWIN_DEFLATE_FN, bgzf_block = devcodec.AmpBamOutInfo, devcodec.TWIN_DEFLATE_FN, devcodec.bgzf_block
 
 
 def twin_sources():
     """amp_bgzf.hip (which includes amp_bamout.hip, the re-encoder's lanes and driver) and the lane functions' headers."""
     here = os.path.dirname(os.path.abspath(__file__))
     return tuple(os.path.join(here, "csrc", f) for f in ("amp_bgzf.hip", "amp_bgzf.hpp", "amp_bamout.hip", "amp_bamout.hpp"))
-
-
-def bgzf_block(data, level=6):
-    """One BGZF block of ``data`` (at most 0xFF00 bytes) made on the host: zlib's stream, the framing of flush_blocks."""
-    co = zlib.compressobj(level, zlib.DEFLATED, -15)
-    comp = co.compress(data) + co.flush()
-    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(comp) + 25) + comp
-            + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
 
 
 def build_twin(out_path, sanitize=False, main_source=None):
@@ -228,16 +214,6 @@ class BamCodec(devcodec.DeviceCodec):
                                                               (res.ref_len, np.int32), (res.trim_flags, np.uint8))]
         self._chk(self.L.amp_bam_twin_set_trim(self.h, *[C.c_void_p(abi.ptr(a)) for a in self._trim], C.c_int64(first_bad)), "amp_bam_twin_set_trim")
 
-    def set_deflater(self, fn):
-        """Twin only: the DEFLATE encoder of its encodes -- the address of ampdf_hostsim_blocks (amp_deflate.hip's host phases), or a
-        TWIN_DEFLATE_FN object."""
-        self._deflater = fn
-        self._chk(self.L.amp_bam_twin_set_deflater(self.h, fn), "amp_bam_twin_set_deflater")
-
-    def guards_ok(self):
-        """Twin only: no encode so far wrote behind one of its buffers."""
-        return int(self.L.amp_bam_twin_guards(self.h)) == 0
-
     def encode(self, min_length, include_no_primer, final=False):
         """amp_bam_encode + amp_bam_encoded_to_host: (the BGZF blocks of this call as they go into the file, info).  The kept rows
         of the last feed (A:910), behind what the call before left over; final: the last partial block too.  A block whose
@@ -247,31 +223,7 @@ class BamCodec(devcodec.DeviceCodec):
         if rc == -1:
             raise bam_native.AmpBamError("write: %s" % bam_native.load().ampbam_strerror(-1).decode())      # (what ampbam_write_rows answers)
         self._chk(rc, "amp_bam_encode")
-        self.out_info = info
-        out = np.empty(max(int(info.file_bytes), 1), np.uint8)
-        if info.file_bytes:
-            self._chk(self.L.amp_bam_encoded_to_host(self.h, C.c_void_p(abi.ptr(out)), C.c_int64(out.size)), "amp_bam_encoded_to_host")
-        out = out[:int(info.file_bytes)]
-        if info.n_blocks_host:
-            lens = np.zeros(int(info.n_blocks), np.uint32)
-            self._chk(self.L.amp_bam_encoded_blocks(self.h, C.c_void_p(abi.ptr(lens)), C.c_int64(lens.size)), "amp_bam_encoded_blocks")
-            enc = int(info.stream_bytes) - int(info.carry_out)
-            parts, at = [], 0
-            for k, n in enumerate(int(x) for x in lens):
-                if n:
-                    parts.append(out[at:at + n].tobytes()); at += n
-                else:
-                    parts.append(bgzf_block(self.stream(k * OUT_BS, min(OUT_BS, enc - k * OUT_BS)).tobytes()))
-                    info.bytes_down += min(OUT_BS, enc - k * OUT_BS)
-            out = np.frombuffer(b"".join(parts), np.uint8)
-        return out, info
-
-    def stream(self, start=0, n=None):
-        """Bytes [start, start + n) of the uncompressed stream [carry | new records] of the last encode (n None: to its end)."""
-        n = int(self.out_info.stream_bytes) - start if n is None else n
-        buf = np.zeros(max(n, 1), np.uint8)
-        self._chk(self.L.amp_bam_stream_to_host(self.h, C.c_int64(start), C.c_int64(n), C.c_void_p(abi.ptr(buf))), "amp_bam_stream_to_host")
-        return buf[:n]
+        return self._encoded(info)
 
     def image(self):
         """(the image of the last feed, the offsets of its records in it)."""
@@ -356,7 +308,13 @@ class DeviceBamOutput:
         self.path = path
 
     def encode(self, codec, stats, min_length, include_no_primer, final=False):
-        blocks, info = codec.encode(min_length, include_no_primer, final)
+        return self._append(stats, *codec.encode(min_length, include_no_primer, final))
+
+    def encode_bytes(self, codec, stats, data, final=False):
+        """Record bytes made on the host through the same stream (sam_native.SamCodec.encode_bytes)."""
+        return self._append(stats, *codec.encode_bytes(data, final))
+
+    def _append(self, stats, blocks, info):
         self.writer.append_framed(blocks)
         stats["out_blocks_device"] += int(info.n_blocks) - int(info.n_blocks_host)
         stats["out_blocks_host"] += int(info.n_blocks_host)

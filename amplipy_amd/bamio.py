@@ -312,6 +312,28 @@ class AlignmentReader:
 # ---------------------------------------------------------------------------------------------
 # writers
 # ---------------------------------------------------------------------------------------------
+def bam_record_bytes(r, pos, cigar):
+    """The bytes of record ``r`` in a BAM stream, block_size word included, with the 0-based POS ``pos`` and the CIGAR ``cigar``
+    (list[(op, len)] or None)."""
+    name = r.qname.encode("ascii") + b"\0"
+    l_seq = 0 if r.seq is None else len(r.seq)
+    rlen = sum(n for op, n in (cigar or ()) if op in (0, 2, 3, 7, 8))
+    end = pos + (rlen if rlen else 1)
+    core = struct.pack("<iiBBHHHiiii", r.ref_id, pos, len(name), r.mapq, reg2bin(max(pos, 0), max(end, 1)),
+                       len(cigar or ()), r.flag, l_seq, r.next_ref_id, r.next_pos, r.tlen)
+    cg = struct.pack("<%dI" % len(cigar or ()), *[(n << 4) | op for op, n in (cigar or ())])
+    sq = b""
+    if l_seq:
+        codes = [_NT16_ENC.get(c, 15) for c in r.seq]
+        if l_seq & 1:
+            codes.append(0)
+        sq = bytes((codes[k] << 4) | codes[k + 1] for k in range(0, len(codes), 2))
+    ql = (bytes(r.qual) if r.qual is not None else b"\xff" * l_seq)
+    aux = r.aux_bam if r.aux_bam is not None else aux_sam_to_bam(r.aux_sam or [])
+    body = core + name + cg + sq + ql + aux
+    return struct.pack("<i", len(body)) + body
+
+
 class AlignmentWriter:
     def __init__(self, path, mode, header, fileobj=None):
         """fileobj (text mode only): an open text file to write to in place of ``path``; it is left open by close()."""
@@ -336,23 +358,7 @@ class AlignmentWriter:
         pos = r.pos if pos is None else pos
         cigar = r.cigar if cigar is None else cigar
         if self.mode == "wb":
-            name = r.qname.encode("ascii") + b"\0"
-            l_seq = 0 if r.seq is None else len(r.seq)
-            rlen = sum(n for op, n in (cigar or ()) if op in (0, 2, 3, 7, 8))
-            end = pos + (rlen if rlen else 1)
-            core = struct.pack("<iiBBHHHiiii", r.ref_id, pos, len(name), r.mapq, reg2bin(max(pos, 0), max(end, 1)),
-                               len(cigar or ()), r.flag, l_seq, r.next_ref_id, r.next_pos, r.tlen)
-            cg = struct.pack("<%dI" % len(cigar or ()), *[(n << 4) | op for op, n in (cigar or ())])
-            sq = b""
-            if l_seq:
-                codes = [_NT16_ENC.get(c, 15) for c in r.seq]
-                if l_seq & 1:
-                    codes.append(0)
-                sq = bytes((codes[k] << 4) | codes[k + 1] for k in range(0, len(codes), 2))
-            ql = (bytes(r.qual) if r.qual is not None else b"\xff" * l_seq)
-            aux = r.aux_bam if r.aux_bam is not None else aux_sam_to_bam(r.aux_sam or [])
-            body = core + name + cg + sq + ql + aux
-            self._w.write(struct.pack("<i", len(body)) + body)
+            self._w.write(bam_record_bytes(r, pos, cigar))
         else:
             rn = self._ref_name(r.ref_id)
             rnext = "*" if r.next_ref_id < 0 else ("=" if r.next_ref_id == r.ref_id else self._ref_name(r.next_ref_id))

@@ -16,10 +16,11 @@ SRC = os.path.join(CSRC, "amplihip.hip")
 HEADERS = [os.path.join(_HERE, "..", "include", "amplihip.h")] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
 UNIT_DEPS = {"amplihip.hip": HEADERS, "amp_ins.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_ins.hpp")],
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
-             "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_codec.hpp")],
+             "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in
+                             ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamtail.hpp")],
              # (amp_bamout.hip, the re-encoder of trimmed records, is part of amp_bgzf.hip's unit: it is included there)
              "amp_bgzf.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in
-                              ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamout.hip")]}
+                              ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamtail.hpp", "amp_bamout.hip")]}
 DEPS = [os.path.join(CSRC, u) for u in UNITS] + [os.path.join(CSRC, "amp_bamout.hip")] + HEADERS
 OUT = os.path.join(_HERE, "libamplihip.so")
 OBJ_DIR = os.path.join(_HERE, "build")

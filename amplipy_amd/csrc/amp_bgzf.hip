@@ -29,8 +29,7 @@
 
 #include "amp_codec.hpp"
 #define BGZ_HD AMP_HD
-#include "amp_bgzf.hpp"
-#include "amp_bamout.hpp"
+#include "amp_bamtail.hpp"
 
 namespace ampbgzf {
 
@@ -288,18 +287,9 @@ struct amp_bam {
     int64_t refused_left = 0, force_refuse = -1;
     unsigned long long h_ctl[CTL_WORDS];
     // the re-encoder of trimmed records (amp_bamout.hip)
-    bool processed = false, encoded = false, out_ok = false;      // of the last feed: results are there; its rows were encoded
+    bool processed = false, encoded = false;          // of the last feed: results are there; its rows were encoded
     int64_t good_rows = 0;                            // rows in front of the first failing one
-    uint8_t *oarena = nullptr, *ocarry = nullptr;
-    size_t cap_oarena = 0, cap_ocarry = 0;
-    int64_t oarena_rows = 0, oarena_stream = 0, oarena_blocks = 0;
-    int64_t ocarry_len = 0;                           // bytes of the record stream behind its last whole 0xFF00-byte chunk, kept in `ocarry`
-    amp_bam_out_info oinfo{};
-    unsigned long long h_octl[ampbamout::OCTL_WORDS];
-#ifdef AMPBGZF_HOSTSIM
-    amp_bam_twin_deflate_fn twin_deflate = nullptr;
-    std::vector<std::pair<uint8_t *, size_t>> guards;     // the bytes behind the encoder's buffers, which nothing may write
-#endif
+    ampbamout::Tail tail;                             // the encoder's buffers, carry and counters (amp_bamtail.hpp)
 };
 
 #ifndef AMPBGZF_HOSTSIM
@@ -438,7 +428,7 @@ void amp_bam_destroy(amp_bam *s) {
     if (!s) return;
     DevGuard guard(s->sh);
     (void)codec_wait(s->sh);
-    codec_free(s->arena); codec_free(s->img); codec_free(s->comp); codec_free(s->carry); codec_free(s->oarena); codec_free(s->ocarry);
+    codec_free(s->arena); codec_free(s->img); codec_free(s->comp); codec_free(s->carry); ampbamout::tail_free(s->tail);
     codec_delete(s);
 }
 

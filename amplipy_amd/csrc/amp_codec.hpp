@@ -246,24 +246,32 @@ static int codec_results_room(Shell &sh, int64_t n_rows, int64_t n_cig, Trim &t)
     return AMP_OK;
 }
 
-// the first row with a non-zero status (-1: none) and that status: one kernel, eight bytes down, one wait
-static int codec_first_bad(Shell &sh, const Trim &t, int64_t n_rows, int64_t *first_bad_row, uint8_t *its_status) {
+// the first row with a non-zero status (-1: none) and that status: one kernel, eight bytes down, one wait.  The two halves are
+// there for a codec whose next stage reads the key where it lies (sh.bad_key) and brings it down with its own wait.
+static int codec_first_bad_launch(Shell &sh, const Trim &t, int64_t n_rows) {
     CODEC_OK(codec_zero(sh, sh.bad_key, 0xFF, 8));
-    CODEC_OK(codec_run_first_bad(sh, t.status, n_rows));
-    unsigned long long key = ~0ull;
-    CODEC_OK(codec_down(sh, &key, sh.bad_key, 8));
-    CODEC_OK(codec_wait(sh));
+    return codec_run_first_bad(sh, t.status, n_rows);
+}
+static void codec_first_bad_of(unsigned long long key, int64_t *first_bad_row, uint8_t *its_status) {
     const bool any = key != ~0ull;
     if (first_bad_row) *first_bad_row = any ? (int64_t)(key >> 8) : -1;
     if (its_status) *its_status = any ? (uint8_t)(key & 255u) : 0;
+}
+static int codec_first_bad(Shell &sh, const Trim &t, int64_t n_rows, int64_t *first_bad_row, uint8_t *its_status) {
+    CODEC_OK(codec_first_bad_launch(sh, t, n_rows));
+    unsigned long long key = ~0ull;
+    CODEC_OK(codec_down(sh, &key, sh.bad_key, 8));
+    CODEC_OK(codec_wait(sh));
+    codec_first_bad_of(key, first_bad_row, its_status);
     return AMP_OK;
 }
 
 #ifndef AMP_CODEC_HOSTSIM
 // A:896-915 for the rows of the batch: amp_process_batch_device on it where it lies, the results kept in the shell (t points at
-// them); the events `stage` and `stage + 1` around the read pass
+// them); the events `stage` and `stage + 1` around the read pass.  defer: the key of the first failing row stays on the device
+// (sh.bad_key) and nothing is waited for
 static int codec_process(Shell &sh, const Batch &b, Trim &t, int64_t n_rows, int64_t n_cig, int64_t n_bases_padded, uint64_t read_base, int stage,
-                         int64_t *first_bad_row, uint8_t *its_status) {
+                         int64_t *first_bad_row, uint8_t *its_status, bool defer = false) {
     DevGuard guard(sh);
     CODEC_OK(codec_results_room(sh, n_rows, n_cig, t));
     codec_mark(sh, stage);
@@ -273,6 +281,7 @@ static int codec_process(Shell &sh, const Batch &b, Trim &t, int64_t n_rows, int
         CODEC_OK(amp_process_batch_device(sh.ctx, &rd, read_base, &o));
     }
     codec_mark(sh, stage + 1);
+    if (defer) return codec_first_bad_launch(sh, t, n_rows);
     return codec_first_bad(sh, t, n_rows, first_bad_row, its_status);
 }
 
@@ -282,6 +291,7 @@ static int codec_stage_ms(Shell &sh, int on, float *ms) {
     if (ms && sh.timed) {
         CODEC_OK(codec_wait(sh));
         for (int k = 0; k < sh.n_stages; ++k) if (hipEventElapsedTime(&ms[k], sh.ev[k], sh.ev[k + 1]) != hipSuccess) ms[k] = -1.f;
+        (void)hipGetLastError();                      // (a stage that did not run: its event was never recorded)
     }
     sh.timed = on != 0;
     return AMP_OK;

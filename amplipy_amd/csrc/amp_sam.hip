@@ -26,11 +26,13 @@
 // What surrounds the stages -- stream, copies, scan, events, the batch's way into the read pass and back -- is the shell of
 // amp_codec.hpp.
 #include "amp_codec.hpp"
+#define BGZ_HD AMP_HD
+#include "amp_bamtail.hpp"
 
 namespace ampsam {
 
 enum { CTL_NLINES = 0, CTL_NREC, CTL_NROWS, CTL_NCIG, CTL_NBASES, CTL_NSLOTS, CTL_ODD, CTL_BADBYTE, CTL_FMT_BYTES, CTL_FMT_ROWS,
-       CTL_WORDS = 16 };
+       CTL_NTABS, CTL_BAM_BYTES, CTL_WORDS = 16 };
 enum { FTABS = 11, WAVE = 64 };
 static const uint32_t QUAL_STAR = 0xFFFFFFFFu;
 
@@ -55,7 +57,16 @@ struct BufRows {
     const uint8_t *names; const uint32_t *ref_off; int32_t n_ref;
     unsigned long long *ctl;   // [CTL_WORDS]
 };
-struct Buf : BufLines, ampcodec::Batch, BufRows, ampcodec::Trim {
+// BAM output (amp_sam_set_output): a table per tab of the chunk, a size per row, the encoder's Out
+struct BufBam {
+    int32_t bam_mode, pad; int64_t tab_cap;
+    uint32_t *tab_pos;         // [tab_cap] where tab T of the chunk lies
+    uint32_t *aux_sz;          // [tab_cap + 1] BAM bytes of the aux field behind tab T (0: no aux field), then their exclusive sum
+    uint32_t *row_bsz;         // [line_cap + 1] per row: bytes of its BAM record, block_size word included, CIGAR left out
+    const unsigned long long *bad_key;      // the key of the first failing row where the read pass left it (NULL: good_rows holds it)
+    ampbamout::Out o;
+};
+struct Buf : BufLines, ampcodec::Batch, BufRows, ampcodec::Trim, BufBam {
     uint32_t *out_off, *cig_tlen; uint8_t *out;
     int32_t min_length, include_no_primer; int64_t good_rows;
 };
@@ -107,7 +118,7 @@ AMP_HD void lane_lines(const Buf &b, int64_t j) {
         }
         ++line;
     }
-    if (j == b.n_slots16 - 1) b.ctl[CTL_NLINES] = line;
+    if (j == b.n_slots16 - 1) { b.ctl[CTL_NLINES] = line; b.ctl[CTL_NTABS] = tabr + (uint32_t)__builtin_popcount(tabm); }
 }
 
 AMP_HD void lane_tabs(const Buf &b, int64_t j) {
@@ -123,6 +134,7 @@ AMP_HD void lane_tabs(const Buf &b, int64_t j) {
             const uint32_t f = tabr - b.line_tab0[line];
             if (f < FTABS) b.ftab[(size_t)line * FTABS + f] = (uint32_t)(j * 16 + k);
         }
+        if (b.bam_mode && (int64_t)tabr < b.tab_cap) b.tab_pos[tabr] = (uint32_t)(j * 16 + k);
         ++tabr;
     }
 }
@@ -267,6 +279,11 @@ AMP_HD void lane_records(const Buf &b, int64_t i) {
             if (!why && !qstar && sstar) why = AMP_SAM_ODD_QUAL_NO_SEQ;
             if (!why && !qstar && qlen != slen) why = AMP_SAM_ODD_QUAL_LEN;
             if (!why && !qstar && low_before(b, fe) != low_before(b, fs)) why = AMP_SAM_ODD_QUAL_CHAR;
+            if (b.bam_mode) {                                        // what a BAM record's fields cannot hold
+                field(b, i, ln, 0, fs, fe);
+                if (!why && fe - fs > 254u) why = AMP_SAM_ODD_QNAME;
+                if (!why && nc > 65535 - (int)ampbamout::OUT_SPARE_OPS) why = AMP_SAM_ODD_CIGAR_OPS;
+            }
             if (!why && !(flag & 4) && nc > 0) {                     // A:902
                 row = 1; ncig = (uint32_t)nc; slots = sstar ? 0u : (slen + 7u) >> 3;
             }
@@ -301,6 +318,12 @@ AMP_HD void lane_rows(const Buf &b, int64_t i) {
         b.cig_off32[r] = b.s_ncig[i]; b.seq_off8[r] = b.s_slots[i];
         b.src_index[r] = (int64_t)b.s_rec[i]; b.row_line[r] = (uint32_t)i;
         AMP_ADD64(&b.ctl[CTL_NBASES], L);
+        if (b.bam_mode) {
+            field(b, i, ln, 0, fs, fe);
+            const uint32_t aux = b.aux_sz[b.line_tab0[i + 1]] - b.aux_sz[b.line_tab0[i] + 10u];
+            b.row_bsz[r] = 36u + (fe - fs) + 1u + ((L + 1u) >> 1) + L + aux;
+            AMP_ADD64(&b.ctl[CTL_BAM_BYTES], b.row_bsz[r]);
+        }
     }
     if (i == last) {
         const uint32_t n = b.s_row[i] + b.l_row[i];
@@ -409,6 +432,249 @@ AMP_HD void lane_fmt_copy(const Buf &b, int64_t r, uint32_t lane) {
     if (lane == 0) *d = '\n';
 }
 
+// ---- BAM output: aux fields, text to binary (aux_sam_to_bam of bamio.py) ------------------------------------------------------------
+using ampbamout::o_wr16;
+using ampbamout::o_wr32;
+
+// -?(0|[1-9][0-9]*); values beyond 2^40 stay beyond it
+AMP_HD bool aux_int(const uint8_t *t, uint32_t fs, uint32_t fe, int64_t &v) {
+    if (fe == fs) return false;
+    const bool neg = t[fs] == '-';
+    uint32_t p = fs + (neg ? 1u : 0u);
+    if (p == fe || (t[p] == '0' && fe - p > 1)) return false;
+    int64_t a = 0;
+    for (; p < fe; ++p) {
+        const uint32_t c = (uint32_t)t[p] - '0';
+        if (c > 9u) return false;
+        if (a < (1ll << 40)) a = a * 10 + (int64_t)c;
+    }
+    v = neg ? -a : a;
+    return true;
+}
+// the first of c C s S i I that holds x (the order of the Python loop): 0..5, -1: none
+AMP_HD int int_code(int64_t x) {
+    if (x >= -128 && x <= 127) return 0;
+    if (x >= 0 && x <= 255) return 1;
+    if (x >= -32768 && x <= 32767) return 2;
+    if (x >= 0 && x <= 65535) return 3;
+    if (x >= -2147483648ll && x <= 2147483647ll) return 4;
+    if (x >= 0 && x <= 4294967295ll) return 5;
+    return -1;
+}
+AMP_HD bool int_fits(int code, int64_t x) {
+    switch (code) {
+        case 0: return x >= -128 && x <= 127;
+        case 1: return x >= 0 && x <= 255;
+        case 2: return x >= -32768 && x <= 32767;
+        case 3: return x >= 0 && x <= 65535;
+        case 4: return x >= -2147483648ll && x <= 2147483647ll;
+        default: return x >= 0 && x <= 4294967295ll;
+    }
+}
+AMP_HD uint32_t int_bytes(int code) { return code < 2 ? 1u : code < 4 ? 2u : 4u; }
+AMP_HD void put_int(uint8_t *d, int code, int64_t x) {
+    if (code < 2) d[0] = (uint8_t)x;
+    else if (code < 4) o_wr16(d, (uint32_t)x);
+    else o_wr32(d, (uint32_t)x);
+}
+
+// struct.pack("<f", float(v)) for the spellings -?digits[.digits][e[+-]digits] with at most 15 significant digits and a power of
+// ten, the fraction folded in, within +-22: the digits are an integer M < 10^15 < 2^53 and 10^|p| <= 10^22, both exact doubles, so
+// ONE multiplication or division gives the correctly rounded double (what float() gives); the cast rounds once more, as pack does.
+// Everything else -- inf, nan, more digits, a bare '.', an 'E' -- is not taken (false): the line is odd.  No fused operation can
+// arise from a single product or quotient, and this unit is built without fast-math.
+AMP_HD bool aux_float(const uint8_t *t, uint32_t fs, uint32_t fe, float &out) {
+    uint32_t p = fs;
+    bool neg = false;
+    if (p < fe && t[p] == '-') { neg = true; ++p; }
+    uint64_t M = 0;
+    int nsig = 0;
+    int64_t nfrac = 0, e = 0;
+    uint32_t p0 = p;
+    for (; p < fe && (uint32_t)t[p] - '0' <= 9u; ++p) {
+        const uint32_t d = (uint32_t)t[p] - '0';
+        if (M || d) ++nsig;
+        if (nsig <= 15) M = M * 10 + d;
+    }
+    if (p == p0) return false;
+    if (p < fe && t[p] == '.') {
+        p0 = ++p;
+        for (; p < fe && (uint32_t)t[p] - '0' <= 9u; ++p) {
+            const uint32_t d = (uint32_t)t[p] - '0';
+            if (M || d) ++nsig;
+            if (nsig <= 15) M = M * 10 + d;
+            ++nfrac;
+        }
+        if (p == p0) return false;
+    }
+    if (p < fe && t[p] == 'e') {
+        ++p;
+        bool eneg = false;
+        if (p < fe && (t[p] == '+' || t[p] == '-')) { eneg = t[p] == '-'; ++p; }
+        p0 = p;
+        for (; p < fe && (uint32_t)t[p] - '0' <= 9u; ++p) if (e < 100000) e = e * 10 + (int64_t)((uint32_t)t[p] - '0');
+        if (p == p0) return false;
+        if (eneg) e = -e;
+    }
+    if (p != fe || nsig > 15) return false;
+    const int64_t pw = e - nfrac;
+    if (pw < -22 || pw > 22) return false;
+    double t10 = 1.0;                                               // 10^k, k <= 22: every product is exact
+    for (int64_t k = 0; k < (pw < 0 ? -pw : pw); ++k) t10 *= 10.0;
+    const double d = pw >= 0 ? (double)M * t10 : (double)M / t10;
+    out = (float)(neg ? -d : d);
+    return true;
+}
+AMP_HD void put_float(uint8_t *d, float f) { uint32_t w; __builtin_memcpy(&w, &f, 4); o_wr32(d, w); }
+
+// One aux field text[fs, fe) as BAM: its size; d != NULL: its bytes, all but the body of a Z / H string (the wave copies that to
+// d + 3).  why = the reason the field makes its line odd (then the size means nothing), 0: none.
+AMP_HD uint32_t aux_conv(const uint8_t *t, uint32_t fs, uint32_t fe, uint8_t *d, int &why) {
+    why = 0;
+    if (fe - fs < 5u || t[fs + 2] != ':' || t[fs + 4] != ':' || (uint32_t)t[fs] - 33u > 93u || (uint32_t)t[fs + 1] - 33u > 93u) { why = AMP_SAM_ODD_AUX_TAG; return 0; }
+    const uint32_t type = t[fs + 3], vs = fs + 5u, vn = fe - vs;
+    if (d) { d[0] = t[fs]; d[1] = t[fs + 1]; }
+    if (type == 'A') {
+        if (vn != 1u) { why = AMP_SAM_ODD_AUX_A; return 0; }
+        if (d) { d[2] = 'A'; d[3] = t[vs]; }
+        return 4u;
+    }
+    if (type == 'i') {
+        int64_t x = 0;
+        if (!aux_int(t, vs, fe, x)) { why = AMP_SAM_ODD_AUX_INT; return 0; }
+        const int code = int_code(x);
+        if (code < 0) { why = AMP_SAM_ODD_AUX_INT_RANGE; return 0; }
+        if (d) { d[2] = (uint8_t)"cCsSiI"[code]; put_int(d + 3, code, x); }
+        return 3u + int_bytes(code);
+    }
+    if (type == 'f') {
+        float f = 0.f;
+        if (!aux_float(t, vs, fe, f)) { why = AMP_SAM_ODD_AUX_FLOAT; return 0; }
+        if (d) { d[2] = 'f'; put_float(d + 3, f); }
+        return 7u;
+    }
+    if (type == 'Z' || type == 'H') {
+        if (d) { d[2] = (uint8_t)type; d[3 + vn] = 0; }
+        return 4u + vn;
+    }
+    if (type != 'B') { why = AMP_SAM_ODD_AUX_TAG; return 0; }
+    if (vn == 0) { why = AMP_SAM_ODD_AUX_B; return 0; }
+    const uint32_t sub = t[vs];
+    int code = -1;                                                  // 0..5: c C s S i I, 6: f
+    for (int k = 0; k < 7; ++k) if (sub == (uint32_t)"cCsSiIf"[k]) code = k;
+    if (code < 0) { why = AMP_SAM_ODD_AUX_B; return 0; }
+    const uint32_t esz = code == 6 ? 4u : int_bytes(code);
+    uint32_t count = 0, p = vs + 1u;
+    while (p < fe) {
+        if (t[p] != ',') { why = AMP_SAM_ODD_AUX_B; return 0; }
+        uint32_t q = ++p;
+        while (q < fe && t[q] != ',') ++q;
+        if (q == p) { why = AMP_SAM_ODD_AUX_B; return 0; }
+        uint8_t *e = d ? d + 8 + (size_t)count * esz : nullptr;
+        if (code == 6) {
+            float f = 0.f;
+            if (!aux_float(t, p, q, f)) { why = AMP_SAM_ODD_AUX_FLOAT; return 0; }
+            if (e) put_float(e, f);
+        } else {
+            int64_t x = 0;
+            if (!aux_int(t, p, q, x)) { why = AMP_SAM_ODD_AUX_B; return 0; }
+            if (!int_fits(code, x)) { why = AMP_SAM_ODD_AUX_B_RANGE; return 0; }
+            if (e) put_int(e, code, x);
+        }
+        ++count; p = q;
+    }
+    if (d) { d[2] = 'B'; d[3] = (uint8_t)sub; o_wr32(d + 4, count); }
+    return 8u + count * esz;
+}
+
+// where the aux field behind tab T of line i ends (the line's tabs are [line_tab0[i], line_tab0[i + 1]))
+AMP_HD uint32_t aux_end(const Buf &b, int64_t i, const Line &ln, uint32_t T) { return T + 1u < b.line_tab0[i + 1] ? b.tab_pos[T + 1u] : ln.end; }
+
+// aux: lane = tab of the chunk.  A tab with number 10 or more in its line opens an aux field: its BAM size, its verdict.
+AMP_HD void lane_aux(const Buf &b, int64_t T) {
+    const uint32_t p = b.tab_pos[T], m = b.mask[p >> 4] & 0xFFFFu;
+    const int64_t i = (int64_t)((uint32_t)b.rank[p >> 4] + (uint32_t)__builtin_popcount(m & ((1u << (p & 15u)) - 1u)));
+    uint32_t sz = 0;
+    if (i < b.line_cap && (uint32_t)T - b.line_tab0[i] >= 10u) {
+        const Line ln = line_of(b, i);
+        int why = 0;
+        sz = aux_conv(b.text, p + 1u, aux_end(b, i, ln, (uint32_t)T), nullptr, why);
+        if (why) { odd(b, i, why); sz = 0; }
+    }
+    b.aux_sz[T] = sz;
+}
+
+// ---- BAM output: the records (AlignmentWriter.write of bamio.py, mode "wb") -----------------------------------------------------
+AMP_HD void lane_bam_size(const Buf &b, int64_t r) {              // r == n_rows: the slot the scan leaves the total in
+    const ampbamout::Out &o = b.o;
+    uint64_t sz = 0;
+    // (the verdict of a deferred amp_sam_process is read where it lies: rows in front of the first failing one)
+    const int64_t good = !b.bad_key ? b.good_rows : *b.bad_key == ~0ull ? o.n_rows : (int64_t)(*b.bad_key >> 8);
+    if (r < o.n_rows && r < good && row_kept(b, r)) {
+        // (the stream has room for three ops more than the line's, and the line has 65,532 at most: see lane_records)
+        if (b.new_ncig[r] > b.cig_off32[r + 1] - b.cig_off32[r] + ampbamout::OUT_SPARE_OPS) AMP_ADD64(&o.octl[ampbamout::OCTL_BAD], 1);
+        else { sz = (uint64_t)b.row_bsz[r] + 4ull * b.new_ncig[r]; AMP_ADD64(&o.octl[ampbamout::OCTL_ROWS], 1); }
+    }
+    o.row_off[r] = sz;
+}
+
+// One wave per kept row.  Lane 0: block_size, the 32 fixed bytes, the new CIGAR words.  The wave: QNAME from the text; packed
+// bases and qualities from the row's slots of the resident batch, where k_sam_pack left them in BAM's own form (nibbles with
+// a zero spare nibble, character - 33, 0xFF for '*') -- (l_seq + 1) / 2 + l_seq bytes to copy instead of 2 l_seq bytes of text
+// to read and map again; aux fields one per lane (64 at a time), the bodies of Z / H strings by the whole wave.
+AMP_HD void lane_bam_record(const Buf &b, int64_t r, uint32_t lane) {
+    const ampbamout::Out &o = b.o;
+    if (o.octl[ampbamout::OCTL_BAD] || o.row_off[r + 1] == o.row_off[r]) return;
+    uint8_t *d = o.stream + o.carry_in + o.row_off[r];
+    const int64_t i = b.row_line[r];
+    const Line ln = line_of(b, i);
+    const uint8_t *t = b.text;
+    uint32_t qs, qe, fs, fe;
+    field(b, i, ln, 0, qs, qe);
+    const uint32_t l_name = qe - qs + 1u, nn = b.new_ncig[r], L = b.lseq[r];
+    if (lane == 0) {
+        const uint32_t *cg = row_new_cig(b, r);
+        int64_t v = 0, rlen = 0;
+        for (uint32_t k = 0; k < nn; ++k) {
+            const uint32_t op = cg[k] & 15u;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += cg[k] >> 4;
+        }
+        const int64_t pos = b.new_pos[r], end = pos + (rlen ? rlen : 1);
+        field(b, i, ln, 2, fs, fe);
+        const int rn = name_id(b, fs, fe);
+        field(b, i, ln, 6, fs, fe);
+        const int rx = (fe - fs == 1 && t[fs] == '=') ? rn : name_id(b, fs, fe);
+        o_wr32(d, b.row_bsz[r] - 4u + 4u * nn);
+        o_wr32(d + 4, (uint32_t)(rn < 0 ? -1 : rn));
+        o_wr32(d + 8, (uint32_t)b.new_pos[r]);
+        d[12] = (uint8_t)l_name;
+        field(b, i, ln, 4, fs, fe); (void)parse_int(t, fs, fe, v); d[13] = (uint8_t)v;
+        o_wr16(d + 14, ampbamout::reg2bin(pos > 0 ? pos : 0, end > 1 ? end : 1));
+        o_wr16(d + 16, nn);
+        o_wr16(d + 18, b.flag[r]);
+        o_wr32(d + 20, L);
+        o_wr32(d + 24, (uint32_t)(rx < 0 ? -1 : rx));
+        field(b, i, ln, 7, fs, fe); (void)parse_int(t, fs, fe, v); o_wr32(d + 28, (uint32_t)(v - 1));
+        o_wr32(d + 32, (uint32_t)b.tlen[r]);
+        d[36 + l_name - 1u] = 0;
+        for (uint32_t k = 0; k < nn; ++k) o_wr32(d + 36 + l_name + 4 * k, cg[k]);
+    }
+    wave_copy(d + 36, t + qs, qe - qs, lane);
+    uint8_t *sq = d + 36 + l_name + 4u * nn;
+    wave_copy(sq, b.seq + 4 * (size_t)b.seq_off8[r], (L + 1u) >> 1, lane);
+    wave_copy(sq + ((L + 1u) >> 1), b.qual + 8 * (size_t)b.seq_off8[r], L, lane);
+    uint8_t *ax = sq + ((L + 1u) >> 1) + L;
+    const uint32_t T0 = b.line_tab0[i] + 10u, T1 = b.line_tab0[i + 1], base = b.aux_sz[T0];
+    for (uint32_t T = T0 + lane; T < T1; T += WAVE) {
+        int why = 0;
+        (void)aux_conv(t, b.tab_pos[T] + 1u, aux_end(b, i, ln, T), ax + (b.aux_sz[T] - base), why);
+    }
+    for (uint32_t T = T0; T < T1; ++T) {
+        const uint32_t as = b.tab_pos[T] + 1u, type = t[as + 3];
+        if (type == 'Z' || type == 'H') wave_copy(ax + (b.aux_sz[T] - base) + 3, t + as + 5u, aux_end(b, i, ln, T) - as - 5u, lane);
+    }
+}
+
 // ---- layout of a chunk's memory ---------------------------------------------------------------------------------------------
 static inline int64_t line_cap_for(int64_t n_bytes) { return n_bytes / 64 + 1024; }       // a record is far longer than 64 bytes; a chunk
                                                                                          // with more lines than this is odd (AMP_SAM_ODD_LINES)
@@ -429,6 +695,11 @@ static size_t carve(Buf &b, uint8_t *base, int64_t cap_bytes) {
     b.cig = (uint32_t *)take((n / 2 + 4) * 4); b.seq = take(n / 2 + 64); b.qual = take(n + 64);
     b.out_off = (uint32_t *)take((LC + 1) * 4); b.cig_tlen = (uint32_t *)take((LC + 1) * 4);
     b.ctl = (unsigned long long *)take(CTL_WORDS * 8);
+    if (b.bam_mode) {                                               // a chunk has fewer tabs than bytes
+        b.tab_cap = cap_bytes + 16;
+        b.tab_pos = (uint32_t *)take(((size_t)b.tab_cap + 1) * 4); b.aux_sz = (uint32_t *)take(((size_t)b.tab_cap + 2) * 4);
+        b.row_bsz = (uint32_t *)take((LC + 1) * 4);
+    }
     return take.o;
 }
 
@@ -445,9 +716,16 @@ CODEC_KERNEL(k_sam_records, lane_records)
 CODEC_KERNEL(k_sam_rows, lane_rows)
 CODEC_KERNEL(k_sam_pack, lane_pack)
 CODEC_KERNEL(k_sam_fmt_len, lane_fmt_len)
+CODEC_KERNEL(k_sam_aux, lane_aux)
+CODEC_KERNEL(k_sam_bam_size, lane_bam_size)
 __global__ void __launch_bounds__(256) k_sam_fmt_copy(Buf b, int64_t n_rows) {      // one wave per row
     const uint32_t lane = threadIdx.x & 63u;
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n_rows; r += (int64_t)gridDim.x * 4) lane_fmt_copy(b, r, lane);
+}
+// One wave per row (four a workgroup), as k_sam_fmt_copy: no LDS, and nothing a lane keeps lives in an array.
+__global__ void __launch_bounds__(256) k_sam_bam_records(Buf b) {
+    const uint32_t lane = threadIdx.x & 63u;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < b.o.n_rows; r += (int64_t)gridDim.x * 4) lane_bam_record(b, r, lane);
 }
 #endif
 CODEC_FIRST_BAD_KERNEL(k_sam_first_bad)
@@ -463,6 +741,13 @@ struct amp_sam {
     bool parsed = false, processed = false;
     int64_t good_rows = 0;
     unsigned long long h_ctl[CTL_WORDS];
+    // trimmed reads as BAM (amp_sam_set_output, amp_sam_encode)
+    bool encoded = false;                             // the rows of the last parse went into the stream
+    bool verdict_pending = false;                     // amp_sam_process was deferred: the first failing row is not known here yet
+    int64_t bad_row = -1; uint8_t bad_status = 0;     // the verdict of the last amp_sam_process
+    unsigned long long h_key = ~0ull;
+    ampbamout::Tail tail;
+    uint64_t h_new_bytes = 0;                         // (amp_sam_encode_bytes: what its one "row" holds, on its way up)
 };
 
 static int sam_ensure(amp_sam *s, int64_t n_bytes) {
@@ -489,6 +774,7 @@ void amp_sam_destroy(amp_sam *s) {
     DevGuard guard(s->sh);
     (void)codec_wait(s->sh);
     codec_free(s->arena); codec_free(s->names); codec_free(s->ref_off); codec_free(s->out);
+    ampbamout::tail_free(s->tail);
     codec_delete(s);
 }
 
@@ -524,7 +810,7 @@ int amp_sam_parse(amp_sam *s, const uint8_t *text, int64_t n_bytes, amp_sam_info
     if (n_bytes && text[n_bytes - 1] != '\n') return AMP_EINVAL;
     if (s->n_ref < 0) return AMP_ESTATE;
     DevGuard guard(s->sh);
-    s->parsed = s->processed = false;
+    s->parsed = s->processed = s->encoded = false;
     amp_sam_info z{};
     z.first_odd_line = -1;
     s->info = *info = z;
@@ -549,6 +835,10 @@ int amp_sam_parse(amp_sam *s, const uint8_t *text, int64_t n_bytes, amp_sam_info
         CODEC_RUN(s, k_sam_lines, lane_lines, S, -1);
         CODEC_RUN(s, k_sam_tabs, lane_tabs, S, -1);
         codec_mark(s->sh, 3);
+        if (b.bam_mode) {
+            CODEC_RUN(s, k_sam_aux, lane_aux, b.tab_cap, CTL_NTABS);
+            CODEC_OK(codec_scan(s->sh, b.aux_sz, b.tab_cap + 1));
+        }
         CODEC_RUN(s, k_sam_records, lane_records, LC, -1);
         CODEC_OK(codec_scan(s->sh, b.s_rec, LC));
         CODEC_OK(codec_scan(s->sh, b.s_row, LC));
@@ -591,8 +881,23 @@ int amp_sam_batch_to_host(amp_sam *s, const amp_reads *dst, int64_t *src_index) 
 static int sam_processed(amp_sam *s, int rc, int64_t bad, int64_t *first_bad_row) {
     if (rc) return rc;
     s->good_rows = bad >= 0 ? bad : s->info.n_rows;
-    s->processed = true;
+    s->bad_row = bad;
+    s->processed = true; s->verdict_pending = false;
     if (first_bad_row) *first_bad_row = bad;
+    return AMP_OK;
+}
+// the key of a deferred amp_sam_process has come down (h_key)
+static void sam_verdict(amp_sam *s) {
+    codec_first_bad_of(s->h_key, &s->bad_row, &s->bad_status);
+    s->good_rows = s->bad_row >= 0 ? s->bad_row : s->info.n_rows;
+    s->verdict_pending = false;
+}
+static int sam_verdict_now(amp_sam *s) {
+    if (!s->verdict_pending) return AMP_OK;
+    DevGuard guard(s->sh);
+    CODEC_OK(codec_down(s->sh, &s->h_key, s->sh.bad_key, 8));
+    CODEC_OK(codec_wait(s->sh));
+    sam_verdict(s);
     return AMP_OK;
 }
 
@@ -602,7 +907,15 @@ int amp_sam_process(amp_sam *s, uint64_t read_base, int64_t *first_bad_row, uint
     if (!s) return AMP_EINVAL;
     if (!s->parsed || s->info.first_odd_line >= 0) return AMP_ESTATE;
     int64_t bad = -1;
-    const int rc = codec_process(s->sh, s->b, s->b, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded, read_base, 6, &bad, its_status);
+    uint8_t st = 0;
+    if (!first_bad_row && !its_status) {              // deferred: amp_sam_encode or amp_sam_first_bad brings the verdict down
+        CODEC_OK(codec_process(s->sh, s->b, s->b, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded, read_base, 6, nullptr, nullptr, true));
+        s->processed = s->verdict_pending = true;
+        return AMP_OK;
+    }
+    const int rc = codec_process(s->sh, s->b, s->b, s->info.n_rows, s->info.n_cig, s->info.n_bases_padded, read_base, 6, &bad, &st);
+    s->bad_status = st;
+    if (its_status) *its_status = st;
     return sam_processed(s, rc, bad, first_bad_row);
 }
 
@@ -621,7 +934,10 @@ int amp_sam_twin_set_results(amp_sam *s, const int32_t *new_pos, const uint32_t 
     memcpy((void *)b.new_cig, new_cig, ((size_t)s->info.n_cig + 3 * n) * 4);
     memcpy((void *)b.trim_flags, trim_flags, n); memcpy((void *)b.status, status, n);
     int64_t bad = -1;
-    const int rc = codec_first_bad(s->sh, s->b, s->info.n_rows, &bad, its_status);
+    uint8_t st = 0;
+    const int rc = codec_first_bad(s->sh, s->b, s->info.n_rows, &bad, &st);
+    s->bad_status = st;
+    if (its_status) *its_status = st;
     return sam_processed(s, rc, bad, first_bad_row);
 }
 #endif
@@ -630,6 +946,7 @@ int amp_sam_twin_set_results(amp_sam *s, const int32_t *new_pos, const uint32_t 
 int amp_sam_format(amp_sam *s, int32_t min_length, int32_t include_no_primer, uint8_t *out, int64_t cap, int64_t *n_bytes, int64_t *n_rows_written) {
     if (!s || !n_bytes || cap < 0 || (cap && !out)) return AMP_EINVAL;
     if (!s->parsed || !s->processed) return AMP_EINVAL;
+    CODEC_OK(sam_verdict_now(s));
     DevGuard guard(s->sh);
     Buf &b = s->b;
     const int64_t n = s->info.n_rows;
@@ -660,5 +977,106 @@ int amp_sam_format(amp_sam *s, int32_t min_length, int32_t include_no_primer, ui
     codec_mark(s->sh, 10);
     return codec_wait(s->sh);
 }
+
+// ---- trimmed reads as BAM -----------------------------------------------------------------------------------
+// what the trimmed reads of the run are written as; before the first parse (the tables of a chunk depend on it)
+int amp_sam_set_output(amp_sam *s, int32_t mode) {
+    if (!s || (mode != AMP_SAM_OUT_TEXT && mode != AMP_SAM_OUT_BAM)) return AMP_EINVAL;
+    if ((mode == AMP_SAM_OUT_BAM) == (s->b.bam_mode != 0)) return AMP_OK;
+    DevGuard guard(s->sh);
+    CODEC_OK(codec_sync(s->sh));
+    s->b.bam_mode = mode == AMP_SAM_OUT_BAM ? 1 : 0;
+    s->cap_bytes = 0;                                 // the next parse carves its memory anew
+    s->parsed = s->processed = false;
+    return AMP_OK;
+}
+
+static int sam_out_records(amp_sam *s) {
+#ifndef AMPSAM_HOSTSIM
+    if (s->b.o.n_rows > 0) {
+        k_sam_bam_records<<<codec_grid(s->b.o.n_rows * 64), 256, 0, s->sh.stream>>>(s->b);
+        if (hipGetLastError() != hipSuccess) return AMP_EHIP;
+    }
+#else
+    for (int64_t r = 0; r < s->b.o.n_rows; ++r) for (uint32_t lane = 0; lane < WAVE; ++lane) lane_bam_record(s->b, r, lane);
+#endif
+    return AMP_OK;
+}
+
+// AlignmentWriter(mode="wb").write(r, pos=, cigar=) + BgzfWriter for the kept rows of the last parse (none when they were encoded
+// already, or the chunk was odd: a bare flush)
+int amp_sam_encode(amp_sam *s, int32_t min_length, int32_t include_no_primer, int32_t final, amp_bam_out_info *info) {
+    if (!s || !info) return AMP_EINVAL;
+    if (!s->b.bam_mode) return AMP_ESTATE;
+    const bool fresh = s->parsed && !s->encoded && s->info.first_odd_line < 0;
+    const int64_t n_rows = fresh ? s->info.n_rows : 0;
+    if (n_rows && !s->processed) return AMP_ESTATE;
+    DevGuard guard(s->sh);
+    const int64_t waits0 = s->sh.waits;
+    Buf &b = s->b;
+    // the new records: the rows' sizes without their CIGARs came down with the parse, a new CIGAR has three ops more at most
+    const int64_t new_bytes = n_rows ? (int64_t)s->h_ctl[CTL_BAM_BYTES] + 4 * (s->info.n_cig + (int64_t)ampbamout::OUT_SPARE_OPS * n_rows) : 0;
+    CODEC_OK(ampbamout::tail_begin(s->sh, s->tail, b.o, n_rows, new_bytes, final, 11));
+    const bool pending = n_rows && s->verdict_pending;
+    b.min_length = min_length; b.include_no_primer = include_no_primer ? 1 : 0; b.good_rows = n_rows ? s->good_rows : 0;
+    b.bad_key = pending ? s->sh.bad_key : nullptr;
+    if (pending) { b.good_rows = n_rows; CODEC_OK(codec_down(s->sh, &s->h_key, s->sh.bad_key, 8)); }      // (down with the encode's wait)
+    if (n_rows) {
+        CODEC_RUN(s, k_sam_bam_size, lane_bam_size, n_rows + 1, -1);
+        CODEC_OK(codec_scan(s->sh, b.o.row_off, n_rows + 1));
+    }
+    CODEC_OK(ampbamout::tail_plan<amp_sam>(s->sh, b.o));
+    CODEC_OK(sam_out_records(s));
+    const int rc = ampbamout::tail_finish<amp_sam>(s->sh, s->tail, b.o, 11, waits0, info);
+    if (pending && rc != AMP_EHIP) sam_verdict(s);    // (the wait was reached: the key is here)
+    if (rc) return rc;
+    if (fresh) s->encoded = true;
+    return AMP_OK;
+}
+
+// the verdict of the last amp_sam_process: *first_bad_row = the first row whose status is not AMP_RS_OK and *its_status that
+// status, -1 and 0 when there is none.  Waits only when the process was deferred and no encode has brought the verdict down.
+int amp_sam_first_bad(amp_sam *s, int64_t *first_bad_row, uint8_t *its_status) {
+    if (!s) return AMP_EINVAL;
+    if (!s->parsed || !s->processed) return AMP_ESTATE;
+    CODEC_OK(sam_verdict_now(s));
+    if (first_bad_row) *first_bad_row = s->bad_row;
+    if (its_status) *its_status = s->bad_status;
+    return AMP_OK;
+}
+
+// waits for the device since the amp_sam was made (growth of a buffer does not count): tests and tools
+int64_t amp_sam_waits(amp_sam *s) { return s ? s->sh.waits : -1; }
+
+// the same tail over [carry | n record bytes made on the host]: how a chunk that went through the Python codec joins the stream
+int amp_sam_encode_bytes(amp_sam *s, const uint8_t *bytes, int64_t n, int32_t final, amp_bam_out_info *info) {
+    if (!s || !info || n < 0 || n >= (1ll << 31) || (n && !bytes)) return AMP_EINVAL;
+    if (!s->b.bam_mode) return AMP_ESTATE;
+    DevGuard guard(s->sh);
+    const int64_t waits0 = s->sh.waits;
+    ampbamout::Out &o = s->b.o;
+    CODEC_OK(ampbamout::tail_begin(s->sh, s->tail, o, 0, n, final, 11));
+    s->h_new_bytes = (uint64_t)n;
+    CODEC_OK(codec_up(s->sh, o.stream + o.carry_in, bytes, (size_t)n));
+    CODEC_OK(codec_up(s->sh, o.row_off, &s->h_new_bytes, 8));
+    CODEC_OK(ampbamout::tail_plan<amp_sam>(s->sh, o));
+    return ampbamout::tail_finish<amp_sam>(s->sh, s->tail, o, 11, waits0, info);
+}
+
+// the framed blocks, the blocks' sizes and the uncompressed stream of the last encode, as their amp_bam_* siblings
+int amp_sam_encoded_to_host(amp_sam *s, uint8_t *dst, int64_t cap) { return s ? ampbamout::tail_encoded_to_host(s->sh, s->tail, s->b.o, dst, cap, 15) : AMP_EINVAL; }
+int amp_sam_encoded_blocks(amp_sam *s, uint32_t *blk_len, int64_t cap) { return s ? ampbamout::tail_encoded_blocks(s->sh, s->tail, s->b.o, blk_len, cap) : AMP_EINVAL; }
+int amp_sam_stream_to_host(amp_sam *s, int64_t from, int64_t n, uint8_t *dst) { return s ? ampbamout::tail_stream_to_host(s->sh, s->tail, s->b.o, from, n, dst) : AMP_EINVAL; }
+
+#ifdef AMPSAM_HOSTSIM
+// Entry points of the host twin alone (not part of include/amplihip.h): the DEFLATE encoder of its encodes (amp_deflate.hip's host
+// phases, ampdf_hostsim_blocks), and the guard bytes behind the encoder's buffers (0: untouched, else 1 + the buffer's number)
+int amp_sam_twin_set_deflater(amp_sam *s, amp_bam_twin_deflate_fn fn) {
+    if (!s) return AMP_EINVAL;
+    s->tail.twin_deflate = fn;
+    return AMP_OK;
+}
+int amp_sam_twin_guards(amp_sam *s) { return s ? ampbamout::tail_guards(s->tail) : AMP_EINVAL; }
+#endif
 
 }  // extern "C"

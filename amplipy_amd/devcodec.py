@@ -1,19 +1,42 @@
 """What the device codecs of libamplihip.so share on the Python side (sam_native / amp_sam_*, bam_device / amp_bam_*; the C
-half is amplipy_amd/csrc/amp_codec.hpp): the binding of the entry points every codec has, the build of a host twin, and the
-thread that reads one piece ahead of the consumer."""
+half is amplipy_amd/csrc/amp_codec.hpp and, for trimmed BAM out of either codec, amp_bamtail.hpp): the binding of the entry points
+every codec has, the build of a host twin, and the thread that reads one piece ahead of the consumer."""
 from __future__ import annotations
 
 import ctypes as C
 import os
 import queue
 import shutil
+import struct
 import subprocess
 import threading
+import zlib
 
 import numpy as np
 
 from . import abi
 from .batch import ReadBatch
+
+
+OUT_BS = 0xFF00                    # uncompressed bytes of a BGZF block of the trimmed output (the host writer's)
+
+
+class AmpBamOutInfo(C.Structure):
+    """amp_bam_out_info: what amp_bam_encode and amp_sam_encode answer."""
+    _fields_ = [(n, C.c_int64) for n in ("n_rows_written", "stream_bytes", "carry_in", "carry_out", "n_blocks", "file_bytes", "n_blocks_host",
+                                         "waits", "bytes_down")]
+
+
+# amp_bam_twin_deflate_fn of amp_bamout.hpp
+TWIN_DEFLATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_uint32))
+
+
+def bgzf_block(data, level=6):
+    """One BGZF block of ``data`` (at most 0xFF00 bytes) made on the host: zlib's stream, the framing of flush_blocks."""
+    co = zlib.compressobj(level, zlib.DEFLATED, -15)
+    comp = co.compress(data) + co.flush()
+    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(comp) + 25) + comp
+            + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
 
 
 def build_twin(source, define, out_path, sanitize=False, main_source=None):
@@ -118,6 +141,46 @@ class DeviceCodec:
         self._chk(self._fn("process")(self.h, C.c_uint64(read_base), C.byref(bad), C.byref(st)), self.prefix + "_process")
         self.first_bad = int(bad.value)
         return int(bad.value), int(st.value)
+
+    # ---- trimmed BAM out of the codec (amp_bam_encode / amp_sam_encode and the tail they share) --------------------------------
+    def set_deflater(self, fn):
+        """Twin only: the DEFLATE encoder of its encodes -- the address of ampdf_hostsim_blocks (amp_deflate.hip's host phases), or a
+        TWIN_DEFLATE_FN object."""
+        self._deflater = fn
+        self._chk(self._fn("twin_set_deflater")(self.h, fn), self.prefix + "_twin_set_deflater")
+
+    def guards_ok(self):
+        """Twin only: no encode so far wrote behind one of its buffers."""
+        return int(self._fn("twin_guards")(self.h)) == 0
+
+    def _encoded(self, info):
+        """The BGZF blocks of the encode that answered ``info``, as they go into the file.  A block whose stream did not fit comes
+        down raw and is compressed here (info.n_blocks_host counts it; never on real data)."""
+        self.out_info = info
+        out = np.empty(max(int(info.file_bytes), 1), np.uint8)
+        if info.file_bytes:
+            self._chk(self._fn("encoded_to_host")(self.h, C.c_void_p(abi.ptr(out)), C.c_int64(out.size)), self.prefix + "_encoded_to_host")
+        out = out[:int(info.file_bytes)]
+        if info.n_blocks_host:
+            lens = np.zeros(int(info.n_blocks), np.uint32)
+            self._chk(self._fn("encoded_blocks")(self.h, C.c_void_p(abi.ptr(lens)), C.c_int64(lens.size)), self.prefix + "_encoded_blocks")
+            enc = int(info.stream_bytes) - int(info.carry_out)
+            parts, at = [], 0
+            for k, n in enumerate(int(x) for x in lens):
+                if n:
+                    parts.append(out[at:at + n].tobytes()); at += n
+                else:
+                    parts.append(bgzf_block(self.stream(k * OUT_BS, min(OUT_BS, enc - k * OUT_BS)).tobytes()))
+                    info.bytes_down += min(OUT_BS, enc - k * OUT_BS)
+            out = np.frombuffer(b"".join(parts), np.uint8)
+        return out, info
+
+    def stream(self, start=0, n=None):
+        """Bytes [start, start + n) of the uncompressed stream [carry | new records] of the last encode (n None: to its end)."""
+        n = int(self.out_info.stream_bytes) - start if n is None else n
+        buf = np.zeros(max(n, 1), np.uint8)
+        self._chk(self._fn("stream_to_host")(self.h, C.c_int64(start), C.c_int64(n), C.c_void_p(abi.ptr(buf))), self.prefix + "_stream_to_host")
+        return buf[:n]
 
     def stage_ms(self, on=True, read=True):
         ms = (C.c_float * self.n_stages)(*([-1.0] * self.n_stages))

@@ -34,6 +34,8 @@ EXPORTS = [
     "amp_bam_create", "amp_bam_destroy", "amp_bam_feed", "amp_bam_dev_refuse", "amp_bam_refused", "amp_bam_patch_block", "amp_bam_reindex",
     "amp_bam_reads", "amp_bam_batch_to_host", "amp_bam_image_to_host", "amp_bam_process", "amp_bam_stage_ms",
     "amp_bam_encode", "amp_bam_encoded_to_host", "amp_bam_encoded_blocks", "amp_bam_stream_to_host",
+    "amp_sam_set_output", "amp_sam_encode", "amp_sam_encode_bytes", "amp_sam_encoded_to_host", "amp_sam_encoded_blocks", "amp_sam_stream_to_host",
+    "amp_sam_first_bad", "amp_sam_waits",
 ]
 
 

@@ -411,9 +411,23 @@ int amp_deflate_blocks_cb(void *user, const uint8_t *in, int64_t n_bytes, int32_
 #define AMP_SAM_ODD_QUAL_LEN 10    /* QUAL given, its length is not SEQ's */
 #define AMP_SAM_ODD_QUAL_CHAR 11   /* a QUAL character below '!' */
 #define AMP_SAM_ODD_LINES 12       /* more lines than the line tables hold (n_bytes / 64 + 1024): not SAM records */
+/* ... and, with BAM output only (amp_sam_set_output), what aux_sam_to_bam / struct.pack would not turn into the
+ * bytes the device makes; of several such faults on one line the smallest number is reported: */
+#define AMP_SAM_ODD_QNAME 13       /* QNAME longer than 254 bytes (l_read_name is one byte) */
+#define AMP_SAM_ODD_AUX_TAG 14     /* an aux field that is not ^[!-~]{2}:[AifZHB]: */
+#define AMP_SAM_ODD_AUX_A 15       /* A whose value is not exactly one byte */
+#define AMP_SAM_ODD_AUX_INT 16     /* i that is not -?(0|[1-9][0-9]*) */
+#define AMP_SAM_ODD_AUX_INT_RANGE 17  /* i outside [-2^31, 2^32 - 1] */
+#define AMP_SAM_ODD_AUX_B 18       /* B that is not [cCsSiIf](,value)* */
+#define AMP_SAM_ODD_AUX_B_RANGE 19 /* an element of B outside its subtype's range */
+#define AMP_SAM_ODD_AUX_FLOAT 20   /* f, or an element of B:f, not -?digits[.digits][e[+-]digits] with at most 15 significant digits
+                                    * and a power of ten (the fraction folded in) within +-22 */
+#define AMP_SAM_ODD_CIGAR_OPS 21   /* more than 65,532 CIGAR ops: the trimmed CIGAR (three more at most) might not fit n_cigar_op */
 #define AMP_SAM_MAX_REFS 64        /* @SQ names the device table holds; a header with more keeps the run on the Python codec */
 #define AMP_SAM_MAX_REF_BYTES 4096 /* ... and their bytes */
-#define AMP_SAM_N_STAGES 10
+#define AMP_SAM_N_STAGES 15
+#define AMP_SAM_OUT_TEXT 0
+#define AMP_SAM_OUT_BAM 1
 
 typedef struct amp_sam amp_sam;
 typedef struct amp_sam_info {
@@ -437,8 +451,15 @@ int amp_sam_reads(amp_sam *s, amp_dev_reads *out);
  * the number of each row's record among the chunk's records (ReadBatch.src_index): tests and tools. */
 int amp_sam_batch_to_host(amp_sam *s, const amp_reads *dst, int64_t *src_index);
 /* A:896-915 for the chunk: amp_process_batch_device on the batch, the result arrays owned by s.  *first_bad_row = the first
- * row whose status is not AMP_RS_OK and *its_status that status; -1 and 0 when there is none.  AMP_ESTATE for an odd chunk. */
+ * row whose status is not AMP_RS_OK and *its_status that status; -1 and 0 when there is none.  AMP_ESTATE for an odd chunk.
+ * With both pointers NULL the call is DEFERRED: the pass is enqueued, nothing is waited for, and the verdict stays on the device
+ * until amp_sam_encode brings it down with its own wait (or amp_sam_first_bad / amp_sam_format with one of theirs). */
 int amp_sam_process(amp_sam *s, uint64_t read_base, int64_t *first_bad_row, uint8_t *its_status);
+/* The verdict of the last amp_sam_process, deferred or not. */
+int amp_sam_first_bad(amp_sam *s, int64_t *first_bad_row, uint8_t *its_status);
+/* Waits for the device since the amp_sam was made (a parse costs one, a process that is not deferred one, a format two, an encode
+ * one): tests and tools. */
+int64_t amp_sam_waits(amp_sam *s);
 /* AlignmentWriter.write(r, pos=, cigar=) (out_aln.write, A:911) for every row in front of the first failing one that passes
  * ref_len >= min_length and (trimmed at a primer or include_no_primer) (A:910): the input line with field 4 = new_pos + 1,
  * field 6 = the new CIGAR, a '\r' before the '\n' dropped.  AMP_EOVERFLOW with *n_bytes = the size needed when cap is
@@ -446,8 +467,9 @@ int amp_sam_process(amp_sam *s, uint64_t read_base, int64_t *first_bad_row, uint
 int amp_sam_format(amp_sam *s, int32_t min_length, int32_t include_no_primer, uint8_t *out, int64_t cap, int64_t *n_bytes,
                    int64_t *n_rows_written);
 /* Development aid: ms[AMP_SAM_N_STAGES] of the last chunk from HIP events on the ctx stream -- [0] copy up, [1] scan and
- * ranks, [2] lines and tabs, [3] records and rows, [4] pack, [6] the read pass, [8] format kernels, [9] copy down ([5], [7]:
- * host time between the calls).  on != 0 records the events from the next call on. */
+ * ranks, [2] lines and tabs, [3] records and rows (with BAM output: aux sizes too), [4] pack, [6] the read pass, [8] format kernels,
+ * [9] copy down, [11] BAM records, [12] their DEFLATE, [13] CRC and framing, [14] copy down ([5], [7], [10]: host time between the
+ * calls; a stage that did not run reads -1).  on != 0 records the events from the next call on. */
 int amp_sam_stage_ms(amp_sam *s, int on, float *ms);
 
 /* ---- BAM input on the device (opt-in codec of the command line: AMPLIPY_GPU_BAM=1) ---------------------
@@ -547,6 +569,27 @@ int amp_bam_encoded_to_host(amp_bam *s, uint8_t *dst, int64_t cap);
 int amp_bam_encoded_blocks(amp_bam *s, uint32_t *blk_len, int64_t cap);
 /* n bytes from offset `from` of the uncompressed stream of the last encode: tests, and the chunks of blocks handed to the host. */
 int amp_bam_stream_to_host(amp_bam *s, int64_t from, int64_t n, uint8_t *dst);
+
+/* ---- SAM text in, trimmed BAM out (opt-in: AMPLIPY_GPU_SAM=1 with AMPLIPY_GPU_BAM_WRITE=1) ---------------
+ * The Python codec writes a trimmed read with AlignmentWriter(mode="wb").write(r, pos=, cigar=): the record packed with struct,
+ * aux fields through aux_sam_to_bam, 0xFF00-byte chunks of the record stream compressed by BgzfWriter.  With BAM output an
+ * amp_sam makes the same record bytes in HBM from the line's text, the resident batch and the results of amp_sam_process, and
+ * hands the stream to the tail amp_bam_encode uses (carry, DEFLATE, CRC-32, framing, gather): amp_bam_out_info and the three
+ * copies below mean what they mean there.  More lines are odd with BAM output (AMP_SAM_ODD_QNAME and following): the device never
+ * emits what the Python codec would not.  The caller sends the records of such a chunk, made by the Python codec, through
+ * amp_sam_encode_bytes, so the stream and its block boundaries do not depend on which side encoded a chunk. */
+/* AMP_SAM_OUT_TEXT (the default) or AMP_SAM_OUT_BAM; once per run, before the first parse. */
+int amp_sam_set_output(amp_sam *s, int32_t mode);
+/* The kept rows of the last parse (A:910, rows in front of the first failing one) behind the bytes the call before left over; a
+ * call without a fresh, processed, non-odd chunk behind it appends nothing (with final: the bare flush).  One wait per call, which
+ * also brings the verdict of a deferred amp_sam_process down: a chunk then costs two waits, the parse's and this one.
+ * AMP_ESTATE without BAM output, or when the chunk has rows and amp_sam_process has not run. */
+int amp_sam_encode(amp_sam *s, int32_t min_length, int32_t include_no_primer, int32_t final, amp_bam_out_info *info);
+/* n < 2^31 bytes of BAM records made on the host appended in the same way (n_rows_written stays 0).  One wait per call. */
+int amp_sam_encode_bytes(amp_sam *s, const uint8_t *bytes, int64_t n, int32_t final, amp_bam_out_info *info);
+int amp_sam_encoded_to_host(amp_sam *s, uint8_t *dst, int64_t cap);
+int amp_sam_encoded_blocks(amp_sam *s, uint32_t *blk_len, int64_t cap);
+int amp_sam_stream_to_host(amp_sam *s, int64_t from, int64_t n, uint8_t *dst);
 
 #ifdef __cplusplus
 }
