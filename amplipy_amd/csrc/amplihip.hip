@@ -18,6 +18,7 @@
 
 #include "../../include/amplihip.h"
 #include "amp_read.hpp"
+#include "amp_call.hpp"
 #include "amp_tile.hpp"
 #include "amp_fast.hpp"
 #include "amp_fast5.hpp"
@@ -660,9 +661,8 @@ __global__ void k_add_u32(uint32_t *dst, const uint32_t *src, int64_t n) {
 }
 
 // Calling (A:756-771 alleles_from_counts + A:917-952), one lane per reference position.
-// Everything that does not depend on the TEXT of an insertion allele is decided here: total
-// depth, the six base symbols ranked like sorted(..., reverse=True) (count descending, ties by
-// symbol descending: 'T' > 'N' > 'G' > 'C' > 'A' > '-'), consensus symbol, variant record.
+// Everything that does not depend on the TEXT of an insertion allele is decided here, by call_position (amp_call.hpp):
+// total depth, the six base symbols ranked like sorted(..., reverse=True), consensus symbol, variant record.
 // An insertion string can only matter when the position's insertion events could out-rank
 // the best base symbol or reach the variant frequency threshold; such positions are flagged
 // AMP_CALL_INS_RELEVANT and finished by the host from the event list.
@@ -674,47 +674,11 @@ k_call(const uint32_t *__restrict__ counts, const uint32_t *__restrict__ ins_at,
     int32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = p < ref_len;
     if (!live) p = ref_len - 1;            // keep the whole block alive for the block-level counts
-    const int desc[6] = {3, 4, 2, 1, 0, 5};            // T N G C A -
-    const char sym_of[6] = {'A', 'C', 'G', 'T', 'N', '-'};
-    uint32_t c[6], idx[6];
-    uint64_t total = ins_at[p];
-    for (int k = 0; k < 6; ++k) { idx[k] = desc[k]; c[k] = counts[(size_t)p * AMP_NSYM + desc[k]]; total += c[k]; }
-    for (int a = 1; a < 6; ++a) {                      // stable: ties keep the symbol order
-        uint32_t cv = c[a], iv = idx[a];
-        int b = a - 1;
-        while (b >= 0 && c[b] < cv) { c[b + 1] = c[b]; idx[b + 1] = idx[b]; --b; }
-        c[b + 1] = cv; idx[b + 1] = iv;
-    }
-    uint32_t order = 0, nnz = 0;
-    for (int k = 0; k < 6; ++k) { order |= idx[k] << (3 * k); nnz += c[k] != 0; }
-    amp_pos_call o;
-    o.total_depth = (uint32_t)total;
-    o.order = order | (nnz << 18);
-    o.consensus_sym = -1;
-    o.flags = 0; o.alt_mask = 0; o.ref_count = 0;
-    const uint32_t ins = ins_at[p];
-    const double dtot = (double)total;
-    bool relevant = false;
-    if (ins) {
-        relevant = pr.full_ranking != 0 || ins >= c[0];
-        if (pr.run_variants && (double)ins / dtot >= pr.min_freq_variants) relevant = true;
-    }
-    if (pr.run_consensus && nnz && (int64_t)c[0] >= (int64_t)pr.min_depth_consensus &&
-        (double)c[0] / dtot >= pr.min_freq_consensus) o.consensus_sym = (int8_t)idx[0];       // A:928-929
-    if (pr.run_variants) {                                                                     // A:933-951
-        const char rs = (char)ref[p];
-        uint32_t rc = 0; double rf = 0.0; uint32_t n_alt = 0, altm = 0;
-        for (int k = 0; k < 6; ++k) {
-            if (!c[k]) continue;
-            double f = (double)c[k] / dtot;
-            if (sym_of[idx[k]] == rs) { rc = c[k]; rf = f; }
-            else if (f >= pr.min_freq_variants) { altm |= 1u << k; ++n_alt; }
-        }
-        o.ref_count = rc; o.alt_mask = (uint8_t)altm;
-        if ((int64_t)total >= (int64_t)pr.min_depth_variants && n_alt) o.flags |= AMP_CALL_VARIANT;
-        if ((int64_t)rc >= (int64_t)pr.min_depth_variants && rf >= pr.min_freq_variants) o.flags |= AMP_CALL_GT_HAS_REF;
-    }
-    if (relevant) { o.flags |= AMP_CALL_INS_RELEVANT; if (n_relevant && live) atomicAdd(n_relevant, 1ull); }
+    uint32_t cnt[6];
+    for (int k = 0; k < 6; ++k) cnt[k] = counts[(size_t)p * AMP_NSYM + k];
+    bool relevant;
+    const amp_pos_call o = call_position(cnt, ins_at[p], ref + p, pr, relevant);   // amp_call.hpp
+    if (relevant && n_relevant && live) atomicAdd(n_relevant, 1ull);
     if (live) out[p] = o;
     if (blk) {   // records per 256-position block, for k_call_compact
         const bool isr = live && relevant, isv = live && !relevant && (o.flags & AMP_CALL_VARIANT);

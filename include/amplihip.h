@@ -302,7 +302,7 @@ typedef struct amp_call_params {
 #define AMP_CALL_INS_RELEVANT 4u /* insertion alleles may change this position's outcome */
 
 typedef struct amp_pos_call {
-    uint32_t total_depth; /* :767 */
+    uint32_t total_depth; /* :767; 32-bit: the counts of a position, insertion events included, must sum below 2^32 */
     uint32_t ref_count;   /* count of the reference symbol (:937); 0 when it is not one of A C G T N - */
     uint32_t order;       /* bits 3k..3k+2: column (A C G T N - = 0..5) of the k-th ranked base symbol;
                              bits 18..20: number of base symbols with a non-zero count */

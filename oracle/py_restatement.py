@@ -10,6 +10,10 @@ lazily instead of being materialised.
 
 process(batch, ref_len, min_start, max_end, max_primer_len, min_quality, window) -> uint32[ref_len][6]
 (insertion events are returned by process_full).  Reads outside the reference's domain raise like it does.
+
+alleles_from_counts / call_positions restate the calling step (A:756-771, A:917-952) over one {symbol or insertion
+string: count} dict per reference position: Python ints, Python true division, Python tuple order.  They are what the
+device's per-position decision (amp_call.hpp) and the host finish (amplipy_amd/calling.py) are compared with.
 """
 from __future__ import annotations
 
@@ -282,3 +286,52 @@ def process_full(batch, ref_len, min_start, max_end, max_primer_len, min_quality
 
 def process(batch, ref_len, min_start, max_end, max_primer_len, min_quality=20, window=4):
     return process_full(batch, ref_len, min_start, max_end, max_primer_len, min_quality, window)[0]
+
+
+def alleles_from_counts(symbol_counts):
+    """A:756-771: (depth, [(count, count / depth, symbol)] best first) of one position's {symbol: count}.  The order is
+    Python's own over the tuples: count, then frequency (equal where the counts are), then the symbol as a string."""
+    depth = sum(symbol_counts.values())
+    if depth == 0:
+        return 0, []
+    present = [(n, n / depth, sym) for sym, n in symbol_counts.items() if n != 0]
+    return depth, sorted(present, reverse=True)
+
+
+def call_positions(ref_seq, tables, params):
+    """A:917-952 for every position of ``ref_seq``.  ``tables[p]``: {symbol or insertion string: count};  ``params``: a
+    mapping with min_depth_consensus, min_freq_consensus, min_depth_variants, min_freq_variants and, optionally,
+    run_consensus / run_variants (both on when absent).
+    -> one (consensus or None, record or None, depth, ranked) per position; a record holds ref, alts, DP, REF_DP,
+    ALT_DP, REF_FREQ, ALT_FREQ, GT with the two joined strings built as A:944 / A:946 build them and REF_FREQ as
+    float.hex() (it is an int 0 in the reference when the reference symbol was not seen)."""
+    want_cons = bool(params.get("run_consensus", True))
+    want_vars = bool(params.get("run_variants", True))
+    depth_c, freq_c = params["min_depth_consensus"], params["min_freq_consensus"]
+    depth_v, freq_v = params["min_depth_variants"], params["min_freq_variants"]
+    out = []
+    for p, ref_symbol in enumerate(ref_seq):
+        depth, ranked = alleles_from_counts(tables[p])
+        consensus = None
+        if want_cons and ranked:
+            n, f, sym = ranked[0]
+            if n >= depth_c and f >= freq_c:                                   # A:928
+                consensus = sym
+        record = None
+        if want_vars:
+            seen = 0
+            ref_n, ref_f = 0, 0
+            alts = []
+            for n, f, sym in ranked:                                            # A:934-939
+                seen += n
+                if sym == ref_symbol:
+                    ref_n, ref_f = n, f
+                elif f >= freq_v:
+                    alts.append((sym, n, f))
+            if seen >= depth_v and alts:                                        # A:940
+                first = 0 if (ref_n >= depth_v and ref_f >= freq_v) else 1      # A:948-951
+                record = {"ref": ref_symbol, "alts": [a[0] for a in alts], "DP": depth, "REF_DP": ref_n,
+                          "ALT_DP": ",".join(str(a[1]) for a in alts), "REF_FREQ": float(ref_f).hex(),
+                          "ALT_FREQ": ",".join(str(a[2]) for a in alts), "GT": list(range(first, len(alts) + 1))}
+        out.append((consensus, record, depth, ranked))
+    return out

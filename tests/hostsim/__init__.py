@@ -3,6 +3,9 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
+from amplipy_amd import abi
 from oracle import oracle
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -14,7 +17,7 @@ def lib():
     if _LIB is None:
         so = os.path.join(_HERE, "libhostsim.so")
         src = os.path.join(_HERE, "hostsim.hip")
-        hdrs = [os.path.join(_HERE, "..", "..", "amplipy_amd", "csrc", h) for h in ("amp_read.hpp", "amp_bf.hpp", "amp_plan.hpp")]
+        hdrs = [os.path.join(_HERE, "..", "..", "amplipy_amd", "csrc", h) for h in ("amp_read.hpp", "amp_bf.hpp", "amp_plan.hpp", "amp_call.hpp")]
         if not os.path.isfile(so) or os.path.getmtime(so) < max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in hdrs]):
             subprocess.check_call(["hipcc", "-O1", "-fPIC", "-shared", "--offload-arch=gfx950", "-o", so, src])
         _LIB = C.CDLL(so)
@@ -54,3 +57,20 @@ def regops_fuzz(seed, iters):
     ne, nr = C.c_long(0), C.c_long(0)
     bad = L.sim_regops_fuzz(C.c_uint64(seed), C.c_long(iters), C.byref(ne), C.byref(nr))
     return int(bad), int(ne.value), int(nr.value)
+
+
+def call_positions(counts, ins_at, ref_seq, params):
+    """The per-position decision of k_call (amp_call.hpp) on the CPU -> (POS_CALL_DTYPE[ref_len], n_relevant), the shape of
+    Engine.call_positions.  ``ref_seq`` may be None when params.run_variants is 0."""
+    L = lib()
+    L.sim_call_positions.restype = C.c_int
+    c = np.ascontiguousarray(counts, np.uint32); ia = np.ascontiguousarray(ins_at, np.uint32)
+    G = ia.size
+    assert c.size == G * abi.NSYM
+    ref = None if ref_seq is None else np.frombuffer(ref_seq.encode("ascii"), np.uint8)
+    assert ref is None or ref.size == G
+    out = np.zeros(G, abi.POS_CALL_DTYPE); nr = C.c_int64(0)
+    rc = L.sim_call_positions(C.c_void_p(abi.ptr(c)), C.c_void_p(abi.ptr(ia)), C.c_void_p(abi.ptr(ref)), C.c_int32(G),
+                              C.byref(params), C.c_void_p(abi.ptr(out)), C.byref(nr))
+    assert rc == 0
+    return out, int(nr.value)

@@ -1,6 +1,7 @@
 // hostsim -- TEST INFRASTRUCTURE.  Runs the per-read device functions of
-// amplipy_amd/csrc/amp_read.hpp on the CPU so that their logic can be checked against the
-// golden vectors in a container without a GPU.  Never loaded by the amplipy_amd package
+// amplipy_amd/csrc/amp_read.hpp and the per-position decision of calling (amp_call.hpp) on the
+// CPU so that their logic can be checked against the golden vectors and a plain restatement in
+// a container without a GPU.  Never loaded by the amplipy_amd package
 // and not a fallback: the product library has no host execution path.
 #include <stdio.h>
 #include <stdlib.h>
@@ -10,6 +11,7 @@
 
 #include "../../amplipy_amd/csrc/amp_read.hpp"
 #include "../../amplipy_amd/csrc/amp_bf.hpp"
+#include "../../amplipy_amd/csrc/amp_call.hpp"
 
 using namespace amp;
 
@@ -63,6 +65,23 @@ extern "C" int sim_process_range(int32_t min_quality, int32_t window, int32_t do
     return 0;
 }
 extern "C" void sim_free(void *p) { free(p); }
+
+// The per-position decision of k_call (amp_call.hpp) looped over the reference on the CPU: the same records and the same
+// count of insertion-relevant positions as amp_call_positions.  ref may be null when run_variants is 0.
+extern "C" int sim_call_positions(const uint32_t *counts, const uint32_t *ins_at, const uint8_t *ref, int32_t ref_len,
+                                  const amp_call_params *pr, amp_pos_call *out, int64_t *n_relevant) {
+    int64_t nr = 0;
+    for (int32_t p = 0; p < ref_len; ++p) {
+        uint32_t cnt[6];
+        for (int k = 0; k < 6; ++k) cnt[k] = counts[(size_t)p * AMP_NSYM + k];
+        bool relevant;
+        out[p] = call_position(cnt, ins_at[p], ref + p, *pr, relevant);
+        out[p].pad = 0;
+        nr += relevant;
+    }
+    if (n_relevant) *n_relevant = nr;
+    return 0;
+}
 
 
 // ---- fuzz of the two-segment closed forms (Cig2) against the generic trim code ------------------------------
