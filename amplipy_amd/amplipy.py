@@ -266,6 +266,40 @@ def open_device_bam_write(input_fn, output_fn):
     return src, bam_device.DeviceBamOutput(output_fn, hdr.text, src.references, level=int(os.environ.get("AMPLIPY_BAM_LEVEL", "-1")))
 
 
+def open_device_bam_text(input_fn, output_fn):
+    """(bam_device.DeviceBamInput, AlignmentWriter, binary output) when the device codec for BAM input can write this run's trimmed
+    reads as SAM text: an existing BAM file in, under the conditions of open_device_bam, and stdout or a new
+    .sam file out; a header of plain ASCII text whose @SQ names fit the device's name table (the test open_native_sam applies).
+    None otherwise: the other codecs serve (and refuse) the run as before, with their own messages.  The header goes out through
+    the text layer as in open_native_sam; the writer is the Python codec's, for the pieces the device hands back."""
+    import io
+    if open_device_bam(input_fn) is None or output_fn is None:
+        return None
+    to_stdout = output_fn.lower() == "stdout"
+    if to_stdout and not hasattr(sys.stdout, "buffer"):
+        return None
+    if not to_stdout and (isfile(output_fn) or not output_fn.lower().endswith(".sam")):
+        return None
+    from . import bam_device, bam_native
+    try:
+        src = bam_device.DeviceBamInput(input_fn)
+    except bam_native.AmpBamError:
+        return None                       # (not a BAM file the host codec's block walk takes: the Python codec says what it finds)
+    names = [n for n, _ in src.references]
+    if not all(ord(c) < 128 for c in src.header_text) or len(names) > bam_device.MAX_REFS or sum(len(n) for n in names) > bam_device.MAX_REF_BYTES \
+            or not all(n not in ("", "*", "=") and all(33 <= ord(c) < 127 for c in n) for n in names):
+        return None
+    out_hdr = bamio.Header(src.header_text, src.references).with_amplipy_pg(VERSION, " ".join(sys.argv))
+    if to_stdout:
+        outt, outb = sys.stdout, sys.stdout.buffer
+    else:
+        outb = open(output_fn, "wb")
+        outt = io.TextIOWrapper(outb, write_through=True)       # (what open(output_fn, "w") is made of)
+    writer = bamio.AlignmentWriter(None, "w", out_hdr, fileobj=outt)
+    outt.flush()
+    return src, writer, outb
+
+
 def open_native_sam(input_fn, output_fn, bam_write=False):
     """(SamTextInput, Header, AlignmentWriter or None, binary output or None, device_ok, DeviceBamOutput or None) when the device
     codec for SAM text can serve this run (sam_native): stdin or an existing .sam file in, and stdout, a new
@@ -394,6 +428,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     decoded on the device (bam_device) instead of by libampbam; one process only.  Runs that write trimmed reads keep libampbam,
     unless gpu_bam_write (default: AMPLIPY_GPU_BAM_WRITE, off) is on as well: a BAM file in and a new BAM file of trimmed reads out
     (trim, aio) then stay on the device codec, which re-encodes, compresses and frames the kept records too.
+    gpu_bam and gpu_sam both on: a BAM file in and trimmed reads out as SAM text (stdout or a new .sam file; trim, aio) stay on the
+    device codec for BAM input, which turns the kept records into SAM lines (bam_device); a piece with a record
+    the device would not write exactly like the Python codec goes through that codec.  One process only.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -459,7 +496,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    native = reader = writer = vcf = sam = bamdev = bamdev_io = None
+    native = reader = writer = vcf = sam = bamdev = bamdev_io = bamdev_text = None
     rank_error = None
     use_sam = dist is None and gpu_sam_wanted(gpu_sam)
     use_bam = dist is None and gpu_bam_wanted(gpu_bam)
@@ -471,6 +508,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if use_bam_write:
                 bamdev_io = open_device_bam_write(untrimmed_reads_fn, trimmed_reads_fn)
                 bamdev = untrimmed_reads_fn if bamdev_io is not None else None
+            if bamdev is None and use_bam and use_sam:
+                bamdev_text = open_device_bam_text(untrimmed_reads_fn, trimmed_reads_fn)
+                bamdev = untrimmed_reads_fn if bamdev_text is not None else None
             if bamdev is None:
                 native = open_native_bam(untrimmed_reads_fn, trimmed_reads_fn, rank, world, device)
             if native is not None and use_bam:
@@ -538,6 +578,22 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         for k_ in range(n_seen + (-n_seen) % PROGRESS_NUM_READS, n_seen + count, PROGRESS_NUM_READS):
             if k_:
                 print_log("Processed %d reads..." % k_)
+
+    def python_records(recs):
+        """Records a device codec handed back, through the Python codec: the loop of the last branch below on them (the skip of
+        A:902, the progress lines, batches through flush())."""
+        nonlocal n_seen, s_i
+        for rec in recs:
+            s_i = n_seen
+            n_seen += 1
+            if s_i % PROGRESS_NUM_READS == 0 and s_i != 0:
+                print_log("Processed %d reads..." % s_i)
+            if (rec.flag & 4) or rec.cigar is None:            # AmpliPy.py:902
+                continue
+            pending.append(rec)
+            if len(pending) >= BATCH_READS:
+                flush()
+        flush()
 
     def device_piece(codec, info, emit=None, defer=False):
         """A piece or chunk whose batch a device codec has built (info: n_records, n_rows, n_bases): counted, through the read pass
@@ -657,11 +713,14 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         # checks every block's CRC, indexes the records and decodes the rows into the packed batch (bam_device; the next piece
         # is read and copied up while this one is there).  The read pass runs on that batch.  A run that writes trimmed reads
         # (both switches on) has the kept records of every piece re-encoded, compressed and framed there as well: the BGZF
-        # blocks of the trimmed BAM are all that comes back.
+        # blocks of the trimmed BAM are all that comes back.  With the SAM switch on as well and trimmed reads going out as text
+        # (section 14), the kept records of a piece become SAM lines there; a piece with a record the device calls odd comes down as
+        # its image and goes through the Python codec (same Rec / flush() code as the last branch), then the next piece is the
+        # device's again; rows stay in input order.
         from . import bam_device
         stats = bam_device.LAST_RUN_STATS
         stats.update(pieces=0, blocks_device=0, blocks_host=0, index_rounds=0, waits=0, records=0, bytes_up=0, bytes_file=0)
-        stats.update((k_, 0) for k_ in bam_device.OUT_STATS)
+        stats.update((k_, 0) for k_ in bam_device.OUT_STATS + bam_device.TEXT_STATS)
         refuse = os.environ.get("AMPLIPY_GPU_BAM_REFUSE_BLOCK") if os.environ.get("AMPLIPY_DEV") == "1" else None
         codec = None
         out = None
@@ -678,13 +737,47 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 nonlocal flushed
                 flushed = running["pieces"] == len(src.pieces) and codec.first_bad < 0
                 out.encode(codec, running, min_length, include_no_primer, final=flushed)
+        outb = None
+        if bamdev_text is not None:
+            src, writer, outb = bamdev_text
+
+            def emit():                   # AmpliPy.py:910-911 for the piece: the lines of the kept rows in front of a failing one
+                text, ti = codec.format(min_length, include_no_primer)
+                outb.write(text)
+                running["text_rows"] += int(ti.n_rows_written)
+                running["text_bytes"] += int(ti.n_bytes)
+                running["bytes_down"] += int(ti.bytes_down)
+                running["waits"] += int(ti.waits)
+
+        def image_records():
+            """The records that end in the piece's image, as the Python codec reads them."""
+            img, offs = codec.image()
+            running["bytes_down"] += int(img.size) + 4 * int(offs.size)
+            running["waits"] += 1
+            for o in (int(x) for x in offs):
+                yield bamio.rec_of_bam_bytes(img[o + 4:o + 4 + int(img[o:o + 4].view("<u4")[0])].tobytes())
         try:
-            if out is None:
+            if out is None and outb is None:
                 src = bam_device.DeviceBamInput(bamdev)
             codec = bam_device.BamCodec(eng)
+            if outb is not None:
+                codec.set_references([n for n, _ in src.references])
             for info, running in bam_device.walk(codec, src, refuse_block=int(refuse) if refuse else None):
                 try:
-                    device_piece(codec, info, emit)
+                    odd = False
+                    if outb is not None:
+                        ti = codec.text_check()
+                        running["waits"] += int(ti.waits)
+                        running["bytes_down"] += int(ti.bytes_down)
+                        odd = ti.first_odd_row >= 0
+                        running["text_pieces_python" if odd else "text_pieces_device"] += 1
+                    if odd:               # the read pass does not run on the device's batch of this piece: nothing is counted twice
+                        try:
+                            python_records(image_records())
+                        finally:
+                            writer._f.flush()
+                    else:
+                        device_piece(codec, info, emit)
                 finally:
                     stats.update(running)
             if out is not None:
@@ -695,8 +788,15 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log("BAM device codec: %d pieces, %d blocks on the device, %d through the host codec, %d index rounds"
                       % (stats["pieces"], stats["blocks_device"], stats["blocks_host"], stats["index_rounds"])
                       + ("" if out is None else "; trimmed reads: %d blocks on the device, %d through the host codec, %d bytes down"
-                         % (stats["out_blocks_device"], stats["out_blocks_host"], stats["bytes_down"])))
+                         % (stats["out_blocks_device"], stats["out_blocks_host"], stats["bytes_down"]))
+                      + ("" if outb is None else "; trimmed reads as SAM text: %d pieces on the device, %d through the Python codec"
+                         % (stats["text_pieces_device"], stats["text_pieces_python"])))
         finally:
+            if outb is not None:
+                writer._f.flush()
+                outb.flush()
+                if outb is not getattr(sys.stdout, "buffer", None):
+                    outb.close()
             if codec is not None:
                 codec.close()
     elif sam is not None:
@@ -749,17 +849,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 if info is None or info.first_odd_line >= 0:
                     stats["python_chunks"] += 1
                     try:
-                        for rec in py_reader.records_of(io.TextIOWrapper(io.BytesIO(chunk))):
-                            s_i = n_seen
-                            n_seen += 1
-                            if s_i % PROGRESS_NUM_READS == 0 and s_i != 0:
-                                print_log("Processed %d reads..." % s_i)
-                            if (rec.flag & 4) or rec.cigar is None:            # AmpliPy.py:902
-                                continue
-                            pending.append(rec)
-                            if len(pending) >= BATCH_READS:
-                                flush()
-                        flush()
+                        python_records(py_reader.records_of(io.TextIOWrapper(io.BytesIO(chunk))))
                     finally:
                         if bam_out is not None:
                             send_host_recs()          # (on a failing read too: the rows in front of it were written)

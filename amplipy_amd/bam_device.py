@@ -1,5 +1,7 @@
-"""BAM input through the device codec of libamplihip.so (amp_bam_*, amplipy_amd/csrc/amp_bgzf.hip), and
-trimmed BAM output from it (amp_bam_encode, amplipy_amd/csrc/amp_bamout.hip; section 12).
+"""BAM input through the device codec of libamplihip.so (amp_bam_*, amplipy_amd/csrc/amp_bgzf.hip),
+trimmed BAM output from it (amp_bam_encode, amplipy_amd/csrc/amp_bamout.hip; section 12) and trimmed SAM text from it
+(amp_bam_text_check / amp_bam_format, amplipy_amd/csrc/amp_bamtext.hip; section 14: AMPLIPY_GPU_SAM=1 as well, and stdout or a
+new .sam file out).
 
 Opt-in (AMPLIPY_GPU_BAM=1 or run_amplipy(gpu_bam=True)), for single-process runs that read an existing BAM file and write no
 trimmed reads -- or, with AMPLIPY_GPU_BAM_WRITE=1 / gpu_bam_write=True as well, a new trimmed BAM file, whose records are
@@ -28,7 +30,7 @@ from . import abi, bam_native, devcodec
 PIECE_BYTES = 16 << 20
 IMAGE_LIMIT = 256 << 20            # AMP_BAM_IMAGE_LIMIT of amplihip.h
 PIECE_ISIZE_LIMIT = 120 << 20      # ISIZE sum of a piece: with a carry of at most one record (2^27 + 4 bytes) the image fits
-N_STAGES = 12                      # AMP_BAM_N_STAGES
+N_STAGES = 16                      # AMP_BAM_N_STAGES
 OUT_BS = devcodec.OUT_BS
 FORMAT_ERROR = -3                  # AMPBAM_EFORMAT
 
@@ -36,8 +38,14 @@ FORMAT_ERROR = -3                  # AMPBAM_EFORMAT
 LAST_RUN_STATS = {"pieces": 0, "blocks_device": 0, "blocks_host": 0, "index_rounds": 0, "waits": 0, "records": 0,
                   "bytes_up": 0, "bytes_file": 0,
                   # a run that writes trimmed reads through amp_bam_encode (section 12)
-                  "out_blocks_device": 0, "out_blocks_host": 0, "out_rows": 0, "bytes_down": 0, "bytes_out_file": 0}
+                  "out_blocks_device": 0, "out_blocks_host": 0, "out_rows": 0, "bytes_down": 0, "bytes_out_file": 0,
+                  # a run that writes trimmed reads as SAM text through amp_bam_format (section 14)
+                  "text_pieces_device": 0, "text_pieces_python": 0, "text_rows": 0, "text_bytes": 0}
 OUT_STATS = ("out_blocks_device", "out_blocks_host", "out_rows", "bytes_down", "bytes_out_file")
+TEXT_STATS = ("text_pieces_device", "text_pieces_python", "text_rows", "text_bytes")
+ODD_REASONS = ("NONE", "QNAME", "REF", "CIGAR_OP", "QUAL", "AUX_TYPE", "AUX_TRUNC", "AUX_CHAR", "AUX_FLOAT")       # AMP_BAM_ODD_*
+MAX_REFS, MAX_REF_BYTES = 64, 4096 # AMP_SAM_MAX_REFS, AMP_SAM_MAX_REF_BYTES: the name table of amp_bam_set_references
+OVERFLOW = -6                      # AMP_EOVERFLOW
 
 
 class AmpBamBlock(C.Structure):
@@ -50,13 +58,19 @@ class AmpBamInfo(C.Structure):
                                          "bytes_up")] + [("bad_record", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AmpBamTextInfo(C.Structure):
+    _fields_ = [("first_odd_row", C.c_int64), ("odd_reason", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, C.c_int64) for n in ("n_rows_written", "n_bytes", "waits", "bytes_down")]
+
+
 AmpBamOutInfo, TWIN_DEFLATE_FN, bgzf_block = devcodec.AmpBamOutInfo, devcodec.TWIN_DEFLATE_FN, devcodec.bgzf_block
 
 
 def twin_sources():
-    """amp_bgzf.hip (which includes amp_bamout.hip, the re-encoder's lanes and driver) and the lane functions' headers."""
+    """amp_bgzf.hip (which includes amp_bamout.hip, the re-encoder's lanes and driver, and amp_bamtext.hip, the text stage's) and the
+    lane functions' headers."""
     here = os.path.dirname(os.path.abspath(__file__))
-    return tuple(os.path.join(here, "csrc", f) for f in ("amp_bgzf.hip", "amp_bgzf.hpp", "amp_bamout.hip", "amp_bamout.hpp"))
+    return tuple(os.path.join(here, "csrc", f) for f in ("amp_bgzf.hip", "amp_bgzf.hpp", "amp_bamout.hip", "amp_bamout.hpp", "amp_bamtext.hip", "amp_bamtext.hpp"))
 
 
 def build_twin(out_path, sanitize=False, main_source=None):
@@ -225,6 +239,44 @@ class BamCodec(devcodec.DeviceCodec):
         self._chk(rc, "amp_bam_encode")
         return self._encoded(info)
 
+    # ---- trimmed reads as SAM text (section 14) ----------------------------------------------------------------------------------
+    def set_references(self, names):
+        """amp_bam_set_references: the names RNAME / RNEXT are written from (header.refs of the writer), once per run."""
+        enc = [n.encode("ascii") for n in names]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        self._chk(self.L.amp_bam_set_references(self.h, C.c_int32(len(enc)), arr), "amp_bam_set_references")
+
+    def text_check(self):
+        """amp_bam_text_check behind a feed whose index stands: the info (first_odd_row -1: the device formats the piece)."""
+        info = AmpBamTextInfo()
+        self._chk(self.L.amp_bam_text_check(self.h, C.byref(info)), "amp_bam_text_check")
+        self.text_info = info
+        return info
+
+    def format(self, min_length, include_no_primer):
+        """amp_bam_format: (the lines of the kept rows of the last feed as bytes, info).  The buffer it copies into is kept; when it
+        is short the call names the size, the buffer grows and the call is made again (info.waits has the wait of the short try
+        too, ``self.text_retries`` counts them: pieces of a run have one size, so the first pieces at most)."""
+        info = AmpBamTextInfo()
+        room = max(2 * int(self.info.image_bytes), 1 << 16)             # (a line is at most about twice its record)
+        if getattr(self, "_text", None) is None or self._text.size < room:
+            self._text = np.empty(room, np.uint8)
+
+        def call():
+            return self.L.amp_bam_format(self.h, C.c_int32(int(min_length)), C.c_int32(1 if include_no_primer else 0),
+                                         C.c_void_p(abi.ptr(self._text)), C.c_int64(self._text.size), C.byref(info))
+        rc = call()
+        waits = 0
+        if rc == OVERFLOW and info.n_bytes < (1 << 32):
+            waits = int(info.waits)
+            self.text_retries = getattr(self, "text_retries", 0) + 1
+            self._text = np.empty(int(info.n_bytes) + int(info.n_bytes) // 4, np.uint8)
+            rc = call()
+        self._chk(rc, "amp_bam_format")
+        info.waits += waits
+        self.text_info = info
+        return self._text[:int(info.n_bytes)].tobytes(), info
+
     def image(self):
         """(the image of the last feed, the offsets of its records in it)."""
         img = np.zeros(max(int(self.info.image_bytes), 1), np.uint8)
@@ -270,7 +322,7 @@ def walk(codec, src, refuse_block=None):
     stats = the running totals (the keys of LAST_RUN_STATS).  refuse_block: development only -- that block of the file is
     treated as refused."""
     stats = dict(pieces=0, blocks_device=0, blocks_host=0, index_rounds=0, waits=0, records=0, bytes_up=0, bytes_file=src.file_bytes)
-    stats.update((k, 0) for k in OUT_STATS)
+    stats.update((k, 0) for k in OUT_STATS + TEXT_STATS)
     n_ref = len(src.references)
     first = src.first_record
     for comp, tab, k_lo, last in src:

@@ -203,6 +203,29 @@ def reg2bin(beg, end):
 # ---------------------------------------------------------------------------------------------
 # readers
 # ---------------------------------------------------------------------------------------------
+def rec_of_bam_bytes(b):
+    """The Rec of one BAM record: ``b`` = its bytes behind the block_size word."""
+    ref_id, pos, l_name, mapq, _bin, n_cig, flag, l_seq, nref, npos, tlen = struct.unpack_from("<iiBBHHHiiii", b, 0)
+    o = 32
+    qname = b[o:o + l_name - 1].decode("ascii"); o += l_name
+    cig = None
+    if n_cig:
+        raw = struct.unpack_from("<%dI" % n_cig, b, o)
+        cig = [(v & 15, v >> 4) for v in raw]
+    o += 4 * n_cig
+    seq = None
+    if l_seq:
+        packed = np.frombuffer(b, np.uint8, (l_seq + 1) // 2, o)
+        codes = np.empty(packed.size * 2, np.uint8); codes[0::2] = packed >> 4; codes[1::2] = packed & 15
+        seq = "".join(SEQ_NT16[c] for c in codes[:l_seq])
+    o += (l_seq + 1) // 2
+    qual = b[o:o + l_seq] if l_seq else None
+    if qual is not None and l_seq and qual[0] == 0xFF:
+        qual = None
+    o += l_seq
+    return Rec(qname, flag, ref_id, pos, mapq, cig, nref, npos, tlen, seq, qual, aux_bam=b[o:])
+
+
 class AlignmentReader:
     """Iterates Rec objects of a SAM (text) or BAM file, in file order, mapped or not."""
 
@@ -255,26 +278,7 @@ class AlignmentReader:
             if len(h) < 4:
                 return
             bs = struct.unpack("<i", h)[0]
-            b = self._take(bs)
-            ref_id, pos, l_name, mapq, _bin, n_cig, flag, l_seq, nref, npos, tlen = struct.unpack_from("<iiBBHHHiiii", b, 0)
-            o = 32
-            qname = b[o:o + l_name - 1].decode("ascii"); o += l_name
-            cig = None
-            if n_cig:
-                raw = struct.unpack_from("<%dI" % n_cig, b, o)
-                cig = [(v & 15, v >> 4) for v in raw]
-            o += 4 * n_cig
-            seq = None
-            if l_seq:
-                packed = np.frombuffer(b, np.uint8, (l_seq + 1) // 2, o)
-                codes = np.empty(packed.size * 2, np.uint8); codes[0::2] = packed >> 4; codes[1::2] = packed & 15
-                seq = "".join(SEQ_NT16[c] for c in codes[:l_seq])
-            o += (l_seq + 1) // 2
-            qual = b[o:o + l_seq] if l_seq else None
-            if qual is not None and l_seq and qual[0] == 0xFF:
-                qual = None
-            o += l_seq
-            yield Rec(qname, flag, ref_id, pos, mapq, cig, nref, npos, tlen, seq, qual, aux_bam=b[o:])
+            yield rec_of_bam_bytes(self._take(bs))
 
     @classmethod
     def for_header(cls, header):

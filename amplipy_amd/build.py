@@ -18,10 +18,11 @@ UNIT_DEPS = {"amplihip.hip": HEADERS, "amp_ins.hip": [os.path.join(_HERE, "..", 
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
              "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in
                              ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamtail.hpp")],
-             # (amp_bamout.hip, the re-encoder of trimmed records, is part of amp_bgzf.hip's unit: it is included there)
+             # (amp_bamout.hip, the re-encoder of trimmed records, and amp_bamtext.hip, trimmed records as SAM text, are part of
+             # amp_bgzf.hip's unit: they are included there)
              "amp_bgzf.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in
-                              ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamtail.hpp", "amp_bamout.hip")]}
-DEPS = [os.path.join(CSRC, u) for u in UNITS] + [os.path.join(CSRC, "amp_bamout.hip")] + HEADERS
+                              ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamtail.hpp", "amp_bamout.hip", "amp_bamtext.hpp", "amp_bamtext.hip")]}
+DEPS = [os.path.join(CSRC, u) for u in UNITS] + [os.path.join(CSRC, f) for f in ("amp_bamout.hip", "amp_bamtext.hip")] + HEADERS
 OUT = os.path.join(_HERE, "libamplihip.so")
 OBJ_DIR = os.path.join(_HERE, "build")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function"]

@@ -30,6 +30,7 @@
 #include "amp_codec.hpp"
 #define BGZ_HD AMP_HD
 #include "amp_bamtail.hpp"
+#include "amp_bamtext.hpp"
 
 namespace ampbgzf {
 
@@ -55,6 +56,7 @@ struct Buf : BufIndex, ampcodec::Batch {
     unsigned long long *ctl;
     uint64_t spare;            // (the kernels' other arguments stay where they were when a pointer lay here)
     ampbamout::Out o;          // the re-encoder of trimmed records (amp_bamout.hip)
+    ampbamtext::Text x;        // trimmed records as SAM text (amp_bamtext.hip)
 };
 
 // ---- inflate / crc: one wave per block ----------------------------------------------------------------------------------------
@@ -290,6 +292,7 @@ struct amp_bam {
     bool processed = false, encoded = false;          // of the last feed: results are there; its rows were encoded
     int64_t good_rows = 0;                            // rows in front of the first failing one
     ampbamout::Tail tail;                             // the encoder's buffers, carry and counters (amp_bamtail.hpp)
+    ampbamtext::State text;                           // trimmed records as SAM text: name table, sizes, the text (amp_bamtext.hip)
 };
 
 #ifndef AMPBGZF_HOSTSIM
@@ -429,6 +432,7 @@ void amp_bam_destroy(amp_bam *s) {
     DevGuard guard(s->sh);
     (void)codec_wait(s->sh);
     codec_free(s->arena); codec_free(s->img); codec_free(s->comp); codec_free(s->carry); ampbamout::tail_free(s->tail);
+    codec_free(s->text.names); codec_free(s->text.name_off); codec_free(s->text.arena); codec_free(s->text.out);
     codec_delete(s);
 }
 
@@ -437,7 +441,7 @@ int amp_bam_feed(amp_bam *s, const uint8_t *comp, int64_t n_comp, const amp_bam_
                  int32_t n_ref, int64_t rec_base, amp_bam_info *info) {
     if (!s || !info || n_comp < 0 || n_blocks < 0 || (n_comp && !comp) || (n_blocks && !blocks) || n_ref < 0 || n_comp >= (1ll << 31)) return AMP_EINVAL;
     DevGuard guard(s->sh);
-    s->fed = s->processed = s->encoded = false;
+    s->fed = s->processed = s->encoded = s->text.checked = false;
     const int64_t waits0 = s->sh.waits;
     int64_t isize = 0;
     try { s->h_blocks.resize((size_t)n_blocks); s->h_verdict.assign((size_t)n_blocks, 0); } catch (const std::bad_alloc &) { return AMP_ENOMEM; }
@@ -516,6 +520,7 @@ int amp_bam_reindex(amp_bam *s, amp_bam_info *info) {
     if (!s || !info) return AMP_EINVAL;
     if (!s->fed || s->refused_left != 0) return AMP_ESTATE;
     DevGuard guard(s->sh);
+    s->text.checked = false;
     const int64_t waits0 = s->info.waits, w0 = s->sh.waits;
     CODEC_OK(codec_zero(s->sh, s->b.ctl, 0, CTL_WORDS * 8));
     CODEC_OK(bam_index_decode(s));
@@ -571,3 +576,4 @@ int amp_bam_stage_ms(amp_bam *s, int on, float *ms) { return s ? codec_stage_ms(
 }  // extern "C"
 
 #include "amp_bamout.hip"
+#include "amp_bamtext.hip"

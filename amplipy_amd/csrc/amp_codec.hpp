@@ -72,7 +72,7 @@ AMP_HD void lane_first_bad(const uint8_t *status, unsigned long long *key, int64
 }
 typedef void (*FirstBadFn)(const uint8_t *status, unsigned long long *key, int64_t n);
 
-enum { MAX_STAGES = 15 };
+enum { MAX_STAGES = 16 };
 
 struct Shell {
     int n_stages = 0;

@@ -36,6 +36,7 @@ EXPORTS = [
     "amp_bam_encode", "amp_bam_encoded_to_host", "amp_bam_encoded_blocks", "amp_bam_stream_to_host",
     "amp_sam_set_output", "amp_sam_encode", "amp_sam_encode_bytes", "amp_sam_encoded_to_host", "amp_sam_encoded_blocks", "amp_sam_stream_to_host",
     "amp_sam_first_bad", "amp_sam_waits",
+    "amp_bam_set_references", "amp_bam_text_check", "amp_bam_format",
 ]
 
 

@@ -488,7 +488,7 @@ int amp_sam_stage_ms(amp_sam *s, int on, float *ms);
  * (ampbam_inflate_raw / zlib, CRC checked), patches the bytes in and asks for the index again.  On a valid file no block is. */
 #define AMP_BAM_IMAGE_LIMIT (256ll << 20) /* bytes of an image: carry + the ISIZE sum of a piece.  A record is at most 2^27 + 4 bytes
                                            * (a longer block_size is a format error), so pieces of up to 120 MiB inflated always fit */
-#define AMP_BAM_N_STAGES 12
+#define AMP_BAM_N_STAGES 16
 typedef struct amp_bam amp_bam;
 typedef struct amp_bam_block {   /* one BGZF block of a piece */
     uint32_t in_off, in_len;     /* its raw DEFLATE stream in the piece's compressed bytes */
@@ -535,7 +535,9 @@ int amp_bam_image_to_host(amp_bam *s, uint8_t *image, int64_t image_cap, uint32_
 int amp_bam_process(amp_bam *s, uint64_t read_base, int64_t *first_bad_row, uint8_t *its_status);
 /* Development aid: ms[AMP_BAM_N_STAGES] of the last piece from HIP events on the ctx stream -- [0] copy up, [1] inflate, [2] CRC,
  * [3] record index, [4] decode, [6] the read pass, [8] re-encode of trimmed records, [9] their DEFLATE, [10] CRC and framing,
- * [11] copy down ([5], [7]: the waits and host time between the calls).  on != 0 records from the next call on. */
+ * [11] copy down ([5], [7]: the waits and host time between the calls); with trimmed reads as SAM text (section 14) [12] the
+ * text check, [14] sizes and lines, [15] the text's copy down ([13]: the read pass and host time between check and format).
+ * on != 0 records from the next call on. */
 int amp_bam_stage_ms(amp_bam *s, int on, float *ms);
 
 /* ---- trimmed BAM out of an amp_bam (opt-in: AMPLIPY_GPU_BAM_WRITE=1 with AMPLIPY_GPU_BAM=1) -------------
@@ -590,6 +592,44 @@ int amp_sam_encode_bytes(amp_sam *s, const uint8_t *bytes, int64_t n, int32_t fi
 int amp_sam_encoded_to_host(amp_sam *s, uint8_t *dst, int64_t cap);
 int amp_sam_encoded_blocks(amp_sam *s, uint32_t *blk_len, int64_t cap);
 int amp_sam_stream_to_host(amp_sam *s, int64_t from, int64_t n, uint8_t *dst);
+
+/* ---- BAM in, trimmed SAM text out (opt-in: AMPLIPY_GPU_BAM=1 with AMPLIPY_GPU_SAM=1) ----------------------
+ * The Python codec writes a trimmed read of a BAM input with AlignmentWriter(mode="w").write(r, pos=, cigar=) (out_aln.write,
+ * AmpliPy.py:911): QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL and the aux fields through aux_bam_to_sam, joined by
+ * tabs.  An amp_bam makes the same line in HBM from the record where it lies in the piece's image, the new POS and CIGAR from the
+ * results of amp_bam_process.  A row is ODD when the Python codec would raise on its record or might not write exactly the
+ * device's bytes; a piece with an odd row is not formatted here at all (amp_bam_format refuses it): the caller brings the image
+ * down (amp_bam_image_to_host) and hands its records to the Python codec, so whatever that does with the row still happens.
+ * Records that are no rows (A:902) are never written and never checked.  Of several faults of one row the smallest number is
+ * reported; the rule is stricter than needed in places, which costs a fallback, never a difference: */
+#define AMP_BAM_ODD_NONE 0
+#define AMP_BAM_ODD_QNAME 1        /* a QNAME byte outside '!'..'~', or l_read_name 0 */
+#define AMP_BAM_ODD_REF 2          /* ref_id or next_ref_id not below the number of names (IndexError) */
+#define AMP_BAM_ODD_CIGAR_OP 3     /* an op code above 9 in the record's CIGAR */
+#define AMP_BAM_ODD_QUAL 4         /* a quality above 93 in a QUAL that does not start with 0xFF */
+#define AMP_BAM_ODD_AUX_TYPE 5     /* an aux type that is none of A c C s S i I f Z H B, or a B subtype that is none of c C s S i I f */
+#define AMP_BAM_ODD_AUX_TRUNC 6    /* a value, a B array, or a Z / H without its NUL reaching behind the record; 1-2 bytes left over */
+#define AMP_BAM_ODD_AUX_CHAR 7     /* a tag or A byte outside '!'..'~', a Z / H byte outside ' '..'~' */
+#define AMP_BAM_ODD_AUX_FLOAT 8    /* f, or an element of B:f, that is neither +-0 nor finite with 1e-4 <= |v| < 2^63 */
+typedef struct amp_bam_text_info {
+    int64_t first_odd_row;   /* -1: none (of the last check) */
+    int32_t odd_reason, reserved;
+    int64_t n_rows_written;  /* lines of this format */
+    int64_t n_bytes;         /* ... and their bytes (with AMP_EOVERFLOW: the size needed) */
+    int64_t waits;           /* waits for the device this call cost */
+    int64_t bytes_down;      /* device-to-host bytes: the counters, and the text */
+} amp_bam_text_info;
+/* header.refs of the writer: the names RNAME / RNEXT are written from, at most AMP_SAM_MAX_REFS of AMP_SAM_MAX_REF_BYTES bytes
+ * together.  Once per run, before the first check. */
+int amp_bam_set_references(amp_bam *s, int32_t n_ref, const char *const *names);
+/* The verdict on the rows of the last feed, whose index stands (no refused block left, no bad record), and the sizes of their
+ * lines.  One wait (none for a piece without rows).  AMP_ESTATE without such a feed or before amp_bam_set_references. */
+int amp_bam_text_check(amp_bam *s, amp_bam_text_info *info);
+/* AlignmentWriter.write(r, pos=, cigar=) for every row in front of the first failing one that passes A:910 (as amp_bam_encode
+ * and amp_sam_format choose them), n_bytes of text to `out`.  AMP_EOVERFLOW with n_bytes = the size needed when cap is short
+ * (or the text would pass 2^32 bytes); AMP_ESTATE before amp_bam_process, or on a piece whose check found an odd row or never
+ * ran.  Two waits at most: the sizes, then the copy.  The text buffer belongs to the amp_bam and grows to the largest piece. */
+int amp_bam_format(amp_bam *s, int32_t min_length, int32_t include_no_primer, uint8_t *out, int64_t cap, amp_bam_text_info *info);
 
 #ifdef __cplusplus
 }
