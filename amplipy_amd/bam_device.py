@@ -193,16 +193,27 @@ class BamCodec(devcodec.DeviceCodec):
         self._chk(self.L.amp_bam_refused(self.h, C.c_void_p(abi.ptr(idx)), C.c_int64(idx.size), C.byref(n)), "amp_bam_refused")
         return [int(x) for x in idx[:int(n.value)]]
 
-    def patch_through_host(self):
+    def verdicts(self):
+        """amp_bam_verdicts: one byte per block of the last feed -- 0 accepted, 1 refused by the decoder, 2 by the CRC check."""
+        v = np.zeros(max(int(self.info.n_blocks), 1), np.uint8)
+        self._chk(self.L.amp_bam_verdicts(self.h, C.c_void_p(abi.ptr(v)), C.c_int64(v.size)), "amp_bam_verdicts")
+        return v[:int(self.info.n_blocks)]
+
+    def patch_through_host(self, comp=None, blocks=None):
         """Every refused block of the last feed through the host's inflate and CRC check: the number of blocks patched, or None
-        when one of them is damaged (the caller raises what the host codec raises for the file).  Then the index again."""
+        when one of them is damaged (the caller raises what the host codec raises for the file).  Then the index again.
+        comp, blocks: the host reads these instead of what was fed (same block count and ISIZEs; tests)."""
+        if comp is None:
+            comp, blocks = self._comp, self._blocks
+        else:
+            comp, blocks = np.frombuffer(comp, np.uint8), np.asarray(blocks, np.uint64).reshape(-1, 4)
         n = 0
         for k in self.refused():
-            off, ln, isize, crc = (int(x) for x in self._blocks[k])
+            off, ln, isize, crc = (int(x) for x in blocks[k])
             out = b""
             if isize:
                 try:
-                    out = zlib.decompress(self._comp[off:off + ln].tobytes(), -15)
+                    out = zlib.decompress(comp[off:off + ln].tobytes(), -15)
                 except zlib.error:
                     return None
                 if len(out) != isize or (zlib.crc32(out) & 0xFFFFFFFF) != crc:

@@ -501,6 +501,16 @@ int amp_bam_refused(amp_bam *s, int64_t *idx, int64_t cap, int64_t *n) {
     return AMP_OK;
 }
 
+// why: one byte per block of the last feed as the kernels left it -- 0 accepted, 1 refused by the decoder, 2 by the CRC (tests)
+int amp_bam_verdicts(amp_bam *s, uint8_t *verdict, int64_t cap) {
+    if (!s || cap < 0 || (cap && !verdict)) return AMP_EINVAL;
+    if (!s->fed) return AMP_ESTATE;
+    if (cap < (int64_t)s->h_blocks.size()) return AMP_EOVERFLOW;
+    DevGuard guard(s->sh);
+    CODEC_OK(codec_down(s->sh, verdict, s->b.verdict, s->h_blocks.size()));
+    return codec_wait(s->sh);
+}
+
 // the bytes of block k as the host inflated them (ampbam_inflate_raw / zlib, CRC checked by the caller) into the image
 int amp_bam_patch_block(amp_bam *s, int64_t k, const uint8_t *bytes, int64_t n_bytes) {
     if (!s || k < 0 || n_bytes < 0 || (n_bytes && !bytes)) return AMP_EINVAL;

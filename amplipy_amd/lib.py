@@ -31,7 +31,7 @@ EXPORTS = [
     "amp_deflate_blocks", "amp_deflate_blocks_device", "amp_deflate_blocks_device_counted", "amp_deflate_sync", "amp_deflate_blocks_cb",
     "amp_sam_create", "amp_sam_destroy", "amp_sam_set_references", "amp_sam_parse", "amp_sam_reads", "amp_sam_batch_to_host",
     "amp_sam_process", "amp_sam_format", "amp_sam_stage_ms",
-    "amp_bam_create", "amp_bam_destroy", "amp_bam_feed", "amp_bam_dev_refuse", "amp_bam_refused", "amp_bam_patch_block", "amp_bam_reindex",
+    "amp_bam_create", "amp_bam_destroy", "amp_bam_feed", "amp_bam_dev_refuse", "amp_bam_refused", "amp_bam_verdicts", "amp_bam_patch_block", "amp_bam_reindex",
     "amp_bam_reads", "amp_bam_batch_to_host", "amp_bam_image_to_host", "amp_bam_process", "amp_bam_stage_ms",
     "amp_bam_encode", "amp_bam_encoded_to_host", "amp_bam_encoded_blocks", "amp_bam_stream_to_host",
     "amp_sam_set_output", "amp_sam_encode", "amp_sam_encode_bytes", "amp_sam_encoded_to_host", "amp_sam_encoded_blocks", "amp_sam_stream_to_host",

@@ -521,6 +521,9 @@ int amp_bam_dev_refuse(amp_bam *s, int64_t k);
 /* The blocks the last feed handed back (piece-relative numbers), the host's bytes for one of them, and the index and decode
  * again once all of them are patched. */
 int amp_bam_refused(amp_bam *s, int64_t *idx, int64_t cap, int64_t *n);
+/* Why: one byte per block of the last feed as the kernels left it (cap >= n_blocks) -- 0 accepted, 1 refused by the decoder,
+ * 2 by the CRC check.  Tests and tools. */
+int amp_bam_verdicts(amp_bam *s, uint8_t *verdict, int64_t cap);
 int amp_bam_patch_block(amp_bam *s, int64_t k, const uint8_t *bytes, int64_t n_bytes);
 int amp_bam_reindex(amp_bam *s, amp_bam_info *info);
 /* The batch of the last feed (ampbam_decode's rows): device pointers, valid until the next feed. */

@@ -12,7 +12,9 @@ import zlib
 import numpy as np
 import pytest
 
-from amplipy_amd import bam_device, bam_native, bamio, synth
+from amplipy_amd import bam_device, bam_native, synth
+from tests.bam_util import (_assert_rows, _bgzf, _blocks_of, _check_file, _make_decoy_bam, _make_lseq0_bam, _make_repeated_bam, _run,
+                            _whole)
 from tests.test_bam_native import _make_bam
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +23,9 @@ NAMES = ("pos", "flag", "tlen", "lseq", "cig_off", "cig", "seq_off", "seq", "qua
 
 @pytest.fixture(scope="module")
 def twin(tmp_path_factory):
-    return bam_device.build_twin(str(tmp_path_factory.mktemp("twin") / "libampbgzf_twin.so"))
+    """A factory of codecs on the host twin."""
+    so = bam_device.build_twin(str(tmp_path_factory.mktemp("twin") / "libampbgzf_twin.so"))
+    return lambda: bam_device.BamCodec(twin=so)
 
 
 @pytest.fixture(scope="module")
@@ -52,12 +56,6 @@ def _inflate(L, raw, n_out, pad=64):
     rc = L.t_inflate(C.c_void_p(src.ctypes.data), C.c_int64(len(raw)), C.c_void_p(out.ctypes.data + pad), C.c_int64(n_out))
     assert (out[:pad] == 0xA5).all() and (out[pad + n_out:] == 0xA5).all(), "wrote outside the output range"
     return rc, out[pad:pad + n_out].tobytes()
-
-
-def _blocks_of(path):
-    tab = bam_device.block_table(path)
-    raw = open(path, "rb").read()
-    return [(raw[int(o):int(o + n)], int(isz), int(crc)) for o, n, isz, crc in tab]
 
 
 def test_block_table_is_the_files(tmp_path):
@@ -189,80 +187,6 @@ def test_crc_equals_zlibs(lane_lib):
 
 
 # ---- index and decode ---------------------------------------------------------------------------------------------------------------
-def _serial_walk(image, first):
-    off = []
-    o = first
-    while o + 4 <= len(image):
-        bs = struct.unpack_from("<I", image, o)[0]
-        if o + 4 + bs > len(image):
-            break
-        off.append(o)
-        o += 4 + bs
-    return off, o
-
-
-def _whole(path):
-    f = bam_native.BamFile(path)                      # ampbam_open: the file opened whole, not walked in pieces
-    want, _ = f.decode(0, f.n_records, copy=False)
-    return f, want
-
-
-def _run(twin, path, piece_bytes, refuse_block=None):
-    """The walk of run_amplipy on the twin: (rows of all pieces concatenated with the last piece's slack, record offsets in the
-    file's inflated stream, stats)."""
-    src = bam_device.DeviceBamInput(path, piece_bytes)
-    c = bam_device.BamCodec(twin=twin)
-    rows, offs, base, st = [], [], 0, None
-    for info, st in bam_device.walk(c, src, refuse_block=refuse_block):
-        img, off = c.image()
-        offs.extend(int(x) + base - int(info.carry_in) for x in off)
-        base += int(info.n_inflated)
-        assert int(info.carry_out) <= int(info.image_bytes)
-        if info.n_rows:
-            rows.append(c.batch(slack=True))
-    c.close()
-    return rows, offs, dict(st)
-
-
-def _assert_rows(rows, want, f_n_records=None):
-    """Equal to ampbam_decode's batch: scalars, offsets (piece-relative ones re-based), CIGAR words, bases and qualities with
-    every pad, and 16 zero bytes of slack behind each piece's arrays."""
-    for _, (cig_tail, seq_tail, qual_tail) in rows:
-        assert cig_tail.size == 4 and not cig_tail.any() and seq_tail.size == 16 and not seq_tail.any() and qual_tail.size == 16 and not qual_tail.any()
-    rows = [r for r, _ in rows]
-    assert sum(r.n for r in rows) == want.n
-    for name in ("pos", "flag", "tlen", "lseq", "src_index"):
-        assert np.array_equal(np.concatenate([getattr(r, name) for r in rows]), getattr(want, name)), name
-    assert np.array_equal(np.concatenate([r.cig[:int(r.cig_off[-1])] for r in rows]), want.cig)
-    assert np.array_equal(np.concatenate([r.seq[:int(r.seq_off[-1]) // 2] for r in rows]), want.seq)
-    assert np.array_equal(np.concatenate([r.qual[:int(r.seq_off[-1])] for r in rows]), want.qual)
-    co, so, cb, sb = [], [], 0, 0
-    for r in rows:
-        co.append(r.cig_off[:-1] + np.uint64(cb)); so.append(r.seq_off[:-1] + np.uint64(sb))
-        cb += int(r.cig_off[-1]); sb += int(r.seq_off[-1])
-    assert np.array_equal(np.concatenate(co), want.cig_off[:-1]) and np.array_equal(np.concatenate(so), want.seq_off[:-1])
-    assert cb == int(want.cig_off[-1]) and sb == int(want.seq_off[-1])
-
-
-def _check_file(twin, path, piece_sizes, ordinary=True):
-    f, want = _whole(path)
-    image = b"".join(zlib.decompress(raw, -15) for raw, _, _ in _blocks_of(path))
-    _, _, first = bam_device.read_header(path, bam_device.block_table(path))
-    serial, end = _serial_walk(image, first)
-    assert len(serial) == f.n_records and end == len(image)
-    out = {}
-    for pb in piece_sizes:
-        rows, offs, st = _run(twin, path, pb)
-        assert offs == serial, pb
-        assert st["records"] == f.n_records and st["blocks_host"] == 0, (pb, st)
-        if ordinary:                                  # one wait for the device per piece, one index round
-            assert st["waits"] == st["pieces"] and st["index_rounds"] <= st["pieces"], (pb, st)
-        _assert_rows(rows, want)
-        out[pb] = st
-    f.close()
-    return out
-
-
 def test_decode_equals_ampbam_decode(twin, tmp_path):
     """_make_bam files (aux tags, an unmapped record, a record without CIGAR, QUAL absent, odd l_seq) and one with l_seq 0, at
     pieces of one block, 64 KB, 1 MB and the whole file: records and their 36 fixed bytes straddle pieces."""
@@ -270,17 +194,7 @@ def test_decode_equals_ampbam_decode(twin, tmp_path):
     _make_bam(bam, n=4000)
     st = _check_file(twin, bam, (1, 65536, 1 << 20, 1 << 30))
     assert st[1]["pieces"] > 15 and st[1 << 30]["pieces"] == 1
-    g = synth.make_genome()
-    hdr = bamio.Header("@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:SYN_REF\tLN:%d\n" % g.size, [("SYN_REF", int(g.size))])
-    p2 = str(tmp_path / "z.bam")
-    w = bamio.AlignmentWriter(p2, "wb", hdr)
-    rng = np.random.default_rng(4)
-    for i in range(3000):
-        L = int(rng.integers(0, 40)) if i % 3 else 0
-        seq = "".join("ACGTN"[int(x)] for x in rng.integers(0, 5, L))
-        w.write(bamio.Rec("q%d" % i, 0, 0, 10 + i, 60, [(0, max(L, 1))], -1, -1, 0, seq if L else None,
-                          bytes(rng.integers(0, 60, L).astype(np.uint8)) if L and i % 5 else None))
-    w.close()
+    p2 = _make_lseq0_bam(str(tmp_path / "z.bam"))
     _check_file(twin, p2, (1, 4096, 1 << 30))
 
 
@@ -293,14 +207,7 @@ def test_decode_of_write_batch_and_compressible_files(twin, tmp_path):
     write_bam(p1, synth.make_amplicon_batch(g, amps, 20000, seed=5), int(g.size))
     st = _check_file(twin, p1, (65536, 1 << 20, 1 << 30))
     assert st[65536]["index_rounds"] == st[65536]["pieces"]            # one round per piece on an ordinary file
-    one = synth.make_amplicon_batch(g, amps, 1, seed=1)
-    p2 = str(tmp_path / "rep.bam")
-    f = bam_native.BamFile(p1)
-    w = bam_native.BamWriter(p2, f.header_text, f, level=6)
-    for _ in range(40):
-        for k in range(500):
-            w.write_batch(one, name_base=0)
-    w.close(); f.close()
+    p2 = _make_repeated_bam(str(tmp_path / "rep.bam"), p1)
     assert sum(isz for _, isz, _ in _blocks_of(p2)) > 20 * os.path.getsize(p2)
     _check_file(twin, p2, (4096, 1 << 30))
 
@@ -309,37 +216,10 @@ def test_index_ignores_decoys(twin, tmp_path):
     """The decoy file of test_record_index_ignores_decoy_records (runs of 70 plausible fake records inside quality bytes) and the
     decoy that ends with its host record (test_piece_walk_does_not_guess_record_starts): exactly the offsets of a serial walk.
     Records longer than one and than ten stretches; a file of one record; the rounds are reported."""
-    g = synth.make_genome(); primers, amps = synth.make_artic_scheme()
-    segs = synth.make_mixed_segments(g, amps, 6000, seed=3)
-    hdr = bamio.Header("@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:SYN_REF\tLN:%d\n" % g.size, [("SYN_REF", int(g.size))])
-    fake = struct.pack("<iiiBBHHHIiii", 34, 0, 5, 2, 60, 4680, 0, 0, 0, -1, -1, 0) + b"A\0"
-    decoy_q = bytes([30]) * 3 + fake * 70 + bytes([30]) * 40
-    tag = b"zzBC" + struct.pack("<I", 80 * len(fake)) + fake * 80
-    long_q = bytes([31]) * 50000                                       # a record longer than ten stretches
-    recs = []
-    for i, s in enumerate(segs):
-        r = bamio.Rec("r%d" % i, s.flag, 0, s.reference_start, 60, s.cigartuples, 0, s.reference_start, s.template_length,
-                      s.query_sequence, bytes(s.query_qualities))
-        if i % 97 == 13:
-            r.aux_bam = tag
-        recs.append(r)
-        if i % 150 == 75:
-            L = len(decoy_q)
-            recs.append(bamio.Rec("decoy%d" % i, 0, 0, 100 + i % 1000, 60, [(0, L)], -1, -1, 0, "ACGT" * (L // 4) + "A" * (L % 4), decoy_q))
-        if i % 1500 == 700:
-            L = len(long_q)
-            recs.append(bamio.Rec("long%d" % i, 0, 0, 100, 60, [(0, L)], -1, -1, 0, "ACGT" * (L // 4), long_q))
-    bam = str(tmp_path / "d.bam")
-    w = bamio.AlignmentWriter(bam, "wb", hdr)
-    for r in recs:
-        w.write(r)
-    w.close()
+    bam = str(tmp_path / "d.bam"); one = str(tmp_path / "one.bam")
+    _make_decoy_bam(bam, one)
     st = _check_file(twin, bam, (1, 300000, 1 << 30), ordinary=False)
     assert st[1 << 30]["index_rounds"] > 1 and st[1 << 30]["waits"] >= 1           # guesses inside decoys were overruled, and counted
-    one = str(tmp_path / "one.bam")
-    w = bamio.AlignmentWriter(one, "wb", hdr)
-    w.write(recs[0])
-    w.close()
     st = _check_file(twin, one, (1, 1 << 30))
     assert st[1 << 30]["records"] == 1 and st[1 << 30]["index_rounds"] == 1
 
@@ -386,10 +266,3 @@ def test_refused_blocks_go_through_the_host(twin, tmp_path):
         with pytest.raises(bam_native.AmpBamError) as dev:
             _run(twin, p, 65536)
         assert str(dev.value) == str(host.value), name
-
-
-def _bgzf(data):
-    co = zlib.compressobj(6, zlib.DEFLATED, -15)
-    comp = co.compress(data) + co.flush()
-    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(comp) + 25) + comp
-            + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from amplipy_amd import bam_device, bam_native, bamio, synth
-from tests.test_bam_device_twin import _bgzf, _blocks_of
+from tests.bam_util import _bgzf, _blocks_of
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
