@@ -44,8 +44,12 @@ LAST_RUN_STATS = {"pieces": 0, "blocks_device": 0, "blocks_host": 0, "index_roun
 OUT_STATS = ("out_blocks_device", "out_blocks_host", "out_rows", "bytes_down", "bytes_out_file")
 TEXT_STATS = ("text_pieces_device", "text_pieces_python", "text_rows", "text_bytes")
 ODD_REASONS = ("NONE", "QNAME", "REF", "CIGAR_OP", "QUAL", "AUX_TYPE", "AUX_TRUNC", "AUX_CHAR", "AUX_FLOAT")       # AMP_BAM_ODD_*
-MAX_REFS, MAX_REF_BYTES = 64, 4096 # AMP_SAM_MAX_REFS, AMP_SAM_MAX_REF_BYTES: the name table of amp_bam_set_references
 OVERFLOW = -6                      # AMP_EOVERFLOW
+
+
+def zeroed_stats():
+    """The keys of LAST_RUN_STATS, all zero: a run's totals before its first piece."""
+    return dict.fromkeys(LAST_RUN_STATS, 0)
 
 
 class AmpBamBlock(C.Structure):
@@ -251,12 +255,6 @@ class BamCodec(devcodec.DeviceCodec):
         return self._encoded(info)
 
     # ---- trimmed reads as SAM text (section 14) ----------------------------------------------------------------------------------
-    def set_references(self, names):
-        """amp_bam_set_references: the names RNAME / RNEXT are written from (header.refs of the writer), once per run."""
-        enc = [n.encode("ascii") for n in names]
-        arr = (C.c_char_p * max(len(enc), 1))(*enc)
-        self._chk(self.L.amp_bam_set_references(self.h, C.c_int32(len(enc)), arr), "amp_bam_set_references")
-
     def text_check(self):
         """amp_bam_text_check behind a feed whose index stands: the info (first_odd_row -1: the device formats the piece)."""
         info = AmpBamTextInfo()
@@ -332,8 +330,8 @@ def walk(codec, src, refuse_block=None):
     blocks went through the host (counted), a damaged block or record raised what the host codec raises for the file.
     stats = the running totals (the keys of LAST_RUN_STATS).  refuse_block: development only -- that block of the file is
     treated as refused."""
-    stats = dict(pieces=0, blocks_device=0, blocks_host=0, index_rounds=0, waits=0, records=0, bytes_up=0, bytes_file=src.file_bytes)
-    stats.update((k, 0) for k in OUT_STATS + TEXT_STATS)
+    stats = zeroed_stats()
+    stats["bytes_file"] = src.file_bytes
     n_ref = len(src.references)
     first = src.first_record
     for comp, tab, k_lo, last in src:

@@ -372,6 +372,11 @@ class AlignmentWriter:
                  "".join(chr(q + 33) for q in r.qual) if r.qual is not None else "*"] + list(aux)
             self._f.write("\t".join(f) + "\n")
 
+    def flush(self):
+        """Text mode: the lines written so far leave the text layer (bytes written to the file under it come behind them)."""
+        if self.mode != "wb":
+            self._f.flush()
+
     def close(self):
         if self.mode == "wb":
             self._w.close()

@@ -19,6 +19,15 @@ from .batch import ReadBatch
 
 
 OUT_BS = 0xFF00                    # uncompressed bytes of a BGZF block of the trimmed output (the host writer's)
+MAX_REFS = 64                      # AMP_SAM_MAX_REFS / AMP_SAM_MAX_REF_BYTES of amplihip.h: the name table of amp_*_set_references
+MAX_REF_BYTES = 4096
+
+
+def names_fit(names):
+    """Can the device's name table take these reference names: at most MAX_REFS of them and MAX_REF_BYTES bytes, each printable
+    ASCII without a blank and none of "", "*", "=" (what RNAME / RNEXT mean something else by)."""
+    return len(names) <= MAX_REFS and sum(len(n) for n in names) <= MAX_REF_BYTES \
+        and all(n not in ("", "*", "=") and all(33 <= ord(c) < 127 for c in n) for n in names)
 
 
 class AmpBamOutInfo(C.Structure):
@@ -113,6 +122,12 @@ class DeviceCodec:
             self.close()
         except Exception:
             pass
+
+    def set_references(self, names):
+        """amp_*_set_references: the names RNAME / RNEXT are read as or written from (the header's @SQ lines), once per run."""
+        enc = [n.encode("ascii") for n in names]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        self._chk(self._fn("set_references")(self.h, C.c_int32(len(enc)), arr), self.prefix + "_set_references")
 
     def dev_reads(self):
         rd = abi.AmpDevReads()

@@ -23,8 +23,6 @@ import numpy as np
 from . import abi, devcodec
 
 CHUNK_BYTES = 16 << 20             # text per device chunk (AMPLIPY_SAM_CHUNK_BYTES): see the sweep in DESIGN.md section 10
-MAX_REFS = 64                      # AMP_SAM_MAX_REFS / AMP_SAM_MAX_REF_BYTES of amplihip.h
-MAX_REF_BYTES = 4096
 N_STAGES = 15                      # AMP_SAM_N_STAGES
 OUT_TEXT, OUT_BAM = 0, 1           # AMP_SAM_OUT_*
 
@@ -40,6 +38,11 @@ LAST_RUN_STATS = {"device_chunks": 0, "python_chunks": 0, "records": 0,
                   # by the host, rows the device encoded, device-to-host bytes, bytes of the file's record blocks, encodes, their waits
                   "out_blocks_device": 0, "out_blocks_host": 0, "out_rows": 0, "bytes_down": 0, "bytes_out_file": 0, "encodes": 0, "waits": 0}
 OUT_STATS = ("out_blocks_device", "out_blocks_host", "out_rows", "bytes_down", "bytes_out_file", "encodes", "waits")
+
+
+def zeroed_stats():
+    """The keys of LAST_RUN_STATS, all zero: a run's totals before its first chunk."""
+    return dict.fromkeys(LAST_RUN_STATS, 0)
 
 
 class AmpSamInfo(C.Structure):
@@ -66,11 +69,6 @@ class SamCodec(devcodec.DeviceCodec):
     def __init__(self, engine=None, twin=None):
         super().__init__("amp_sam", N_STAGES, engine, twin)
         self._out = np.zeros(1 << 16, np.uint8)
-
-    def set_references(self, names):
-        enc = [n.encode("ascii") for n in names]
-        arr = (C.c_char_p * max(len(enc), 1))(*enc)
-        self._chk(self.L.amp_sam_set_references(self.h, C.c_int32(len(enc)), arr), "amp_sam_set_references")
 
     def parse(self, text):
         """amp_sam_parse on bytes (whole lines): AmpSamInfo."""
