@@ -67,6 +67,24 @@ VAR_REC_DTYPE = np.dtype([("pos", "<i4"), ("total_depth", "<u4"), ("ref_count", 
                           ("gt_has_ref", "u1"), ("alt_col", "u1", (6,)), ("alt_count", "<u4", (6,))])
 assert VAR_REC_DTYPE.itemsize == 44
 
+# ---- QC report (amp_qc_*) ----
+QC_MAX_DEPTHS = 4
+
+
+class AmpQcParams(C.Structure):
+    _fields_ = [("n_primers", C.c_int32), ("starts", C.c_void_p), ("ends", C.c_void_p), ("primer_pos_offset", C.c_int32),
+                ("min_length", C.c_int32), ("include_no_primer", C.c_int32), ("n_regions", C.c_int32),
+                ("region_start", C.c_void_p), ("region_end", C.c_void_p), ("n_depths", C.c_int32),
+                ("depths", C.c_uint32 * QC_MAX_DEPTHS)]
+
+
+# amp_qc_reads, in the order of the struct
+QC_READ_FIELDS = ("rows", "errors", "primer_start", "primer_end", "primer_both", "primer_none", "quality",
+                  "kept", "dropped_short", "dropped_no_primer", "ref_bases_in", "ref_bases_out")
+QC_REGION_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("depth_sum", "<u8"), ("depth_min", "<u4"), ("depth_max", "<u4"),
+                            ("covered", "<u4", (QC_MAX_DEPTHS,))])
+assert QC_REGION_DTYPE.itemsize == 40
+
 
 def ptr(a):
     """Address of a contiguous numpy array (or None)."""

@@ -14,7 +14,7 @@ import os
 import sys
 from os.path import isfile
 
-from . import AMPLIPY_VERSION, calling, lib, parallel
+from . import AMPLIPY_VERSION, calling, lib, parallel, qc
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -122,7 +122,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 consensus_fn=None, primer_pos_offset=None, min_length=None, min_quality=None, sliding_window_width=None,
                 min_freq_consensus=None, min_freq_variants=None, min_depth_consensus=None, min_depth_variants=None,
                 unknown_symbol=None, include_no_primer=None, run_trim=False, run_variants=False, run_consensus=False,
-                device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None):
+                device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None, qc_fn=None, qc_regions_fn=None, qc_depths=None,
+                qc_depth_fn=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -135,6 +136,10 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     gpu_bam and gpu_sam both on: a BAM file in and trimmed reads out as SAM text (stdout or a new .sam file; trim, aio) stay on the
     device codec for BAM input, which turns the kept records into SAM lines (bam_device); a piece with a record
     the device would not write exactly like the Python codec goes through that codec.  One process only.
+    qc_fn (default: off): the amplicon QC report as JSON -- reads per primer, reads kept and dropped, depth
+    per region -- tallied on the device behind every batch's read pass, whichever codec feeds it.  qc_regions_fn: a BED of further
+    regions (ref, start, end, name); qc_depths: up to 4 depth thresholds (1, 10, 100); qc_depth_fn: depth of every position as a
+    TSV file (runs with a count table).  With all four None the engine's report is never switched on.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -164,6 +169,15 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("Unknown symbol must be exactly 1 character: %s" % unknown_symbol)
     if not (run_trim or run_variants or run_consensus):
         error("Not running any of the AmpliPy operations")
+    if qc_fn is None and (qc_regions_fn is not None or qc_depths is not None):
+        error("QC regions and QC depth thresholds need a QC report (--qc)")
+    if qc_depth_fn is not None and not (run_variants or run_consensus):
+        error("A run that only trims has no count table: no per-position depth (--qc_depth_out)")
+    qc_on = qc_fn is not None or qc_depth_fn is not None
+    if qc_on:
+        qc_depths = list(qc.DEFAULT_DEPTHS) if qc_depths is None else list(qc_depths)
+        if len(qc_depths) > 4 or any(d < 0 for d in qc_depths):
+            error("QC depth thresholds: at most 4, each non-negative: %s" % (qc_depths,))
     mode = "Trim" if run_trim and not (run_variants or run_consensus) else \
         "Variants" if run_variants and not (run_trim or run_consensus) else \
         "Consensus" if run_consensus and not (run_trim or run_variants) else "All-In-One"
@@ -201,6 +215,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
     driver = vcf = rank_error = None
+    qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
         if run_trim:
@@ -216,6 +231,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
             vcf = VcfWriter(variants_fn, ref_id)
+        if qc_on:
+            qc_regions = [(0, G, qc.WHOLE)] + (qc.load_regions(qc_regions_fn) if qc_regions_fn is not None else [])
+            qc_primers = qc.load_primer_rows(primer_fn) if run_trim else []
+            if rank == 0:
+                qc_files = [qc.open_new(fn) if fn is not None else None for fn in (qc_fn, qc_depth_fn)]
     except (Exception, SystemExit) as e:
         if dist is None:
             raise
@@ -225,6 +245,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     eng.set_params(min_quality if min_quality is not None else 20,
                    sliding_window_width if sliding_window_width is not None else 4, run_trim, do_count)
 
+    if qc_on and rank_error is None:
+        eng.qc_enable([(s, e) for s, e, _ in qc_primers], primer_pos_offset or 0, min_length if min_length is not None else 0,
+                      include_no_primer, [(s, e) for s, e, _ in qc_regions], qc_depths)
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -252,6 +275,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             tot = max(sum(b_ for _, b_ in shares), 1)
             print_log("Shares of the %d ranks: records %s; bases %s (%s %% of the job)" % (world, [r_ for r_, _ in shares], [b_ for _, b_ in shares],
                                                                                         ", ".join("%.1f" % (100.0 * b_ / tot) for _, b_ in shares)))
+        if qc_on:                        # every rank's tallies to rank 0, which adds them up
+            qc_parts = parallel.gather_objects(dist, rank, world, eng.qc_read_tallies())
         if final_trimmed_fn is not None and driver.part_writer is not None:
             # the ranks' files (all closed by now: the writer threads were joined in run()) become the one trimmed BAM
             parts = parallel.gather_objects(dist, rank, world, (driver.part_writer.path, driver.part_writer.header_bytes))
@@ -264,6 +289,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
 
     failed = True
     try:
+        qc_depth = qc_region_recs = None
+        if qc_on and rank == 0:
+            qc_tallies = qc.merge_read_tallies(qc_parts) if dist is not None else eng.qc_read_tallies()
         if do_count:
             cp = calling.call_params(min_depth_consensus if min_depth_consensus is not None else 0,
                                      min_freq_consensus if min_freq_consensus is not None else 0,
@@ -274,6 +302,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if dist is not None:
                 eng.sync()
                 parallel.allreduce_table(dist, table)      # the ONE collective of the run: every rank now holds the job's table
+            if qc_on and rank == 0:                        # depth from the job's table
+                qc_depth, qc_region_recs = eng.qc_depth(want_depth=qc_depth_fn is not None)
 
             def ins_tallies(positions):
                 triples = loop.ins_store.counted_pairs(positions)
@@ -290,8 +320,23 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 f = gzip.open(consensus_fn, "wt") if consensus_fn.lower().endswith(".gz") else open(consensus_fn, "w")
                 f.write(">sample\n%s\n" % res.consensus_string(unknown_symbol))
                 f.close()
+        if qc_on and rank == 0:
+            if qc_fn is not None:
+                report = qc.build_report(
+                    dict(primer_pos_offset=primer_pos_offset or 0, min_length=min_length, include_no_primer=bool(include_no_primer), depths=qc_depths)
+                    if run_trim else dict(depths=qc_depths),
+                    qc_tallies[0], run_trim, qc_primers, qc_tallies[1], qc_tallies[2],
+                    [name for _, _, name in qc_regions], qc_region_recs, qc_depths)
+                qc.write_json(qc_files[0], report)
+                print_log("Output QC report: %s" % qc_fn)
+                print_log(qc.summary_line(report))
+            if qc_depth_fn is not None:
+                qc.write_depth(qc_files[1], ref_id, qc_depth)
         failed = False
     finally:
+        for f in qc_files:
+            if f is not None:
+                f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)
     eng.close()
     parallel.finish(dist)
@@ -359,24 +404,33 @@ def parse_args(argv=None):
     a.add_argument("-mdv", "--min_depth_variants", required=False, type=int, default=D["min_depth_variants"], help="Minimum depth to call variant")
     a.add_argument("-n", "--unknown_symbol", required=False, type=str, default=D["unknown_symbol"], help="Character to print in regions with less than minimum coverage")
     a.add_argument("-e", "--include_no_primer", action="store_true", help="Include reads with no primers")
+    for p in (t, v, c, a):
+        p.add_argument("--qc", required=False, type=str, default=None, help="Amplicon QC report (JSON): reads per primer, reads kept and dropped, depth per region")
+        p.add_argument("--qc_regions", required=False, type=str, default=None, help="Further regions of the QC report (BED: ref, start, end, name); needs --qc")
+        p.add_argument("--qc_depths", required=False, type=str, default=None, help="Depth thresholds of the QC report, at most 4 (1,10,100 when omitted); needs --qc")
+        p.add_argument("--qc_depth_out", required=False, type=str, default=None, help="Depth of every position (TSV or TSV.gz: ref, position, depth)")
     return parser.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.qc is None and (args.qc_regions is not None or args.qc_depths is not None):
+        error("--qc_regions and --qc_depths need --qc")
+    qc_args = dict(qc_fn=args.qc, qc_regions_fn=args.qc_regions, qc_depth_fn=args.qc_depth_out,
+                   qc_depths=qc.parse_depths(args.qc_depths) if args.qc_depths is not None else None)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,
                     min_quality=args.min_quality, sliding_window_width=args.sliding_window_width,
-                    include_no_primer=args.include_no_primer, run_trim=True)
+                    include_no_primer=args.include_no_primer, run_trim=True, **qc_args)
     elif args.command == "variants":
         run_amplipy(trimmed_reads_fn=args.input, reference_fn=args.reference, variants_fn=args.output,
                     min_quality=args.min_quality, min_freq_variants=args.min_freq, min_depth_variants=args.min_depth,
-                    run_variants=True)
+                    run_variants=True, **qc_args)
     elif args.command == "consensus":
         run_amplipy(trimmed_reads_fn=args.input, reference_fn=args.reference, consensus_fn=args.output,
                     min_quality=args.min_quality, min_freq_consensus=args.min_freq, min_depth_consensus=args.min_depth,
-                    unknown_symbol=args.unknown_symbol, run_consensus=True)
+                    unknown_symbol=args.unknown_symbol, run_consensus=True, **qc_args)
     elif args.command == "aio":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output_trimmed_reads, variants_fn=args.output_variants,
@@ -385,7 +439,7 @@ def main(argv=None):
                     sliding_window_width=args.sliding_window_width, min_freq_consensus=args.min_freq_consensus,
                     min_freq_variants=args.min_freq_variants, min_depth_consensus=args.min_depth_consensus,
                     min_depth_variants=args.min_depth_variants, unknown_symbol=args.unknown_symbol,
-                    include_no_primer=args.include_no_primer, run_trim=True, run_variants=True, run_consensus=True)
+                    include_no_primer=args.include_no_primer, run_trim=True, run_variants=True, run_consensus=True, **qc_args)
 
 
 if __name__ == "__main__":

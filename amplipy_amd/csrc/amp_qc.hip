@@ -1,0 +1,383 @@
+// amp_qc.hip -- the amplicon QC report on the device (C ABI: the amp_qc_* entry points of amplihip.h).
+//
+// k_qc_reads runs behind the read pass of every batch while the report is on: one lane per read classifies it
+// (qc_classify, amp_qc.hpp) from the batch and the pass's per-read results where they lie in HBM, and the block adds what
+// its reads came to onto twelve 64-bit tallies and two per-primer read counts.  The normal input is a coordinate-sorted pile
+// of thousands of reads on one primer, so nothing is added per lane: the scalar tallies are summed per wave (ballot and
+// popcount for the counts, a shuffle sum for the two sums), then per block through LDS, and reach memory as one 64-bit add per
+// tally and block; for the primer counts neighbouring lanes with the same owner form a run whose head adds the run's length
+// -- to a histogram in LDS that the block flushes once when the primer set fits it, straight to the global arrays otherwise.
+// No step relies on the reads being sorted: an unsorted batch only makes shorter runs.
+// k_qc_depth and k_qc_regions turn the count table as it stands into depth per position and per-region figures, without
+// atomics: the output does not depend on the order anything ran in.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "amp_qc.hpp"
+
+namespace amp {
+
+struct QcState {
+    amp_qc_params p{};                    // (its pointers are not kept: the arrays are copied below)
+    int32_t *d_left = nullptr, *d_right = nullptr;        // [ref_len] owners
+    unsigned long long *d_tally = nullptr;                // [QC_N_TALLIES + 2 * n_primers]: scalars, start counts, end counts
+    int32_t *d_rstart = nullptr, *d_rend = nullptr;       // [n_regions], clamped
+    amp_qc_region *d_regions = nullptr;                   // [n_regions]
+    uint32_t *d_depth = nullptr;                          // [ref_len]
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
+    size_t tally_words() const { return (size_t)QC_N_TALLIES + 2 * (size_t)p.n_primers; }
+};
+
+struct QcReadsArgs {
+    int64_t n;
+    const int32_t *pos;
+    const uint32_t *cig_off32, *cig;
+    const int32_t *ref_len_out;
+    const uint8_t *trim_flags, *status;
+    const int32_t *left_owner, *right_owner;
+    unsigned long long *tally;
+    int32_t n_primers;
+    QcReadParams P;
+};
+
+__device__ __forceinline__ int qc_lane() { return (int)(threadIdx.x & 63u); }
+
+// Lanes of a wave that carry the same owner as their left neighbour form a run; the run's first lane adds its length.
+// Every lane of the wave calls this (owner -1: nothing to add).
+template <class Add>
+__device__ __forceinline__ void qc_add_runs(int32_t owner, Add add) {
+    const int lane = qc_lane();
+    const int32_t prev = __shfl_up(owner, 1);
+    const bool head = lane == 0 || prev != owner;
+    const unsigned long long heads = __ballot(head);
+    if (head && owner >= 0) {
+        const unsigned long long behind = (heads >> lane) >> 1;       // run heads to the right of this lane
+        add(owner, (uint32_t)(behind ? __ffsll((long long)behind) : 64 - lane));
+    }
+}
+
+template <bool LDS_HIST>
+__global__ void __launch_bounds__(QC_BLOCK)
+k_qc_reads(QcReadsArgs a) {
+    __shared__ uint32_t s_hist[LDS_HIST ? QC_LDS_COUNTERS : 1];
+    __shared__ unsigned long long s_part[QC_BLOCK / 64][QC_N_TALLIES];
+    const int tid = (int)threadIdx.x, lane = qc_lane(), wave = tid >> 6;
+    const int n_hist = 2 * a.n_primers;
+    if (LDS_HIST) {
+        for (int k = tid; k < n_hist; k += QC_BLOCK) s_hist[k] = 0u;
+        __syncthreads();
+    }
+    unsigned long long *const g_start = a.tally + QC_N_TALLIES, *const g_end = g_start + a.n_primers;
+    uint32_t cnt[QC_N_FLAGS];                 // wave-uniform: reads of this wave with the bit set
+#pragma unroll
+    for (int k = 0; k < QC_N_FLAGS; ++k) cnt[k] = 0u;
+    unsigned long long sum_in = 0ull, sum_out = 0ull;       // per lane
+    // grid-stride over tiles of QC_BLOCK reads; the bound is the same for every lane of the block, so the shuffles and
+    // ballots below always see whole waves
+    for (int64_t base = (int64_t)blockIdx.x * QC_BLOCK; base < a.n; base += (int64_t)gridDim.x * QC_BLOCK) {
+        const int64_t i = base + tid;
+        uint32_t bits = 0u;
+        int32_t own_s = -1, own_e = -1;
+        if (i < a.n) {
+            const uint32_t c0 = a.cig_off32[i], c1 = a.cig_off32[i + 1];
+            const uint32_t st = a.status ? a.status[i] : 0u;
+            const int32_t rl = a.P.do_trim ? a.ref_len_out[i] : 0;
+            const uint32_t tf = a.P.do_trim ? a.trim_flags[i] : 0u;
+            const QcRead r = qc_classify(a.pos[i], a.cig + c0, c1 - c0, rl, tf, st, a.P, a.left_owner, a.right_owner);
+            bits = r.bits; own_s = r.owner_start; own_e = r.owner_end;
+            sum_in += r.ref_in; sum_out += r.ref_out;
+        }
+#pragma unroll
+        for (int k = 0; k < QC_N_FLAGS; ++k) cnt[k] += (uint32_t)__popcll(__ballot((bits >> k) & 1u));
+        if (a.P.do_trim && a.n_primers > 0) {
+            if (LDS_HIST) {
+                qc_add_runs(own_s, [&](int32_t o, uint32_t len) { atomicAdd(&s_hist[o], len); });
+                qc_add_runs(own_e, [&](int32_t o, uint32_t len) { atomicAdd(&s_hist[a.n_primers + o], len); });
+            } else {
+                qc_add_runs(own_s, [&](int32_t o, uint32_t len) { atomicAdd(&g_start[o], (unsigned long long)len); });
+                qc_add_runs(own_e, [&](int32_t o, uint32_t len) { atomicAdd(&g_end[o], (unsigned long long)len); });
+            }
+        }
+    }
+    // the two sums over the wave, then everything over the block's waves, then one add per tally
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        sum_in += __shfl_down(sum_in, d);
+        sum_out += __shfl_down(sum_out, d);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < QC_N_FLAGS; ++k) s_part[wave][k] = cnt[k];
+        s_part[wave][QC_REF_BASES_IN] = sum_in;
+        s_part[wave][QC_REF_BASES_OUT] = sum_out;
+    }
+    __syncthreads();
+    if (tid < QC_N_TALLIES) {
+        unsigned long long t = 0ull;
+        for (int w = 0; w < QC_BLOCK / 64; ++w) t += s_part[w][tid];
+        if (t) atomicAdd(&a.tally[tid], t);
+    }
+    if (LDS_HIST) {
+        for (int k = tid; k < n_hist; k += QC_BLOCK) {
+            const uint32_t v = s_hist[k];
+            if (v) atomicAdd(&g_start[k], (unsigned long long)v);       // (the end counts lie behind the start counts here as there)
+        }
+    }
+}
+
+__global__ void __launch_bounds__(QC_BLOCK)
+k_qc_depth(const uint32_t *__restrict__ counts, int32_t ref_len, uint32_t *__restrict__ depth) {
+    for (int64_t p = (int64_t)blockIdx.x * QC_BLOCK + threadIdx.x; p < ref_len; p += (int64_t)gridDim.x * QC_BLOCK)
+        depth[p] = qc_depth_of(counts + (size_t)p * AMP_NSYM);
+}
+
+__device__ __forceinline__ QcRegionAcc qc_shfl_down(const QcRegionAcc &a, int d) {
+    QcRegionAcc b;
+    b.sum = __shfl_down((unsigned long long)a.sum, d);
+    b.mn = __shfl_down(a.mn, d);
+    b.mx = __shfl_down(a.mx, d);
+#pragma unroll
+    for (int k = 0; k < AMP_QC_MAX_DEPTHS; ++k) b.covered[k] = __shfl_down(a.covered[k], d);
+    return b;
+}
+
+struct QcDepths { int32_t n; uint32_t d[AMP_QC_MAX_DEPTHS]; };
+
+__global__ void __launch_bounds__(QC_BLOCK)
+k_qc_regions(const uint32_t *__restrict__ depth, int32_t n_regions, const int32_t *__restrict__ rstart, const int32_t *__restrict__ rend,
+             QcDepths dp, amp_qc_region *__restrict__ out) {
+    __shared__ QcRegionAcc s_acc[QC_BLOCK / 64];
+    const int tid = (int)threadIdx.x, lane = qc_lane(), wave = tid >> 6;
+    for (int32_t r = (int32_t)blockIdx.x; r < n_regions; r += (int32_t)gridDim.x) {
+        const int32_t s = rstart[r], e = rend[r];           // clamped by the host: 0 <= s <= e <= ref_len
+        QcRegionAcc acc = qc_region_empty();
+        for (int64_t p = (int64_t)s + tid; p < e; p += QC_BLOCK) qc_region_add(acc, depth[p], dp.n, dp.d);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const QcRegionAcc o = qc_shfl_down(acc, d);
+            qc_region_merge(acc, o);
+        }
+        if (lane == 0) s_acc[wave] = acc;
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < QC_BLOCK / 64; ++w) qc_region_merge(acc, s_acc[w]);
+            out[r] = qc_region_result(s, e, acc);
+        }
+        __syncthreads();
+    }
+}
+
+#define QCCHK(q, call)                                                                                                       \
+    do {                                                                                                                     \
+        hipError_t e__ = (call);                                                                                             \
+        if (e__ != hipSuccess) {                                                                                             \
+            snprintf((q).err, (q).err_cap, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__);      \
+            return e__ == hipErrorOutOfMemory ? AMP_ENOMEM : AMP_EHIP;                                                       \
+        }                                                                                                                    \
+    } while (0)
+
+struct QcGuard {      // the ctx's device is current for the duration of a call
+    int prev = -1;
+    explicit QcGuard(int device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != device) (void)hipSetDevice(device);
+    }
+    ~QcGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+static void qc_free(QcState *s) {
+    if (!s) return;
+    void *bufs[] = {s->d_left, s->d_right, s->d_tally, s->d_rstart, s->d_rend, s->d_regions, s->d_depth};
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    delete s;
+}
+
+int qc_check_out(amp_ctx *c, const amp_trim_out *o) {
+    const QcCtx q = ctx_qc(c);
+    if (q.do_trim && (!o || !o->new_pos || !o->ref_len || !o->trim_flags || !o->status)) {
+        snprintf(q.err, q.err_cap, "the QC report needs new_pos, ref_len, trim_flags and status of a trimming pass");
+        return AMP_EINVAL;
+    }
+    return AMP_OK;
+}
+
+int qc_enqueue_reads(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
+    const QcCtx q = ctx_qc(c);
+    QcState *s = (QcState *)*q.state;
+    if (!s) return AMP_ESTATE;
+    s->timed = false;
+    const int64_t n = rd->n_reads;
+    if (n <= 0) return AMP_OK;
+    int rc = qc_check_out(c, o);
+    if (rc != AMP_OK) return rc;
+    QcReadsArgs a;
+    a.n = n; a.pos = rd->pos; a.cig_off32 = rd->cig_off32; a.cig = rd->cig;
+    a.ref_len_out = o ? o->ref_len : nullptr; a.trim_flags = o ? o->trim_flags : nullptr; a.status = o ? o->status : nullptr;
+    a.left_owner = s->d_left; a.right_owner = s->d_right;
+    a.tally = s->d_tally; a.n_primers = s->p.n_primers;
+    a.P = QcReadParams{q.ref_len, q.do_trim ? 1 : 0, s->p.min_length, s->p.include_no_primer};
+    // a block takes QC_TILES_PER_BLOCK tiles and more (its LDS histogram and its twelve adds are paid once), up to
+    // QC_BLOCKS_PER_CU blocks per CU; from there on the blocks take more tiles each
+    const int64_t tiles = (n + QC_BLOCK - 1) / QC_BLOCK;
+    const int64_t grid = std::min<int64_t>(std::max<int64_t>((tiles + QC_TILES_PER_BLOCK - 1) / QC_TILES_PER_BLOCK, 1), (int64_t)QC_BLOCKS_PER_CU * q.n_cu);
+    QCCHK(q, hipEventRecord(s->ev0, q.stream));
+    if (2 * (int64_t)s->p.n_primers <= QC_LDS_COUNTERS) k_qc_reads<true><<<(unsigned)grid, QC_BLOCK, 0, q.stream>>>(a);
+    else k_qc_reads<false><<<(unsigned)grid, QC_BLOCK, 0, q.stream>>>(a);
+    QCCHK(q, hipGetLastError());
+    QCCHK(q, hipEventRecord(s->ev1, q.stream));
+    s->timed = true;
+    return AMP_OK;
+}
+
+int qc_reset(amp_ctx *c) {
+    const QcCtx q = ctx_qc(c);
+    QcState *s = (QcState *)*q.state;
+    if (!s) return AMP_OK;
+    QCCHK(q, hipMemsetAsync(s->d_tally, 0, s->tally_words() * sizeof(unsigned long long), q.stream));
+    return AMP_OK;
+}
+
+void qc_destroy(amp_ctx *c) {
+    const QcCtx q = ctx_qc(c);
+    qc_free((QcState *)*q.state);
+    *q.state = nullptr;
+    *q.on = false;
+}
+
+}  // namespace amp
+
+using namespace amp;
+
+extern "C" {
+
+int amp_qc_find_primer_owners(int32_t ref_len, int32_t n, const int32_t *starts, const int32_t *ends, int32_t off,
+                              int32_t *left_owner, int32_t *right_owner) {
+    if (ref_len < 0 || n < 0 || off < 0 || (n && (!starts || !ends)) || (ref_len && (!left_owner || !right_owner))) return AMP_EINVAL;
+    // a sweep over the positions with the primers whose window has opened and whose index is not below that of the first
+    // one still open, in index (= start) order; closed windows among them are skipped
+    std::vector<int32_t> open((size_t)std::max(n, 1));
+    int head = 0, tail = 0, next = 0;
+    for (int32_t p = 0; p < ref_len; ++p) {
+        while (next < n && (int64_t)p >= (int64_t)starts[next] - off) open[tail++] = next++;
+        while (head != tail && (int64_t)p >= (int64_t)ends[open[head]] + off) ++head;
+        int32_t lo = -1, ro = -1;
+        for (int k = head; k < tail; ++k) {
+            const int32_t i = open[k];
+            if ((int64_t)p >= (int64_t)ends[i] + off) continue;
+            if (lo < 0 || ends[i] > ends[lo]) lo = i;
+            if (ro < 0 || starts[i] < starts[ro]) ro = i;
+        }
+        left_owner[p] = lo; right_owner[p] = ro;
+    }
+    return AMP_OK;
+}
+
+int amp_qc_enable(amp_ctx *c, const amp_qc_params *p) {
+    if (!c) return AMP_EINVAL;
+    const QcCtx q = ctx_qc(c);
+    if (!p) { *q.on = false; return AMP_OK; }
+    if (p->n_primers < 0 || (p->n_primers && (!p->starts || !p->ends)) || p->primer_pos_offset < 0 || p->n_regions < 0 ||
+        (p->n_regions && (!p->region_start || !p->region_end)) || p->n_depths < 0 || p->n_depths > AMP_QC_MAX_DEPTHS) return AMP_EINVAL;
+    for (int32_t k = 1; k < p->n_primers; ++k)
+        if (p->starts[k] < p->starts[k - 1] || (p->starts[k] == p->starts[k - 1] && p->ends[k] < p->ends[k - 1])) return AMP_EINVAL;
+    if (q.do_trim && !q.have_primers) return AMP_ESTATE;
+    QcGuard g(q.device);
+    QCCHK(q, hipStreamSynchronize(q.stream));        // (a report that is replaced may still have a kernel in flight)
+    qc_free((QcState *)*q.state);
+    *q.state = nullptr; *q.on = false;
+    QcState *s = new (std::nothrow) QcState();
+    if (!s) return AMP_ENOMEM;
+    struct Drop { QcState *s; ~Drop() { qc_free(s); } } drop{s};      // until the state is handed to the ctx
+    s->p = *p;
+    s->p.starts = s->p.ends = s->p.region_start = s->p.region_end = nullptr;
+    const size_t G = (size_t)q.ref_len, R = (size_t)p->n_regions;
+    std::vector<int32_t> lo(G), ro(G), rs(R), re(R);
+    int rc = amp_qc_find_primer_owners(q.ref_len, p->n_primers, p->starts, p->ends, p->primer_pos_offset, lo.data(), ro.data());
+    if (rc != AMP_OK) return rc;
+    for (size_t r = 0; r < R; ++r) {
+        rs[r] = p->region_start[r]; re[r] = p->region_end[r];
+        qc_region_clamp(q.ref_len, rs[r], re[r]);
+    }
+    QCCHK(q, hipMalloc((void **)&s->d_left, G * 4));
+    QCCHK(q, hipMalloc((void **)&s->d_right, G * 4));
+    QCCHK(q, hipMalloc((void **)&s->d_depth, G * 4));
+    QCCHK(q, hipMalloc((void **)&s->d_tally, s->tally_words() * sizeof(unsigned long long)));
+    if (R) {
+        QCCHK(q, hipMalloc((void **)&s->d_rstart, R * 4));
+        QCCHK(q, hipMalloc((void **)&s->d_rend, R * 4));
+        QCCHK(q, hipMalloc((void **)&s->d_regions, R * sizeof(amp_qc_region)));
+        QCCHK(q, hipMemcpyAsync(s->d_rstart, rs.data(), R * 4, hipMemcpyHostToDevice, q.stream));
+        QCCHK(q, hipMemcpyAsync(s->d_rend, re.data(), R * 4, hipMemcpyHostToDevice, q.stream));
+    }
+    QCCHK(q, hipMemcpyAsync(s->d_left, lo.data(), G * 4, hipMemcpyHostToDevice, q.stream));
+    QCCHK(q, hipMemcpyAsync(s->d_right, ro.data(), G * 4, hipMemcpyHostToDevice, q.stream));
+    QCCHK(q, hipMemsetAsync(s->d_tally, 0, s->tally_words() * sizeof(unsigned long long), q.stream));
+    QCCHK(q, hipEventCreate(&s->ev0));
+    QCCHK(q, hipEventCreate(&s->ev1));
+    QCCHK(q, hipStreamSynchronize(q.stream));        // (the host vectors go away)
+    drop.s = nullptr;
+    *q.state = s; *q.on = true;
+    return AMP_OK;
+}
+
+int amp_qc_read_tallies(amp_ctx *c, amp_qc_reads *out, uint64_t *primer_reads_start, uint64_t *primer_reads_end) {
+    if (!c) return AMP_EINVAL;
+    const QcCtx q = ctx_qc(c);
+    QcState *s = (QcState *)*q.state;
+    if (!s) return AMP_ESTATE;
+    QcGuard g(q.device);
+    const size_t np = (size_t)s->p.n_primers;
+    if (out) QCCHK(q, hipMemcpyAsync(out, s->d_tally, sizeof(amp_qc_reads), hipMemcpyDeviceToHost, q.stream));
+    if (primer_reads_start && np) QCCHK(q, hipMemcpyAsync(primer_reads_start, s->d_tally + QC_N_TALLIES, np * 8, hipMemcpyDeviceToHost, q.stream));
+    if (primer_reads_end && np) QCCHK(q, hipMemcpyAsync(primer_reads_end, s->d_tally + QC_N_TALLIES + np, np * 8, hipMemcpyDeviceToHost, q.stream));
+    QCCHK(q, hipStreamSynchronize(q.stream));
+    return AMP_OK;
+}
+
+int amp_qc_depth(amp_ctx *c, uint32_t *depth, amp_qc_region *regions) {
+    if (!c) return AMP_EINVAL;
+    const QcCtx q = ctx_qc(c);
+    QcState *s = (QcState *)*q.state;
+    if (!s) return AMP_ESTATE;
+    QcGuard g(q.device);
+    const int64_t blocks = ((int64_t)q.ref_len + QC_BLOCK - 1) / QC_BLOCK;
+    k_qc_depth<<<(unsigned)std::min<int64_t>(blocks, (int64_t)QC_BLOCKS_PER_CU * q.n_cu), QC_BLOCK, 0, q.stream>>>(q.counts, q.ref_len, s->d_depth);
+    QCCHK(q, hipGetLastError());
+    if (depth) QCCHK(q, hipMemcpyAsync(depth, s->d_depth, (size_t)q.ref_len * 4, hipMemcpyDeviceToHost, q.stream));
+    const int32_t R = s->p.n_regions;
+    if (regions && R) {
+        QcDepths dp;
+        dp.n = s->p.n_depths;
+        for (int k = 0; k < AMP_QC_MAX_DEPTHS; ++k) dp.d[k] = k < dp.n ? s->p.depths[k] : 0u;
+        k_qc_regions<<<(unsigned)std::min<int64_t>(R, (int64_t)QC_BLOCKS_PER_CU * q.n_cu), QC_BLOCK, 0, q.stream>>>(s->d_depth, R, s->d_rstart, s->d_rend, dp, s->d_regions);
+        QCCHK(q, hipGetLastError());
+        QCCHK(q, hipMemcpyAsync(regions, s->d_regions, (size_t)R * sizeof(amp_qc_region), hipMemcpyDeviceToHost, q.stream));
+    }
+    QCCHK(q, hipStreamSynchronize(q.stream));
+    return AMP_OK;
+}
+
+int amp_qc_last_ms(amp_ctx *c, float *reads_ms) {
+    if (!c) return AMP_EINVAL;
+    const QcCtx q = ctx_qc(c);
+    QcState *s = (QcState *)*q.state;
+    if (!s || !s->timed) return AMP_ESTATE;
+    QcGuard g(q.device);
+    QCCHK(q, hipEventSynchronize(s->ev1));
+    float t = 0;
+    QCCHK(q, hipEventElapsedTime(&t, s->ev0, s->ev1));
+    if (reads_ms) *reads_ms = t;
+    return AMP_OK;
+}
+
+}  // extern "C"

@@ -26,6 +26,7 @@
 #include "amp_fast7.hpp"
 #include "amp_wave.hpp"
 #include "amp_ins.hpp"
+#include "amp_qc.hpp"
 #define AMP_CODEC_CTX_ONLY
 #include "amp_codec.hpp"
 
@@ -97,6 +98,8 @@ struct amp_ctx {
     int kernel_variant = 0;       // 0 = by the batch (4 for reads of up to 152 padded bases on average, else 5), 5 = fast kernel (second generation) + general pass, 4 = its first generation, 1 = one lane per read (reference kernels), 2 = fused tile kernel, 3 = k_trim + k_scan + k_tile<SPLIT>,
                                   // 4 = k_fast (simple reads, one pass over their bytes) + k_tile<LIST> over the others
     uint32_t *dbg_dcnt = nullptr; int dbg_grid = 0;
+    bool qc_on = false;            // the QC report (amp_qc_enable): one more kernel behind the read pass
+    void *qc = nullptr;            // ... and its state, owned by amp_qc.hip
     uint32_t phases = 0xFFu;       // always 0xFF in the shipped library; -DAMP_DEV builds can mask phases of the tile kernel (AMPLIHIP_PHASES)
     char err[320] = {0};
 };
@@ -761,6 +764,10 @@ __global__ void k_event_strings(amp_dev_reads rd, uint64_t read_base, int64_t n_
 namespace amp {
 hipStream_t ctx_stream(const amp_ctx *c) { return c->stream; }
 int ctx_device(const amp_ctx *c) { return c->device; }
+// ... and the QC report (amp_qc.hip)
+QcCtx ctx_qc(amp_ctx *c) {
+    return QcCtx{c->device, c->ref_len, c->stream, c->d_counts, c->do_trim, c->have_primers ? 1 : 0, c->n_cu, c->err, sizeof(c->err), &c->qc_on, &c->qc};
+}
 }  // namespace amp
 
 // ---------------------------------------------------------------------------------------
@@ -888,6 +895,7 @@ void amp_ctx_destroy(amp_ctx *c) {
     if (!c) return;
     Guard g(c);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    qc_destroy(c);
     if (c->own_counts && c->d_counts) (void)hipFree(c->d_counts);
     if (c->d_min_start) (void)hipFree(c->d_min_start);
     if (c->d_max_end) (void)hipFree(c->d_max_end);
@@ -1116,7 +1124,10 @@ int amp_process_batch_device(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
                         !rd->seq || !rd->qual)) return AMP_EINVAL;
     Guard g(c);
     c->staged_n = -1;          // (amp_event_strings(reads = NULL) refers to the last HOST batch: there is none now)
-    return launch_reads(c, rd, read_base, dev_out);
+    if (c->qc_on && rd->n_reads) { const int qrc = qc_check_out(c, dev_out); if (qrc != AMP_OK) return qrc; }
+    const int rc = launch_reads(c, rd, read_base, dev_out);
+    if (rc == AMP_OK && c->qc_on) return qc_enqueue_reads(c, rd, dev_out);      // k_qc_reads on the ctx stream
+    return rc;
 }
 
 int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const amp_trim_out *out) {
@@ -1154,6 +1165,7 @@ int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const 
                       c->o_flags.as<uint8_t>(), c->o_status.as<uint8_t>()};
     int rc = launch_reads(c, &rd, read_base, &dout);
     if (rc != AMP_OK) return rc;
+    if (c->qc_on) { rc = qc_enqueue_reads(c, &rd, &dout); if (rc != AMP_OK) return rc; }      // k_qc_reads on the ctx stream
     if (out) {
         if (out->new_pos) HIPCHK(c, hipMemcpyAsync(out->new_pos, dout.new_pos, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         if (out->new_ncig) HIPCHK(c, hipMemcpyAsync(out->new_ncig, dout.new_ncig, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -1320,7 +1332,7 @@ int amp_reset(amp_ctx *c) {
     constexpr size_t ctr_words = 2 * CTR_WORDS;      // the 64-bit counters as the 32-bit words k_reset writes
     k_reset<<<(unsigned)((words + ctr_words + 1023) / 1024), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, ctr_words);
     HIPCHK(c, hipGetLastError());
-    return AMP_OK;
+    return qc_reset(c);            // (the report's tallies, when there is one)
 }
 
 // RCCL is resolved at run time so the library has no link-time dependency on it and uses

@@ -37,6 +37,7 @@ EXPORTS = [
     "amp_sam_set_output", "amp_sam_encode", "amp_sam_encode_bytes", "amp_sam_encoded_to_host", "amp_sam_encoded_blocks", "amp_sam_stream_to_host",
     "amp_sam_first_bad", "amp_sam_waits",
     "amp_bam_set_references", "amp_bam_text_check", "amp_bam_format",
+    "amp_qc_find_primer_owners", "amp_qc_enable", "amp_qc_read_tallies", "amp_qc_depth", "amp_qc_last_ms",
 ]
 
 
@@ -82,6 +83,21 @@ def find_overlapping_primers(ref_len, primers, offset):
     if rc:
         raise AmpliHipError(rc, "amp_find_overlapping_primers")
     return mn, mx, int(mpl.value)
+
+
+def find_primer_owners(ref_len, primers, offset):
+    """amp_qc_find_primer_owners -> (left_owner, right_owner), int32[ref_len] of indices into sorted(primers); -1: no primer
+    covers the position.  left_owner[p] is the primer max_primer_end[p] comes from (A:450), right_owner[p] the one
+    min_primer_start[p] comes from (A:451); ties go to the smallest index."""
+    L = load()
+    ps = sorted((int(a), int(b)) for a, b in primers)
+    st = np.array([p[0] for p in ps], np.int32); en = np.array([p[1] for p in ps], np.int32)
+    lo = np.empty(ref_len, np.int32); ro = np.empty(ref_len, np.int32)
+    rc = L.amp_qc_find_primer_owners(C.c_int32(ref_len), C.c_int32(len(ps)), C.c_void_p(abi.ptr(st)), C.c_void_p(abi.ptr(en)),
+                                     C.c_int32(offset), C.c_void_p(abi.ptr(lo)), C.c_void_p(abi.ptr(ro)))
+    if rc:
+        raise AmpliHipError(rc, "amp_qc_find_primer_owners")
+    return lo, ro
 
 
 class Engine:
@@ -245,6 +261,48 @@ class Engine:
 
     def reset(self):
         self._chk(self.L.amp_reset(self.h), "amp_reset")
+
+    # ---- QC report -------------------------------------------------------------------
+    def qc_enable(self, primers=(), primer_pos_offset=0, min_length=0, include_no_primer=False, regions=(), depths=()):
+        """amp_qc_enable: the report on, its tallies zero.  primers: (start, end) pairs (sorted here like load_primers does);
+        regions: (start, end) pairs, the caller's region 0 included; depths: up to 4 thresholds.  ``qc_disable`` turns it off."""
+        ps = sorted((int(a), int(b)) for a, b in primers)
+        st = np.array([p[0] for p in ps], np.int32); en = np.array([p[1] for p in ps], np.int32)
+        rs = np.array([int(r[0]) for r in regions], np.int32); re_ = np.array([int(r[1]) for r in regions], np.int32)
+        if len(depths) > abi.QC_MAX_DEPTHS:
+            raise ValueError("at most %d depth thresholds" % abi.QC_MAX_DEPTHS)
+        p = abi.AmpQcParams(len(ps), abi.ptr(st) if len(ps) else None, abi.ptr(en) if len(ps) else None, int(primer_pos_offset),
+                            int(min_length), int(bool(include_no_primer)), rs.size, abi.ptr(rs) if rs.size else None,
+                            abi.ptr(re_) if rs.size else None, len(depths))
+        for k, d in enumerate(depths):
+            p.depths[k] = int(d)
+        self._chk(self.L.amp_qc_enable(self.h, C.byref(p)), "amp_qc_enable")
+        self._qc_shape = (len(ps), int(rs.size))
+
+    def qc_disable(self):
+        self._chk(self.L.amp_qc_enable(self.h, None), "amp_qc_enable")
+
+    def qc_read_tallies(self):
+        """amp_qc_read_tallies -> (dict of the amp_qc_reads fields, reads_start uint64[n_primers], reads_end uint64[n_primers])."""
+        n_primers = getattr(self, "_qc_shape", (0, 0))[0]
+        t = np.zeros(len(abi.QC_READ_FIELDS), np.uint64)
+        ps = np.zeros(max(n_primers, 1), np.uint64); pe = np.zeros(max(n_primers, 1), np.uint64)
+        self._chk(self.L.amp_qc_read_tallies(self.h, C.c_void_p(abi.ptr(t)), C.c_void_p(abi.ptr(ps)), C.c_void_p(abi.ptr(pe))),
+                  "amp_qc_read_tallies")
+        return {k: int(v) for k, v in zip(abi.QC_READ_FIELDS, t)}, ps[:n_primers], pe[:n_primers]
+
+    def qc_depth(self, want_depth=True):
+        """amp_qc_depth on the table as it stands -> (depth uint32[ref_len] or None, QC_REGION_DTYPE[n_regions])."""
+        depth = np.zeros(self.ref_len, np.uint32) if want_depth else None
+        n_regions = getattr(self, "_qc_shape", (0, 0))[1]
+        regions = np.zeros(max(n_regions, 1), abi.QC_REGION_DTYPE)
+        self._chk(self.L.amp_qc_depth(self.h, C.c_void_p(abi.ptr(depth)), C.c_void_p(abi.ptr(regions))), "amp_qc_depth")
+        return depth, regions[:n_regions]
+
+    def qc_last_ms(self):
+        t = C.c_float(0)
+        self._chk(self.L.amp_qc_last_ms(self.h, C.byref(t)), "amp_qc_last_ms")
+        return float(t.value)
 
     # ---- calling ---------------------------------------------------------------------
     def set_reference(self, ref_seq):

@@ -634,6 +634,60 @@ int amp_bam_text_check(amp_bam *s, amp_bam_text_info *info);
  * ran.  Two waits at most: the sizes, then the copy.  The text buffer belongs to the amp_bam and grows to the largest piece. */
 int amp_bam_format(amp_bam *s, int32_t min_length, int32_t include_no_primer, uint8_t *out, int64_t cap, amp_bam_text_info *info);
 
+/* ---- amplicon QC report (opt-in) ---------------------------------------------------------------------------
+ * What a run of an amplicon panel is looked at for first, from the data that is in HBM when the read pass ends: how many reads
+ * each primer took, how many reads were kept or dropped, how deep each region is covered.  The reference has no such report; its
+ * numbers are defined from the reference's own rules.  A read's start trim is looked up at its ORIGINAL reference_start and its
+ * end trim at its original reference_end - 1 (AmpliPy.py:450-451): the primer a trim is counted for is the OWNER of that position,
+ * the primer that gave the table entry trim_read read there.  A read is kept, dropped as too short or dropped for lack of a primer
+ * by the write filter (AmpliPy.py:910).  With the report on, one more kernel runs behind the read pass of every amp_process_batch*
+ * on the ctx stream; nothing per read leaves the device.  With it off (the default) nothing changes. */
+#define AMP_QC_MAX_DEPTHS 4
+typedef struct amp_qc_params {
+    int32_t n_primers;               /* 0 is legal: a run without trimming has no BED */
+    const int32_t *starts, *ends;    /* host; sorted ascending by (start, end) like amp_find_overlapping_primers */
+    int32_t primer_pos_offset;
+    int32_t min_length, include_no_primer;   /* the write filter, AmpliPy.py:910 */
+    int32_t n_regions;
+    const int32_t *region_start, *region_end;   /* host; half-open, clamped to [0, ref_len) by the library; region 0 is the caller's to supply */
+    int32_t n_depths;                /* 0..AMP_QC_MAX_DEPTHS */
+    uint32_t depths[AMP_QC_MAX_DEPTHS];
+} amp_qc_params;
+/* 64-bit tallies over all batches since amp_reset.  A row with a non-zero status adds to rows and errors only.  Without do_trim only
+ * rows, errors and ref_bases_in are filled.  With it: the three AMP_TRIM_* bits (AmpliPy.py:687), both / neither primer bit, and
+ * exactly one of kept / dropped_short / dropped_no_primer (AmpliPy.py:910), so kept + dropped_short + dropped_no_primer = rows - errors.
+ * ref_bases_in: reference length of the original CIGAR (ops M D N = X); ref_bases_out: reference_length after trimming. */
+typedef struct amp_qc_reads {
+    uint64_t rows, errors, primer_start, primer_end, primer_both, primer_none, quality,
+        kept, dropped_short, dropped_no_primer, ref_bases_in, ref_bases_out;
+} amp_qc_reads;
+/* depth = A + C + G + T + N + '-' of the count table (the insertion tally is not part of it; the sum must stay below 2^32 like
+ * amp_pos_call.total_depth).  covered[k] = positions of the region with depth >= depths[k].  An empty region has end = start and zeros. */
+typedef struct amp_qc_region {
+    int32_t start, end; /* clamped */
+    uint64_t depth_sum;
+    uint32_t depth_min, depth_max;
+    uint32_t covered[AMP_QC_MAX_DEPTHS];
+} amp_qc_region;
+/* The owners of every reference position (host, no ctx, no GPU).  Primer i covers p when starts[i] - offset <= p < ends[i] + offset
+ * (the window of find_overlapping_primers, AmpliPy.py:174-209).  left_owner[p]: the covering primer with the largest end -- the one
+ * max_primer_end[p] comes from, read at AmpliPy.py:450; right_owner[p]: the one with the smallest start (min_primer_start[p],
+ * AmpliPy.py:451).  Ties go to the smallest index; -1 where no primer covers p. */
+int amp_qc_find_primer_owners(int32_t ref_len, int32_t n, const int32_t *starts, const int32_t *ends, int32_t offset,
+                              int32_t *left_owner, int32_t *right_owner);
+/* p == NULL: off (the default; the tallies read so far stay readable).  Otherwise on, with tallies of zero: copies everything it is
+ * given.  AMP_ESTATE when the ctx trims (amp_set_params) and has no primer tables (amp_set_primers).  With the report on and do_trim
+ * set, amp_process_batch_device refuses a dev_out without new_pos, ref_len, trim_flags or status (AMP_EINVAL) before anything runs. */
+int amp_qc_enable(amp_ctx *ctx, const amp_qc_params *p);
+/* The tallies since amp_reset (waits for the stream).  primer_reads_start[i] / primer_reads_end[i]: reads whose start / end trim
+ * (AmpliPy.py:450-451) primer i owns; [n_primers] each, either may be NULL. */
+int amp_qc_read_tallies(amp_ctx *ctx, amp_qc_reads *out, uint64_t *primer_reads_start, uint64_t *primer_reads_end);
+/* Depth per position and the figures of the regions given to amp_qc_enable, from the table as it stands (several ranks: after
+ * amp_reduce / the all-reduce).  Host pointers. */
+int amp_qc_depth(amp_ctx *ctx, uint32_t *depth /* [ref_len] or NULL */, amp_qc_region *regions /* [n_regions] or NULL */);
+/* Time of the report's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+int amp_qc_last_ms(amp_ctx *ctx, float *reads_ms);
+
 #ifdef __cplusplus
 }
 #endif
