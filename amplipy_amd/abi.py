@@ -67,6 +67,10 @@ VAR_REC_DTYPE = np.dtype([("pos", "<i4"), ("total_depth", "<u4"), ("ref_count", 
                           ("gt_has_ref", "u1"), ("alt_col", "u1", (6,)), ("alt_count", "<u4", (6,))])
 assert VAR_REC_DTYPE.itemsize == 44
 
+# ---- strand and base-quality tallies (amp_strand_*): rev uint32[G][NSYM], qsum uint64[G][STRAND_QSUM_COLS] ----
+STRAND_QSUM_COLS = 5
+STRAND_CELLS = 11          # NSYM + STRAND_QSUM_COLS: the columns of one position when both tables travel as one
+
 # ---- QC report (amp_qc_*) ----
 QC_MAX_DEPTHS = 4
 

@@ -14,7 +14,7 @@ import os
 import sys
 from os.path import isfile
 
-from . import AMPLIPY_VERSION, calling, lib, parallel, qc
+from . import AMPLIPY_VERSION, calling, lib, parallel, qc, strand as strand_mod
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -78,7 +78,8 @@ def open_device_bam_text(input_fn, output_fn):
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
-    def __init__(self, fn, ref_id):
+    def __init__(self, fn, ref_id, strand=False):
+        """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables)."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -101,17 +102,18 @@ class VcfWriter:
         w("##INFO=<ID=ALT_DP,Number=1,Type=String,Description=\"Depth of alternate base\">\n")
         w("##INFO=<ID=REF_FREQ,Number=1,Type=Float,Description=\"Frequency of reference base\">\n")
         w("##INFO=<ID=ALT_FREQ,Number=1,Type=String,Description=\"Frequency of alternate base\">\n")
+        if strand:
+            w(strand_mod.HEADER_LINES)
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
-    def line(self, r):
-        return "%s\t%d\t.\t%s\t%s\t.\tPASS\tDP=%d;REF_DP=%d;ALT_DP=%s;REF_FREQ=%g;ALT_FREQ=%s\tGT\t%s\n" % (
-            self.ref_id, r.pos + 1, r.ref, ",".join(r.alts), r.DP, r.REF_DP, r.ALT_DP, r.REF_FREQ, r.ALT_FREQ, "/".join(map(str, r.GT)))
+    def line(self, r, strand=None):
+        return calling.vcf_line(self.ref_id, r, strand)
 
-    def write(self, r):
-        self.f.write(self.line(r))
+    def write(self, r, strand=None):
+        self.f.write(self.line(r, strand))
 
-    def write_all(self, records):
-        self.f.write("".join([self.line(r) for r in records]))
+    def write_all(self, records, strand=None):
+        self.f.write("".join([self.line(r, strand) for r in records]))
 
     def close(self):
         if self.f is not sys.stdout:
@@ -123,7 +125,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 min_freq_consensus=None, min_freq_variants=None, min_depth_consensus=None, min_depth_variants=None,
                 unknown_symbol=None, include_no_primer=None, run_trim=False, run_variants=False, run_consensus=False,
                 device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None, qc_fn=None, qc_regions_fn=None, qc_depths=None,
-                qc_depth_fn=None):
+                qc_depth_fn=None, strand=False, strand_fn=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -140,6 +142,10 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     per region -- tallied on the device behind every batch's read pass, whichever codec feeds it.  qc_regions_fn: a BED of further
     regions (ref, start, end, name); qc_depths: up to 4 depth thresholds (1, 10, 100); qc_depth_fn: depth of every position as a
     TSV file (runs with a count table).  With all four None the engine's report is never switched on.
+    strand (default: off; runs that write a VCF): every VCF record also carries REF_RV, ALT_RV, REF_QUAL, ALT_QUAL and SB
+     -- reverse-strand depth, mean base quality and a strand-bias p-value per allele -- from two more tables
+    the device tallies behind every batch's read pass.  strand_fn: the tables of every position as a TSV file (runs with a count
+    table).  With both off the engine's tallies are never switched on.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -173,6 +179,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("QC regions and QC depth thresholds need a QC report (--qc)")
     if qc_depth_fn is not None and not (run_variants or run_consensus):
         error("A run that only trims has no count table: no per-position depth (--qc_depth_out)")
+    if (strand or strand_fn is not None) and not (run_variants or run_consensus):
+        error("A run that only trims has no count table: no strand tallies (--strand, --strand_out)")
+    if strand and not run_variants:
+        error("The strand INFO keys need a VCF (--strand on variants or aio)")
+    strand_on = bool(strand) or strand_fn is not None
     qc_on = qc_fn is not None or qc_depth_fn is not None
     if qc_on:
         qc_depths = list(qc.DEFAULT_DEPTHS) if qc_depths is None else list(qc_depths)
@@ -214,7 +225,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    driver = vcf = rank_error = None
+    driver = vcf = rank_error = strand_file = None
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
@@ -230,7 +241,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(route.note)
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
-            vcf = VcfWriter(variants_fn, ref_id)
+            vcf = VcfWriter(variants_fn, ref_id, strand=strand)
+        if strand_fn is not None and rank == 0:
+            strand_file = qc.open_new(strand_fn)
         if qc_on:
             qc_regions = [(0, G, qc.WHOLE)] + (qc.load_regions(qc_regions_fn) if qc_regions_fn is not None else [])
             qc_primers = qc.load_primer_rows(primer_fn) if run_trim else []
@@ -248,6 +261,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     if qc_on and rank_error is None:
         eng.qc_enable([(s, e) for s, e, _ in qc_primers], primer_pos_offset or 0, min_length if min_length is not None else 0,
                       include_no_primer, [(s, e) for s, e, _ in qc_regions], qc_depths)
+    if strand_on and rank_error is None:
+        eng.strand_enable()
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -304,6 +319,16 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 parallel.allreduce_table(dist, table)      # the ONE collective of the run: every rank now holds the job's table
             if qc_on and rank == 0:                        # depth from the job's table
                 qc_depth, qc_region_recs = eng.qc_depth(want_depth=qc_depth_fn is not None)
+            strand_tables = None
+            if strand_on:
+                s_rev, s_qsum = eng.strand_tables()
+                if dist is not None:                       # one more all-reduce: both tables as one int64 tensor of G x 11
+                    import torch
+                    wire = torch.from_numpy(strand_mod.to_wire(s_rev, s_qsum)).to("cuda:%d" % device)
+                    parallel.allreduce_table(dist, wire)
+                    s_rev, s_qsum = strand_mod.from_wire(wire.cpu().numpy())
+                if rank == 0:
+                    strand_tables = strand_mod.Tables(eng.counts(), s_rev, s_qsum)
 
             def ins_tallies(positions):
                 triples = loop.ins_store.counted_pairs(positions)
@@ -314,12 +339,15 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if rank != 0:
                 run_variants = run_consensus = False       # rank 0 writes the outputs
             if run_variants:
-                vcf.f.write(res.vcf_text(vcf.ref_id))        # (= vcf.write(r) for r in res.records)
+                vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None))        # (= vcf.write(r) for r in res.records)
                 vcf.close()
             if run_consensus:
                 f = gzip.open(consensus_fn, "wt") if consensus_fn.lower().endswith(".gz") else open(consensus_fn, "w")
                 f.write(">sample\n%s\n" % res.consensus_string(unknown_symbol))
                 f.close()
+        if strand_file is not None:
+            strand_mod.write_tsv(strand_file, ref_id, strand_tables)
+            print_log("Output strand tallies: %s" % strand_fn)
         if qc_on and rank == 0:
             if qc_fn is not None:
                 report = qc.build_report(
@@ -334,7 +362,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 qc.write_depth(qc_files[1], ref_id, qc_depth)
         failed = False
     finally:
-        for f in qc_files:
+        for f in qc_files + [strand_file]:
             if f is not None:
                 f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)
@@ -409,6 +437,8 @@ def parse_args(argv=None):
         p.add_argument("--qc_regions", required=False, type=str, default=None, help="Further regions of the QC report (BED: ref, start, end, name); needs --qc")
         p.add_argument("--qc_depths", required=False, type=str, default=None, help="Depth thresholds of the QC report, at most 4 (1,10,100 when omitted); needs --qc")
         p.add_argument("--qc_depth_out", required=False, type=str, default=None, help="Depth of every position (TSV or TSV.gz: ref, position, depth)")
+        p.add_argument("--strand", action="store_true", help="VCF records also carry REF_RV, ALT_RV, REF_QUAL, ALT_QUAL and SB: reverse-strand depth, mean base quality and strand bias per allele (variants, aio)")
+        p.add_argument("--strand_out", required=False, type=str, default=None, help="Count, reverse-strand count and quality sum of every position and symbol (TSV or TSV.gz; variants, consensus, aio)")
     return parser.parse_args(argv)
 
 
@@ -418,6 +448,7 @@ def main(argv=None):
         error("--qc_regions and --qc_depths need --qc")
     qc_args = dict(qc_fn=args.qc, qc_regions_fn=args.qc_regions, qc_depth_fn=args.qc_depth_out,
                    qc_depths=qc.parse_depths(args.qc_depths) if args.qc_depths is not None else None)
+    qc_args.update(strand=args.strand, strand_fn=args.strand_out)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,

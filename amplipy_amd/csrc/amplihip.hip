@@ -27,6 +27,7 @@
 #include "amp_wave.hpp"
 #include "amp_ins.hpp"
 #include "amp_qc.hpp"
+#include "amp_strand.hpp"
 #define AMP_CODEC_CTX_ONLY
 #include "amp_codec.hpp"
 
@@ -100,6 +101,8 @@ struct amp_ctx {
     uint32_t *dbg_dcnt = nullptr; int dbg_grid = 0;
     bool qc_on = false;            // the QC report (amp_qc_enable): one more kernel behind the read pass
     void *qc = nullptr;            // ... and its state, owned by amp_qc.hip
+    bool strand_on = false;        // the strand and base-quality tallies (amp_strand_enable): one more kernel behind the read pass
+    void *strand = nullptr;        // ... and their state, owned by amp_strand.hip
     uint32_t phases = 0xFFu;       // always 0xFF in the shipped library; -DAMP_DEV builds can mask phases of the tile kernel (AMPLIHIP_PHASES)
     char err[320] = {0};
 };
@@ -768,6 +771,10 @@ int ctx_device(const amp_ctx *c) { return c->device; }
 QcCtx ctx_qc(amp_ctx *c) {
     return QcCtx{c->device, c->ref_len, c->stream, c->d_counts, c->do_trim, c->have_primers ? 1 : 0, c->n_cu, c->err, sizeof(c->err), &c->qc_on, &c->qc};
 }
+// ... and the strand tallies (amp_strand.hip)
+StrandCtx ctx_strand(amp_ctx *c) {
+    return StrandCtx{c->device, c->ref_len, c->stream, c->do_trim, c->min_quality, c->n_cu, c->err, sizeof(c->err), &c->strand_on, &c->strand};
+}
 }  // namespace amp
 
 // ---------------------------------------------------------------------------------------
@@ -896,6 +903,7 @@ void amp_ctx_destroy(amp_ctx *c) {
     Guard g(c);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     qc_destroy(c);
+    strand_destroy(c);
     if (c->own_counts && c->d_counts) (void)hipFree(c->d_counts);
     if (c->d_min_start) (void)hipFree(c->d_min_start);
     if (c->d_max_end) (void)hipFree(c->d_max_end);
@@ -1125,8 +1133,10 @@ int amp_process_batch_device(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
     Guard g(c);
     c->staged_n = -1;          // (amp_event_strings(reads = NULL) refers to the last HOST batch: there is none now)
     if (c->qc_on && rd->n_reads) { const int qrc = qc_check_out(c, dev_out); if (qrc != AMP_OK) return qrc; }
-    const int rc = launch_reads(c, rd, read_base, dev_out);
-    if (rc == AMP_OK && c->qc_on) return qc_enqueue_reads(c, rd, dev_out);      // k_qc_reads on the ctx stream
+    if (c->strand_on && rd->n_reads) { const int src = strand_check_out(c, dev_out); if (src != AMP_OK) return src; }
+    int rc = launch_reads(c, rd, read_base, dev_out);
+    if (rc == AMP_OK && c->qc_on) rc = qc_enqueue_reads(c, rd, dev_out);        // k_qc_reads on the ctx stream
+    if (rc == AMP_OK && c->strand_on) rc = strand_enqueue(c, rd, dev_out);      // k_strand on the ctx stream
     return rc;
 }
 
@@ -1166,6 +1176,7 @@ int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const 
     int rc = launch_reads(c, &rd, read_base, &dout);
     if (rc != AMP_OK) return rc;
     if (c->qc_on) { rc = qc_enqueue_reads(c, &rd, &dout); if (rc != AMP_OK) return rc; }      // k_qc_reads on the ctx stream
+    if (c->strand_on) { rc = strand_enqueue(c, &rd, &dout); if (rc != AMP_OK) return rc; }    // k_strand on the ctx stream
     if (out) {
         if (out->new_pos) HIPCHK(c, hipMemcpyAsync(out->new_pos, dout.new_pos, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         if (out->new_ncig) HIPCHK(c, hipMemcpyAsync(out->new_ncig, dout.new_ncig, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -1332,7 +1343,8 @@ int amp_reset(amp_ctx *c) {
     constexpr size_t ctr_words = 2 * CTR_WORDS;      // the 64-bit counters as the 32-bit words k_reset writes
     k_reset<<<(unsigned)((words + ctr_words + 1023) / 1024), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, ctr_words);
     HIPCHK(c, hipGetLastError());
-    return qc_reset(c);            // (the report's tallies, when there is one)
+    const int qrc = qc_reset(c);   // (the report's tallies, when there is one)
+    return qrc != AMP_OK ? qrc : strand_reset(c);      // (... and the strand tables)
 }
 
 // RCCL is resolved at run time so the library has no link-time dependency on it and uses

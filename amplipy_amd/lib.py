@@ -38,6 +38,7 @@ EXPORTS = [
     "amp_sam_first_bad", "amp_sam_waits",
     "amp_bam_set_references", "amp_bam_text_check", "amp_bam_format",
     "amp_qc_find_primer_owners", "amp_qc_enable", "amp_qc_read_tallies", "amp_qc_depth", "amp_qc_last_ms",
+    "amp_strand_enable", "amp_strand_get", "amp_strand_add", "amp_strand_last_ms",
 ]
 
 
@@ -302,6 +303,32 @@ class Engine:
     def qc_last_ms(self):
         t = C.c_float(0)
         self._chk(self.L.amp_qc_last_ms(self.h, C.byref(t)), "amp_qc_last_ms")
+        return float(t.value)
+
+    # ---- strand and base-quality tallies ---------------------------------------------
+    def strand_enable(self):
+        """amp_strand_enable(1): the tallies on, the tables zero.  ``strand_disable`` turns them off."""
+        self._chk(self.L.amp_strand_enable(self.h, C.c_int(1)), "amp_strand_enable")
+
+    def strand_disable(self):
+        self._chk(self.L.amp_strand_enable(self.h, C.c_int(0)), "amp_strand_enable")
+
+    def strand_tables(self):
+        """amp_strand_get -> (rev uint32[ref_len][6], qsum uint64[ref_len][5]) as they stand."""
+        rev = np.zeros((self.ref_len, abi.NSYM), np.uint32)
+        qsum = np.zeros((self.ref_len, abi.STRAND_QSUM_COLS), np.uint64)
+        self._chk(self.L.amp_strand_get(self.h, C.c_void_p(abi.ptr(rev)), C.c_void_p(abi.ptr(qsum))), "amp_strand_get")
+        return rev, qsum
+
+    def strand_add(self, rev, qsum):
+        """amp_strand_add: host tables added element-wise (the merge of partial tables)."""
+        r = np.ascontiguousarray(rev, np.uint32); q = np.ascontiguousarray(qsum, np.uint64)
+        assert r.size == self.ref_len * abi.NSYM and q.size == self.ref_len * abi.STRAND_QSUM_COLS
+        self._chk(self.L.amp_strand_add(self.h, C.c_void_p(abi.ptr(r)), C.c_void_p(abi.ptr(q))), "amp_strand_add")
+
+    def strand_last_ms(self):
+        t = C.c_float(0)
+        self._chk(self.L.amp_strand_last_ms(self.h, C.byref(t)), "amp_strand_last_ms")
         return float(t.value)
 
     # ---- calling ---------------------------------------------------------------------

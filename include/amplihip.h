@@ -688,6 +688,26 @@ int amp_qc_depth(amp_ctx *ctx, uint32_t *depth /* [ref_len] or NULL */, amp_qc_r
 /* Time of the report's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_qc_last_ms(amp_ctx *ctx, float *reads_ms);
 
+/* ---- per-allele strand and base-quality tallies (opt-in) ----------------------------------------------------
+ * The evidence behind a call that the count table forgets.  For every read with status 0, each increment update_base_counts
+ * (AmpliPy.py:690-753) makes to one of the six fixed keys A C G T N '-' of position r (columns 0..5 as in the count table) also adds
+ *   rev[r][c] += 1                       when the read's FLAG has 0x10      (uint32[ref_len][6]; forward support is counts - rev)
+ *   qsum[r][c] += query_qual[q_pos]      for the five base columns          (uint64[ref_len][5]; a deleted position has no quality)
+ * Insertion alleles are not part of the tables.  With do_trim the alignment walked is the trimmed one, without it the read as it came
+ * in.  A batch with a read of non-zero status leaves the tables as unspecified as it leaves the count table.  With the tallies on,
+ * one more kernel runs behind the read pass of every amp_process_batch* on the ctx stream; with them off (the default) nothing
+ * changes.  amp_reset zeroes the tables. */
+/* on != 0: the tallies on, the tables (64 bytes per reference position, allocated at the first call) zero.  on == 0: off; the tables
+ * stay readable.  With the tallies on and do_trim set, amp_process_batch_device refuses a dev_out without new_pos, new_ncig, new_cig
+ * or status (AMP_EINVAL) before anything runs. */
+int amp_strand_enable(amp_ctx *ctx, int on);
+/* Host copies of the tables as they stand (waits for the stream); either pointer may be NULL.  AMP_ESTATE before the first enable. */
+int amp_strand_get(amp_ctx *ctx, uint32_t *rev /* [ref_len][6] */, uint64_t *qsum /* [ref_len][5] */);
+/* Host tables added element-wise, like amp_add_counts (the merge of partial tables); either pointer may be NULL. */
+int amp_strand_add(amp_ctx *ctx, const uint32_t *rev, const uint64_t *qsum);
+/* Time of the tallies' kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+int amp_strand_last_ms(amp_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
