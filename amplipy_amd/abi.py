@@ -71,6 +71,9 @@ assert VAR_REC_DTYPE.itemsize == 44
 STRAND_QSUM_COLS = 5
 STRAND_CELLS = 11          # NSYM + STRAND_QSUM_COLS: the columns of one position when both tables travel as one
 
+# ---- per-amplicon allele counts (amp_amplicon_*): counts uint32[sum of spans][NSYM], reads uint64[n_amp + 1] ----
+AMPLICON_MAX_CELLS = 1 << 22   # span positions of all amplicons together; more is refused with AMP_EINVAL
+
 # ---- QC report (amp_qc_*) ----
 QC_MAX_DEPTHS = 4
 

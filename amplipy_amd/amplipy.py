@@ -14,7 +14,9 @@ import os
 import sys
 from os.path import isfile
 
-from . import AMPLIPY_VERSION, calling, lib, parallel, qc, strand as strand_mod
+import numpy as np
+
+from . import AMPLIPY_VERSION, amplicon as amplicon_mod, calling, lib, parallel, qc, strand as strand_mod
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -78,8 +80,9 @@ def open_device_bam_text(input_fn, output_fn):
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
-    def __init__(self, fn, ref_id, strand=False):
-        """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables)."""
+    def __init__(self, fn, ref_id, strand=False, amplicon=False):
+        """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables);
+        amplicon: likewise the seven keys of --amplicons, behind them."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -104,16 +107,18 @@ class VcfWriter:
         w("##INFO=<ID=ALT_FREQ,Number=1,Type=String,Description=\"Frequency of alternate base\">\n")
         if strand:
             w(strand_mod.HEADER_LINES)
+        if amplicon:
+            w(amplicon_mod.HEADER_LINES)
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
-    def line(self, r, strand=None):
-        return calling.vcf_line(self.ref_id, r, strand)
+    def line(self, r, strand=None, amplicon=None):
+        return calling.vcf_line(self.ref_id, r, strand, amplicon)
 
-    def write(self, r, strand=None):
-        self.f.write(self.line(r, strand))
+    def write(self, r, strand=None, amplicon=None):
+        self.f.write(self.line(r, strand, amplicon))
 
-    def write_all(self, records, strand=None):
-        self.f.write("".join([self.line(r, strand) for r in records]))
+    def write_all(self, records, strand=None, amplicon=None):
+        self.f.write("".join([self.line(r, strand, amplicon) for r in records]))
 
     def close(self):
         if self.f is not sys.stdout:
@@ -125,7 +130,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 min_freq_consensus=None, min_freq_variants=None, min_depth_consensus=None, min_depth_variants=None,
                 unknown_symbol=None, include_no_primer=None, run_trim=False, run_variants=False, run_consensus=False,
                 device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None, qc_fn=None, qc_regions_fn=None, qc_depths=None,
-                qc_depth_fn=None, strand=False, strand_fn=None):
+                qc_depth_fn=None, strand=False, strand_fn=None, amplicons_fn=None, amplicon_out_fn=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -146,6 +151,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
      -- reverse-strand depth, mean base quality and a strand-bias p-value per allele -- from two more tables
     the device tallies behind every batch's read pass.  strand_fn: the tables of every position as a TSV file (runs with a count
     table).  With both off the engine's tallies are never switched on.
+    amplicons_fn (default: off; aio only): the amplicon file -- left primer, right primer and, optionally, an amplicon name per
+    line.  Every read is assigned to an amplicon by its original coordinates, the device keeps a count
+    table per amplicon behind every batch's read pass, and every VCF record also carries AMP, AMP_DP, AMP_REF_DP, AMP_ALT_DP,
+    AMP_NA_DP, AMP_P and PRIMER.  amplicon_out_fn: the per-amplicon table as a TSV file.  With amplicons_fn None the engine's
+    hook is never switched on.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -183,6 +193,12 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("A run that only trims has no count table: no strand tallies (--strand, --strand_out)")
     if strand and not run_variants:
         error("The strand INFO keys need a VCF (--strand on variants or aio)")
+    if amplicon_out_fn is not None and amplicons_fn is None:
+        error("The per-amplicon table (--amplicon_out) needs the amplicon file (--amplicons)")
+    if amplicons_fn is not None and not (run_trim and run_variants and run_consensus):
+        error("Per-amplicon counts (--amplicons, --amplicon_out) work on aio only: reads are assigned to amplicons by their original "
+              "coordinates against the primer BED, which only a run that trims has, and are counted for a VCF, which only a run that "
+              "calls variants writes")
     strand_on = bool(strand) or strand_fn is not None
     qc_on = qc_fn is not None or qc_depth_fn is not None
     if qc_on:
@@ -225,7 +241,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    driver = vcf = rank_error = strand_file = None
+    driver = vcf = rank_error = strand_file = amps = amp_file = None
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
@@ -241,9 +257,14 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(route.note)
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
-            vcf = VcfWriter(variants_fn, ref_id, strand=strand)
+            vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None)
+            if amplicon_out_fn is not None:
+                amp_file = qc.open_new(amplicon_out_fn)
         if strand_fn is not None and rank == 0:
             strand_file = qc.open_new(strand_fn)
+        if amplicons_fn is not None:
+            print_log("Loading amplicons: %s" % amplicons_fn)
+            amps = amplicon_mod.load_amplicons(amplicons_fn, qc.load_primer_rows(primer_fn), primer_pos_offset or 0, G)
         if qc_on:
             qc_regions = [(0, G, qc.WHOLE)] + (qc.load_regions(qc_regions_fn) if qc_regions_fn is not None else [])
             qc_primers = qc.load_primer_rows(primer_fn) if run_trim else []
@@ -263,6 +284,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                       include_no_primer, [(s, e) for s, e, _ in qc_regions], qc_depths)
     if strand_on and rank_error is None:
         eng.strand_enable()
+    if amps is not None and rank_error is None:
+        amplicon_mod.enable(eng, amps)
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -292,6 +315,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                                                                                         ", ".join("%.1f" % (100.0 * b_ / tot) for _, b_ in shares)))
         if qc_on:                        # every rank's tallies to rank 0, which adds them up
             qc_parts = parallel.gather_objects(dist, rank, world, eng.qc_read_tallies())
+        if amps is not None:             # ... and every rank's reads per amplicon
+            amp_read_parts = parallel.gather_objects(dist, rank, world, eng.amplicon_tables()[1])
         if final_trimmed_fn is not None and driver.part_writer is not None:
             # the ranks' files (all closed by now: the writer threads were joined in run()) become the one trimmed BAM
             parts = parallel.gather_objects(dist, rank, world, (driver.part_writer.path, driver.part_writer.header_bytes))
@@ -329,6 +354,18 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                     s_rev, s_qsum = strand_mod.from_wire(wire.cpu().numpy())
                 if rank == 0:
                     strand_tables = strand_mod.Tables(eng.counts(), s_rev, s_qsum)
+            amp_tables = None
+            if amps is not None:
+                a_counts, a_reads = eng.amplicon_tables()
+                if dist is not None:                       # one more all-reduce: the per-amplicon table
+                    import torch
+                    wire = torch.from_numpy(a_counts.astype(np.int64).reshape(-1)).to("cuda:%d" % device)
+                    parallel.allreduce_table(dist, wire)
+                    a_counts = wire.cpu().numpy().astype(np.uint32).reshape(-1, 6)
+                    if rank == 0:
+                        a_reads = np.sum([np.asarray(part, np.uint64) for part in amp_read_parts], axis=0, dtype=np.uint64)
+                if rank == 0:
+                    amp_tables = amplicon_mod.Tables(amps, eng.counts(), a_counts, a_reads)
 
             def ins_tallies(positions):
                 triples = loop.ins_store.counted_pairs(positions)
@@ -339,7 +376,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if rank != 0:
                 run_variants = run_consensus = False       # rank 0 writes the outputs
             if run_variants:
-                vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None))        # (= vcf.write(r) for r in res.records)
+                vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables))        # (= vcf.write(r) for r in res.records)
                 vcf.close()
             if run_consensus:
                 f = gzip.open(consensus_fn, "wt") if consensus_fn.lower().endswith(".gz") else open(consensus_fn, "w")
@@ -348,6 +385,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if strand_file is not None:
             strand_mod.write_tsv(strand_file, ref_id, strand_tables)
             print_log("Output strand tallies: %s" % strand_fn)
+        if amp_file is not None:
+            amplicon_mod.write_tsv(amp_file, ref_id, amp_tables)
+            print_log("Output per-amplicon counts: %s" % amplicon_out_fn)
         if qc_on and rank == 0:
             if qc_fn is not None:
                 report = qc.build_report(
@@ -355,14 +395,18 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                     if run_trim else dict(depths=qc_depths),
                     qc_tallies[0], run_trim, qc_primers, qc_tallies[1], qc_tallies[2],
                     [name for _, _, name in qc_regions], qc_region_recs, qc_depths)
+                if amps is not None:
+                    amplicon_mod.add_to_report(report, amp_tables)
                 qc.write_json(qc_files[0], report)
                 print_log("Output QC report: %s" % qc_fn)
                 print_log(qc.summary_line(report))
             if qc_depth_fn is not None:
                 qc.write_depth(qc_files[1], ref_id, qc_depth)
+        if amps is not None and rank == 0:
+            print_log(amp_tables.summary_line())
         failed = False
     finally:
-        for f in qc_files + [strand_file]:
+        for f in qc_files + [strand_file, amp_file]:
             if f is not None:
                 f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)
@@ -438,6 +482,8 @@ def parse_args(argv=None):
         p.add_argument("--qc_depths", required=False, type=str, default=None, help="Depth thresholds of the QC report, at most 4 (1,10,100 when omitted); needs --qc")
         p.add_argument("--qc_depth_out", required=False, type=str, default=None, help="Depth of every position (TSV or TSV.gz: ref, position, depth)")
         p.add_argument("--strand", action="store_true", help="VCF records also carry REF_RV, ALT_RV, REF_QUAL, ALT_QUAL and SB: reverse-strand depth, mean base quality and strand bias per allele (variants, aio)")
+        p.add_argument("--amplicons", required=False, type=str, default=None, help="Amplicon file (TSV: left primer, right primer[, amplicon name]): per-amplicon allele counts on the device, and AMP, AMP_DP, AMP_REF_DP, AMP_ALT_DP, AMP_NA_DP, AMP_P and PRIMER on every VCF record (aio)")
+        p.add_argument("--amplicon_out", required=False, type=str, default=None, help="Count of every symbol per amplicon and position of its span (TSV or TSV.gz; aio, needs --amplicons)")
         p.add_argument("--strand_out", required=False, type=str, default=None, help="Count, reverse-strand count and quality sum of every position and symbol (TSV or TSV.gz; variants, consensus, aio)")
     return parser.parse_args(argv)
 
@@ -448,7 +494,7 @@ def main(argv=None):
         error("--qc_regions and --qc_depths need --qc")
     qc_args = dict(qc_fn=args.qc, qc_regions_fn=args.qc_regions, qc_depth_fn=args.qc_depth_out,
                    qc_depths=qc.parse_depths(args.qc_depths) if args.qc_depths is not None else None)
-    qc_args.update(strand=args.strand, strand_fn=args.strand_out)
+    qc_args.update(strand=args.strand, strand_fn=args.strand_out, amplicons_fn=args.amplicons, amplicon_out_fn=args.amplicon_out)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,

@@ -10,14 +10,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # translation units of libamplihip.so: the kernels + C ABI, and the insertion-event aggregation (its sort headers triple the
 # compile time of whatever includes them, so it is built -- and cached -- on its own), the DEFLATE encoder of the BAM writer, and
-# the codecs for SAM text and for BAM (input, and trimmed records out), the QC report, and the strand tallies
-UNITS = ["amplihip.hip", "amp_ins.hip", "amp_deflate.hip", "amp_sam.hip", "amp_bgzf.hip", "amp_qc.hip", "amp_strand.hip"]
+# the codecs for SAM text and for BAM (input, and trimmed records out), the QC report, the strand tallies, and the per-amplicon counts
+UNITS = ["amplihip.hip", "amp_ins.hip", "amp_deflate.hip", "amp_sam.hip", "amp_bgzf.hip", "amp_qc.hip", "amp_strand.hip", "amp_amplicon.hip"]
 SRC = os.path.join(CSRC, "amplihip.hip")
 HEADERS = [os.path.join(_HERE, "..", "include", "amplihip.h")] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
 UNIT_DEPS = {"amplihip.hip": HEADERS, "amp_ins.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_ins.hpp")],
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
              "amp_qc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_qc.hpp")],
              "amp_strand.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_strand.hpp")],
+             "amp_amplicon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_strand.hpp", "amp_amplicon.hpp")],
              "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in
                              ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamtail.hpp")],
              # (amp_bamout.hip, the re-encoder of trimmed records, and amp_bamtext.hip, trimmed records as SAM text, are part of

@@ -1,0 +1,445 @@
+// amp_amplicon.hip -- per-amplicon allele counts on the device (C ABI: the amp_amplicon_* entry points
+// of amplihip.h).
+//
+// k_amplicon runs behind the read pass of every batch while the hook is on and touches every counted base once more, like
+// k_strand, whose shape it starts from: a block takes a contiguous run of tiles of 256 neighbouring reads.  Phase A, one lane
+// per read: the read's amplicon from its ORIGINAL coordinates (amplicon_assign, amp_amplicon.hpp), the reads per amplicon (a
+// ballot and run heads per wave: a pile costs one add per wave and amplicon), and the counted alignment as a few segments.
+// The block keeps AM_SLOTS windows of AM_W positions x 6 columns in LDS (row stride 7), each bound to (amplicon, anchor); the
+// distinct amplicons of a tile are found wave by wave (a loop over the wave's distinct values), and one lane settles all of
+// the tile's requests against the slots (amplicon_resolve).  Slots persist across the block's tiles; a slot goes to the table
+// -- its non-zero cells, one atomic each -- when it is given to another amplicon, when its anchor moves, and at block end.
+// Phase B, position-major: per slot in use, each wave owns every fourth 64-position chunk of the window and each lane one
+// position of it; the wave takes the segment list 64 entries at a time, ballots which of them lie in its slot and overlap its
+// chunk, and lane p adds into its OWN cell with a plain LDS add.  Reads the window did not take -- more segments than list
+// slots, an irregular CIGAR, an amplicon without a slot in this tile, a read outside its slot's window -- walk serially, one
+// lane per read (amplicon_walk), with LDS atomics where slot and position are resident and global atomics otherwise: slow and
+// correct.  No step relies on the reads being sorted.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "amp_amplicon.hpp"
+
+namespace amp {
+
+struct AmpliconState {
+    int32_t n_amp = 0;
+    int64_t cells = 0;                         // positions of all spans together
+    int32_t *d_lo = nullptr, *d_hi = nullptr;  // one allocation: lo, hi, cell_off
+    uint32_t *d_off = nullptr;
+    int32_t *d_start = nullptr, *d_end = nullptr;      // one allocation: amp_start, amp_end
+    uint32_t *d_counts = nullptr;              // [cells][6]
+    unsigned long long *d_reads = nullptr;     // [n_amp + 1]
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
+};
+
+struct AmpliconArgs {
+    int64_t n;
+    const int32_t *pos;
+    const uint32_t *lseq, *cig_off32, *cig, *seq_off8;
+    const uint8_t *seq, *qual;
+    const int32_t *new_pos;                    // the trimmed alignment (do_trim)
+    const uint32_t *new_ncig, *new_cig;
+    const uint8_t *status;                     // may be null without do_trim
+    int32_t do_trim;
+    StrandParams P;
+    AmpliconTables T;
+    uint32_t *counts;
+    unsigned long long *reads;
+};
+
+// the non-zero cells of the slots in `mask` to the table, one atomic each; those slots are all zero afterwards
+__device__ __forceinline__ void amplicon_flush(uint32_t *s_cell, const AmSlots &S, uint32_t mask, const AmpliconArgs &a) {
+    for (int k = 0; k < AM_SLOTS; ++k) {
+        if (!((mask >> k) & 1u)) continue;
+        const int32_t amp = S.amp[k], anchor = S.anchor[k];
+        if (amp < 0 || amp >= a.T.n_amp) continue;                 // (a free slot holds nothing)
+        const int32_t lo = a.T.lo[amp], hi = a.T.hi[amp];
+        const size_t row0 = (size_t)a.T.cell_off[amp];
+        uint32_t *const cell = s_cell + k * AM_SLOT_WORDS;
+        for (int i = (int)threadIdx.x; i < AM_SLOT_WORDS; i += AM_BLOCK) {
+            const uint32_t v = cell[i];
+            if (!v) continue;
+            cell[i] = 0u;
+            const int64_t r = (int64_t)anchor + i / AM_STRIDE;
+            const int c = i % AM_STRIDE;
+            if (c >= AM_COLS || r < lo || r >= hi) continue;       // (nothing is ever added there)
+            atomicAdd(&a.counts[(row0 + (size_t)(r - lo)) * AM_COLS + c], v);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(AM_BLOCK)
+k_amplicon(AmpliconArgs a) {
+    __shared__ uint32_t s_cell[AM_SLOTS * AM_SLOT_WORDS];
+    __shared__ AmSeg s_seg[AM_BLOCK * AM_SEG_SLOTS];
+    __shared__ AmReq s_req[AM_REQS];
+    __shared__ int s_nreq[AM_BLOCK / 64];
+    __shared__ AmSlots s_slots;
+    __shared__ uint32_t s_nseg;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int k = tid; k < AM_SLOTS * AM_SLOT_WORDS; k += AM_BLOCK) s_cell[k] = 0u;
+    if (tid == 0) { s_nseg = 0u; amplicon_slots_init(s_slots); }
+    // the block's contiguous run of tiles (the bounds are the same for every lane: the barriers below see whole blocks)
+    const int64_t tiles = (a.n + AM_BLOCK - 1) / AM_BLOCK;
+    const int64_t t0 = tiles * (int64_t)blockIdx.x / (int64_t)gridDim.x, t1 = tiles * ((int64_t)blockIdx.x + 1) / (int64_t)gridDim.x;
+    int since = 0;                             // tiles since every slot was last flushed
+    __syncthreads();
+    for (int64_t t = t0; t < t1; ++t) {
+        // ---- phase A: one lane per read
+        const int64_t i = t * AM_BLOCK + tid;
+        StrandRead R;
+        R.pos = 0; R.cig = a.cig; R.n_ops = 0u; R.lseq = 0; R.rev = 0u; R.base = 0ull;
+        StrandShape sh;
+        sh.regular = false; sh.n_seg = 0; sh.ref_end = 0;
+        bool live = false;
+        uint32_t qual0 = 0xFFu;
+        int32_t amp = -1, lo_a = 0, hi_a = 0;
+        size_t row0 = 0;
+        if (i < a.n && (a.status ? a.status[i] == 0 : true)) {
+            live = true;
+            const uint32_t c0 = a.cig_off32[i];
+            const int32_t p = a.pos[i];
+            amp = amplicon_assign(p, (int64_t)p + am_cigar_ref_len(a.cig + c0, a.cig_off32[i + 1] - c0), a.T);
+            if (amp >= 0) {
+                lo_a = a.T.lo[amp]; hi_a = a.T.hi[amp]; row0 = (size_t)a.T.cell_off[amp];
+                if (a.do_trim) {
+                    R.pos = a.new_pos[i]; R.cig = a.new_cig + (size_t)c0 + 3 * (size_t)i; R.n_ops = a.new_ncig[i];
+                } else {
+                    R.pos = p; R.cig = a.cig + c0; R.n_ops = a.cig_off32[i + 1] - c0;
+                }
+                R.lseq = (int32_t)a.lseq[i];
+                R.base = (uint64_t)a.seq_off8[i] * 8ull;
+                if (R.lseq > 0) qual0 = a.qual[R.base];
+                sh = amplicon_segments(R, a.P, qual0, 0, [](const AmSeg &) {});
+            }
+        }
+        // reads per amplicon: neighbouring lanes with the same amplicon are one run, and its first lane adds the run's length
+        {
+            const int32_t key = live ? (amp >= 0 ? amp : a.T.n_amp) : -1;
+            const int32_t before = __shfl_up(key, 1);
+            const unsigned long long heads = __ballot(lane == 0 || key != before);
+            if (key >= 0 && ((heads >> lane) & 1ull)) {
+                const unsigned long long later = lane == 63 ? 0ull : heads >> (lane + 1);
+                const int len = later ? __ffsll((long long)later) : 64 - lane;
+                atomicAdd(&a.reads[key], (unsigned long long)len);
+            }
+        }
+        // the wave's distinct amplicons that want a window, one request each: (amplicon, first position, last end)
+        const bool want = live && amplicon_wants_slot(amp, sh, R.pos, lo_a, hi_a);
+        {
+            unsigned long long pending = __ballot(want);
+            int nreq = 0;
+            while (pending) {                                      // (wave-uniform)
+                const int src = __ffsll((long long)pending) - 1;
+                const int32_t v = __shfl(amp, src);
+                const bool mine = want && amp == v;
+                int32_t l = mine ? R.pos : 0x7FFFFFFF, h = mine ? sh.ref_end : -0x7FFFFFFF - 1;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) {
+                    l = min(l, __shfl_xor(l, d));
+                    h = max(h, __shfl_xor(h, d));
+                }
+                if (lane == src && nreq < AM_REQ_PER_WAVE) s_req[wave * AM_REQ_PER_WAVE + nreq] = AmReq{v, l, h, lo_a};
+                ++nreq;
+                pending &= ~__ballot(mine);
+            }
+            if (lane == 0) s_nreq[wave] = min(nreq, AM_REQ_PER_WAVE);
+        }
+        __syncthreads();
+        if (tid == 0) {                                            // one lane settles the tile's requests against the slots
+            int n = 0;
+            for (int w = 0; w < AM_BLOCK / 64; ++w)
+                for (int k = 0; k < s_nreq[w]; ++k) s_req[n++] = s_req[w * AM_REQ_PER_WAVE + k];       // (n <= the index read)
+            amplicon_resolve(s_slots, s_req, n);
+        }
+        __syncthreads();
+        {
+            uint32_t flush = s_slots.flush;                        // (the same for every lane)
+            if (since >= AM_MAX_TILES_PER_FLUSH) { flush = (1u << AM_SLOTS) - 1u; since = 0; }
+            if (flush) amplicon_flush(s_cell, s_slots, flush, a);
+        }
+        ++since;
+        __syncthreads();
+        if (tid == 0) amplicon_commit(s_slots);
+        __syncthreads();
+        const uint32_t used = s_slots.used;
+        const int slot = live ? amplicon_read_slot(s_slots, amp, sh, R.pos, lo_a, hi_a) : -1;
+        const bool win = slot >= 0;
+        const bool nothing = live && amp >= 0 && sh.regular && sh.n_seg == 0;      // a regular read whose segments are all empty adds nothing
+        if (win) {
+            uint32_t at = atomicAdd(&s_nseg, (uint32_t)sh.n_seg);  // (at most AM_SEG_SLOTS per read: the list cannot overflow)
+            amplicon_segments(R, a.P, qual0, slot, [&](const AmSeg &s) { s_seg[at++] = s; });
+        }
+        __syncthreads();
+        // ---- phase B: position-major over the tile's segments; in slot k, lane `lane` of the wave owns window position
+        // c * 64 + lane of chunk c.  The wave takes the list 64 segments at a time, a segment per lane, ballots which of them
+        // lie in slot k and overlap the chunk, and visits only those (their fields broadcast by shuffle).
+        const uint32_t ns = s_nseg;
+        for (uint32_t s0 = 0; s0 < ns; s0 += 64u) {                // (ns and used are block-uniform: whole waves at the ballots)
+            const bool have = s0 + (uint32_t)lane < ns;
+            AmSeg mine;
+            mine.r0 = 0; mine.len_kind = 0u; mine.q0 = 0ull;
+            if (have) mine = s_seg[s0 + (uint32_t)lane];
+            const int my_slot = am_seg_slot(mine);
+            for (int k = 0; k < AM_SLOTS; ++k) {
+                if (!((used >> k) & 1u)) continue;
+                const int32_t anchor = s_slots.anchor[k];
+                const int32_t m0 = mine.r0 - anchor, m1 = m0 + am_seg_len(mine);
+                for (int c = wave; c < AM_W / AM_CHUNK; c += AM_BLOCK / 64) {
+                    const int32_t c0 = c * AM_CHUNK;
+                    unsigned long long hits = __ballot(have && my_slot == k && m1 > c0 && m0 < c0 + AM_CHUNK);
+                    const int32_t p = c0 + lane;
+                    while (hits) {
+                        const int src = __ffsll((long long)hits) - 1;
+                        hits &= hits - 1ull;
+                        AmSeg g;
+                        g.r0 = __shfl(mine.r0, src);
+                        g.len_kind = __shfl(mine.len_kind, src);
+                        g.q0 = __shfl((unsigned long long)mine.q0, src);
+                        const int32_t a0 = g.r0 - anchor, a1 = a0 + am_seg_len(g);
+                        if (p < a0 || p >= a1) {
+                            // (not this lane's position; every lane is back for the next segment's shuffles)
+                        } else if (am_seg_del(g)) {
+                            s_cell[am_cell(k, p, 5u)] += 1u;
+                        } else {
+                            uint32_t col, qv;
+                            if (strand_base(a.seq, a.qual, g.q0 + (uint64_t)(p - a0), a.P.min_quality, col, qv)) s_cell[am_cell(k, p, col)] += 1u;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (tid == 0) s_nseg = 0u;
+        // ---- the serial path: assigned reads the window did not take
+        if (live && amp >= 0 && !win && !nothing) {
+            const int k = amplicon_slot_of(s_slots, amp);
+            const int32_t anchor = k >= 0 ? s_slots.anchor[k] : 0;
+            amplicon_walk(R, a.P, a.seq, a.qual, lo_a, hi_a, [&](int32_t r, uint32_t col) {
+                const int64_t w = (int64_t)r - (int64_t)anchor;
+                if (k >= 0 && w >= 0 && w < AM_W) atomicAdd(&s_cell[am_cell(k, (int32_t)w, col)], 1u);
+                else atomicAdd(&a.counts[(row0 + (size_t)(r - lo_a)) * AM_COLS + col], 1u);
+            });
+        }
+        __syncthreads();
+    }
+    amplicon_flush(s_cell, s_slots, (1u << AM_SLOTS) - 1u, a);
+}
+
+#define AMCHK(q, call)                                                                                                       \
+    do {                                                                                                                     \
+        hipError_t e__ = (call);                                                                                             \
+        if (e__ != hipSuccess) {                                                                                             \
+            snprintf((q).err, (q).err_cap, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__);      \
+            return e__ == hipErrorOutOfMemory ? AMP_ENOMEM : AMP_EHIP;                                                       \
+        }                                                                                                                    \
+    } while (0)
+
+struct AmpliconGuard {      // the ctx's device is current for the duration of a call
+    int prev = -1;
+    explicit AmpliconGuard(int device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != device) (void)hipSetDevice(device);
+    }
+    ~AmpliconGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+static size_t count_bytes(const AmpliconState *s) { return (size_t)s->cells * AM_COLS * 4; }
+static size_t read_bytes(const AmpliconState *s) { return ((size_t)s->n_amp + 1) * 8; }
+
+static void amplicon_free(AmpliconState *s) {
+    if (!s) return;
+    if (s->d_lo) (void)hipFree(s->d_lo);
+    if (s->d_start) (void)hipFree(s->d_start);
+    if (s->d_counts) (void)hipFree(s->d_counts);
+    if (s->d_reads) (void)hipFree(s->d_reads);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    delete s;
+}
+
+int amplicon_check_out(amp_ctx *c, const amp_trim_out *o) {
+    const AmpliconCtx q = ctx_amplicon(c);
+    if (q.do_trim && (!o || !o->new_pos || !o->new_ncig || !o->new_cig || !o->status)) {
+        snprintf(q.err, q.err_cap, "the amplicon tables need new_pos, new_ncig, new_cig and status of a trimming pass");
+        return AMP_EINVAL;
+    }
+    return AMP_OK;
+}
+
+int amplicon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
+    const AmpliconCtx q = ctx_amplicon(c);
+    AmpliconState *s = (AmpliconState *)*q.state;
+    if (!s) return AMP_ESTATE;
+    s->timed = false;
+    const int64_t n = rd->n_reads;
+    if (n <= 0) return AMP_OK;
+    const int rc = amplicon_check_out(c, o);
+    if (rc != AMP_OK) return rc;
+    AmpliconArgs a;
+    a.n = n; a.pos = rd->pos; a.lseq = rd->lseq; a.cig_off32 = rd->cig_off32; a.cig = rd->cig; a.seq_off8 = rd->seq_off8;
+    a.seq = rd->seq; a.qual = rd->qual;
+    a.new_pos = o ? o->new_pos : nullptr; a.new_ncig = o ? o->new_ncig : nullptr; a.new_cig = o ? o->new_cig : nullptr;
+    a.status = o ? o->status : nullptr;
+    a.do_trim = q.do_trim ? 1 : 0;
+    a.P = StrandParams{q.ref_len, q.min_quality};
+    a.T = AmpliconTables{q.ref_len, s->n_amp, s->d_lo, s->d_hi, s->d_off, s->d_start, s->d_end};
+    a.counts = s->d_counts; a.reads = s->d_reads;
+    // a block takes AM_TILES_PER_BLOCK tiles and more (its slots go to the table when they move, not per tile), up to
+    // AM_BLOCKS_PER_CU blocks per CU; from there on the blocks take more tiles each
+    const int64_t tiles = (n + AM_BLOCK - 1) / AM_BLOCK;
+    const int64_t grid = std::min<int64_t>(std::max<int64_t>((tiles + AM_TILES_PER_BLOCK - 1) / AM_TILES_PER_BLOCK, 1), (int64_t)AM_BLOCKS_PER_CU * q.n_cu);
+    AMCHK(q, hipEventRecord(s->ev0, q.stream));
+    k_amplicon<<<(unsigned)grid, AM_BLOCK, 0, q.stream>>>(a);
+    AMCHK(q, hipGetLastError());
+    AMCHK(q, hipEventRecord(s->ev1, q.stream));
+    s->timed = true;
+    return AMP_OK;
+}
+
+static int amplicon_zero(const AmpliconCtx &q, AmpliconState *s) {
+    AMCHK(q, hipMemsetAsync(s->d_counts, 0, count_bytes(s), q.stream));
+    AMCHK(q, hipMemsetAsync(s->d_reads, 0, read_bytes(s), q.stream));
+    return AMP_OK;
+}
+
+int amplicon_reset(amp_ctx *c) {
+    const AmpliconCtx q = ctx_amplicon(c);
+    AmpliconState *s = (AmpliconState *)*q.state;
+    if (!s) return AMP_OK;
+    return amplicon_zero(q, s);
+}
+
+void amplicon_destroy(amp_ctx *c) {
+    const AmpliconCtx q = ctx_amplicon(c);
+    amplicon_free((AmpliconState *)*q.state);
+    *q.state = nullptr;
+    *q.on = false;
+}
+
+}  // namespace amp
+
+using namespace amp;
+
+extern "C" {
+
+int amp_amplicon_enable(amp_ctx *c, int32_t n_amp, const int32_t *lo, const int32_t *hi, const int32_t *amp_start, const int32_t *amp_end) {
+    if (!c) return AMP_EINVAL;
+    const AmpliconCtx q = ctx_amplicon(c);
+    if (n_amp == 0 || !lo || !hi || !amp_start || !amp_end) { *q.on = false; return AMP_OK; }
+    if (n_amp < 0) return AMP_EINVAL;
+    const size_t A = (size_t)n_amp, G = (size_t)q.ref_len;
+    std::vector<uint32_t> off(A);
+    int64_t cells = 0;
+    for (size_t k = 0; k < A; ++k) {
+        if (lo[k] < 0 || lo[k] >= hi[k] || hi[k] > q.ref_len) {
+            snprintf(q.err, q.err_cap, "amplicon %zu: span [%d, %d) is empty or outside the reference", k, lo[k], hi[k]);
+            return AMP_EINVAL;
+        }
+        off[k] = (uint32_t)cells;
+        cells += (int64_t)hi[k] - lo[k];
+        if (cells > AM_MAX_CELLS) {
+            snprintf(q.err, q.err_cap, "the amplicon spans add up to more than %lld positions", (long long)AM_MAX_CELLS);
+            return AMP_EINVAL;
+        }
+    }
+    for (size_t p = 0; p < G; ++p) {
+        if (amp_start[p] < -1 || amp_start[p] >= n_amp || amp_end[p] < -1 || amp_end[p] >= n_amp) {
+            snprintf(q.err, q.err_cap, "owner tables: position %zu names an amplicon outside [0, %d)", p, n_amp);
+            return AMP_EINVAL;
+        }
+    }
+    AmpliconGuard g(q.device);
+    AmpliconState *s = (AmpliconState *)*q.state;
+    if (s && (s->n_amp != n_amp || s->cells != cells)) {
+        // another amplicon set: the tables are laid out again (a kernel of the old one may still be in flight)
+        AMCHK(q, hipStreamSynchronize(q.stream));
+        amplicon_free(s);
+        s = nullptr; *q.state = nullptr; *q.on = false;
+    }
+    if (!s) {
+        s = new (std::nothrow) AmpliconState();
+        if (!s) return AMP_ENOMEM;
+        struct Drop { AmpliconState *s; ~Drop() { amplicon_free(s); } } drop{s};      // until the state is handed to the ctx
+        s->n_amp = n_amp; s->cells = cells;
+        AMCHK(q, hipMalloc((void **)&s->d_lo, A * 12));
+        s->d_hi = s->d_lo + A; s->d_off = (uint32_t *)(s->d_hi + A);
+        AMCHK(q, hipMalloc((void **)&s->d_start, std::max<size_t>(G * 8, 8)));
+        s->d_end = s->d_start + G;
+        AMCHK(q, hipMalloc((void **)&s->d_counts, count_bytes(s)));
+        AMCHK(q, hipMalloc((void **)&s->d_reads, read_bytes(s)));
+        AMCHK(q, hipEventCreate(&s->ev0));
+        AMCHK(q, hipEventCreate(&s->ev1));
+        drop.s = nullptr;
+        *q.state = s;
+    }
+    *q.on = false;
+    AMCHK(q, hipMemcpyAsync(s->d_lo, lo, A * 4, hipMemcpyHostToDevice, q.stream));
+    AMCHK(q, hipMemcpyAsync(s->d_hi, hi, A * 4, hipMemcpyHostToDevice, q.stream));
+    AMCHK(q, hipMemcpyAsync(s->d_off, off.data(), A * 4, hipMemcpyHostToDevice, q.stream));
+    if (G) {
+        AMCHK(q, hipMemcpyAsync(s->d_start, amp_start, G * 4, hipMemcpyHostToDevice, q.stream));
+        AMCHK(q, hipMemcpyAsync(s->d_end, amp_end, G * 4, hipMemcpyHostToDevice, q.stream));
+    }
+    const int rc = amplicon_zero(q, s);
+    if (rc != AMP_OK) return rc;
+    AMCHK(q, hipStreamSynchronize(q.stream));        // (the caller's arrays and `off` are free again)
+    *q.on = true;
+    return AMP_OK;
+}
+
+int amp_amplicon_get(amp_ctx *c, uint32_t *counts, uint64_t *reads) {
+    if (!c) return AMP_EINVAL;
+    const AmpliconCtx q = ctx_amplicon(c);
+    AmpliconState *s = (AmpliconState *)*q.state;
+    if (!s) return AMP_ESTATE;
+    AmpliconGuard g(q.device);
+    if (counts) AMCHK(q, hipMemcpyAsync(counts, s->d_counts, count_bytes(s), hipMemcpyDeviceToHost, q.stream));
+    if (reads) AMCHK(q, hipMemcpyAsync(reads, s->d_reads, read_bytes(s), hipMemcpyDeviceToHost, q.stream));
+    AMCHK(q, hipStreamSynchronize(q.stream));
+    return AMP_OK;
+}
+
+int amp_amplicon_add(amp_ctx *c, const uint32_t *counts, const uint64_t *reads) {
+    if (!c) return AMP_EINVAL;
+    const AmpliconCtx q = ctx_amplicon(c);
+    AmpliconState *s = (AmpliconState *)*q.state;
+    if (!s) return AMP_ESTATE;
+    AmpliconGuard g(q.device);
+    // the tables to the host, the sums there, and back: a call per job (the merge of partial tables), not per batch
+    std::vector<uint32_t> hc(counts ? (size_t)s->cells * AM_COLS : 0);
+    std::vector<uint64_t> hr(reads ? (size_t)s->n_amp + 1 : 0);
+    if (counts) AMCHK(q, hipMemcpyAsync(hc.data(), s->d_counts, hc.size() * 4, hipMemcpyDeviceToHost, q.stream));
+    if (reads) AMCHK(q, hipMemcpyAsync(hr.data(), s->d_reads, hr.size() * 8, hipMemcpyDeviceToHost, q.stream));
+    AMCHK(q, hipStreamSynchronize(q.stream));
+    for (size_t k = 0; k < hc.size(); ++k) hc[k] += counts[k];
+    for (size_t k = 0; k < hr.size(); ++k) hr[k] += reads[k];
+    if (counts) AMCHK(q, hipMemcpyAsync(s->d_counts, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, q.stream));
+    if (reads) AMCHK(q, hipMemcpyAsync(s->d_reads, hr.data(), hr.size() * 8, hipMemcpyHostToDevice, q.stream));
+    AMCHK(q, hipStreamSynchronize(q.stream));
+    return AMP_OK;
+}
+
+int amp_amplicon_last_ms(amp_ctx *c, float *ms) {
+    if (!c) return AMP_EINVAL;
+    const AmpliconCtx q = ctx_amplicon(c);
+    AmpliconState *s = (AmpliconState *)*q.state;
+    if (!s || !s->timed) return AMP_ESTATE;
+    AmpliconGuard g(q.device);
+    AMCHK(q, hipEventSynchronize(s->ev1));
+    float t = 0;
+    AMCHK(q, hipEventElapsedTime(&t, s->ev0, s->ev1));
+    if (ms) *ms = t;
+    return AMP_OK;
+}
+
+}  // extern "C"

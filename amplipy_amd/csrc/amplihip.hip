@@ -28,6 +28,7 @@
 #include "amp_ins.hpp"
 #include "amp_qc.hpp"
 #include "amp_strand.hpp"
+#include "amp_amplicon.hpp"
 #define AMP_CODEC_CTX_ONLY
 #include "amp_codec.hpp"
 
@@ -103,6 +104,8 @@ struct amp_ctx {
     void *qc = nullptr;            // ... and its state, owned by amp_qc.hip
     bool strand_on = false;        // the strand and base-quality tallies (amp_strand_enable): one more kernel behind the read pass
     void *strand = nullptr;        // ... and their state, owned by amp_strand.hip
+    bool amplicon_on = false;      // the per-amplicon allele counts (amp_amplicon_enable): one more kernel behind the read pass
+    void *amplicon = nullptr;      // ... and their state, owned by amp_amplicon.hip
     uint32_t phases = 0xFFu;       // always 0xFF in the shipped library; -DAMP_DEV builds can mask phases of the tile kernel (AMPLIHIP_PHASES)
     char err[320] = {0};
 };
@@ -775,6 +778,10 @@ QcCtx ctx_qc(amp_ctx *c) {
 StrandCtx ctx_strand(amp_ctx *c) {
     return StrandCtx{c->device, c->ref_len, c->stream, c->do_trim, c->min_quality, c->n_cu, c->err, sizeof(c->err), &c->strand_on, &c->strand};
 }
+// ... and the per-amplicon counts (amp_amplicon.hip)
+AmpliconCtx ctx_amplicon(amp_ctx *c) {
+    return AmpliconCtx{c->device, c->ref_len, c->stream, c->do_trim, c->min_quality, c->n_cu, c->err, sizeof(c->err), &c->amplicon_on, &c->amplicon};
+}
 }  // namespace amp
 
 // ---------------------------------------------------------------------------------------
@@ -904,6 +911,7 @@ void amp_ctx_destroy(amp_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     qc_destroy(c);
     strand_destroy(c);
+    amplicon_destroy(c);
     if (c->own_counts && c->d_counts) (void)hipFree(c->d_counts);
     if (c->d_min_start) (void)hipFree(c->d_min_start);
     if (c->d_max_end) (void)hipFree(c->d_max_end);
@@ -1134,9 +1142,11 @@ int amp_process_batch_device(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
     c->staged_n = -1;          // (amp_event_strings(reads = NULL) refers to the last HOST batch: there is none now)
     if (c->qc_on && rd->n_reads) { const int qrc = qc_check_out(c, dev_out); if (qrc != AMP_OK) return qrc; }
     if (c->strand_on && rd->n_reads) { const int src = strand_check_out(c, dev_out); if (src != AMP_OK) return src; }
+    if (c->amplicon_on && rd->n_reads) { const int arc = amplicon_check_out(c, dev_out); if (arc != AMP_OK) return arc; }
     int rc = launch_reads(c, rd, read_base, dev_out);
     if (rc == AMP_OK && c->qc_on) rc = qc_enqueue_reads(c, rd, dev_out);        // k_qc_reads on the ctx stream
     if (rc == AMP_OK && c->strand_on) rc = strand_enqueue(c, rd, dev_out);      // k_strand on the ctx stream
+    if (rc == AMP_OK && c->amplicon_on) rc = amplicon_enqueue(c, rd, dev_out);  // k_amplicon on the ctx stream
     return rc;
 }
 
@@ -1177,6 +1187,7 @@ int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const 
     if (rc != AMP_OK) return rc;
     if (c->qc_on) { rc = qc_enqueue_reads(c, &rd, &dout); if (rc != AMP_OK) return rc; }      // k_qc_reads on the ctx stream
     if (c->strand_on) { rc = strand_enqueue(c, &rd, &dout); if (rc != AMP_OK) return rc; }    // k_strand on the ctx stream
+    if (c->amplicon_on) { rc = amplicon_enqueue(c, &rd, &dout); if (rc != AMP_OK) return rc; }        // k_amplicon on the ctx stream
     if (out) {
         if (out->new_pos) HIPCHK(c, hipMemcpyAsync(out->new_pos, dout.new_pos, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         if (out->new_ncig) HIPCHK(c, hipMemcpyAsync(out->new_ncig, dout.new_ncig, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -1344,7 +1355,9 @@ int amp_reset(amp_ctx *c) {
     k_reset<<<(unsigned)((words + ctr_words + 1023) / 1024), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, ctr_words);
     HIPCHK(c, hipGetLastError());
     const int qrc = qc_reset(c);   // (the report's tallies, when there is one)
-    return qrc != AMP_OK ? qrc : strand_reset(c);      // (... and the strand tables)
+    if (qrc != AMP_OK) return qrc;
+    const int src = strand_reset(c);                   // (... and the strand tables)
+    return src != AMP_OK ? src : amplicon_reset(c);    // (... and the per-amplicon tables and read counts)
 }
 
 // RCCL is resolved at run time so the library has no link-time dependency on it and uses

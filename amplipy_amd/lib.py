@@ -39,6 +39,7 @@ EXPORTS = [
     "amp_bam_set_references", "amp_bam_text_check", "amp_bam_format",
     "amp_qc_find_primer_owners", "amp_qc_enable", "amp_qc_read_tallies", "amp_qc_depth", "amp_qc_last_ms",
     "amp_strand_enable", "amp_strand_get", "amp_strand_add", "amp_strand_last_ms",
+    "amp_amplicon_enable", "amp_amplicon_get", "amp_amplicon_add", "amp_amplicon_last_ms",
 ]
 
 
@@ -329,6 +330,43 @@ class Engine:
     def strand_last_ms(self):
         t = C.c_float(0)
         self._chk(self.L.amp_strand_last_ms(self.h, C.byref(t)), "amp_strand_last_ms")
+        return float(t.value)
+
+    # ---- per-amplicon allele counts ---------------------------------------------------
+    def amplicon_enable(self, lo, hi, amp_start, amp_end):
+        """amp_amplicon_enable: the hook on for the amplicons with spans [lo[a], hi[a]) and the two owner tables
+        (int32[ref_len], -1: none), the tables zero.  ``amplicon_disable`` turns it off."""
+        lo = np.ascontiguousarray(lo, np.int32); hi = np.ascontiguousarray(hi, np.int32)
+        st = np.ascontiguousarray(amp_start, np.int32); en = np.ascontiguousarray(amp_end, np.int32)
+        if lo.size == 0 or lo.size != hi.size:
+            raise ValueError("one span per amplicon, at least one amplicon")
+        if st.size != self.ref_len or en.size != self.ref_len:
+            raise ValueError("the owner tables have one entry per reference position")
+        pad = lambda a: a if a.size else np.zeros(1, np.int32)          # (a reference of no bases: the pointers are still there)
+        self._chk(self.L.amp_amplicon_enable(self.h, C.c_int32(lo.size), C.c_void_p(abi.ptr(lo)), C.c_void_p(abi.ptr(hi)),
+                                             C.c_void_p(abi.ptr(pad(st))), C.c_void_p(abi.ptr(pad(en)))), "amp_amplicon_enable")
+        self._amplicon_shape = (int(lo.size), int((hi.astype(np.int64) - lo).sum()))
+
+    def amplicon_disable(self):
+        self._chk(self.L.amp_amplicon_enable(self.h, C.c_int32(0), None, None, None, None), "amp_amplicon_enable")
+
+    def amplicon_tables(self):
+        """amp_amplicon_get -> (counts uint32[sum span][6], reads uint64[n_amp + 1]) as they stand."""
+        n_amp, cells = getattr(self, "_amplicon_shape", (0, 0))
+        counts = np.zeros((max(cells, 1), abi.NSYM), np.uint32); reads = np.zeros(n_amp + 1, np.uint64)
+        self._chk(self.L.amp_amplicon_get(self.h, C.c_void_p(abi.ptr(counts)), C.c_void_p(abi.ptr(reads))), "amp_amplicon_get")
+        return counts[:cells], reads
+
+    def amplicon_add(self, counts, reads):
+        """amp_amplicon_add: host tables added element-wise (the merge of partial tables)."""
+        n_amp, cells = getattr(self, "_amplicon_shape", (0, 0))
+        c = np.ascontiguousarray(counts, np.uint32); r = np.ascontiguousarray(reads, np.uint64)
+        assert c.size == cells * abi.NSYM and r.size == n_amp + 1
+        self._chk(self.L.amp_amplicon_add(self.h, C.c_void_p(abi.ptr(c)), C.c_void_p(abi.ptr(r))), "amp_amplicon_add")
+
+    def amplicon_last_ms(self):
+        t = C.c_float(0)
+        self._chk(self.L.amp_amplicon_last_ms(self.h, C.byref(t)), "amp_amplicon_last_ms")
         return float(t.value)
 
     # ---- calling ---------------------------------------------------------------------

@@ -708,6 +708,27 @@ int amp_strand_add(amp_ctx *ctx, const uint32_t *rev, const uint64_t *qsum);
 /* Time of the tallies' kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_strand_last_ms(amp_ctx *ctx, float *ms);
 
+/* ---- per-amplicon allele counts (opt-in) ---------------------------------------------------------------------
+ * Which amplicon the evidence at a position comes from.  An amplicon a has a span [lo[a], hi[a]) of the reference; amp_start[p] /
+ * amp_end[p] (int32[ref_len], -1: none) name the amplicon whose left / right primer owns position p.  A read with status 0 that came
+ * in at [p, e) -- ORIGINAL coordinates, e = p + the reference bases of the original CIGAR -- belongs to the first of amp_start[p]
+ * (0 <= p < ref_len), amp_end[e - 1] (0 < e <= ref_len) whose span contains [p, e), else to none.  For every increment
+ * update_base_counts (AmpliPy.py:690-753) makes to one of the six fixed keys A C G T N '-' at position r for a read of amplicon a,
+ *   counts[cell_off[a] + r - lo[a]][c] += 1      (uint32[sum of hi - lo][6], cell_off[a] = sum of hi[b] - lo[b] over b < a)
+ *   reads[a] += 1 per read of a, reads[n_amp] += 1 per read with status 0 that belongs to none      (uint64[n_amp + 1])
+ * Insertion alleles are not part of the tables. */
+/* The hook on for the n_amp amplicons given (the arrays are copied; 0 <= lo < hi <= ref_len, owner entries in [-1, n_amp), the spans
+ * at most 2^22 positions together: AMP_EINVAL otherwise), the tables (allocated at the first call, again when the set's size changes)
+ * zero.  n_amp == 0 or a NULL array: off; the tables stay readable.  With the hook on and do_trim set, amp_process_batch_device
+ * refuses a dev_out without new_pos, new_ncig, new_cig or status (AMP_EINVAL) before anything runs. */
+int amp_amplicon_enable(amp_ctx *ctx, int32_t n_amp, const int32_t *lo, const int32_t *hi, const int32_t *amp_start, const int32_t *amp_end);
+/* Host copies of the tables as they stand (waits for the stream); either pointer may be NULL.  AMP_ESTATE before the first enable. */
+int amp_amplicon_get(amp_ctx *ctx, uint32_t *counts /* [sum span][6] */, uint64_t *reads /* [n_amp + 1] */);
+/* Host tables added element-wise, like amp_add_counts (the merge of partial tables); either pointer may be NULL. */
+int amp_amplicon_add(amp_ctx *ctx, const uint32_t *counts, const uint64_t *reads);
+/* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+int amp_amplicon_last_ms(amp_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
