@@ -58,20 +58,8 @@ static InsLayout carve(void *scratch, int64_t n_slots) {
     return L;
 }
 
-__device__ __forceinline__ uint32_t ins_code(const amp_dev_reads &rd, int64_t boff, int32_t q) {
-    const int64_t k = boff + q;
-    const uint32_t b = rd.seq[k >> 1];
-    return (k & 1) ? (b & 15u) : (b >> 4);
-}
-
-// slot j of the concatenated shard regions -> its event
-struct ShardMap { const amp_ins_event *ev; long long cap; long long start[9]; };      // start[s] = slots in front of shard s
-__device__ __forceinline__ const amp_ins_event &slot_event(const ShardMap &M, int64_t j) {
-    int s = 0;
-#pragma unroll
-    for (int k = 1; k < 8; ++k) s += j >= M.start[k] ? 1 : 0;
-    return M.ev[(size_t)s * (size_t)M.cap + (size_t)(j - M.start[s])];
-}
+// The per-event steps (nibble fetch, hash fold, position key, read-id rule, allele comparison, shard map, run number) are the
+// functions of amp_ins.hpp, which tests/hostsim/ins_twin.cpp runs on the CPU.
 
 // pass 1: hash of the allele's base codes (the low sort key); unused slots sort behind everything
 __global__ void k_ins_hash(amp_dev_reads rd, uint64_t read_base, ShardMap M, int64_t n_slots, uint64_t *key, uint32_t *idx, unsigned long long *nvalid) {
@@ -79,21 +67,16 @@ __global__ void k_ins_hash(amp_dev_reads rd, uint64_t read_base, ShardMap M, int
     if (j >= n_slots) return;
     const amp_ins_event e = slot_event(M, j);
     idx[j] = (uint32_t)j;
-    if (e.ref_pos < 0) { key[j] = ~0ull; return; }
-    const int64_t i = (int64_t)((uint64_t)e.read - read_base) & 0xFFFFFFFFll;
-    const int64_t boff = (int64_t)rd.seq_off8[i] * 8;
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-    for (int32_t q = e.q_from; q < e.q_to; ++q) { h ^= (uint64_t)ins_code(rd, boff, q) + 1ull; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 29; }
-    key[j] = h >> 1;                                         // (the top bit is kept for the unused slots)
-    atomicAdd(&nvalid[0], 1ull);
+    const uint64_t k = ins_hash_key(rd.seq, rd.seq_off8, read_base, e);
+    key[j] = k;
+    if (k != INS_KEY_UNUSED) atomicAdd(&nvalid[0], 1ull);      // (a real key has its top bit clear)
 }
 
 // pass 2: the high sort key of the events in hash order: ref_pos << 32 | length
 __global__ void k_ins_poskey(ShardMap M, int64_t n_slots, const uint32_t *idx, uint64_t *key) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_slots) return;
-    const amp_ins_event e = slot_event(M, (int64_t)idx[j]);
-    key[j] = e.ref_pos < 0 ? ~0ull : ((uint64_t)(uint32_t)e.ref_pos << 32) | (uint64_t)(uint32_t)(e.q_to - e.q_from);
+    key[j] = ins_pos_key(slot_event(M, (int64_t)idx[j]));
 }
 
 // an event opens a run when it differs from its predecessor in position, length or any base code
@@ -103,15 +86,8 @@ __global__ void k_ins_heads(amp_dev_reads rd, uint64_t read_base, ShardMap M, co
     const int64_t n = (int64_t)nvalid[0];
     if (j >= n) return;
     uint32_t h = 1u;
-    if (j > 0 && key[j] == key[j - 1]) {
-        const amp_ins_event a = slot_event(M, (int64_t)idx[j]), b = slot_event(M, (int64_t)idx[j - 1]);
-        const int64_t ia = (int64_t)((uint64_t)a.read - read_base) & 0xFFFFFFFFll, ib = (int64_t)((uint64_t)b.read - read_base) & 0xFFFFFFFFll;
-        const int64_t oa = (int64_t)rd.seq_off8[ia] * 8, ob = (int64_t)rd.seq_off8[ib] * 8;
-        const int32_t len = a.q_to - a.q_from;
-        bool same = true;
-        for (int32_t q = 0; q < len && same; ++q) same = ins_code(rd, oa, a.q_from + q) == ins_code(rd, ob, b.q_from + q);
-        h = same ? 0u : 1u;
-    }
+    if (j > 0 && key[j] == key[j - 1])
+        h = ins_same_allele(rd.seq, rd.seq_off8, read_base, slot_event(M, (int64_t)idx[j]), slot_event(M, (int64_t)idx[j - 1])) ? 0u : 1u;
     head[j] = h;
 }
 
@@ -121,8 +97,7 @@ __global__ void k_ins_runs(ShardMap M, const unsigned long long *nvalid, const u
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t n = (int64_t)nvalid[0];
     if (j >= n) return;
-    // rid = exclusive sum of head: the run of event j is rid[j] + head[j] - 1
-    const uint32_t r = rid[j] + head[j] - 1u;
+    const uint32_t r = ins_run_of(rid[j], head[j]);
     if (head[j]) runs[r].first = slot_event(M, (int64_t)idx[j]);
     atomicAdd(&runs[r].count, 1u);
     if (j == n - 1) nruns[0] = (unsigned long long)r + 1ull;
@@ -130,11 +105,8 @@ __global__ void k_ins_runs(ShardMap M, const unsigned long long *nvalid, const u
 
 int ins_aggregate(hipStream_t s, const amp_dev_reads &rd, uint64_t read_base, const amp_ins_event *ev, long long cap, const unsigned long long *shard_n,
                   void *scratch, amp_ins_run *d_runs, int64_t *n_events, int64_t *n_runs) {
-    ShardMap M;
-    M.ev = ev; M.cap = cap;
-    long long tot = 0;
-    for (int k = 0; k < 8; ++k) { M.start[k] = tot; tot += (long long)shard_n[k]; }
-    M.start[8] = tot;
+    const ShardMap M = ins_shard_map(ev, cap, shard_n);
+    const long long tot = M.start[8];
     *n_events = 0; *n_runs = 0;
     if (tot == 0) return 0;
     if (tot > 0x7FFFFFFFll) return -1;

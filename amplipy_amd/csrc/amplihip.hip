@@ -760,10 +760,10 @@ __global__ void k_event_strings(amp_dev_reads rd, uint64_t read_base, int64_t n_
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_ev) return;
     const char nt16[17] = "=ACMGRSVTWYHKDBN";
-    const int64_t i = (int64_t)((uint64_t)ev[e].read - read_base);
+    const int64_t i = amp::ins_read_row(ev[e].read, read_base);      // read ids are relative to read_base modulo 2^32, as in k_ins_hash
     const int64_t boff = (int64_t)rd.seq_off8[i] * 8;
     uint8_t *dst = text + off[e];
-    for (int32_t q = ev[e].q_from; q < ev[e].q_to; ++q) *dst++ = (uint8_t)nt16[base_code(rd.seq, boff, q)];
+    for (int32_t q = ev[e].q_from; q < ev[e].q_to; ++q) *dst++ = (uint8_t)nt16[amp::ins_code(rd.seq, boff, q)];
 }
 
 // what the device codecs (translation units of their own: amp_codec.hpp) need to know of a ctx
@@ -1277,6 +1277,7 @@ int amp_drain_ins_events(amp_ctx *c, int64_t *n, amp_ins_event *buf, int64_t cap
 
 int amp_aggregate_ins_events(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base, int drain, int64_t *n_runs, amp_ins_run *buf, int64_t cap) {
     if (!c || !n_runs) return AMP_EINVAL;
+    if (!rd && c->staged_n < 0) return AMP_ESTATE;       // no batch to read the alleles from: the size query says so, too
     Guard g(c);
     unsigned long long h[EV_SHARDS];
     HIPCHK(c, hipMemcpyAsync(h, &c->d_ctr[CTR_EV_SHARD0], sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -1288,7 +1289,6 @@ int amp_aggregate_ins_events(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
     if (total > cap) return AMP_EOVERFLOW;
     amp_dev_reads staged;
     if (!rd) {
-        if (c->staged_n < 0) return AMP_ESTATE;
         staged = staged_reads(c);
         rd = &staged;
     }
@@ -1569,8 +1569,8 @@ int amp_event_strings(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base, i
         rd = &staged;
     }
     for (int64_t e = 0; e < n_ev; ++e) {
-        uint64_t i = (uint64_t)ev[e].read - read_base;
-        if (i >= (uint64_t)rd->n_reads || ev[e].q_from < 0 || ev[e].q_to < ev[e].q_from ||
+        const int64_t i = amp::ins_read_row(ev[e].read, read_base);
+        if (i >= rd->n_reads || ev[e].q_from < 0 || ev[e].q_to < ev[e].q_from ||
             off[e + 1] - off[e] != (uint64_t)(ev[e].q_to - ev[e].q_from)) return AMP_EINVAL;
     }
     Guard g(c);

@@ -205,13 +205,17 @@ int amp_get_ins_events(amp_ctx *ctx, int64_t *n, amp_ins_event *buf, int64_t cap
 int amp_drain_ins_events(amp_ctx *ctx, int64_t *n, amp_ins_event *buf, int64_t cap);
 void *amp_counts_device_ptr(amp_ctx *ctx);
 /* On-device aggregation of the insertion events recorded since the last amp_reset / drain (the dict
- * keys of AmpliPy.py:745-748, consumed at A:767-771): the device sorts the events by (ref_pos, allele) and run-length
- * encodes them.  One amp_ins_run per run of events with the same position and the same allele text: `count` events and one
- * representative (its text through amp_event_strings).  Two runs may carry the same allele (a 64-bit hash collision between
- * two alleles of one position and length, never seen): the consumer sums counts by (ref_pos, text); a run never mixes alleles.
- * reads = the device batch the events' read ids refer to, read_base as given to amp_process_batch* (reads == NULL: the batch
- * of the last amp_process_batch call, still staged on the device).  buf == NULL: *n_runs = an upper bound (list slots in
- * use); buf != NULL (cap >= that bound): the records, *n_runs = their number, sorted by (ref_pos, allele length).
+ * keys of AmpliPy.py:745-748, consumed at A:767-771): the device sorts the events by (ref_pos, allele length, a 64-bit hash of
+ * the allele) and run-length encodes them.  One amp_ins_run per run of events with the same position and the same allele text:
+ * `count` events and one representative, an event of that run (its text through amp_event_strings); `reserved` is 0.  The runs
+ * are ordered by (ref_pos, allele length).  Equal alleles are adjacent, so an allele is one run, unless two alleles of one
+ * position and length collide in the hash and interleave (never seen): then an allele comes as more than one run, and the
+ * consumer sums counts by (ref_pos, text).  A run never mixes alleles.
+ * reads = the device batch the events' read ids refer to, read_base as given to amp_process_batch* (ids are taken relative to
+ * read_base modulo 2^32; reads == NULL: the batch of the last amp_process_batch call, still staged on the device --
+ * AMP_ESTATE when there is none, on a ctx that has taken no batch for one, whether or not buf is NULL and whether or not there
+ * are events).  buf == NULL: *n_runs = an upper bound (list slots in use); buf != NULL (cap >= that bound): the records,
+ * *n_runs = their number.  AMP_EOVERFLOW when a buffer reserved with amp_reserve_events was too small for the events.
  * drain != 0: the event list is empty afterwards (the per-position tally of amp_get_counts stays). */
 typedef struct amp_ins_run {
     amp_ins_event first;
@@ -356,7 +360,10 @@ int amp_call_compact_begin(amp_ctx *ctx, const amp_call_params *params);
  * SEQ[q_from:q_to] of event e (off[e+1]-off[e] must equal q_to-q_from). ev/off/text are host.
  * reads == NULL: the batch of the last amp_process_batch call (its device copy stays in the ctx until the next one;
  * AMP_ESTATE when there was none) -- a caller that feeds host batches gets the allele text of a batch's events
- * without gathering the bases on the host (AmpliPy.py:736-738 builds each string from the read it is looking at). */
+ * without gathering the bases on the host (AmpliPy.py:736-738 builds each string from the read it is looking at).
+ * An event's row is (read - read_base) modulo 2^32, as in amp_aggregate_ins_events: read ids are 32-bit and a batch's ids may
+ * wrap.  AMP_EINVAL when that row is not one of the batch, or q_from / q_to / off do not fit together; q_to is NOT held against
+ * the row's l_seq (that lives on the device): the caller passes events of this batch. */
 int amp_event_strings(amp_ctx *ctx, const amp_dev_reads *reads, uint64_t read_base, int64_t n_events,
                       const amp_ins_event *events, const uint64_t *off, uint8_t *text);
 

@@ -8,6 +8,7 @@ from amplipy_amd.batch import ReadBatch
 from oracle import oracle
 from tests import helpers as H
 from tests.gpu_util import GpuRunner, assert_same
+from tests.ins_util import _runs_as_counter
 
 pytestmark = pytest.mark.gpu
 
@@ -751,22 +752,6 @@ def test_event_text_from_the_staged_batch(scheme):
     a.add(b, ev, 1000); d.add_text(ev["ref_pos"], length, blob)
     assert a.pairs() == d.pairs()
     e.close()
-
-
-def _runs_as_counter(e, runs, read_base):
-    """{(ref_pos, allele text): events} of Engine.aggregate_events records (text of the representative events from the device)."""
-    from collections import Counter
-    from amplipy_amd import abi
-    rows = np.zeros(runs.size, abi.INS_EVENT_DTYPE)
-    for f in ("ref_pos", "q_from", "q_to"):
-        rows[f] = runs[f]
-    rows["read"] = runs["read"] - np.uint32(read_base)
-    length, blob = e.event_text(rows, 0) if runs.size else (np.zeros(0, np.int64), np.zeros(0, np.uint8))
-    raw = blob.tobytes(); off = np.cumsum(length) - length
-    out = Counter()
-    for k in range(runs.size):
-        out[(int(runs["ref_pos"][k]), raw[int(off[k]):int(off[k]) + int(length[k])].decode("ascii"))] += int(runs["count"][k])
-    return out
 
 
 def test_insertion_events_aggregated_on_the_device(scheme):
