@@ -16,9 +16,10 @@ SRC = os.path.join(CSRC, "amplihip.hip")
 HEADERS = [os.path.join(_HERE, "..", "include", "amplihip.h")] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
 UNIT_DEPS = {"amplihip.hip": HEADERS, "amp_ins.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_ins.hpp")],
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
-             "amp_qc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_qc.hpp")],
-             "amp_strand.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_strand.hpp")],
-             "amp_amplicon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_strand.hpp", "amp_amplicon.hpp")],
+             # (amp_hook.hpp: the host shell the three hooks behind the read pass share; amplihip.hip has it through HEADERS)
+             "amp_qc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_qc.hpp")],
+             "amp_strand.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp")],
+             "amp_amplicon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_amplicon.hpp")],
              "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in
                              ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamtail.hpp")],
              # (amp_bamout.hip, the re-encoder of trimmed records, and amp_bamtext.hip, trimmed records as SAM text, are part of

@@ -25,6 +25,7 @@
 #include <new>
 #include <vector>
 
+#include "amp_hook.hpp"
 #include "amp_amplicon.hpp"
 
 namespace amp {
@@ -37,8 +38,7 @@ struct AmpliconState {
     int32_t *d_start = nullptr, *d_end = nullptr;      // one allocation: amp_start, amp_end
     uint32_t *d_counts = nullptr;              // [cells][6]
     unsigned long long *d_reads = nullptr;     // [n_amp + 1]
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    HookTimer timer;
 };
 
 struct AmpliconArgs {
@@ -235,55 +235,29 @@ k_amplicon(AmpliconArgs a) {
     amplicon_flush(s_cell, s_slots, (1u << AM_SLOTS) - 1u, a);
 }
 
-#define AMCHK(q, call)                                                                                                       \
-    do {                                                                                                                     \
-        hipError_t e__ = (call);                                                                                             \
-        if (e__ != hipSuccess) {                                                                                             \
-            snprintf((q).err, (q).err_cap, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__);      \
-            return e__ == hipErrorOutOfMemory ? AMP_ENOMEM : AMP_EHIP;                                                       \
-        }                                                                                                                    \
-    } while (0)
-
-struct AmpliconGuard {      // the ctx's device is current for the duration of a call
-    int prev = -1;
-    explicit AmpliconGuard(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) (void)hipSetDevice(device);
-    }
-    ~AmpliconGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 static size_t count_bytes(const AmpliconState *s) { return (size_t)s->cells * AM_COLS * 4; }
 static size_t read_bytes(const AmpliconState *s) { return ((size_t)s->n_amp + 1) * 8; }
 
-static void amplicon_free(AmpliconState *s) {
+static AmpliconState *amplicon_state(amp_ctx *c) { return (AmpliconState *)hook_slot(c, HOOK_AMPLICON).state; }
+
+static void amplicon_free(void *state) {
+    AmpliconState *s = (AmpliconState *)state;
     if (!s) return;
     if (s->d_lo) (void)hipFree(s->d_lo);
     if (s->d_start) (void)hipFree(s->d_start);
     if (s->d_counts) (void)hipFree(s->d_counts);
     if (s->d_reads) (void)hipFree(s->d_reads);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    s->timer.destroy();
     delete s;
 }
 
-int amplicon_check_out(amp_ctx *c, const amp_trim_out *o) {
-    const AmpliconCtx q = ctx_amplicon(c);
-    if (q.do_trim && (!o || !o->new_pos || !o->new_ncig || !o->new_cig || !o->status)) {
-        snprintf(q.err, q.err_cap, "the amplicon tables need new_pos, new_ncig, new_cig and status of a trimming pass");
-        return AMP_EINVAL;
-    }
-    return AMP_OK;
-}
-
-int amplicon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
-    const AmpliconCtx q = ctx_amplicon(c);
-    AmpliconState *s = (AmpliconState *)*q.state;
-    if (!s) return AMP_ESTATE;
-    s->timed = false;
+static int amplicon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
+    const HookCtx q = ctx_hook(c);
+    AmpliconState *s = amplicon_state(c);
+    s->timer.timed = false;
     const int64_t n = rd->n_reads;
     if (n <= 0) return AMP_OK;
-    const int rc = amplicon_check_out(c, o);
+    const int rc = hook_check_out(q, o, amplicon_hook);
     if (rc != AMP_OK) return rc;
     AmpliconArgs a;
     a.n = n; a.pos = rd->pos; a.lseq = rd->lseq; a.cig_off32 = rd->cig_off32; a.cig = rd->cig; a.seq_off8 = rd->seq_off8;
@@ -294,37 +268,23 @@ int amplicon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o)
     a.P = StrandParams{q.ref_len, q.min_quality};
     a.T = AmpliconTables{q.ref_len, s->n_amp, s->d_lo, s->d_hi, s->d_off, s->d_start, s->d_end};
     a.counts = s->d_counts; a.reads = s->d_reads;
-    // a block takes AM_TILES_PER_BLOCK tiles and more (its slots go to the table when they move, not per tile), up to
-    // AM_BLOCKS_PER_CU blocks per CU; from there on the blocks take more tiles each
-    const int64_t tiles = (n + AM_BLOCK - 1) / AM_BLOCK;
-    const int64_t grid = std::min<int64_t>(std::max<int64_t>((tiles + AM_TILES_PER_BLOCK - 1) / AM_TILES_PER_BLOCK, 1), (int64_t)AM_BLOCKS_PER_CU * q.n_cu);
-    AMCHK(q, hipEventRecord(s->ev0, q.stream));
-    k_amplicon<<<(unsigned)grid, AM_BLOCK, 0, q.stream>>>(a);
-    AMCHK(q, hipGetLastError());
-    AMCHK(q, hipEventRecord(s->ev1, q.stream));
-    s->timed = true;
+    // (a block's slots go to the table when they move, not per tile)
+    HOOKCHK(q, s->timer.begin(q.stream));
+    k_amplicon<<<hook_grid(n, AM_BLOCK, AM_TILES_PER_BLOCK, AM_BLOCKS_PER_CU, q.n_cu), AM_BLOCK, 0, q.stream>>>(a);
+    HOOKCHK(q, hipGetLastError());
+    HOOKCHK(q, s->timer.end(q.stream));
     return AMP_OK;
 }
 
-static int amplicon_zero(const AmpliconCtx &q, AmpliconState *s) {
-    AMCHK(q, hipMemsetAsync(s->d_counts, 0, count_bytes(s), q.stream));
-    AMCHK(q, hipMemsetAsync(s->d_reads, 0, read_bytes(s), q.stream));
+static int amplicon_reset(amp_ctx *c) {
+    const HookCtx q = ctx_hook(c);
+    AmpliconState *s = amplicon_state(c);
+    HOOKCHK(q, hipMemsetAsync(s->d_counts, 0, count_bytes(s), q.stream));
+    HOOKCHK(q, hipMemsetAsync(s->d_reads, 0, read_bytes(s), q.stream));
     return AMP_OK;
 }
 
-int amplicon_reset(amp_ctx *c) {
-    const AmpliconCtx q = ctx_amplicon(c);
-    AmpliconState *s = (AmpliconState *)*q.state;
-    if (!s) return AMP_OK;
-    return amplicon_zero(q, s);
-}
-
-void amplicon_destroy(amp_ctx *c) {
-    const AmpliconCtx q = ctx_amplicon(c);
-    amplicon_free((AmpliconState *)*q.state);
-    *q.state = nullptr;
-    *q.on = false;
-}
+HookOps amplicon_hook = {"the amplicon tables need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, amplicon_enqueue, amplicon_reset, amplicon_free};
 
 }  // namespace amp
 
@@ -334,8 +294,9 @@ extern "C" {
 
 int amp_amplicon_enable(amp_ctx *c, int32_t n_amp, const int32_t *lo, const int32_t *hi, const int32_t *amp_start, const int32_t *amp_end) {
     if (!c) return AMP_EINVAL;
-    const AmpliconCtx q = ctx_amplicon(c);
-    if (n_amp == 0 || !lo || !hi || !amp_start || !amp_end) { *q.on = false; return AMP_OK; }
+    const HookCtx q = ctx_hook(c);
+    HookSlot &slot = hook_slot(c, HOOK_AMPLICON);
+    if (n_amp == 0 || !lo || !hi || !amp_start || !amp_end) { slot.on = false; return AMP_OK; }
     if (n_amp < 0) return AMP_EINVAL;
     const size_t A = (size_t)n_amp, G = (size_t)q.ref_len;
     std::vector<uint32_t> off(A);
@@ -358,88 +319,70 @@ int amp_amplicon_enable(amp_ctx *c, int32_t n_amp, const int32_t *lo, const int3
             return AMP_EINVAL;
         }
     }
-    AmpliconGuard g(q.device);
-    AmpliconState *s = (AmpliconState *)*q.state;
+    Guard g(q.device);
+    AmpliconState *s = amplicon_state(c);
     if (s && (s->n_amp != n_amp || s->cells != cells)) {
         // another amplicon set: the tables are laid out again (a kernel of the old one may still be in flight)
-        AMCHK(q, hipStreamSynchronize(q.stream));
+        HOOKCHK(q, hipStreamSynchronize(q.stream));
         amplicon_free(s);
-        s = nullptr; *q.state = nullptr; *q.on = false;
+        s = nullptr; slot.state = nullptr; slot.on = false;
     }
     if (!s) {
         s = new (std::nothrow) AmpliconState();
         if (!s) return AMP_ENOMEM;
-        struct Drop { AmpliconState *s; ~Drop() { amplicon_free(s); } } drop{s};      // until the state is handed to the ctx
+        HookDrop drop{amplicon_hook, s};
         s->n_amp = n_amp; s->cells = cells;
-        AMCHK(q, hipMalloc((void **)&s->d_lo, A * 12));
+        HOOKCHK(q, hipMalloc((void **)&s->d_lo, A * 12));
         s->d_hi = s->d_lo + A; s->d_off = (uint32_t *)(s->d_hi + A);
-        AMCHK(q, hipMalloc((void **)&s->d_start, std::max<size_t>(G * 8, 8)));
+        HOOKCHK(q, hipMalloc((void **)&s->d_start, std::max<size_t>(G * 8, 8)));
         s->d_end = s->d_start + G;
-        AMCHK(q, hipMalloc((void **)&s->d_counts, count_bytes(s)));
-        AMCHK(q, hipMalloc((void **)&s->d_reads, read_bytes(s)));
-        AMCHK(q, hipEventCreate(&s->ev0));
-        AMCHK(q, hipEventCreate(&s->ev1));
-        drop.s = nullptr;
-        *q.state = s;
+        HOOKCHK(q, hipMalloc((void **)&s->d_counts, count_bytes(s)));
+        HOOKCHK(q, hipMalloc((void **)&s->d_reads, read_bytes(s)));
+        HOOKCHK(q, s->timer.create());
+        drop.state = nullptr;
+        slot.state = s;
     }
-    *q.on = false;
-    AMCHK(q, hipMemcpyAsync(s->d_lo, lo, A * 4, hipMemcpyHostToDevice, q.stream));
-    AMCHK(q, hipMemcpyAsync(s->d_hi, hi, A * 4, hipMemcpyHostToDevice, q.stream));
-    AMCHK(q, hipMemcpyAsync(s->d_off, off.data(), A * 4, hipMemcpyHostToDevice, q.stream));
+    slot.on = false;
+    HOOKCHK(q, hipMemcpyAsync(s->d_lo, lo, A * 4, hipMemcpyHostToDevice, q.stream));
+    HOOKCHK(q, hipMemcpyAsync(s->d_hi, hi, A * 4, hipMemcpyHostToDevice, q.stream));
+    HOOKCHK(q, hipMemcpyAsync(s->d_off, off.data(), A * 4, hipMemcpyHostToDevice, q.stream));
     if (G) {
-        AMCHK(q, hipMemcpyAsync(s->d_start, amp_start, G * 4, hipMemcpyHostToDevice, q.stream));
-        AMCHK(q, hipMemcpyAsync(s->d_end, amp_end, G * 4, hipMemcpyHostToDevice, q.stream));
+        HOOKCHK(q, hipMemcpyAsync(s->d_start, amp_start, G * 4, hipMemcpyHostToDevice, q.stream));
+        HOOKCHK(q, hipMemcpyAsync(s->d_end, amp_end, G * 4, hipMemcpyHostToDevice, q.stream));
     }
-    const int rc = amplicon_zero(q, s);
+    const int rc = amplicon_reset(c);
     if (rc != AMP_OK) return rc;
-    AMCHK(q, hipStreamSynchronize(q.stream));        // (the caller's arrays and `off` are free again)
-    *q.on = true;
+    HOOKCHK(q, hipStreamSynchronize(q.stream));        // (the caller's arrays and `off` are free again)
+    slot.on = true;
     return AMP_OK;
 }
 
 int amp_amplicon_get(amp_ctx *c, uint32_t *counts, uint64_t *reads) {
     if (!c) return AMP_EINVAL;
-    const AmpliconCtx q = ctx_amplicon(c);
-    AmpliconState *s = (AmpliconState *)*q.state;
+    const HookCtx q = ctx_hook(c);
+    AmpliconState *s = amplicon_state(c);
     if (!s) return AMP_ESTATE;
-    AmpliconGuard g(q.device);
-    if (counts) AMCHK(q, hipMemcpyAsync(counts, s->d_counts, count_bytes(s), hipMemcpyDeviceToHost, q.stream));
-    if (reads) AMCHK(q, hipMemcpyAsync(reads, s->d_reads, read_bytes(s), hipMemcpyDeviceToHost, q.stream));
-    AMCHK(q, hipStreamSynchronize(q.stream));
+    Guard g(q.device);
+    if (counts) HOOKCHK(q, hipMemcpyAsync(counts, s->d_counts, count_bytes(s), hipMemcpyDeviceToHost, q.stream));
+    if (reads) HOOKCHK(q, hipMemcpyAsync(reads, s->d_reads, read_bytes(s), hipMemcpyDeviceToHost, q.stream));
+    HOOKCHK(q, hipStreamSynchronize(q.stream));
     return AMP_OK;
 }
 
 int amp_amplicon_add(amp_ctx *c, const uint32_t *counts, const uint64_t *reads) {
     if (!c) return AMP_EINVAL;
-    const AmpliconCtx q = ctx_amplicon(c);
-    AmpliconState *s = (AmpliconState *)*q.state;
+    const HookCtx q = ctx_hook(c);
+    AmpliconState *s = amplicon_state(c);
     if (!s) return AMP_ESTATE;
-    AmpliconGuard g(q.device);
-    // the tables to the host, the sums there, and back: a call per job (the merge of partial tables), not per batch
-    std::vector<uint32_t> hc(counts ? (size_t)s->cells * AM_COLS : 0);
-    std::vector<uint64_t> hr(reads ? (size_t)s->n_amp + 1 : 0);
-    if (counts) AMCHK(q, hipMemcpyAsync(hc.data(), s->d_counts, hc.size() * 4, hipMemcpyDeviceToHost, q.stream));
-    if (reads) AMCHK(q, hipMemcpyAsync(hr.data(), s->d_reads, hr.size() * 8, hipMemcpyDeviceToHost, q.stream));
-    AMCHK(q, hipStreamSynchronize(q.stream));
-    for (size_t k = 0; k < hc.size(); ++k) hc[k] += counts[k];
-    for (size_t k = 0; k < hr.size(); ++k) hr[k] += reads[k];
-    if (counts) AMCHK(q, hipMemcpyAsync(s->d_counts, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, q.stream));
-    if (reads) AMCHK(q, hipMemcpyAsync(s->d_reads, hr.data(), hr.size() * 8, hipMemcpyHostToDevice, q.stream));
-    AMCHK(q, hipStreamSynchronize(q.stream));
-    return AMP_OK;
+    Guard g(q.device);
+    const int rc = hook_add(q, s->d_counts, counts, (size_t)s->cells * AM_COLS);
+    return rc != AMP_OK ? rc : hook_add(q, (uint64_t *)s->d_reads, reads, (size_t)s->n_amp + 1);
 }
 
 int amp_amplicon_last_ms(amp_ctx *c, float *ms) {
     if (!c) return AMP_EINVAL;
-    const AmpliconCtx q = ctx_amplicon(c);
-    AmpliconState *s = (AmpliconState *)*q.state;
-    if (!s || !s->timed) return AMP_ESTATE;
-    AmpliconGuard g(q.device);
-    AMCHK(q, hipEventSynchronize(s->ev1));
-    float t = 0;
-    AMCHK(q, hipEventElapsedTime(&t, s->ev0, s->ev1));
-    if (ms) *ms = t;
-    return AMP_OK;
+    AmpliconState *s = amplicon_state(c);
+    return s ? s->timer.last_ms(ctx_hook(c), ms) : AMP_ESTATE;
 }
 
 }  // extern "C"

@@ -237,30 +237,4 @@ AMP_AM_HD int amplicon_read_slot(const AmSlots &S, int32_t a, const StrandShape 
 }
 
 }  // namespace amp
-
-#ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-
-namespace amp {
-
-// What amp_amplicon.hip needs to know of a ctx (amplihip.hip owns the struct and fills this in).
-struct AmpliconCtx {
-    int device;
-    int32_t ref_len;
-    hipStream_t stream;
-    int do_trim, min_quality, n_cu;
-    char *err; size_t err_cap;
-    bool *on;                   // the switch the two hooks of amplihip.hip read
-    void **state;               // the tables and the timer, owned by amp_amplicon.hip
-};
-AmpliconCtx ctx_amplicon(amp_ctx *c);
-
-// The hooks of amplihip.hip.  amplicon_check_out: the result arrays the kernel reads are there (in front of the pass, so
-// that a refused call changes nothing).  amplicon_enqueue: k_amplicon behind the read pass on the ctx stream.
-int amplicon_check_out(amp_ctx *c, const amp_trim_out *dev_out);
-int amplicon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *dev_out);
-int amplicon_reset(amp_ctx *c);       // amp_reset: the tables and read counts start over
-void amplicon_destroy(amp_ctx *c);    // amp_ctx_destroy
-
-}  // namespace amp
-#endif
+// (the hook amplihip.hip runs behind the read pass is amplicon_hook of amp_amplicon.hip, declared in amp_hook.hpp)

@@ -1,0 +1,154 @@
+// amp_hook.hpp -- the host shell of the opt-in kernels that run behind every batch's read pass: the QC
+// report (amp_qc.hip), the strand tallies (amp_strand.hip), the per-amplicon counts (amp_amplicon.hip).  What a hook needs to
+// know of a ctx, and what the hooks have in common -- the check macro, the device guard, the timer round a launch, the grid
+// rule, the merge of host tables, the check of a trimming pass's results -- each once.  amplihip.hip owns amp_ctx, keeps one
+// slot (switch, state) per hook and walks the table of HookOps; a unit keeps its state, its kernels and what it enables.
+#pragma once
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/amplihip.h"
+
+// `call` failed: the message (with `text`, the call as written) to err and the call's code out of the enclosing function
+#define AMP_HIPCHK(err, cap, text, call)                                                                                     \
+    do {                                                                                                                     \
+        hipError_t e__ = (call);                                                                                             \
+        if (e__ != hipSuccess) {                                                                                             \
+            snprintf((err), (cap), "%s failed: %s (%s:%d)", text, hipGetErrorString(e__), __FILE__, __LINE__);               \
+            return e__ == hipErrorOutOfMemory ? AMP_ENOMEM : AMP_EHIP;                                                       \
+        }                                                                                                                    \
+    } while (0)
+#define HOOKCHK(q, call) AMP_HIPCHK((q).err, (q).err_cap, #call, call)       // q: a HookCtx
+
+namespace amp {
+
+struct Guard {      // the device is current for the duration of a call
+    int prev = -1;
+    bool ok = true;
+    explicit Guard(int device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != device) ok = hipSetDevice(device) == hipSuccess;
+    }
+    ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// What a hook needs to know of a ctx (amplihip.hip owns the struct and fills this in).
+struct HookCtx {
+    int device;
+    int32_t ref_len;
+    hipStream_t stream;
+    const uint32_t *counts;     // the device table as it stands
+    int do_trim, have_primers, min_quality, n_cu;
+    char *err; size_t err_cap;
+};
+HookCtx ctx_hook(amp_ctx *c);
+
+// The hooks; the numeric order is the order their kernels run in behind the read pass.
+enum { HOOK_QC, HOOK_STRAND, HOOK_AMPLICON, N_HOOKS };
+struct HookSlot {
+    bool on;                    // the switch amplihip.hip reads per batch
+    void *state;                // the hook's device state, owned by its unit; it outlives the switch (tables stay readable)
+};
+HookSlot &hook_slot(amp_ctx *c, int which);
+
+// The results of a trimming pass (the fields of amp_trim_out, in its order) a hook's kernel reads.
+enum : uint32_t { OUT_NEW_POS = 1u, OUT_NEW_NCIG = 2u, OUT_NEW_CIG = 4u, OUT_REF_LEN = 8u, OUT_TRIM_FLAGS = 16u, OUT_STATUS = 32u };
+
+struct HookOps {
+    const char *name;           // as a refusal begins: "the QC report needs"
+    uint32_t needs;             // OUT_* bits
+    int (*enqueue)(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *dev_out);       // the kernel on the ctx stream; the state exists
+    int (*reset)(amp_ctx *c);   // amp_reset: the tables start over; the state exists
+    void (*free_state)(void *state);        // null: nothing to do
+};
+// One per unit; amplihip.hip keeps them in enum order.  (Not const objects, though nothing writes them: hipcc emits a const
+// object with a constant initialiser into the device image as well, host function pointers and all.)
+extern HookOps qc_hook, strand_hook, amplicon_hook;
+
+// With trimming on, every result in `needs` must be there; otherwise the refusal is in q.err.  amplihip.hip asks in front of a
+// device batch's read pass, so that a refused call changes nothing; an enqueue asks again.
+inline int hook_check_out(const HookCtx &q, const amp_trim_out *o, const HookOps &ops) {
+    if (!q.do_trim) return AMP_OK;
+    static const char *const field[] = {"new_pos", "new_ncig", "new_cig", "ref_len", "trim_flags", "status"};
+    const void *have[] = {o ? o->new_pos : nullptr, o ? o->new_ncig : nullptr, o ? o->new_cig : nullptr,
+                          o ? o->ref_len : nullptr, o ? o->trim_flags : nullptr, o ? o->status : nullptr};
+    bool all = true;
+    char list[80];
+    int at = 0;
+    for (int k = 0; k < 6; ++k) {
+        if (!((ops.needs >> k) & 1u)) continue;
+        all = all && have[k];
+        const uint32_t later = ops.needs >> (k + 1);
+        at += snprintf(list + at, sizeof(list) - (size_t)at, "%s%s", field[k], !later ? "" : (later & (later - 1u)) ? ", " : " and ");
+    }
+    if (all) return AMP_OK;
+    snprintf(q.err, q.err_cap, "%s %s of a trimming pass", ops.name, list);
+    return AMP_EINVAL;
+}
+
+struct HookTimer {              // the time of a hook's last kernel: an event on either side of the launch
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;         // cleared at the start of every enqueue: a batch without reads leaves nothing to ask for
+    hipError_t create() {
+        const hipError_t e = hipEventCreate(&ev0);
+        return e != hipSuccess ? e : hipEventCreate(&ev1);
+    }
+    void destroy() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        ev0 = ev1 = nullptr;
+    }
+    hipError_t begin(hipStream_t s) { return hipEventRecord(ev0, s); }
+    hipError_t end(hipStream_t s) {
+        const hipError_t e = hipEventRecord(ev1, s);
+        timed = e == hipSuccess;
+        return e;
+    }
+    int last_ms(const HookCtx &q, float *ms) {      // waits for the kernel; AMP_ESTATE when the last batch launched none
+        if (!timed) return AMP_ESTATE;
+        Guard g(q.device);
+        HOOKCHK(q, hipEventSynchronize(ev1));
+        float t = 0;
+        HOOKCHK(q, hipEventElapsedTime(&t, ev0, ev1));
+        if (ms) *ms = t;
+        return AMP_OK;
+    }
+};
+
+// The grid of a hook's kernel over n reads: a block takes tiles_per_block tiles of `block` reads and more (what a block pays
+// once -- an LDS histogram, a window's flush -- is paid for several tiles), up to blocks_per_cu blocks per CU; from there on
+// the blocks take more tiles each.
+inline unsigned hook_grid(int64_t n, int block, int tiles_per_block, int blocks_per_cu, int n_cu) {
+    const int64_t tiles = (n + block - 1) / block;
+    return (unsigned)std::min<int64_t>(std::max<int64_t>((tiles + tiles_per_block - 1) / tiles_per_block, 1), (int64_t)blocks_per_cu * n_cu);
+}
+
+// dev[k] += host[k]: the table to the host, the sums there, and back.  A call per job (the merge of partial tables), not per
+// batch.  A null host table is left out.
+template <class T>
+int hook_add(const HookCtx &q, T *dev, const T *host, size_t count) {
+    if (!host || !count) return AMP_OK;
+    std::vector<T> h(count);
+    HOOKCHK(q, hipMemcpyAsync(h.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost, q.stream));
+    HOOKCHK(q, hipStreamSynchronize(q.stream));
+    for (size_t k = 0; k < count; ++k) h[k] += host[k];
+    HOOKCHK(q, hipMemcpyAsync(dev, h.data(), count * sizeof(T), hipMemcpyHostToDevice, q.stream));
+    HOOKCHK(q, hipStreamSynchronize(q.stream));
+    return AMP_OK;
+}
+
+struct HookDrop {               // a state under construction is freed unless it was handed to the ctx (state = nullptr)
+    const HookOps &ops;
+    void *state;
+    ~HookDrop() { ops.free_state(state); }
+};
+
+}  // namespace amp
+#endif

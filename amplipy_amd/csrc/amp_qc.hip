@@ -20,6 +20,7 @@
 #include <new>
 #include <vector>
 
+#include "amp_hook.hpp"
 #include "amp_qc.hpp"
 
 namespace amp {
@@ -31,8 +32,7 @@ struct QcState {
     int32_t *d_rstart = nullptr, *d_rend = nullptr;       // [n_regions], clamped
     amp_qc_region *d_regions = nullptr;                   // [n_regions]
     uint32_t *d_depth = nullptr;                          // [ref_len]
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    HookTimer timer;
     size_t tally_words() const { return (size_t)QC_N_TALLIES + 2 * (size_t)p.n_primers; }
 };
 
@@ -175,50 +175,24 @@ k_qc_regions(const uint32_t *__restrict__ depth, int32_t n_regions, const int32_
     }
 }
 
-#define QCCHK(q, call)                                                                                                       \
-    do {                                                                                                                     \
-        hipError_t e__ = (call);                                                                                             \
-        if (e__ != hipSuccess) {                                                                                             \
-            snprintf((q).err, (q).err_cap, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__);      \
-            return e__ == hipErrorOutOfMemory ? AMP_ENOMEM : AMP_EHIP;                                                       \
-        }                                                                                                                    \
-    } while (0)
+static QcState *qc_state(amp_ctx *c) { return (QcState *)hook_slot(c, HOOK_QC).state; }
 
-struct QcGuard {      // the ctx's device is current for the duration of a call
-    int prev = -1;
-    explicit QcGuard(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) (void)hipSetDevice(device);
-    }
-    ~QcGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-static void qc_free(QcState *s) {
+static void qc_free(void *state) {
+    QcState *s = (QcState *)state;
     if (!s) return;
     void *bufs[] = {s->d_left, s->d_right, s->d_tally, s->d_rstart, s->d_rend, s->d_regions, s->d_depth};
     for (void *b : bufs) if (b) (void)hipFree(b);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    s->timer.destroy();
     delete s;
 }
 
-int qc_check_out(amp_ctx *c, const amp_trim_out *o) {
-    const QcCtx q = ctx_qc(c);
-    if (q.do_trim && (!o || !o->new_pos || !o->ref_len || !o->trim_flags || !o->status)) {
-        snprintf(q.err, q.err_cap, "the QC report needs new_pos, ref_len, trim_flags and status of a trimming pass");
-        return AMP_EINVAL;
-    }
-    return AMP_OK;
-}
-
-int qc_enqueue_reads(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
-    const QcCtx q = ctx_qc(c);
-    QcState *s = (QcState *)*q.state;
-    if (!s) return AMP_ESTATE;
-    s->timed = false;
+static int qc_enqueue_reads(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
+    const HookCtx q = ctx_hook(c);
+    QcState *s = qc_state(c);
+    s->timer.timed = false;
     const int64_t n = rd->n_reads;
     if (n <= 0) return AMP_OK;
-    int rc = qc_check_out(c, o);
+    const int rc = hook_check_out(q, o, qc_hook);
     if (rc != AMP_OK) return rc;
     QcReadsArgs a;
     a.n = n; a.pos = rd->pos; a.cig_off32 = rd->cig_off32; a.cig = rd->cig;
@@ -226,33 +200,23 @@ int qc_enqueue_reads(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o)
     a.left_owner = s->d_left; a.right_owner = s->d_right;
     a.tally = s->d_tally; a.n_primers = s->p.n_primers;
     a.P = QcReadParams{q.ref_len, q.do_trim ? 1 : 0, s->p.min_length, s->p.include_no_primer};
-    // a block takes QC_TILES_PER_BLOCK tiles and more (its LDS histogram and its twelve adds are paid once), up to
-    // QC_BLOCKS_PER_CU blocks per CU; from there on the blocks take more tiles each
-    const int64_t tiles = (n + QC_BLOCK - 1) / QC_BLOCK;
-    const int64_t grid = std::min<int64_t>(std::max<int64_t>((tiles + QC_TILES_PER_BLOCK - 1) / QC_TILES_PER_BLOCK, 1), (int64_t)QC_BLOCKS_PER_CU * q.n_cu);
-    QCCHK(q, hipEventRecord(s->ev0, q.stream));
-    if (2 * (int64_t)s->p.n_primers <= QC_LDS_COUNTERS) k_qc_reads<true><<<(unsigned)grid, QC_BLOCK, 0, q.stream>>>(a);
-    else k_qc_reads<false><<<(unsigned)grid, QC_BLOCK, 0, q.stream>>>(a);
-    QCCHK(q, hipGetLastError());
-    QCCHK(q, hipEventRecord(s->ev1, q.stream));
-    s->timed = true;
+    const unsigned grid = hook_grid(n, QC_BLOCK, QC_TILES_PER_BLOCK, QC_BLOCKS_PER_CU, q.n_cu);     // (paid once per block: its LDS histogram and its twelve adds)
+    HOOKCHK(q, s->timer.begin(q.stream));
+    if (2 * (int64_t)s->p.n_primers <= QC_LDS_COUNTERS) k_qc_reads<true><<<grid, QC_BLOCK, 0, q.stream>>>(a);
+    else k_qc_reads<false><<<grid, QC_BLOCK, 0, q.stream>>>(a);
+    HOOKCHK(q, hipGetLastError());
+    HOOKCHK(q, s->timer.end(q.stream));
     return AMP_OK;
 }
 
-int qc_reset(amp_ctx *c) {
-    const QcCtx q = ctx_qc(c);
-    QcState *s = (QcState *)*q.state;
-    if (!s) return AMP_OK;
-    QCCHK(q, hipMemsetAsync(s->d_tally, 0, s->tally_words() * sizeof(unsigned long long), q.stream));
+static int qc_reset(amp_ctx *c) {
+    const HookCtx q = ctx_hook(c);
+    QcState *s = qc_state(c);
+    HOOKCHK(q, hipMemsetAsync(s->d_tally, 0, s->tally_words() * sizeof(unsigned long long), q.stream));
     return AMP_OK;
 }
 
-void qc_destroy(amp_ctx *c) {
-    const QcCtx q = ctx_qc(c);
-    qc_free((QcState *)*q.state);
-    *q.state = nullptr;
-    *q.on = false;
-}
+HookOps qc_hook = {"the QC report needs", OUT_NEW_POS | OUT_REF_LEN | OUT_TRIM_FLAGS | OUT_STATUS, qc_enqueue_reads, qc_reset, qc_free};
 
 }  // namespace amp
 
@@ -284,20 +248,21 @@ int amp_qc_find_primer_owners(int32_t ref_len, int32_t n, const int32_t *starts,
 
 int amp_qc_enable(amp_ctx *c, const amp_qc_params *p) {
     if (!c) return AMP_EINVAL;
-    const QcCtx q = ctx_qc(c);
-    if (!p) { *q.on = false; return AMP_OK; }
+    const HookCtx q = ctx_hook(c);
+    HookSlot &slot = hook_slot(c, HOOK_QC);
+    if (!p) { slot.on = false; return AMP_OK; }
     if (p->n_primers < 0 || (p->n_primers && (!p->starts || !p->ends)) || p->primer_pos_offset < 0 || p->n_regions < 0 ||
         (p->n_regions && (!p->region_start || !p->region_end)) || p->n_depths < 0 || p->n_depths > AMP_QC_MAX_DEPTHS) return AMP_EINVAL;
     for (int32_t k = 1; k < p->n_primers; ++k)
         if (p->starts[k] < p->starts[k - 1] || (p->starts[k] == p->starts[k - 1] && p->ends[k] < p->ends[k - 1])) return AMP_EINVAL;
     if (q.do_trim && !q.have_primers) return AMP_ESTATE;
-    QcGuard g(q.device);
-    QCCHK(q, hipStreamSynchronize(q.stream));        // (a report that is replaced may still have a kernel in flight)
-    qc_free((QcState *)*q.state);
-    *q.state = nullptr; *q.on = false;
+    Guard g(q.device);
+    HOOKCHK(q, hipStreamSynchronize(q.stream));      // (a report that is replaced may still have a kernel in flight)
+    qc_free(slot.state);
+    slot.state = nullptr; slot.on = false;
     QcState *s = new (std::nothrow) QcState();
     if (!s) return AMP_ENOMEM;
-    struct Drop { QcState *s; ~Drop() { qc_free(s); } } drop{s};      // until the state is handed to the ctx
+    HookDrop drop{qc_hook, s};
     s->p = *p;
     s->p.starts = s->p.ends = s->p.region_start = s->p.region_end = nullptr;
     const size_t G = (size_t)q.ref_len, R = (size_t)p->n_regions;
@@ -308,76 +273,68 @@ int amp_qc_enable(amp_ctx *c, const amp_qc_params *p) {
         rs[r] = p->region_start[r]; re[r] = p->region_end[r];
         qc_region_clamp(q.ref_len, rs[r], re[r]);
     }
-    QCCHK(q, hipMalloc((void **)&s->d_left, G * 4));
-    QCCHK(q, hipMalloc((void **)&s->d_right, G * 4));
-    QCCHK(q, hipMalloc((void **)&s->d_depth, G * 4));
-    QCCHK(q, hipMalloc((void **)&s->d_tally, s->tally_words() * sizeof(unsigned long long)));
+    HOOKCHK(q, hipMalloc((void **)&s->d_left, G * 4));
+    HOOKCHK(q, hipMalloc((void **)&s->d_right, G * 4));
+    HOOKCHK(q, hipMalloc((void **)&s->d_depth, G * 4));
+    HOOKCHK(q, hipMalloc((void **)&s->d_tally, s->tally_words() * sizeof(unsigned long long)));
     if (R) {
-        QCCHK(q, hipMalloc((void **)&s->d_rstart, R * 4));
-        QCCHK(q, hipMalloc((void **)&s->d_rend, R * 4));
-        QCCHK(q, hipMalloc((void **)&s->d_regions, R * sizeof(amp_qc_region)));
-        QCCHK(q, hipMemcpyAsync(s->d_rstart, rs.data(), R * 4, hipMemcpyHostToDevice, q.stream));
-        QCCHK(q, hipMemcpyAsync(s->d_rend, re.data(), R * 4, hipMemcpyHostToDevice, q.stream));
+        HOOKCHK(q, hipMalloc((void **)&s->d_rstart, R * 4));
+        HOOKCHK(q, hipMalloc((void **)&s->d_rend, R * 4));
+        HOOKCHK(q, hipMalloc((void **)&s->d_regions, R * sizeof(amp_qc_region)));
+        HOOKCHK(q, hipMemcpyAsync(s->d_rstart, rs.data(), R * 4, hipMemcpyHostToDevice, q.stream));
+        HOOKCHK(q, hipMemcpyAsync(s->d_rend, re.data(), R * 4, hipMemcpyHostToDevice, q.stream));
     }
-    QCCHK(q, hipMemcpyAsync(s->d_left, lo.data(), G * 4, hipMemcpyHostToDevice, q.stream));
-    QCCHK(q, hipMemcpyAsync(s->d_right, ro.data(), G * 4, hipMemcpyHostToDevice, q.stream));
-    QCCHK(q, hipMemsetAsync(s->d_tally, 0, s->tally_words() * sizeof(unsigned long long), q.stream));
-    QCCHK(q, hipEventCreate(&s->ev0));
-    QCCHK(q, hipEventCreate(&s->ev1));
-    QCCHK(q, hipStreamSynchronize(q.stream));        // (the host vectors go away)
-    drop.s = nullptr;
-    *q.state = s; *q.on = true;
+    HOOKCHK(q, hipMemcpyAsync(s->d_left, lo.data(), G * 4, hipMemcpyHostToDevice, q.stream));
+    HOOKCHK(q, hipMemcpyAsync(s->d_right, ro.data(), G * 4, hipMemcpyHostToDevice, q.stream));
+    HOOKCHK(q, hipMemsetAsync(s->d_tally, 0, s->tally_words() * sizeof(unsigned long long), q.stream));
+    HOOKCHK(q, s->timer.create());
+    HOOKCHK(q, hipStreamSynchronize(q.stream));        // (the host vectors go away)
+    drop.state = nullptr;
+    slot.state = s; slot.on = true;
     return AMP_OK;
 }
 
 int amp_qc_read_tallies(amp_ctx *c, amp_qc_reads *out, uint64_t *primer_reads_start, uint64_t *primer_reads_end) {
     if (!c) return AMP_EINVAL;
-    const QcCtx q = ctx_qc(c);
-    QcState *s = (QcState *)*q.state;
+    const HookCtx q = ctx_hook(c);
+    QcState *s = qc_state(c);
     if (!s) return AMP_ESTATE;
-    QcGuard g(q.device);
+    Guard g(q.device);
     const size_t np = (size_t)s->p.n_primers;
-    if (out) QCCHK(q, hipMemcpyAsync(out, s->d_tally, sizeof(amp_qc_reads), hipMemcpyDeviceToHost, q.stream));
-    if (primer_reads_start && np) QCCHK(q, hipMemcpyAsync(primer_reads_start, s->d_tally + QC_N_TALLIES, np * 8, hipMemcpyDeviceToHost, q.stream));
-    if (primer_reads_end && np) QCCHK(q, hipMemcpyAsync(primer_reads_end, s->d_tally + QC_N_TALLIES + np, np * 8, hipMemcpyDeviceToHost, q.stream));
-    QCCHK(q, hipStreamSynchronize(q.stream));
+    if (out) HOOKCHK(q, hipMemcpyAsync(out, s->d_tally, sizeof(amp_qc_reads), hipMemcpyDeviceToHost, q.stream));
+    if (primer_reads_start && np) HOOKCHK(q, hipMemcpyAsync(primer_reads_start, s->d_tally + QC_N_TALLIES, np * 8, hipMemcpyDeviceToHost, q.stream));
+    if (primer_reads_end && np) HOOKCHK(q, hipMemcpyAsync(primer_reads_end, s->d_tally + QC_N_TALLIES + np, np * 8, hipMemcpyDeviceToHost, q.stream));
+    HOOKCHK(q, hipStreamSynchronize(q.stream));
     return AMP_OK;
 }
 
 int amp_qc_depth(amp_ctx *c, uint32_t *depth, amp_qc_region *regions) {
     if (!c) return AMP_EINVAL;
-    const QcCtx q = ctx_qc(c);
-    QcState *s = (QcState *)*q.state;
+    const HookCtx q = ctx_hook(c);
+    QcState *s = qc_state(c);
     if (!s) return AMP_ESTATE;
-    QcGuard g(q.device);
+    Guard g(q.device);
     const int64_t blocks = ((int64_t)q.ref_len + QC_BLOCK - 1) / QC_BLOCK;
     k_qc_depth<<<(unsigned)std::min<int64_t>(blocks, (int64_t)QC_BLOCKS_PER_CU * q.n_cu), QC_BLOCK, 0, q.stream>>>(q.counts, q.ref_len, s->d_depth);
-    QCCHK(q, hipGetLastError());
-    if (depth) QCCHK(q, hipMemcpyAsync(depth, s->d_depth, (size_t)q.ref_len * 4, hipMemcpyDeviceToHost, q.stream));
+    HOOKCHK(q, hipGetLastError());
+    if (depth) HOOKCHK(q, hipMemcpyAsync(depth, s->d_depth, (size_t)q.ref_len * 4, hipMemcpyDeviceToHost, q.stream));
     const int32_t R = s->p.n_regions;
     if (regions && R) {
         QcDepths dp;
         dp.n = s->p.n_depths;
         for (int k = 0; k < AMP_QC_MAX_DEPTHS; ++k) dp.d[k] = k < dp.n ? s->p.depths[k] : 0u;
         k_qc_regions<<<(unsigned)std::min<int64_t>(R, (int64_t)QC_BLOCKS_PER_CU * q.n_cu), QC_BLOCK, 0, q.stream>>>(s->d_depth, R, s->d_rstart, s->d_rend, dp, s->d_regions);
-        QCCHK(q, hipGetLastError());
-        QCCHK(q, hipMemcpyAsync(regions, s->d_regions, (size_t)R * sizeof(amp_qc_region), hipMemcpyDeviceToHost, q.stream));
+        HOOKCHK(q, hipGetLastError());
+        HOOKCHK(q, hipMemcpyAsync(regions, s->d_regions, (size_t)R * sizeof(amp_qc_region), hipMemcpyDeviceToHost, q.stream));
     }
-    QCCHK(q, hipStreamSynchronize(q.stream));
+    HOOKCHK(q, hipStreamSynchronize(q.stream));
     return AMP_OK;
 }
 
 int amp_qc_last_ms(amp_ctx *c, float *reads_ms) {
     if (!c) return AMP_EINVAL;
-    const QcCtx q = ctx_qc(c);
-    QcState *s = (QcState *)*q.state;
-    if (!s || !s->timed) return AMP_ESTATE;
-    QcGuard g(q.device);
-    QCCHK(q, hipEventSynchronize(s->ev1));
-    float t = 0;
-    QCCHK(q, hipEventElapsedTime(&t, s->ev0, s->ev1));
-    if (reads_ms) *reads_ms = t;
-    return AMP_OK;
+    QcState *s = qc_state(c);
+    return s ? s->timer.last_ms(ctx_hook(c), reads_ms) : AMP_ESTATE;
 }
 
 }  // extern "C"

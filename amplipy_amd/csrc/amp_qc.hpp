@@ -140,31 +140,4 @@ AMP_QC_HD amp_qc_region qc_region_result(int32_t start, int32_t end, const QcReg
 }
 
 }  // namespace amp
-
-#ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-
-namespace amp {
-
-// What amp_qc.hip needs to know of a ctx (amplihip.hip owns the struct and fills this in).
-struct QcCtx {
-    int device;
-    int32_t ref_len;
-    hipStream_t stream;
-    const uint32_t *counts;     // the device table as it stands
-    int do_trim, have_primers, n_cu;
-    char *err; size_t err_cap;
-    bool *on;                   // the switch the two hooks of amplihip.hip read
-    void **state;               // the report's device state, owned by amp_qc.hip
-};
-QcCtx ctx_qc(amp_ctx *c);
-
-// The hooks of amplihip.hip.  qc_check_out: the result arrays the report reads are there (in front of the pass, so that a
-// refused call changes nothing).  qc_enqueue_reads: k_qc_reads behind the read pass on the ctx stream.
-int qc_check_out(amp_ctx *c, const amp_trim_out *dev_out);
-int qc_enqueue_reads(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *dev_out);
-int qc_reset(amp_ctx *c);       // amp_reset: the tallies start over
-void qc_destroy(amp_ctx *c);    // amp_ctx_destroy
-
-}  // namespace amp
-#endif
+// (the hook amplihip.hip runs behind the read pass is qc_hook of amp_qc.hip, declared in amp_hook.hpp)

@@ -24,6 +24,7 @@
 #include <new>
 #include <vector>
 
+#include "amp_hook.hpp"
 #include "amp_strand.hpp"
 
 namespace amp {
@@ -31,8 +32,7 @@ namespace amp {
 struct StrandState {
     unsigned long long *d_qsum = nullptr;      // [ref_len][5]; one allocation of 64 bytes per position with ...
     uint32_t *d_rev = nullptr;                 // ... [ref_len][6] behind it
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    HookTimer timer;
 };
 
 struct StrandArgs {
@@ -182,51 +182,25 @@ k_strand(StrandArgs a) {
     strand_flush(s_cell, anchor, a);
 }
 
-#define STCHK(q, call)                                                                                                       \
-    do {                                                                                                                     \
-        hipError_t e__ = (call);                                                                                             \
-        if (e__ != hipSuccess) {                                                                                             \
-            snprintf((q).err, (q).err_cap, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__);      \
-            return e__ == hipErrorOutOfMemory ? AMP_ENOMEM : AMP_EHIP;                                                       \
-        }                                                                                                                    \
-    } while (0)
-
-struct StrandGuard {      // the ctx's device is current for the duration of a call
-    int prev = -1;
-    explicit StrandGuard(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) (void)hipSetDevice(device);
-    }
-    ~StrandGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 static size_t strand_bytes(int32_t ref_len) { return (size_t)ref_len * 64; }
 
-static void strand_free(StrandState *s) {
+static StrandState *strand_state(amp_ctx *c) { return (StrandState *)hook_slot(c, HOOK_STRAND).state; }
+
+static void strand_free(void *state) {
+    StrandState *s = (StrandState *)state;
     if (!s) return;
     if (s->d_qsum) (void)hipFree(s->d_qsum);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    s->timer.destroy();
     delete s;
 }
 
-int strand_check_out(amp_ctx *c, const amp_trim_out *o) {
-    const StrandCtx q = ctx_strand(c);
-    if (q.do_trim && (!o || !o->new_pos || !o->new_ncig || !o->new_cig || !o->status)) {
-        snprintf(q.err, q.err_cap, "the strand tallies need new_pos, new_ncig, new_cig and status of a trimming pass");
-        return AMP_EINVAL;
-    }
-    return AMP_OK;
-}
-
-int strand_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
-    const StrandCtx q = ctx_strand(c);
-    StrandState *s = (StrandState *)*q.state;
-    if (!s) return AMP_ESTATE;
-    s->timed = false;
+static int strand_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
+    const HookCtx q = ctx_hook(c);
+    StrandState *s = strand_state(c);
+    s->timer.timed = false;
     const int64_t n = rd->n_reads;
     if (n <= 0) return AMP_OK;
-    const int rc = strand_check_out(c, o);
+    const int rc = hook_check_out(q, o, strand_hook);
     if (rc != AMP_OK) return rc;
     StrandArgs a;
     a.n = n; a.pos = rd->pos; a.flag = rd->flag; a.lseq = rd->lseq; a.cig_off32 = rd->cig_off32; a.cig = rd->cig; a.seq_off8 = rd->seq_off8;
@@ -236,32 +210,20 @@ int strand_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     a.do_trim = q.do_trim ? 1 : 0;
     a.P = StrandParams{q.ref_len, q.min_quality};
     a.rev = s->d_rev; a.qsum = s->d_qsum;
-    // a block takes ST_TILES_PER_BLOCK tiles and more (its window is flushed when it moves, not per tile), up to
-    // ST_BLOCKS_PER_CU blocks per CU; from there on the blocks take more tiles each
-    const int64_t tiles = (n + ST_BLOCK - 1) / ST_BLOCK;
-    const int64_t grid = std::min<int64_t>(std::max<int64_t>((tiles + ST_TILES_PER_BLOCK - 1) / ST_TILES_PER_BLOCK, 1), (int64_t)ST_BLOCKS_PER_CU * q.n_cu);
-    STCHK(q, hipEventRecord(s->ev0, q.stream));
-    k_strand<<<(unsigned)grid, ST_BLOCK, 0, q.stream>>>(a);
-    STCHK(q, hipGetLastError());
-    STCHK(q, hipEventRecord(s->ev1, q.stream));
-    s->timed = true;
+    HOOKCHK(q, s->timer.begin(q.stream));           // (below: a block's window is flushed when it moves, not per tile)
+    k_strand<<<hook_grid(n, ST_BLOCK, ST_TILES_PER_BLOCK, ST_BLOCKS_PER_CU, q.n_cu), ST_BLOCK, 0, q.stream>>>(a);
+    HOOKCHK(q, hipGetLastError());
+    HOOKCHK(q, s->timer.end(q.stream));
     return AMP_OK;
 }
 
-int strand_reset(amp_ctx *c) {
-    const StrandCtx q = ctx_strand(c);
-    StrandState *s = (StrandState *)*q.state;
-    if (!s) return AMP_OK;
-    STCHK(q, hipMemsetAsync(s->d_qsum, 0, strand_bytes(q.ref_len), q.stream));
+static int strand_reset(amp_ctx *c) {
+    const HookCtx q = ctx_hook(c);
+    HOOKCHK(q, hipMemsetAsync(strand_state(c)->d_qsum, 0, strand_bytes(q.ref_len), q.stream));
     return AMP_OK;
 }
 
-void strand_destroy(amp_ctx *c) {
-    const StrandCtx q = ctx_strand(c);
-    strand_free((StrandState *)*q.state);
-    *q.state = nullptr;
-    *q.on = false;
-}
+HookOps strand_hook = {"the strand tallies need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, strand_enqueue, strand_reset, strand_free};
 
 }  // namespace amp
 
@@ -271,72 +233,54 @@ extern "C" {
 
 int amp_strand_enable(amp_ctx *c, int on) {
     if (!c) return AMP_EINVAL;
-    const StrandCtx q = ctx_strand(c);
-    if (!on) { *q.on = false; return AMP_OK; }
-    StrandGuard g(q.device);
-    StrandState *s = (StrandState *)*q.state;
+    const HookCtx q = ctx_hook(c);
+    HookSlot &slot = hook_slot(c, HOOK_STRAND);
+    if (!on) { slot.on = false; return AMP_OK; }
+    Guard g(q.device);
+    StrandState *s = strand_state(c);
     if (!s) {
         s = new (std::nothrow) StrandState();
         if (!s) return AMP_ENOMEM;
-        struct Drop { StrandState *s; ~Drop() { strand_free(s); } } drop{s};      // until the state is handed to the ctx
-        STCHK(q, hipMalloc((void **)&s->d_qsum, std::max<size_t>(strand_bytes(q.ref_len), 64)));
+        HookDrop drop{strand_hook, s};
+        HOOKCHK(q, hipMalloc((void **)&s->d_qsum, std::max<size_t>(strand_bytes(q.ref_len), 64)));
         s->d_rev = (uint32_t *)(s->d_qsum + (size_t)q.ref_len * ST_QSUM_COLS);
-        STCHK(q, hipEventCreate(&s->ev0));
-        STCHK(q, hipEventCreate(&s->ev1));
-        drop.s = nullptr;
-        *q.state = s;
+        HOOKCHK(q, s->timer.create());
+        drop.state = nullptr;
+        slot.state = s;
     }
-    STCHK(q, hipMemsetAsync(s->d_qsum, 0, strand_bytes(q.ref_len), q.stream));
-    *q.on = true;
+    HOOKCHK(q, hipMemsetAsync(s->d_qsum, 0, strand_bytes(q.ref_len), q.stream));
+    slot.on = true;
     return AMP_OK;
 }
 
 int amp_strand_get(amp_ctx *c, uint32_t *rev, uint64_t *qsum) {
     if (!c) return AMP_EINVAL;
-    const StrandCtx q = ctx_strand(c);
-    StrandState *s = (StrandState *)*q.state;
+    const HookCtx q = ctx_hook(c);
+    StrandState *s = strand_state(c);
     if (!s) return AMP_ESTATE;
-    StrandGuard g(q.device);
+    Guard g(q.device);
     const size_t G = (size_t)q.ref_len;
-    if (rev && G) STCHK(q, hipMemcpyAsync(rev, s->d_rev, G * ST_REV_COLS * 4, hipMemcpyDeviceToHost, q.stream));
-    if (qsum && G) STCHK(q, hipMemcpyAsync(qsum, s->d_qsum, G * ST_QSUM_COLS * 8, hipMemcpyDeviceToHost, q.stream));
-    STCHK(q, hipStreamSynchronize(q.stream));
+    if (rev && G) HOOKCHK(q, hipMemcpyAsync(rev, s->d_rev, G * ST_REV_COLS * 4, hipMemcpyDeviceToHost, q.stream));
+    if (qsum && G) HOOKCHK(q, hipMemcpyAsync(qsum, s->d_qsum, G * ST_QSUM_COLS * 8, hipMemcpyDeviceToHost, q.stream));
+    HOOKCHK(q, hipStreamSynchronize(q.stream));
     return AMP_OK;
 }
 
 int amp_strand_add(amp_ctx *c, const uint32_t *rev, const uint64_t *qsum) {
     if (!c) return AMP_EINVAL;
-    const StrandCtx q = ctx_strand(c);
-    StrandState *s = (StrandState *)*q.state;
+    const HookCtx q = ctx_hook(c);
+    StrandState *s = strand_state(c);
     if (!s) return AMP_ESTATE;
-    StrandGuard g(q.device);
+    Guard g(q.device);
     const size_t G = (size_t)q.ref_len;
-    if (!G) return AMP_OK;
-    // the tables to the host, the sums there, and back: a call per job (the merge of partial tables), not per batch
-    std::vector<uint32_t> hr(rev ? G * ST_REV_COLS : 0);
-    std::vector<uint64_t> hq(qsum ? G * ST_QSUM_COLS : 0);
-    if (rev) STCHK(q, hipMemcpyAsync(hr.data(), s->d_rev, hr.size() * 4, hipMemcpyDeviceToHost, q.stream));
-    if (qsum) STCHK(q, hipMemcpyAsync(hq.data(), s->d_qsum, hq.size() * 8, hipMemcpyDeviceToHost, q.stream));
-    STCHK(q, hipStreamSynchronize(q.stream));
-    for (size_t k = 0; k < hr.size(); ++k) hr[k] += rev[k];
-    for (size_t k = 0; k < hq.size(); ++k) hq[k] += qsum[k];
-    if (rev) STCHK(q, hipMemcpyAsync(s->d_rev, hr.data(), hr.size() * 4, hipMemcpyHostToDevice, q.stream));
-    if (qsum) STCHK(q, hipMemcpyAsync(s->d_qsum, hq.data(), hq.size() * 8, hipMemcpyHostToDevice, q.stream));
-    STCHK(q, hipStreamSynchronize(q.stream));
-    return AMP_OK;
+    const int rc = hook_add(q, s->d_rev, rev, G * ST_REV_COLS);
+    return rc != AMP_OK ? rc : hook_add(q, (uint64_t *)s->d_qsum, qsum, G * ST_QSUM_COLS);
 }
 
 int amp_strand_last_ms(amp_ctx *c, float *ms) {
     if (!c) return AMP_EINVAL;
-    const StrandCtx q = ctx_strand(c);
-    StrandState *s = (StrandState *)*q.state;
-    if (!s || !s->timed) return AMP_ESTATE;
-    StrandGuard g(q.device);
-    STCHK(q, hipEventSynchronize(s->ev1));
-    float t = 0;
-    STCHK(q, hipEventElapsedTime(&t, s->ev0, s->ev1));
-    if (ms) *ms = t;
-    return AMP_OK;
+    StrandState *s = strand_state(c);
+    return s ? s->timer.last_ms(ctx_hook(c), ms) : AMP_ESTATE;
 }
 
 }  // extern "C"

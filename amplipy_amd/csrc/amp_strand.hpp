@@ -245,30 +245,4 @@ AMP_ST_HD void strand_walk(const StrandRead &R, const StrandParams &P, const uin
 }
 
 }  // namespace amp
-
-#ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-
-namespace amp {
-
-// What amp_strand.hip needs to know of a ctx (amplihip.hip owns the struct and fills this in).
-struct StrandCtx {
-    int device;
-    int32_t ref_len;
-    hipStream_t stream;
-    int do_trim, min_quality, n_cu;
-    char *err; size_t err_cap;
-    bool *on;                   // the switch the two hooks of amplihip.hip read
-    void **state;               // the tables and the timer, owned by amp_strand.hip
-};
-StrandCtx ctx_strand(amp_ctx *c);
-
-// The hooks of amplihip.hip.  strand_check_out: the result arrays the kernel reads are there (in front of the pass, so that
-// a refused call changes nothing).  strand_enqueue: k_strand behind the read pass on the ctx stream.
-int strand_check_out(amp_ctx *c, const amp_trim_out *dev_out);
-int strand_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *dev_out);
-int strand_reset(amp_ctx *c);       // amp_reset: the tables start over
-void strand_destroy(amp_ctx *c);    // amp_ctx_destroy
-
-}  // namespace amp
-#endif
+// (the hook amplihip.hip runs behind the read pass is strand_hook of amp_strand.hip, declared in amp_hook.hpp)

@@ -26,9 +26,7 @@
 #include "amp_fast7.hpp"
 #include "amp_wave.hpp"
 #include "amp_ins.hpp"
-#include "amp_qc.hpp"
-#include "amp_strand.hpp"
-#include "amp_amplicon.hpp"
+#include "amp_hook.hpp"
 #define AMP_CODEC_CTX_ONLY
 #include "amp_codec.hpp"
 
@@ -100,27 +98,14 @@ struct amp_ctx {
     int kernel_variant = 0;       // 0 = by the batch (4 for reads of up to 152 padded bases on average, else 5), 5 = fast kernel (second generation) + general pass, 4 = its first generation, 1 = one lane per read (reference kernels), 2 = fused tile kernel, 3 = k_trim + k_scan + k_tile<SPLIT>,
                                   // 4 = k_fast (simple reads, one pass over their bytes) + k_tile<LIST> over the others
     uint32_t *dbg_dcnt = nullptr; int dbg_grid = 0;
-    bool qc_on = false;            // the QC report (amp_qc_enable): one more kernel behind the read pass
-    void *qc = nullptr;            // ... and its state, owned by amp_qc.hip
-    bool strand_on = false;        // the strand and base-quality tallies (amp_strand_enable): one more kernel behind the read pass
-    void *strand = nullptr;        // ... and their state, owned by amp_strand.hip
-    bool amplicon_on = false;      // the per-amplicon allele counts (amp_amplicon_enable): one more kernel behind the read pass
-    void *amplicon = nullptr;      // ... and their state, owned by amp_amplicon.hip
+    HookSlot hooks[N_HOOKS] = {};  // the opt-in kernels behind the read pass (amp_hook.hpp): a hook that is on costs one more kernel per batch
     uint32_t phases = 0xFFu;       // always 0xFF in the shipped library; -DAMP_DEV builds can mask phases of the tile kernel (AMPLIHIP_PHASES)
     char err[320] = {0};
 };
 
 static hipError_t grow_events(amp_ctx *c, int64_t ncap);
 
-#define HIPCHK(ctx, call)                                                                          \
-    do {                                                                                           \
-        hipError_t e__ = (call);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            snprintf((ctx)->err, sizeof((ctx)->err), "%s failed: %s (%s:%d)", #call,               \
-                     hipGetErrorString(e__), __FILE__, __LINE__);                                  \
-            return e__ == hipErrorOutOfMemory ? AMP_ENOMEM : AMP_EHIP;                             \
-        }                                                                                          \
-    } while (0)
+#define HIPCHK(ctx, call) AMP_HIPCHK((ctx)->err, sizeof((ctx)->err), #call, call)
 
 static hipError_t grow_events(amp_ctx *c, int64_t ncap) {   // re-lays the shard regions out for a larger capacity
     if (ncap <= c->ev_cap) return hipSuccess;
@@ -139,16 +124,6 @@ static hipError_t grow_events(amp_ctx *c, int64_t ncap) {   // re-lays the shard
     c->ev_cap = ncap;
     return hipSuccess;
 }
-
-struct Guard {  // make the ctx's device current for the duration of a call
-    int prev = -1;
-    bool ok = true;
-    explicit Guard(amp_ctx *c) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != c->device) ok = hipSetDevice(c->device) == hipSuccess;
-    }
-    ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // ---------------------------------------------------------------------------------------
 // kernels shared by both variants
@@ -770,19 +745,25 @@ __global__ void k_event_strings(amp_dev_reads rd, uint64_t read_base, int64_t n_
 namespace amp {
 hipStream_t ctx_stream(const amp_ctx *c) { return c->stream; }
 int ctx_device(const amp_ctx *c) { return c->device; }
-// ... and the QC report (amp_qc.hip)
-QcCtx ctx_qc(amp_ctx *c) {
-    return QcCtx{c->device, c->ref_len, c->stream, c->d_counts, c->do_trim, c->have_primers ? 1 : 0, c->n_cu, c->err, sizeof(c->err), &c->qc_on, &c->qc};
+// ... and the hooks behind the read pass (amp_hook.hpp)
+HookCtx ctx_hook(amp_ctx *c) {
+    return HookCtx{c->device, c->ref_len, c->stream, c->d_counts, c->do_trim, c->have_primers ? 1 : 0, c->min_quality, c->n_cu, c->err, sizeof(c->err)};
 }
-// ... and the strand tallies (amp_strand.hip)
-StrandCtx ctx_strand(amp_ctx *c) {
-    return StrandCtx{c->device, c->ref_len, c->stream, c->do_trim, c->min_quality, c->n_cu, c->err, sizeof(c->err), &c->strand_on, &c->strand};
-}
-// ... and the per-amplicon counts (amp_amplicon.hip)
-AmpliconCtx ctx_amplicon(amp_ctx *c) {
-    return AmpliconCtx{c->device, c->ref_len, c->stream, c->do_trim, c->min_quality, c->n_cu, c->err, sizeof(c->err), &c->amplicon_on, &c->amplicon};
-}
+HookSlot &hook_slot(amp_ctx *c, int which) { return c->hooks[which]; }
 }  // namespace amp
+
+static const HookOps *const HOOKS[N_HOOKS] = {&qc_hook, &strand_hook, &amplicon_hook};      // in the enum's order: the run order
+
+// The kernels of the hooks that are on, behind the read pass on the ctx stream, until one fails.
+static int enqueue_hooks(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *dev_out) {
+    for (int k = 0; k < N_HOOKS; ++k) {
+        if (!c->hooks[k].on) continue;
+        if (!c->hooks[k].state) return AMP_ESTATE;
+        const int rc = HOOKS[k]->enqueue(c, rd, dev_out);
+        if (rc != AMP_OK) return rc;
+    }
+    return AMP_OK;
+}
 
 // ---------------------------------------------------------------------------------------
 // library / context API
@@ -874,7 +855,7 @@ int amp_ctx_create(amp_ctx **out, int device, int32_t ref_len) {
     amp_ctx *c = new (std::nothrow) amp_ctx();
     if (!c) return AMP_ENOMEM;
     c->device = device; c->ref_len = ref_len;
-    Guard g(c);
+    Guard g(c->device);
     if (!g.ok) { delete c; return AMP_ENODEV; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -907,11 +888,12 @@ int amp_ctx_create(amp_ctx **out, int device, int32_t ref_len) {
 
 void amp_ctx_destroy(amp_ctx *c) {
     if (!c) return;
-    Guard g(c);
+    Guard g(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    qc_destroy(c);
-    strand_destroy(c);
-    amplicon_destroy(c);
+    for (int k = 0; k < N_HOOKS; ++k) {
+        HOOKS[k]->free_state(c->hooks[k].state);
+        c->hooks[k] = HookSlot{false, nullptr};
+    }
     if (c->own_counts && c->d_counts) (void)hipFree(c->d_counts);
     if (c->d_min_start) (void)hipFree(c->d_min_start);
     if (c->d_max_end) (void)hipFree(c->d_max_end);
@@ -933,7 +915,7 @@ void amp_ctx_destroy(amp_ctx *c) {
 
 int amp_ctx_set_stream(amp_ctx *c, void *s) {
     if (!c) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = (hipStream_t)s;
@@ -943,7 +925,7 @@ int amp_ctx_set_stream(amp_ctx *c, void *s) {
 
 int amp_ctx_bind_counts(amp_ctx *c, void *dev_counts) {
     if (!c || !dev_counts) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     size_t cb = (size_t)c->ref_len * AMP_DEV_COLS * sizeof(uint32_t);
     HIPCHK(c, hipMemcpyAsync(dev_counts, c->d_counts, cb, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -957,7 +939,7 @@ int amp_ctx_bind_counts(amp_ctx *c, void *dev_counts) {
 
 int amp_set_primers(amp_ctx *c, const int32_t *mn, const int32_t *mx, int32_t max_primer_len) {
     if (!c || !mn || !mx || max_primer_len < 0) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     HIPCHK(c, hipMemcpyAsync(c->d_min_start, mn, (size_t)c->ref_len * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_max_end, mx, (size_t)c->ref_len * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1002,7 +984,7 @@ int amp_set_timing(amp_ctx *c, int split) {
 
 int amp_reserve_events(amp_ctx *c, int64_t cap) {
     if (!c || cap < 0) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     HIPCHK(c, grow_events(c, cap));
     c->ev_reserved = true;
     return AMP_OK;
@@ -1010,7 +992,7 @@ int amp_reserve_events(amp_ctx *c, int64_t cap) {
 
 int amp_sync(amp_ctx *c) {
     if (!c) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return AMP_OK;
 }
@@ -1138,16 +1120,15 @@ int amp_process_batch_device(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
     if (!c || !rd || rd->n_reads < 0) return AMP_EINVAL;
     if (rd->n_reads && (!rd->pos || !rd->flag || !rd->tlen || !rd->lseq || !rd->cig_off32 || !rd->cig || !rd->seq_off8 ||
                         !rd->seq || !rd->qual)) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     c->staged_n = -1;          // (amp_event_strings(reads = NULL) refers to the last HOST batch: there is none now)
-    if (c->qc_on && rd->n_reads) { const int qrc = qc_check_out(c, dev_out); if (qrc != AMP_OK) return qrc; }
-    if (c->strand_on && rd->n_reads) { const int src = strand_check_out(c, dev_out); if (src != AMP_OK) return src; }
-    if (c->amplicon_on && rd->n_reads) { const int arc = amplicon_check_out(c, dev_out); if (arc != AMP_OK) return arc; }
-    int rc = launch_reads(c, rd, read_base, dev_out);
-    if (rc == AMP_OK && c->qc_on) rc = qc_enqueue_reads(c, rd, dev_out);        // k_qc_reads on the ctx stream
-    if (rc == AMP_OK && c->strand_on) rc = strand_enqueue(c, rd, dev_out);      // k_strand on the ctx stream
-    if (rc == AMP_OK && c->amplicon_on) rc = amplicon_enqueue(c, rd, dev_out);  // k_amplicon on the ctx stream
-    return rc;
+    for (int k = 0; k < N_HOOKS && rd->n_reads; ++k) {      // in front of the pass: a refused call changes nothing
+        if (!c->hooks[k].on) continue;
+        const int rc = hook_check_out(ctx_hook(c), dev_out, *HOOKS[k]);
+        if (rc != AMP_OK) return rc;
+    }
+    const int rc = launch_reads(c, rd, read_base, dev_out);
+    return rc != AMP_OK ? rc : enqueue_hooks(c, rd, dev_out);
 }
 
 int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const amp_trim_out *out) {
@@ -1155,7 +1136,7 @@ int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const 
     const int64_t n = r->n_reads;
     if (n == 0) return AMP_OK;
     if (!r->pos || !r->flag || !r->tlen || !r->lseq || !r->cig_off || !r->cig || !r->seq_off || !r->seq || !r->qual) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     const uint64_t n_cig = r->cig_off[n], n_bases = r->seq_off[n];
     if (n_cig > 0xFFFFFFF0ull || (n_bases >> 3) > 0xFFFFFFF0ull || (n_bases & 7)) return AMP_EINVAL;
     std::vector<uint32_t> co((size_t)n + 1), so((size_t)n + 1);
@@ -1185,9 +1166,8 @@ int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const 
                       c->o_flags.as<uint8_t>(), c->o_status.as<uint8_t>()};
     int rc = launch_reads(c, &rd, read_base, &dout);
     if (rc != AMP_OK) return rc;
-    if (c->qc_on) { rc = qc_enqueue_reads(c, &rd, &dout); if (rc != AMP_OK) return rc; }      // k_qc_reads on the ctx stream
-    if (c->strand_on) { rc = strand_enqueue(c, &rd, &dout); if (rc != AMP_OK) return rc; }    // k_strand on the ctx stream
-    if (c->amplicon_on) { rc = amplicon_enqueue(c, &rd, &dout); if (rc != AMP_OK) return rc; }        // k_amplicon on the ctx stream
+    rc = enqueue_hooks(c, &rd, &dout);         // (no check in front of the pass here: dout is always complete)
+    if (rc != AMP_OK) return rc;
     if (out) {
         if (out->new_pos) HIPCHK(c, hipMemcpyAsync(out->new_pos, dout.new_pos, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         if (out->new_ncig) HIPCHK(c, hipMemcpyAsync(out->new_ncig, dout.new_ncig, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -1203,7 +1183,7 @@ int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const 
 int amp_last_kernel_ms(amp_ctx *c, float *total_ms, float *scan_ms) {
     if (!c) return AMP_EINVAL;
     if (!c->timed) return AMP_ESTATE;
-    Guard g(c);
+    Guard g(c->device);
     HIPCHK(c, hipEventSynchronize(c->ev3));
     float t = 0, s = 0;
     HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev3));
@@ -1216,7 +1196,7 @@ int amp_last_kernel_ms(amp_ctx *c, float *total_ms, float *scan_ms) {
 
 int amp_get_counts(amp_ctx *c, uint32_t *counts) {
     if (!c || !counts) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     HIPCHK(c, hipMemcpyAsync(counts, c->d_counts, (size_t)c->ref_len * AMP_NSYM * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return AMP_OK;
@@ -1224,7 +1204,7 @@ int amp_get_counts(amp_ctx *c, uint32_t *counts) {
 
 int amp_add_counts(amp_ctx *c, const uint32_t *counts) {
     if (!c || !counts) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     size_t n = (size_t)c->ref_len * AMP_NSYM;
     c->call_pending = false;       // the table changes: calls begun earlier are for the table as it was
     HIPCHK(c, c->call_buf.ensure(n * 4));
@@ -1239,7 +1219,7 @@ void *amp_counts_device_ptr(amp_ctx *c) { return c ? c->d_counts : nullptr; }
 
 int amp_get_ins_events(amp_ctx *c, int64_t *n, amp_ins_event *buf, int64_t cap) {
     if (!c || !n) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     unsigned long long h[EV_SHARDS];
     HIPCHK(c, hipMemcpyAsync(h, &c->d_ctr[CTR_EV_SHARD0], sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1270,7 +1250,7 @@ int amp_drain_ins_events(amp_ctx *c, int64_t *n, amp_ins_event *buf, int64_t cap
     // event once instead of the whole accumulated list after each batch, and the device list stays one batch long
     const int rc = amp_get_ins_events(c, n, buf, cap);
     if (rc != AMP_OK || !buf) return rc;
-    Guard g(c);
+    Guard g(c->device);
     HIPCHK(c, hipMemsetAsync(&c->d_ctr[CTR_EV_SHARD0], 0, EV_SHARDS * sizeof(unsigned long long), c->stream));
     return AMP_OK;
 }
@@ -1278,7 +1258,7 @@ int amp_drain_ins_events(amp_ctx *c, int64_t *n, amp_ins_event *buf, int64_t cap
 int amp_aggregate_ins_events(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base, int drain, int64_t *n_runs, amp_ins_run *buf, int64_t cap) {
     if (!c || !n_runs) return AMP_EINVAL;
     if (!rd && c->staged_n < 0) return AMP_ESTATE;       // no batch to read the alleles from: the size query says so, too
-    Guard g(c);
+    Guard g(c->device);
     unsigned long long h[EV_SHARDS];
     HIPCHK(c, hipMemcpyAsync(h, &c->d_ctr[CTR_EV_SHARD0], sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1310,7 +1290,7 @@ int amp_aggregate_ins_events(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
 
 int amp_debug_blocks(amp_ctx *c, uint32_t *out, int cap_blocks, int *n_blocks) {   // [block][dur, rebases, p2 chunks, p4 chunks]
     if (!c || !out || !n_blocks || !c->dbg_dcnt) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     int nb = c->dbg_grid < cap_blocks ? c->dbg_grid : cap_blocks;
     HIPCHK(c, hipMemcpyAsync(out, c->dbg_dcnt + c->dbg_grid + 64, (size_t)nb * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1320,7 +1300,7 @@ int amp_debug_blocks(amp_ctx *c, uint32_t *out, int cap_blocks, int *n_blocks) {
 
 int amp_debug_counters(amp_ctx *c, uint64_t *out16) {  // raw device counters (development aid)
     if (!c || !out16) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     HIPCHK(c, hipMemcpyAsync(out16, c->d_ctr, CTR_DEBUG_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->kernel_variant != 1 && c->dbg_dcnt && c->dbg_grid > 0) {      // [3]: deferred reads of the LAST batch, from the per-block list counts
@@ -1337,7 +1317,7 @@ int amp_debug_counters(amp_ctx *c, uint64_t *out16) {  // raw device counters (d
 
 int amp_error_reads(amp_ctx *c, int64_t *n) {  // reads with a non-zero status since the last reset
     if (!c || !n) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     unsigned long long h = 0;
     HIPCHK(c, hipMemcpyAsync(&h, &c->d_ctr[CTR_ERROR_READS], sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1347,17 +1327,19 @@ int amp_error_reads(amp_ctx *c, int64_t *n) {  // reads with a non-zero status s
 
 int amp_reset(amp_ctx *c) {
     if (!c) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     c->call_pending = false;
     // one small kernel for the table and the counters (two hipMemsetAsync calls are three fill kernels of 5 us each)
     const size_t words = (size_t)c->ref_len * AMP_DEV_COLS;
     constexpr size_t ctr_words = 2 * CTR_WORDS;      // the 64-bit counters as the 32-bit words k_reset writes
     k_reset<<<(unsigned)((words + ctr_words + 1023) / 1024), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, ctr_words);
     HIPCHK(c, hipGetLastError());
-    const int qrc = qc_reset(c);   // (the report's tallies, when there is one)
-    if (qrc != AMP_OK) return qrc;
-    const int src = strand_reset(c);                   // (... and the strand tables)
-    return src != AMP_OK ? src : amplicon_reset(c);    // (... and the per-amplicon tables and read counts)
+    for (int k = 0; k < N_HOOKS; ++k) {        // (... and the tables of every hook that has some, on or off)
+        if (!c->hooks[k].state) continue;
+        const int rc = HOOKS[k]->reset(c);
+        if (rc != AMP_OK) return rc;
+    }
+    return AMP_OK;
 }
 
 // RCCL is resolved at run time so the library has no link-time dependency on it and uses
@@ -1367,7 +1349,7 @@ typedef int (*nccl_allreduce_fn)(const void *, void *, size_t, int, int, void *,
 int amp_reduce(amp_ctx *c, void *comm, int root) {
     if (!c) return AMP_EINVAL;
     if (!comm) return AMP_OK;
-    Guard g(c);
+    Guard g(c->device);
     c->call_pending = false;       // the table changes: calls begun earlier are for the un-reduced table
     void *h = dlopen(nullptr, RTLD_NOW);
     void *f_red = h ? dlsym(h, "ncclReduce") : nullptr;
@@ -1392,7 +1374,7 @@ int amp_reduce(amp_ctx *c, void *comm, int root) {
 // ---------------------------------------------------------------------------------------
 int amp_set_reference(amp_ctx *c, const uint8_t *ref_ascii) {
     if (!c || !ref_ascii) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     HIPCHK(c, hipMemcpyAsync(c->d_ref, ref_ascii, (size_t)c->ref_len, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_ref = true;
@@ -1402,7 +1384,7 @@ int amp_set_reference(amp_ctx *c, const uint8_t *ref_ascii) {
 int amp_call_positions(amp_ctx *c, const amp_call_params *pr, amp_pos_call *out, int64_t *n_relevant) {
     if (!c || !pr || !out) return AMP_EINVAL;
     if (pr->run_variants && !c->have_ref) return AMP_ESTATE;
-    Guard g(c);
+    Guard g(c->device);
     const int32_t G = c->ref_len;
     HIPCHK(c, c->call_buf.ensure((size_t)G * sizeof(amp_pos_call)));
     HIPCHK(c, hipMemsetAsync(&c->d_ctr[CTR_CALL_RELEVANT], 0, sizeof(unsigned long long), c->stream));
@@ -1462,7 +1444,7 @@ static int call_compact_enqueue(amp_ctx *c, const amp_call_params *pr, bool pinn
 int amp_call_compact_begin(amp_ctx *c, const amp_call_params *pr) {
     if (!c || !pr) return AMP_EINVAL;
     if (pr->run_variants && !c->have_ref) return AMP_ESTATE;
-    Guard g(c);
+    Guard g(c->device);
     const int rc = call_compact_enqueue(c, pr, true);
     if (rc != AMP_OK) return rc;
     c->call_pending = true; c->call_pending_params = *pr;     // (the view waits for the copy's event, not for what is enqueued behind it)
@@ -1472,7 +1454,7 @@ int amp_call_compact_begin(amp_ctx *c, const amp_call_params *pr) {
 int amp_call_compact_view(amp_ctx *c, const amp_call_params *pr, amp_call_view *view) {
     if (!c || !pr || !view) return AMP_EINVAL;
     if (pr->run_variants && !c->have_ref) return AMP_ESTATE;
-    Guard g(c);
+    Guard g(c->device);
     const int32_t G = c->ref_len;
     const CallImage L(G);
     // work enqueued by amp_call_compact_begin with the same parameters is picked up here; anything else starts now
@@ -1533,7 +1515,7 @@ int amp_coordinate_helpers(amp_ctx *c, int64_t n, const uint32_t *cig_off, const
         return AMP_EINVAL;
     const size_t nc = cig_off[n];
     if (nc && !cig) return AMP_EINVAL;
-    Guard g(c);
+    Guard g(c->device);
     // one scratch image: offsets | ops | starts | ref positions | query positions | the two results | fixed ops | their counts | status
     const size_t words = ((size_t)n + 1) + nc + 3 * (size_t)n + 2 * (size_t)n + nc + (size_t)n + ((size_t)n + 3) / 4 + 16;
     HIPCHK(c, c->call_buf.ensure(words * 4));
@@ -1573,7 +1555,7 @@ int amp_event_strings(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base, i
         if (i >= rd->n_reads || ev[e].q_from < 0 || ev[e].q_to < ev[e].q_from ||
             off[e + 1] - off[e] != (uint64_t)(ev[e].q_to - ev[e].q_from)) return AMP_EINVAL;
     }
-    Guard g(c);
+    Guard g(c->device);
     const size_t tb = (size_t)off[n_ev];
     const size_t need = (size_t)n_ev * sizeof(amp_ins_event) + ((size_t)n_ev + 1) * 8 + tb + 64;
     HIPCHK(c, c->call_buf.ensure(need));

@@ -301,10 +301,14 @@ class Engine:
         self._chk(self.L.amp_qc_depth(self.h, C.c_void_p(abi.ptr(depth)), C.c_void_p(abi.ptr(regions))), "amp_qc_depth")
         return depth, regions[:n_regions]
 
-    def qc_last_ms(self):
+    def _hook_last_ms(self, entry):
+        """Milliseconds of a hook's kernel behind the last batch (``entry``: its amp_*_last_ms); ESTATE when none ran."""
         t = C.c_float(0)
-        self._chk(self.L.amp_qc_last_ms(self.h, C.byref(t)), "amp_qc_last_ms")
+        self._chk(getattr(self.L, entry)(self.h, C.byref(t)), entry)
         return float(t.value)
+
+    def qc_last_ms(self):
+        return self._hook_last_ms("amp_qc_last_ms")
 
     # ---- strand and base-quality tallies ---------------------------------------------
     def strand_enable(self):
@@ -328,9 +332,7 @@ class Engine:
         self._chk(self.L.amp_strand_add(self.h, C.c_void_p(abi.ptr(r)), C.c_void_p(abi.ptr(q))), "amp_strand_add")
 
     def strand_last_ms(self):
-        t = C.c_float(0)
-        self._chk(self.L.amp_strand_last_ms(self.h, C.byref(t)), "amp_strand_last_ms")
-        return float(t.value)
+        return self._hook_last_ms("amp_strand_last_ms")
 
     # ---- per-amplicon allele counts ---------------------------------------------------
     def amplicon_enable(self, lo, hi, amp_start, amp_end):
@@ -365,9 +367,7 @@ class Engine:
         self._chk(self.L.amp_amplicon_add(self.h, C.c_void_p(abi.ptr(c)), C.c_void_p(abi.ptr(r))), "amp_amplicon_add")
 
     def amplicon_last_ms(self):
-        t = C.c_float(0)
-        self._chk(self.L.amp_amplicon_last_ms(self.h, C.byref(t)), "amp_amplicon_last_ms")
-        return float(t.value)
+        return self._hook_last_ms("amp_amplicon_last_ms")
 
     # ---- calling ---------------------------------------------------------------------
     def set_reference(self, ref_seq):
