@@ -1,8 +1,8 @@
 // amp_hook.hpp -- the host shell of the opt-in kernels that run behind every batch's read pass: the QC
 // report (amp_qc.hip), the strand tallies (amp_strand.hip), the per-amplicon counts (amp_amplicon.hip).  What a hook needs to
 // know of a ctx, and what the hooks have in common -- the check macro, the device guard, the timer round a launch, the grid
-// rule, the merge of host tables, the check of a trimming pass's results -- each once.  amplihip.hip owns amp_ctx, keeps one
-// slot (switch, state) per hook and walks the table of HookOps; a unit keeps its state, its kernels and what it enables.
+// rule, the merge of host tables, the check of a trimming pass's results -- each once.  amp_ctx (amp_ctx.hpp) keeps one
+// slot (switch, state) per hook and amplihip.hip walks the table of HookOps; a unit keeps its state, its kernels and what it enables.
 #pragma once
 
 #ifdef __HIPCC__
@@ -39,7 +39,7 @@ struct Guard {      // the device is current for the duration of a call
     ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-// What a hook needs to know of a ctx (amplihip.hip owns the struct and fills this in).
+// What a hook needs to know of a ctx (the struct is amp_ctx.hpp's; amplihip.hip fills this in).
 struct HookCtx {
     int device;
     int32_t ref_len;

@@ -1,6 +1,6 @@
 // amp_plan.hpp -- the host's plan for one batch of reads: which kernels it takes, how large their grids are and where
 // each of them finds its piece of the scratch buffer.  Plain C++ (no HIP): the kernel headers include it for the
-// geometry constants and grid functions they share with the host, launch_reads (amplihip.hip) turns a ReadPlan into
+// geometry constants and grid functions they share with the host, launch_reads (amp_readpass.hip) turns a ReadPlan into
 // pointers and launches, and tests/test_read_plan.py checks it on a machine without a GPU.
 #pragma once
 

@@ -23,11 +23,11 @@
 //                         different banks.
 //     Chunk lanes find their owner through a byte map in LDS that the read lanes fill
 //     (chunk -> read for P2, chunk -> segment for P4); the map aliases the spare CIGAR buffer.
-//   * everything else is DEFERRED through the block's own segment of a list to the second pass in
-//     amplihip.hip: "light" entries (deletions and insertion events of reads whose match bases were
-//     counted here) to k_deferred_light, "heavy" entries to k_deferred_heavy, which runs the exact code
-//     of amp_read.hpp -- reads with more CIGAR ops than the LDS columns hold, reads of 64 k bases or
-//     more, reads whose trimmed CIGAR is not regular (clips only at the ends, body of M/=/X/I/D/N),
+//   * deletions and insertion events of regular reads (clips only at the ends, body of M/=/X/I/D/N) are
+//     done here too, by a lane-per-read walk over the final CIGAR; everything else is DEFERRED through
+//     the block's own segment of a list to the second pass, k_deferred_heavy (amp_heavy.hpp), which runs
+//     the exact code of amp_read.hpp: only "heavy" entries are left -- reads with more CIGAR ops than
+//     the LDS columns hold, reads of 64 k bases or more, reads whose trimmed CIGAR is not regular,
 //     reads whose segments do not fit the tile's segment table, and (status only) reads on which a
 //     chunk lane met an error.
 #pragma once
