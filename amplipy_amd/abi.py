@@ -74,6 +74,10 @@ STRAND_CELLS = 11          # NSYM + STRAND_QSUM_COLS: the columns of one positio
 # ---- per-amplicon allele counts (amp_amplicon_*): counts uint32[sum of spans][NSYM], reads uint64[n_amp + 1] ----
 AMPLICON_MAX_CELLS = 1 << 22   # span positions of all amplicons together; more is refused with AMP_EINVAL
 
+# ---- codon tallies (amp_codon_*): codon uint32[n_slots][CODON_CELLS], reads uint64[2] ----
+CODON_CELLS = 65               # the 64 triplets (16 b0 + 4 b1 + b2, A C G T as 0 1 2 3), then broken
+CODON_MAX_SLOTS = 1 << 20      # more is refused with AMP_EINVAL
+
 # ---- QC report (amp_qc_*) ----
 QC_MAX_DEPTHS = 4
 

@@ -16,7 +16,7 @@ from os.path import isfile
 
 import numpy as np
 
-from . import AMPLIPY_VERSION, amplicon as amplicon_mod, calling, lib, parallel, qc, strand as strand_mod
+from . import AMPLIPY_VERSION, amplicon as amplicon_mod, calling, codon as codon_mod, lib, parallel, qc, strand as strand_mod
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -80,9 +80,9 @@ def open_device_bam_text(input_fn, output_fn):
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
-    def __init__(self, fn, ref_id, strand=False, amplicon=False):
+    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False):
         """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables);
-        amplicon: likewise the seven keys of --amplicons, behind them."""
+        amplicon: likewise the seven keys of --amplicons, behind them; codon: likewise the five keys of --codons, last."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -109,16 +109,18 @@ class VcfWriter:
             w(strand_mod.HEADER_LINES)
         if amplicon:
             w(amplicon_mod.HEADER_LINES)
+        if codon:
+            w(codon_mod.HEADER_LINES)
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
-    def line(self, r, strand=None, amplicon=None):
-        return calling.vcf_line(self.ref_id, r, strand, amplicon)
+    def line(self, r, strand=None, amplicon=None, codon=None):
+        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon)
 
-    def write(self, r, strand=None, amplicon=None):
-        self.f.write(self.line(r, strand, amplicon))
+    def write(self, r, strand=None, amplicon=None, codon=None):
+        self.f.write(self.line(r, strand, amplicon, codon))
 
-    def write_all(self, records, strand=None, amplicon=None):
-        self.f.write("".join([self.line(r, strand, amplicon) for r in records]))
+    def write_all(self, records, strand=None, amplicon=None, codon=None):
+        self.f.write("".join([self.line(r, strand, amplicon, codon) for r in records]))
 
     def close(self):
         if self.f is not sys.stdout:
@@ -130,7 +132,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 min_freq_consensus=None, min_freq_variants=None, min_depth_consensus=None, min_depth_variants=None,
                 unknown_symbol=None, include_no_primer=None, run_trim=False, run_variants=False, run_consensus=False,
                 device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None, qc_fn=None, qc_regions_fn=None, qc_depths=None,
-                qc_depth_fn=None, strand=False, strand_fn=None, amplicons_fn=None, amplicon_out_fn=None):
+                qc_depth_fn=None, strand=False, strand_fn=None, amplicons_fn=None, amplicon_out_fn=None, codons_fn=None,
+                codon_out_fn=None, aa_out_fn=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -156,6 +159,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     table per amplicon behind every batch's read pass, and every VCF record also carries AMP, AMP_DP, AMP_REF_DP, AMP_ALT_DP,
     AMP_NA_DP, AMP_P and PRIMER.  amplicon_out_fn: the per-amplicon table as a TSV file.  With amplicons_fn None the engine's
     hook is never switched on.
+    codons_fn (default: off; runs with a count table): the CDS file -- name, start, end and, optionally, strand per line, 0-based
+    and half-open.  The device tallies, behind every batch's read pass, which bases stand together on one
+    read in the three positions of every codon, and every VCF record also carries CDS, CODON_DP, ALT_AA, ALT_CODON and
+    ALT_CODON_DP.  codon_out_fn: the codon table as a TSV file; aa_out_fn (runs that call variants): the amino-acid changes at or
+    above the variant thresholds.  With codons_fn None the engine's hook is never switched on.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -199,6 +207,12 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("Per-amplicon counts (--amplicons, --amplicon_out) work on aio only: reads are assigned to amplicons by their original "
               "coordinates against the primer BED, which only a run that trims has, and are counted for a VCF, which only a run that "
               "calls variants writes")
+    if (codon_out_fn is not None or aa_out_fn is not None) and codons_fn is None:
+        error("The codon table and the amino-acid calls (--codon_out, --aa_out) need the CDS file (--codons)")
+    if codons_fn is not None and not (run_variants or run_consensus):
+        error("A run that only trims has no count table: no codon tallies (--codons, --codon_out, --aa_out)")
+    if aa_out_fn is not None and not run_variants:
+        error("The amino-acid calls (--aa_out) use the variant thresholds: variants or aio")
     strand_on = bool(strand) or strand_fn is not None
     qc_on = qc_fn is not None or qc_depth_fn is not None
     if qc_on:
@@ -241,7 +255,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    driver = vcf = rank_error = strand_file = amps = amp_file = None
+    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = None
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
@@ -257,7 +271,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(route.note)
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
-            vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None)
+            vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None, codon=codons_fn is not None)
             if amplicon_out_fn is not None:
                 amp_file = qc.open_new(amplicon_out_fn)
         if strand_fn is not None and rank == 0:
@@ -265,6 +279,12 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if amplicons_fn is not None:
             print_log("Loading amplicons: %s" % amplicons_fn)
             amps = amplicon_mod.load_amplicons(amplicons_fn, qc.load_primer_rows(primer_fn), primer_pos_offset or 0, G)
+        if codons_fn is not None:
+            print_log("Loading CDS rows: %s" % codons_fn)
+            cds = codon_mod.load_cds(codons_fn, G)
+            if rank == 0:
+                codon_file = qc.open_new(codon_out_fn) if codon_out_fn is not None else None
+                aa_file = qc.open_new(aa_out_fn) if aa_out_fn is not None else None
         if qc_on:
             qc_regions = [(0, G, qc.WHOLE)] + (qc.load_regions(qc_regions_fn) if qc_regions_fn is not None else [])
             qc_primers = qc.load_primer_rows(primer_fn) if run_trim else []
@@ -286,6 +306,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.strand_enable()
     if amps is not None and rank_error is None:
         amplicon_mod.enable(eng, amps)
+    if cds is not None and rank_error is None:
+        codon_mod.enable(eng, cds)
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -317,6 +339,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             qc_parts = parallel.gather_objects(dist, rank, world, eng.qc_read_tallies())
         if amps is not None:             # ... and every rank's reads per amplicon
             amp_read_parts = parallel.gather_objects(dist, rank, world, eng.amplicon_tables()[1])
+        if cds is not None:              # ... and every rank's tallied and skipped reads
+            codon_read_parts = parallel.gather_objects(dist, rank, world, eng.codon_tables()[1])
         if final_trimmed_fn is not None and driver.part_writer is not None:
             # the ranks' files (all closed by now: the writer threads were joined in run()) become the one trimmed BAM
             parts = parallel.gather_objects(dist, rank, world, (driver.part_writer.path, driver.part_writer.header_bytes))
@@ -338,6 +362,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                                      min_depth_variants if min_depth_variants is not None else 0,
                                      min_freq_variants if min_freq_variants is not None else 0,
                                      run_consensus, run_variants)
+            v_min_depth = min_depth_variants if min_depth_variants is not None else 0
+            v_min_freq = min_freq_variants if min_freq_variants is not None else 0
             eng.set_reference(ref_seq)
             if dist is not None:
                 eng.sync()
@@ -366,6 +392,18 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                         a_reads = np.sum([np.asarray(part, np.uint64) for part in amp_read_parts], axis=0, dtype=np.uint64)
                 if rank == 0:
                     amp_tables = amplicon_mod.Tables(amps, eng.counts(), a_counts, a_reads)
+            codon_tables = None
+            if cds is not None:
+                c_codon, c_reads = eng.codon_tables()
+                if dist is not None:                       # one more all-reduce: the codon table
+                    import torch
+                    wire = torch.from_numpy(c_codon.astype(np.int64).reshape(-1)).to("cuda:%d" % device)
+                    parallel.allreduce_table(dist, wire)
+                    c_codon = wire.cpu().numpy().astype(np.uint32).reshape(-1, codon_mod.CELLS)
+                    if rank == 0:
+                        c_reads = np.sum([np.asarray(part, np.uint64) for part in codon_read_parts], axis=0, dtype=np.uint64)
+                if rank == 0:
+                    codon_tables = codon_mod.Tables(cds, ref_seq, c_codon, c_reads, v_min_depth, v_min_freq)
 
             def ins_tallies(positions):
                 triples = loop.ins_store.counted_pairs(positions)
@@ -376,7 +414,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if rank != 0:
                 run_variants = run_consensus = False       # rank 0 writes the outputs
             if run_variants:
-                vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables))        # (= vcf.write(r) for r in res.records)
+                vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables, codon_tables))        # (= vcf.write(r) for r in res.records)
                 vcf.close()
             if run_consensus:
                 f = gzip.open(consensus_fn, "wt") if consensus_fn.lower().endswith(".gz") else open(consensus_fn, "w")
@@ -388,6 +426,12 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if amp_file is not None:
             amplicon_mod.write_tsv(amp_file, ref_id, amp_tables)
             print_log("Output per-amplicon counts: %s" % amplicon_out_fn)
+        if codon_file is not None:
+            codon_mod.write_codon_tsv(codon_file, ref_id, codon_tables)
+            print_log("Output codon table: %s" % codon_out_fn)
+        if aa_file is not None:
+            codon_mod.write_aa_tsv(aa_file, ref_id, codon_tables)
+            print_log("Output amino-acid calls: %s" % aa_out_fn)
         if qc_on and rank == 0:
             if qc_fn is not None:
                 report = qc.build_report(
@@ -404,9 +448,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 qc.write_depth(qc_files[1], ref_id, qc_depth)
         if amps is not None and rank == 0:
             print_log(amp_tables.summary_line())
+        if cds is not None and rank == 0:
+            print_log(codon_tables.summary_line())
         failed = False
     finally:
-        for f in qc_files + [strand_file, amp_file]:
+        for f in qc_files + [strand_file, amp_file, codon_file, aa_file]:
             if f is not None:
                 f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)
@@ -484,6 +530,9 @@ def parse_args(argv=None):
         p.add_argument("--strand", action="store_true", help="VCF records also carry REF_RV, ALT_RV, REF_QUAL, ALT_QUAL and SB: reverse-strand depth, mean base quality and strand bias per allele (variants, aio)")
         p.add_argument("--amplicons", required=False, type=str, default=None, help="Amplicon file (TSV: left primer, right primer[, amplicon name]): per-amplicon allele counts on the device, and AMP, AMP_DP, AMP_REF_DP, AMP_ALT_DP, AMP_NA_DP, AMP_P and PRIMER on every VCF record (aio)")
         p.add_argument("--amplicon_out", required=False, type=str, default=None, help="Count of every symbol per amplicon and position of its span (TSV or TSV.gz; aio, needs --amplicons)")
+        p.add_argument("--codons", required=False, type=str, default=None, help="CDS file (TSV: name, start, end[, strand]; 0-based, half-open): codon tallies within single reads on the device, and CDS, CODON_DP, ALT_AA, ALT_CODON and ALT_CODON_DP on every VCF record (variants, consensus, aio)")
+        p.add_argument("--codon_out", required=False, type=str, default=None, help="Count of every codon seen on single reads, per CDS row and codon (TSV or TSV.gz; needs --codons)")
+        p.add_argument("--aa_out", required=False, type=str, default=None, help="Amino-acid changes at or above the variant thresholds, per CDS row and codon (TSV or TSV.gz; variants, aio; needs --codons)")
         p.add_argument("--strand_out", required=False, type=str, default=None, help="Count, reverse-strand count and quality sum of every position and symbol (TSV or TSV.gz; variants, consensus, aio)")
     return parser.parse_args(argv)
 
@@ -494,7 +543,8 @@ def main(argv=None):
         error("--qc_regions and --qc_depths need --qc")
     qc_args = dict(qc_fn=args.qc, qc_regions_fn=args.qc_regions, qc_depth_fn=args.qc_depth_out,
                    qc_depths=qc.parse_depths(args.qc_depths) if args.qc_depths is not None else None)
-    qc_args.update(strand=args.strand, strand_fn=args.strand_out, amplicons_fn=args.amplicons, amplicon_out_fn=args.amplicon_out)
+    qc_args.update(strand=args.strand, strand_fn=args.strand_out, amplicons_fn=args.amplicons, amplicon_out_fn=args.amplicon_out,
+                   codons_fn=args.codons, codon_out_fn=args.codon_out, aa_out_fn=args.aa_out)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,

@@ -40,6 +40,7 @@ EXPORTS = [
     "amp_qc_find_primer_owners", "amp_qc_enable", "amp_qc_read_tallies", "amp_qc_depth", "amp_qc_last_ms",
     "amp_strand_enable", "amp_strand_get", "amp_strand_add", "amp_strand_last_ms",
     "amp_amplicon_enable", "amp_amplicon_get", "amp_amplicon_add", "amp_amplicon_last_ms",
+    "amp_codon_enable", "amp_codon_get", "amp_codon_add", "amp_codon_last_ms",
 ]
 
 
@@ -368,6 +369,36 @@ class Engine:
 
     def amplicon_last_ms(self):
         return self._hook_last_ms("amp_amplicon_last_ms")
+
+    # ---- codon tallies ----------------------------------------------------------------
+    def codon_enable(self, starts):
+        """amp_codon_enable: the hook on for the codon slots at ``starts`` (int32, strictly increasing), the tables zero
+        (DESIGN.md section 18).  ``codon_disable`` turns it off."""
+        st = np.ascontiguousarray(starts, np.int32)
+        if st.size == 0:
+            raise ValueError("at least one codon slot")
+        self._chk(self.L.amp_codon_enable(self.h, C.c_int32(st.size), C.c_void_p(abi.ptr(st))), "amp_codon_enable")
+        self._codon_slots = int(st.size)
+
+    def codon_disable(self):
+        self._chk(self.L.amp_codon_enable(self.h, C.c_int32(0), None), "amp_codon_enable")
+
+    def codon_tables(self):
+        """amp_codon_get -> (codon uint32[n_slots][65], reads uint64[2]: tallied, skipped) as they stand."""
+        n = getattr(self, "_codon_slots", 0)
+        codon = np.zeros((max(n, 1), abi.CODON_CELLS), np.uint32); reads = np.zeros(2, np.uint64)
+        self._chk(self.L.amp_codon_get(self.h, C.c_void_p(abi.ptr(codon)), C.c_void_p(abi.ptr(reads))), "amp_codon_get")
+        return codon[:n], reads
+
+    def codon_add(self, codon, reads):
+        """amp_codon_add: host tables added element-wise (the merge of partial tables)."""
+        n = getattr(self, "_codon_slots", 0)
+        c = np.ascontiguousarray(codon, np.uint32); r = np.ascontiguousarray(reads, np.uint64)
+        assert c.size == n * abi.CODON_CELLS and r.size == 2
+        self._chk(self.L.amp_codon_add(self.h, C.c_void_p(abi.ptr(c)), C.c_void_p(abi.ptr(r))), "amp_codon_add")
+
+    def codon_last_ms(self):
+        return self._hook_last_ms("amp_codon_last_ms")
 
     # ---- calling ---------------------------------------------------------------------
     def set_reference(self, ref_seq):

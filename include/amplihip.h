@@ -736,6 +736,31 @@ int amp_amplicon_add(amp_ctx *ctx, const uint32_t *counts, const uint64_t *reads
 /* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_amplicon_last_ms(amp_ctx *ctx, float *ms);
 
+/* ---- codon tallies within single reads (opt-in) --------------------------------------------------------------
+ * Which bases stand together on ONE read in the three positions of a codon.  The slots are codon start positions,
+ * starts[n_slots], strictly increasing, 0 <= s and s + 3 <= ref_len; names, strands and translation stay with the caller.  Only
+ * reads with status 0 take part, as they were counted (the trimmed alignment with do_trim).  A read with a regular CIGAR -- hard
+ * clips, soft clips, a core of M = X I D N ops, soft clips, hard clips, its query bases adding up to l_seq, QUAL present, all of it
+ * inside the reference -- adds for the slot at start p:
+ *   codon[slot][16 b0 + 4 b1 + b2] += 1   when [p, p + 3) lies inside one match segment (a run of M = X ops with no inserted,
+ *                                         deleted or skipped base inside) and the three bases are among A C G T (0 1 2 3,
+ *                                         reference-forward) with quality >= min_quality;
+ *   codon[slot][64] += 1                  when [p, p + 3) lies inside [pos, ref_end) but inside no match segment: a deletion or
+ *                                         skip overlaps it or an insertion sits between two of its positions (no quality test).
+ * A codon the read covers only in part adds nothing.  reads[0] += 1 per such read; every other read with status 0 adds nothing to
+ * the table and reads[1] += 1.  (codon: uint32[n_slots][65], reads: uint64[2].) */
+/* The hook on for the slots given (the array is copied; more than 2^20 slots, an array that is not strictly increasing or a codon
+ * that reaches past the reference: AMP_EINVAL), the tables zero; they are laid out again only when the set changed.  n_slots == 0
+ * or a NULL array: off; the tables stay readable.  With the hook on and do_trim set, amp_process_batch_device refuses a dev_out
+ * without new_pos, new_ncig, new_cig or status (AMP_EINVAL) before anything runs. */
+int amp_codon_enable(amp_ctx *ctx, int32_t n_slots, const int32_t *starts);
+/* Host copies of the tables as they stand (waits for the stream); either pointer may be NULL.  AMP_ESTATE before the first enable. */
+int amp_codon_get(amp_ctx *ctx, uint32_t *codon /* [n_slots][65] */, uint64_t *reads /* [2] */);
+/* Host tables added element-wise, like amp_add_counts (the merge of partial tables); either pointer may be NULL. */
+int amp_codon_add(amp_ctx *ctx, const uint32_t *codon, const uint64_t *reads);
+/* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+int amp_codon_last_ms(amp_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
