@@ -1,36 +1,34 @@
 // amp_amplicon.hip -- per-amplicon allele counts on the device (C ABI: the amp_amplicon_* entry points
 // of amplihip.h).
 //
-// k_amplicon runs behind the read pass of every batch while the hook is on and touches every counted base once more, like
-// k_strand, whose shape it starts from: a block takes a contiguous run of tiles of 256 neighbouring reads.  Phase A, one lane
-// per read: the read's amplicon from its ORIGINAL coordinates (amplicon_assign, amp_amplicon.hpp), the reads per amplicon (a
-// ballot and run heads per wave: a pile costs one add per wave and amplicon), and the counted alignment as a few segments.
+// k_amplicon runs behind the read pass of every batch while the hook is on and touches every counted base once more, in the
+// shape of amp_tally.hpp; what follows is its own part.  Phase A: the read's amplicon from its ORIGINAL coordinates
+// (amplicon_assign, amp_amplicon.hpp), the reads per amplicon (a ballot and run heads per wave: a pile costs one add per wave
+// and amplicon), and the counted alignment as a few segments.
 // The block keeps AM_SLOTS windows of AM_W positions x 6 columns in LDS (row stride 7), each bound to (amplicon, anchor); the
 // distinct amplicons of a tile are found wave by wave (a loop over the wave's distinct values), and one lane settles all of
 // the tile's requests against the slots (amplicon_resolve).  Slots persist across the block's tiles; a slot goes to the table
 // -- its non-zero cells, one atomic each -- when it is given to another amplicon, when its anchor moves, and at block end.
 // Phase B, position-major: per slot in use, each wave owns every fourth 64-position chunk of the window and each lane one
-// position of it; the wave takes the segment list 64 entries at a time, ballots which of them lie in its slot and overlap its
-// chunk, and lane p adds into its OWN cell with a plain LDS add.  Reads the window did not take -- more segments than list
-// slots, an irregular CIGAR, an amplicon without a slot in this tile, a read outside its slot's window -- walk serially, one
-// lane per read (amplicon_walk), with LDS atomics where slot and position are resident and global atomics otherwise: slow and
-// correct.  No step relies on the reads being sorted.
+// position of it; the wave visits the segments that lie in its slot and overlap its chunk.  Reads the window did not take --
+// more segments than list slots, an irregular CIGAR, an amplicon without a slot in this tile, a read outside its slot's
+// window -- walk serially (amplicon_walk), with LDS atomics where slot and position are resident and global atomics
+// otherwise: slow and correct.  No step relies on the reads being sorted.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 #include <stdio.h>
-#include <string.h>
 
 #include <algorithm>
-#include <new>
 #include <vector>
 
 #include "amp_hook.hpp"
 #include "amp_amplicon.hpp"
+#include "amp_tally.hpp"
 
 namespace amp {
 
-struct AmpliconState {
+struct AmpliconState : HookState {
     int32_t n_amp = 0;
     int64_t cells = 0;                         // positions of all spans together
     int32_t *d_lo = nullptr, *d_hi = nullptr;  // one allocation: lo, hi, cell_off
@@ -38,25 +36,16 @@ struct AmpliconState {
     int32_t *d_start = nullptr, *d_end = nullptr;      // one allocation: amp_start, amp_end
     uint32_t *d_counts = nullptr;              // [cells][6]
     unsigned long long *d_reads = nullptr;     // [n_amp + 1]
-    HookTimer timer;
 };
 
 struct AmpliconArgs {
-    int64_t n;
-    const int32_t *pos;
-    const uint32_t *lseq, *cig_off32, *cig, *seq_off8;
-    const uint8_t *seq, *qual;
-    const int32_t *new_pos;                    // the trimmed alignment (do_trim)
-    const uint32_t *new_ncig, *new_cig;
-    const uint8_t *status;                     // may be null without do_trim
-    int32_t do_trim;
-    StrandParams P;
+    TallyReads in;
     AmpliconTables T;
     uint32_t *counts;
     unsigned long long *reads;
 };
 
-// the non-zero cells of the slots in `mask` to the table, one atomic each; those slots are all zero afterwards
+// the slots in `mask` to the table
 __device__ __forceinline__ void amplicon_flush(uint32_t *s_cell, const AmSlots &S, uint32_t mask, const AmpliconArgs &a) {
     for (int k = 0; k < AM_SLOTS; ++k) {
         if (!((mask >> k) & 1u)) continue;
@@ -64,16 +53,12 @@ __device__ __forceinline__ void amplicon_flush(uint32_t *s_cell, const AmSlots &
         if (amp < 0 || amp >= a.T.n_amp) continue;                 // (a free slot holds nothing)
         const int32_t lo = a.T.lo[amp], hi = a.T.hi[amp];
         const size_t row0 = (size_t)a.T.cell_off[amp];
-        uint32_t *const cell = s_cell + k * AM_SLOT_WORDS;
-        for (int i = (int)threadIdx.x; i < AM_SLOT_WORDS; i += AM_BLOCK) {
-            const uint32_t v = cell[i];
-            if (!v) continue;
-            cell[i] = 0u;
+        tally_flush<AM_BLOCK>(s_cell + k * AM_SLOT_WORDS, AM_SLOT_WORDS, [&](int i, uint32_t v) {
             const int64_t r = (int64_t)anchor + i / AM_STRIDE;
             const int c = i % AM_STRIDE;
-            if (c >= AM_COLS || r < lo || r >= hi) continue;       // (nothing is ever added there)
+            if (c >= AM_COLS || r < lo || r >= hi) return;         // (nothing is ever added there)
             atomicAdd(&a.counts[(row0 + (size_t)(r - lo)) * AM_COLS + c], v);
-        }
+        });
     }
 }
 
@@ -85,41 +70,32 @@ k_amplicon(AmpliconArgs a) {
     __shared__ int s_nreq[AM_BLOCK / 64];
     __shared__ AmSlots s_slots;
     __shared__ uint32_t s_nseg;
+    const TallyReads &in = a.in;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int k = tid; k < AM_SLOTS * AM_SLOT_WORDS; k += AM_BLOCK) s_cell[k] = 0u;
     if (tid == 0) { s_nseg = 0u; amplicon_slots_init(s_slots); }
-    // the block's contiguous run of tiles (the bounds are the same for every lane: the barriers below see whole blocks)
-    const int64_t tiles = (a.n + AM_BLOCK - 1) / AM_BLOCK;
-    const int64_t t0 = tiles * (int64_t)blockIdx.x / (int64_t)gridDim.x, t1 = tiles * ((int64_t)blockIdx.x + 1) / (int64_t)gridDim.x;
+    int64_t t0, t1;
+    tally_tile_range(in.n, AM_BLOCK, t0, t1);
     int since = 0;                             // tiles since every slot was last flushed
     __syncthreads();
     for (int64_t t = t0; t < t1; ++t) {
         // ---- phase A: one lane per read
         const int64_t i = t * AM_BLOCK + tid;
         StrandRead R;
-        R.pos = 0; R.cig = a.cig; R.n_ops = 0u; R.lseq = 0; R.rev = 0u; R.base = 0ull;
-        StrandShape sh;
-        sh.regular = false; sh.n_seg = 0; sh.ref_end = 0;
-        bool live = false;
-        uint32_t qual0 = 0xFFu;
+        uint32_t qual0;
+        tally_no_read(in, R, qual0);
+        StrandShape sh = {false, 0, 0};
+        const bool live = tally_live(in, i);
         int32_t amp = -1, lo_a = 0, hi_a = 0;
         size_t row0 = 0;
-        if (i < a.n && (a.status ? a.status[i] == 0 : true)) {
-            live = true;
-            const uint32_t c0 = a.cig_off32[i];
-            const int32_t p = a.pos[i];
-            amp = amplicon_assign(p, (int64_t)p + am_cigar_ref_len(a.cig + c0, a.cig_off32[i + 1] - c0), a.T);
+        if (live) {
+            const uint32_t c0 = in.cig_off32[i];
+            const int32_t p = in.pos[i];
+            amp = amplicon_assign(p, (int64_t)p + am_cigar_ref_len(in.cig + c0, in.cig_off32[i + 1] - c0), a.T);
             if (amp >= 0) {
                 lo_a = a.T.lo[amp]; hi_a = a.T.hi[amp]; row0 = (size_t)a.T.cell_off[amp];
-                if (a.do_trim) {
-                    R.pos = a.new_pos[i]; R.cig = a.new_cig + (size_t)c0 + 3 * (size_t)i; R.n_ops = a.new_ncig[i];
-                } else {
-                    R.pos = p; R.cig = a.cig + c0; R.n_ops = a.cig_off32[i + 1] - c0;
-                }
-                R.lseq = (int32_t)a.lseq[i];
-                R.base = (uint64_t)a.seq_off8[i] * 8ull;
-                if (R.lseq > 0) qual0 = a.qual[R.base];
-                sh = amplicon_segments(R, a.P, qual0, 0, [](const AmSeg &) {});
+                tally_counted_read(in, i, R, qual0);
+                sh = amplicon_segments(R, in.P, qual0, 0, [](const AmSeg &) {});
             }
         }
         // reads per amplicon: neighbouring lanes with the same amplicon are one run, and its first lane adds the run's length
@@ -142,12 +118,8 @@ k_amplicon(AmpliconArgs a) {
                 const int src = __ffsll((long long)pending) - 1;
                 const int32_t v = __shfl(amp, src);
                 const bool mine = want && amp == v;
-                int32_t l = mine ? R.pos : 0x7FFFFFFF, h = mine ? sh.ref_end : -0x7FFFFFFF - 1;
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    l = min(l, __shfl_xor(l, d));
-                    h = max(h, __shfl_xor(h, d));
-                }
+                int32_t l = mine ? R.pos : SPAN_NO_LO, h = mine ? sh.ref_end : SPAN_NO_HI;
+                wave_span(l, h);
                 if (lane == src && nreq < AM_REQ_PER_WAVE) s_req[wave * AM_REQ_PER_WAVE + nreq] = AmReq{v, l, h, lo_a};
                 ++nreq;
                 pending &= ~__ballot(mine);
@@ -177,18 +149,15 @@ k_amplicon(AmpliconArgs a) {
         const bool nothing = live && amp >= 0 && sh.regular && sh.n_seg == 0;      // a regular read whose segments are all empty adds nothing
         if (win) {
             uint32_t at = atomicAdd(&s_nseg, (uint32_t)sh.n_seg);  // (at most AM_SEG_SLOTS per read: the list cannot overflow)
-            amplicon_segments(R, a.P, qual0, slot, [&](const AmSeg &s) { s_seg[at++] = s; });
+            amplicon_segments(R, in.P, qual0, slot, [&](const AmSeg &s) { s_seg[at++] = s; });
         }
         __syncthreads();
         // ---- phase B: position-major over the tile's segments; in slot k, lane `lane` of the wave owns window position
-        // c * 64 + lane of chunk c.  The wave takes the list 64 segments at a time, a segment per lane, ballots which of them
-        // lie in slot k and overlap the chunk, and visits only those (their fields broadcast by shuffle).
+        // c * 64 + lane of chunk c; the wave visits the segments that lie in slot k and overlap the chunk.
         const uint32_t ns = s_nseg;
         for (uint32_t s0 = 0; s0 < ns; s0 += 64u) {                // (ns and used are block-uniform: whole waves at the ballots)
-            const bool have = s0 + (uint32_t)lane < ns;
-            AmSeg mine;
-            mine.r0 = 0; mine.len_kind = 0u; mine.q0 = 0ull;
-            if (have) mine = s_seg[s0 + (uint32_t)lane];
+            bool have;
+            const AmSeg mine = seg_take(s_seg, s0, ns, lane, have);
             const int my_slot = am_seg_slot(mine);
             for (int k = 0; k < AM_SLOTS; ++k) {
                 if (!((used >> k) & 1u)) continue;
@@ -201,10 +170,7 @@ k_amplicon(AmpliconArgs a) {
                     while (hits) {
                         const int src = __ffsll((long long)hits) - 1;
                         hits &= hits - 1ull;
-                        AmSeg g;
-                        g.r0 = __shfl(mine.r0, src);
-                        g.len_kind = __shfl(mine.len_kind, src);
-                        g.q0 = __shfl((unsigned long long)mine.q0, src);
+                        const AmSeg g = seg_from(mine, src);
                         const int32_t a0 = g.r0 - anchor, a1 = a0 + am_seg_len(g);
                         if (p < a0 || p >= a1) {
                             // (not this lane's position; every lane is back for the next segment's shuffles)
@@ -212,7 +178,7 @@ k_amplicon(AmpliconArgs a) {
                             s_cell[am_cell(k, p, 5u)] += 1u;
                         } else {
                             uint32_t col, qv;
-                            if (strand_base(a.seq, a.qual, g.q0 + (uint64_t)(p - a0), a.P.min_quality, col, qv)) s_cell[am_cell(k, p, col)] += 1u;
+                            if (strand_base(in.seq, in.qual, g.q0 + (uint64_t)(p - a0), in.P.min_quality, col, qv)) s_cell[am_cell(k, p, col)] += 1u;
                         }
                     }
                 }
@@ -224,7 +190,7 @@ k_amplicon(AmpliconArgs a) {
         if (live && amp >= 0 && !win && !nothing) {
             const int k = amplicon_slot_of(s_slots, amp);
             const int32_t anchor = k >= 0 ? s_slots.anchor[k] : 0;
-            amplicon_walk(R, a.P, a.seq, a.qual, lo_a, hi_a, [&](int32_t r, uint32_t col) {
+            amplicon_walk(R, in.P, in.seq, in.qual, lo_a, hi_a, [&](int32_t r, uint32_t col) {
                 const int64_t w = (int64_t)r - (int64_t)anchor;
                 if (k >= 0 && w >= 0 && w < AM_W) atomicAdd(&s_cell[am_cell(k, (int32_t)w, col)], 1u);
                 else atomicAdd(&a.counts[(row0 + (size_t)(r - lo_a)) * AM_COLS + col], 1u);
@@ -238,10 +204,10 @@ k_amplicon(AmpliconArgs a) {
 static size_t count_bytes(const AmpliconState *s) { return (size_t)s->cells * AM_COLS * 4; }
 static size_t read_bytes(const AmpliconState *s) { return ((size_t)s->n_amp + 1) * 8; }
 
-static AmpliconState *amplicon_state(amp_ctx *c) { return (AmpliconState *)hook_slot(c, HOOK_AMPLICON).state; }
+static AmpliconState *amplicon_state(amp_ctx *c) { return hook_state<AmpliconState>(c, HOOK_AMPLICON); }
 
 static void amplicon_free(void *state) {
-    AmpliconState *s = (AmpliconState *)state;
+    AmpliconState *s = hook_state_of<AmpliconState>(state);
     if (!s) return;
     if (s->d_lo) (void)hipFree(s->d_lo);
     if (s->d_start) (void)hipFree(s->d_start);
@@ -254,26 +220,11 @@ static void amplicon_free(void *state) {
 static int amplicon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
     AmpliconState *s = amplicon_state(c);
-    s->timer.timed = false;
-    const int64_t n = rd->n_reads;
-    if (n <= 0) return AMP_OK;
-    const int rc = hook_check_out(q, o, amplicon_hook);
-    if (rc != AMP_OK) return rc;
-    AmpliconArgs a;
-    a.n = n; a.pos = rd->pos; a.lseq = rd->lseq; a.cig_off32 = rd->cig_off32; a.cig = rd->cig; a.seq_off8 = rd->seq_off8;
-    a.seq = rd->seq; a.qual = rd->qual;
-    a.new_pos = o ? o->new_pos : nullptr; a.new_ncig = o ? o->new_ncig : nullptr; a.new_cig = o ? o->new_cig : nullptr;
-    a.status = o ? o->status : nullptr;
-    a.do_trim = q.do_trim ? 1 : 0;
-    a.P = StrandParams{q.ref_len, q.min_quality};
-    a.T = AmpliconTables{q.ref_len, s->n_amp, s->d_lo, s->d_hi, s->d_off, s->d_start, s->d_end};
-    a.counts = s->d_counts; a.reads = s->d_reads;
     // (a block's slots go to the table when they move, not per tile)
-    HOOKCHK(q, s->timer.begin(q.stream));
-    k_amplicon<<<hook_grid(n, AM_BLOCK, AM_TILES_PER_BLOCK, AM_BLOCKS_PER_CU, q.n_cu), AM_BLOCK, 0, q.stream>>>(a);
-    HOOKCHK(q, hipGetLastError());
-    HOOKCHK(q, s->timer.end(q.stream));
-    return AMP_OK;
+    return hook_launch(q, s, amplicon_hook, rd->n_reads, o, AM_BLOCK, AM_TILES_PER_BLOCK, AM_BLOCKS_PER_CU, [&](unsigned grid) {
+        const AmpliconTables T = {q.ref_len, s->n_amp, s->d_lo, s->d_hi, s->d_off, s->d_start, s->d_end};
+        k_amplicon<<<grid, AM_BLOCK, 0, q.stream>>>(AmpliconArgs{tally_reads(q, rd, o), T, s->d_counts, s->d_reads});
+    });
 }
 
 static int amplicon_reset(amp_ctx *c) {
@@ -328,19 +279,17 @@ int amp_amplicon_enable(amp_ctx *c, int32_t n_amp, const int32_t *lo, const int3
         s = nullptr; slot.state = nullptr; slot.on = false;
     }
     if (!s) {
-        s = new (std::nothrow) AmpliconState();
-        if (!s) return AMP_ENOMEM;
-        HookDrop drop{amplicon_hook, s};
-        s->n_amp = n_amp; s->cells = cells;
-        HOOKCHK(q, hipMalloc((void **)&s->d_lo, A * 12));
-        s->d_hi = s->d_lo + A; s->d_off = (uint32_t *)(s->d_hi + A);
-        HOOKCHK(q, hipMalloc((void **)&s->d_start, std::max<size_t>(G * 8, 8)));
-        s->d_end = s->d_start + G;
-        HOOKCHK(q, hipMalloc((void **)&s->d_counts, count_bytes(s)));
-        HOOKCHK(q, hipMalloc((void **)&s->d_reads, read_bytes(s)));
-        HOOKCHK(q, s->timer.create());
-        drop.state = nullptr;
-        slot.state = s;
+        const int rc = hook_new_state(q, slot, amplicon_hook, s, [&](AmpliconState &f) -> int {
+            f.n_amp = n_amp; f.cells = cells;
+            HOOKCHK(q, hipMalloc((void **)&f.d_lo, A * 12));
+            f.d_hi = f.d_lo + A; f.d_off = (uint32_t *)(f.d_hi + A);
+            HOOKCHK(q, hipMalloc((void **)&f.d_start, std::max<size_t>(G * 8, 8)));
+            f.d_end = f.d_start + G;
+            HOOKCHK(q, hipMalloc((void **)&f.d_counts, count_bytes(&f)));
+            HOOKCHK(q, hipMalloc((void **)&f.d_reads, read_bytes(&f)));
+            return AMP_OK;
+        });
+        if (rc != AMP_OK) return rc;
     }
     slot.on = false;
     HOOKCHK(q, hipMemcpyAsync(s->d_lo, lo, A * 4, hipMemcpyHostToDevice, q.stream));
@@ -379,10 +328,6 @@ int amp_amplicon_add(amp_ctx *c, const uint32_t *counts, const uint64_t *reads) 
     return rc != AMP_OK ? rc : hook_add(q, (uint64_t *)s->d_reads, reads, (size_t)s->n_amp + 1);
 }
 
-int amp_amplicon_last_ms(amp_ctx *c, float *ms) {
-    if (!c) return AMP_EINVAL;
-    AmpliconState *s = amplicon_state(c);
-    return s ? s->timer.last_ms(ctx_hook(c), ms) : AMP_ESTATE;
-}
+int amp_amplicon_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_AMPLICON, ms); }
 
 }  // extern "C"

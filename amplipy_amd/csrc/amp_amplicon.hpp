@@ -71,60 +71,19 @@ AMP_AM_HD int32_t amplicon_assign(int32_t p, int64_t e, const AmpliconTables &T)
     return -1;
 }
 
-// A segment of a regular read.  len_kind = length << 4 | slot << 1 | deletion; q0: the index in qual / seq of the segment's
-// first base (match segments).
-struct AmSeg {
-    int32_t r0;
-    uint32_t len_kind;
-    uint64_t q0;
-};
+// A segment of a regular read: a StrandSeg with len_kind = length << 4 | slot << 1 | deletion.
+using AmSeg = StrandSeg;
 AMP_AM_HD int32_t am_seg_len(const AmSeg &s) { return (int32_t)(s.len_kind >> 4); }
 AMP_AM_HD int am_seg_slot(const AmSeg &s) { return (int)((s.len_kind >> 1) & 7u); }
 AMP_AM_HD bool am_seg_del(const AmSeg &s) { return (s.len_kind & 1u) != 0u; }
 
-// The segments of a read, in CIGAR order, to put(seg) -- strand_segments with every deletion handed out and the slot in
-// place of the strand.  The shape says whether they may be used.  Segments of length 0 are not handed out.
+// The segments of a read, in CIGAR order, to put(seg): every segment of the scan (regular_scan, amp_strand.hpp), deletions on
+// either strand, with the slot in place of the strand.
 template <class Put>
 AMP_AM_HD StrandShape amplicon_segments(const StrandRead &R, const StrandParams &P, uint32_t qual0, int slot, Put put) {
-    StrandShape sh;
-    sh.regular = false; sh.n_seg = 0; sh.ref_end = R.pos;
-    int phase = 0;                       // 0 leading H, 1 leading S, 2 core, 3 trailing S, 4 trailing H
-    int64_t q = 0, r = R.pos;
-    bool ok = R.lseq > 0 && qual0 != 0xFFu && R.pos >= 0;
-    for (uint32_t k = 0; ok && k < R.n_ops; ++k) {
-        const uint32_t v = R.cig[k], op = v & 15u;
-        const int64_t len = (int64_t)(v >> 4);
-        if (op == ST_OP_H) {
-            if (phase == 1) ok = false;
-            else if (phase >= 2) phase = 4;
-        } else if (op == ST_OP_S) {
-            if (phase <= 1) phase = 1;
-            else if (phase <= 3) phase = 3;
-            else ok = false;
-            q += len;
-        } else if (st_is_match(op) || op == ST_OP_I || st_is_del(op)) {
-            if (phase > 2) { ok = false; break; }
-            phase = 2;
-            if (op == ST_OP_I) { q += len; continue; }
-            const bool del = st_is_del(op);
-            if (r + len > (int64_t)P.ref_len || (!del && q + len > (int64_t)R.lseq)) { ok = false; break; }
-            if (len > 0) {
-                AmSeg s;
-                s.r0 = (int32_t)r;
-                s.len_kind = ((uint32_t)len << 4) | ((uint32_t)slot << 1) | (del ? 1u : 0u);
-                s.q0 = R.base + (uint64_t)q;
-                put(s);
-                ++sh.n_seg;
-            }
-            if (!del) q += len;
-            r += len;
-        } else {
-            ok = false;                  // P, and op codes the format does not have
-        }
-    }
-    sh.regular = ok && phase >= 2 && q == (int64_t)R.lseq;
-    sh.ref_end = (int32_t)r;
-    return sh;
+    return regular_scan(R, P, qual0, [&](int32_t r0, uint64_t q0, uint32_t len, bool del) {
+        put(AmSeg{r0, (len << 4) | ((uint32_t)slot << 1) | (del ? 1u : 0u), q0});
+    });
 }
 
 // The bounded pair-by-pair walk: sink(ref_pos, col) for every increment of the read inside [lo, hi).  A position outside

@@ -1,66 +1,50 @@
 // amp_codon.hip -- codon tallies within single reads on the device (C ABI: the amp_codon_* entry points
 // of amplihip.h).
 //
-// k_codon runs behind the read pass of every batch while the hook is on, last of the hooks.  It has k_strand's shape
-// (amp_strand.hip) with lanes owning codon slots instead of positions.  A block takes 256 neighbouring reads.  Phase A, one
-// lane per read: the read's CIGAR becomes a few list entries in LDS (codon_segments, amp_codon.hpp) -- match segments as the
-// codon starts they hold, and the intervals of codon starts the read breaks.  Phase B, slot-major: the block keeps a window of
-// CD_W consecutive slots x 65 u32 cells in LDS; a wave owns a 64-slot chunk of it and each lane one slot; the wave takes the
-// list 64 entries at a time, ballots the entries that overlap its chunk's range of starts, and the lane of slot s tests whether
-// its codon start lies in the entry: for a match segment it loads three quality bytes and three nibbles and adds to its
-// triplet's cell, for a break interval it adds to cell 64 -- a plain LDS add into the lane's OWN cells.  The window stays while
-// the block's next tile fits it; when it moves, and when the block ends, the non-zero cells go to the global table, one atomic
-// each.  Reads the list does not cover -- more entries than CD_SLOTS, a read outside the window -- go serially, one lane per
-// read (codon_read), with LDS atomics inside the window and global atomics outside.  No step relies on the reads being sorted.
+// k_codon runs behind the read pass of every batch while the hook is on, last of the hooks, in the shape of amp_tally.hpp
+// with lanes owning codon slots instead of positions; what follows is its own part.  Phase A: the read's CIGAR becomes a
+// few list entries in LDS (codon_segments, amp_codon.hpp) -- match segments as the codon starts they hold, and the intervals
+// of codon starts the read breaks.  Phase B, slot-major: the block keeps a window of CD_W consecutive slots x 65 u32 cells in
+// LDS; a wave owns a 64-slot chunk of it and each lane one slot; the wave visits the entries that overlap its chunk's range of
+// starts, and the lane of slot s tests whether its codon start lies in the entry: for a match segment it loads three quality
+// bytes and three nibbles and adds to its triplet's cell, for a break interval it adds to cell 64.  The window stays while the
+// block's next tile fits it.  Reads the list does not cover -- more entries than CD_SLOTS, a read outside the window -- go
+// serially (codon_read), with LDS atomics inside the window and global atomics outside.  No step relies on the reads being
+// sorted.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
-#include <algorithm>
-#include <new>
 #include <vector>
 
 #include "amp_hook.hpp"
 #include "amp_codon.hpp"
+#include "amp_tally.hpp"
 
 namespace amp {
 
-struct CodonState {
+struct CodonState : HookState {
     int32_t n_slots = 0;
     std::vector<int32_t> starts;               // the host's copy: the set is laid out again only when it changed
     int32_t *d_starts = nullptr;               // [n_slots]
     uint32_t *d_codon = nullptr;               // [n_slots][65]
     unsigned long long *d_reads = nullptr;     // [2]: tallied, skipped
-    HookTimer timer;
 };
 
 struct CodonArgs {
-    int64_t n;
-    const int32_t *pos;
-    const uint32_t *lseq, *cig_off32, *cig, *seq_off8;
-    const uint8_t *seq, *qual;
-    const int32_t *new_pos;                    // the trimmed alignment (do_trim)
-    const uint32_t *new_ncig, *new_cig;
-    const uint8_t *status;                     // may be null without do_trim
-    int32_t do_trim;
-    StrandParams P;
+    TallyReads in;
     int32_t n_slots;
     const int32_t *starts;
     uint32_t *codon;
     unsigned long long *reads;
 };
 
-// the non-zero cells of the window to the global table, one atomic each; the window is all zero afterwards.  (Only slots below
-// n_slots are ever added to: a0 + k / 65 is inside the table for every non-zero cell.)
+// the window to the global table.  (Only slots below n_slots are ever added to: a0 + k / 65 is inside the table for every
+// non-zero cell.)
 __device__ __forceinline__ void codon_flush(uint32_t *s_cell, int32_t a0, const CodonArgs &a) {
-    for (int k = (int)threadIdx.x; k < CD_W * CD_CELLS; k += CD_BLOCK) {
-        const uint32_t v = s_cell[k];
-        if (!v) continue;
-        s_cell[k] = 0u;
-        atomicAdd(&a.codon[(size_t)a0 * CD_CELLS + (size_t)k], v);
-    }
+    tally_flush<CD_BLOCK>(s_cell, CD_W * CD_CELLS, [&](int k, uint32_t v) { atomicAdd(&a.codon[(size_t)a0 * CD_CELLS + (size_t)k], v); });
 }
 
 __global__ void __launch_bounds__(CD_BLOCK)
@@ -69,12 +53,12 @@ k_codon(CodonArgs a) {
     __shared__ StrandSeg s_seg[CD_BLOCK * CD_SLOTS];
     __shared__ int32_t s_lo[CD_BLOCK / 64], s_hi[CD_BLOCK / 64];
     __shared__ uint32_t s_nseg;
+    const TallyReads &in = a.in;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int k = tid; k < CD_W * CD_CELLS; k += CD_BLOCK) s_cell[k] = 0u;
     if (tid == 0) s_nseg = 0u;
-    // the block's contiguous run of tiles (the bounds are the same for every lane: the barriers below see whole blocks)
-    const int64_t tiles = (a.n + CD_BLOCK - 1) / CD_BLOCK;
-    const int64_t t0 = tiles * (int64_t)blockIdx.x / (int64_t)gridDim.x, t1 = tiles * ((int64_t)blockIdx.x + 1) / (int64_t)gridDim.x;
+    int64_t t0, t1;
+    tally_tile_range(in.n, CD_BLOCK, t0, t1);
     CodonWindow win_at = codon_window_none();
     int since = 0;                             // tiles since the last flush
     uint32_t n_tallied = 0u, n_skipped = 0u;   // this lane's reads
@@ -83,35 +67,17 @@ k_codon(CodonArgs a) {
         // ---- phase A: one lane per read
         const int64_t i = t * CD_BLOCK + tid;
         StrandRead R;
-        R.pos = 0; R.cig = a.cig; R.n_ops = 0u; R.lseq = 0; R.rev = 0u; R.base = 0ull;
-        CodonShape sh;
-        sh.regular = false; sh.n_seg = 0; sh.ref_end = 0;
-        bool live = false;
-        uint32_t qual0 = 0xFFu;
-        if (i < a.n && (a.status ? a.status[i] == 0 : true)) {
-            live = true;
-            const uint32_t c0 = a.cig_off32[i];
-            if (a.do_trim) {
-                R.pos = a.new_pos[i]; R.cig = a.new_cig + (size_t)c0 + 3 * (size_t)i; R.n_ops = a.new_ncig[i];
-            } else {
-                R.pos = a.pos[i]; R.cig = a.cig + c0; R.n_ops = a.cig_off32[i + 1] - c0;
-            }
-            R.lseq = (int32_t)a.lseq[i];
-            R.base = (uint64_t)a.seq_off8[i] * 8ull;
-            if (R.lseq > 0) qual0 = a.qual[R.base];
-            sh = codon_segments(R, a.P, qual0, [](const StrandSeg &) {});
+        uint32_t qual0;
+        tally_no_read(in, R, qual0);
+        CodonShape sh = {false, 0, 0};
+        const bool live = tally_live(in, i);
+        if (live) {
+            tally_counted_read(in, i, R, qual0);
+            sh = codon_segments(R, in.P, qual0, [](const StrandSeg &) {});
             if (sh.regular) ++n_tallied; else ++n_skipped;
         }
-        int32_t lo = sh.regular ? R.pos : 0x7FFFFFFF, hi = sh.regular ? sh.ref_end : -0x7FFFFFFF - 1;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            lo = min(lo, __shfl_xor(lo, d));
-            hi = max(hi, __shfl_xor(hi, d));
-        }
-        if (lane == 0) { s_lo[wave] = lo; s_hi[wave] = hi; }
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < CD_BLOCK / 64; ++w) { lo = min(lo, s_lo[w]); hi = max(hi, s_hi[w]); }
+        int32_t lo = sh.regular ? R.pos : SPAN_NO_LO, hi = sh.regular ? sh.ref_end : SPAN_NO_HI;
+        block_span<CD_BLOCK>(lo, hi, s_lo, s_hi);
         if (!codon_window_keeps(win_at, lo, hi) || since >= CD_MAX_TILES_PER_FLUSH) {         // (the same for every lane)
             codon_flush(s_cell, win_at.a0, a);
             if (lo <= hi) win_at = codon_window_at(a.starts, a.n_slots, lo);                  // (every lane searches: the same loads)
@@ -122,7 +88,7 @@ k_codon(CodonArgs a) {
         const bool win = live && codon_read_windowed(sh, R.pos, win_at);
         if (win && sh.n_seg > 0) {
             uint32_t slot = atomicAdd(&s_nseg, (uint32_t)sh.n_seg);        // (at most CD_SLOTS per read: the list cannot overflow)
-            codon_segments(R, a.P, qual0, [&](const StrandSeg &s) { s_seg[slot++] = s; });
+            codon_segments(R, in.P, qual0, [&](const StrandSeg &s) { s_seg[slot++] = s; });
         }
         __syncthreads();
         // ---- phase B: slot-major over the tile's list; lane `lane` of the wave owns slot a0 + c * 64 + lane of chunk c
@@ -137,10 +103,8 @@ k_codon(CodonArgs a) {
             const int32_t c_hi = a.starts[min((int64_t)a.n_slots - 1, first + CD_CHUNK - 1)];      // the chunk's starts lie in [c_lo, c_hi]
             uint32_t *my = s_cell + (size_t)(c * CD_CHUNK + lane) * CD_CELLS;
             for (uint32_t s0 = 0; s0 < ns; s0 += 64u) {                    // (ns is block-uniform: whole waves at the ballots)
-                const bool have = s0 + (uint32_t)lane < ns;
-                StrandSeg mine;
-                mine.r0 = 0; mine.len_kind = 0u; mine.q0 = 0ull;
-                if (have) mine = s_seg[s0 + (uint32_t)lane];
+                bool have;
+                const StrandSeg mine = seg_take(s_seg, s0, ns, lane, have);
                 unsigned long long hits = __ballot(have && (int64_t)mine.r0 <= (int64_t)c_hi && (int64_t)mine.r0 + st_seg_len(mine) > (int64_t)c_lo);
                 // CD_UNROLL entries at a time: first the loads of all of them (a hit costs one trip to memory, and the trips
                 // of one group overlap), then the adds
@@ -152,23 +116,20 @@ k_codon(CodonArgs a) {
                         if (!hits) continue;                                   // (wave-uniform)
                         const int src = __ffsll((long long)hits) - 1;
                         hits &= hits - 1ull;
-                        StrandSeg g;
-                        g.r0 = __shfl(mine.r0, src);
-                        g.len_kind = __shfl(mine.len_kind, src);
-                        g.q0 = __shfl((unsigned long long)mine.q0, src);
+                        const StrandSeg g = seg_from(mine, src);
                         if (owns && p >= g.r0 && (int64_t)p < (int64_t)g.r0 + st_seg_len(g)) {
                             if (cd_seg_break(g)) {
                                 what[u] = 1u;
                             } else {
                                 const uint64_t k = g.q0 + (uint64_t)(p - g.r0);
-                                what[u] = 2u; quals[u] = codon_load_quals(a.qual, k); codes[u] = codon_load_codes(a.seq, k);
+                                what[u] = 2u; quals[u] = codon_load_quals(in.qual, k); codes[u] = codon_load_codes(in.seq, k);
                             }
                         }
                     }
 #pragma unroll
                     for (int u = 0; u < CD_UNROLL; ++u) {
                         uint32_t cell = (uint32_t)CD_BROKEN;
-                        if (what[u] == 1u || (what[u] == 2u && codon_cell_of(quals[u], codes[u], a.P.min_quality, cell))) my[cell] += 1u;
+                        if (what[u] == 1u || (what[u] == 2u && codon_cell_of(quals[u], codes[u], in.P.min_quality, cell))) my[cell] += 1u;
                     }
                 }
             }
@@ -178,7 +139,7 @@ k_codon(CodonArgs a) {
         // ---- the serial path: reads the window did not take
         if (live && !win && sh.regular) {
             const int32_t a0 = win_at.a0;
-            codon_read(R, a.P, a.seq, a.qual, qual0, a.starts, a.n_slots, [&](int32_t s, uint32_t cell) {
+            codon_read(R, in.P, in.seq, in.qual, qual0, a.starts, a.n_slots, [&](int32_t s, uint32_t cell) {
                 const int64_t w = (int64_t)s - (int64_t)a0;
                 if (w >= 0 && w < CD_W) atomicAdd(&s_cell[(size_t)w * CD_CELLS + cell], 1u);
                 else atomicAdd(&a.codon[(size_t)s * CD_CELLS + cell], 1u);
@@ -201,10 +162,10 @@ k_codon(CodonArgs a) {
 
 static size_t codon_bytes(const CodonState *s) { return (size_t)s->n_slots * CD_CELLS * 4; }
 
-static CodonState *codon_state(amp_ctx *c) { return (CodonState *)hook_slot(c, HOOK_CODON).state; }
+static CodonState *codon_state(amp_ctx *c) { return hook_state<CodonState>(c, HOOK_CODON); }
 
 static void codon_free(void *state) {
-    CodonState *s = (CodonState *)state;
+    CodonState *s = hook_state_of<CodonState>(state);
     if (!s) return;
     if (s->d_starts) (void)hipFree(s->d_starts);
     if (s->d_codon) (void)hipFree(s->d_codon);
@@ -216,25 +177,10 @@ static void codon_free(void *state) {
 static int codon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
     CodonState *s = codon_state(c);
-    s->timer.timed = false;
-    const int64_t n = rd->n_reads;
-    if (n <= 0) return AMP_OK;
-    const int rc = hook_check_out(q, o, codon_hook);
-    if (rc != AMP_OK) return rc;
-    CodonArgs a;
-    a.n = n; a.pos = rd->pos; a.lseq = rd->lseq; a.cig_off32 = rd->cig_off32; a.cig = rd->cig; a.seq_off8 = rd->seq_off8;
-    a.seq = rd->seq; a.qual = rd->qual;
-    a.new_pos = o ? o->new_pos : nullptr; a.new_ncig = o ? o->new_ncig : nullptr; a.new_cig = o ? o->new_cig : nullptr;
-    a.status = o ? o->status : nullptr;
-    a.do_trim = q.do_trim ? 1 : 0;
-    a.P = StrandParams{q.ref_len, q.min_quality};
-    a.n_slots = s->n_slots; a.starts = s->d_starts;
-    a.codon = s->d_codon; a.reads = s->d_reads;
-    HOOKCHK(q, s->timer.begin(q.stream));           // (below: a block's window is flushed when it moves, not per tile)
-    k_codon<<<hook_grid(n, CD_BLOCK, CD_TILES_PER_BLOCK, CD_BLOCKS_PER_CU, q.n_cu), CD_BLOCK, 0, q.stream>>>(a);
-    HOOKCHK(q, hipGetLastError());
-    HOOKCHK(q, s->timer.end(q.stream));
-    return AMP_OK;
+    // (a block's window is flushed when it moves, not per tile)
+    return hook_launch(q, s, codon_hook, rd->n_reads, o, CD_BLOCK, CD_TILES_PER_BLOCK, CD_BLOCKS_PER_CU, [&](unsigned grid) {
+        k_codon<<<grid, CD_BLOCK, 0, q.stream>>>(CodonArgs{tally_reads(q, rd, o), s->n_slots, s->d_starts, s->d_codon, s->d_reads});
+    });
 }
 
 static int codon_reset(amp_ctx *c) {
@@ -278,19 +224,17 @@ int amp_codon_enable(amp_ctx *c, int32_t n_slots, const int32_t *starts) {
         s = nullptr; slot.state = nullptr; slot.on = false;
     }
     if (!s) {
-        s = new (std::nothrow) CodonState();
-        if (!s) return AMP_ENOMEM;
-        HookDrop drop{codon_hook, s};
-        s->n_slots = n_slots;
-        s->starts.assign(starts, starts + N);
-        HOOKCHK(q, hipMalloc((void **)&s->d_starts, N * 4));
-        HOOKCHK(q, hipMalloc((void **)&s->d_codon, codon_bytes(s)));
-        HOOKCHK(q, hipMalloc((void **)&s->d_reads, 16));
-        HOOKCHK(q, s->timer.create());
-        HOOKCHK(q, hipMemcpyAsync(s->d_starts, s->starts.data(), N * 4, hipMemcpyHostToDevice, q.stream));
-        HOOKCHK(q, hipStreamSynchronize(q.stream));
-        drop.state = nullptr;
-        slot.state = s;
+        const int rc = hook_new_state(q, slot, codon_hook, s, [&](CodonState &f) -> int {
+            f.n_slots = n_slots;
+            f.starts.assign(starts, starts + N);
+            HOOKCHK(q, hipMalloc((void **)&f.d_starts, N * 4));
+            HOOKCHK(q, hipMalloc((void **)&f.d_codon, codon_bytes(&f)));
+            HOOKCHK(q, hipMalloc((void **)&f.d_reads, 16));
+            HOOKCHK(q, hipMemcpyAsync(f.d_starts, f.starts.data(), N * 4, hipMemcpyHostToDevice, q.stream));
+            HOOKCHK(q, hipStreamSynchronize(q.stream));
+            return AMP_OK;
+        });
+        if (rc != AMP_OK) return rc;
     }
     slot.on = false;
     const int rc = codon_reset(c);
@@ -321,10 +265,6 @@ int amp_codon_add(amp_ctx *c, const uint32_t *codon, const uint64_t *reads) {
     return rc != AMP_OK ? rc : hook_add(q, (uint64_t *)s->d_reads, reads, 2);
 }
 
-int amp_codon_last_ms(amp_ctx *c, float *ms) {
-    if (!c) return AMP_EINVAL;
-    CodonState *s = codon_state(c);
-    return s ? s->timer.last_ms(ctx_hook(c), ms) : AMP_ESTATE;
-}
+int amp_codon_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_CODON, ms); }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // amp_codon.hpp -- codon tallies within single reads.  The slots are the codon start positions of the
-// CDS rows, starts[n_slots], strictly increasing; the table is codon[n_slots][65].  A REGULAR read (strand_segments,
+// CDS rows, starts[n_slots], strictly increasing; the table is codon[n_slots][65].  A REGULAR read (regular_scan,
 // amp_strand.hpp) adds, for the slot at start p:
 //   a triplet: [p, p + 3) lies inside one match segment -- a maximal run of M = X ops with no inserted, deleted or skipped
 //     base inside it -- and all three bases are among A C G T with quality >= min_quality: cell 16 b0 + 4 b1 + b2 += 1;
@@ -33,7 +33,7 @@ static_assert((uint64_t)CD_MAX_TILES_PER_FLUSH * CD_BLOCK < (1ull << 32), "a win
 static_assert(CD_W * 3 >= 512, "a window of at least 512 positions on a single-frame CDS");
 
 struct CodonShape {
-    bool regular;          // strand_segments' word on the read
+    bool regular;          // regular_scan's word on the read
     int32_t n_seg;         // list entries codon_segments hands out
     int32_t ref_end;
 };
@@ -79,8 +79,6 @@ AMP_ST_HD bool codon_cell(const uint8_t *seq, const uint8_t *qual, uint64_t k, i
 // them) are one match segment.  The entries of a read that turns out not to be regular are to be thrown away.
 template <class Put>
 AMP_ST_HD CodonShape codon_segments(const StrandRead &R, const StrandParams &P, uint32_t qual0, Put put) {
-    StrandRead A = R;
-    A.rev = 1u;                          // (strand_segments leaves a forward read's deletions out)
     int32_t n = 0;
     bool have_m = false, have_b = false;
     int64_t m_r0 = 0, m_r1 = 0, b0 = 0, b1 = 0;      // the match segment [m_r0, m_r1) and the break starts [b0, b1] being built
@@ -101,19 +99,19 @@ AMP_ST_HD CodonShape codon_segments(const StrandRead &R, const StrandParams &P, 
         if (have_b) emit(b0, b1 - b0 + 1, true, 0ull);
         have_b = true; b0 = s0; b1 = s1;
     };
-    const StrandShape sh = strand_segments(A, P, qual0, [&](const StrandSeg &s) {
-        const int64_t r0 = s.r0, len = st_seg_len(s);
-        if (st_seg_del(s)) {
+    const StrandShape sh = regular_scan(R, P, qual0, [&](int32_t seg_r0, uint64_t q0, uint32_t seg_len, bool del) {
+        const int64_t r0 = seg_r0, len = seg_len;
+        if (del) {
             if (have_m) { emit(m_r0, m_r1 - m_r0 - 2, false, m_q0); have_m = false; }
             add_break(r0 - 2, r0 + len - 1);
-        } else if (have_m && s.q0 == m_q0 + (uint64_t)(m_r1 - m_r0)) {
+        } else if (have_m && q0 == m_q0 + (uint64_t)(m_r1 - m_r0)) {
             m_r1 += len;                 // the same run goes on (r0 == m_r1: nothing but match ops since)
         } else {
             if (have_m) {                // an insertion between two match segments
                 emit(m_r0, m_r1 - m_r0 - 2, false, m_q0);
                 add_break(r0 - 2, r0 - 1);
             }
-            have_m = true; m_r0 = r0; m_r1 = r0 + len; m_q0 = s.q0;
+            have_m = true; m_r0 = r0; m_r1 = r0 + len; m_q0 = q0;
         }
     });
     if (have_m) emit(m_r0, m_r1 - m_r0 - 2, false, m_q0);

@@ -1,9 +1,10 @@
 // amp_hook.hpp -- the host shell of the opt-in kernels that run behind every batch's read pass: the QC
 // report (amp_qc.hip), the strand tallies (amp_strand.hip), the per-amplicon counts (amp_amplicon.hip), the codon tallies
-// (amp_codon.hip).  What a hook needs to
-// know of a ctx, and what the hooks have in common -- the check macro, the device guard, the timer round a launch, the grid
-// rule, the merge of host tables, the check of a trimming pass's results -- each once.  amp_ctx (amp_ctx.hpp) keeps one
-// slot (switch, state) per hook and amplihip.hip walks the table of HookOps; a unit keeps its state, its kernels and what it enables.
+// (amp_codon.hip).  What a hook needs to know of a ctx, and what the hooks have in common -- the check macro, the device
+// guard, the timer round a launch, the grid rule, the merge of host tables, the check of a trimming pass's results, the common
+// part of a state and its construction, the frame of an enqueue, last_ms -- each once.  (What the three tally kernels share
+// on the device is amp_tally.hpp.)  amp_ctx (amp_ctx.hpp) keeps one slot (switch, state) per hook and amplihip.hip walks the
+// table of HookOps; a unit keeps its state, its kernels and what it enables.
 #pragma once
 
 #ifdef __HIPCC__
@@ -13,6 +14,7 @@
 #include <stdio.h>
 
 #include <algorithm>
+#include <new>
 #include <vector>
 
 #include "../../include/amplihip.h"
@@ -145,11 +147,49 @@ int hook_add(const HookCtx &q, T *dev, const T *host, size_t count) {
     return AMP_OK;
 }
 
-struct HookDrop {               // a state under construction is freed unless it was handed to the ctx (state = nullptr)
-    const HookOps &ops;
-    void *state;
-    ~HookDrop() { ops.free_state(state); }
+// What every hook's state begins with; a slot's `state` points at this part.
+struct HookState {
+    HookTimer timer;
 };
+template <class S> S *hook_state_of(void *state) { return static_cast<S *>(static_cast<HookState *>(state)); }
+template <class S> S *hook_state(amp_ctx *c, int which) { return hook_state_of<S>(hook_slot(c, which).state); }
+
+// A new state for the slot: fill(*s) allocates what the unit keeps (AMP_OK, or the code of what failed), then the timer;
+// the state is handed to the slot, or freed again when a step failed (s is null then).
+template <class S, class Fill>
+int hook_new_state(const HookCtx &q, HookSlot &slot, const HookOps &ops, S *&s, Fill fill) {
+    S *fresh = new (std::nothrow) S();
+    s = nullptr;
+    if (!fresh) return AMP_ENOMEM;
+    int rc = fill(*fresh);
+    if (rc == AMP_OK) rc = [&]() -> int { HOOKCHK(q, fresh->timer.create()); return AMP_OK; }();
+    if (rc != AMP_OK) { ops.free_state(static_cast<HookState *>(fresh)); return rc; }
+    slot.state = static_cast<HookState *>(s = fresh);
+    return AMP_OK;
+}
+
+// The frame of an enqueue: a batch without reads times nothing; a missing result of the trimming pass is refused; else
+// launch(grid) -- the unit's <<<>>> on q.stream -- between the timer's two events.
+template <class Launch>
+int hook_launch(const HookCtx &q, HookState *s, const HookOps &ops, int64_t n, const amp_trim_out *o, int block, int tiles_per_block, int blocks_per_cu,
+                Launch launch) {
+    s->timer.timed = false;
+    if (n <= 0) return AMP_OK;
+    const int rc = hook_check_out(q, o, ops);
+    if (rc != AMP_OK) return rc;
+    HOOKCHK(q, s->timer.begin(q.stream));
+    launch(hook_grid(n, block, tiles_per_block, blocks_per_cu, q.n_cu));
+    HOOKCHK(q, hipGetLastError());
+    HOOKCHK(q, s->timer.end(q.stream));
+    return AMP_OK;
+}
+
+// amp_*_last_ms: the time of the hook's last kernel
+inline int hook_last_ms(amp_ctx *c, int which, float *ms) {
+    if (!c) return AMP_EINVAL;
+    HookState *s = (HookState *)hook_slot(c, which).state;
+    return s ? s->timer.last_ms(ctx_hook(c), ms) : AMP_ESTATE;
+}
 
 }  // namespace amp
 #endif

@@ -25,14 +25,13 @@
 
 namespace amp {
 
-struct QcState {
+struct QcState : HookState {
     amp_qc_params p{};                    // (its pointers are not kept: the arrays are copied below)
     int32_t *d_left = nullptr, *d_right = nullptr;        // [ref_len] owners
     unsigned long long *d_tally = nullptr;                // [QC_N_TALLIES + 2 * n_primers]: scalars, start counts, end counts
     int32_t *d_rstart = nullptr, *d_rend = nullptr;       // [n_regions], clamped
     amp_qc_region *d_regions = nullptr;                   // [n_regions]
     uint32_t *d_depth = nullptr;                          // [ref_len]
-    HookTimer timer;
     size_t tally_words() const { return (size_t)QC_N_TALLIES + 2 * (size_t)p.n_primers; }
 };
 
@@ -175,10 +174,10 @@ k_qc_regions(const uint32_t *__restrict__ depth, int32_t n_regions, const int32_
     }
 }
 
-static QcState *qc_state(amp_ctx *c) { return (QcState *)hook_slot(c, HOOK_QC).state; }
+static QcState *qc_state(amp_ctx *c) { return hook_state<QcState>(c, HOOK_QC); }
 
 static void qc_free(void *state) {
-    QcState *s = (QcState *)state;
+    QcState *s = hook_state_of<QcState>(state);
     if (!s) return;
     void *bufs[] = {s->d_left, s->d_right, s->d_tally, s->d_rstart, s->d_rend, s->d_regions, s->d_depth};
     for (void *b : bufs) if (b) (void)hipFree(b);
@@ -189,24 +188,17 @@ static void qc_free(void *state) {
 static int qc_enqueue_reads(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
     QcState *s = qc_state(c);
-    s->timer.timed = false;
-    const int64_t n = rd->n_reads;
-    if (n <= 0) return AMP_OK;
-    const int rc = hook_check_out(q, o, qc_hook);
-    if (rc != AMP_OK) return rc;
     QcReadsArgs a;
-    a.n = n; a.pos = rd->pos; a.cig_off32 = rd->cig_off32; a.cig = rd->cig;
+    a.n = rd->n_reads; a.pos = rd->pos; a.cig_off32 = rd->cig_off32; a.cig = rd->cig;
     a.ref_len_out = o ? o->ref_len : nullptr; a.trim_flags = o ? o->trim_flags : nullptr; a.status = o ? o->status : nullptr;
     a.left_owner = s->d_left; a.right_owner = s->d_right;
     a.tally = s->d_tally; a.n_primers = s->p.n_primers;
     a.P = QcReadParams{q.ref_len, q.do_trim ? 1 : 0, s->p.min_length, s->p.include_no_primer};
-    const unsigned grid = hook_grid(n, QC_BLOCK, QC_TILES_PER_BLOCK, QC_BLOCKS_PER_CU, q.n_cu);     // (paid once per block: its LDS histogram and its twelve adds)
-    HOOKCHK(q, s->timer.begin(q.stream));
-    if (2 * (int64_t)s->p.n_primers <= QC_LDS_COUNTERS) k_qc_reads<true><<<grid, QC_BLOCK, 0, q.stream>>>(a);
-    else k_qc_reads<false><<<grid, QC_BLOCK, 0, q.stream>>>(a);
-    HOOKCHK(q, hipGetLastError());
-    HOOKCHK(q, s->timer.end(q.stream));
-    return AMP_OK;
+    // (paid once per block: its LDS histogram and its twelve adds)
+    return hook_launch(q, s, qc_hook, a.n, o, QC_BLOCK, QC_TILES_PER_BLOCK, QC_BLOCKS_PER_CU, [&](unsigned grid) {
+        if (2 * (int64_t)s->p.n_primers <= QC_LDS_COUNTERS) k_qc_reads<true><<<grid, QC_BLOCK, 0, q.stream>>>(a);
+        else k_qc_reads<false><<<grid, QC_BLOCK, 0, q.stream>>>(a);
+    });
 }
 
 static int qc_reset(amp_ctx *c) {
@@ -260,38 +252,38 @@ int amp_qc_enable(amp_ctx *c, const amp_qc_params *p) {
     HOOKCHK(q, hipStreamSynchronize(q.stream));      // (a report that is replaced may still have a kernel in flight)
     qc_free(slot.state);
     slot.state = nullptr; slot.on = false;
-    QcState *s = new (std::nothrow) QcState();
-    if (!s) return AMP_ENOMEM;
-    HookDrop drop{qc_hook, s};
-    s->p = *p;
-    s->p.starts = s->p.ends = s->p.region_start = s->p.region_end = nullptr;
-    const size_t G = (size_t)q.ref_len, R = (size_t)p->n_regions;
-    std::vector<int32_t> lo(G), ro(G), rs(R), re(R);
-    int rc = amp_qc_find_primer_owners(q.ref_len, p->n_primers, p->starts, p->ends, p->primer_pos_offset, lo.data(), ro.data());
-    if (rc != AMP_OK) return rc;
-    for (size_t r = 0; r < R; ++r) {
-        rs[r] = p->region_start[r]; re[r] = p->region_end[r];
-        qc_region_clamp(q.ref_len, rs[r], re[r]);
-    }
-    HOOKCHK(q, hipMalloc((void **)&s->d_left, G * 4));
-    HOOKCHK(q, hipMalloc((void **)&s->d_right, G * 4));
-    HOOKCHK(q, hipMalloc((void **)&s->d_depth, G * 4));
-    HOOKCHK(q, hipMalloc((void **)&s->d_tally, s->tally_words() * sizeof(unsigned long long)));
-    if (R) {
-        HOOKCHK(q, hipMalloc((void **)&s->d_rstart, R * 4));
-        HOOKCHK(q, hipMalloc((void **)&s->d_rend, R * 4));
-        HOOKCHK(q, hipMalloc((void **)&s->d_regions, R * sizeof(amp_qc_region)));
-        HOOKCHK(q, hipMemcpyAsync(s->d_rstart, rs.data(), R * 4, hipMemcpyHostToDevice, q.stream));
-        HOOKCHK(q, hipMemcpyAsync(s->d_rend, re.data(), R * 4, hipMemcpyHostToDevice, q.stream));
-    }
-    HOOKCHK(q, hipMemcpyAsync(s->d_left, lo.data(), G * 4, hipMemcpyHostToDevice, q.stream));
-    HOOKCHK(q, hipMemcpyAsync(s->d_right, ro.data(), G * 4, hipMemcpyHostToDevice, q.stream));
-    HOOKCHK(q, hipMemsetAsync(s->d_tally, 0, s->tally_words() * sizeof(unsigned long long), q.stream));
-    HOOKCHK(q, s->timer.create());
-    HOOKCHK(q, hipStreamSynchronize(q.stream));        // (the host vectors go away)
-    drop.state = nullptr;
-    slot.state = s; slot.on = true;
-    return AMP_OK;
+    QcState *made = nullptr;
+    const int made_rc = hook_new_state(q, slot, qc_hook, made, [&](QcState &fresh) -> int {
+        QcState *const s = &fresh;
+        s->p = *p;
+        s->p.starts = s->p.ends = s->p.region_start = s->p.region_end = nullptr;
+        const size_t G = (size_t)q.ref_len, R = (size_t)p->n_regions;
+        std::vector<int32_t> lo(G), ro(G), rs(R), re(R);
+        int rc = amp_qc_find_primer_owners(q.ref_len, p->n_primers, p->starts, p->ends, p->primer_pos_offset, lo.data(), ro.data());
+        if (rc != AMP_OK) return rc;
+        for (size_t r = 0; r < R; ++r) {
+            rs[r] = p->region_start[r]; re[r] = p->region_end[r];
+            qc_region_clamp(q.ref_len, rs[r], re[r]);
+        }
+        HOOKCHK(q, hipMalloc((void **)&s->d_left, G * 4));
+        HOOKCHK(q, hipMalloc((void **)&s->d_right, G * 4));
+        HOOKCHK(q, hipMalloc((void **)&s->d_depth, G * 4));
+        HOOKCHK(q, hipMalloc((void **)&s->d_tally, s->tally_words() * sizeof(unsigned long long)));
+        if (R) {
+            HOOKCHK(q, hipMalloc((void **)&s->d_rstart, R * 4));
+            HOOKCHK(q, hipMalloc((void **)&s->d_rend, R * 4));
+            HOOKCHK(q, hipMalloc((void **)&s->d_regions, R * sizeof(amp_qc_region)));
+            HOOKCHK(q, hipMemcpyAsync(s->d_rstart, rs.data(), R * 4, hipMemcpyHostToDevice, q.stream));
+            HOOKCHK(q, hipMemcpyAsync(s->d_rend, re.data(), R * 4, hipMemcpyHostToDevice, q.stream));
+        }
+        HOOKCHK(q, hipMemcpyAsync(s->d_left, lo.data(), G * 4, hipMemcpyHostToDevice, q.stream));
+        HOOKCHK(q, hipMemcpyAsync(s->d_right, ro.data(), G * 4, hipMemcpyHostToDevice, q.stream));
+        HOOKCHK(q, hipMemsetAsync(s->d_tally, 0, s->tally_words() * sizeof(unsigned long long), q.stream));
+        HOOKCHK(q, hipStreamSynchronize(q.stream));        // (the host vectors go away)
+        return AMP_OK;
+    });
+    slot.on = made_rc == AMP_OK;
+    return made_rc;
 }
 
 int amp_qc_read_tallies(amp_ctx *c, amp_qc_reads *out, uint64_t *primer_reads_start, uint64_t *primer_reads_end) {
@@ -331,10 +323,6 @@ int amp_qc_depth(amp_ctx *c, uint32_t *depth, amp_qc_region *regions) {
     return AMP_OK;
 }
 
-int amp_qc_last_ms(amp_ctx *c, float *reads_ms) {
-    if (!c) return AMP_EINVAL;
-    QcState *s = qc_state(c);
-    return s ? s->timer.last_ms(ctx_hook(c), reads_ms) : AMP_ESTATE;
-}
+int amp_qc_last_ms(amp_ctx *c, float *reads_ms) { return hook_last_ms(c, HOOK_QC, reads_ms); }
 
 }  // extern "C"

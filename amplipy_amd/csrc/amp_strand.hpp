@@ -5,7 +5,8 @@
 // tests/hostsim/strand_twin.cpp loops the same functions over arrays on the CPU, built with plain g++ (no HIP headers: the
 // two attributes are defined away), against the restatement in tests/strand_util.py.
 //
-// Two views of a read's alignment.  strand_segments: a read with a REGULAR CIGAR -- hard clips, then soft clips, then a core
+// Two views of a read's alignment.  regular_scan (under strand_segments, and under amplicon_segments and codon_segments of
+// amp_amplicon.hpp and amp_codon.hpp): a read with a REGULAR CIGAR -- hard clips, then soft clips, then a core
 // of M = X I D N ops, then soft clips, then hard clips, its query bases adding up to l_seq -- is a list of segments: a match
 // segment (reference start, query start, length) per M = X op and a deletion segment (reference start, length) per D N op.
 // On such a read every pair of a match op lies inside [query_alignment_start, query_alignment_end), the pairs the insertion
@@ -86,14 +87,15 @@ AMP_ST_HD uint32_t st_base_code(const uint8_t *seq, uint64_t k) {
 
 struct StrandShape {
     bool regular;          // the segments are the read's whole counted set, and all of it lies inside the reference
-    int32_t n_seg;         // segments strand_segments hands out (a forward read's deletions add nothing and are left out)
+    int32_t n_seg;         // segments handed out
     int32_t ref_end;       // pos + the reference bases of the CIGAR (regular reads)
 };
 
-// The segments of a read, in CIGAR order, to put(seg); the shape says whether they may be used.  qual0: the read's first
-// quality byte (0xFF: QUAL '*').  Segments of length 0 are not handed out.
+// The scan of a read's CIGAR, the one place where "regular" is decided: put(r0, q_index, len, is_del) for every non-empty
+// match and deletion segment in CIGAR order (q_index: the index in qual / seq of a match segment's first base), n_seg of
+// them; the shape says whether they may be used.  qual0: the read's first quality byte (0xFF: QUAL '*').
 template <class Put>
-AMP_ST_HD StrandShape strand_segments(const StrandRead &R, const StrandParams &P, uint32_t qual0, Put put) {
+AMP_ST_HD StrandShape regular_scan(const StrandRead &R, const StrandParams &P, uint32_t qual0, Put put) {
     StrandShape sh;
     sh.regular = false; sh.n_seg = 0; sh.ref_end = R.pos;
     int phase = 0;                       // 0 leading H, 1 leading S, 2 core, 3 trailing S, 4 trailing H
@@ -116,12 +118,8 @@ AMP_ST_HD StrandShape strand_segments(const StrandRead &R, const StrandParams &P
             if (op == ST_OP_I) { q += len; continue; }
             const bool del = st_is_del(op);
             if (r + len > (int64_t)P.ref_len || (!del && q + len > (int64_t)R.lseq)) { ok = false; break; }
-            if (len > 0 && (!del || R.rev)) {
-                StrandSeg s;
-                s.r0 = (int32_t)r;
-                s.len_kind = ((uint32_t)len << 2) | (del ? 2u : 0u) | (R.rev ? 1u : 0u);
-                s.q0 = R.base + (uint64_t)q;
-                put(s);
+            if (len > 0) {
+                put((int32_t)r, R.base + (uint64_t)q, (uint32_t)len, del);
                 ++sh.n_seg;
             }
             if (!del) q += len;
@@ -132,6 +130,20 @@ AMP_ST_HD StrandShape strand_segments(const StrandRead &R, const StrandParams &P
     }
     sh.regular = ok && phase >= 2 && q == (int64_t)R.lseq;
     sh.ref_end = (int32_t)r;
+    return sh;
+}
+
+// The segments the strand tallies use, to put(seg): the scan's, without a forward read's deletions (they add nothing; n_seg
+// leaves them out).
+template <class Put>
+AMP_ST_HD StrandShape strand_segments(const StrandRead &R, const StrandParams &P, uint32_t qual0, Put put) {
+    int32_t n = 0;
+    StrandShape sh = regular_scan(R, P, qual0, [&](int32_t r0, uint64_t q0, uint32_t len, bool del) {
+        if (del && !R.rev) return;
+        put(StrandSeg{r0, (len << 2) | (del ? 2u : 0u) | (R.rev ? 1u : 0u), q0});
+        ++n;
+    });
+    sh.n_seg = n;
     return sh;
 }
 

@@ -1,7 +1,8 @@
 """The three opt-in kernels behind the read pass -- the QC report, the strand tallies, the per-amplicon counts (DESIGN.md
 section 9c) -- switched on TOGETHER on one engine.  What each computes alone is pinned by test_gpu_qc.py, test_gpu_strand.py and
 test_gpu_amplicon.py; here: with all three on, each one's tables are bit for bit what an engine with only that one on gives for
-the same batch, and trim results, count table and events are what an engine with none on gives; reset zeroes all three and a
+the same batch, and trim results, count table and events are what an engine with none on gives; the three windowed tally
+kernels (strand, amplicon, codon) on a batch whose last tile holds one read, with and without trimming; reset zeroes all three and a
 disabled one is left out; a trimming pass without its results is refused by the first hook in run order that is on, before
 anything ran; and every hook's timer answers after a batch and answers ESTATE after an empty one."""
 import numpy as np
@@ -116,6 +117,32 @@ def test_all_three_on_together_give_what_each_gives_alone(n):
     assert np.array_equal(np.sort(eng.events(), order=EVENT_ORDER), events_off)
     if n >= 1025:
         assert events_off.size > 0
+
+
+@pytest.mark.parametrize("do_trim", [True, False])
+def test_a_last_tile_of_one_read_with_and_without_trimming(do_trim):
+    """257 reads: the second tile of the three windowed tally kernels (amp_tally.hpp) holds one live read and 255 lanes past n.
+    Strand, amplicon and codon tables against their restatements, on the trimmed alignment and on the original one."""
+    from amplipy_amd import codon
+    from tests import codon_util as U
+    st = state()
+    b, amps = batch(257), st["amps"]
+    cds = U.overlapping(amps.G)
+    eng = fresh(("strand", "amplicon"))
+    eng.set_params(MQ, WINDOW, do_trim, True)
+    codon.enable(eng, cds)
+    try:
+        res = eng.process(b)
+        assert not res.status.any()
+        segs = S.walked_segments(b, res if do_trim else None)
+        counts, rev, qsum = S.tables(segs, amps.G, MQ)
+        assert np.array_equal(eng.counts(), counts) and counts.any()
+        for hook, got, want in (("strand", eng.strand_tables(), (rev, qsum)),
+                                ("amplicon", eng.amplicon_tables(), A.tables(b, res, amps, MQ, do_trim)[:2]),
+                                ("codon", eng.codon_tables(), U.tables(segs, amps.G, cds.starts, MQ))):
+            assert all(np.array_equal(g, w) for g, w in zip(got, want)), hook
+    finally:
+        eng.codon_disable()
 
 
 def test_reset_zeroes_all_three_and_a_disabled_hook_is_left_out():

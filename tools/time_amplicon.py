@@ -15,47 +15,25 @@ import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-LAUNCHES, WARMUP = 20, 5
+from tools import time_hooks
+from tools.time_hooks import LAUNCHES
 
 
 def leg(with_hook):
     """One process, one build of the library: medians over LAUNCHES launches."""
     import numpy as np
-    import torch
-    from amplipy_amd import abi, amplicon, lib, synth, synth_torch
+    from amplipy_amd import amplicon, lib
     if not with_hook:              # (a build from before the hook has none of its entry points)
         lib.EXPORTS[:] = [n for n in lib.EXPORTS if not n.startswith("amp_amplicon_")]
-    g = synth.make_genome(); primers, amps = synth.make_artic_scheme(); G = int(g.size)
-    pr = sorted((s, e) for s, e, _ in primers)
-    n = synth.reads_for_depth(10000)
-    mn, mx, mpl = lib.find_overlapping_primers(G, pr, 0)
-    b = synth_torch.make_amplicon_batch_device(g, amps, n, 1000, "cuda:0"); torch.cuda.synchronize()
-    rd = b.struct()
-    out = {k: torch.zeros(sz, dtype=dt, device="cuda:0") for k, sz, dt in
-           (("new_pos", n, torch.int32), ("new_ncig", n, torch.int32), ("new_cig", b.n_cig + 3 * n, torch.int32),
-            ("ref_len", n, torch.int32), ("trim_flags", n, torch.uint8), ("status", n, torch.uint8))}
-    dev_out = abi.AmpTrimOut(*[out[k].data_ptr() for k in ("new_pos", "new_ncig", "new_cig", "ref_len", "trim_flags", "status")])
-    e = lib.Engine(G); e.set_primers(mn, mx, mpl); e.set_params(20, 4, True, True); e.reserve_events(1 << 22)
-
-    def launches(timer=None):
-        ps, ks = [], []
-        for it in range(WARMUP + LAUNCHES):
-            e.reset(); e.process_device(rd, 0, dev_out); e.sync()
-            if it >= WARMUP:
-                ps.append(e.last_kernel_ms()[0])
-                if timer is not None:
-                    ks.append(timer())
-        return ps, ks
+    s = time_hooks.Setup()
+    e, n, launches = s.eng, s.n, s.launches
     res = {"reads": n, "pass_off_ms": statistics.median(launches()[0])}
     if with_hook:
-        rows = sorted(primers, key=lambda r: (r[0], r[1]))
-        pairs = [("SYN_%d_LEFT" % k, "SYN_%d_RIGHT" % k, "SYN_%d" % k) for k in range(1, len(primers) // 2 + 1)]
-        aset = amplicon.build_amplicons(pairs, rows, 0, G)
+        aset = s.amplicon_set()
         e.strand_enable()
         ps, ks = launches(e.strand_last_ms)
         res.update(strand_ms=statistics.median(ks))
@@ -78,14 +56,7 @@ def leg(with_hook):
 
 
 def child(lib_path, with_hook):
-    env = dict(os.environ)
-    if lib_path:
-        env.update(AMPLIPY_DEV="1", AMPLIHIP_LIB=lib_path)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", "hook" if with_hook else "pass"], env=env, capture_output=True,
-                       text=True, timeout=300)
-    if r.returncode != 0:
-        raise RuntimeError("leg failed (%d): %s" % (r.returncode, r.stderr[-2000:]))
-    return json.loads([l for l in r.stdout.splitlines() if l.startswith("LEG ")][-1][4:])
+    return time_hooks.child(__file__, ["--leg", "hook" if with_hook else "pass"], lib_path)
 
 
 def main():

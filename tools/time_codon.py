@@ -14,40 +14,19 @@ import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-LAUNCHES, WARMUP = 20, 5
+from tools import time_hooks
+from tools.time_hooks import LAUNCHES
 
 
 def leg():
     """One process: medians over LAUNCHES launches."""
     import numpy as np
-    import torch
-    from amplipy_amd import abi, lib, synth, synth_torch
-    g = synth.make_genome(); primers, amps = synth.make_artic_scheme(); G = int(g.size)
-    pr = sorted((s, e) for s, e, _ in primers)
-    n = synth.reads_for_depth(10000)
-    mn, mx, mpl = lib.find_overlapping_primers(G, pr, 0)
-    b = synth_torch.make_amplicon_batch_device(g, amps, n, 1000, "cuda:0"); torch.cuda.synchronize()
-    rd = b.struct()
-    out = {k: torch.zeros(sz, dtype=dt, device="cuda:0") for k, sz, dt in
-           (("new_pos", n, torch.int32), ("new_ncig", n, torch.int32), ("new_cig", b.n_cig + 3 * n, torch.int32),
-            ("ref_len", n, torch.int32), ("trim_flags", n, torch.uint8), ("status", n, torch.uint8))}
-    dev_out = abi.AmpTrimOut(*[out[k].data_ptr() for k in ("new_pos", "new_ncig", "new_cig", "ref_len", "trim_flags", "status")])
-    e = lib.Engine(G); e.set_primers(mn, mx, mpl); e.set_params(20, 4, True, True); e.reserve_events(1 << 22)
-
-    def launches(hook_ms=None):
-        ps, ks = [], []
-        for it in range(WARMUP + LAUNCHES):
-            e.reset(); e.process_device(rd, 0, dev_out); e.sync()
-            if it >= WARMUP:
-                ps.append(e.last_kernel_ms()[0])
-                if hook_ms is not None:
-                    ks.append(hook_ms())
-        return ps, ks
+    s = time_hooks.Setup()
+    e, n, G, launches = s.eng, s.n, s.G, s.launches
     res = {"reads": n, "pass_off_ms": statistics.median(launches()[0])}
     e.strand_enable()
     ps, ks = launches(e.strand_last_ms)
@@ -73,10 +52,7 @@ def leg():
 
 
 def child():
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg"], capture_output=True, text=True, timeout=300)
-    if r.returncode != 0:
-        raise RuntimeError("leg failed (%d): %s" % (r.returncode, r.stderr[-2000:]))
-    return json.loads([l for l in r.stdout.splitlines() if l.startswith("LEG ")][-1][4:])
+    return time_hooks.child(__file__, ["--leg"])
 
 
 def main():
@@ -87,7 +63,7 @@ def main():
     a = ap.parse_args()
     if a.leg:
         return leg()
-    res = {"batch": "10k x depth, 150-base reads (synth_torch, seed 1000)", "launches_per_figure": LAUNCHES, "rounds": []}
+    res = {"batch": time_hooks.BATCH, "launches_per_figure": LAUNCHES, "rounds": []}
     for k in range(a.rounds):                 # a process each
         r = child()
         assert r["invariant_holds_one_frame"] and r["invariant_holds_three_frames"]
