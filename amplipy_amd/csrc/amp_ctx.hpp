@@ -67,6 +67,7 @@ struct amp_ctx {
     DBuf o_pos, o_ncig, o_cig, o_reflen, o_flags, o_status;
     DBuf scratch;                 // CIGAR scratch for reads whose ops do not fit the LDS slots
     DBuf call_buf;
+    DBuf call_sync;                // k_call_fused's ticket and flags (zero between launches)
     DBuf agg_buf;                  // amp_aggregate_ins_events: run records + the sort's scratch
     void *h_pin = nullptr; size_t h_pin_cap = 0;   // pinned staging for call results (amp_call_compact_begin: written by the kernel itself)
     std::vector<uint8_t> h_img; bool img_pinned = false;   // ... and the pageable image of a view that was not begun (one copy)
@@ -80,6 +81,14 @@ struct amp_ctx {
     int n_cu = 256;
     int cu_share = 1;              // the fast kernels of this ctx are sized for n_cu / cu_share CUs (amp_set_cu_share)
     uint32_t epoch = 0;            // launches of the read kernels so far (KParams::epoch)
+    // What the last finished pass of variant 4 left for its second kernels, written by k_deferred_heavy into pinned host memory
+    // (no copy, no wait): [0] = epoch << 32 | heavy entries, [1] = epoch << 32 | reads on the general list.  launch_reads sizes
+    // the next pass's second kernels by it (ReadPlan::gen_blocks / heavy_blocks) when both words carry one epoch, not older than
+    // hist_from (the setters of the plan's inputs and every pass of another variant move it past the passes launched so far).
+    unsigned long long *h_hist = nullptr;
+    uint32_t hist_from = 1;
+    int force_gen_blocks = 0, force_heavy_blocks = 0;      // amp_debug_second_grids: 0 = by the plan
+    int last_gen_blocks = 0, last_heavy_blocks = 0;        // what the last pass of variant 4 was launched with (amp_debug_last_second_grids)
     // amp_set_kernel_variant: 0 = by the batch (route_variant, amp_plan.hpp), 1 = one lane per read (the reference kernel),
     // 2 = fused tile kernel, 3 = split pipeline (k_trim + k_scan + k_tile<SPLIT>), 4 / 5 / 6 / 7 = a fast kernel (k_fast, k_fast5,
     // k_fast6, k_fast7: the four generations) + the general pass (k_tile<LIST> over the other reads)

@@ -511,10 +511,27 @@ __device__ __forceinline__ void heavy_pass(HeavyLds &L, const KParams &P, const 
 __global__ void __launch_bounds__(256)
 k_deferred_heavy(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *scratch, uint32_t *counts,
                  EventBuf eb, const uint32_t *dlist, const uint32_t *dcnt, long long tiles_per_block, long long n_seg,
-                 const GenGeo *geo, long long dcnt_stride, const uint32_t *segfirst) {
+                 const GenGeo *geo, long long dcnt_stride, const uint32_t *segfirst, unsigned long long *hist) {
     __shared__ HeavyLds L;
-    if (__hip_atomic_load(&eb.ctr[CTR_HEAVY_FLAG], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull) return;   // set by the tile kernel
+    const bool any = __hip_atomic_load(&eb.ctr[CTR_HEAVY_FLAG], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull;   // set by the tile kernel
     if (geo) { tiles_per_block = (long long)geo->tpb; n_seg = (long long)geo->n_seg; }
+    if (hist && blockIdx.x == 0) {
+        // for the host's plan of the engine's next pass (amp_ctx::h_hist): the lengths of this pass's two lists, each in one
+        // 8-byte word of pinned host memory with the pass's epoch
+        if (threadIdx.x == 0) L.nev = 0;
+        __syncthreads();
+        uint32_t h = 0;
+        if (any) for (long long s = threadIdx.x; s < n_seg; s += blockDim.x) h += dcnt[5 * dcnt_stride + 64 + s];
+        if (h) atomicAdd(&L.nev, h);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned long long tag = (unsigned long long)P.epoch << 32;
+            __hip_atomic_store(&hist[0], tag | L.nev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&hist[1], tag | (uint32_t)eb.ctr[CTR_GEN_LIST_N], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        __syncthreads();
+    }
+    if (!any) return;
     heavy_pass<true>(L, P, rd, read_base, out, scratch, counts, eb, dlist, dcnt, tiles_per_block, n_seg, dcnt_stride, segfirst);
     __syncthreads();
     heavy_pass<false>(L, P, rd, read_base, out, scratch, counts, eb, dlist, dcnt, tiles_per_block, n_seg, dcnt_stride, segfirst);
@@ -524,8 +541,9 @@ k_deferred_heavy(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, ui
 // given) the list's geometry is decided on the device and read from geo; behind the other tile kernels it is tg's.
 static inline int heavy_launch(const KParams &P, const amp_dev_reads &rd, uint64_t read_base, const DevOut &out, uint32_t *scratch,
                                uint32_t *counts, const EventBuf &eb, const uint32_t *dlist, const uint32_t *dcnt, int64_t grid,
-                               const TileGrid &tg, const GenGeo *geo, const uint32_t *segfirst, hipStream_t stream) {
+                               const TileGrid &tg, const GenGeo *geo, const uint32_t *segfirst, hipStream_t stream,
+                               unsigned long long *hist = nullptr) {
     k_deferred_heavy<<<(unsigned)grid, 256, 0, stream>>>(P, rd, read_base, out, scratch, counts, eb, dlist, dcnt, geo ? 0 : (long long)tg.tpb,
-                                                         geo ? 0 : (long long)tg.grid, geo, (long long)tg.grid, segfirst);
+                                                         geo ? 0 : (long long)tg.grid, geo, (long long)tg.grid, segfirst, hist);
     return (int)hipGetLastError();
 }

@@ -2,6 +2,17 @@
 // each of them finds its piece of the scratch buffer.  Plain C++ (no HIP): the kernel headers include it for the
 // geometry constants and grid functions they share with the host, launch_reads (amp_readpass.hip) turns a ReadPlan into
 // pointers and launches, and tests/test_read_plan.py checks it on a machine without a GPU.
+//
+// The plan is a pure function of PlanIn.  Two of its inputs are history: the lengths of the general list and of the heavy list
+// of the engine's previous pass (launch_reads reads them from two words the heavy kernel leaves in pinned host memory; negative =
+// unknown).  They decide nothing but how many BLOCKS the two kernels behind a fast kernel are launched with (gen_blocks,
+// heavy_blocks): twice what the previous pass would have kept busy, between PREDICT_MIN and the full grid for the engine's share
+// of the CUs.  The SEGMENTS the lists are cut into (gen_grid, heavy_grid), every other grid and the scratch layout do not depend
+// on them, and a block walks as many segments as it has to: a batch unlike the one before runs correctly on the wrong number of
+// blocks, only slower, and the pass after it is sized by what it found (tests/test_read_plan_history.py).  "Previous" is the last
+// pass that had FINISHED when the host planned this one (the words are read without a wait, so the two block counts depend on
+// the host's timing; nothing else does), and only a pass behind a fast kernel leaves history: after a pass of another variant,
+// as after a setter that changes a plan input, the next pass has none and takes the full grids.
 #pragma once
 
 #include <stddef.h>
@@ -103,12 +114,29 @@ static inline int route_variant(int requested_variant, int64_t n_reads, int64_t 
     return (kv1 == 6 && min_quality < 1) ? 4 : kv1;      // (the third generation tells a masked base by its zeroed code: with min_quality 0 the pad bases of a row would count as kept)
 }
 
+// ---- the blocks of the second kernels ---------------------------------------------------------------------------
+// Segments (blocks' shares) a list of n_list reads is cut into for a general pass of gen_grid segments at most: k_tile<LIST> and
+// k_gcompact derive the same on the device (tiles per segment: whole super-tiles, at least one).
+static inline int64_t gen_segments(int64_t n_list, int64_t gen_grid) {
+    const int64_t tiles = (n_list + TILE - 1) / TILE;
+    int64_t tpb = (tiles + gen_grid - 1) / gen_grid;
+    tpb = std::max<int64_t>(((tpb + T_WAVES - 1) / T_WAVES) * T_WAVES, T_WAVES);
+    return (tiles + tpb - 1) / tpb;
+}
+constexpr int64_t PREDICT_MIN = 8;      // blocks of a launch that is expected to find nothing (about one per XCD)
+static inline int64_t predicted_blocks(int64_t units_before, int64_t cap) {
+    return std::min<int64_t>(std::max<int64_t>(2 * units_before, std::min<int64_t>(PREDICT_MIN, cap)), cap);
+}
+
 // ---- the plan -------------------------------------------------------------------------------------------------
 struct PlanIn {
     int64_t n_reads, n_cig, n_bases_padded;      // amp_dev_reads
     int32_t window, min_quality;
     int requested_variant, n_cu, cu_share;       // amp_set_kernel_variant, the device's CUs, amp_set_cu_share
     bool caller_gives_new_pos, caller_gives_new_ncig, caller_gives_new_cig;      // outputs the caller has buffers for
+    // what the previous pass of this engine left for its second kernels: reads on the general list, entries on the heavy
+    // (deferred) list.  Negative: no history -- the engine's first pass, or one behind a setter that changed the plan's inputs.
+    int64_t prev_list = -1, prev_heavy = -1;
 };
 
 struct Region { size_t off, words; };      // a piece of the scratch buffer, in 32-bit words (arrays of such words: nothing asks for more than their alignment)
@@ -118,7 +146,8 @@ struct ReadPlan {
     FastGrid fg;          // grid of the fast kernel of `kv` (variants 1-3 launch none)
     int fast_waves;       // ... and its waves per block (0: none)
     TileGrid tg;
-    int64_t gen_grid, heavy_grid;      // blocks of k_tile<LIST> (the general pass of variant 4) and of k_deferred_heavy
+    int64_t gen_grid, heavy_grid;      // list segments of k_tile<LIST> (the general pass of variant 4); the most blocks k_deferred_heavy is given on the whole chip
+    int64_t gen_blocks, heavy_blocks;  // blocks the two are launched with (variant 4): predicted from the engine's previous pass, see plan_reads
     bool long_kernel;     // k_long (amp_wave.hpp) takes the reads with many CIGAR ops
     bool direct;          // k_tile<LIST> indexes the fast kernel's per-block segments itself: no k_gcompact
     int64_t ev_fixed;     // event-list slots to reserve on top of the bound of the batch's events
@@ -153,6 +182,17 @@ static inline bool plan_reads(const PlanIn &in, ReadPlan &p) {
     // tiles would still have to be placed on a CU one after the other), tiles per block decided on the device
     p.gen_grid = std::min<int64_t>(std::min<int64_t>(p.tg.grid, 4 * (int64_t)in.n_cu), GEN_MAXGRID);
     p.heavy_grid = std::min<int64_t>(p.tg.grid, 2 * (int64_t)in.n_cu);
+    // ... and how many blocks walk those segments.  Blocks of a launch with nothing to do still have to be placed, each on a CU
+    // that no block of a fast kernel holds (a k_fast block takes its CU whole), so the launch is sized for the work the engine's
+    // previous pass had: twice the segments its list would fill today, and twice the rounds of 256 entries its heavy list was,
+    // between PREDICT_MIN and the full grid for this engine's share of the CUs.  A block walks segments b, b + blocks, ...: a
+    // wrong prediction costs time, never the result, and the next pass is sized by what this one finds.
+    {
+        const int64_t gen_cap = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(p.tg.grid, 4 * (int64_t)fast_cus), GEN_MAXGRID));
+        const int64_t heavy_cap = std::max<int64_t>(1, std::min<int64_t>(p.tg.grid, 2 * (int64_t)fast_cus));
+        p.gen_blocks = in.prev_list < 0 ? gen_cap : predicted_blocks(gen_segments(in.prev_list, p.gen_grid), gen_cap);
+        p.heavy_blocks = in.prev_heavy < 0 ? heavy_cap : predicted_blocks((in.prev_heavy + 255) / 256, heavy_cap);
+    }
     // a batch of reads with many CIGAR ops (eight a read on average: Nanopore-like) gets k_long (amp_wave.hpp) for them; the
     // results do not depend on this choice
     p.long_kernel = p.variant == 4 && in.n_cig >= 8 * n;

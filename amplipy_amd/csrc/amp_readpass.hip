@@ -34,10 +34,23 @@ int amp::launch_reads(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base, c
     DevOut out{o ? o->new_pos : nullptr, o ? o->new_ncig : nullptr, o ? o->new_cig : nullptr, o ? o->ref_len : nullptr,
                o ? o->trim_flags : nullptr, o ? o->status : nullptr};
     ReadPlan pl;
-    if (!plan_reads(PlanIn{n, rd->n_cig, rd->n_bases_padded, c->window, c->min_quality, c->kernel_variant, c->n_cu, c->cu_share,
-                           out.new_pos != nullptr, out.new_ncig != nullptr, out.new_cig != nullptr}, pl)) {
+    PlanIn pin{n, rd->n_cig, rd->n_bases_padded, c->window, c->min_quality, c->kernel_variant, c->n_cu, c->cu_share,
+               out.new_pos != nullptr, out.new_ncig != nullptr, out.new_cig != nullptr};
+    {   // The lists of the engine's last FINISHED pass (amp_ctx::h_hist): both words of one pass, and of one behind the last setter
+        // and behind the last pass of another variant.  The words are read as they stand, without waiting for the pass before: a
+        // caller that launches the next pass before that one has finished gets the history of the pass before it, or none -- so
+        // the two grids, and with them traces and timings, depend on when the host arrives here.  The results do not.
+        const unsigned long long w0 = __atomic_load_n(&c->h_hist[0], __ATOMIC_RELAXED), w1 = __atomic_load_n(&c->h_hist[1], __ATOMIC_RELAXED);
+        const uint32_t e = (uint32_t)(w0 >> 32);
+        if (e == (uint32_t)(w1 >> 32) && (int32_t)(e - c->hist_from) >= 0 && (int32_t)(c->epoch - e) >= 0) {
+            pin.prev_heavy = (int64_t)(uint32_t)w0; pin.prev_list = (int64_t)(uint32_t)w1;
+        }
+    }
+    if (!plan_reads(pin, pl)) {
         snprintf(c->err, sizeof(c->err), "a batch holds at most %u reads", DEFER_INDEX_MASK); return AMP_EINVAL;
     }
+    if (c->force_gen_blocks > 0) pl.gen_blocks = std::min<int64_t>(c->force_gen_blocks, pl.gen_grid);
+    if (c->force_heavy_blocks > 0) pl.heavy_blocks = std::min<int64_t>(c->force_heavy_blocks, pl.heavy_grid);
     const int kv = pl.kv, variant = pl.variant;
     const TileGrid &tg = pl.tg;
     const FastGrid &fg = pl.fg;
@@ -103,15 +116,16 @@ int amp::launch_reads(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base, c
 #ifdef AMP_DEV
         if (c->phases & 0x100u) {           // stamps of the general pass alone: the fast kernel's are dropped
             HIPCHK(c, hipMemsetAsync(&c->d_ctr[CTR_STAMP0], 0, (CTR_EV_SHARD0 - CTR_STAMP0) * sizeof(unsigned long long), c->stream));
-            k_tile<true, false, true><<<(unsigned)pl.gen_grid, T_WAVES * 64, 0, c->stream>>>(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, 0, none,
+            k_tile<true, false, true><<<(unsigned)pl.gen_blocks, T_WAVES * 64, 0, c->stream>>>(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, 0, none,
                                                                                        direct ? nullptr : gdense, geo, (uint32_t)tg.grid, ls AMP_PHASES_ARG(c->phases));
         } else
 #endif
-        k_tile<false, false, true><<<(unsigned)pl.gen_grid, T_WAVES * 64, 0, c->stream>>>(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, 0, none,
+        k_tile<false, false, true><<<(unsigned)pl.gen_blocks, T_WAVES * 64, 0, c->stream>>>(P, *rd, read_base, out, c->d_counts, eb, dlist, dcnt, 0, none,
                                                                                     direct ? nullptr : gdense, geo, (uint32_t)tg.grid, ls AMP_PHASES_ARG(c->phases));
         HIPCHK(c, hipGetLastError());
         // (the tile kernel does the indels of regular reads itself and raises the heavy pass's flag)
-        HIPCHK(c, (hipError_t)heavy_launch(P, *rd, read_base, out, at(pl.pingpong), c->d_counts, eb, dlist, dcnt, pl.heavy_grid, tg, geo, segfirst, c->stream));
+        HIPCHK(c, (hipError_t)heavy_launch(P, *rd, read_base, out, at(pl.pingpong), c->d_counts, eb, dlist, dcnt, pl.heavy_blocks, tg, geo, segfirst, c->stream, c->h_hist));
+        c->last_gen_blocks = (int)pl.gen_blocks; c->last_heavy_blocks = (int)pl.heavy_blocks;
     } else {
         HIPCHK(c, hipEventRecord(c->ev1, c->stream));
         uint32_t *const sp = at(pl.split);      // variant 3 hand-over arrays
@@ -127,6 +141,7 @@ int amp::launch_reads(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_base, c
     c->timed = true;
     c->last_split = variant != 4 || c->split_timing;
     c->last_kv = kv;
+    if (variant != 4) c->hist_from = c->epoch + 1;      // no k_deferred_heavy behind a fast kernel wrote the lists of this pass: the next one has no history
     return AMP_OK;
 }
 

@@ -591,7 +591,7 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
             ls.geo_out->n_list = 0u; ls.geo_out->tpb = (uint32_t)T_WAVES; ls.geo_out->n_seg = 0u; ls.geo_out->live_counted = 0u;
             ctr[CTR_GEN_LIST_N] = 0ull;
         }
-        if (tid == 0) { dcnt[blockIdx.x] = 0; dcnt[5 * dcnt_stride + 64 + blockIdx.x] = 0; }
+        for (uint32_t v = blockIdx.x * blockDim.x + tid; v < ls.gen_grid; v += gridDim.x * blockDim.x) { dcnt[v] = 0; dcnt[5 * dcnt_stride + 64 + v] = 0; }
         return;
     }
     if (direct) {
@@ -625,14 +625,20 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
         return ls.glist[(size_t)lo * (size_t)ls.rpb + (size_t)(li - (int64_t)L.gpre[lo])];
     };
     const int64_t n_tiles = (n + TILE - 1) / TILE;
-    const int64_t tile_begin = (int64_t)blockIdx.x * tiles_per_block;
+    // LIST: the list is cut into ls.gen_grid segments, whatever the grid: this block takes segments blockIdx.x, blockIdx.x + gridDim.x, ...
+    // one after the other (the host launches as many blocks as it expects to be busy: ReadPlan::gen_blocks).  Everything that
+    // was the block's -- its tiles, its segment of the deferred list, its counts -- is the segment's, `vb`.
+    const uint32_t n_vb = LIST ? ls.gen_grid : gridDim.x;
+    for (uint32_t vb = blockIdx.x; vb < n_vb; vb += gridDim.x) {
+    if (vb != blockIdx.x) __syncthreads();      // the segment before is flushed: its window, its counts
+    const int64_t tile_begin = (int64_t)vb * tiles_per_block;
     const int64_t tile_end = tile_begin + tiles_per_block < n_tiles ? tile_begin + tiles_per_block : n_tiles;
     if (tile_begin >= tile_end || (LIST && !direct && geo->live_counted && ctr[CTR_GEN_LEFT] == 0ull)) {
-        if (threadIdx.x == 0) { dcnt[blockIdx.x] = 0; dcnt[5 * dcnt_stride + 64 + blockIdx.x] = 0; }
-        return;
+        if (threadIdx.x == 0) { dcnt[vb] = 0; dcnt[5 * dcnt_stride + 64 + vb] = 0; }
+        continue;
     }
 
-    if (LIST && ls.segfirst && tid == 0) ls.segfirst[blockIdx.x] = list_entry(tile_begin * TILE) & GL_INDEX_MASK;
+    if (LIST && ls.segfirst && tid == 0) ls.segfirst[vb] = list_entry(tile_begin * TILE) & GL_INDEX_MASK;
     lds_u32 *const win = (lds_u32 *)L.win;
     lds_u32 *const lut = (lds_u32 *)L.lut;
     for (int i = tid; i < AMP_NSYM * T_W; i += T_WAVES * 64) win[i] = 0;
@@ -934,7 +940,7 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
             const uint32_t nev_all = *evcur;
             const uint32_t nev = nev_all < T_EVCAP ? nev_all : T_EVCAP;
             if (nev) {
-                const unsigned shard = blockIdx.x & (EV_SHARDS - 1);
+                const unsigned shard = vb & (EV_SHARDS - 1);
                 unsigned long long eb0 = 0;
                 if (lane == 0) eb0 = atomicAdd(&eb.ctr[CTR_EV_SHARD0 + shard], (unsigned long long)nev);
                 eb0 = __shfl(eb0, 0);
@@ -999,7 +1005,7 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
     }
     if (n_err) atomicAdd(&ctr[CTR_ERROR_READS], n_err);
     if (tid == 0) {
-        dcnt[blockIdx.x] = L.dcount; dcnt[5 * dcnt_stride + 64 + blockIdx.x] = L.dcount2;
+        dcnt[vb] = L.dcount; dcnt[5 * dcnt_stride + 64 + vb] = L.dcount2;
         if (L.dcount2) atomicOr(&ctr[CTR_HEAVY_FLAG], 1ull);        // tells the heavy pass that it has something to do at all (sticky until amp_reset)
         // (no per-block atomic on a shared counter here: thousands of blocks on one address serialise;
         //  amp_debug_counters sums the per-block list counts instead)
@@ -1011,13 +1017,14 @@ k_tile(KParams P, amp_dev_reads rd, uint64_t read_base, DevOut out, uint32_t *co
         atomicAdd(&ctr[CTR_PHASE0 + 7], 1ull);
         if (tid == 0) {
             const unsigned long long dur = __builtin_amdgcn_s_memtime() - t_kernel0;
-            atomicMax(&ctr[CTR_PHASE0 + 6], (dur << 16) | (unsigned long long)(blockIdx.x & 0xFFFF));            // slowest block and its id
-            atomicMax(&ctr[CTR_STAMP0 + 1], ((0xFFFFFFFFFFFFull - dur) << 16) | (unsigned long long)(blockIdx.x & 0xFFFF));   // fastest block
+            atomicMax(&ctr[CTR_PHASE0 + 6], (dur << 16) | (unsigned long long)(vb & 0xFFFF));            // slowest block and its id
+            atomicMax(&ctr[CTR_STAMP0 + 1], ((0xFFFFFFFFFFFFull - dur) << 16) | (unsigned long long)(vb & 0xFFFF));   // fastest block
             atomicAdd(&ctr[CTR_STAMP0], dur);
-            dcnt[dcnt_stride + 64 + blockIdx.x * 4 + 0] = (uint32_t)dur; dcnt[dcnt_stride + 64 + blockIdx.x * 4 + 1] = bs_rebase;
+            dcnt[dcnt_stride + 64 + vb * 4 + 0] = (uint32_t)dur; dcnt[dcnt_stride + 64 + vb * 4 + 1] = bs_rebase;
         }
-        if (lane == 0) { atomicAdd(&dcnt[dcnt_stride + 64 + blockIdx.x * 4 + 2], bs_c2); atomicAdd(&dcnt[dcnt_stride + 64 + blockIdx.x * 4 + 3], bs_c4); }
+        if (lane == 0) { atomicAdd(&dcnt[dcnt_stride + 64 + vb * 4 + 2], bs_c2); atomicAdd(&dcnt[dcnt_stride + 64 + vb * 4 + 3], bs_c4); }
     }
+    }   // segments of this block
 }
 
 static inline int tile_launch(const KParams &P, const amp_dev_reads &rd, uint64_t read_base, const DevOut &out,

@@ -43,15 +43,22 @@ hipError_t amp::grow_events(amp_ctx *c, int64_t ncap) {   // re-lays the shard r
     return hipSuccess;
 }
 
-// amp_reset: zeroes the device table and the counters
+// amp_reset: zeroes the device table and the counters.  A handful of blocks (RESET_BLOCKS) that store 16 bytes per lane in a
+// grid-stride loop: while a pass of another engine runs, every block of this kernel has to wait for a CU that no block of a
+// fast kernel holds, and the pass behind it on the stream waits with it.
+constexpr unsigned RESET_BLOCKS = 8;
 __global__ void __launch_bounds__(256)
 k_reset(uint32_t *a, size_t na, uint32_t *b, size_t nb) {
-    const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const size_t i = i0 + k;
-        if (i < na) a[i] = 0u;
-        else if (i - na < nb) b[i - na] = 0u;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, nt = (size_t)gridDim.x * 256;
+    const size_t to16 = (size_t)((16u - (unsigned)((uintptr_t)a & 15u)) & 15u) / 4;
+    const size_t head = to16 < na ? to16 : na;      // words in front of the first 16-byte boundary
+    const size_t nvec = (na - head) / 4, tail = na - head - nvec * 4;
+    uint4 *const v = (uint4 *)(a + head);
+    for (size_t i = t; i < nvec; i += nt) v[i] = make_uint4(0u, 0u, 0u, 0u);
+    for (size_t i = t; i < head + tail + nb; i += nt) {
+        if (i < head) a[i] = 0u;
+        else if (i < head + tail) a[head + nvec * 4 + (i - head)] = 0u;
+        else b[i - head - tail] = 0u;
     }
 }
 
@@ -141,6 +148,105 @@ k_call_compact(const amp_pos_call *__restrict__ pc, const uint32_t *__restrict__
     if (blockIdx.x == gridDim.x - 1 && tid == 255) {   // last thread of the last block knows both totals
         n_out[0] = ov + (isv ? 1u : 0u);
         n_out[1] = orl + (isr ? 1u : 0u);
+    }
+}
+
+// k_call and k_call_compact as ONE launch, for the pipelined callers (amp_call_compact_begin): a launch behind a pass costs its
+// blocks' wait for free CUs and a place in the stream's queue, and nothing but the per-block record counts crosses from the one
+// kernel to the other.  A block calls its 256 positions, keeps them in registers, publishes its two record counts and adds up
+// those of the blocks in front of it (a look-back over their flags), then writes its part of the image.
+// A block's number is the order of its arrival (a ticket), not blockIdx.x: every block with a smaller number has started, and
+// a block publishes its counts before it waits for any, so the wait ends wherever the blocks are placed and however few of
+// them are resident at a time.  sync: [0] ticket, [1] blocks that are through, [2] waits given up, [CALL_SYNC_FLAG0 + b] the flag
+// of block b: bit 63 | relevant positions << 32 | variant records.  All zero before the launch; the last block through leaves
+// them zero again.  A wait is given up after CALL_WAIT_TICKS of the 100 MHz clock (seconds: it cannot happen unless a block in
+// front was lost); the image then says so in n_out[2] and the host refuses it.
+constexpr int CALL_SYNC_FLAG0 = 4;
+constexpr unsigned long long CALL_WAIT_TICKS = 400000000ull;
+__global__ void __launch_bounds__(256)
+k_call_fused(const uint32_t *__restrict__ counts, const uint32_t *__restrict__ ins_at, const uint8_t *__restrict__ ref, int32_t ref_len,
+             amp_call_params pr, int8_t *__restrict__ cons, amp_var_rec *__restrict__ vars, int32_t *__restrict__ rel,
+             unsigned long long *n_out, unsigned long long *sync) {
+    __shared__ uint32_t s_vb, s_last, s_pv[4], s_pr[4], s_wv[4], s_wr[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    unsigned long long *const flag = sync + CALL_SYNC_FLAG0;
+    if (tid == 0) s_vb = (uint32_t)__hip_atomic_fetch_add(&sync[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const uint32_t vb = s_vb;
+    const int32_t p = (int32_t)(vb * 256u) + tid;
+    const bool live = p < ref_len;
+    const int32_t pp = live ? p : ref_len - 1;            // keep the whole block alive for the block-level counts
+    uint32_t cnt[6];
+    for (int k = 0; k < 6; ++k) cnt[k] = counts[(size_t)pp * AMP_NSYM + k];
+    bool relevant;
+    const amp_pos_call c = call_position(cnt, ins_at[pp], ref + pp, pr, relevant);   // amp_call.hpp
+    if (live) cons[p] = c.consensus_sym;
+    const bool isr = live && relevant, isv = live && !relevant && (c.flags & AMP_CALL_VARIANT);
+    const unsigned long long bv = __ballot(isv), br = __ballot(isr);
+    if (lane == 0) { s_wv[wave] = (uint32_t)__popcll(bv); s_wr[wave] = (uint32_t)__popcll(br); }
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned long long tv = s_wv[0] + s_wv[1] + s_wv[2] + s_wv[3], tr = s_wr[0] + s_wr[1] + s_wr[2] + s_wr[3];
+        __hip_atomic_store(&flag[vb], (1ull << 63) | (tr << 32) | tv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // totals of the blocks in front of this one
+    uint32_t pv = 0, prl = 0;
+    bool gave_up = false;
+    const unsigned long long t_wait0 = wall_clock64();
+    for (uint32_t b = (uint32_t)tid; b < vb; b += 256u) {
+        unsigned long long x = __hip_atomic_load(&flag[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        while (!(x >> 63)) {
+            if (wall_clock64() - t_wait0 > CALL_WAIT_TICKS) { gave_up = true; break; }
+            x = __hip_atomic_load(&flag[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        pv += (uint32_t)x; prl += (uint32_t)(x >> 32) & 0x7FFFFFFFu;
+    }
+    if (gave_up) __hip_atomic_fetch_add(&sync[2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int o = 32; o > 0; o >>= 1) { pv += __shfl_down(pv, o); prl += __shfl_down(prl, o); }
+    if (lane == 0) { s_pv[wave] = pv; s_pr[wave] = prl; }
+    __syncthreads();
+    uint32_t ov = s_pv[0] + s_pv[1] + s_pv[2] + s_pv[3], orl = s_pr[0] + s_pr[1] + s_pr[2] + s_pr[3];
+    for (int w = 0; w < wave; ++w) { ov += s_wv[w]; orl += s_wr[w]; }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    ov += (uint32_t)__popcll(bv & below); orl += (uint32_t)__popcll(br & below);
+    // (offsets are sums of counts of distinct positions: inside the image whatever a given-up wait left out)
+    if (isr) rel[orl] = p;
+    if (isv) {
+        amp_var_rec v;
+        v.pos = p; v.total_depth = c.total_depth; v.ref_count = c.ref_count;
+        v.gt_has_ref = (c.flags & AMP_CALL_GT_HAS_REF) ? 1 : 0;
+        uint32_t m = c.alt_mask & 0x3Fu;      // (static slot indices: see k_call_compact)
+        uint8_t na = 0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            if (m) {
+                const int k = __builtin_ctz(m);
+                m &= m - 1u;
+                const uint32_t col = (c.order >> (3 * k)) & 7u;
+                v.alt_col[j] = (uint8_t)col; v.alt_count[j] = counts[(size_t)p * AMP_NSYM + col]; ++na;
+            } else {
+                v.alt_col[j] = 0xFF; v.alt_count[j] = 0;
+            }
+        }
+        v.n_alt = na;
+        vars[ov] = v;
+    }
+    if (vb == gridDim.x - 1 && tid == 255) {   // last thread of the last block knows both totals
+        n_out[0] = ov + (isv ? 1u : 0u);
+        n_out[1] = orl + (isr ? 1u : 0u);
+    }
+    // The last block through tidies up for the next launch.  The count is a relaxed add: what it has to come after are this
+    // block's loads of the flags, and their values were used in front of the barrier.  (As an agent-scope release it makes every
+    // block wait for the write-back of its stores to the host image: profiles/small_launches_release_variant.json.)
+    __syncthreads();
+    if (tid == 0) s_last = __hip_atomic_fetch_add(&sync[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned long long)gridDim.x - 1ull;
+    __syncthreads();
+    if (s_last) {
+        if (tid == 0) {
+            n_out[2] = __hip_atomic_load(&sync[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int k = 0; k < 3; ++k) __hip_atomic_store(&sync[k], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        for (uint32_t b = (uint32_t)tid; b < gridDim.x; b += 256u) __hip_atomic_store(&flag[b], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -286,6 +392,8 @@ int amp_ctx_create(amp_ctx **out, int device, int32_t ref_len) {
     if (hipMalloc((void **)&c->d_max_end, (size_t)ref_len * 4) != hipSuccess) return fail(AMP_ENOMEM);
     if (hipMalloc((void **)&c->d_ctr, CTR_WORDS * sizeof(unsigned long long)) != hipSuccess) return fail(AMP_ENOMEM);
     if (hipMalloc((void **)&c->d_ref, (size_t)ref_len) != hipSuccess) return fail(AMP_ENOMEM);
+    if (hipHostMalloc((void **)&c->h_hist, 64, hipHostMallocDefault) != hipSuccess) return fail(AMP_ENOMEM);
+    memset(c->h_hist, 0, 64);
     if (hipMemsetAsync(c->d_counts, 0, cb, c->stream) != hipSuccess) return fail(AMP_EHIP);
     if (hipMemsetAsync(c->d_ctr, 0, CTR_WORDS * sizeof(unsigned long long), c->stream) != hipSuccess) return fail(AMP_EHIP);
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
@@ -315,6 +423,7 @@ void amp_ctx_destroy(amp_ctx *c) {
     if (c->d_max_end) (void)hipFree(c->d_max_end);
     if (c->d_ctr) (void)hipFree(c->d_ctr);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
+    if (c->h_hist) (void)hipHostFree(c->h_hist);
     if (c->d_ref) (void)hipFree(c->d_ref);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -362,6 +471,8 @@ int amp_set_primers(amp_ctx *c, const int32_t *mn, const int32_t *mx, int32_t ma
 
 int amp_set_params(amp_ctx *c, int32_t min_quality, int32_t window, int32_t do_trim, int32_t do_count) {
     if (!c || min_quality < 0 || window < 1) return AMP_EINVAL;  // A:841-844
+    // (new values: the passes so far say nothing about the lists of the next one)
+    if (c->min_quality != min_quality || c->window != window || c->do_trim != (do_trim != 0) || c->do_count != (do_count != 0)) c->hist_from = c->epoch + 1;
     c->min_quality = min_quality; c->window = window; c->do_trim = do_trim != 0; c->do_count = do_count != 0;
     return AMP_OK;
 }
@@ -370,6 +481,7 @@ int amp_set_params(amp_ctx *c, int32_t min_quality, int32_t window, int32_t do_t
 // generations) + the general pass
 int amp_set_kernel_variant(amp_ctx *c, int variant) {
     if (!c || variant < 0 || variant > 7) return AMP_EINVAL;
+    if (c->kernel_variant != variant) c->hist_from = c->epoch + 1;
     c->kernel_variant = variant;
     return AMP_OK;
 }
@@ -386,7 +498,20 @@ int amp_last_kernel_variant(amp_ctx *c) {
 
 int amp_set_cu_share(amp_ctx *c, int divisor) {
     if (!c || divisor < 1 || divisor > 16) return AMP_EINVAL;
+    if (c->cu_share != divisor) c->hist_from = c->epoch + 1;
     c->cu_share = divisor;
+    return AMP_OK;
+}
+
+int amp_debug_second_grids(amp_ctx *c, int gen_blocks, int heavy_blocks) {
+    if (!c || gen_blocks < 0 || heavy_blocks < 0) return AMP_EINVAL;
+    c->force_gen_blocks = gen_blocks; c->force_heavy_blocks = heavy_blocks;
+    return AMP_OK;
+}
+
+int amp_debug_last_second_grids(amp_ctx *c, int *gen_blocks, int *heavy_blocks) {
+    if (!c || !gen_blocks || !heavy_blocks) return AMP_EINVAL;
+    *gen_blocks = c->last_gen_blocks; *heavy_blocks = c->last_heavy_blocks;
     return AMP_OK;
 }
 
@@ -627,7 +752,7 @@ int amp_reset(amp_ctx *c) {
     // one small kernel for the table and the counters (two hipMemsetAsync calls are three fill kernels of 5 us each)
     const size_t words = (size_t)c->ref_len * AMP_DEV_COLS;
     constexpr size_t ctr_words = 2 * CTR_WORDS;      // the 64-bit counters as the 32-bit words k_reset writes
-    k_reset<<<(unsigned)((words + ctr_words + 1023) / 1024), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, ctr_words);
+    k_reset<<<std::min<unsigned>(RESET_BLOCKS, (unsigned)((words + ctr_words + 1023) / 1024)), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, ctr_words);
     HIPCHK(c, hipGetLastError());
     for (int k = 0; k < N_HOOKS; ++k) {        // (... and the tables of every hook that has some, on or off)
         if (!c->hooks[k].state) continue;
@@ -725,11 +850,23 @@ static int call_compact_enqueue(amp_ctx *c, const amp_call_params *pr, bool pinn
         hz = base + L.off_img;
         if (c->h_img.size() < L.img_size) c->h_img.resize(L.img_size);
     }
-    k_call<<<L.nblk, 256, 0, c->stream>>>(c->d_counts, c->d_ins_at, c->d_ref, G, *pr, d_pc, nullptr, (uint2 *)(base + L.off_blk));
-    HIPCHK(c, hipGetLastError());
-    k_call_compact<<<L.nblk, 256, 0, c->stream>>>(d_pc, c->d_counts, G, (const uint2 *)(base + L.off_blk), (int8_t *)(hz + L.img_cons),
-                                                  (amp_var_rec *)(hz + L.img_vars), (int32_t *)(hz + L.img_rel), (unsigned long long *)hz);
-    HIPCHK(c, hipGetLastError());
+    if (pinned) {
+        // one launch (k_call_fused); its flags are zero from the allocation on: every launch leaves them so
+        const size_t sync_bytes = ((size_t)CALL_SYNC_FLAG0 + L.nblk) * sizeof(unsigned long long);
+        if (c->call_sync.cap < sync_bytes) {
+            HIPCHK(c, c->call_sync.ensure(sync_bytes));
+            HIPCHK(c, hipMemsetAsync(c->call_sync.p, 0, c->call_sync.cap, c->stream));
+        }
+        k_call_fused<<<L.nblk, 256, 0, c->stream>>>(c->d_counts, c->d_ins_at, c->d_ref, G, *pr, (int8_t *)(hz + L.img_cons), (amp_var_rec *)(hz + L.img_vars),
+                                                    (int32_t *)(hz + L.img_rel), (unsigned long long *)hz, c->call_sync.as<unsigned long long>());
+        HIPCHK(c, hipGetLastError());
+    } else {
+        k_call<<<L.nblk, 256, 0, c->stream>>>(c->d_counts, c->d_ins_at, c->d_ref, G, *pr, d_pc, nullptr, (uint2 *)(base + L.off_blk));
+        HIPCHK(c, hipGetLastError());
+        k_call_compact<<<L.nblk, 256, 0, c->stream>>>(d_pc, c->d_counts, G, (const uint2 *)(base + L.off_blk), (int8_t *)(hz + L.img_cons),
+                                                      (amp_var_rec *)(hz + L.img_vars), (int32_t *)(hz + L.img_rel), (unsigned long long *)hz);
+        HIPCHK(c, hipGetLastError());
+    }
     if (!pinned) HIPCHK(c, hipMemcpyAsync(c->h_img.data(), hz, L.img_size, hipMemcpyDeviceToHost, c->stream));
     c->img_pinned = pinned;
     HIPCHK(c, hipEventRecord(c->ev_call, c->stream));     // "the image has arrived"
@@ -762,6 +899,11 @@ int amp_call_compact_view(amp_ctx *c, const amp_call_params *pr, amp_call_view *
     amp_var_rec *h_vars = (amp_var_rec *)(hp + L.img_vars);
     int32_t *h_rel = (int32_t *)(hp + L.img_rel);
     HIPCHK(c, hipEventSynchronize(c->ev_call));
+    if (c->img_pinned && h_nn[2] != 0ull) {
+        // (a launch that lost a block may not have left its ticket and flags zero: clear them for the next one)
+        if (c->call_sync.p) HIPCHK(c, hipMemsetAsync(c->call_sync.p, 0, c->call_sync.cap, c->stream));
+        snprintf(c->err, sizeof(c->err), "the calling kernel gave up waiting for one of its blocks"); return AMP_EHIP;
+    }
     const int64_t nv = (int64_t)h_nn[0], nr = (int64_t)h_nn[1];
     *view = amp_call_view{h_cons, h_vars, h_rel, nv, nr};
     return AMP_OK;

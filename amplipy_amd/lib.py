@@ -26,7 +26,7 @@ EXPORTS = [
     "amp_process_batch_device", "amp_sync", "amp_last_kernel_ms", "amp_get_counts", "amp_add_counts",
     "amp_get_ins_events", "amp_counts_device_ptr", "amp_reduce", "amp_reset", "amp_error_reads",
     "amp_reserve_events", "amp_set_kernel_variant", "amp_set_reference", "amp_call_positions",
-    "amp_event_strings", "amp_debug_counters", "amp_call_compact", "amp_debug_blocks", "amp_call_compact_view", "amp_set_timing", "amp_call_compact_begin", "amp_coordinate_helpers", "amp_drain_ins_events", "amp_set_cu_share",
+    "amp_event_strings", "amp_debug_counters", "amp_call_compact", "amp_debug_blocks", "amp_call_compact_view", "amp_set_timing", "amp_call_compact_begin", "amp_coordinate_helpers", "amp_drain_ins_events", "amp_set_cu_share", "amp_debug_second_grids", "amp_debug_last_second_grids",
     "amp_aggregate_ins_events", "amp_fast_path_active", "amp_last_kernel_variant",
     "amp_deflate_blocks", "amp_deflate_blocks_device", "amp_deflate_blocks_device_counted", "amp_deflate_sync", "amp_deflate_blocks_cb",
     "amp_sam_create", "amp_sam_destroy", "amp_sam_set_references", "amp_sam_parse", "amp_sam_reads", "amp_sam_batch_to_host",
@@ -163,6 +163,16 @@ class Engine:
     def set_cu_share(self, divisor):
         """The fast kernel's grid for 1 / divisor of the CUs: for several engines in flight on different streams."""
         self._chk(self.L.amp_set_cu_share(self.h, C.c_int(divisor)), "amp_set_cu_share")
+
+    def debug_second_grids(self, gen_blocks=0, heavy_blocks=0):
+        """Development aid: blocks of the general pass / the heavy pass behind a fast kernel (0 = predicted from the last pass)."""
+        self._chk(self.L.amp_debug_second_grids(self.h, C.c_int(gen_blocks), C.c_int(heavy_blocks)), "amp_debug_second_grids")
+
+    def debug_last_second_grids(self):
+        """(blocks of the general pass, blocks of the heavy pass) of the last pass behind a fast kernel."""
+        a, b = C.c_int(0), C.c_int(0)
+        self._chk(self.L.amp_debug_last_second_grids(self.h, C.byref(a), C.byref(b)), "amp_debug_last_second_grids")
+        return int(a.value), int(b.value)
 
     def set_stream(self, hip_stream):
         self._chk(self.L.amp_ctx_set_stream(self.h, C.c_void_p(hip_stream)), "amp_ctx_set_stream")

@@ -246,6 +246,12 @@ int amp_debug_counters(amp_ctx *ctx, uint64_t *out16);
 /* Development aid (AMPLIHIP_PHASES bit 0x100): per tile-kernel block {cycles, window rebases,
  * quality-scan chunks, counting chunks} of the last launch. */
 int amp_debug_blocks(amp_ctx *ctx, uint32_t *out, int cap_blocks, int *n_blocks);
+/* Development aid (tests/test_gpu_general_grid.py; no part of the interface a caller builds on): launch the general pass / the
+ * heavy pass behind a fast kernel with so many blocks, at most their full grids; 0 = by the rule at amp_set_cu_share.  Results
+ * do not depend on it. */
+int amp_debug_second_grids(amp_ctx *ctx, int gen_blocks, int heavy_blocks);
+/* ... and the blocks the two were launched with in the ctx's last pass behind a fast kernel (0 before the first). */
+int amp_debug_last_second_grids(amp_ctx *ctx, int *gen_blocks, int *heavy_blocks);
 /* Pre-size the insertion-event buffer.  Without it every amp_process_batch* call first runs
  * a small bound kernel and synchronises to size the buffer; with it the call is fully
  * asynchronous and amp_get_ins_events reports AMP_EOVERFLOW if the reservation was short.
@@ -277,7 +283,16 @@ int amp_last_kernel_variant(amp_ctx *ctx);
  * several batches in flight on different streams (one ctx each): two passes side by side on half the chip each finish
  * sooner than one after the other on all of it -- a block then works twice as long, so its start-up, its flush and the idle
  * end of its last round of tiles weigh half as much (bench.py: 0.224 -> 0.212 ms per 2 M-read step with divisor 2, eight
- * steps in flight).  A pass that runs alone should keep the default.  Results do not depend on it. */
+ * steps in flight).  A pass that runs alone should keep the default.  Results do not depend on it.
+ * The two kernels behind a fast kernel (the general pass over the reads it hands over, the heavy pass over the reads that one
+ * defers) are launched with as many blocks as the ctx's previous pass would have kept busy, times two, between 8 and their full
+ * grids for the ctx's share of the CUs: in most batches of an amplicon run both find nothing to do, and every block of an idle
+ * launch still waits for a CU that no fast-kernel block of another ctx holds.  A batch with far more such reads than the one
+ * before runs correctly on the small grid (a block walks several list segments), only slower; the pass after it gets the large
+ * one.  "Previous" is the last pass that had finished when the next one was launched (nothing waits for it: with passes in
+ * flight the two block counts depend on the host's timing, the results never do).  The ctx's first pass, the first pass behind a
+ * call of amp_set_params, amp_set_kernel_variant or amp_set_cu_share that changed a value, and the pass behind one that took no
+ * fast kernel take the full grids. */
 int amp_set_cu_share(amp_ctx *ctx, int divisor);
 
 /* ---- calling: alleles_from_counts (AmpliPy.py:756-771) + the loop AmpliPy.py:917-952 --------
