@@ -78,6 +78,12 @@ AMPLICON_MAX_CELLS = 1 << 22   # span positions of all amplicons together; more 
 CODON_CELLS = 65               # the 64 triplets (16 b0 + 4 b1 + b2, A C G T as 0 1 2 3), then broken
 CODON_MAX_SLOTS = 1 << 20      # more is refused with AMP_EINVAL
 
+# ---- deletion events (amp_del_*): amp_del_event[used], amp_del_info ----
+DEL_LOG2_DEFAULT, DEL_LOG2_MIN, DEL_LOG2_MAX = 20, 4, 28       # slots of the device table (16 bytes each): 0 asks for the default
+DEL_EVENT_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("count", "<u4"), ("rev", "<u4")])
+DEL_INFO_FIELDS = ("used", "capacity", "lost")                  # amp_del_info, uint64 each
+assert DEL_EVENT_DTYPE.itemsize == 16
+
 # ---- QC report (amp_qc_*) ----
 QC_MAX_DEPTHS = 4
 

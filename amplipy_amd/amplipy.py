@@ -16,7 +16,7 @@ from os.path import isfile
 
 import numpy as np
 
-from . import AMPLIPY_VERSION, amplicon as amplicon_mod, calling, codon as codon_mod, lib, parallel, qc, strand as strand_mod
+from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, deletion as deletion_mod, lib, parallel, qc, strand as strand_mod
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -80,9 +80,10 @@ def open_device_bam_text(input_fn, output_fn):
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
-    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False):
+    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False):
         """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables);
-        amplicon: likewise the seven keys of --amplicons, behind them; codon: likewise the five keys of --codons, last."""
+        amplicon: likewise the seven keys of --amplicons, behind them; codon: likewise the five keys of --codons; deletion:
+        likewise the two keys of --deletions, last."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -111,16 +112,18 @@ class VcfWriter:
             w(amplicon_mod.HEADER_LINES)
         if codon:
             w(codon_mod.HEADER_LINES)
+        if deletion:
+            w(deletion_mod.HEADER_LINES)
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
-    def line(self, r, strand=None, amplicon=None, codon=None):
-        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon)
+    def line(self, r, strand=None, amplicon=None, codon=None, deletion=None):
+        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon, deletion)
 
-    def write(self, r, strand=None, amplicon=None, codon=None):
-        self.f.write(self.line(r, strand, amplicon, codon))
+    def write(self, r, strand=None, amplicon=None, codon=None, deletion=None):
+        self.f.write(self.line(r, strand, amplicon, codon, deletion))
 
-    def write_all(self, records, strand=None, amplicon=None, codon=None):
-        self.f.write("".join([self.line(r, strand, amplicon, codon) for r in records]))
+    def write_all(self, records, strand=None, amplicon=None, codon=None, deletion=None):
+        self.f.write("".join([self.line(r, strand, amplicon, codon, deletion) for r in records]))
 
     def close(self):
         if self.f is not sys.stdout:
@@ -133,7 +136,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 unknown_symbol=None, include_no_primer=None, run_trim=False, run_variants=False, run_consensus=False,
                 device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None, qc_fn=None, qc_regions_fn=None, qc_depths=None,
                 qc_depth_fn=None, strand=False, strand_fn=None, amplicons_fn=None, amplicon_out_fn=None, codons_fn=None,
-                codon_out_fn=None, aa_out_fn=None):
+                codon_out_fn=None, aa_out_fn=None, deletions=False, del_out_fn=None, indel_vcf_fn=None, del_capacity=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -164,6 +167,12 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     read in the three positions of every codon, and every VCF record also carries CDS, CODON_DP, ALT_AA, ALT_CODON and
     ALT_CODON_DP.  codon_out_fn: the codon table as a TSV file; aa_out_fn (runs that call variants): the amino-acid changes at or
     above the variant thresholds.  With codons_fn None the engine's hook is never switched on.
+    deletions (default: off; runs that write a VCF): the device tallies, behind every batch's read pass, deletions as whole
+    events -- the positions ONE read skipped together, with the reads and the reverse reads that carry each (DESIGN.md section
+    19) -- and every VCF record also carries DEL_N and DEL.  del_out_fn: every event as a TSV file (runs with a count table);
+    indel_vcf_fn (runs that call variants): a second, spec-valid VCF of anchored indels -- the events and the call's insertion
+    alleles at or above the variant thresholds.  del_capacity: log2 of the device table's slots (default 20).  Reads of events
+    the table had no slot for end the run with an error.  With the first three off the engine's hook is never switched on.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -213,6 +222,19 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("A run that only trims has no count table: no codon tallies (--codons, --codon_out, --aa_out)")
     if aa_out_fn is not None and not run_variants:
         error("The amino-acid calls (--aa_out) use the variant thresholds: variants or aio")
+    del_on = bool(deletions) or del_out_fn is not None or indel_vcf_fn is not None
+    if del_on and not (run_variants or run_consensus):
+        error("A run that only trims has no count table: no deletion events (--deletions, --del_out, --indel_vcf)")
+    if deletions and not run_variants:
+        error("The deletion INFO keys need a VCF (--deletions on variants or aio)")
+    if indel_vcf_fn is not None and not run_variants:
+        error("The indel VCF (--indel_vcf) uses the variant thresholds: variants or aio")
+    if del_capacity is not None and not del_on:
+        error("The deletion events' table size (--del_capacity) needs --deletions, --del_out or --indel_vcf")
+    if del_capacity is not None and not abi.DEL_LOG2_MIN <= del_capacity <= abi.DEL_LOG2_MAX:
+        error("--del_capacity is the log2 of the table's slots, %d to %d: %s" % (abi.DEL_LOG2_MIN, abi.DEL_LOG2_MAX, del_capacity))
+    if indel_vcf_fn is not None and not indel_vcf_fn.lower().endswith((".vcf", ".vcf.gz")):
+        error("Invalid indel VCF extension (should be .vcf or .vcf.gz): %s" % indel_vcf_fn)
     strand_on = bool(strand) or strand_fn is not None
     qc_on = qc_fn is not None or qc_depth_fn is not None
     if qc_on:
@@ -255,7 +277,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = None
+    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = None
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
@@ -271,11 +293,14 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(route.note)
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
-            vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None, codon=codons_fn is not None)
+            vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None, codon=codons_fn is not None, deletion=bool(deletions))
             if amplicon_out_fn is not None:
                 amp_file = qc.open_new(amplicon_out_fn)
         if strand_fn is not None and rank == 0:
             strand_file = qc.open_new(strand_fn)
+        if del_on and rank == 0:
+            del_file = qc.open_new(del_out_fn) if del_out_fn is not None else None
+            indel_file = qc.open_new(indel_vcf_fn) if indel_vcf_fn is not None else None
         if amplicons_fn is not None:
             print_log("Loading amplicons: %s" % amplicons_fn)
             amps = amplicon_mod.load_amplicons(amplicons_fn, qc.load_primer_rows(primer_fn), primer_pos_offset or 0, G)
@@ -308,6 +333,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         amplicon_mod.enable(eng, amps)
     if cds is not None and rank_error is None:
         codon_mod.enable(eng, cds)
+    if del_on and rank_error is None:
+        eng.del_enable(del_capacity or 0)
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -341,6 +368,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             amp_read_parts = parallel.gather_objects(dist, rank, world, eng.amplicon_tables()[1])
         if cds is not None:              # ... and every rank's tallied and skipped reads
             codon_read_parts = parallel.gather_objects(dist, rank, world, eng.codon_tables()[1])
+        if del_on:                       # ... and every rank's events: rank 0 sums them per key on the host
+            del_parts = parallel.gather_objects(dist, rank, world, eng.del_events())
         if final_trimmed_fn is not None and driver.part_writer is not None:
             # the ranks' files (all closed by now: the writer threads were joined in run()) become the one trimmed BAM
             parts = parallel.gather_objects(dist, rank, world, (driver.part_writer.path, driver.part_writer.header_bytes))
@@ -354,6 +383,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     failed = True
     try:
         qc_depth = qc_region_recs = None
+        del_lost = 0
         if qc_on and rank == 0:
             qc_tallies = qc.merge_read_tallies(qc_parts) if dist is not None else eng.qc_read_tallies()
         if do_count:
@@ -404,6 +434,18 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                         c_reads = np.sum([np.asarray(part, np.uint64) for part in codon_read_parts], axis=0, dtype=np.uint64)
                 if rank == 0:
                     codon_tables = codon_mod.Tables(cds, ref_seq, c_codon, c_reads, v_min_depth, v_min_freq)
+            del_tables = None
+            if del_on:
+                if dist is None:
+                    d_events, d_info = eng.del_events()
+                    del_lost = d_info["lost"]
+                elif rank == 0:
+                    d_events = deletion_mod.merge_events([part[0] for part in del_parts])
+                    del_lost = sum(part[1]["lost"] for part in del_parts)
+                else:
+                    del_lost = eng.del_events()[1]["lost"]
+                if rank == 0:
+                    del_tables = deletion_mod.Tables(d_events, eng.counts(), ref_seq, v_min_depth, v_min_freq)
 
             def ins_tallies(positions):
                 triples = loop.ins_store.counted_pairs(positions)
@@ -414,8 +456,15 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if rank != 0:
                 run_variants = run_consensus = False       # rank 0 writes the outputs
             if run_variants:
-                vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables, codon_tables))        # (= vcf.write(r) for r in res.records)
+                vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables, codon_tables,
+                                         del_tables if deletions else None))        # (= vcf.write(r) for r in res.records)
                 vcf.close()
+            if indel_file is not None:
+                deletion_mod.write_indel_vcf(indel_file, ref_id, del_tables, deletion_mod.insertion_rows(res.records), " ".join(sys.argv))
+                print_log("Output indel VCF: %s" % indel_vcf_fn)
+            if del_file is not None:
+                deletion_mod.write_tsv(del_file, ref_id, del_tables)
+                print_log("Output deletion events: %s" % del_out_fn)
             if run_consensus:
                 f = gzip.open(consensus_fn, "wt") if consensus_fn.lower().endswith(".gz") else open(consensus_fn, "w")
                 f.write(">sample\n%s\n" % res.consensus_string(unknown_symbol))
@@ -450,9 +499,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(amp_tables.summary_line())
         if cds is not None and rank == 0:
             print_log(codon_tables.summary_line())
+        if del_on:
+            deletion_mod.check_lost(del_lost)              # (behind the run's last collective: no rank is left waiting)
         failed = False
     finally:
-        for f in qc_files + [strand_file, amp_file, codon_file, aa_file]:
+        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file]:
             if f is not None:
                 f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)
@@ -533,6 +584,10 @@ def parse_args(argv=None):
         p.add_argument("--codons", required=False, type=str, default=None, help="CDS file (TSV: name, start, end[, strand]; 0-based, half-open): codon tallies within single reads on the device, and CDS, CODON_DP, ALT_AA, ALT_CODON and ALT_CODON_DP on every VCF record (variants, consensus, aio)")
         p.add_argument("--codon_out", required=False, type=str, default=None, help="Count of every codon seen on single reads, per CDS row and codon (TSV or TSV.gz; needs --codons)")
         p.add_argument("--aa_out", required=False, type=str, default=None, help="Amino-acid changes at or above the variant thresholds, per CDS row and codon (TSV or TSV.gz; variants, aio; needs --codons)")
+        p.add_argument("--deletions", action="store_true", help="Deletions tallied as whole events on the device; VCF records also carry DEL_N and DEL: the events that cover the position (variants, aio)")
+        p.add_argument("--del_out", required=False, type=str, default=None, help="Every deletion event: start, length, reads, reverse reads, depth, frequency, deleted text (TSV or TSV.gz; variants, consensus, aio)")
+        p.add_argument("--indel_vcf", required=False, type=str, default=None, help="A second VCF of anchored indels: deletion events and insertion alleles at or above the variant thresholds (VCF or VCF.gz; variants, aio)")
+        p.add_argument("--del_capacity", required=False, type=int, default=None, help="log2 of the slots of the deletion events' table on the device, 4 to 28 (20 when omitted)")
         p.add_argument("--strand_out", required=False, type=str, default=None, help="Count, reverse-strand count and quality sum of every position and symbol (TSV or TSV.gz; variants, consensus, aio)")
     return parser.parse_args(argv)
 
@@ -544,7 +599,8 @@ def main(argv=None):
     qc_args = dict(qc_fn=args.qc, qc_regions_fn=args.qc_regions, qc_depth_fn=args.qc_depth_out,
                    qc_depths=qc.parse_depths(args.qc_depths) if args.qc_depths is not None else None)
     qc_args.update(strand=args.strand, strand_fn=args.strand_out, amplicons_fn=args.amplicons, amplicon_out_fn=args.amplicon_out,
-                   codons_fn=args.codons, codon_out_fn=args.codon_out, aa_out_fn=args.aa_out)
+                   codons_fn=args.codons, codon_out_fn=args.codon_out, aa_out_fn=args.aa_out, deletions=args.deletions,
+                   del_out_fn=args.del_out, indel_vcf_fn=args.indel_vcf, del_capacity=args.del_capacity)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,

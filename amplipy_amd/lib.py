@@ -41,6 +41,7 @@ EXPORTS = [
     "amp_strand_enable", "amp_strand_get", "amp_strand_add", "amp_strand_last_ms",
     "amp_amplicon_enable", "amp_amplicon_get", "amp_amplicon_add", "amp_amplicon_last_ms",
     "amp_codon_enable", "amp_codon_get", "amp_codon_add", "amp_codon_last_ms",
+    "amp_del_enable", "amp_del_get", "amp_del_add", "amp_del_last_ms",
 ]
 
 
@@ -409,6 +410,35 @@ class Engine:
 
     def codon_last_ms(self):
         return self._hook_last_ms("amp_codon_last_ms")
+
+    # ---- deletion events ---------------------------------------------------------------
+    def del_enable(self, log2_capacity=0):
+        """amp_del_enable: the hook on, the table zero, 2^log2_capacity slots (0: the default).
+        ``del_disable`` turns it off; the table stays readable."""
+        self._chk(self.L.amp_del_enable(self.h, C.c_int(1), C.c_int(int(log2_capacity))), "amp_del_enable")
+
+    def del_disable(self):
+        self._chk(self.L.amp_del_enable(self.h, C.c_int(0), C.c_int(0)), "amp_del_enable")
+
+    def del_events(self):
+        """amp_del_get -> (abi.DEL_EVENT_DTYPE[used] ordered by (start, len), {"used", "capacity", "lost"})."""
+        n = C.c_int64(0)
+        info = np.zeros(len(abi.DEL_INFO_FIELDS), np.uint64)
+        rc = self.L.amp_del_get(self.h, None, C.c_int64(0), C.byref(n), C.c_void_p(abi.ptr(info)))
+        ev = np.zeros(max(int(n.value), 1), abi.DEL_EVENT_DTYPE)
+        if rc == -1 and n.value > 0:            # (AMP_EINVAL with the needed size: the table is not empty)
+            rc = self.L.amp_del_get(self.h, C.c_void_p(abi.ptr(ev)), C.c_int64(ev.size), C.byref(n), C.c_void_p(abi.ptr(info)))
+        self._chk(rc, "amp_del_get")
+        return ev[:int(n.value)], {k: int(v) for k, v in zip(abi.DEL_INFO_FIELDS, info)}
+
+    def del_add(self, events):
+        """amp_del_add: host entries (abi.DEL_EVENT_DTYPE) through the kernel's insert path (the merge of partial tables)."""
+        ev = np.ascontiguousarray(events, abi.DEL_EVENT_DTYPE)
+        if ev.size:
+            self._chk(self.L.amp_del_add(self.h, C.c_void_p(abi.ptr(ev)), C.c_int64(ev.size)), "amp_del_add")
+
+    def del_last_ms(self):
+        return self._hook_last_ms("amp_del_last_ms")
 
     # ---- calling ---------------------------------------------------------------------
     def set_reference(self, ref_seq):

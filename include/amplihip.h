@@ -776,6 +776,39 @@ int amp_codon_add(amp_ctx *ctx, const uint32_t *codon, const uint64_t *reads);
 /* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_codon_last_ms(amp_ctx *ctx, float *ms);
 
+/* ---- deletion events (opt-in) ---------------------------------------------------------------------------------
+ * The count table records a deleted base as one more '-' at one position (update_base_counts, AmpliPy.py:713-715): that one read
+ * skipped several positions TOGETHER is lost there.  For a read with status 0, as it was counted (the trimmed alignment with
+ * do_trim), an event is a maximal run of consecutive reference positions each of which the read's count walk adds to the '-' column
+ * (AmpliPy.py:713-715): key (start, len), start 0-based, len >= 1.  D and N ops are alike; neighbouring D / N ops, and D / N ops
+ * with only an insertion between them, are one event; a deletion that runs past the reference end is cut where the walk stops.  Per
+ * key the table holds count (reads) and rev (those whose FLAG has 0x10), so that for every position p the counts of the events
+ * with start <= p < start + len add up to counts[p]['-'] and their rev to rev[p][5] of the strand tallies.  The table is an
+ * open-addressed hash table on the device that persists across batches; an event that finds no slot (every probe loop is
+ * bounded) adds its reads to `lost` and is dropped -- never merged into another key.  amp_reset zeroes the table. */
+typedef struct amp_del_event {
+    int32_t start, len;         /* 0-based first deleted position, deleted positions */
+    uint32_t count, rev;        /* reads that carry the event, those of them on the reverse strand */
+} amp_del_event;
+typedef struct amp_del_info {
+    uint64_t used;              /* distinct events the table holds */
+    uint64_t capacity;          /* its slots */
+    uint64_t lost;              /* reads of events that found no slot */
+} amp_del_info;
+/* on != 0: the hook on, the table zero; 2^log2_capacity slots of 16 bytes (0: the default, 20; else 4 to 28, AMP_EINVAL
+ * otherwise), laid out again only when the capacity changed.  on == 0: off; the table stays readable.  With the hook on and
+ * do_trim set, amp_process_batch_device refuses a dev_out without new_pos, new_ncig, new_cig or status (AMP_EINVAL) before
+ * anything runs. */
+int amp_del_enable(amp_ctx *ctx, int on, int log2_capacity);
+/* The used entries as they stand (waits for the stream), compacted on the device, ordered by (start, len); *n: their number.
+ * AMP_EINVAL, with the needed size in *n, when cap is smaller (info is filled in either way); AMP_ESTATE before the first enable.
+ * n and info may be NULL, entries when cap is 0. */
+int amp_del_get(amp_ctx *ctx, amp_del_event *entries, int64_t cap, int64_t *n, amp_del_info *info);
+/* Host entries inserted through the kernel's own insert path (the merge of partial tables): a call per job, not per batch. */
+int amp_del_add(amp_ctx *ctx, const amp_del_event *entries, int64_t n);
+/* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+int amp_del_last_ms(amp_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
