@@ -848,10 +848,12 @@ k_fast(F_ARGS F_DBG_PARAM) {
         uint32_t ncig = 0, cw[5] = {0u, 0u, 0u, 0u, 0u};
         int32_t reflen = 0;
         if (shaped) {
-            // the read's first quality byte (0xFF = QUAL '*') is byte phi of piece 0, which sits in slot (np - rot) mod np
+            // the read's first quality byte (0xFF = QUAL '*') is byte phi of piece 0, which sits in slot (np - rot) mod np: slot 0
+            // when rot is 0 (slot np holds a copy of the LAST piece then, not piece 0)
             uint32_t fb = phi ? q16[0].z : q16[0].x;
+            const uint32_t slot0 = rot ? np - rot : 0u;
 #pragma unroll
-            for (int k = 1; k < F_NP; ++k) fb = ((uint32_t)k + rot == np) ? (phi ? q16[k].z : q16[k].x) : fb;
+            for (int k = 1; k < F_NP; ++k) fb = ((uint32_t)k == slot0) ? (phi ? q16[k].z : q16[k].x) : fb;
             if ((fb & 0xFFu) == 0xFFu || s.punt) {
                 general = true;                   // QUAL '*': the generic code reports it (A:561-562, A:718); a shape the closed forms leave
             } else {
