@@ -576,6 +576,31 @@ extern "C" int ampdf_hostsim_blocks(const uint8_t *in, int64_t n_bytes, int32_t 
     host_deflate(Args{in, n_bytes, block_bytes, out, out_stride, out_room, out_len, tokens}, (n_bytes + block_bytes - 1) / block_bytes);
     return AMP_OK;
 }
+// the code lengths the phases give an alphabet of n symbols with these frequencies: max_bits 7 as phases 10 and 11 build the
+// code-length code (build_lengths from the frequencies as they are), max_bits 15 as phases 5 to 8 build the other two (merge_tree,
+// every leaf's walk, and build_lengths from halved frequencies only when a leaf is deeper than 15).  For tests/test_deflate_enc_craft.py:
+// frequencies that no chunk gives reach the limits here.
+extern "C" int ampdf_hostsim_lengths(const uint32_t *freq, int n, int max_bits, uint8_t *len) {
+    using namespace ampdf;
+    if (!freq || !len || n < 2 || n > 286 || (max_bits != 7 && max_bits != 15) || (max_bits == 7 && n > NC)) return AMP_EINVAL;
+    static uint32_t weight[2 * NL];
+    static uint16_t parent[2 * NL], order[NL];
+    static uint8_t depth[2 * NL];
+    uint32_t used = 0;
+    for (int i = 0; i < n; ++i) len[i] = 0;
+    for (int i = 0; i < n; ++i) rank_symbol(freq, n, i, order, weight, &used);
+    if (used < 2) return AMP_EINVAL;
+    if (max_bits == 7) { build_lengths(freq, order, (int)used, 7, 0, weight, parent, depth, len); return AMP_OK; }
+    merge_tree((int)used, weight, parent);
+    bool deep = false;
+    for (int i = 0; i < (int)used; ++i) {
+        const int dl = leaf_depth((int)used, parent, i);
+        len[order[i]] = (uint8_t)dl;
+        deep = deep || dl > 15;
+    }
+    if (deep) build_lengths(freq, order, (int)used, 15, 1, weight, parent, depth, len);
+    return AMP_OK;
+}
 namespace ampdf {
 #endif
 

@@ -443,13 +443,8 @@ def test_hook_can_be_taken_out_again(tmp_path, scheme):
 def test_encoder_phases_on_the_host(tmp_path, scheme):
     """amp_deflate.hip's phase functions compile for the host too (-DAMPDF_HOSTSIM: thread after thread, phase after phase): the
     streams they give there pass the block-level checks, so the encoder's logic is tested where there is no GPU."""
-    import shutil
-    from amplipy_amd import build
-    so = str(tmp_path / "libampdf_hostsim.so")
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-Wno-unused-function", "-DAMPDF_HOSTSIM",
-                           "-o", so, os.path.join(build.CSRC, "amp_deflate.hip")])
-    sim = C.CDLL(so)
+    from tests.deflate_enc_craft import hostsim_library
+    sim = hostsim_library()
     path, _ = _synthetic_bam(tmp_path, scheme, 6000, level=1)
     image = gzip.open(path).read()
     cases = [(image, BS), (image[5:300000], 12345), (bytes(2 * BS + 17), BS), (b"Q", BS), (_fibonacci_bytes(), BS), (os.urandom(70000), BS),
@@ -468,14 +463,9 @@ def test_encoder_phases_on_the_host(tmp_path, scheme):
 @pytest.mark.gpu
 def test_device_streams_are_the_host_phases_streams(tmp_path, bam_image):
     """... and the device gives exactly those streams: nothing in them depends on how the threads were scheduled."""
-    import shutil
-    from amplipy_amd import build
-    so = str(tmp_path / "libampdf_hostsim.so")
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-Wno-unused-function", "-DAMPDF_HOSTSIM",
-                           "-o", so, os.path.join(build.CSRC, "amp_deflate.hip")])
+    from tests.deflate_enc_craft import hostsim_library
     data = bam_image[:40 * BS + 321]
-    assert _deflate_blocks(data)[1] == _deflate_blocks(data, hostsim=C.CDLL(so))[1]
+    assert _deflate_blocks(data)[1] == _deflate_blocks(data, hostsim=hostsim_library())[1]
 
 
 # ---- 6. size -------------------------------------------------------------------------------------------------------------------------
