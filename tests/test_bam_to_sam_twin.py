@@ -254,31 +254,48 @@ def float_patterns(n, seed):
     return all_
 
 
-def test_floats_equal_percent_g(twin, tmp_path):
-    """100,000 seeded in-set bit patterns, 100 per binary exponent, the neighbours of 1e-4, 1e6, 999999.5, 2^62 and 2^63, both
-    zeros: carried in B:f arrays (and a few as f fields), compared with '%g' through the Python codec."""
-    bits = float_patterns(100000, 7)
-    assert bits.size >= 100000
+def float_carrier_recs(bits):
+    """Records that carry the bit patterns 2,000 each in a B:f array (and the first twenty of each as f fields)."""
     recs = []
     for k in range(0, bits.size, 2000):
         chunk = bits[k:k + 2000]
         aux = b"flB" + b"f" + struct.pack("<I", chunk.size) + chunk.astype("<u4").tobytes() + b"".join(b"f%cf" % (65 + j) + chunk[j:j + 1].astype("<u4").tobytes()
                                                                                                       for j in range(min(20, chunk.size)))
         recs.append(bamio.Rec("f%d" % k, 0, 0, 10, 60, [(0, 4)], -1, -1, 0, "ACGT", bytes([30] * 4), aux_bam=aux))
-    path = write_raw(str(tmp_path / "floats.bam"), recs)
+    return recs
+
+
+def percent_g_of_arrays(text):
+    """The elements of the B:f array of every line (its first aux field, behind "fl:B:f,"), joined by commas."""
+    return b",".join(line.split(b"\t")[11][7:] for line in text.split(b"\n")[:-1])
+
+
+def test_floats_equal_percent_g(twin, tmp_path):
+    """100,000 seeded in-set bit patterns, 100 per binary exponent, the neighbours of 1e-4, 1e6, 999999.5, 2^62 and 2^63, both
+    zeros: carried in B:f arrays (and a few as f fields), compared with '%g' through the Python codec."""
+    bits = float_patterns(100000, 7)
+    assert bits.size >= 100000
+    path = write_raw(str(tmp_path / "floats.bam"), float_carrier_recs(bits))
     f = bam_device.bam_native.BamFile(path)
     want, _ = f.decode(0, f.n_records, copy=True)
     f.close()
     text = all_pieces(twin, path, identity_results(want), include_no_primer=True, pieces=(1 << 30,))
     # the comparison above is with aux_bam_to_sam; this one with '%g' itself
     vals = bits.view(np.float32)
-    got = b",".join(line.split(b"\t")[11][7:] for line in text.split(b"\n")[:-1])
-    assert got == ",".join("%g" % float(v) for v in vals).encode()
+    assert percent_g_of_arrays(text) ==",".join("%g" % float(v) for v in vals).encode()
+
+
+OUT_OF_SET_BITS = (LO_BITS - 1, HI_BITS, 0x7F800000, 0xFF800000, 0x7FC00000, 1, 0x007FFFFF, 0x00800000, 0x80000001, 0x7F7FFFFF, 0x38D1B717 | 0x80000000)
+
+
+def out_of_set_aux(b):
+    """The bit pattern as an f field, and as the second element of a B:f array."""
+    return b"xff" + struct.pack("<I", b), b"xfBf" + struct.pack("<III", 2, 0x3F800000, b)
 
 
 def test_floats_outside_the_set_are_odd(twin, tmp_path):
-    for k, b in enumerate((LO_BITS - 1, HI_BITS, 0x7F800000, 0xFF800000, 0x7FC00000, 1, 0x007FFFFF, 0x00800000, 0x80000001, 0x7F7FFFFF, 0x38D1B717 | 0x80000000)):
-        for aux in (b"xff" + struct.pack("<I", b), b"xfBf" + struct.pack("<III", 2, 0x3F800000, b)):
+    for k, b in enumerate(OUT_OF_SET_BITS):
+        for aux in out_of_set_aux(b):
             path = write_raw(str(tmp_path / ("odd_%d_%d.bam" % (k, len(aux)))), [bamio.Rec("q", 0, 0, 10, 60, [(0, 4)], -1, -1, 0, "ACGT", bytes([30] * 4), aux_bam=aux)])
             _, checks, _ = twin_text(twin, path, Results(_Empty, *[np.zeros(1, t) for t in (np.int32, np.uint32)], [np.zeros(0, np.uint32)],
                                                          np.zeros(1, np.int32), np.zeros(1, np.uint8)), 1 << 30, 30, True)

@@ -350,11 +350,12 @@ def test_corner_lines(twin):
             assert stream == expected(text, i2, 0, True), l[:60]
 
 
-def test_floats_are_packed_like_struct_pack(twin):
-    """Spellings of the exact set, seeded: the bytes of the f field are struct.pack("<f", float(v))."""
-    rng = np.random.default_rng(5)
+def float_spellings(n, seed):
+    """Spellings of the exact set, seeded: up to 15 digits with or without a point and an exponent, three in ten negative (of n
+    draws, those outside the set are left out)."""
+    rng = np.random.default_rng(seed)
     vals = []
-    for _ in range(3000):
+    for _ in range(n):
         nd = int(rng.integers(1, 16))
         digits = "".join(str(int(d)) for d in rng.integers(0, 10, nd))
         cutp = int(rng.integers(1, nd + 1))
@@ -365,7 +366,18 @@ def test_floats_are_packed_like_struct_pack(twin):
         elif not -22 <= -(nd - cutp) <= 22:
             continue
         vals.append(("-" if rng.random() < 0.3 else "") + s)
-    lines = [line("f%d" % k, aux=("XF:f:" + v, "BF:B:f," + v + "," + v)) for k, v in enumerate(vals)]
+    return vals
+
+
+def float_lines(vals):
+    """One line per spelling: as an f field and twice in a B:f array."""
+    return [line("f%d" % k, aux=("XF:f:" + v, "BF:B:f," + v + "," + v)) for k, v in enumerate(vals)]
+
+
+def test_floats_are_packed_like_struct_pack(twin):
+    """Spellings of the exact set, seeded: the bytes of the f field are struct.pack("<f", float(v))."""
+    vals = float_spellings(3000, 5)
+    lines = float_lines(vals)
     recs, pb = whole_batch(lines)
     res = identity(pb)
     stream, framed, infos = twin_run(twin, [b"".join(lines)], res, 0, True)
