@@ -84,6 +84,12 @@ DEL_EVENT_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("count", "<u4"), 
 DEL_INFO_FIELDS = ("used", "capacity", "lost")                  # amp_del_info, uint64 each
 assert DEL_EVENT_DTYPE.itemsize == 16
 
+# ---- co-occurrence of listed mutations (amp_cooc_*): cooc uint32[n_sets][COOC_CELLS], reads uint64[2] ----
+COOC_CELLS = 65                # the 64 patterns (site 0 is bit 0), then partial
+COOC_SITES = 6                 # sites of a set at most
+COOC_MAX_SETS = 1 << 16        # more is refused with AMP_EINVAL
+COOC_MAX_SPAN = 1 << 16        # last site's position minus the first site's, at most
+
 # ---- QC report (amp_qc_*) ----
 QC_MAX_DEPTHS = 4
 

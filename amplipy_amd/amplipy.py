@@ -16,7 +16,7 @@ from os.path import isfile
 
 import numpy as np
 
-from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, deletion as deletion_mod, lib, parallel, qc, strand as strand_mod
+from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, cooc as cooc_mod, deletion as deletion_mod, lib, parallel, qc, strand as strand_mod
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -80,10 +80,10 @@ def open_device_bam_text(input_fn, output_fn):
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
-    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False):
+    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False):
         """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables);
         amplicon: likewise the seven keys of --amplicons, behind them; codon: likewise the five keys of --codons; deletion:
-        likewise the two keys of --deletions, last."""
+        likewise the two keys of --deletions; cooc: likewise the key of --cooc, last."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -114,16 +114,18 @@ class VcfWriter:
             w(codon_mod.HEADER_LINES)
         if deletion:
             w(deletion_mod.HEADER_LINES)
+        if cooc:
+            w(cooc_mod.HEADER_LINES)
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
-    def line(self, r, strand=None, amplicon=None, codon=None, deletion=None):
-        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon, deletion)
+    def line(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None):
+        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon, deletion, cooc)
 
-    def write(self, r, strand=None, amplicon=None, codon=None, deletion=None):
-        self.f.write(self.line(r, strand, amplicon, codon, deletion))
+    def write(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None):
+        self.f.write(self.line(r, strand, amplicon, codon, deletion, cooc))
 
-    def write_all(self, records, strand=None, amplicon=None, codon=None, deletion=None):
-        self.f.write("".join([self.line(r, strand, amplicon, codon, deletion) for r in records]))
+    def write_all(self, records, strand=None, amplicon=None, codon=None, deletion=None, cooc=None):
+        self.f.write("".join([self.line(r, strand, amplicon, codon, deletion, cooc) for r in records]))
 
     def close(self):
         if self.f is not sys.stdout:
@@ -136,7 +138,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 unknown_symbol=None, include_no_primer=None, run_trim=False, run_variants=False, run_consensus=False,
                 device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None, qc_fn=None, qc_regions_fn=None, qc_depths=None,
                 qc_depth_fn=None, strand=False, strand_fn=None, amplicons_fn=None, amplicon_out_fn=None, codons_fn=None,
-                codon_out_fn=None, aa_out_fn=None, deletions=False, del_out_fn=None, indel_vcf_fn=None, del_capacity=None):
+                codon_out_fn=None, aa_out_fn=None, deletions=False, del_out_fn=None, indel_vcf_fn=None, del_capacity=None, cooc_fn=None,
+                cooc_out_fn=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -173,6 +176,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     indel_vcf_fn (runs that call variants): a second, spec-valid VCF of anchored indels -- the events and the call's insertion
     alleles at or above the variant thresholds.  del_capacity: log2 of the device table's slots (default 20).  Reads of events
     the table had no slot for end the run with an error.  With the first three off the engine's hook is never switched on.
+    cooc_fn (default: off; runs with a count table): the mutation-set file -- a name and a comma-separated list of mutations per
+    line, A23403G, del21765-21770 or del21991, POSITIONS 1-BASED as in the VCF.  The device tallies,
+    behind every batch's read pass, per set the reads that show all its sites by the pattern of mutations they carry, and every
+    VCF record also carries COOC.  cooc_out_fn: the pattern table as a TSV file.  With cooc_fn None the engine's hook is never
+    switched on.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -222,6 +230,10 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("A run that only trims has no count table: no codon tallies (--codons, --codon_out, --aa_out)")
     if aa_out_fn is not None and not run_variants:
         error("The amino-acid calls (--aa_out) use the variant thresholds: variants or aio")
+    if cooc_out_fn is not None and cooc_fn is None:
+        error("The co-occurrence table (--cooc_out) needs the mutation-set file (--cooc)")
+    if cooc_fn is not None and not (run_variants or run_consensus):
+        error("A run that only trims has no count table: no co-occurrence tallies (--cooc, --cooc_out)")
     del_on = bool(deletions) or del_out_fn is not None or indel_vcf_fn is not None
     if del_on and not (run_variants or run_consensus):
         error("A run that only trims has no count table: no deletion events (--deletions, --del_out, --indel_vcf)")
@@ -277,7 +289,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = None
+    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = cooc_sets = cooc_file = None
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
@@ -293,7 +305,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(route.note)
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
-            vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None, codon=codons_fn is not None, deletion=bool(deletions))
+            vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None, codon=codons_fn is not None, deletion=bool(deletions),
+                            cooc=cooc_fn is not None)
             if amplicon_out_fn is not None:
                 amp_file = qc.open_new(amplicon_out_fn)
         if strand_fn is not None and rank == 0:
@@ -310,6 +323,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if rank == 0:
                 codon_file = qc.open_new(codon_out_fn) if codon_out_fn is not None else None
                 aa_file = qc.open_new(aa_out_fn) if aa_out_fn is not None else None
+        if cooc_fn is not None:
+            print_log("Loading mutation sets: %s" % cooc_fn)
+            cooc_sets = cooc_mod.load_sets(cooc_fn, ref_seq)
+            if rank == 0:
+                cooc_file = qc.open_new(cooc_out_fn) if cooc_out_fn is not None else None
         if qc_on:
             qc_regions = [(0, G, qc.WHOLE)] + (qc.load_regions(qc_regions_fn) if qc_regions_fn is not None else [])
             qc_primers = qc.load_primer_rows(primer_fn) if run_trim else []
@@ -335,6 +353,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         codon_mod.enable(eng, cds)
     if del_on and rank_error is None:
         eng.del_enable(del_capacity or 0)
+    if cooc_sets is not None and rank_error is None:
+        cooc_mod.enable(eng, cooc_sets)
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -368,6 +388,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             amp_read_parts = parallel.gather_objects(dist, rank, world, eng.amplicon_tables()[1])
         if cds is not None:              # ... and every rank's tallied and skipped reads
             codon_read_parts = parallel.gather_objects(dist, rank, world, eng.codon_tables()[1])
+        if cooc_sets is not None:        # ... likewise for the co-occurrence tallies
+            cooc_read_parts = parallel.gather_objects(dist, rank, world, eng.cooc_tables()[1])
         if del_on:                       # ... and every rank's events: rank 0 sums them per key on the host
             del_parts = parallel.gather_objects(dist, rank, world, eng.del_events())
         if final_trimmed_fn is not None and driver.part_writer is not None:
@@ -434,6 +456,18 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                         c_reads = np.sum([np.asarray(part, np.uint64) for part in codon_read_parts], axis=0, dtype=np.uint64)
                 if rank == 0:
                     codon_tables = codon_mod.Tables(cds, ref_seq, c_codon, c_reads, v_min_depth, v_min_freq)
+            cooc_tables = None
+            if cooc_sets is not None:
+                o_cooc, o_reads = eng.cooc_tables()
+                if dist is not None:                       # one more all-reduce: the co-occurrence table
+                    import torch
+                    wire = torch.from_numpy(o_cooc.astype(np.int64).reshape(-1)).to("cuda:%d" % device)
+                    parallel.allreduce_table(dist, wire)
+                    o_cooc = wire.cpu().numpy().astype(np.uint32).reshape(-1, cooc_mod.CELLS)
+                    if rank == 0:
+                        o_reads = np.sum([np.asarray(part, np.uint64) for part in cooc_read_parts], axis=0, dtype=np.uint64)
+                if rank == 0:
+                    cooc_tables = cooc_mod.Tables(cooc_sets, o_cooc, o_reads)
             del_tables = None
             if del_on:
                 if dist is None:
@@ -457,7 +491,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 run_variants = run_consensus = False       # rank 0 writes the outputs
             if run_variants:
                 vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables, codon_tables,
-                                         del_tables if deletions else None))        # (= vcf.write(r) for r in res.records)
+                                         del_tables if deletions else None, cooc_tables))        # (= vcf.write(r) for r in res.records)
                 vcf.close()
             if indel_file is not None:
                 deletion_mod.write_indel_vcf(indel_file, ref_id, del_tables, deletion_mod.insertion_rows(res.records), " ".join(sys.argv))
@@ -481,6 +515,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if aa_file is not None:
             codon_mod.write_aa_tsv(aa_file, ref_id, codon_tables)
             print_log("Output amino-acid calls: %s" % aa_out_fn)
+        if cooc_file is not None:
+            cooc_mod.write_tsv(cooc_file, ref_id, cooc_tables)
+            print_log("Output co-occurrence table: %s" % cooc_out_fn)
         if qc_on and rank == 0:
             if qc_fn is not None:
                 report = qc.build_report(
@@ -499,11 +536,13 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(amp_tables.summary_line())
         if cds is not None and rank == 0:
             print_log(codon_tables.summary_line())
+        if cooc_sets is not None and rank == 0:
+            print_log(cooc_tables.summary_line())
         if del_on:
             deletion_mod.check_lost(del_lost)              # (behind the run's last collective: no rank is left waiting)
         failed = False
     finally:
-        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file]:
+        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file, cooc_file]:
             if f is not None:
                 f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)
@@ -588,6 +627,8 @@ def parse_args(argv=None):
         p.add_argument("--del_out", required=False, type=str, default=None, help="Every deletion event: start, length, reads, reverse reads, depth, frequency, deleted text (TSV or TSV.gz; variants, consensus, aio)")
         p.add_argument("--indel_vcf", required=False, type=str, default=None, help="A second VCF of anchored indels: deletion events and insertion alleles at or above the variant thresholds (VCF or VCF.gz; variants, aio)")
         p.add_argument("--del_capacity", required=False, type=int, default=None, help="log2 of the slots of the deletion events' table on the device, 4 to 28 (20 when omitted)")
+        p.add_argument("--cooc", required=False, type=str, default=None, help="Mutation-set file (TSV: name, comma-separated mutations such as A23403G, del21765-21770, del21991; positions 1-BASED as in the VCF, unlike --codons): per set, the reads that carry its mutations together, tallied on the device, and COOC on every VCF record (variants, consensus, aio)")
+        p.add_argument("--cooc_out", required=False, type=str, default=None, help="Reads per mutation set and pattern of mutations carried (TSV or TSV.gz; needs --cooc)")
         p.add_argument("--strand_out", required=False, type=str, default=None, help="Count, reverse-strand count and quality sum of every position and symbol (TSV or TSV.gz; variants, consensus, aio)")
     return parser.parse_args(argv)
 
@@ -600,7 +641,7 @@ def main(argv=None):
                    qc_depths=qc.parse_depths(args.qc_depths) if args.qc_depths is not None else None)
     qc_args.update(strand=args.strand, strand_fn=args.strand_out, amplicons_fn=args.amplicons, amplicon_out_fn=args.amplicon_out,
                    codons_fn=args.codons, codon_out_fn=args.codon_out, aa_out_fn=args.aa_out, deletions=args.deletions,
-                   del_out_fn=args.del_out, indel_vcf_fn=args.indel_vcf, del_capacity=args.del_capacity)
+                   del_out_fn=args.del_out, indel_vcf_fn=args.indel_vcf, del_capacity=args.del_capacity, cooc_fn=args.cooc, cooc_out_fn=args.cooc_out)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,

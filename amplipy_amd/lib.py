@@ -42,6 +42,7 @@ EXPORTS = [
     "amp_amplicon_enable", "amp_amplicon_get", "amp_amplicon_add", "amp_amplicon_last_ms",
     "amp_codon_enable", "amp_codon_get", "amp_codon_add", "amp_codon_last_ms",
     "amp_del_enable", "amp_del_get", "amp_del_add", "amp_del_last_ms",
+    "amp_cooc_enable", "amp_cooc_get", "amp_cooc_add", "amp_cooc_last_ms",
 ]
 
 
@@ -439,6 +440,43 @@ class Engine:
 
     def del_last_ms(self):
         return self._hook_last_ms("amp_del_last_ms")
+
+    # ---- co-occurrence of listed mutations ---------------------------------------------
+    def cooc_enable(self, set_off, site_pos, site_len, site_sym):
+        """amp_cooc_enable: the hook on for the sets given -- set s has the sites [set_off[s], set_off[s + 1]) of site_pos
+        (0-based), site_len (0: a substitution) and site_sym (0..3 for A C G T); sorted by first site -- the tables zero
+        (DESIGN.md section 20).  ``cooc_disable`` turns it off."""
+        off = np.ascontiguousarray(set_off, np.int32)
+        pos = np.ascontiguousarray(site_pos, np.int32); ln = np.ascontiguousarray(site_len, np.int32)
+        sym = np.ascontiguousarray(site_sym, np.uint8)
+        if off.size < 2:
+            raise ValueError("at least one mutation set")
+        if off[0] != 0 or not (pos.size == ln.size == sym.size) or (np.diff(off) < 0).any() or int(off[-1]) != pos.size:
+            raise ValueError("set_off does not describe the site arrays")
+        pad = lambda a: a if a.size else np.zeros(1, a.dtype)
+        self._chk(self.L.amp_cooc_enable(self.h, C.c_int32(off.size - 1), C.c_void_p(abi.ptr(off)), C.c_void_p(abi.ptr(pad(pos))),
+                                         C.c_void_p(abi.ptr(pad(ln))), C.c_void_p(abi.ptr(pad(sym)))), "amp_cooc_enable")
+        self._cooc_sets = int(off.size - 1)
+
+    def cooc_disable(self):
+        self._chk(self.L.amp_cooc_enable(self.h, C.c_int32(0), None, None, None, None), "amp_cooc_enable")
+
+    def cooc_tables(self):
+        """amp_cooc_get -> (cooc uint32[n_sets][65], reads uint64[2]: tallied, skipped) as they stand."""
+        n = getattr(self, "_cooc_sets", 0)
+        cooc = np.zeros((max(n, 1), abi.COOC_CELLS), np.uint32); reads = np.zeros(2, np.uint64)
+        self._chk(self.L.amp_cooc_get(self.h, C.c_void_p(abi.ptr(cooc)), C.c_void_p(abi.ptr(reads))), "amp_cooc_get")
+        return cooc[:n], reads
+
+    def cooc_add(self, cooc, reads):
+        """amp_cooc_add: host tables added element-wise (the merge of partial tables)."""
+        n = getattr(self, "_cooc_sets", 0)
+        c = np.ascontiguousarray(cooc, np.uint32); r = np.ascontiguousarray(reads, np.uint64)
+        assert c.size == n * abi.COOC_CELLS and r.size == 2
+        self._chk(self.L.amp_cooc_add(self.h, C.c_void_p(abi.ptr(c)), C.c_void_p(abi.ptr(r))), "amp_cooc_add")
+
+    def cooc_last_ms(self):
+        return self._hook_last_ms("amp_cooc_last_ms")
 
     # ---- calling ---------------------------------------------------------------------
     def set_reference(self, ref_seq):

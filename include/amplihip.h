@@ -809,6 +809,34 @@ int amp_del_add(amp_ctx *ctx, const amp_del_event *entries, int64_t n);
 /* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_del_last_ms(amp_ctx *ctx, float *ms);
 
+/* ---- co-occurrence of listed mutations on single reads (opt-in) ----------------------------------------------
+ * Do these listed mutations stand together on the SAME reads?  A set has 1 to 6 sites in strictly increasing position that do not
+ * overlap, its first and last site at most 2^16 positions apart; set s has the sites [set_off[s], set_off[s + 1]) of site_pos
+ * (0-based), site_len (0: a substitution; else a deletion of that many positions) and site_sym (substitutions: the base, 0..3 for
+ * A C G T); the sets are sorted by the position of their first site (equal ones in any order).  Only reads with status 0 take
+ * part, as they were counted (the trimmed alignment with do_trim, [pos, ref_end)).  On a read with a regular CIGAR (as for the
+ * codon tallies) a site is
+ *   substitution (p, b): MUT / NOT when p is a match position whose base is among A C G T with quality >= min_quality and is / is
+ *                        not b; NOT when p is inside a D or N op; NONE otherwise (outside the alignment, base N, low quality);
+ *   deletion (p, len):   NONE unless p - 1 and p + len lie in [pos, ref_end); then MUT when every position of [p, p + len) is
+ *                        inside a D or N op and neither p - 1 nor p + len is, NOT otherwise (no quality test; positions, not ops);
+ * and the read adds cooc[set][sum of 2^j over the sites j that are MUT] += 1 when no site is NONE, cooc[set][64] += 1 when some
+ * but not all are, nothing when all are.  reads[0] += 1 per such read; every other read with status 0 adds nothing to the table
+ * and reads[1] += 1.  Insertions are not sites.  (cooc: uint32[n_sets][65], reads: uint64[2].) */
+/* The hook on for the sets given (the arrays are copied; more than 2^16 sets, a set without or with more than 6 sites, sites that
+ * overlap or are out of order, a site outside the reference, sets that are not sorted, a span above 2^16: AMP_EINVAL), the tables
+ * zero; they are laid out again only when the sets changed.  n_sets == 0 or a NULL set_off: off; the tables stay readable.  With
+ * the hook on and do_trim set, amp_process_batch_device refuses a dev_out without new_pos, new_ncig, new_cig or status
+ * (AMP_EINVAL) before anything runs. */
+int amp_cooc_enable(amp_ctx *ctx, int32_t n_sets, const int32_t *set_off /* [n_sets + 1] */, const int32_t *site_pos, const int32_t *site_len,
+                    const uint8_t *site_sym);
+/* Host copies of the tables as they stand (waits for the stream); either pointer may be NULL.  AMP_ESTATE before the first enable. */
+int amp_cooc_get(amp_ctx *ctx, uint32_t *cooc /* [n_sets][65] */, uint64_t *reads /* [2] */);
+/* Host tables added element-wise, like amp_add_counts (the merge of partial tables); either pointer may be NULL. */
+int amp_cooc_add(amp_ctx *ctx, const uint32_t *cooc, const uint64_t *reads);
+/* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+int amp_cooc_last_ms(amp_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
