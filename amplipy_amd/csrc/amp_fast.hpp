@@ -345,7 +345,7 @@ __device__ __forceinline__ uint32_t range_bits16(int32_t klo, int32_t khi) {
 #define F_STAMP_DECL unsigned long long f_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, f_prev = __builtin_amdgcn_s_memtime(); const unsigned long long f_k0 = f_prev, f_w0 = wall_clock64(); unsigned long long f_ep[3] = {0, 0, 0}, f_epw[2] = {0, 0}; uint32_t f_glob = 0
 #define F_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0xC07F); unsigned long long f_n = __builtin_amdgcn_s_memtime(); f_t[k] += f_n - f_prev; f_prev = f_n; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define F_STAMP_VM(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0x0070); unsigned long long f_n = __builtin_amdgcn_s_memtime(); f_t[k] += f_n - f_prev; f_prev = f_n; __builtin_amdgcn_sched_barrier(0); } while (0)
-#define F_STAMP_OUT do { f_t[0] = __builtin_amdgcn_s_memtime() - f_k0; const unsigned long long f_w1 = wall_clock64(); f_t[7] = f_w1 - f_w0; if (lane == 0) { for (int k = 0; k < 8; ++k) atomicAdd(&ctr[CTR_PHASE0 + k], f_t[k]); \
+#define F_STAMP_OUT do { f_t[0] = __builtin_amdgcn_s_memtime() - f_k0; const unsigned long long f_w1 = wall_clock64(); f_t[7] = f_w1 - f_w0; if (lane == 0) { unsigned long long *const ctr = late_ctr(); for (int k = 0; k < 8; ++k) atomicAdd(&ctr[CTR_PHASE0 + k], f_t[k]); \
     atomicMax(&ctr[CTR_STAMP0], f_t[7]); atomicMax(&ctr[CTR_STAMP0 + 1], ~f_t[7]); atomicMax(&ctr[CTR_STAMP0 + 2], ~f_w0); atomicMax(&ctr[CTR_STAMP0 + 3], f_w1); \
     if (f_dbg && wave == 0) { uint32_t *f_o = f_dbg + blockIdx.x * 8; f_o[0] = (uint32_t)f_t[7]; f_o[1] = (uint32_t)f_w0; for (int k = 1; k < 7; ++k) f_o[1 + k] = (uint32_t)(f_t[k] >> 4); } \
     if (f_dbg) { uint32_t *f_o = f_dbg + F_DBG_WAVE0 + (blockIdx.x * F_WAVES + wave) * F_DBG_WAVEWORDS; f_o[0] = (uint32_t)((f_t[1] + f_t[2] + f_t[3] + f_t[4] + f_t[5] + f_t[6]) >> 4); f_o[1] = (uint32_t)(f_epw[0] - f_w0); f_o[2] = (uint32_t)(f_epw[1] - f_epw[0]); f_o[3] = (uint32_t)(f_ep[0] - f_epw[1]); f_o[4] = (uint32_t)(f_ep[1] - f_ep[0]); f_o[5] = (uint32_t)(f_ep[2] - f_ep[1]); } } } while (0)
@@ -363,7 +363,7 @@ __device__ __forceinline__ uint32_t range_bits16(int32_t klo, int32_t khi) {
 
 // The kernel's arguments are passed one by one, every pointer followed by a 32-bit value (round 4): a struct argument -- and a run of
 // adjacent pointers -- is loaded as ONE wide register tuple, and a kernel as short of scalar registers as this one spills and
-// reloads the whole tuple around every use of one field.
+// reloads the whole tuple around every use of one field.  (The KA_* offsets below restate this layout: change both together.)
 #define F_ARGS \
     const int32_t *a_pos, int32_t a_min_quality, const uint16_t *a_flag, int32_t a_window, const int32_t *a_tlen, int32_t a_do_trim, \
     const uint32_t *a_lseq, int32_t a_do_count, const uint32_t *a_cig_off32, int32_t a_ref_len, const uint32_t *a_cig, int32_t a_max_primer_len, \
@@ -380,6 +380,29 @@ __device__ __forceinline__ uint32_t range_bits16(int32_t klo, int32_t khi) {
     (out).new_cig, 0, (out).ref_len, 0, (out).trim_flags, 0, (out).status, 0, counts, 0, (eb).ev, 0, (eb).ctr, 0, (eb).ins_at, 0, glist, 0, gcnt, 0, \
     (rd).n_reads, 0, read_base, 0, (eb).cap
 
+// Arguments the tile loop uses once per tile or less are NOT taken from the parameter list (a parameter the body names is loaded at
+// entry and holds its scalar registers for the whole kernel: 22 pointers and 14 scalars are more than half of the register file, and
+// what did not fit was spilled to lanes of a vector register and read back with v_readlane on the vector pipe).  They are read from the
+// kernarg page where they are used: one scalar load, counted in lgkmcnt.  The offset goes through an empty asm so that the load cannot
+// be hoisted back to the entry block.  Every pointer / 64-bit value of F_ARGS sits on a 16-byte pitch, its 32-bit companion 8 bytes behind.
+enum : uint32_t { KA_MIN_START = 144, KA_MAX_END = 160, KA_NEW_POS = 176, KA_NEW_NCIG = 192, KA_NEW_CIG = 208, KA_O_REF_LEN = 224, KA_TRIM_FLAGS = 240,
+                  KA_STATUS = 256, KA_COUNTS = 272, KA_EV = 288, KA_CTR = 304, KA_INS_AT = 320, KA_GLIST = 336, KA_GCNT = 352, KA_N_READS = 368,
+                  KA_READ_BASE = 384, KA_EV_CAP = 400 };
+template <typename T>
+__device__ __forceinline__ T karg_late(uint32_t off) {
+    static_assert(sizeof(T) == 8, "the late-loaded arguments are pointers and 64-bit values");
+    asm volatile("" : "+s"(off));
+    const unsigned long long v = *(const __attribute__((address_space(4))) unsigned long long *)
+        ((const __attribute__((address_space(4))) uint8_t *)__builtin_amdgcn_kernarg_segment_ptr() + off);
+    return __builtin_bit_cast(T, v);
+}
+// ... a pointer into global memory (the address space is stated: a pointer loaded from memory would otherwise be used with flat
+// instructions, which count in vmcnt AND lgkmcnt)
+template <typename T>
+__device__ __forceinline__ T *karg_late_ptr(uint32_t off) {
+    return (T *)karg_late<__attribute__((address_space(1))) T *>(off);
+}
+
 #if AMP_F_ADD64
 #define F_COUNT5(sq, m, d0, lim, wr) count_piece5q(sq, m, d0, lim, wr, (uint32_t)(F_REPW * 4))
 #else
@@ -388,10 +411,11 @@ __device__ __forceinline__ uint32_t range_bits16(int32_t klo, int32_t khi) {
 template <int W>
 __global__ void __launch_bounds__(F_WAVES * 64, 2)
 k_fast(F_ARGS F_DBG_PARAM) {
-    const KParams P{a_min_quality, a_window, a_do_trim, a_do_count, a_ref_len, a_max_primer_len, a_min_start, a_max_end, (uint32_t)a_epoch};
+    // (the primer tables, the six outputs, the event buffer, the lists, read_base: karg_late at their uses)
+    const KParams P{a_min_quality, a_window, a_do_trim, a_do_count, a_ref_len, a_max_primer_len, nullptr, nullptr, (uint32_t)a_epoch};
     const amp_dev_reads rd{a_n_reads, a_pos, a_flag, a_tlen, a_lseq, a_cig_off32, a_cig, a_seq_off8, a_seq, a_qual, 0, 0};
-    const DevOut out{a_new_pos, a_new_ncig, a_new_cig, a_o_ref_len, a_trim_flags, a_status};
-    const EventBuf eb{a_ev, a_ctr, a_ins_at, a_ev_cap};
+    auto late_ctr = [] { return karg_late_ptr<unsigned long long>(KA_CTR); };
+    auto late_eb = [] { return EventBuf{karg_late_ptr<amp_ins_event>(KA_EV), karg_late_ptr<unsigned long long>(KA_CTR), karg_late_ptr<uint32_t>(KA_INS_AT), karg_late<long long>(KA_EV_CAP)}; };
     // THREE separate LDS objects, not one struct: the compiler orders every LDS access behind LDS-DMA loads in flight
     // (s_waitcnt vmcnt) unless alias scopes tell it that the access cannot touch the DMA's destination, and it only
     // builds those scopes per LDS variable.  With one struct every counter add waited for the next tile's bytes.
@@ -403,7 +427,6 @@ k_fast(F_ARGS F_DBG_PARAM) {
     __shared__ uint32_t s_pad[AMP_F_LDSPAD / 4];                      // (occupancy experiments: keeps a second block off the CU)
     if (P.ref_len == -12345) s_pad[threadIdx.x] = 1;
 #endif
-    unsigned long long *const ctr = eb.ctr;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     F_STAMP_DECL;
     const int64_t n = rd.n_reads;
@@ -415,7 +438,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
     for (int i = lane; i < F_REP * F_REPW; i += 64) pwin[i] = 0;
     if (lane < F_PAD / 4) ((lds_u32 *)s_stage[wave])[lane] = 0x11111111u;      // (the bytes in front of a staged run are read as bases by the lanes whose pieces start 8 bases early)
     if (tid == 0) { s_ticket = 0; s_gcur = 0; }
-    if (tid == 0 && blockIdx.x == 0) { eb.ctr[CTR_LONG_N] = 0ull; eb.ctr[CTR_LONG_TICKET] = 0ull; eb.ctr[CTR_GEN_LEFT] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
+    if (tid == 0 && blockIdx.x == 0) { unsigned long long *const ctr = late_ctr(); ctr[CTR_LONG_N] = 0ull; ctr[CTR_LONG_TICKET] = 0ull; ctr[CTR_GEN_LEFT] = 0ull; }      // k_gcompact / k_long's counters (amp_wave.hpp)
     // the block's window: anchored 16 positions left of its first read (sorted input: nothing of this block starts
     // left of that read)
     int32_t bw_base = rb < n ? rd.pos[rb] : 0;
@@ -458,7 +481,6 @@ k_fast(F_ARGS F_DBG_PARAM) {
     int pw_tiles = F_FLUSH;                                         // tiles added since the last fold (forces an anchor for the first tile)
     // the wave's granule of the event list (see the insertion events below)
     const unsigned ev_shard = blockIdx.x & (EV_SHARDS - 1);
-    amp_ins_event *const ev_list = eb.ev + (size_t)ev_shard * (size_t)eb.cap;
     unsigned long long ev_base = 0;
     uint32_t ev_left = 0;
 
@@ -483,7 +505,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
                 for (int c = 0; c < 4; ++c) {
                     if (!c4[c]) continue;
                     if (d < (uint32_t)F_BW) lds_add(bwin + c * F_BW + d, c4[c]);
-                    else if ((uint32_t)p < G) { atomicAdd(&counts[(size_t)p * AMP_NSYM + c], c4[c]); F_GLOB; }
+                    else if ((uint32_t)p < G) { atomicAdd(&karg_late_ptr<uint32_t>(KA_COUNTS)[(size_t)p * AMP_NSYM + c], c4[c]); F_GLOB; }
                 }
             }
         }
@@ -491,7 +513,10 @@ k_fast(F_ARGS F_DBG_PARAM) {
     };
     // the slots a wave reserved on the event list and did not use are marked (ref_pos = -1: dropped at read-out)
     auto pad_events = [&]() {
-        if ((uint32_t)lane < ev_left && (long long)(ev_base + (unsigned)lane) < eb.cap) ev_list[ev_base + (unsigned)lane] = amp_ins_event{-1, 0u, 0, 0};
+        if ((uint32_t)lane < ev_left) {
+            const EventBuf eb = late_eb();
+            if ((long long)(ev_base + (unsigned)lane) < eb.cap) eb.ev[(size_t)ev_shard * (size_t)eb.cap + ev_base + (unsigned)lane] = amp_ins_event{-1, 0u, 0, 0};
+        }
     };
 
     // ---- software pipeline: while tile t is computed from registers, the bytes of tile t + 1 are on their way and the
@@ -567,10 +592,11 @@ k_fast(F_ARGS F_DBG_PARAM) {
     auto shape_of = [&](const HdrP &h, const Cg &c, bool fastq) {
         Shape r;
 #if AMP_F4_BF
+        // (a lane the fast path does not take passes l_seq 0: bf_from_words5 refuses that and hands the all-zero shape back itself,
+        //  one select instead of a second pick of every field)
         bool ok;
-        r.s = cig2_of(bf_from_words5((int)h.nops(), c.w[0], c.w[1], c.w[2], c.w[3], c.w[4], (int32_t)h.lseq(), F_MAXINS, F_MAXDEL, ok));
-        r.ok = ok & fastq;
-        if (!r.ok) r.s = Cig2{0u, 0, 0, 0, 0, 0, 0, false};
+        r.s = cig2_of(bf_from_words5((int)h.nops(), c.w[0], c.w[1], c.w[2], c.w[3], c.w[4], fastq ? (int32_t)h.lseq() : 0, F_MAXINS, F_MAXDEL, ok));
+        r.ok = ok;
 #else
         r.s = Cig2{0u, 0, 0, 0, 0, 0, 0, false};
         const int nops = (int)h.nops();
@@ -581,11 +607,11 @@ k_fast(F_ARGS F_DBG_PARAM) {
         r.refspan = r.ok ? r.s.m1 + r.s.m2 + (r.s.kind == 2 ? r.s.k : 0) : 1;               // (m2 = 0 without an indel; soft clips cover no reference)
         return r;
     };
-    // the two primer-table entries of A:450-451
-    auto load_tabs = [&](const HdrP &h, const Shape &sh) {
+    // the two primer-table entries of A:450-451; both -1 (None) for a lane whose primers are not trimmed: the primer clips below rely on it
+    auto load_tabs = [&](const HdrP &h, const Shape &sh, bool trim) {
         Tabs t{-1, -1};
         const bool in_ref = (uint32_t)h.pos < G && (uint32_t)(h.pos + sh.refspan - 1) < G;
-        if (sh.ok && P.do_trim && in_ref) { t.L = P.max_end[h.pos]; t.R = P.min_start[h.pos + sh.refspan - 1]; }
+        if (trim && in_ref) { t.L = karg_late_ptr<const int32_t>(KA_MAX_END)[h.pos]; t.R = karg_late_ptr<const int32_t>(KA_MIN_START)[h.pos + sh.refspan - 1]; }
         return t;
     };
     // the tile's quality bytes by LDS-DMA (lane l moves bytes [1024 s + 16 l, + 16) of the run to the same offset of
@@ -625,6 +651,8 @@ k_fast(F_ARGS F_DBG_PARAM) {
 #endif
         const uint32_t ncig = r.meta & 0xFFu;
         if (r.meta & P_STORED) {
+            const DevOut out{karg_late_ptr<int32_t>(KA_NEW_POS), karg_late_ptr<uint32_t>(KA_NEW_NCIG), karg_late_ptr<uint32_t>(KA_NEW_CIG),
+                             karg_late_ptr<int32_t>(KA_O_REF_LEN), karg_late_ptr<uint8_t>(KA_TRIM_FLAGS), karg_late_ptr<uint8_t>(KA_STATUS)};
             uint32_t *home = out.new_cig + ((size_t)r.slot_lo + 3 * (size_t)r.i);
             if (ncig > 0u) home[0] = r.cw0;
             if (ncig > 1u) home[1] = r.cw1;
@@ -645,7 +673,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
             uint32_t base = 0;
             if (lane == 0) base = __hip_atomic_fetch_add((lds_u32 *)&s_gcur, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            if (has) glist[(size_t)rb + base + __popcll(m & ((1ull << lane) - 1ull))] = r.i | ((r.meta & P_STATUS_ONLY) ? GL_STATUS_ONLY : 0u);
+            if (has) karg_late_ptr<uint32_t>(KA_GLIST)[(size_t)rb + base + __popcll(m & ((1ull << lane) - 1ull))] = r.i | ((r.meta & P_STATUS_ONLY) ? GL_STATUS_ONLY : 0u);
         }
     };
 
@@ -657,6 +685,11 @@ k_fast(F_ARGS F_DBG_PARAM) {
 #ifndef AMP_F_STAGGER
 #define AMP_F_STAGGER 4000
 #endif
+    // (the first tile's ticket and header load go out BEFORE the sleep: the header is the first of three dependent memory latencies, and wave 7
+    //  would otherwise start it 28,000 cycles late; the DMA of the bytes stays behind the sleep, it is the row traffic the stagger spreads)
+    uint32_t tkN = take_ticket(), tkN2 = 0;
+    int64_t i0 = rb, i1 = rb + 64 * (int64_t)tkN, i2 = rb;
+    const Hdr h_first = load_hdr(i1);
     if (AMP_F_STAGGER > 0) {       // (the waves of a block start together and take equally long per tile: left alone they ask for memory and compute in step. Wave w starts w steps late: 0.243 -> 0.230 ms on the bench batch)
         const unsigned long long t_end = __builtin_amdgcn_s_memtime() + (unsigned long long)AMP_F_STAGGER * (unsigned)wave;
         while (__builtin_amdgcn_s_memtime() < t_end) __builtin_amdgcn_s_sleep(8);
@@ -666,10 +699,8 @@ k_fast(F_ARGS F_DBG_PARAM) {
     // after it.  They are renamed to "this tile" at the top of the loop, behind the wait, so that no register with a
     // load in flight is touched between the issue of a tile's loads and that wait (the compiler answers every such
     // touch with s_waitcnt vmcnt(0), which would wait for the bytes just requested).
-    uint32_t tkN = take_ticket(), tkN2 = 0;
-    int64_t i0 = rb, i1 = rb + 64 * (int64_t)tkN, i2 = rb;
     int tile_no = 0; (void)tile_no;
-    HdrP hN = pack_hdr(load_hdr(i1));
+    HdrP hN = pack_hdr(h_first);
     Hdr hN2{0, 0, 0u, 0u, 0u, 0u, 0u};
     Cg cN = load_cig(hN);
     uint32_t m0N = 0;
@@ -697,7 +728,12 @@ k_fast(F_ARGS F_DBG_PARAM) {
         const bool solo = g.solo, taken = g.taken, fastq = g.fastq;
         // the primer-table entries of this tile (they hang on its CIGAR words): a short wait behind the row reads below
         const Shape shp = shape_of(h, cA, fastq);
-        const Tabs tA = load_tabs(h, shp);
+        // (the two switches of the run go through an empty asm once per tile: as loop constants they were kept as lane masks in scalar
+        //  register pairs, spilled, and read back lane by lane at every use)
+        int32_t do_trim_t = P.do_trim, do_count_t = P.do_count;
+        asm volatile("" : "+s"(do_trim_t), "+s"(do_count_t));
+        const bool trim = shp.ok & (do_trim_t != 0);
+        const Tabs tA = load_tabs(h, shp, trim);
         // ---- the wave's packed window: fold and re-anchor when the tile has moved on, or before a byte could overflow
         {
             const int32_t first_pos = __builtin_amdgcn_readfirstlane(pos);
@@ -739,23 +775,23 @@ k_fast(F_ARGS F_DBG_PARAM) {
         TrimState ts{pos, 1, 0u, 0};
 #if AMP_F4_BF
         {
-            const bool trim = shaped & (P.do_trim != 0), use = trim & in_ref;
             ts.err = (trim & !in_ref) ? AMP_RS_INDEX_REF : 0;
             int32_t p2 = pos; uint32_t f2 = 0u;
-            const Bf sp = bf_trim_primers(bf_of(s), p2, f2, flag, h.isize_flag(), (int32_t)lseq, tA.L, tA.R);
-            s = cig2_of(bf_pick(use, sp, bf_of(s))); ts.pos = use ? p2 : pos; ts.flags = use ? f2 : 0u;
+            // (no pick by `use` behind it: load_tabs left both entries at -1 for a lane without `use`, and bf_trim_primers with two
+            //  absent entries returns shape, position and flags as they came)
+            s = cig2_of(bf_trim_primers(bf_of(s), p2, f2, flag, h.isize_flag(), (int32_t)lseq, tA.L, tA.R)); ts.pos = p2; ts.flags = f2;
         }
-        const bool scan = shaped & (P.do_trim != 0) & (ts.err == 0) & !s.punt;
+        const bool scan = trim & (ts.err == 0) & !s.punt;
         // aligned-quality window [lo, hi) in PIECE coordinates (query index + phi)
         int32_t lo, qlen;
         bf_quality_window(bf_of(s), (int32_t)lseq, lo, qlen);
         lo = scan ? lo + (int32_t)phi : 0; qlen = scan ? qlen : 0;
 #else
-        if (shaped && P.do_trim) {
+        if (trim) {
             if (!in_ref) ts.err = AMP_RS_INDEX_REF;
             else cig2_trim_primers_isize(ts, flag, h.isize_flag(), (int32_t)lseq, s, tA.L, tA.R);
         }
-        const bool scan = shaped && P.do_trim && !ts.err && !s.punt;
+        const bool scan = trim && !ts.err && !s.punt;
         // aligned-quality window [lo, hi) in PIECE coordinates (query index + phi)
         int32_t lo = 0, qlen = 0;
         if (scan) { cig2_quality_window(s, (int32_t)lseq, lo, qlen); lo += (int32_t)phi; }
@@ -770,6 +806,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
         const amp_u32x2 tw0 = *(const lds_u32x2 *)(lq + tab), tw1 = *(const lds_u32x2 *)(lq + tab + 8);
         const amp_u32x2 iq0 = *(const lds_u32x2 *)(lq + g_ins), iq1 = *(const lds_u32x2 *)(lq + g_ins + 8);
         const amp_u32x2 bq0 = *(const lds_u32x2 *)(lq + g_b), bq1 = *(const lds_u32x2 *)(lq + g_b + 8);
+        const uint32_t fb = *lq;                      // the read's first quality byte (0xFF = QUAL '*'); which slot holds it depends on the lane's rotation
         wave_sync();
 #pragma unroll
         for (int sl = 0; sl < F_STAGE / 2048; ++sl) *(lds_u32x4 *)(stage + sl * 1024 + lane * 16) = amp_u32x4{xA.raws[sl].x, xA.raws[sl].y, xA.raws[sl].z, xA.raws[sl].w};
@@ -817,9 +854,9 @@ k_fast(F_ARGS F_DBG_PARAM) {
         // ---- sliding-window scan: first failing window start (forward) / last failing window end (reverse) --
         int32_t ffmin = 0x7FFFFFFF, lemax = -1;
 #if defined(AMP_DEV) && defined(AMP_ABL)
-        if (P.do_trim && !(AMP_ABL & 4)) {
+        if (do_trim_t && !(AMP_ABL & 4)) {
 #else
-        if (P.do_trim) {
+        if (do_trim_t) {
 #endif
 #pragma unroll
             for (int k = 0; k < F_NP; ++k) {
@@ -848,13 +885,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
         uint32_t ncig = 0, cw[5] = {0u, 0u, 0u, 0u, 0u};
         int32_t reflen = 0;
         if (shaped) {
-            // the read's first quality byte (0xFF = QUAL '*') is byte phi of piece 0, which sits in slot (np - rot) mod np: slot 0
-            // when rot is 0 (slot np holds a copy of the LAST piece then, not piece 0)
-            uint32_t fb = phi ? q16[0].z : q16[0].x;
-            const uint32_t slot0 = rot ? np - rot : 0u;
-#pragma unroll
-            for (int k = 1; k < F_NP; ++k) fb = ((uint32_t)k == slot0) ? (phi ? q16[k].z : q16[k].x) : fb;
-            if ((fb & 0xFFu) == 0xFFu || s.punt) {
+            if (fb == 0xFFu || s.punt) {
                 general = true;                   // QUAL '*': the generic code reports it (A:561-562, A:718); a shape the closed forms leave
             } else {
                 if (scan) {
@@ -884,7 +915,8 @@ k_fast(F_ARGS F_DBG_PARAM) {
                     general = true;
                 } else {
                     if (!ts.err) {
-                        // [S a][op m1][I|D k][op m2][S c], absent parts left out: slot `ncig` takes the next part
+                        // [S a][op m1][I|D k][op m2][S c], absent parts left out: slot `ncig` takes the next part (part t can only land
+                        // in slots 0..t, and the second match op is never there without the indel in front of it)
                         const uint32_t part[5] = {((uint32_t)s.a << 4) | OP_S, ((uint32_t)s.m1 << 4) | s.op,
                                                   ((uint32_t)s.k << 4) | (s.kind == 1 ? OP_I : OP_D), ((uint32_t)s.m2 << 4) | s.op,
                                                   ((uint32_t)s.c << 4) | OP_S};
@@ -893,7 +925,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
                         for (int t = 0; t < 5; ++t) {
                             if (has[t]) {
 #pragma unroll
-                                for (int j = 0; j < 5; ++j) cw[j] = ncig == (uint32_t)j ? part[t] : cw[j];
+                                for (int j = (t == 3 ? 1 : 0); j <= t; ++j) cw[j] = ncig == (uint32_t)j ? part[t] : cw[j];
                                 ++ncig;
                             }
                         }
@@ -904,7 +936,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
                 }
             }
         }
-        const bool counted = stored && !ts.err && P.do_count;
+        const bool counted = stored && !ts.err && do_count_t;
         F_STAMP(4);          // quality clip, results
         // ---- counting (A:709-753): the counted query ranges [qa1, qb1) and [qa2, qb2) in piece coordinates, the window
         // offset of piece coordinate 0 for each of them ------------------------------------------------------------------
@@ -920,7 +952,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
                 const uint32_t d = (uint32_t)(r - bw_base);
                 if ((uint32_t)r >= G) bad_extra = true;
                 else if (d < (uint32_t)F_BW) lds_add_nt(bwin + 4 * F_BW + d, 1u);
-                else atomicAdd(&counts[(size_t)r * AMP_NSYM + 5], 1u);
+                else atomicAdd(&karg_late_ptr<uint32_t>(KA_COUNTS)[(size_t)r * AMP_NSYM + 5], 1u);
             }
         }
         // insertion (A:730-748): one event per maximal run of good-quality inserted bases (cig2_indels in amp_read.hpp;
@@ -943,14 +975,15 @@ k_fast(F_ARGS F_DBG_PARAM) {
                 if (total > ev_left) {
                     pad_events();
                     unsigned long long nb = 0;
-                    if (lane == 0) nb = atomicAdd(&ctr[CTR_EV_SHARD0 + ev_shard], (unsigned long long)F_EVGRAN);
+                    if (lane == 0) nb = atomicAdd(&late_ctr()[CTR_EV_SHARD0 + ev_shard], (unsigned long long)F_EVGRAN);
                     ev_base = __shfl(nb, 0); ev_left = F_EVGRAN;
                 }
                 if (runs) {
                     const int32_t q0 = s.a + s.m1, r2 = ts.pos + s.m1, ref_end = ts.pos + s.m1 + s.m2;
                     // the lane's first run takes its slot of the granule; further runs of one insertion (rare) go the slow way
                     const unsigned long long slot = ev_base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
-                    const uint32_t rid = (uint32_t)(read_base + (uint64_t)i);
+                    const uint32_t rid = (uint32_t)(karg_late<uint64_t>(KA_READ_BASE) + (uint64_t)i);
+                    const EventBuf eb = late_eb();
                     bool firstrun = true;
                     while (runs) {
                         const int32_t js = __builtin_ctz(runs);
@@ -964,7 +997,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
                         const bool inside = (uint32_t)ins_pos < G;
                         if (!inside) bad_extra = true;
                         if (firstrun) {
-                            if ((long long)slot < eb.cap) ev_list[slot] = inside ? amp_ins_event{ins_pos, rid, elo, ehi} : amp_ins_event{-1, 0u, 0, 0};
+                            if ((long long)slot < eb.cap) eb.ev[(size_t)ev_shard * (size_t)eb.cap + slot] = inside ? amp_ins_event{ins_pos, rid, elo, ehi} : amp_ins_event{-1, 0u, 0, 0};
                             if (inside) {
                                 const uint32_t d = (uint32_t)(ins_pos - bw_base);
                                 if (d < (uint32_t)F_BW) lds_add_nt(bwin + 5 * F_BW + d, 1u);
@@ -1067,7 +1100,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
                         const uint32_t d = (uint32_t)(rp - bw_base);
                         if (col > 4u || (uint32_t)rp >= G) want_status = true;
                         else if (d < (uint32_t)F_BW && col < (uint32_t)F_NPL) lds_add_nt(bwin + col * F_BW + d, 1u);
-                        else atomicAdd(&counts[(size_t)rp * AMP_NSYM + col], 1u);
+                        else atomicAdd(&karg_late_ptr<uint32_t>(KA_COUNTS)[(size_t)rp * AMP_NSYM + col], 1u);
                     }
                 };
                 for (int k = 0; k < F_NP; ++k) {
@@ -1103,21 +1136,22 @@ k_fast(F_ARGS F_DBG_PARAM) {
 #if defined(AMP_DEV) && defined(AMP_ABL)
     if (AMP_ABL & 16) return;
 #endif
+    uint32_t *const counts_l = karg_late_ptr<uint32_t>(KA_COUNTS), *const ins_at_l = karg_late_ptr<uint32_t>(KA_INS_AT);
     for (int i = tid; i < F_BPL * F_BW; i += F_WAVES * 64) {
         const uint32_t v = bwin[i];
         if (v) {
             const int pl = i / F_BW, d = i - pl * F_BW;
             const uint32_t p = (uint32_t)(bw_base + d);
             if (p < G) {
-                if (pl < F_NPL) atomicAdd(&counts[(size_t)p * AMP_NSYM + pl], v);
-                else if (pl == 4) atomicAdd(&counts[(size_t)p * AMP_NSYM + 5], v);      // '-'
-                else atomicAdd(&eb.ins_at[p], v);
+                if (pl < F_NPL) atomicAdd(&counts_l[(size_t)p * AMP_NSYM + pl], v);
+                else if (pl == 4) atomicAdd(&counts_l[(size_t)p * AMP_NSYM + 5], v);      // '-'
+                else atomicAdd(&ins_at_l[p], v);
             }
         }
     }
-    if (n_err) atomicAdd(&ctr[CTR_ERROR_READS], n_err);
+    if (n_err) atomicAdd(&late_ctr()[CTR_ERROR_READS], n_err);
     F_STAMP_OUT;
-    if (tid == 0) { gcnt[blockIdx.x] = s_gcur; if (s_gcur) eb.ctr[CTR_EPOCH] = (unsigned long long)P.epoch; }      // (every block writes the same value)
+    if (tid == 0) { karg_late_ptr<uint32_t>(KA_GCNT)[blockIdx.x] = s_gcur; if (s_gcur) late_ctr()[CTR_EPOCH] = (unsigned long long)P.epoch; }      // (every block writes the same value)
 }
 
 // Dense list of the reads the fast kernel handed over + the geometry of the general pass.  Block b places the
