@@ -90,6 +90,11 @@ COOC_SITES = 6                 # sites of a set at most
 COOC_MAX_SETS = 1 << 16        # more is refused with AMP_EINVAL
 COOC_MAX_SPAN = 1 << 16        # last site's position minus the first site's, at most
 
+# ---- error profile (amp_errprof_*): cyc uint64[2][EP_CYCLES][2], qualt uint64[2][EP_QUALS][2], sub uint64[2][2][2][4][4], reads uint64[2] ----
+EP_CYCLES = 512                # cycles from the 5' end of the stored SEQ; the last bin is open-ended
+EP_QUALS = 94                  # reported qualities; the last bin is open-ended
+EP_CYC_SHAPE, EP_QUAL_SHAPE, EP_SUB_SHAPE = (2, EP_CYCLES, 2), (2, EP_QUALS, 2), (2, 2, 2, 4, 4)
+
 # ---- QC report (amp_qc_*) ----
 QC_MAX_DEPTHS = 4
 

@@ -16,7 +16,7 @@ from os.path import isfile
 
 import numpy as np
 
-from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, cooc as cooc_mod, deletion as deletion_mod, lib, parallel, qc, strand as strand_mod
+from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, cooc as cooc_mod, deletion as deletion_mod, errprof as errprof_mod, lib, parallel, qc, strand as strand_mod
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -80,10 +80,10 @@ def open_device_bam_text(input_fn, output_fn):
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
-    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False):
+    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False, errprof=False):
         """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables);
         amplicon: likewise the seven keys of --amplicons, behind them; codon: likewise the five keys of --codons; deletion:
-        likewise the two keys of --deletions; cooc: likewise the key of --cooc, last."""
+        likewise the two keys of --deletions; cooc: likewise the key of --cooc; errprof: likewise the two keys of --error_profile, last."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -116,16 +116,18 @@ class VcfWriter:
             w(deletion_mod.HEADER_LINES)
         if cooc:
             w(cooc_mod.HEADER_LINES)
+        if errprof:
+            w(errprof_mod.HEADER_LINES)
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
-    def line(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None):
-        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon, deletion, cooc)
+    def line(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None):
+        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon, deletion, cooc, errprof)
 
-    def write(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None):
-        self.f.write(self.line(r, strand, amplicon, codon, deletion, cooc))
+    def write(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None):
+        self.f.write(self.line(r, strand, amplicon, codon, deletion, cooc, errprof))
 
-    def write_all(self, records, strand=None, amplicon=None, codon=None, deletion=None, cooc=None):
-        self.f.write("".join([self.line(r, strand, amplicon, codon, deletion, cooc) for r in records]))
+    def write_all(self, records, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None):
+        self.f.write("".join([self.line(r, strand, amplicon, codon, deletion, cooc, errprof) for r in records]))
 
     def close(self):
         if self.f is not sys.stdout:
@@ -139,7 +141,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None, qc_fn=None, qc_regions_fn=None, qc_depths=None,
                 qc_depth_fn=None, strand=False, strand_fn=None, amplicons_fn=None, amplicon_out_fn=None, codons_fn=None,
                 codon_out_fn=None, aa_out_fn=None, deletions=False, del_out_fn=None, indel_vcf_fn=None, del_capacity=None, cooc_fn=None,
-                cooc_out_fn=None):
+                cooc_out_fn=None, error_profile_fn=None, error_mask_fn=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -181,6 +183,13 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     behind every batch's read pass, per set the reads that show all its sites by the pattern of mutations they carry, and every
     VCF record also carries COOC.  cooc_out_fn: the pattern table as a TSV file.  With cooc_fn None the engine's hook is never
     switched on.
+    error_profile_fn (default: off; runs with a count table): the error profile as JSON -- how often a base
+    differs from the reference by sequencing cycle, by reported quality and by substitution class, tallied on the device behind
+    every batch's read pass over every match base of every regular read -- and, on runs that write a VCF, ERR_RATE and ERR_P
+    on every record: the run's rate of reading the REF base as the ALT base, and the binomial tail of the ALT depth under it.
+    error_mask_fn: positions that take no part, as a VCF (of a first run, say) or a BED file; WITHOUT A MASK THE SITE'S OWN BASES
+    ARE PART OF THE RATE, so a real variant at high frequency raises the rate it is held against.  With error_profile_fn None
+    the engine's hook is never switched on.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -234,6 +243,10 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("The co-occurrence table (--cooc_out) needs the mutation-set file (--cooc)")
     if cooc_fn is not None and not (run_variants or run_consensus):
         error("A run that only trims has no count table: no co-occurrence tallies (--cooc, --cooc_out)")
+    if error_mask_fn is not None and error_profile_fn is None:
+        error("The error mask (--error_mask) needs the error profile (--error_profile)")
+    if error_profile_fn is not None and not (run_variants or run_consensus):
+        error("A run that only trims has no count table: no error profile (--error_profile, --error_mask)")
     del_on = bool(deletions) or del_out_fn is not None or indel_vcf_fn is not None
     if del_on and not (run_variants or run_consensus):
         error("A run that only trims has no count table: no deletion events (--deletions, --del_out, --indel_vcf)")
@@ -289,7 +302,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = cooc_sets = cooc_file = None
+    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = cooc_sets = cooc_file = ep_file = ep_mask = None
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
@@ -306,7 +319,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
             vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None, codon=codons_fn is not None, deletion=bool(deletions),
-                            cooc=cooc_fn is not None)
+                            cooc=cooc_fn is not None, errprof=error_profile_fn is not None)
             if amplicon_out_fn is not None:
                 amp_file = qc.open_new(amplicon_out_fn)
         if strand_fn is not None and rank == 0:
@@ -328,6 +341,12 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             cooc_sets = cooc_mod.load_sets(cooc_fn, ref_seq)
             if rank == 0:
                 cooc_file = qc.open_new(cooc_out_fn) if cooc_out_fn is not None else None
+        if error_profile_fn is not None:
+            if error_mask_fn is not None:
+                print_log("Loading error mask: %s" % error_mask_fn)
+                ep_mask = errprof_mod.load_mask(error_mask_fn, G)
+            if rank == 0:
+                ep_file = qc.open_new(error_profile_fn)
         if qc_on:
             qc_regions = [(0, G, qc.WHOLE)] + (qc.load_regions(qc_regions_fn) if qc_regions_fn is not None else [])
             qc_primers = qc.load_primer_rows(primer_fn) if run_trim else []
@@ -355,6 +374,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.del_enable(del_capacity or 0)
     if cooc_sets is not None and rank_error is None:
         cooc_mod.enable(eng, cooc_sets)
+    if error_profile_fn is not None and rank_error is None:
+        errprof_mod.enable(eng, ref_seq, ep_mask)
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -404,7 +425,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
 
     failed = True
     try:
-        qc_depth = qc_region_recs = None
+        qc_depth = qc_region_recs = ep_tables = None
         del_lost = 0
         if qc_on and rank == 0:
             qc_tallies = qc.merge_read_tallies(qc_parts) if dist is not None else eng.qc_read_tallies()
@@ -468,6 +489,16 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                         o_reads = np.sum([np.asarray(part, np.uint64) for part in cooc_read_parts], axis=0, dtype=np.uint64)
                 if rank == 0:
                     cooc_tables = cooc_mod.Tables(cooc_sets, o_cooc, o_reads)
+            if error_profile_fn is not None:
+                e_tabs = eng.errprof_tables()
+                if dist is not None:                       # one more all-reduce: the three tables and the read counters as one int64 tensor
+                    import torch
+                    wire = torch.from_numpy(errprof_mod.to_wire(*e_tabs)).to("cuda:%d" % device)
+                    parallel.allreduce_table(dist, wire)
+                    e_tabs = errprof_mod.from_wire(wire.cpu().numpy())
+                if rank == 0:
+                    ep_tables = errprof_mod.Tables(*e_tabs, min_quality if min_quality is not None else 20,
+                                                   int(ep_mask.sum()) if ep_mask is not None else 0, eng.counts() if run_variants else None)
             del_tables = None
             if del_on:
                 if dist is None:
@@ -491,7 +522,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 run_variants = run_consensus = False       # rank 0 writes the outputs
             if run_variants:
                 vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables, codon_tables,
-                                         del_tables if deletions else None, cooc_tables))        # (= vcf.write(r) for r in res.records)
+                                         del_tables if deletions else None, cooc_tables, ep_tables))      # (= vcf.write(r) for r in res.records)
                 vcf.close()
             if indel_file is not None:
                 deletion_mod.write_indel_vcf(indel_file, ref_id, del_tables, deletion_mod.insertion_rows(res.records), " ".join(sys.argv))
@@ -518,6 +549,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if cooc_file is not None:
             cooc_mod.write_tsv(cooc_file, ref_id, cooc_tables)
             print_log("Output co-occurrence table: %s" % cooc_out_fn)
+        if ep_file is not None:
+            qc.write_json(ep_file, ep_tables.report())
+            print_log("Output error profile: %s" % error_profile_fn)
         if qc_on and rank == 0:
             if qc_fn is not None:
                 report = qc.build_report(
@@ -538,11 +572,13 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(codon_tables.summary_line())
         if cooc_sets is not None and rank == 0:
             print_log(cooc_tables.summary_line())
+        if ep_tables is not None:
+            print_log(ep_tables.summary_line())
         if del_on:
             deletion_mod.check_lost(del_lost)              # (behind the run's last collective: no rank is left waiting)
         failed = False
     finally:
-        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file, cooc_file]:
+        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file, cooc_file, ep_file]:
             if f is not None:
                 f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)
@@ -629,6 +665,8 @@ def parse_args(argv=None):
         p.add_argument("--del_capacity", required=False, type=int, default=None, help="log2 of the slots of the deletion events' table on the device, 4 to 28 (20 when omitted)")
         p.add_argument("--cooc", required=False, type=str, default=None, help="Mutation-set file (TSV: name, comma-separated mutations such as A23403G, del21765-21770, del21991; positions 1-BASED as in the VCF, unlike --codons): per set, the reads that carry its mutations together, tallied on the device, and COOC on every VCF record (variants, consensus, aio)")
         p.add_argument("--cooc_out", required=False, type=str, default=None, help="Reads per mutation set and pattern of mutations carried (TSV or TSV.gz; needs --cooc)")
+        p.add_argument("--error_profile", required=False, type=str, default=None, help="Error profile (JSON): how often a base differs from the reference by sequencing cycle, by reported quality and by substitution class, tallied on the device over every match base; ERR_RATE and ERR_P on every VCF record. Without --error_mask the site's own bases are part of the rate (variants, consensus, aio)")
+        p.add_argument("--error_mask", required=False, type=str, default=None, help="Positions that take no part in the error profile, the known or called variants: a .vcf / .vcf.gz (every record masks its REF span) or a BED (columns 2 and 3; .gz allowed); needs --error_profile")
         p.add_argument("--strand_out", required=False, type=str, default=None, help="Count, reverse-strand count and quality sum of every position and symbol (TSV or TSV.gz; variants, consensus, aio)")
     return parser.parse_args(argv)
 
@@ -641,7 +679,8 @@ def main(argv=None):
                    qc_depths=qc.parse_depths(args.qc_depths) if args.qc_depths is not None else None)
     qc_args.update(strand=args.strand, strand_fn=args.strand_out, amplicons_fn=args.amplicons, amplicon_out_fn=args.amplicon_out,
                    codons_fn=args.codons, codon_out_fn=args.codon_out, aa_out_fn=args.aa_out, deletions=args.deletions,
-                   del_out_fn=args.del_out, indel_vcf_fn=args.indel_vcf, del_capacity=args.del_capacity, cooc_fn=args.cooc, cooc_out_fn=args.cooc_out)
+                   del_out_fn=args.del_out, indel_vcf_fn=args.indel_vcf, del_capacity=args.del_capacity, cooc_fn=args.cooc, cooc_out_fn=args.cooc_out,
+                   error_profile_fn=args.error_profile, error_mask_fn=args.error_mask)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,

@@ -43,6 +43,7 @@ EXPORTS = [
     "amp_codon_enable", "amp_codon_get", "amp_codon_add", "amp_codon_last_ms",
     "amp_del_enable", "amp_del_get", "amp_del_add", "amp_del_last_ms",
     "amp_cooc_enable", "amp_cooc_get", "amp_cooc_add", "amp_cooc_last_ms",
+    "amp_errprof_enable", "amp_errprof_get", "amp_errprof_add", "amp_errprof_last_ms",
 ]
 
 
@@ -477,6 +478,46 @@ class Engine:
 
     def cooc_last_ms(self):
         return self._hook_last_ms("amp_cooc_last_ms")
+
+    # ---- error profile -----------------------------------------------------------------
+    def errprof_enable(self, ref_seq, mask=None):
+        """amp_errprof_enable(1): the hook on for the reference letters ``ref_seq`` (str or bytes of ref_len letters), the
+        tables zero.  ``mask``: bool[ref_len], True for a position that takes no part, or None.
+        ``errprof_disable`` turns it off; the tables stay readable."""
+        ref = np.frombuffer(ref_seq.encode("ascii") if isinstance(ref_seq, str) else bytes(ref_seq), np.uint8)
+        if ref.size != self.ref_len:
+            raise ValueError("the reference has %d letters, the engine %d positions" % (ref.size, self.ref_len))
+        bits = None
+        if mask is not None:
+            mk = np.ascontiguousarray(mask, bool)
+            if mk.size != self.ref_len:
+                raise ValueError("the mask has one entry per reference position")
+            bits = np.zeros((self.ref_len + 31) // 32 + 1, np.uint32)
+            p = np.nonzero(mk)[0]
+            np.bitwise_or.at(bits, p >> 5, (np.uint32(1) << (p & 31).astype(np.uint32)).astype(np.uint32))
+        pad = ref if ref.size else np.zeros(1, np.uint8)
+        self._chk(self.L.amp_errprof_enable(self.h, C.c_int(1), C.c_void_p(abi.ptr(pad)), C.c_void_p(abi.ptr(bits))), "amp_errprof_enable")
+
+    def errprof_disable(self):
+        self._chk(self.L.amp_errprof_enable(self.h, C.c_int(0), None, None), "amp_errprof_enable")
+
+    def errprof_tables(self):
+        """amp_errprof_get -> (cyc uint64[2][512][2], qualt uint64[2][94][2], sub uint64[2][2][2][4][4], reads uint64[2]:
+        profiled, skipped) as they stand."""
+        cyc = np.zeros(abi.EP_CYC_SHAPE, np.uint64); qualt = np.zeros(abi.EP_QUAL_SHAPE, np.uint64)
+        sub = np.zeros(abi.EP_SUB_SHAPE, np.uint64); reads = np.zeros(2, np.uint64)
+        self._chk(self.L.amp_errprof_get(self.h, C.c_void_p(abi.ptr(cyc)), C.c_void_p(abi.ptr(qualt)), C.c_void_p(abi.ptr(sub)),
+                                         C.c_void_p(abi.ptr(reads))), "amp_errprof_get")
+        return cyc, qualt, sub, reads
+
+    def errprof_add(self, cyc, qualt, sub, reads):
+        """amp_errprof_add: host tables added element-wise (the merge of partial tables)."""
+        arrs = [np.ascontiguousarray(a, np.uint64) for a in (cyc, qualt, sub, reads)]
+        assert [a.size for a in arrs] == [int(np.prod(s)) for s in (abi.EP_CYC_SHAPE, abi.EP_QUAL_SHAPE, abi.EP_SUB_SHAPE)] + [2]
+        self._chk(self.L.amp_errprof_add(self.h, *[C.c_void_p(abi.ptr(a)) for a in arrs]), "amp_errprof_add")
+
+    def errprof_last_ms(self):
+        return self._hook_last_ms("amp_errprof_last_ms")
 
     # ---- calling ---------------------------------------------------------------------
     def set_reference(self, ref_seq):

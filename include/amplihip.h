@@ -837,6 +837,34 @@ int amp_cooc_add(amp_ctx *ctx, const uint32_t *cooc, const uint64_t *reads);
 /* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_cooc_last_ms(amp_ctx *ctx, float *ms);
 
+/* ---- The error profile by cycle, quality and substitution (opt-in) ----
+ * How often a base differs from the reference.  While the hook is on, one more kernel behind the read pass of every batch (the
+ * last of the hooks) visits every read with status 0 whose counted alignment (the trimmed one with do_trim) is regular in the
+ * sense of the codon tallies above.  Every base of every match op (M = X) of such a read, WHATEVER its quality, with
+ *   b: the read base, one of A C G T;  x: the reference letter at its position, upper-cased, one of A C G T, not masked
+ *      (a base with another b or x takes no part);
+ *   m: FLAG & 0x80 (unpaired reads are mate 0);  s: FLAG & 0x10;
+ *   c: min(s ? l_seq - 1 - q : q, 511) for query index q -- the cycle from the 5' end of the stored SEQ, hard clips not counted;
+ *   v: min(qual, 93);  e: b != x;  g: qual >= min_quality
+ * adds 1 to cyc[m][c][e], qualt[m][v][e] and sub[m][s][g][x][b] (x, b: A C G T as 0 1 2 3).  reads[0] += 1 per such read; every
+ * other read with status 0 adds nothing to the tables and reads[1] += 1.  For each m the sums of cyc[m], qualt[m] and sub[m] are
+ * equal; with no mask, on a batch whose status-0 reads are all regular, the sum over m, s of sub[m][s][1][X][b] is the sum of
+ * counts[p][b] over the positions p whose upper-cased reference letter is X.
+ * (cyc: uint64[2][512][2], qualt: uint64[2][94][2], sub: uint64[2][2][2][4][4], reads: uint64[2].) */
+#define AMP_EP_CYCLES 512
+#define AMP_EP_QUALS 94
+/* on != 0: the hook on for the reference letters given (copied; mask_bits: bit p & 31 of word p >> 5 set for a position that
+ * takes no part, NULL: none), the tables zero -- at every call.  A NULL ref_ascii with on: AMP_EINVAL.  on == 0: off; the
+ * tables stay readable.  With the hook on and do_trim set, amp_process_batch_device refuses a dev_out without new_pos, new_ncig,
+ * new_cig or status (AMP_EINVAL) before anything runs. */
+int amp_errprof_enable(amp_ctx *ctx, int on, const uint8_t *ref_ascii /* [ref_len] */, const uint32_t *mask_bits /* [(ref_len + 31) / 32] or NULL */);
+/* Host copies of the tables as they stand (waits for the stream); any pointer may be NULL.  AMP_ESTATE before the first enable. */
+int amp_errprof_get(amp_ctx *ctx, uint64_t *cyc, uint64_t *qualt, uint64_t *sub, uint64_t *reads);
+/* Host tables added element-wise, like amp_add_counts (the merge of partial tables); any pointer may be NULL. */
+int amp_errprof_add(amp_ctx *ctx, const uint64_t *cyc, const uint64_t *qualt, const uint64_t *sub, const uint64_t *reads);
+/* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+int amp_errprof_last_ms(amp_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
