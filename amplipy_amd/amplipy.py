@@ -194,8 +194,10 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
     order), every rank's count table is summed with ONE all-reduce over RCCL (parallel.allreduce_table), the
-    insertion alleles of the flagged positions are exchanged, and rank 0 writes the VCF / consensus.  A trimmed
-    BAM is written per rank (``<name>.part<rank>.bam``; the parts concatenate to the single-GPU file's records).
+    insertion alleles of the flagged positions are exchanged, and rank 0 writes the VCF / consensus and every report.
+    Trimmed reads are written per rank (``<name>.part<rank><ext>``).  For BAM input (libampbam) rank 0 joins the parts into
+    the ONE file the caller named and removes them.  For text input the reads are dealt out one by one and the parts are
+    NOT joined: they stay, and their records together are the one-process file's records in another order.
     """
     dist, rank, world = parallel.init_from_env()
     if device is None:
@@ -289,8 +291,6 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if run_trim and trimmed_reads_fn is not None and world > 1:
             # every rank writes the trimmed reads of its share to a file of its own; rank 0 joins them into the ONE file the
             # caller asked for once every rank is done (BGZF members concatenate: bam_native.stitch_bam_parts)
-            if rank == 0 and trimmed_reads_fn.lower() != "stdout" and isfile(trimmed_reads_fn):
-                error("File already exists: %s" % trimmed_reads_fn)
             final_trimmed_fn = trimmed_reads_fn
             root, ext = os.path.splitext(trimmed_reads_fn)
             trimmed_reads_fn = "%s.part%d%s" % (root, rank, ext)
@@ -306,6 +306,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
+        if rank == 0 and final_trimmed_fn is not None and final_trimmed_fn.lower() != "stdout" and isfile(final_trimmed_fn):
+            raise FileExistsError("File already exists: %s" % final_trimmed_fn)      # (only rank 0 looks: carried to the exchange like the rest)
         if run_trim:
             print_log("Input untrimmed SAM/BAM: %s" % untrimmed_reads_fn)
             print_log("Output trimmed SAM/BAM: %s" % trimmed_reads_fn)
@@ -392,6 +394,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         # where the one before it ended: what makes the split of ampbam_open_range exact)
         trouble = parallel.exchange_notes(dist, world, driver.seam if driver is not None else [None, None], rank_error)
         if trouble:
+            print_log("ERROR: %s" % trouble)          # (every rank's log names the rank that failed and what it failed of)
             eng.close()
             parallel.finish(dist)
             if rank_error is not None:

@@ -711,6 +711,9 @@ int ampbam_open_range_at(const char *path, int n_threads, int part, int n_parts,
         return AMPBAM_OK;
     };
     if (b_lo >= nb || b_lo >= b_hi) {                     // an empty part (more parts than blocks)
+        // a walk that knows where the part before this one ended keeps that place: the record that starts there may have begun
+        // in front of the block this part would start with, and the part behind this one is opened at this part's end
+        if (first_hint != UINT64_MAX && part > 0 && first_hint > f->img_base) f->part_first = f->part_end = first_hint;
         f->rec_off.push_back(0);
         *out = f;
         return AMPBAM_OK;

@@ -225,12 +225,14 @@ class NativeInput:
         self.seam = [None, None]
         cur = self.first_part()
         self._first = None
+        exact = self.k_lo == 0          # the walk knows where a record starts: from the file's first piece on, else from its first record on
         for k in range(self.k_lo, self.k_hi):
-            # the piece behind this one starts where this one ends: it is told so, and only the rank's FIRST piece (whose
-            # predecessor another rank reads) is found by the codec's chain-of-plausible-records search
+            # the piece behind this one starts where this one ends: it is told so, and only the rank's FIRST pieces (whose
+            # predecessor another rank reads), up to the first with a record, are found by the codec's chain-of-plausible-records
+            # search (a guessed piece without records does not know where it ends; a told one hands on what it was told)
             a, b = cur.part_range()
+            exact = exact or cur.n_records > 0
             if k + 1 < self.k_hi:
-                exact = cur.n_records > 0 or k > self.k_lo or self.k_lo == 0      # (a guessed piece without records does not know where it ends)
                 self._start(k + 1, b if exact else None)
             if cur.n_records:
                 if prev_end is not None and a != prev_end:

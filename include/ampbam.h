@@ -68,7 +68,8 @@ int ampbam_open_range(const char *path, int n_threads, int part, int n_parts, am
 /* The same when the caller KNOWS where the part's first record starts -- the inflated offset at which the part before it ended
  * (ampbam_part_range of that part): nothing is guessed, which is how one process walks a file piece by piece (only a rank's
  * first piece needs the heuristic above).  first_hint == UINT64_MAX: ampbam_open_range.  A hint at or behind the part's last
- * block means no record starts in the part: an empty part whose range is (hint, hint).  AMPBAM_EINVAL for a hint in front of
+ * block means no record starts in the part: an empty part whose range is (hint, hint); a part without a block of its own
+ * (more parts than blocks) has that range too, so that the part behind it is told the same place.  AMPBAM_EINVAL for a hint in front of
  * the part's first block, AMPBAM_EFORMAT when no chain of records runs from the hint to the part's end. */
 int ampbam_open_range_at(const char *path, int n_threads, int part, int n_parts, uint64_t first_hint, ampbam_file **out);
 /* Offsets in the file's INFLATED stream of the part's first record and of the byte behind its last record (equal for a

@@ -394,6 +394,49 @@ def test_piece_walk_does_not_guess_record_starts(tmp_path, monkeypatch):
         assert total == 500, n_parts
 
 
+def test_piece_walk_with_pieces_smaller_than_a_block(tmp_path, monkeypatch):
+    """AMPLIPY_PART_BYTES below the size of a BGZF block: some pieces hold no block at all.  Such a piece inside a walk keeps the
+    place where the piece before it ended (a record of the Python codec's files straddles the block boundary, so that place is
+    not the next block's start) and hands it on; it used to report the block's start, and the piece behind it was opened in the
+    middle of a record.  One process and the ranks of worlds 2 and 3 each walk their run of pieces to the whole file's rows,
+    and the shares of neighbouring ranks meet."""
+    from amplipy_amd import amplipy
+    from tools.e2e_legs import write_bam
+    g = synth.make_genome(); primers, amps = synth.make_artic_scheme()
+    hb = synth.make_amplicon_batch(g, amps, 3000, seed=6)
+    bam = str(tmp_path / "s.bam")
+    write_bam(bam, hb, int(g.size))
+    whole = bam_native.BamFile(bam)
+    wb, _ = whole.decode(0, whole.n_records, copy=True)
+    whole.close()
+    assert wb.n == hb.n
+    with open(bam, "rb") as f:
+        n_blocks = sum(1 for _ in bamio.bgzf_blocks(f))
+    monkeypatch.setenv("AMPLIPY_PART_BYTES", "3000")
+    for world in (1, 2, 3):
+        rows, seams, n_empty = [], [], 0
+        for rank in range(world):
+            src = amplipy.NativeInput(bam, rank, world)
+            assert src.n_parts > 2 * n_blocks
+            for piece in src:
+                n_empty += piece.n_records == 0
+                if piece.n_records:
+                    rows.append(piece.decode(0, piece.n_records, copy=True)[0])
+                piece.close()
+            seams.append(src.seam)
+        assert n_empty > n_blocks
+        assert np.array_equal(np.concatenate([r.pos for r in rows]), wb.pos) and np.array_equal(np.concatenate([r.qual for r in rows]), wb.qual), world
+        assert all(x[1] == y[0] for x, y in zip(seams[:-1], seams[1:])), (world, seams)
+    # the chain of hinted opens over more parts than blocks: every part starts where the one before it ended
+    end = None
+    for k in range(64):
+        f = bam_native.BamFile(bam, part=k, n_parts=64, first_hint=end)
+        a, b = f.part_range()
+        assert end is None or a == end, k
+        end = b
+        f.close()
+
+
 def test_write_batch_round_trip(tmp_path):
     """ampbam_write_batch (files made from packed rows: the benchmarks' inputs): odd and even read lengths, indel CIGARs, a read
     without qualities; libampbam's own reader and the Python codec read back what was packed."""
