@@ -95,6 +95,18 @@ EP_CYCLES = 512                # cycles from the 5' end of the stored SEQ; the l
 EP_QUALS = 94                  # reported qualities; the last bin is open-ended
 EP_CYC_SHAPE, EP_QUAL_SHAPE, EP_SUB_SHAPE = (2, EP_CYCLES, 2), (2, EP_QUALS, 2), (2, 2, 2, 4, 4)
 
+# ---- read haplotypes per region (amp_hap_*): amp_hap_entry[used], amp_hap_info, tally uint64[n_regions][HAP_TALLY_COLS], reads uint64[2] ----
+HAP_MAX_DIFFS = 13             # differences of a key at most; a read with more is tallied as OVERFLOW
+HAP_MAX_REGION = 4096          # positions of a region at most
+HAP_MAX_REGIONS = 1 << 16      # more is refused with AMP_EINVAL
+HAP_TALLY_COLS = 6
+HAP_COVER, HAP_REF, HAP_REF_REV, HAP_LOWQ, HAP_OVERFLOW, HAP_EDGE = range(6)       # the columns of tally
+HAP_KIND_N, HAP_KIND_DEL = 4, 5                                  # kinds 0..3: a substitution to A C G T
+HAP_LOG2_DEFAULT, HAP_LOG2_MIN, HAP_LOG2_MAX = 20, 4, 28        # slots of the device table (64 bytes each): 0 asks for the default
+HAP_ENTRY_DTYPE = np.dtype([("head", "<u4"), ("diff", "<u4", (HAP_MAX_DIFFS,)), ("count", "<u4"), ("rev", "<u4")])
+HAP_INFO_FIELDS = ("used", "capacity", "lost")                   # amp_hap_info, uint64 each
+assert HAP_ENTRY_DTYPE.itemsize == 64
+
 # ---- QC report (amp_qc_*) ----
 QC_MAX_DEPTHS = 4
 

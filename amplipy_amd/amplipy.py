@@ -16,7 +16,7 @@ from os.path import isfile
 
 import numpy as np
 
-from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, cooc as cooc_mod, deletion as deletion_mod, errprof as errprof_mod, lib, parallel, qc, strand as strand_mod
+from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, cooc as cooc_mod, deletion as deletion_mod, errprof as errprof_mod, haplotype as hap_mod, lib, parallel, qc, strand as strand_mod
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -80,10 +80,11 @@ def open_device_bam_text(input_fn, output_fn):
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
-    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False, errprof=False):
+    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False, errprof=False, hap=False):
         """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables);
         amplicon: likewise the seven keys of --amplicons, behind them; codon: likewise the five keys of --codons; deletion:
-        likewise the two keys of --deletions; cooc: likewise the key of --cooc; errprof: likewise the two keys of --error_profile, last."""
+        likewise the two keys of --deletions; cooc: likewise the key of --cooc; errprof: likewise the two keys of --error_profile;
+        hap: likewise the two keys of --haplotypes, last."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -118,16 +119,18 @@ class VcfWriter:
             w(cooc_mod.HEADER_LINES)
         if errprof:
             w(errprof_mod.HEADER_LINES)
+        if hap:
+            w(hap_mod.HEADER_LINES)
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
-    def line(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None):
-        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon, deletion, cooc, errprof)
+    def line(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None):
+        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon, deletion, cooc, errprof, hap)
 
-    def write(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None):
-        self.f.write(self.line(r, strand, amplicon, codon, deletion, cooc, errprof))
+    def write(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None):
+        self.f.write(self.line(r, strand, amplicon, codon, deletion, cooc, errprof, hap))
 
-    def write_all(self, records, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None):
-        self.f.write("".join([self.line(r, strand, amplicon, codon, deletion, cooc, errprof) for r in records]))
+    def write_all(self, records, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None):
+        self.f.write("".join([self.line(r, strand, amplicon, codon, deletion, cooc, errprof, hap) for r in records]))
 
     def close(self):
         if self.f is not sys.stdout:
@@ -141,7 +144,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 device=None, gpu_sam=None, gpu_bam=None, gpu_bam_write=None, qc_fn=None, qc_regions_fn=None, qc_depths=None,
                 qc_depth_fn=None, strand=False, strand_fn=None, amplicons_fn=None, amplicon_out_fn=None, codons_fn=None,
                 codon_out_fn=None, aa_out_fn=None, deletions=False, del_out_fn=None, indel_vcf_fn=None, del_capacity=None, cooc_fn=None,
-                cooc_out_fn=None, error_profile_fn=None, error_mask_fn=None):
+                cooc_out_fn=None, error_profile_fn=None, error_mask_fn=None, haplotypes_fn=None, hap_out_fn=None, hap_min_reads=None,
+                hap_min_freq=None, hap_capacity=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -190,6 +194,13 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     error_mask_fn: positions that take no part, as a VCF (of a first run, say) or a BED file; WITHOUT A MASK THE SITE'S OWN BASES
     ARE PART OF THE RATE, so a real variant at high frequency raises the rate it is held against.  With error_profile_fn None
     the engine's hook is never switched on.
+    haplotypes_fn (default: off; runs with a count table): the region file, a BED (ref, start, end, name; 0-based, half-open; 1 to
+    4096 positions a region).  The device tallies, behind every batch's read pass, per region the distinct
+    sets of differences from the reference -- substitutions and deletions, never insertions -- that single reads carry over the
+    whole region, and the reads that carry each; every VCF record also carries HAP_N and HAP.  hap_out_fn: the haplotype table as
+    a TSV file, mutations 1-based in the grammar of cooc_fn; hap_min_reads (2) and hap_min_freq (0): what it lists.  hap_capacity:
+    log2 of the device table's slots (default 20).  Reads whose haplotype the table had no slot for end the run with an error.
+    With haplotypes_fn None the engine's hook is never switched on.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -249,6 +260,16 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("The error mask (--error_mask) needs the error profile (--error_profile)")
     if error_profile_fn is not None and not (run_variants or run_consensus):
         error("A run that only trims has no count table: no error profile (--error_profile, --error_mask)")
+    if haplotypes_fn is None and (hap_out_fn is not None or hap_capacity is not None):
+        error("The haplotype table and its size (--hap_out, --hap_capacity) need the region file (--haplotypes)")
+    if haplotypes_fn is not None and not (run_variants or run_consensus):
+        error("A run that only trims has no count table: no read haplotypes (--haplotypes, --hap_out)")
+    if hap_capacity is not None and not abi.HAP_LOG2_MIN <= hap_capacity <= abi.HAP_LOG2_MAX:
+        error("--hap_capacity is the log2 of the table's slots, %d to %d: %s" % (abi.HAP_LOG2_MIN, abi.HAP_LOG2_MAX, hap_capacity))
+    if hap_min_reads is not None and hap_min_reads < 0:
+        error("--hap_min_reads must be non-negative: %s" % hap_min_reads)
+    if hap_min_freq is not None and not 0 <= hap_min_freq <= 1:
+        error("--hap_min_freq must be between 0 and 1: %s" % hap_min_freq)
     del_on = bool(deletions) or del_out_fn is not None or indel_vcf_fn is not None
     if del_on and not (run_variants or run_consensus):
         error("A run that only trims has no count table: no deletion events (--deletions, --del_out, --indel_vcf)")
@@ -302,7 +323,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = cooc_sets = cooc_file = ep_file = ep_mask = None
+    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = cooc_sets = cooc_file = ep_file = ep_mask = hap_regions = hap_file = None
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
@@ -321,7 +342,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
             vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None, codon=codons_fn is not None, deletion=bool(deletions),
-                            cooc=cooc_fn is not None, errprof=error_profile_fn is not None)
+                            cooc=cooc_fn is not None, errprof=error_profile_fn is not None, hap=haplotypes_fn is not None)
             if amplicon_out_fn is not None:
                 amp_file = qc.open_new(amplicon_out_fn)
         if strand_fn is not None and rank == 0:
@@ -349,6 +370,11 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 ep_mask = errprof_mod.load_mask(error_mask_fn, G)
             if rank == 0:
                 ep_file = qc.open_new(error_profile_fn)
+        if haplotypes_fn is not None:
+            print_log("Loading haplotype regions: %s" % haplotypes_fn)
+            hap_regions = hap_mod.load_regions(haplotypes_fn, ref_id, G)
+            if rank == 0:
+                hap_file = qc.open_new(hap_out_fn) if hap_out_fn is not None else None
         if qc_on:
             qc_regions = [(0, G, qc.WHOLE)] + (qc.load_regions(qc_regions_fn) if qc_regions_fn is not None else [])
             qc_primers = qc.load_primer_rows(primer_fn) if run_trim else []
@@ -378,6 +404,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         cooc_mod.enable(eng, cooc_sets)
     if error_profile_fn is not None and rank_error is None:
         errprof_mod.enable(eng, ref_seq, ep_mask)
+    if hap_regions is not None and rank_error is None:
+        hap_mod.enable(eng, hap_regions, ref_seq, hap_capacity)
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -416,6 +444,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             cooc_read_parts = parallel.gather_objects(dist, rank, world, eng.cooc_tables()[1])
         if del_on:                       # ... and every rank's events: rank 0 sums them per key on the host
             del_parts = parallel.gather_objects(dist, rank, world, eng.del_events())
+        if hap_regions is not None:      # ... and every rank's haplotype entries and tallies, likewise
+            hap_parts = parallel.gather_objects(dist, rank, world, eng.hap_tables())
         if final_trimmed_fn is not None and driver.part_writer is not None:
             # the ranks' files (all closed by now: the writer threads were joined in run()) become the one trimmed BAM
             parts = parallel.gather_objects(dist, rank, world, (driver.part_writer.path, driver.part_writer.header_bytes))
@@ -429,7 +459,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     failed = True
     try:
         qc_depth = qc_region_recs = ep_tables = None
-        del_lost = 0
+        del_lost = hap_lost = 0
+        hap_tables = None
         if qc_on and rank == 0:
             qc_tallies = qc.merge_read_tallies(qc_parts) if dist is not None else eng.qc_read_tallies()
         if do_count:
@@ -514,6 +545,20 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                     del_lost = eng.del_events()[1]["lost"]
                 if rank == 0:
                     del_tables = deletion_mod.Tables(d_events, eng.counts(), ref_seq, v_min_depth, v_min_freq)
+            if hap_regions is not None:
+                if dist is None:
+                    h_entries, h_info, h_tally, h_reads = eng.hap_tables()
+                    hap_lost = h_info["lost"]
+                elif rank == 0:
+                    h_entries = hap_mod.merge_entries([part[0] for part in hap_parts])
+                    hap_lost = sum(part[1]["lost"] for part in hap_parts)
+                    h_tally = np.sum([np.asarray(part[2], np.uint64) for part in hap_parts], axis=0, dtype=np.uint64)
+                    h_reads = np.sum([np.asarray(part[3], np.uint64) for part in hap_parts], axis=0, dtype=np.uint64)
+                else:
+                    hap_lost = eng.hap_tables()[1]["lost"]
+                if rank == 0:
+                    hap_tables = hap_mod.Tables(hap_regions, ref_seq, h_entries, h_tally, h_reads, hap_lost, 2 if hap_min_reads is None else hap_min_reads,
+                                                hap_min_freq or 0.0, v_min_freq)
 
             def ins_tallies(positions):
                 triples = loop.ins_store.counted_pairs(positions)
@@ -525,7 +570,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 run_variants = run_consensus = False       # rank 0 writes the outputs
             if run_variants:
                 vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables, codon_tables,
-                                         del_tables if deletions else None, cooc_tables, ep_tables))      # (= vcf.write(r) for r in res.records)
+                                         del_tables if deletions else None, cooc_tables, ep_tables, hap_tables))      # (= vcf.write(r) for r in res.records)
                 vcf.close()
             if indel_file is not None:
                 deletion_mod.write_indel_vcf(indel_file, ref_id, del_tables, deletion_mod.insertion_rows(res.records), " ".join(sys.argv))
@@ -555,6 +600,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if ep_file is not None:
             qc.write_json(ep_file, ep_tables.report())
             print_log("Output error profile: %s" % error_profile_fn)
+        if hap_file is not None:
+            hap_mod.write_tsv(hap_file, ref_id, hap_tables)
+            print_log("Output haplotype table: %s" % hap_out_fn)
         if qc_on and rank == 0:
             if qc_fn is not None:
                 report = qc.build_report(
@@ -577,11 +625,15 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(cooc_tables.summary_line())
         if ep_tables is not None:
             print_log(ep_tables.summary_line())
+        if hap_tables is not None:
+            print_log(hap_tables.summary_line())
         if del_on:
             deletion_mod.check_lost(del_lost)              # (behind the run's last collective: no rank is left waiting)
+        if hap_regions is not None:
+            hap_mod.check_lost(hap_lost)                   # (likewise)
         failed = False
     finally:
-        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file, cooc_file, ep_file]:
+        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file, cooc_file, ep_file, hap_file]:
             if f is not None:
                 f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)
@@ -670,6 +722,11 @@ def parse_args(argv=None):
         p.add_argument("--cooc_out", required=False, type=str, default=None, help="Reads per mutation set and pattern of mutations carried (TSV or TSV.gz; needs --cooc)")
         p.add_argument("--error_profile", required=False, type=str, default=None, help="Error profile (JSON): how often a base differs from the reference by sequencing cycle, by reported quality and by substitution class, tallied on the device over every match base; ERR_RATE and ERR_P on every VCF record. Without --error_mask the site's own bases are part of the rate (variants, consensus, aio)")
         p.add_argument("--error_mask", required=False, type=str, default=None, help="Positions that take no part in the error profile, the known or called variants: a .vcf / .vcf.gz (every record masks its REF span) or a BED (columns 2 and 3; .gz allowed); needs --error_profile")
+        p.add_argument("--haplotypes", required=False, type=str, default=None, help="Region file (BED: ref, start, end, name; 0-based, half-open; 1 to 4096 positions a region): per region, the distinct sets of substitutions and deletions single reads carry over the whole region, tallied on the device, and HAP_N and HAP on every VCF record; insertions are not part of a haplotype (variants, consensus, aio)")
+        p.add_argument("--hap_out", required=False, type=str, default=None, help="Reads per region and haplotype, mutations 1-BASED in the grammar of --cooc (TSV or TSV.gz; needs --haplotypes)")
+        p.add_argument("--hap_min_reads", required=False, type=int, default=2, help="A haplotype below this many reads is not written")
+        p.add_argument("--hap_min_freq", required=False, type=float, default=0.0, help="A haplotype below this share of the region's usable reads is not written")
+        p.add_argument("--hap_capacity", required=False, type=int, default=None, help="log2 of the slots of the haplotype table on the device, 4 to 28 (20 when omitted)")
         p.add_argument("--strand_out", required=False, type=str, default=None, help="Count, reverse-strand count and quality sum of every position and symbol (TSV or TSV.gz; variants, consensus, aio)")
     return parser.parse_args(argv)
 
@@ -683,7 +740,8 @@ def main(argv=None):
     qc_args.update(strand=args.strand, strand_fn=args.strand_out, amplicons_fn=args.amplicons, amplicon_out_fn=args.amplicon_out,
                    codons_fn=args.codons, codon_out_fn=args.codon_out, aa_out_fn=args.aa_out, deletions=args.deletions,
                    del_out_fn=args.del_out, indel_vcf_fn=args.indel_vcf, del_capacity=args.del_capacity, cooc_fn=args.cooc, cooc_out_fn=args.cooc_out,
-                   error_profile_fn=args.error_profile, error_mask_fn=args.error_mask)
+                   error_profile_fn=args.error_profile, error_mask_fn=args.error_mask, haplotypes_fn=args.haplotypes, hap_out_fn=args.hap_out,
+                   hap_min_reads=args.hap_min_reads, hap_min_freq=args.hap_min_freq, hap_capacity=args.hap_capacity)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,

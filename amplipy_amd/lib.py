@@ -44,6 +44,7 @@ EXPORTS = [
     "amp_del_enable", "amp_del_get", "amp_del_add", "amp_del_last_ms",
     "amp_cooc_enable", "amp_cooc_get", "amp_cooc_add", "amp_cooc_last_ms",
     "amp_errprof_enable", "amp_errprof_get", "amp_errprof_add", "amp_errprof_last_ms",
+    "amp_hap_enable", "amp_hap_get", "amp_hap_add", "amp_hap_last_ms",
 ]
 
 
@@ -518,6 +519,54 @@ class Engine:
 
     def errprof_last_ms(self):
         return self._hook_last_ms("amp_errprof_last_ms")
+
+    # ---- read haplotypes per region ----------------------------------------------------
+    def hap_enable(self, starts, ends, ref_seq, log2_capacity=0):
+        """amp_hap_enable: the hook on for the regions [starts[k], ends[k]) (0-based, sorted by start, 1 to 4096 positions each)
+        and the reference letters ``ref_seq`` (str or bytes of ref_len letters), the tables zero, 2^log2_capacity slots (0: the
+        default).  ``hap_disable`` turns it off; the tables stay readable."""
+        st = np.ascontiguousarray(starts, np.int32); en = np.ascontiguousarray(ends, np.int32)
+        if st.ndim != 1 or st.size != en.size or st.size == 0:
+            raise ValueError("one start and one end per region, at least one region")
+        ref = np.frombuffer(ref_seq.encode("ascii") if isinstance(ref_seq, str) else bytes(ref_seq), np.uint8)
+        if ref.size != self.ref_len:
+            raise ValueError("the reference has %d letters, the engine %d positions" % (ref.size, self.ref_len))
+        pad = ref if ref.size else np.zeros(1, np.uint8)
+        self._chk(self.L.amp_hap_enable(self.h, C.c_int32(st.size), C.c_void_p(abi.ptr(st)), C.c_void_p(abi.ptr(en)), C.c_void_p(abi.ptr(pad)),
+                                        C.c_int(int(log2_capacity))), "amp_hap_enable")
+        self._hap_regions = int(st.size)
+
+    def hap_disable(self):
+        self._chk(self.L.amp_hap_enable(self.h, C.c_int32(0), None, None, None, C.c_int(0)), "amp_hap_enable")
+
+    def hap_tables(self):
+        """amp_hap_get -> (abi.HAP_ENTRY_DTYPE[used] ordered by the 14 key words, {"used", "capacity", "lost"},
+        tally uint64[n_regions][6]: COVER REF REF_REV LOWQ OVERFLOW EDGE, reads uint64[2]: covering, other) as they stand."""
+        nr = getattr(self, "_hap_regions", 0)
+        n = C.c_int64(0)
+        info = np.zeros(len(abi.HAP_INFO_FIELDS), np.uint64)
+        tally = np.zeros((max(nr, 1), abi.HAP_TALLY_COLS), np.uint64); reads = np.zeros(2, np.uint64)
+        args = (C.byref(n), C.c_void_p(abi.ptr(info)), C.c_void_p(abi.ptr(tally)), C.c_void_p(abi.ptr(reads)))
+        rc = self.L.amp_hap_get(self.h, None, C.c_int64(0), *args)
+        ev = np.zeros(max(int(n.value), 1), abi.HAP_ENTRY_DTYPE)
+        if rc == -1 and n.value > 0:            # (AMP_EINVAL with the needed size: the table is not empty)
+            rc = self.L.amp_hap_get(self.h, C.c_void_p(abi.ptr(ev)), C.c_int64(ev.size), *args)
+        self._chk(rc, "amp_hap_get")
+        return ev[:int(n.value)], {k: int(v) for k, v in zip(abi.HAP_INFO_FIELDS, info)}, tally[:nr], reads
+
+    def hap_add(self, entries, tally=None, reads=None):
+        """amp_hap_add: host entries (abi.HAP_ENTRY_DTYPE) through the kernel's insert path, tally and reads added element-wise
+        (the merge of partial tables)."""
+        ev = np.ascontiguousarray(entries, abi.HAP_ENTRY_DTYPE)
+        t = None if tally is None else np.ascontiguousarray(tally, np.uint64)
+        r = None if reads is None else np.ascontiguousarray(reads, np.uint64)
+        assert t is None or t.size == getattr(self, "_hap_regions", 0) * abi.HAP_TALLY_COLS
+        assert r is None or r.size == 2
+        self._chk(self.L.amp_hap_add(self.h, C.c_void_p(abi.ptr(ev)) if ev.size else None, C.c_int64(ev.size), C.c_void_p(abi.ptr(t)),
+                                     C.c_void_p(abi.ptr(r))), "amp_hap_add")
+
+    def hap_last_ms(self):
+        return self._hook_last_ms("amp_hap_last_ms")
 
     # ---- calling ---------------------------------------------------------------------
     def set_reference(self, ref_seq):

@@ -865,6 +865,62 @@ int amp_errprof_add(amp_ctx *ctx, const uint64_t *cyc, const uint64_t *qualt, co
 /* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_errprof_last_ms(amp_ctx *ctx, float *ms);
 
+/* ---- read haplotypes per region: distinct mutation sets on single reads (opt-in) ------------------------------
+ * Which combinations of differences from the reference exist on single reads over a stretch, and how many reads carry each?
+ * REGIONS: [start, end), 0-based, 1 to AMP_HAP_MAX_REGION positions each, at most 2^16, sorted by start; they may overlap.
+ * READS: only reads with status 0, as they were counted (the trimmed alignment [pos, ref_end) with do_trim), with a regular CIGAR
+ * (as for the co-occurrence tallies).  Every other status-0 read, and a regular read that covers no region: reads[1] += 1 and
+ * nothing else.  A read that covers at least one region: reads[0] += 1.  A read is tried against every region with pos <= start
+ * and end <= ref_end; inside it every position is a match position or a deleted one (inside a D or N op).
+ * A TRIAL adds tally[region][COVER] += 1, then exactly one of, tested in this order:
+ *   1 EDGE      the region's first or last position is deleted (the run may go on outside the region: it cannot be named);
+ *   2 LOWQ      some match position has a reference letter among A C G T (either case), a read base that differs from it and a
+ *               quality below min_quality (a read without QUAL, 0xFF, counts as below, as everywhere else);
+ *   3 OVERFLOW  the differences (below) are more than AMP_HAP_MAX_DIFFS;
+ *   4 REF       there are none: tally[region][REF] += 1, and tally[region][REF_REV] += 1 when the FLAG has 0x10;
+ *   5           the key (region, differences) goes to the table: count += 1, and rev += 1 when reverse.
+ * DIFFERENCES, in ascending offset: a maximal run of deleted positions is one difference of kind 5 with its length (after the EDGE
+ * test both flanks are match positions inside the region); a match position whose reference letter is among A C G T, whose read
+ * base differs from it and whose quality is at or above min_quality is one of kind 0..3 for A C G T, 4 for N.  A position whose
+ * reference letter is not A C G T is never a difference; a low-quality base that equals the reference is none and does not
+ * disqualify the read.  INSERTIONS ARE NOT DIFFERENCES, as they are not co-occurrence sites: two reads that differ only by an
+ * insertion fall together; the insertion alleles are in the VCF.
+ * THE DIFFERENCE WORD: bits 0-11 the offset in the region, 12-14 the kind, 15-27 the deletion length (0: a substitution), the rest
+ * zero.  THE KEY: 14 words: head = region index | n_diffs << 16, then 13 difference words, the unused ones zero.
+ * THE INVARIANT, per region: COVER == REF + LOWQ + OVERFLOW + EDGE + the counts of the region's entries + its lost reads.
+ * The table is an open-addressed hash table on the device that persists across batches; a read whose key finds no slot (every
+ * probe loop is bounded) adds to `lost` -- counted, never merged into another key.  amp_reset zeroes the tables. */
+#define AMP_HAP_MAX_DIFFS 13
+#define AMP_HAP_MAX_REGION 4096
+#define AMP_HAP_TALLY_COLS 6   /* COVER REF REF_REV LOWQ OVERFLOW EDGE */
+typedef struct amp_hap_entry {   /* 64 bytes */
+    uint32_t head;
+    uint32_t diff[13];
+    uint32_t count;
+    uint32_t rev;
+} amp_hap_entry;
+typedef struct amp_hap_info {
+    uint64_t used;              /* distinct keys the table holds */
+    uint64_t capacity;          /* its slots */
+    uint64_t lost;              /* reads whose key found no slot */
+} amp_hap_info;
+/* The hook on for the regions and the reference letters given (copied; the reference is packed once into 4-bit codes and a mask
+ * of its A C G T positions), the tables zero; 2^log2_capacity slots of 64 bytes (0: the default, 20; else 4 to 28).  A region that
+ * is unsorted, empty, too long or outside the reference, more than 2^16 regions, a bad capacity, regions without ref_ascii:
+ * AMP_EINVAL.  n_regions == 0 or a NULL start or end: off; the tables stay readable.  With the hook on and do_trim set,
+ * amp_process_batch_device refuses a dev_out without new_pos, new_ncig, new_cig or status (AMP_EINVAL) before anything runs. */
+int amp_hap_enable(amp_ctx *ctx, int32_t n_regions, const int32_t *start, const int32_t *end, const uint8_t *ref_ascii /* [ref_len] */, int log2_capacity);
+/* The used entries as they stand (waits for the stream), compacted on the device, ordered by their 14 key words; *n: their number.
+ * AMP_EINVAL, with the needed size in *n, when cap is smaller (info, tally and reads are filled in either way); AMP_ESTATE before
+ * the first enable.  n, info, tally and reads may be NULL, entries when cap is 0. */
+int amp_hap_get(amp_ctx *ctx, amp_hap_entry *entries, int64_t cap, int64_t *n, amp_hap_info *info, uint64_t *tally /* [n_regions][6] */,
+                uint64_t *reads /* [2] */);
+/* Host entries inserted through the kernel's own insert path, tally and reads added element-wise (the merge of partial tables): a
+ * call per job, not per batch.  tally and reads may be NULL. */
+int amp_hap_add(amp_ctx *ctx, const amp_hap_entry *entries, int64_t n, const uint64_t *tally, const uint64_t *reads);
+/* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+int amp_hap_last_ms(amp_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
