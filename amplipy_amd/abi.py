@@ -107,6 +107,11 @@ HAP_ENTRY_DTYPE = np.dtype([("head", "<u4"), ("diff", "<u4", (HAP_MAX_DIFFS,)), 
 HAP_INFO_FIELDS = ("used", "capacity", "lost")                   # amp_hap_info, uint64 each
 assert HAP_ENTRY_DTYPE.itemsize == 64
 
+# ---- read-position tallies per allele (amp_readpos_*): hist uint32[G][NSYM][RP_BINS] ----
+RP_BINS = 7                    # distance-to-end bins: d < 2, 2-3, 4-7, 8-15, 16-31, 32-63, >= 64
+RP_EDGES = (0, 2, 4, 8, 16, 32, 64)       # the least distance of each bin
+RP_CELLS = 42                  # NSYM * RP_BINS: the columns of one position on the wire
+
 # ---- QC report (amp_qc_*) ----
 QC_MAX_DEPTHS = 4
 

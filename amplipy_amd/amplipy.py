@@ -16,7 +16,7 @@ from os.path import isfile
 
 import numpy as np
 
-from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, cooc as cooc_mod, deletion as deletion_mod, errprof as errprof_mod, haplotype as hap_mod, lib, parallel, qc, strand as strand_mod
+from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, cooc as cooc_mod, deletion as deletion_mod, errprof as errprof_mod, haplotype as hap_mod, lib, parallel, qc, readpos as readpos_mod, strand as strand_mod
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -80,11 +80,11 @@ def open_device_bam_text(input_fn, output_fn):
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
-    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False, errprof=False, hap=False):
+    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False, errprof=False, hap=False, readpos=False):
         """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables);
         amplicon: likewise the seven keys of --amplicons, behind them; codon: likewise the five keys of --codons; deletion:
         likewise the two keys of --deletions; cooc: likewise the key of --cooc; errprof: likewise the two keys of --error_profile;
-        hap: likewise the two keys of --haplotypes, last."""
+        hap: likewise the two keys of --haplotypes; readpos: likewise the six keys of --readpos, last."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -121,16 +121,18 @@ class VcfWriter:
             w(errprof_mod.HEADER_LINES)
         if hap:
             w(hap_mod.HEADER_LINES)
+        if readpos:
+            w(readpos_mod.HEADER_LINES)
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
-    def line(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None):
-        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon, deletion, cooc, errprof, hap)
+    def line(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None, readpos=None):
+        return calling.vcf_line(self.ref_id, r, strand, amplicon, codon, deletion, cooc, errprof, hap, readpos)
 
-    def write(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None):
-        self.f.write(self.line(r, strand, amplicon, codon, deletion, cooc, errprof, hap))
+    def write(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None, readpos=None):
+        self.f.write(self.line(r, strand, amplicon, codon, deletion, cooc, errprof, hap, readpos))
 
-    def write_all(self, records, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None):
-        self.f.write("".join([self.line(r, strand, amplicon, codon, deletion, cooc, errprof, hap) for r in records]))
+    def write_all(self, records, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None, readpos=None):
+        self.f.write("".join([self.line(r, strand, amplicon, codon, deletion, cooc, errprof, hap, readpos) for r in records]))
 
     def close(self):
         if self.f is not sys.stdout:
@@ -145,7 +147,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 qc_depth_fn=None, strand=False, strand_fn=None, amplicons_fn=None, amplicon_out_fn=None, codons_fn=None,
                 codon_out_fn=None, aa_out_fn=None, deletions=False, del_out_fn=None, indel_vcf_fn=None, del_capacity=None, cooc_fn=None,
                 cooc_out_fn=None, error_profile_fn=None, error_mask_fn=None, haplotypes_fn=None, hap_out_fn=None, hap_min_reads=None,
-                hap_min_freq=None, hap_capacity=None):
+                hap_min_freq=None, hap_capacity=None, readpos=False, readpos_end=None, readpos_fn=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -201,6 +203,12 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     a TSV file, mutations 1-based in the grammar of cooc_fn; hap_min_reads (2) and hap_min_freq (0): what it lists.  hap_capacity:
     log2 of the device table's slots (default 20).  Reads whose haplotype the table had no slot for end the run with an error.
     With haplotypes_fn None the engine's hook is never switched on.
+    readpos (default: off; runs that write a VCF): every VCF record also carries REF_RP, ALT_RP, REF_END, ALT_END, RPB and RPZ
+     -- where on its reads an allele sits: the supporting bases by their distance to the nearer end of the
+    read's kept bases in seven bins, the support within readpos_end (one of 2, 4, 8, 16, 32, 64; default 8) of a read end, a
+    Fisher p-value and a rank-sum z against the reference base -- from one more table the device tallies behind every batch's
+    read pass.  readpos_fn: the table of every position as a TSV file (runs with a count table); it alone switches the tallies on.
+    With both off the engine's hook is never switched on.
 
     One process drives one GPU.  Under ``torchrun`` (WORLD_SIZE > 1, or AMPLIPY_FORCE_DIST=1 for a one-rank
     rehearsal) the job is range-partitioned: rank r takes the r-th contiguous run of BAM records (coordinate
@@ -270,6 +278,17 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("--hap_min_reads must be non-negative: %s" % hap_min_reads)
     if hap_min_freq is not None and not 0 <= hap_min_freq <= 1:
         error("--hap_min_freq must be between 0 and 1: %s" % hap_min_freq)
+    if (readpos or readpos_fn is not None) and not (run_variants or run_consensus):
+        error("A run that only trims has no count table: no read-position tallies (--readpos, --readpos_out)")
+    if readpos and not run_variants:
+        error("The read-position INFO keys need a VCF (--readpos on variants or aio)")
+    if readpos_end is not None and not readpos:
+        error("The read-end distance (--readpos_end) needs --readpos")
+    if readpos_end is not None:
+        try:
+            readpos_mod.end_bins(readpos_end)
+        except ValueError as e:
+            error(str(e))
     del_on = bool(deletions) or del_out_fn is not None or indel_vcf_fn is not None
     if del_on and not (run_variants or run_consensus):
         error("A run that only trims has no count table: no deletion events (--deletions, --del_out, --indel_vcf)")
@@ -284,6 +303,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     if indel_vcf_fn is not None and not indel_vcf_fn.lower().endswith((".vcf", ".vcf.gz")):
         error("Invalid indel VCF extension (should be .vcf or .vcf.gz): %s" % indel_vcf_fn)
     strand_on = bool(strand) or strand_fn is not None
+    readpos_on = bool(readpos) or readpos_fn is not None
     qc_on = qc_fn is not None or qc_depth_fn is not None
     if qc_on:
         qc_depths = list(qc.DEFAULT_DEPTHS) if qc_depths is None else list(qc_depths)
@@ -323,7 +343,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = cooc_sets = cooc_file = ep_file = ep_mask = hap_regions = hap_file = None
+    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = cooc_sets = cooc_file = ep_file = ep_mask = hap_regions = hap_file = readpos_file = None
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
@@ -342,11 +362,14 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
             vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None, codon=codons_fn is not None, deletion=bool(deletions),
-                            cooc=cooc_fn is not None, errprof=error_profile_fn is not None, hap=haplotypes_fn is not None)
+                            cooc=cooc_fn is not None, errprof=error_profile_fn is not None, hap=haplotypes_fn is not None,
+                            readpos=bool(readpos))
             if amplicon_out_fn is not None:
                 amp_file = qc.open_new(amplicon_out_fn)
         if strand_fn is not None and rank == 0:
             strand_file = qc.open_new(strand_fn)
+        if readpos_fn is not None and rank == 0:
+            readpos_file = qc.open_new(readpos_fn)
         if del_on and rank == 0:
             del_file = qc.open_new(del_out_fn) if del_out_fn is not None else None
             indel_file = qc.open_new(indel_vcf_fn) if indel_vcf_fn is not None else None
@@ -406,6 +429,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         errprof_mod.enable(eng, ref_seq, ep_mask)
     if hap_regions is not None and rank_error is None:
         hap_mod.enable(eng, hap_regions, ref_seq, hap_capacity)
+    if readpos_on and rank_error is None:
+        eng.readpos_enable()
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -487,6 +512,16 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                     s_rev, s_qsum = strand_mod.from_wire(wire.cpu().numpy())
                 if rank == 0:
                     strand_tables = strand_mod.Tables(eng.counts(), s_rev, s_qsum)
+            readpos_tables = None
+            if readpos_on:
+                rp_hist = eng.readpos_tables()
+                if dist is not None:                       # one more all-reduce: the table as one int64 tensor of G x 42
+                    import torch
+                    wire = torch.from_numpy(readpos_mod.to_wire(rp_hist)).to("cuda:%d" % device)
+                    parallel.allreduce_table(dist, wire)
+                    rp_hist = readpos_mod.from_wire(wire.cpu().numpy())
+                if rank == 0:
+                    readpos_tables = readpos_mod.Tables(eng.counts(), rp_hist, readpos_mod.DEFAULT_END if readpos_end is None else readpos_end)
             amp_tables = None
             if amps is not None:
                 a_counts, a_reads = eng.amplicon_tables()
@@ -570,7 +605,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 run_variants = run_consensus = False       # rank 0 writes the outputs
             if run_variants:
                 vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables, codon_tables,
-                                         del_tables if deletions else None, cooc_tables, ep_tables, hap_tables))      # (= vcf.write(r) for r in res.records)
+                                         del_tables if deletions else None, cooc_tables, ep_tables, hap_tables,
+                                         readpos_tables if readpos else None))      # (= vcf.write(r) for r in res.records)
                 vcf.close()
             if indel_file is not None:
                 deletion_mod.write_indel_vcf(indel_file, ref_id, del_tables, deletion_mod.insertion_rows(res.records), " ".join(sys.argv))
@@ -603,6 +639,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         if hap_file is not None:
             hap_mod.write_tsv(hap_file, ref_id, hap_tables)
             print_log("Output haplotype table: %s" % hap_out_fn)
+        if readpos_file is not None:
+            readpos_mod.write_tsv(readpos_file, ref_id, readpos_tables)
+            print_log("Output read-position tallies: %s" % readpos_fn)
         if qc_on and rank == 0:
             if qc_fn is not None:
                 report = qc.build_report(
@@ -633,7 +672,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             hap_mod.check_lost(hap_lost)                   # (likewise)
         failed = False
     finally:
-        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file, cooc_file, ep_file, hap_file]:
+        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file, cooc_file, ep_file, hap_file, readpos_file]:
             if f is not None:
                 f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)
@@ -727,6 +766,9 @@ def parse_args(argv=None):
         p.add_argument("--hap_min_reads", required=False, type=int, default=2, help="A haplotype below this many reads is not written")
         p.add_argument("--hap_min_freq", required=False, type=float, default=0.0, help="A haplotype below this share of the region's usable reads is not written")
         p.add_argument("--hap_capacity", required=False, type=int, default=None, help="log2 of the slots of the haplotype table on the device, 4 to 28 (20 when omitted)")
+        p.add_argument("--readpos", action="store_true", help="VCF records also carry REF_RP, ALT_RP, REF_END, ALT_END, RPB and RPZ: where on its reads an allele sits, by distance to the nearer end of the read's kept bases (seven bins), with a Fisher p-value and a rank-sum z against the reference base (variants, aio)")
+        p.add_argument("--readpos_end", required=False, type=int, default=None, help="Distance below which a base counts as at a read end for REF_END, ALT_END and RPB: one of the bin edges 2, 4, 8, 16, 32, 64 (8 when omitted); needs --readpos")
+        p.add_argument("--readpos_out", required=False, type=str, default=None, help="The seven distance-to-end bins of every position and symbol (TSV or TSV.gz; variants, consensus, aio)")
         p.add_argument("--strand_out", required=False, type=str, default=None, help="Count, reverse-strand count and quality sum of every position and symbol (TSV or TSV.gz; variants, consensus, aio)")
     return parser.parse_args(argv)
 
@@ -741,7 +783,8 @@ def main(argv=None):
                    codons_fn=args.codons, codon_out_fn=args.codon_out, aa_out_fn=args.aa_out, deletions=args.deletions,
                    del_out_fn=args.del_out, indel_vcf_fn=args.indel_vcf, del_capacity=args.del_capacity, cooc_fn=args.cooc, cooc_out_fn=args.cooc_out,
                    error_profile_fn=args.error_profile, error_mask_fn=args.error_mask, haplotypes_fn=args.haplotypes, hap_out_fn=args.hap_out,
-                   hap_min_reads=args.hap_min_reads, hap_min_freq=args.hap_min_freq, hap_capacity=args.hap_capacity)
+                   hap_min_reads=args.hap_min_reads, hap_min_freq=args.hap_min_freq, hap_capacity=args.hap_capacity,
+                   readpos=args.readpos, readpos_end=args.readpos_end, readpos_fn=args.readpos_out)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,

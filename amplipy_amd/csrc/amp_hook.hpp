@@ -1,6 +1,6 @@
 // amp_hook.hpp -- the host shell of the opt-in kernels that run behind every batch's read pass: the QC
 // report (amp_qc.hip), the strand tallies (amp_strand.hip), the per-amplicon counts (amp_amplicon.hip), the codon tallies
-// (amp_codon.hip), the deletion events (amp_del.hip), the co-occurrence tallies (amp_cooc.hip), the error profile (amp_errprof.hip), the read haplotypes (amp_hap.hip).  What a hook needs to know of a ctx, and what the hooks have in common -- the check macro, the device
+// (amp_codon.hip), the deletion events (amp_del.hip), the co-occurrence tallies (amp_cooc.hip), the error profile (amp_errprof.hip), the read haplotypes (amp_hap.hip), the read-position tallies (amp_readpos.hip).  What a hook needs to know of a ctx, and what the hooks have in common -- the check macro, the device
 // guard, the timer round a launch, the grid rule, the merge of host tables, the check of a trimming pass's results, the common
 // part of a state and its construction, the frame of an enqueue, last_ms -- each once.  (What the three tally kernels share
 // on the device is amp_tally.hpp.)  amp_ctx (amp_ctx.hpp) keeps one slot (switch, state) per hook and amplihip.hip walks the
@@ -54,7 +54,7 @@ struct HookCtx {
 HookCtx ctx_hook(amp_ctx *c);
 
 // The hooks; the numeric order is the order their kernels run in behind the read pass.
-enum { HOOK_QC, HOOK_STRAND, HOOK_AMPLICON, HOOK_CODON, HOOK_DEL, HOOK_COOC, HOOK_ERRPROF, HOOK_HAP, N_HOOKS };
+enum { HOOK_QC, HOOK_STRAND, HOOK_AMPLICON, HOOK_CODON, HOOK_DEL, HOOK_COOC, HOOK_ERRPROF, HOOK_HAP, HOOK_READPOS, N_HOOKS };
 struct HookSlot {
     bool on;                    // the switch amplihip.hip reads per batch
     void *state;                // the hook's device state, owned by its unit; it outlives the switch (tables stay readable)
@@ -73,7 +73,7 @@ struct HookOps {
 };
 // One per unit; amplihip.hip keeps them in enum order.  (Not const objects, though nothing writes them: hipcc emits a const
 // object with a constant initialiser into the device image as well, host function pointers and all.)
-extern HookOps qc_hook, strand_hook, amplicon_hook, codon_hook, del_hook, cooc_hook, errprof_hook, hap_hook;
+extern HookOps qc_hook, strand_hook, amplicon_hook, codon_hook, del_hook, cooc_hook, errprof_hook, hap_hook, readpos_hook;
 
 // With trimming on, every result in `needs` must be there; otherwise the refusal is in q.err.  amplihip.hip asks in front of a
 // device batch's read pass, so that a refused call changes nothing; an enqueue asks again.

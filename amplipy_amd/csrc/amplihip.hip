@@ -274,7 +274,7 @@ HookCtx ctx_hook(amp_ctx *c) {
 HookSlot &hook_slot(amp_ctx *c, int which) { return c->hooks[which]; }
 }  // namespace amp
 
-static const HookOps *const HOOKS[N_HOOKS] = {&qc_hook, &strand_hook, &amplicon_hook, &codon_hook, &del_hook, &cooc_hook, &errprof_hook, &hap_hook};      // in the enum's order: the run order
+static const HookOps *const HOOKS[N_HOOKS] = {&qc_hook, &strand_hook, &amplicon_hook, &codon_hook, &del_hook, &cooc_hook, &errprof_hook, &hap_hook, &readpos_hook};      // in the enum's order: the run order
 
 // The kernels of the hooks that are on, behind the read pass on the ctx stream, until one fails.
 static int enqueue_hooks(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *dev_out) {

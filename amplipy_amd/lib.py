@@ -45,6 +45,7 @@ EXPORTS = [
     "amp_cooc_enable", "amp_cooc_get", "amp_cooc_add", "amp_cooc_last_ms",
     "amp_errprof_enable", "amp_errprof_get", "amp_errprof_add", "amp_errprof_last_ms",
     "amp_hap_enable", "amp_hap_get", "amp_hap_add", "amp_hap_last_ms",
+    "amp_readpos_enable", "amp_readpos_get", "amp_readpos_add", "amp_readpos_last_ms",
 ]
 
 
@@ -567,6 +568,29 @@ class Engine:
 
     def hap_last_ms(self):
         return self._hook_last_ms("amp_hap_last_ms")
+
+    # ---- read-position tallies per allele ----------------------------------------------
+    def readpos_enable(self):
+        """amp_readpos_enable(1): the tallies on, the table zero.  ``readpos_disable`` turns them off."""
+        self._chk(self.L.amp_readpos_enable(self.h, C.c_int(1)), "amp_readpos_enable")
+
+    def readpos_disable(self):
+        self._chk(self.L.amp_readpos_enable(self.h, C.c_int(0)), "amp_readpos_enable")
+
+    def readpos_tables(self):
+        """amp_readpos_get -> hist uint32[ref_len][6][7] as it stands."""
+        hist = np.zeros((self.ref_len, abi.NSYM, abi.RP_BINS), np.uint32)
+        self._chk(self.L.amp_readpos_get(self.h, C.c_void_p(abi.ptr(hist))), "amp_readpos_get")
+        return hist
+
+    def readpos_add(self, hist):
+        """amp_readpos_add: a host table added element-wise (the merge of partial tables)."""
+        h = np.ascontiguousarray(hist, np.uint32)
+        assert h.size == self.ref_len * abi.RP_CELLS
+        self._chk(self.L.amp_readpos_add(self.h, C.c_void_p(abi.ptr(h))), "amp_readpos_add")
+
+    def readpos_last_ms(self):
+        return self._hook_last_ms("amp_readpos_last_ms")
 
     # ---- calling ---------------------------------------------------------------------
     def set_reference(self, ref_seq):

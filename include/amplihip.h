@@ -921,6 +921,26 @@ int amp_hap_add(amp_ctx *ctx, const amp_hap_entry *entries, int64_t n, const uin
 /* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_hap_last_ms(amp_ctx *ctx, float *ms);
 
+/* ---- read-position tallies per allele: where on its reads an allele sits (opt-in) ---------------------------
+ * For every increment the read pass makes to one of the six fixed keys A C G T N '-' of a position r (reads with status 0, the
+ * trimmed alignment with do_trim), hist[r][column][bin(d)] += 1.  [qs, qe) is the kept query span of the counted alignment
+ * (query_alignment_start / _end: the read without its soft clips).  A match base at query index q has d = min(q - qs, qe - 1 - q),
+ * the kept query bases between it and the nearer end; a deleted position (D, N) has d = max(0, min(q_next - qs, qe - q_next) - 1),
+ * the smaller distance of its two flanking bases, q_next being the query index of the next base behind the deletion.
+ * bin(d) = min(6, bit_length(d >> 1)): d < 2, 2-3, 4-7, 8-15, 16-31, 32-63, >= 64.  Insertion alleles are not part of the table.
+ * The sum of a cell's bins is the count table's cell, so 32 bits suffice wherever the count table's do.  amp_reset zeroes the table. */
+#define AMP_RP_BINS 7
+/* on != 0: the tallies on, the table (uint32[ref_len][AMP_NSYM][AMP_RP_BINS], allocated at the first call) zero.  on == 0: off; the
+ * table stays readable.  With the tallies on and do_trim set, amp_process_batch_device refuses a dev_out without new_pos, new_ncig,
+ * new_cig or status (AMP_EINVAL) before anything runs. */
+int amp_readpos_enable(amp_ctx *ctx, int on);
+/* Host copy of the table as it stands (waits for the stream); hist may be NULL.  AMP_ESTATE before the first enable. */
+int amp_readpos_get(amp_ctx *ctx, uint32_t *hist /* [ref_len][AMP_NSYM][AMP_RP_BINS] */);
+/* A host table added element-wise, like amp_add_counts (the merge of partial tables); hist may be NULL. */
+int amp_readpos_add(amp_ctx *ctx, const uint32_t *hist);
+/* Time of the tallies' kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+int amp_readpos_last_ms(amp_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
