@@ -8,8 +8,9 @@ from os.path import isfile
 
 import numpy as np
 
-from . import abi, lib
-from .readloop import error
+from . import abi, lib, parallel, qc
+from .readloop import error, print_log
+from .reports import Report
 from .strand import fisher_two_sided
 
 BAD_NAME_CHARS = ",;=|"
@@ -212,3 +213,36 @@ def add_to_report(report, tables):
     report["reads"]["no_amplicon"] = int(tables.amp_reads[-1])
     report["amplicons"] = tables.report_entries()
     return report
+
+
+class AmpliconReport(Report):
+    name, HEADER_LINES, outputs = "amplicon", HEADER_LINES, (("amplicon_out_fn", "per-amplicon counts", write_tsv),)
+    amps = None
+
+    def active(self, run):
+        return run.amplicons_fn is not None
+
+    def check(self, run):
+        if run.amplicon_out_fn is not None and run.amplicons_fn is None:
+            error("The per-amplicon table (--amplicon_out) needs the amplicon file (--amplicons)")
+        if run.amplicons_fn is not None and not (run.run_trim and run.run_variants and run.run_consensus):
+            error("Per-amplicon counts (--amplicons, --amplicon_out) work on aio only: reads are assigned to amplicons by their original "
+                  "coordinates against the primer BED, which only a run that trims has, and are counted for a VCF, which only a run that "
+                  "calls variants writes")
+
+    def load(self, run):
+        print_log("Loading amplicons: %s" % run.amplicons_fn)
+        self.amps = load_amplicons(run.amplicons_fn, qc.load_primer_rows(run.primer_fn), run.primer_pos_offset or 0, run.G)
+
+    def enable(self, run, eng):
+        enable(eng, self.amps)
+
+    def collect(self, run, eng):
+        counts, reads = eng.amplicon_tables()
+        counts = parallel.allreduce_numpy(run.dist, run.device, counts.astype(np.int64).reshape(-1)).astype(np.uint32).reshape(-1, abi.NSYM)
+        reads = parallel.gather_sum_reads(run.dist, run.rank, run.world, reads)
+        if run.rank == 0:
+            self.tables = Tables(self.amps, eng.counts(), counts, reads)
+
+    def add_to_qc(self, report):
+        add_to_report(report, self.tables)

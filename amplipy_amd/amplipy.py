@@ -12,11 +12,10 @@ import argparse
 import gzip
 import os
 import sys
+import types
 from os.path import isfile
 
-import numpy as np
-
-from . import AMPLIPY_VERSION, abi, amplicon as amplicon_mod, calling, codon as codon_mod, cooc as cooc_mod, deletion as deletion_mod, errprof as errprof_mod, haplotype as hap_mod, lib, parallel, qc, readpos as readpos_mod, strand as strand_mod
+from . import AMPLIPY_VERSION, calling, lib, parallel, qc, reports
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -81,10 +80,8 @@ class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
     def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False, errprof=False, hap=False, readpos=False):
-        """strand: the header also declares the five INFO keys of --strand (``line`` appends them when given the tables);
-        amplicon: likewise the seven keys of --amplicons, behind them; codon: likewise the five keys of --codons; deletion:
-        likewise the two keys of --deletions; cooc: likewise the key of --cooc; errprof: likewise the two keys of --error_profile;
-        hap: likewise the two keys of --haplotypes; readpos: likewise the six keys of --readpos, last."""
+        """Each keyword of calling.INFO_ORDER: the header also declares the INFO keys of that report, in that order (``line``
+        appends them when given the report's tables)."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -107,22 +104,8 @@ class VcfWriter:
         w("##INFO=<ID=ALT_DP,Number=1,Type=String,Description=\"Depth of alternate base\">\n")
         w("##INFO=<ID=REF_FREQ,Number=1,Type=Float,Description=\"Frequency of reference base\">\n")
         w("##INFO=<ID=ALT_FREQ,Number=1,Type=String,Description=\"Frequency of alternate base\">\n")
-        if strand:
-            w(strand_mod.HEADER_LINES)
-        if amplicon:
-            w(amplicon_mod.HEADER_LINES)
-        if codon:
-            w(codon_mod.HEADER_LINES)
-        if deletion:
-            w(deletion_mod.HEADER_LINES)
-        if cooc:
-            w(cooc_mod.HEADER_LINES)
-        if errprof:
-            w(errprof_mod.HEADER_LINES)
-        if hap:
-            w(hap_mod.HEADER_LINES)
-        if readpos:
-            w(readpos_mod.HEADER_LINES)
+        on = dict(zip(calling.INFO_ORDER, (strand, amplicon, codon, deletion, cooc, errprof, hap, readpos)))
+        w("".join([R.HEADER_LINES for R in reports.REGISTRY if on[R.name]]))
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
     def line(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None, readpos=None):
@@ -218,9 +201,14 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     the ONE file the caller named and removes them.  For text input the reads are dealt out one by one and the parts are
     NOT joined: they stay, and their records together are the one-process file's records in another order.
     """
+    run = types.SimpleNamespace(**locals())      # (first statement: the keyword arguments, under their names, and nothing else)
     dist, rank, world = parallel.init_from_env()
     if device is None:
         device = int(os.environ.get("LOCAL_RANK", "0")) if dist is not None else 0
+    v_min_depth = min_depth_variants if min_depth_variants is not None else 0
+    v_min_freq = min_freq_variants if min_freq_variants is not None else 0
+    vars(run).update(dist=dist, rank=rank, world=world, device=device, min_quality=min_quality if min_quality is not None else 20,
+                     v_min_depth=v_min_depth, v_min_freq=v_min_freq)
     # argument checks and banner: AmpliPy.py:836-866
     if primer_pos_offset is not None and primer_pos_offset < 0:
         error("Primer position offset must be non-negative: %s" % primer_pos_offset)
@@ -244,66 +232,10 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("QC regions and QC depth thresholds need a QC report (--qc)")
     if qc_depth_fn is not None and not (run_variants or run_consensus):
         error("A run that only trims has no count table: no per-position depth (--qc_depth_out)")
-    if (strand or strand_fn is not None) and not (run_variants or run_consensus):
-        error("A run that only trims has no count table: no strand tallies (--strand, --strand_out)")
-    if strand and not run_variants:
-        error("The strand INFO keys need a VCF (--strand on variants or aio)")
-    if amplicon_out_fn is not None and amplicons_fn is None:
-        error("The per-amplicon table (--amplicon_out) needs the amplicon file (--amplicons)")
-    if amplicons_fn is not None and not (run_trim and run_variants and run_consensus):
-        error("Per-amplicon counts (--amplicons, --amplicon_out) work on aio only: reads are assigned to amplicons by their original "
-              "coordinates against the primer BED, which only a run that trims has, and are counted for a VCF, which only a run that "
-              "calls variants writes")
-    if (codon_out_fn is not None or aa_out_fn is not None) and codons_fn is None:
-        error("The codon table and the amino-acid calls (--codon_out, --aa_out) need the CDS file (--codons)")
-    if codons_fn is not None and not (run_variants or run_consensus):
-        error("A run that only trims has no count table: no codon tallies (--codons, --codon_out, --aa_out)")
-    if aa_out_fn is not None and not run_variants:
-        error("The amino-acid calls (--aa_out) use the variant thresholds: variants or aio")
-    if cooc_out_fn is not None and cooc_fn is None:
-        error("The co-occurrence table (--cooc_out) needs the mutation-set file (--cooc)")
-    if cooc_fn is not None and not (run_variants or run_consensus):
-        error("A run that only trims has no count table: no co-occurrence tallies (--cooc, --cooc_out)")
-    if error_mask_fn is not None and error_profile_fn is None:
-        error("The error mask (--error_mask) needs the error profile (--error_profile)")
-    if error_profile_fn is not None and not (run_variants or run_consensus):
-        error("A run that only trims has no count table: no error profile (--error_profile, --error_mask)")
-    if haplotypes_fn is None and (hap_out_fn is not None or hap_capacity is not None):
-        error("The haplotype table and its size (--hap_out, --hap_capacity) need the region file (--haplotypes)")
-    if haplotypes_fn is not None and not (run_variants or run_consensus):
-        error("A run that only trims has no count table: no read haplotypes (--haplotypes, --hap_out)")
-    if hap_capacity is not None and not abi.HAP_LOG2_MIN <= hap_capacity <= abi.HAP_LOG2_MAX:
-        error("--hap_capacity is the log2 of the table's slots, %d to %d: %s" % (abi.HAP_LOG2_MIN, abi.HAP_LOG2_MAX, hap_capacity))
-    if hap_min_reads is not None and hap_min_reads < 0:
-        error("--hap_min_reads must be non-negative: %s" % hap_min_reads)
-    if hap_min_freq is not None and not 0 <= hap_min_freq <= 1:
-        error("--hap_min_freq must be between 0 and 1: %s" % hap_min_freq)
-    if (readpos or readpos_fn is not None) and not (run_variants or run_consensus):
-        error("A run that only trims has no count table: no read-position tallies (--readpos, --readpos_out)")
-    if readpos and not run_variants:
-        error("The read-position INFO keys need a VCF (--readpos on variants or aio)")
-    if readpos_end is not None and not readpos:
-        error("The read-end distance (--readpos_end) needs --readpos")
-    if readpos_end is not None:
-        try:
-            readpos_mod.end_bins(readpos_end)
-        except ValueError as e:
-            error(str(e))
-    del_on = bool(deletions) or del_out_fn is not None or indel_vcf_fn is not None
-    if del_on and not (run_variants or run_consensus):
-        error("A run that only trims has no count table: no deletion events (--deletions, --del_out, --indel_vcf)")
-    if deletions and not run_variants:
-        error("The deletion INFO keys need a VCF (--deletions on variants or aio)")
-    if indel_vcf_fn is not None and not run_variants:
-        error("The indel VCF (--indel_vcf) uses the variant thresholds: variants or aio")
-    if del_capacity is not None and not del_on:
-        error("The deletion events' table size (--del_capacity) needs --deletions, --del_out or --indel_vcf")
-    if del_capacity is not None and not abi.DEL_LOG2_MIN <= del_capacity <= abi.DEL_LOG2_MAX:
-        error("--del_capacity is the log2 of the table's slots, %d to %d: %s" % (abi.DEL_LOG2_MIN, abi.DEL_LOG2_MAX, del_capacity))
-    if indel_vcf_fn is not None and not indel_vcf_fn.lower().endswith((".vcf", ".vcf.gz")):
-        error("Invalid indel VCF extension (should be .vcf or .vcf.gz): %s" % indel_vcf_fn)
-    strand_on = bool(strand) or strand_fn is not None
-    readpos_on = bool(readpos) or readpos_fn is not None
+    every = [R() for R in reports.REGISTRY]
+    for r in every:
+        r.check(run)
+    on = [r for r in every if r.active(run)]
     qc_on = qc_fn is not None or qc_depth_fn is not None
     if qc_on:
         qc_depths = list(qc.DEFAULT_DEPTHS) if qc_depths is None else list(qc_depths)
@@ -319,6 +251,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         print_log("Loading reference genome: %s" % reference_fn)
         ref_id, ref_seq = load_ref_genome(reference_fn)
     G = len(ref_seq)
+    vars(run).update(G=G, ref_id=ref_id, ref_seq=ref_seq)
     eng = lib.Engine(G, device=device)
     if os.environ.get("AMPLIPY_DEV") == "1" and os.environ.get("AMPLIPY_KERNEL_VARIANT"):      # (A/B checks of the tests: all variants give the same files)
         eng.set_kernel_variant(int(os.environ["AMPLIPY_KERNEL_VARIANT"]))
@@ -343,7 +276,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         eng.set_primers(mn, mx, mpl)
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
-    driver = vcf = rank_error = strand_file = amps = amp_file = cds = codon_file = aa_file = del_file = indel_file = cooc_sets = cooc_file = ep_file = ep_mask = hap_regions = hap_file = readpos_file = None
+    driver = vcf = rank_error = None
     qc_files, qc_regions, qc_primers = [None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
@@ -361,43 +294,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(route.note)
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
-            vcf = VcfWriter(variants_fn, ref_id, strand=strand, amplicon=amplicons_fn is not None, codon=codons_fn is not None, deletion=bool(deletions),
-                            cooc=cooc_fn is not None, errprof=error_profile_fn is not None, hap=haplotypes_fn is not None,
-                            readpos=bool(readpos))
-            if amplicon_out_fn is not None:
-                amp_file = qc.open_new(amplicon_out_fn)
-        if strand_fn is not None and rank == 0:
-            strand_file = qc.open_new(strand_fn)
-        if readpos_fn is not None and rank == 0:
-            readpos_file = qc.open_new(readpos_fn)
-        if del_on and rank == 0:
-            del_file = qc.open_new(del_out_fn) if del_out_fn is not None else None
-            indel_file = qc.open_new(indel_vcf_fn) if indel_vcf_fn is not None else None
-        if amplicons_fn is not None:
-            print_log("Loading amplicons: %s" % amplicons_fn)
-            amps = amplicon_mod.load_amplicons(amplicons_fn, qc.load_primer_rows(primer_fn), primer_pos_offset or 0, G)
-        if codons_fn is not None:
-            print_log("Loading CDS rows: %s" % codons_fn)
-            cds = codon_mod.load_cds(codons_fn, G)
-            if rank == 0:
-                codon_file = qc.open_new(codon_out_fn) if codon_out_fn is not None else None
-                aa_file = qc.open_new(aa_out_fn) if aa_out_fn is not None else None
-        if cooc_fn is not None:
-            print_log("Loading mutation sets: %s" % cooc_fn)
-            cooc_sets = cooc_mod.load_sets(cooc_fn, ref_seq)
-            if rank == 0:
-                cooc_file = qc.open_new(cooc_out_fn) if cooc_out_fn is not None else None
-        if error_profile_fn is not None:
-            if error_mask_fn is not None:
-                print_log("Loading error mask: %s" % error_mask_fn)
-                ep_mask = errprof_mod.load_mask(error_mask_fn, G)
-            if rank == 0:
-                ep_file = qc.open_new(error_profile_fn)
-        if haplotypes_fn is not None:
-            print_log("Loading haplotype regions: %s" % haplotypes_fn)
-            hap_regions = hap_mod.load_regions(haplotypes_fn, ref_id, G)
-            if rank == 0:
-                hap_file = qc.open_new(hap_out_fn) if hap_out_fn is not None else None
+            vcf = VcfWriter(variants_fn, ref_id, **{r.name: r.annotates(run) for r in on})
+        for r in on:
+            r.open(run)
         if qc_on:
             qc_regions = [(0, G, qc.WHOLE)] + (qc.load_regions(qc_regions_fn) if qc_regions_fn is not None else [])
             qc_primers = qc.load_primer_rows(primer_fn) if run_trim else []
@@ -415,22 +314,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     if qc_on and rank_error is None:
         eng.qc_enable([(s, e) for s, e, _ in qc_primers], primer_pos_offset or 0, min_length if min_length is not None else 0,
                       include_no_primer, [(s, e) for s, e, _ in qc_regions], qc_depths)
-    if strand_on and rank_error is None:
-        eng.strand_enable()
-    if amps is not None and rank_error is None:
-        amplicon_mod.enable(eng, amps)
-    if cds is not None and rank_error is None:
-        codon_mod.enable(eng, cds)
-    if del_on and rank_error is None:
-        eng.del_enable(del_capacity or 0)
-    if cooc_sets is not None and rank_error is None:
-        cooc_mod.enable(eng, cooc_sets)
-    if error_profile_fn is not None and rank_error is None:
-        errprof_mod.enable(eng, ref_seq, ep_mask)
-    if hap_regions is not None and rank_error is None:
-        hap_mod.enable(eng, hap_regions, ref_seq, hap_capacity)
-    if readpos_on and rank_error is None:
-        eng.readpos_enable()
+    if rank_error is None:
+        for r in on:
+            r.enable(run, eng)
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
     if driver is not None:
@@ -461,16 +347,6 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                                                                                         ", ".join("%.1f" % (100.0 * b_ / tot) for _, b_ in shares)))
         if qc_on:                        # every rank's tallies to rank 0, which adds them up
             qc_parts = parallel.gather_objects(dist, rank, world, eng.qc_read_tallies())
-        if amps is not None:             # ... and every rank's reads per amplicon
-            amp_read_parts = parallel.gather_objects(dist, rank, world, eng.amplicon_tables()[1])
-        if cds is not None:              # ... and every rank's tallied and skipped reads
-            codon_read_parts = parallel.gather_objects(dist, rank, world, eng.codon_tables()[1])
-        if cooc_sets is not None:        # ... likewise for the co-occurrence tallies
-            cooc_read_parts = parallel.gather_objects(dist, rank, world, eng.cooc_tables()[1])
-        if del_on:                       # ... and every rank's events: rank 0 sums them per key on the host
-            del_parts = parallel.gather_objects(dist, rank, world, eng.del_events())
-        if hap_regions is not None:      # ... and every rank's haplotype entries and tallies, likewise
-            hap_parts = parallel.gather_objects(dist, rank, world, eng.hap_tables())
         if final_trimmed_fn is not None and driver.part_writer is not None:
             # the ranks' files (all closed by now: the writer threads were joined in run()) become the one trimmed BAM
             parts = parallel.gather_objects(dist, rank, world, (driver.part_writer.path, driver.part_writer.header_bytes))
@@ -483,9 +359,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
 
     failed = True
     try:
-        qc_depth = qc_region_recs = ep_tables = None
-        del_lost = hap_lost = 0
-        hap_tables = None
+        qc_depth = qc_region_recs = None
         if qc_on and rank == 0:
             qc_tallies = qc.merge_read_tallies(qc_parts) if dist is not None else eng.qc_read_tallies()
         if do_count:
@@ -494,106 +368,14 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                                      min_depth_variants if min_depth_variants is not None else 0,
                                      min_freq_variants if min_freq_variants is not None else 0,
                                      run_consensus, run_variants)
-            v_min_depth = min_depth_variants if min_depth_variants is not None else 0
-            v_min_freq = min_freq_variants if min_freq_variants is not None else 0
             eng.set_reference(ref_seq)
             if dist is not None:
                 eng.sync()
                 parallel.allreduce_table(dist, table)      # the ONE collective of the run: every rank now holds the job's table
             if qc_on and rank == 0:                        # depth from the job's table
                 qc_depth, qc_region_recs = eng.qc_depth(want_depth=qc_depth_fn is not None)
-            strand_tables = None
-            if strand_on:
-                s_rev, s_qsum = eng.strand_tables()
-                if dist is not None:                       # one more all-reduce: both tables as one int64 tensor of G x 11
-                    import torch
-                    wire = torch.from_numpy(strand_mod.to_wire(s_rev, s_qsum)).to("cuda:%d" % device)
-                    parallel.allreduce_table(dist, wire)
-                    s_rev, s_qsum = strand_mod.from_wire(wire.cpu().numpy())
-                if rank == 0:
-                    strand_tables = strand_mod.Tables(eng.counts(), s_rev, s_qsum)
-            readpos_tables = None
-            if readpos_on:
-                rp_hist = eng.readpos_tables()
-                if dist is not None:                       # one more all-reduce: the table as one int64 tensor of G x 42
-                    import torch
-                    wire = torch.from_numpy(readpos_mod.to_wire(rp_hist)).to("cuda:%d" % device)
-                    parallel.allreduce_table(dist, wire)
-                    rp_hist = readpos_mod.from_wire(wire.cpu().numpy())
-                if rank == 0:
-                    readpos_tables = readpos_mod.Tables(eng.counts(), rp_hist, readpos_mod.DEFAULT_END if readpos_end is None else readpos_end)
-            amp_tables = None
-            if amps is not None:
-                a_counts, a_reads = eng.amplicon_tables()
-                if dist is not None:                       # one more all-reduce: the per-amplicon table
-                    import torch
-                    wire = torch.from_numpy(a_counts.astype(np.int64).reshape(-1)).to("cuda:%d" % device)
-                    parallel.allreduce_table(dist, wire)
-                    a_counts = wire.cpu().numpy().astype(np.uint32).reshape(-1, 6)
-                    if rank == 0:
-                        a_reads = np.sum([np.asarray(part, np.uint64) for part in amp_read_parts], axis=0, dtype=np.uint64)
-                if rank == 0:
-                    amp_tables = amplicon_mod.Tables(amps, eng.counts(), a_counts, a_reads)
-            codon_tables = None
-            if cds is not None:
-                c_codon, c_reads = eng.codon_tables()
-                if dist is not None:                       # one more all-reduce: the codon table
-                    import torch
-                    wire = torch.from_numpy(c_codon.astype(np.int64).reshape(-1)).to("cuda:%d" % device)
-                    parallel.allreduce_table(dist, wire)
-                    c_codon = wire.cpu().numpy().astype(np.uint32).reshape(-1, codon_mod.CELLS)
-                    if rank == 0:
-                        c_reads = np.sum([np.asarray(part, np.uint64) for part in codon_read_parts], axis=0, dtype=np.uint64)
-                if rank == 0:
-                    codon_tables = codon_mod.Tables(cds, ref_seq, c_codon, c_reads, v_min_depth, v_min_freq)
-            cooc_tables = None
-            if cooc_sets is not None:
-                o_cooc, o_reads = eng.cooc_tables()
-                if dist is not None:                       # one more all-reduce: the co-occurrence table
-                    import torch
-                    wire = torch.from_numpy(o_cooc.astype(np.int64).reshape(-1)).to("cuda:%d" % device)
-                    parallel.allreduce_table(dist, wire)
-                    o_cooc = wire.cpu().numpy().astype(np.uint32).reshape(-1, cooc_mod.CELLS)
-                    if rank == 0:
-                        o_reads = np.sum([np.asarray(part, np.uint64) for part in cooc_read_parts], axis=0, dtype=np.uint64)
-                if rank == 0:
-                    cooc_tables = cooc_mod.Tables(cooc_sets, o_cooc, o_reads)
-            if error_profile_fn is not None:
-                e_tabs = eng.errprof_tables()
-                if dist is not None:                       # one more all-reduce: the three tables and the read counters as one int64 tensor
-                    import torch
-                    wire = torch.from_numpy(errprof_mod.to_wire(*e_tabs)).to("cuda:%d" % device)
-                    parallel.allreduce_table(dist, wire)
-                    e_tabs = errprof_mod.from_wire(wire.cpu().numpy())
-                if rank == 0:
-                    ep_tables = errprof_mod.Tables(*e_tabs, min_quality if min_quality is not None else 20,
-                                                   int(ep_mask.sum()) if ep_mask is not None else 0, eng.counts() if run_variants else None)
-            del_tables = None
-            if del_on:
-                if dist is None:
-                    d_events, d_info = eng.del_events()
-                    del_lost = d_info["lost"]
-                elif rank == 0:
-                    d_events = deletion_mod.merge_events([part[0] for part in del_parts])
-                    del_lost = sum(part[1]["lost"] for part in del_parts)
-                else:
-                    del_lost = eng.del_events()[1]["lost"]
-                if rank == 0:
-                    del_tables = deletion_mod.Tables(d_events, eng.counts(), ref_seq, v_min_depth, v_min_freq)
-            if hap_regions is not None:
-                if dist is None:
-                    h_entries, h_info, h_tally, h_reads = eng.hap_tables()
-                    hap_lost = h_info["lost"]
-                elif rank == 0:
-                    h_entries = hap_mod.merge_entries([part[0] for part in hap_parts])
-                    hap_lost = sum(part[1]["lost"] for part in hap_parts)
-                    h_tally = np.sum([np.asarray(part[2], np.uint64) for part in hap_parts], axis=0, dtype=np.uint64)
-                    h_reads = np.sum([np.asarray(part[3], np.uint64) for part in hap_parts], axis=0, dtype=np.uint64)
-                else:
-                    hap_lost = eng.hap_tables()[1]["lost"]
-                if rank == 0:
-                    hap_tables = hap_mod.Tables(hap_regions, ref_seq, h_entries, h_tally, h_reads, hap_lost, 2 if hap_min_reads is None else hap_min_reads,
-                                                hap_min_freq or 0.0, v_min_freq)
+            for r in on:                                   # one more all-reduce or gather per report, in the same order on every rank
+                r.collect(run, eng)
 
             def ins_tallies(positions):
                 triples = loop.ins_store.counted_pairs(positions)
@@ -604,44 +386,18 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             if rank != 0:
                 run_variants = run_consensus = False       # rank 0 writes the outputs
             if run_variants:
-                vcf.f.write(res.vcf_text(vcf.ref_id, strand_tables if strand else None, amp_tables, codon_tables,
-                                         del_tables if deletions else None, cooc_tables, ep_tables, hap_tables,
-                                         readpos_tables if readpos else None))      # (= vcf.write(r) for r in res.records)
+                vcf.f.write(res.vcf_text(vcf.ref_id, **{r.name: r.vcf_tables(run) for r in on}))      # (= vcf.write(r) for r in res.records)
                 vcf.close()
-            if indel_file is not None:
-                deletion_mod.write_indel_vcf(indel_file, ref_id, del_tables, deletion_mod.insertion_rows(res.records), " ".join(sys.argv))
-                print_log("Output indel VCF: %s" % indel_vcf_fn)
-            if del_file is not None:
-                deletion_mod.write_tsv(del_file, ref_id, del_tables)
-                print_log("Output deletion events: %s" % del_out_fn)
+            for r in on:
+                if r.with_calls:
+                    r.write(run, res)
             if run_consensus:
                 f = gzip.open(consensus_fn, "wt") if consensus_fn.lower().endswith(".gz") else open(consensus_fn, "w")
                 f.write(">sample\n%s\n" % res.consensus_string(unknown_symbol))
                 f.close()
-        if strand_file is not None:
-            strand_mod.write_tsv(strand_file, ref_id, strand_tables)
-            print_log("Output strand tallies: %s" % strand_fn)
-        if amp_file is not None:
-            amplicon_mod.write_tsv(amp_file, ref_id, amp_tables)
-            print_log("Output per-amplicon counts: %s" % amplicon_out_fn)
-        if codon_file is not None:
-            codon_mod.write_codon_tsv(codon_file, ref_id, codon_tables)
-            print_log("Output codon table: %s" % codon_out_fn)
-        if aa_file is not None:
-            codon_mod.write_aa_tsv(aa_file, ref_id, codon_tables)
-            print_log("Output amino-acid calls: %s" % aa_out_fn)
-        if cooc_file is not None:
-            cooc_mod.write_tsv(cooc_file, ref_id, cooc_tables)
-            print_log("Output co-occurrence table: %s" % cooc_out_fn)
-        if ep_file is not None:
-            qc.write_json(ep_file, ep_tables.report())
-            print_log("Output error profile: %s" % error_profile_fn)
-        if hap_file is not None:
-            hap_mod.write_tsv(hap_file, ref_id, hap_tables)
-            print_log("Output haplotype table: %s" % hap_out_fn)
-        if readpos_file is not None:
-            readpos_mod.write_tsv(readpos_file, ref_id, readpos_tables)
-            print_log("Output read-position tallies: %s" % readpos_fn)
+            for r in on:                                   # (a report is on only in a run with a count table)
+                if not r.with_calls:
+                    r.write(run, res)
         if qc_on and rank == 0:
             if qc_fn is not None:
                 report = qc.build_report(
@@ -649,30 +405,20 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                     if run_trim else dict(depths=qc_depths),
                     qc_tallies[0], run_trim, qc_primers, qc_tallies[1], qc_tallies[2],
                     [name for _, _, name in qc_regions], qc_region_recs, qc_depths)
-                if amps is not None:
-                    amplicon_mod.add_to_report(report, amp_tables)
+                for r in on:
+                    r.add_to_qc(report)
                 qc.write_json(qc_files[0], report)
                 print_log("Output QC report: %s" % qc_fn)
                 print_log(qc.summary_line(report))
             if qc_depth_fn is not None:
                 qc.write_depth(qc_files[1], ref_id, qc_depth)
-        if amps is not None and rank == 0:
-            print_log(amp_tables.summary_line())
-        if cds is not None and rank == 0:
-            print_log(codon_tables.summary_line())
-        if cooc_sets is not None and rank == 0:
-            print_log(cooc_tables.summary_line())
-        if ep_tables is not None:
-            print_log(ep_tables.summary_line())
-        if hap_tables is not None:
-            print_log(hap_tables.summary_line())
-        if del_on:
-            deletion_mod.check_lost(del_lost)              # (behind the run's last collective: no rank is left waiting)
-        if hap_regions is not None:
-            hap_mod.check_lost(hap_lost)                   # (likewise)
+        for r in on:
+            r.summary(run)
+        for r in on:
+            r.after(run)
         failed = False
     finally:
-        for f in qc_files + [strand_file, amp_file, codon_file, aa_file, del_file, indel_file, cooc_file, ep_file, hap_file, readpos_file]:
+        for f in qc_files + [f for r in on for f in r.files()]:
             if f is not None:
                 f.close()
         driver.finish(failed)             # (the writer thread of the libampbam path, which ran on under the calls)

@@ -15,6 +15,9 @@ import numpy as np
 from . import abi
 
 SYMS = abi.SYMBOLS
+# the reports that annotate a VCF record, in the order of their INFO keys on a line and of their header lines: the keywords of
+# vcf_line, CallResult.vcf_text and amplipy.VcfWriter, the names of reports.REGISTRY, HOOK_STRAND .. HOOK_READPOS of amp_hook.hpp
+INFO_ORDER = ("strand", "amplicon", "codon", "deletion", "cooc", "errprof", "hap", "readpos")
 
 
 class VariantRecord:
@@ -38,27 +41,11 @@ class VariantRecord:
 
 
 def vcf_line(ref_id, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None, readpos=None):
-    """One VCF line of a VariantRecord (AmpliPy.py:941-951).  strand: a strand.Tables, whose five INFO keys (REF_RV ALT_RV
-    REF_QUAL ALT_QUAL SB) are appended behind ALT_FREQ; amplicon: an amplicon.Tables, whose seven keys (AMP .. PRIMER) come
-    behind those; codon: a codon.Tables, whose five keys (CDS .. ALT_CODON_DP) come next; deletion: a deletion.Tables, whose two
-    keys (DEL_N, DEL) come next; cooc: a cooc.Tables, whose key (COOC) comes next; errprof: an errprof.Tables, whose two keys (ERR_RATE,
-    ERR_P) come next; hap: a haplotype.Tables, whose two keys (HAP_N, HAP) come next; readpos: a
-    readpos.Tables, whose six keys (REF_RP .. RPZ) come last; all None: the line as the reference writes it."""
-    more = "" if strand is None else ";" + strand.info(r.pos, r.ref, r.alts)
-    if amplicon is not None:
-        more += ";" + amplicon.info(r.pos, r.ref, r.alts)
-    if codon is not None:
-        more += ";" + codon.info(r.pos, r.ref, r.alts)
-    if deletion is not None:
-        more += ";" + deletion.info(r.pos, r.DP)
-    if cooc is not None:
-        more += ";" + cooc.info(r.pos, r.ref, r.alts)
-    if errprof is not None:
-        more += ";" + errprof.info(r.pos, r.ref, r.alts)
-    if hap is not None:
-        more += ";" + hap.info(r.pos, r.ref, r.alts)
-    if readpos is not None:
-        more += ";" + readpos.info(r.pos, r.ref, r.alts)
+    """One VCF line of a VariantRecord (AmpliPy.py:941-951).  Each keyword of INFO_ORDER: the ``Tables`` of that report's module
+    (haplotype for hap), whose INFO keys are appended behind ALT_FREQ in that order (``info(pos, ref, alts)``; deletion's takes
+    ``(pos, DP)``); all None: the line as the reference writes it."""
+    more = "".join(";" + (t.info(r.pos, r.DP) if name == "deletion" else t.info(r.pos, r.ref, r.alts))
+                   for name, t in zip(INFO_ORDER, (strand, amplicon, codon, deletion, cooc, errprof, hap, readpos)) if t is not None)
     return "%s\t%d\t.\t%s\t%s\t.\tPASS\tDP=%d;REF_DP=%d;ALT_DP=%s;REF_FREQ=%g;ALT_FREQ=%s%s\tGT\t%s\n" % (
         ref_id, r.pos + 1, r.ref, ",".join(r.alts), r.DP, r.REF_DP, r.ALT_DP, r.REF_FREQ, r.ALT_FREQ, more, "/".join(map(str, r.GT)))
 
@@ -123,11 +110,9 @@ class CallResult:
     def vcf_text(self, ref_id, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None, readpos=None):
         """The VCF body (AmpliPy.py:941-951, one line per record, ascending position) straight from the columns: the same text
         as VcfWriter.line over ``records``, without one Python object per record (12,000 records: 15 ms instead of 50).
-        strand: a strand.Tables whose INFO keys every line carries, the records of insertion positions included (record by
-        record: each key looks its position up); amplicon: an amplicon.Tables, codon: a codon.Tables, deletion: a
-        deletion.Tables, cooc: a cooc.Tables, errprof: an errprof.Tables, hap: a haplotype.Tables, readpos: a readpos.Tables,
-        likewise; all None: the column-wise path below."""
-        if strand is not None or amplicon is not None or codon is not None or deletion is not None or cooc is not None or errprof is not None or hap is not None or readpos is not None:
+        The keywords are vcf_line's: with one of them given every line carries that report's INFO keys, the records of insertion
+        positions included (record by record: each key looks its position up); all None: the column-wise path below."""
+        if any(t is not None for t in (strand, amplicon, codon, deletion, cooc, errprof, hap, readpos)):
             return "".join([vcf_line(ref_id, r, strand, amplicon, codon, deletion, cooc, errprof, hap, readpos) for r in self.records])
         tot = self.var_total.tolist(); rcs = self.var_ref_count.tolist(); nas = self.var_nalt.tolist(); gtr = self.var_gt_ref.tolist()
         colL = self.var_alt_col.tolist(); cntL = self.var_alt_count.tolist()

@@ -9,8 +9,9 @@ from os.path import isfile
 
 import numpy as np
 
-from . import abi
-from .readloop import error
+from . import abi, parallel
+from .readloop import error, print_log
+from .reports import Report
 
 BAD_NAME_CHARS = ",;=|:"
 BASES = "ACGT"
@@ -237,3 +238,34 @@ def write_aa_tsv(f, ref_id, tables):
     f.write("#" + "\t".join(AA_COLUMNS) + "\n")
     f.write("".join(["%s\t%s\t%s\t%d\t%d\t%g\t%s\n" % (ref_id, cds, change, count, depth, freq, ",".join("%s:%d" % x for x in pairs))
                      for cds, change, count, depth, freq, pairs in aa_calls(tables)]))
+
+
+class CodonReport(Report):
+    name, HEADER_LINES = "codon", HEADER_LINES
+    outputs = (("codon_out_fn", "codon table", write_codon_tsv), ("aa_out_fn", "amino-acid calls", write_aa_tsv))
+    cds = None
+
+    def active(self, run):
+        return run.codons_fn is not None
+
+    def check(self, run):
+        if (run.codon_out_fn is not None or run.aa_out_fn is not None) and run.codons_fn is None:
+            error("The codon table and the amino-acid calls (--codon_out, --aa_out) need the CDS file (--codons)")
+        if run.codons_fn is not None and not (run.run_variants or run.run_consensus):
+            error("A run that only trims has no count table: no codon tallies (--codons, --codon_out, --aa_out)")
+        if run.aa_out_fn is not None and not run.run_variants:
+            error("The amino-acid calls (--aa_out) use the variant thresholds: variants or aio")
+
+    def load(self, run):
+        print_log("Loading CDS rows: %s" % run.codons_fn)
+        self.cds = load_cds(run.codons_fn, run.G)
+
+    def enable(self, run, eng):
+        enable(eng, self.cds)
+
+    def collect(self, run, eng):
+        codon, reads = eng.codon_tables()
+        codon = parallel.allreduce_numpy(run.dist, run.device, codon.astype(np.int64).reshape(-1)).astype(np.uint32).reshape(-1, CELLS)
+        reads = parallel.gather_sum_reads(run.dist, run.rank, run.world, reads)
+        if run.rank == 0:
+            self.tables = Tables(self.cds, run.ref_seq, codon, reads, run.v_min_depth, run.v_min_freq)

@@ -14,8 +14,9 @@ from os.path import isfile
 
 import numpy as np
 
-from . import abi
-from .readloop import error
+from . import abi, parallel
+from .readloop import error, print_log
+from .reports import Report
 
 BAD_NAME_CHARS = ",;=|:"
 BASES = "ACGT"
@@ -187,3 +188,31 @@ def write_tsv(f, ref_id, tables):
             out.append("%s\t%s\t%s\t%s\t%d\t%d\t%g\t%d\n" % (ref_id, name, text, S.pattern_text(i, t), c[t], complete,
                                                            c[t] / complete if complete else 0.0, c[PARTIAL]))
     f.write("".join(out))
+
+
+class CoocReport(Report):
+    name, HEADER_LINES, outputs = "cooc", HEADER_LINES, (("cooc_out_fn", "co-occurrence table", write_tsv),)
+    sets = None
+
+    def active(self, run):
+        return run.cooc_fn is not None
+
+    def check(self, run):
+        if run.cooc_out_fn is not None and run.cooc_fn is None:
+            error("The co-occurrence table (--cooc_out) needs the mutation-set file (--cooc)")
+        if run.cooc_fn is not None and not (run.run_variants or run.run_consensus):
+            error("A run that only trims has no count table: no co-occurrence tallies (--cooc, --cooc_out)")
+
+    def load(self, run):
+        print_log("Loading mutation sets: %s" % run.cooc_fn)
+        self.sets = load_sets(run.cooc_fn, run.ref_seq)
+
+    def enable(self, run, eng):
+        enable(eng, self.sets)
+
+    def collect(self, run, eng):
+        cooc, reads = eng.cooc_tables()
+        cooc = parallel.allreduce_numpy(run.dist, run.device, cooc.astype(np.int64).reshape(-1)).astype(np.uint32).reshape(-1, CELLS)
+        reads = parallel.gather_sum_reads(run.dist, run.rank, run.world, reads)
+        if run.rank == 0:
+            self.tables = Tables(self.sets, cooc, reads)

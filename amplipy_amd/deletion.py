@@ -6,10 +6,13 @@ reference positions from 0-based ``start`` on together."""
 from __future__ import annotations
 
 import bisect
+import sys
 
 import numpy as np
 
-from . import abi
+from . import abi, parallel
+from .readloop import error
+from .reports import Report
 
 KEYS = ("DEL_N", "DEL")
 HEADER_LINES = (
@@ -143,3 +146,52 @@ def write_indel_vcf(f, ref_id, tables, insertions=(), source=""):
     f.write(INDEL_NOTE + INDEL_INFO_LINES)
     f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
     f.write("".join(["%s\t%d\t.\t%s\t%s\t.\tPASS\t%s\n" % (ref_id, pos, r, a, info) for pos, r, a, info in indel_records(tables, insertions)]))
+
+
+class DeletionReport(Report):
+    """--deletions puts the keys on the VCF; --del_out or --indel_vcf alone switch the hook on too.  The indel VCF takes the
+    call's insertion alleles, so both files are written beside the VCF."""
+    name, HEADER_LINES, with_calls = "deletion", HEADER_LINES, True
+    outputs = (("indel_vcf_fn", "indel VCF", write_indel_vcf), ("del_out_fn", "deletion events", write_tsv))
+
+    def active(self, run):
+        return bool(run.deletions) or run.del_out_fn is not None or run.indel_vcf_fn is not None
+
+    def check(self, run):
+        on = self.active(run)
+        if on and not (run.run_variants or run.run_consensus):
+            error("A run that only trims has no count table: no deletion events (--deletions, --del_out, --indel_vcf)")
+        if run.deletions and not run.run_variants:
+            error("The deletion INFO keys need a VCF (--deletions on variants or aio)")
+        if run.indel_vcf_fn is not None and not run.run_variants:
+            error("The indel VCF (--indel_vcf) uses the variant thresholds: variants or aio")
+        if run.del_capacity is not None and not on:
+            error("The deletion events' table size (--del_capacity) needs --deletions, --del_out or --indel_vcf")
+        if run.del_capacity is not None and not abi.DEL_LOG2_MIN <= run.del_capacity <= abi.DEL_LOG2_MAX:
+            error("--del_capacity is the log2 of the table's slots, %d to %d: %s" % (abi.DEL_LOG2_MIN, abi.DEL_LOG2_MAX, run.del_capacity))
+        if run.indel_vcf_fn is not None and not run.indel_vcf_fn.lower().endswith((".vcf", ".vcf.gz")):
+            error("Invalid indel VCF extension (should be .vcf or .vcf.gz): %s" % run.indel_vcf_fn)
+
+    def enable(self, run, eng):
+        eng.del_enable(run.del_capacity or 0)
+
+    def collect(self, run, eng):
+        events, info = eng.del_events()
+        self.lost = info["lost"]
+        if run.dist is not None:              # every rank's events to rank 0, which sums them per key on the host
+            parts = parallel.gather_objects(run.dist, run.rank, run.world, (events, info))
+            if run.rank == 0:
+                events = merge_events([part[0] for part in parts])
+                self.lost = sum(part[1]["lost"] for part in parts)
+        if run.rank == 0:
+            self.tables = Tables(events, eng.counts(), run.ref_seq, run.v_min_depth, run.v_min_freq)
+
+    def annotates(self, run):
+        return bool(run.deletions)
+
+    def writer_args(self, arg, run, res):
+        more = (insertion_rows(res.records), " ".join(sys.argv)) if arg == "indel_vcf_fn" else ()
+        return (run.ref_id, self.tables) + more
+
+    def after(self, run):
+        check_lost(self.lost)                 # (behind the run's last collective: no rank is left waiting)

@@ -14,8 +14,9 @@ from os.path import isfile
 
 import numpy as np
 
-from . import abi
-from .readloop import error
+from . import abi, parallel, qc
+from .readloop import error, print_log
+from .reports import Report
 
 BASES = "ACGT"
 CYCLES, QUALS = abi.EP_CYCLES, abi.EP_QUALS
@@ -209,3 +210,31 @@ class Tables:
             rates.append("%.4g" % rate)
             ps.append("%.4g" % binom_sf(k, n, rate))
         return "ERR_RATE=%s;ERR_P=%s" % (",".join(rates), ",".join(ps))
+
+
+class ErrprofReport(Report):
+    name, HEADER_LINES = "errprof", HEADER_LINES
+    outputs = (("error_profile_fn", "error profile", lambda f, ref_id, tables: qc.write_json(f, tables.report())),)
+    mask = None
+
+    def active(self, run):
+        return run.error_profile_fn is not None
+
+    def check(self, run):
+        if run.error_mask_fn is not None and run.error_profile_fn is None:
+            error("The error mask (--error_mask) needs the error profile (--error_profile)")
+        if run.error_profile_fn is not None and not (run.run_variants or run.run_consensus):
+            error("A run that only trims has no count table: no error profile (--error_profile, --error_mask)")
+
+    def load(self, run):
+        if run.error_mask_fn is not None:
+            print_log("Loading error mask: %s" % run.error_mask_fn)
+            self.mask = load_mask(run.error_mask_fn, run.G)
+
+    def enable(self, run, eng):
+        enable(eng, run.ref_seq, self.mask)
+
+    def collect(self, run, eng):
+        tabs = from_wire(parallel.allreduce_numpy(run.dist, run.device, to_wire(*eng.errprof_tables())))      # the three tables and the read counters as one int64 array
+        if run.rank == 0:
+            self.tables = Tables(*tabs, run.min_quality, int(self.mask.sum()) if self.mask is not None else 0, eng.counts() if run.run_variants else None)

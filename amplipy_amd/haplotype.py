@@ -16,9 +16,10 @@ from os.path import isfile
 
 import numpy as np
 
-from . import abi
+from . import abi, parallel
 from .cooc import BAD_NAME_CHARS
-from .readloop import error
+from .readloop import error, print_log
+from .reports import Report
 
 KINDS = "ACGTN"
 KEYS = ("HAP_N", "HAP")
@@ -247,3 +248,46 @@ def write_tsv(f, ref_id, tables):
                 ref_id, name, s, e, text, reads, rev, u, "%.6g" % (reads / u) if u > 0 else ".", c[abi.HAP_COVER], c[abi.HAP_LOWQ], c[abi.HAP_OVERFLOW],
                 c[abi.HAP_EDGE]))
     f.write("".join(out))
+
+
+class HapReport(Report):
+    name, HEADER_LINES, outputs = "hap", HEADER_LINES, (("hap_out_fn", "haplotype table", write_tsv),)
+    regions = None
+
+    def active(self, run):
+        return run.haplotypes_fn is not None
+
+    def check(self, run):
+        if run.haplotypes_fn is None and (run.hap_out_fn is not None or run.hap_capacity is not None):
+            error("The haplotype table and its size (--hap_out, --hap_capacity) need the region file (--haplotypes)")
+        if run.haplotypes_fn is not None and not (run.run_variants or run.run_consensus):
+            error("A run that only trims has no count table: no read haplotypes (--haplotypes, --hap_out)")
+        if run.hap_capacity is not None and not abi.HAP_LOG2_MIN <= run.hap_capacity <= abi.HAP_LOG2_MAX:
+            error("--hap_capacity is the log2 of the table's slots, %d to %d: %s" % (abi.HAP_LOG2_MIN, abi.HAP_LOG2_MAX, run.hap_capacity))
+        if run.hap_min_reads is not None and run.hap_min_reads < 0:
+            error("--hap_min_reads must be non-negative: %s" % run.hap_min_reads)
+        if run.hap_min_freq is not None and not 0 <= run.hap_min_freq <= 1:
+            error("--hap_min_freq must be between 0 and 1: %s" % run.hap_min_freq)
+
+    def load(self, run):
+        print_log("Loading haplotype regions: %s" % run.haplotypes_fn)
+        self.regions = load_regions(run.haplotypes_fn, run.ref_id, run.G)
+
+    def enable(self, run, eng):
+        enable(eng, self.regions, run.ref_seq, run.hap_capacity)
+
+    def collect(self, run, eng):
+        entries, info, tally, reads = eng.hap_tables()
+        self.lost = info["lost"]
+        if run.dist is not None:              # every rank's entries and tallies to rank 0, which sums them on the host
+            parts = parallel.gather_objects(run.dist, run.rank, run.world, (entries, info, tally, reads))
+            if run.rank == 0:
+                entries = merge_entries([part[0] for part in parts])
+                self.lost = sum(part[1]["lost"] for part in parts)
+                tally, reads = parallel.sum_reads([part[2] for part in parts]), parallel.sum_reads([part[3] for part in parts])
+        if run.rank == 0:
+            self.tables = Tables(self.regions, run.ref_seq, entries, tally, reads, self.lost, 2 if run.hap_min_reads is None else run.hap_min_reads,
+                                 run.hap_min_freq or 0.0, run.v_min_freq)
+
+    def after(self, run):
+        check_lost(self.lost)                 # (behind the run's last collective: no rank is left waiting)

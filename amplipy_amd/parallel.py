@@ -91,6 +91,30 @@ def allreduce_table(dist, table):
     dist.all_reduce(table, op=dist.ReduceOp.SUM)
 
 
+def allreduce_numpy(dist, device, wire):
+    """An int64 numpy array summed over the ranks, on every rank, through a tensor on ``device`` (allreduce_table); the array
+    itself when ``dist`` is None."""
+    if dist is None:
+        return wire
+    import torch
+    t = torch.from_numpy(wire).to("cuda:%d" % device)
+    allreduce_table(dist, t)
+    return t.cpu().numpy()
+
+
+def sum_reads(parts):
+    """The element-wise sum of the ranks' read counters (uint64 arrays of one shape)."""
+    return np.sum([np.asarray(part, np.uint64) for part in parts], axis=0, dtype=np.uint64)
+
+
+def gather_sum_reads(dist, rank, world, reads):
+    """A rank's read counters -> the job's on rank 0 (None on the other ranks); the counters themselves when ``dist`` is None."""
+    if dist is None:
+        return reads
+    parts = gather_objects(dist, rank, world, reads)
+    return sum_reads(parts) if rank == 0 else None
+
+
 def allgather_relevant_events(dist, world, pairs):
     """Union of [(ref_pos, string)] lists on every rank."""
     gathered = [None] * world

@@ -7,7 +7,9 @@ import math
 
 import numpy as np
 
-from . import abi
+from . import abi, parallel
+from .readloop import error
+from .reports import Report
 from .strand import fisher_two_sided
 
 SYMS = abi.SYMBOLS                      # A C G T N '-': the columns of the count table and of hist
@@ -113,3 +115,35 @@ def to_wire(hist):
 
 def from_wire(wire):
     return np.asarray(wire, np.int64).reshape(-1, abi.NSYM, BINS).astype(np.uint32)
+
+
+class ReadposReport(Report):
+    """--readpos puts the keys on the VCF; --readpos_out alone switches the tallies on too."""
+    name, HEADER_LINES, outputs = "readpos", HEADER_LINES, (("readpos_fn", "read-position tallies", write_tsv),)
+
+    def active(self, run):
+        return bool(run.readpos) or run.readpos_fn is not None
+
+    def check(self, run):
+        if self.active(run) and not (run.run_variants or run.run_consensus):
+            error("A run that only trims has no count table: no read-position tallies (--readpos, --readpos_out)")
+        if run.readpos and not run.run_variants:
+            error("The read-position INFO keys need a VCF (--readpos on variants or aio)")
+        if run.readpos_end is not None and not run.readpos:
+            error("The read-end distance (--readpos_end) needs --readpos")
+        if run.readpos_end is not None:
+            try:
+                end_bins(run.readpos_end)
+            except ValueError as e:
+                error(str(e))
+
+    def enable(self, run, eng):
+        eng.readpos_enable()
+
+    def collect(self, run, eng):
+        hist = from_wire(parallel.allreduce_numpy(run.dist, run.device, to_wire(eng.readpos_tables())))      # the table as one int64 array of G x 42
+        if run.rank == 0:
+            self.tables = Tables(eng.counts(), hist, DEFAULT_END if run.readpos_end is None else run.readpos_end)
+
+    def annotates(self, run):
+        return bool(run.readpos)

@@ -7,7 +7,9 @@ import math
 
 import numpy as np
 
-from . import abi
+from . import abi, parallel
+from .readloop import error
+from .reports import Report
 
 SYMS = abi.SYMBOLS                      # A C G T N '-': the columns of the count table and of rev; qsum has the first five
 QSUM_COLS = abi.STRAND_QSUM_COLS
@@ -152,3 +154,28 @@ def to_wire(rev, qsum):
 def from_wire(wire):
     t = np.asarray(wire, np.int64).reshape(-1, abi.STRAND_CELLS)
     return t[:, :abi.NSYM].astype(np.uint32), t[:, abi.NSYM:].astype(np.uint64)
+
+
+class StrandReport(Report):
+    """--strand puts the keys on the VCF; --strand_out alone switches the tallies on too."""
+    name, HEADER_LINES, outputs = "strand", HEADER_LINES, (("strand_fn", "strand tallies", write_tsv),)
+
+    def active(self, run):
+        return bool(run.strand) or run.strand_fn is not None
+
+    def check(self, run):
+        if self.active(run) and not (run.run_variants or run.run_consensus):
+            error("A run that only trims has no count table: no strand tallies (--strand, --strand_out)")
+        if run.strand and not run.run_variants:
+            error("The strand INFO keys need a VCF (--strand on variants or aio)")
+
+    def enable(self, run, eng):
+        eng.strand_enable()
+
+    def collect(self, run, eng):
+        rev, qsum = from_wire(parallel.allreduce_numpy(run.dist, run.device, to_wire(*eng.strand_tables())))      # both tables as one int64 array of G x 11
+        if run.rank == 0:
+            self.tables = Tables(eng.counts(), rev, qsum)
+
+    def annotates(self, run):
+        return bool(run.strand)

@@ -22,7 +22,7 @@ same files in the same session, in this process.  Its files are what each report
 plain restatement; test_one_process_reference_is_the_restatements repeats that for the error-profile JSON and the --cooc_out
 table of this job.  Text outputs are compared byte for byte, the joined BAM by its inflated bytes and its EOF block.
 
-(a) test_every_report_bam_in_bam_out: aio, BAM in, BAM out, all seven reports and every table file; world 2 on ``turned`` and
+(a) test_every_report_bam_in_bam_out: aio, BAM in, BAM out, all nine reports and every table file; world 2 on ``turned`` and
     world 3 on ``plain`` with two pieces per rank, world 3 on ``plain`` with one piece per rank (AMPLIPY_PART_BYTES larger than
     the file: native_parts never makes fewer pieces than ranks, so every rank still has a third of the file).  Every child
     exits 0, no .partN.bam is left, the directory holds the one-process run's files and nothing else, and no rank but 0
@@ -36,8 +36,8 @@ table of this job.  Text outputs are compared byte for byte, the joined BAM by i
 (c) test_text_in_world_2: the same command with -i in.sam; PythonDriver deals the reads out, every pile is split on every
     read.  VCF, FASTA and every report as one process; the trimmed reads are what the code does today: out.part0.bam and
     out.part1.bam, whose records together are the one-process out.bam's as a multiset, and no out.bam.
-(d) test_variants_and_consensus_alone_world_2: the untrimmed BAM with --strand --deletions --codons --cooc --error_profile
-    (consensus: the table files in place of the two VCF flags); do_trim is off and the hooks read the input CIGAR.  Reach:
+(d) test_variants_and_consensus_alone_world_2: the untrimmed BAM with --strand --deletions --readpos --codons --cooc --error_profile
+    --haplotypes (consensus: the table files in place of the three VCF flags); do_trim is off and the hooks read the input CIGAR.  Reach:
     both shares non-empty.
 (e) test_ranks_with_an_empty_share_world_3: ``thin`` has one block of records, so at world 3 two ranks run with every report
     on and never process a batch: a shares line with two zeros, exit 0 everywhere, the one-process files.  (The full job cannot
@@ -88,7 +88,7 @@ LIMIT = 10 * ONE_PROCESS_SECONDS
 CRASHED = (134, 139, -6, -11)
 CLEARED = ("AMPLIPY_GPU_SAM", "AMPLIPY_GPU_BAM", "AMPLIPY_GPU_BAM_WRITE", "AMPLIPY_GPU_DEFLATE", "AMPLIPY_FORCE_DIST", "AMPLIPY_PART_BYTES",
            "AMPLIPY_PYTHON_BAM", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")
-TEXT_OUTPUTS = ("out.vcf", "out.fas", "q.json", "d.tsv", "s.tsv", "a.tsv", "c.tsv", "aa.tsv", "del.tsv", "indel.vcf", "co.tsv", "ep.json")
+TEXT_OUTPUTS = ("out.vcf", "out.fas", "q.json", "d.tsv", "s.tsv", "a.tsv", "c.tsv", "aa.tsv", "del.tsv", "indel.vcf", "co.tsv", "ep.json", "hap.tsv", "rp.tsv")
 _STOPPED = []                      # why no further children are started
 
 
@@ -236,6 +236,9 @@ class Job:
         self.mask = put("mask.bed", "".join("SYN_REF\t%d\t%d\n" % (p, p + 1) for p in self.mask_positions))
         regions = [(int(a[2]), int(a[3]), "insert%d" % k) for k, a in enumerate(amps[9:12])] + [(G - 50, G + 70, "tail"), (40, 40, "empty")]
         self.regions = put("r.bed", "".join("SYN_REF\t%d\t%d\t%s\n" % r for r in regions))
+        # the regions of --haplotypes: the three inserts (no read spans one: their reads are "other reads") and 45 positions round
+        # the deletion and the insertion, which whole reads cover
+        self.hap_regions = put("h.bed", "".join("SYN_REF\t%d\t%d\t%s\n" % r for r in regions[:3] + [(self.pc - 20, self.pc + 25, "site")]))
         self.primers = sorted((s, e) for s, e, _ in j["primers"])
         self.dir = d
         self._refs, self.logs = {}, {}
@@ -245,14 +248,15 @@ class Job:
                 "--qc", "q.json", "--qc_regions", self.regions, "--qc_depth_out", "d.tsv", "--strand", "--strand_out", "s.tsv",
                 "--amplicons", self.pairs, "--amplicon_out", "a.tsv", "--codons", self.cds, "--codon_out", "c.tsv", "--aa_out", "aa.tsv",
                 "--deletions", "--del_out", "del.tsv", "--indel_vcf", "indel.vcf", "--cooc", self.sets, "--cooc_out", "co.tsv",
-                "--error_profile", "ep.json", "--error_mask", self.mask]
+                "--error_profile", "ep.json", "--error_mask", self.mask, "--haplotypes", self.hap_regions, "--hap_out", "hap.tsv",
+                "--readpos", "--readpos_out", "rp.tsv"]
 
     def alone(self, command):
         """variants or consensus on the untrimmed BAM with every report such a run can have."""
         more = ["--codons", self.cds, "--codon_out", "c.tsv", "--cooc", self.sets, "--cooc_out", "co.tsv", "--error_profile", "ep.json", "--del_out", "del.tsv",
-                "--strand_out", "s.tsv"]
+                "--strand_out", "s.tsv", "--haplotypes", self.hap_regions, "--hap_out", "hap.tsv", "--readpos_out", "rp.tsv"]
         if command == "variants":
-            return ["variants", "-i", self.bam["plain"], "-r", self.ref, "-o", "out.vcf", "--strand", "--deletions"] + more
+            return ["variants", "-i", self.bam["plain"], "-r", self.ref, "-o", "out.vcf", "--strand", "--deletions", "--readpos"] + more
         return ["consensus", "-i", self.bam["plain"], "-r", self.ref, "-o", "out.fas"] + more
 
     def reference(self, tag, argv):
@@ -301,7 +305,7 @@ def check_same_files(got, want, names):
 
 def summary_lines(log):
     """The reports' closing log lines, which carry the read counters that reach no file."""
-    return re.findall(r"\] ((?:QC|Amplicons|Codons|Co-occurrence|Error profile): .*)", log)
+    return re.findall(r"\] ((?:QC|Amplicons|Codons|Co-occurrence|Error profile|Haplotypes): .*)", log)
 
 
 def check_same_summaries(log, want_log, n):
@@ -350,6 +354,20 @@ def test_one_process_reference_is_the_restatements(job):
     assert read(d / "out.bam").endswith(bam_native.BGZF_EOF)
 
 
+def test_one_process_log_names_outputs_and_summaries_in_order(job):
+    """The "Output ..." lines and the reports' closing lines of the one-process run of (a), by their text up to the first colon,
+    against a list that does not come from the walk over reports.REGISTRY: it was written down from a run, with these arguments,
+    of a run_amplipy that threaded every report by hand.  The deletion report's two files come first (they are written beside
+    the VCF), then the other reports' in registry order, the QC report last; then the closing lines."""
+    job.reference("aio_plain", job.aio(job.bam["plain"]))
+    lines = [re.sub(r"^\[[^\]]*\] ", "", l) for l in job.logs["aio_plain"].splitlines()]
+    heads = [l.split(":", 1)[0] for l in lines if l.startswith("Output ") or l in summary_lines(job.logs["aio_plain"])]
+    assert heads == ["Output trimmed SAM/BAM", "Output variants VCF", "Output indel VCF", "Output deletion events", "Output strand tallies",
+                     "Output per-amplicon counts", "Output codon table", "Output amino-acid calls", "Output co-occurrence table", "Output error profile",
+                     "Output haplotype table", "Output read-position tallies", "Output QC report", "QC", "Amplicons", "Codons", "Co-occurrence",
+                     "Error profile", "Haplotypes"]
+
+
 # ---- (a), (b) -------------------------------------------------------------------------------------------------------------------
 def check_reach(job, tag, shares):
     batch = job.batch[tag]
@@ -375,7 +393,7 @@ def test_every_report_bam_in_bam_out(job, tmp_path, world, tag, pieces):
     check_same_files(tmp_path, want, TEXT_OUTPUTS)
     check_same_bam(tmp_path / "out.bam", want / "out.bam")
     assert "Trimmed reads of %d ranks joined" % world in logs[0]
-    check_same_summaries(logs[0], job.logs["aio_" + tag], 5)
+    check_same_summaries(logs[0], job.logs["aio_" + tag], 6)
     check_only_rank_0_wrote(tmp_path, logs)
     how = re.findall(r"rank_worker: all-reduce of device tensors: (.*)", "\n".join(logs))
     print("all-reduce of device tensors:", how)
@@ -391,7 +409,7 @@ def test_text_in_world_2(job, tmp_path):
     assert status == [0, 0], "\n".join(logs)
     for name in TEXT_OUTPUTS:
         assert read(tmp_path / name) == read(want / name), name
-    check_same_summaries(logs[0], job.logs["aio_sam"], 5)
+    check_same_summaries(logs[0], job.logs["aio_sam"], 6)
     # the trimmed reads of dealt-out text are NOT joined: one file per rank, together the one-process file's records
     assert sorted(set(os.listdir(str(tmp_path))) - set(TEXT_OUTPUTS)) == ["out.part0.bam", "out.part1.bam"]
 
@@ -414,9 +432,9 @@ def test_variants_and_consensus_alone_world_2(job, tmp_path, command):
     status, logs = run_ranks(2, tmp_path, argv, part_bytes=size // 4 + 1)
     assert status == [0, 0], "\n".join(logs)
     names = sorted(os.listdir(str(want)))
-    assert names == sorted(["out.vcf" if command == "variants" else "out.fas", "c.tsv", "co.tsv", "ep.json", "del.tsv", "s.tsv"])
+    assert names == sorted(["out.vcf" if command == "variants" else "out.fas", "c.tsv", "co.tsv", "ep.json", "del.tsv", "s.tsv", "hap.tsv", "rp.tsv"])
     check_same_files(tmp_path, want, names)
-    check_same_summaries(logs[0], job.logs[command], 3)
+    check_same_summaries(logs[0], job.logs[command], 4)
     shares = shares_of(logs[0], 2)
     assert all(n > 0 for n in shares) and sum(shares) == job.batch["plain"].n
     check_only_rank_0_wrote(tmp_path, logs, at_least=len(names))
@@ -436,7 +454,7 @@ def test_ranks_with_an_empty_share_world_3(job, tmp_path):
     assert sum("Finished Processing -1 reads" in log for log in logs) == 2
     check_same_files(tmp_path, want, TEXT_OUTPUTS)
     check_same_bam(tmp_path / "out.bam", want / "out.bam")
-    check_same_summaries(logs[0], job.logs["aio_thin"], 5)
+    check_same_summaries(logs[0], job.logs["aio_thin"], 6)
     check_only_rank_0_wrote(tmp_path, logs)
     recs = vcf_records(read(want / "out.vcf").decode())
     assert "A" in recs[job.pa][0] and len(recs) > 5              # (the thin job still calls its variants)
