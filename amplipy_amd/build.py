@@ -26,8 +26,8 @@ UNIT_DEPS = {"amplihip.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")
                                    "amp_fast5.hpp", "amp_fast6.hpp", "amp_fast7.hpp", "amp_wave.hpp", "amp_heavy.hpp")],
              "amp_ins.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_ins.hpp")],
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
-             # (amp_hook.hpp: the host shell the nine hooks behind the read pass share; amp_tally.hpp: the device skeleton of the three
-             # windowed tally kernels)
+             # (amp_hook.hpp: the host shell the nine hooks behind the read pass share; amp_tally.hpp: the device skeleton of the four
+             # windowed tally kernels, and the whole loop of k_strand and k_readpos)
              "amp_qc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_qc.hpp")],
              "amp_strand.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_tally.hpp")],
              "amp_amplicon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_amplicon.hpp", "amp_tally.hpp")],

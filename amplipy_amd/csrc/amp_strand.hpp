@@ -11,11 +11,14 @@
 // segment (reference start, query start, length) per M = X op and a deletion segment (reference start, length) per D N op.
 // On such a read every pair of a match op lies inside [query_alignment_start, query_alignment_end), the pairs the insertion
 // scan (A:730-748) swallows are inserted or clipped bases, and no pair follows the break of A:726 that could count: the
-// counted set is every deleted position and every match base whose quality reaches min_quality.  strand_walk: the six-key
+// counted set is every deleted position and every match base whose quality reaches min_quality.  six_key_walk: the six-key
 // part of the exact walk (count_read_walk, amp_read.hpp) for every other read, pair by pair, with the quality test in front
-// of the soft-clip tests, the break at the first good base at or past query_alignment_end, and the insertion scan's pairs.
+// of the soft-clip tests, the break at the first good base at or past query_alignment_end, and the insertion scan's pairs;
+// strand_walk and readpos_walk (amp_readpos.hpp) are its two adapters.  StrandTally, at the end: what k_strand's loop
+// (tally_poswin, amp_tally.hpp) and the twin's (poswin_twin.hpp) are told about this tally.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/amplihip.h"
@@ -42,9 +45,6 @@ constexpr int ST_CELLS = ST_REV_COLS + ST_QSUM_COLS;      // u32 cells of a wind
 constexpr int ST_TILES_PER_BLOCK = 4;    // a block takes at least this many tiles before another block is added
 constexpr int ST_BLOCKS_PER_CU = 4;      // ... and the grid stops growing here
 constexpr int ST_MAX_TILES_PER_FLUSH = 32768;      // a cell takes at most 256 adds of at most 255 per tile: 32768 tiles stay below 2^32
-static_assert(ST_W % (ST_CHUNK * (ST_BLOCK / 64)) == 0, "every wave owns the same number of chunks of the window");
-static_assert(ST_CELLS == 11 && (ST_CELLS & 1), "an odd stride: the lanes of a wave hit 64 different banks");
-static_assert((uint64_t)ST_MAX_TILES_PER_FLUSH * 256u * 255u < (1ull << 32), "a window cell cannot overflow before its flush");
 
 constexpr uint32_t ST_OP_M = 0, ST_OP_I = 1, ST_OP_D = 2, ST_OP_N = 3, ST_OP_S = 4, ST_OP_H = 5, ST_OP_P = 6, ST_OP_EQ = 7, ST_OP_X = 8;
 AMP_ST_HD bool st_is_match(uint32_t op) { return op == ST_OP_M || op == ST_OP_EQ || op == ST_OP_X; }
@@ -154,19 +154,23 @@ AMP_ST_HD bool strand_base(const uint8_t *seq, const uint8_t *qual, uint64_t k, 
     return (int32_t)qv >= min_quality && col < (uint32_t)ST_QSUM_COLS;
 }
 
-// The window cell of column c's reverse count / quality sum
-AMP_ST_HD int st_cell_rev(int32_t wpos, uint32_t col) { return wpos * ST_CELLS + (int)col; }
-AMP_ST_HD int st_cell_qsum(int32_t wpos, uint32_t col) { return wpos * ST_CELLS + ST_REV_COLS + (int)col; }
-
-// A tile whose regular reads span [lo, hi) stays on a window anchored at `anchor` when all of them fit it; otherwise the
-// window is flushed and anchored again at lo.  (No regular read: lo > hi, nothing moves.)
-AMP_ST_HD bool strand_window_keeps(int32_t anchor, int32_t lo, int32_t hi) {
-    return lo > hi || (lo >= anchor && (int64_t)hi <= (int64_t)anchor + ST_W);
+// The window rule of the position-window tallies (k_strand, k_readpos), on W positions and SLOTS segment slots per read.  A
+// tile whose regular reads span [lo, hi) stays on a window anchored at `anchor` when all of them fit it; otherwise the window
+// is flushed and anchored again at lo.  (No regular read: lo > hi, nothing moves.)
+template <int W>
+AMP_ST_HD bool poswin_keeps(int32_t anchor, int32_t lo, int32_t hi) {
+    return lo > hi || (lo >= anchor && (int64_t)hi <= (int64_t)anchor + W);
 }
 // A read takes the window when it is regular, fits its slots and lies inside the window.
-AMP_ST_HD bool strand_read_windowed(const StrandShape &sh, int32_t pos, int32_t anchor) {
-    return sh.regular && sh.n_seg <= ST_SLOTS && pos >= anchor && (int64_t)sh.ref_end <= (int64_t)anchor + ST_W;
+template <int W, int SLOTS>
+AMP_ST_HD bool poswin_read_windowed(const StrandShape &sh, int32_t pos, int32_t anchor) {
+    return sh.regular && sh.n_seg <= SLOTS && pos >= anchor && (int64_t)sh.ref_end <= (int64_t)anchor + W;
 }
+// The rule and the window cells of column c under the strand tallies' own names, for callers that name them: one-line forwards
+AMP_ST_HD bool strand_window_keeps(int32_t anchor, int32_t lo, int32_t hi) { return poswin_keeps<ST_W>(anchor, lo, hi); }
+AMP_ST_HD bool strand_read_windowed(const StrandShape &sh, int32_t pos, int32_t anchor) { return poswin_read_windowed<ST_W, ST_SLOTS>(sh, pos, anchor); }
+AMP_ST_HD int st_cell_rev(int32_t wpos, uint32_t col) { return wpos * ST_CELLS + (int)col; }
+AMP_ST_HD int st_cell_qsum(int32_t wpos, uint32_t col) { return st_cell_rev(wpos, col) + ST_REV_COLS; }
 
 // query_alignment_start / _end of pysam as count_read_walk reads them (hard clips skipped; a hard clip inside the soft clip
 // raises: such a read has a status and adds nothing).
@@ -213,11 +217,13 @@ struct StrandPairs {
     }
 };
 
-// The six-key part of the exact walk for one read: sink(ref_pos, col, quality) for every increment (col 5: a deleted
-// position, quality 0).  Where the reference raises the read has a status and its adds are unspecified: the walk ends there.
-// Every position handed out lies inside [0, ref_len), every byte read inside the read's l_seq bases.
+// The six-key part of the exact walk for one read, the one copy of it: sink(ref_pos, col, q, qs, qe) for every increment, with
+// the read's query bounds [qs, qe).  A match base: col < 5 and q its query index.  A deleted position: col 5 and q the query
+// index the next pair with one takes.  Where the reference raises the read has a status and its adds are unspecified: the walk
+// ends there.  Every position handed out lies inside [0, ref_len), every byte read and every q of a match base inside the
+// read's l_seq bases.
 template <class Sink>
-AMP_ST_HD void strand_walk(const StrandRead &R, const StrandParams &P, const uint8_t *seq, const uint8_t *qual, Sink sink) {
+AMP_ST_HD void six_key_walk(const StrandRead &R, const StrandParams &P, const uint8_t *seq, const uint8_t *qual, Sink sink) {
     int32_t qs, qe;
     if (!st_query_bounds(R, qs, qe) || R.lseq <= 0) return;
     const bool have_qual = qual[R.base] != 0xFFu;
@@ -231,7 +237,7 @@ AMP_ST_HD void strand_walk(const StrandRead &R, const StrandParams &P, const uin
         else if (!it.next(q, r)) break;
         if (q < 0) {                                                                       // A:714-715
             if ((uint32_t)r >= (uint32_t)P.ref_len) return;
-            sink(r, 5u, 0u);
+            sink(r, 5u, it.q, qs, qe);                                                     // (it.q: the next pair's query index)
             continue;
         }
         if (!have_qual || q >= R.lseq) return;
@@ -252,9 +258,64 @@ AMP_ST_HD void strand_walk(const StrandRead &R, const StrandParams &P, const uin
         if ((uint32_t)r >= (uint32_t)P.ref_len) return;                                    // A:751-753
         const uint32_t col = st_code_to_col(st_base_code(seq, R.base + (uint64_t)q));
         if (col == 0xFFu) return;
-        sink(r, col, (uint32_t)qual[R.base + (uint64_t)q]);
+        sink(r, col, q, qs, qe);
     }
 }
 
+// The walk as the strand tallies, amplicon_walk and del_events_walk take it: sink(ref_pos, col, quality) (col 5: quality 0)
+template <class Sink>
+AMP_ST_HD void strand_walk(const StrandRead &R, const StrandParams &P, const uint8_t *seq, const uint8_t *qual, Sink sink) {
+    six_key_walk(R, P, seq, qual, [&](int32_t r, uint32_t col, int32_t q, int32_t, int32_t) {
+        sink(r, col, col == 5u ? 0u : (uint32_t)qual[R.base + (uint64_t)q]);
+    });
+}
+
+// The strand tallies as tally_poswin (amp_tally.hpp) and its CPU twin (tests/hostsim/poswin_twin.hpp) take them.  A window
+// position has WORDS = 11 u32 words, one per cell: six reverse counts, then five quality sums.  "add(c, v)": cell c of the
+// position at hand gets v.
+struct StrandTally {
+    static constexpr int BLOCK = ST_BLOCK, SLOTS = ST_SLOTS, CHUNK = ST_CHUNK, W = ST_W, WORDS = ST_CELLS, MAX_TILES_PER_FLUSH = ST_MAX_TILES_PER_FLUSH;
+    using Seg = StrandSeg;
+    struct Out {
+        uint32_t *rev;                   // [ref_len][6]
+        unsigned long long *qsum;        // [ref_len][5]
+    };
+    template <class Put>
+    static AMP_ST_HD StrandShape segments(const StrandRead &R, const StrandParams &P, uint32_t qual0, Put put) { return strand_segments(R, P, qual0, put); }
+    // what a segment adds at offset k of its span (a forward read's deletions are not in the list)
+    template <class Add>
+    static AMP_ST_HD void seg_adds(const Seg &g, int32_t k, const uint8_t *seq, const uint8_t *qual, int32_t min_quality, Add add) {
+        if (st_seg_del(g)) {
+            add(5, 1u);
+        } else {
+            uint32_t col, qv;
+            if (strand_base(seq, qual, g.q0 + (uint64_t)k, min_quality, col, qv)) {
+                add(ST_REV_COLS + (int)col, qv);
+                if (st_seg_rev(g)) add((int)col, 1u);
+            }
+        }
+    }
+    // the serial walk, sink(ref_pos, col, quality), and what one of its increments adds
+    template <class Sink>
+    static AMP_ST_HD void walk(const StrandRead &R, const StrandParams &P, const uint8_t *seq, const uint8_t *qual, Sink sink) { strand_walk(R, P, seq, qual, sink); }
+    template <class Add>
+    static AMP_ST_HD void walk_adds(const StrandRead &R, uint32_t col, uint32_t qv, Add add) {
+        if (R.rev) add((int)col, 1u);
+        if (col < (uint32_t)ST_QSUM_COLS) add(ST_REV_COLS + (int)col, qv);
+    }
+    // the window word of cell c of window position w, and what an add of v adds to it
+    static AMP_ST_HD int word(int32_t w, int c) { return w * ST_CELLS + c; }
+    static AMP_ST_HD uint32_t inc(int, uint32_t v) { return v; }
+    // cell c of table position p gets v, by plus(address, v); word k of a flushed window position is cell k
+    template <class Plus>
+    static AMP_ST_HD void to_table(const Out &o, size_t p, int c, uint32_t v, Plus plus) {
+        if (c < ST_REV_COLS) plus(&o.rev[p * ST_REV_COLS + c], v);
+        else plus(&o.qsum[p * ST_QSUM_COLS + (c - ST_REV_COLS)], (unsigned long long)v);
+    }
+    template <class Plus>
+    static AMP_ST_HD void flush_word(const Out &o, size_t p, int k, uint32_t v, Plus plus) { to_table(o, p, k, v, plus); }
+};
+static_assert(StrandTally::WORDS == 11 && (StrandTally::WORDS & 1), "an odd stride: the lanes of a wave hit 64 different banks");
+static_assert((uint64_t)StrandTally::MAX_TILES_PER_FLUSH * StrandTally::BLOCK * 255u < (1ull << 32), "a window cell cannot overflow before its flush");
 }  // namespace amp
 // (the hook amplihip.hip runs behind the read pass is strand_hook of amp_strand.hip, declared in amp_hook.hpp)

@@ -123,22 +123,8 @@ int twin_codon(int64_t n, const int32_t *pos, const uint32_t *lseq, const uint32
 }  // extern "C"
 
 #ifdef CODON_TWIN_MAIN
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd(uint32_t n) {      // xorshift64*, [0, n)
-    rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27;
-    return (uint32_t)(((rng_state * 0x2545F4914F6CDD1Dull) >> 33) % n);
-}
-
-#define CHECK(c)                                                             \
-    do {                                                                     \
-        if (!(c)) { printf("codon_twin: check failed at line %d: %s\n", __LINE__, #c); return 1; } \
-    } while (0)
-
-template <class T> static T *exact(const std::vector<T> &v) {      // a heap block of exactly the vector's size
-    T *p = (T *)malloc(v.size() ? v.size() * sizeof(T) : 1);
-    if (v.size()) memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
+#define TWIN_NAME "codon_twin"
+#include "twin_main.hpp"
 
 int main() {
     static const uint32_t codes[5] = {1, 2, 4, 8, 15};

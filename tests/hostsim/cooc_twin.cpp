@@ -117,22 +117,8 @@ int twin_cooc_plain(int64_t n, const int32_t *pos, const uint32_t *lseq, const u
 }  // extern "C"
 
 #ifdef COOC_TWIN_MAIN
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd(uint32_t n) {      // xorshift64*, [0, n)
-    rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27;
-    return (uint32_t)(((rng_state * 0x2545F4914F6CDD1Dull) >> 33) % n);
-}
-
-#define CHECK(c)                                                             \
-    do {                                                                     \
-        if (!(c)) { printf("cooc_twin: check failed at line %d: %s\n", __LINE__, #c); return 1; } \
-    } while (0)
-
-template <class T> static T *exact(const std::vector<T> &v) {      // a heap block of exactly the vector's size
-    T *p = (T *)malloc(v.size() ? v.size() * sizeof(T) : 1);
-    if (v.size()) memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
+#define TWIN_NAME "cooc_twin"
+#include "twin_main.hpp"
 
 struct Sets {
     std::vector<int32_t> first, off, pos, len, sym;

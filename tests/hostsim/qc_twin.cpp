@@ -64,16 +64,8 @@ void twin_regions(const uint32_t *depth, int32_t ref_len, int32_t n_regions, con
 }  // extern "C"
 
 #ifdef QC_TWIN_MAIN
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd(uint32_t n) {      // xorshift64*, [0, n)
-    rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27;
-    return (uint32_t)(((rng_state * 0x2545F4914F6CDD1Dull) >> 33) % n);
-}
-
-#define CHECK(c)                                                             \
-    do {                                                                     \
-        if (!(c)) { printf("qc_twin: check failed at line %d: %s\n", __LINE__, #c); return 1; } \
-    } while (0)
+#define TWIN_NAME "qc_twin"
+#include "twin_main.hpp"
 
 int main() {
     for (int round = 0; round < 200; ++round) {

@@ -6,16 +6,22 @@
 //   g++ -O1 -g -std=c++17 -DSTRAND_TWIN_MAIN -fsanitize=address,undefined -I amplipy_amd/csrc -o strand_twin strand_twin.cpp && ./strand_twin
 // The second form is a program of its own, so that it runs under the sanitizers without a sanitizer runtime inside Python:
 // seeded batches in heap blocks of exactly the needed size, so a read outside them is reported.
+// The loop itself is twin_poswin of poswin_twin.hpp, shared with readpos_twin.cpp.
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
 
 #include "amp_strand.hpp"
+#include "poswin_twin.hpp"
 
 using namespace amp;
+
+// The strand twin's part of twin_poswin: the bits of the return value, and no checks of its own
+struct StrandTwin {
+    static constexpr int BAD_FLUSH = 1, BAD_LIST = 2, BAD_SEG = 4, BAD_WALK = 8, BAD_CELL = 16;
+    int seg_check(const StrandSeg &, int32_t) { return 0; }
+    int walk_check(uint32_t) { return 0; }
+    void added(int32_t, int, uint32_t) {}
+    int flushed(int32_t, int, uint32_t) { return 0; }
+};
 
 extern "C" {
 
@@ -28,176 +34,30 @@ int twin_slots() { return ST_SLOTS; }
 // Returns non-zero when a step left its bounds (a cell outside the window, a segment past the list, a position past the tables).
 int twin_strand(int64_t n, const int32_t *pos, const uint16_t *flag, const uint32_t *lseq, const uint32_t *cig_off, const uint32_t *cig,
                 const uint32_t *seq_off8, const uint8_t *seq, const uint8_t *qual, const uint8_t *status, int32_t ref_len, int32_t min_quality,
-                int32_t force_serial, uint32_t *rev, uint64_t *qsum, int64_t *info) {
-    const StrandParams P{ref_len, min_quality};
-    std::vector<uint32_t> cell((size_t)ST_W * ST_CELLS, 0u);
-    std::vector<StrandSeg> segs((size_t)ST_BLOCK * ST_SLOTS);
-    int bad = 0;
-    int32_t anchor = 0;
-    int since = 0;
-    for (int k = 0; k < 4; ++k) info[k] = 0;
-    auto flush = [&]() {
-        bool any = false;
-        for (int k = 0; k < ST_W * ST_CELLS; ++k) {
-            const uint32_t v = cell[(size_t)k];
-            if (!v) continue;
-            any = true;
-            cell[(size_t)k] = 0u;
-            const int64_t p = (int64_t)anchor + k / ST_CELLS;
-            const int c = k % ST_CELLS;
-            if (p < 0 || p >= ref_len) { bad |= 1; continue; }
-            if (c < ST_REV_COLS) rev[(size_t)p * ST_REV_COLS + c] += v;
-            else qsum[(size_t)p * ST_QSUM_COLS + (c - ST_REV_COLS)] += v;
-        }
-        if (any) ++info[2];
-    };
-    for (int64_t base = 0; base < n; base += ST_BLOCK) {
-        const int m = (int)(n - base < ST_BLOCK ? n - base : ST_BLOCK);
-        StrandRead R[ST_BLOCK];
-        StrandShape sh[ST_BLOCK];
-        bool live[ST_BLOCK];
-        uint32_t qual0[ST_BLOCK];
-        int32_t lo = 0x7FFFFFFF, hi = -0x7FFFFFFF - 1;
-        for (int t = 0; t < m; ++t) {
-            const int64_t i = base + t;
-            live[t] = !status || status[i] == 0;
-            R[t] = StrandRead{pos[i], cig + cig_off[i], cig_off[i + 1] - cig_off[i], (int32_t)lseq[i], (flag[i] & 0x10u) ? 1u : 0u, (uint64_t)seq_off8[i] * 8ull};
-            qual0[t] = R[t].lseq > 0 ? qual[R[t].base] : 0xFFu;
-            sh[t] = StrandShape{false, 0, 0};
-            if (!live[t]) continue;
-            sh[t] = strand_segments(R[t], P, qual0[t], [](const StrandSeg &) {});
-            if (force_serial) sh[t].regular = false;
-            if (sh[t].regular) { lo = R[t].pos < lo ? R[t].pos : lo; hi = sh[t].ref_end > hi ? sh[t].ref_end : hi; }
-        }
-        if (!strand_window_keeps(anchor, lo, hi) || since >= ST_MAX_TILES_PER_FLUSH) {
-            flush();
-            if (lo <= hi) anchor = lo;
-            since = 0;
-        }
-        ++since;
-        size_t ns = 0;
-        bool win[ST_BLOCK];
-        for (int t = 0; t < m; ++t) {
-            win[t] = live[t] && strand_read_windowed(sh[t], R[t].pos, anchor);
-            if (!win[t]) continue;
-            ++info[0];
-            strand_segments(R[t], P, qual0[t], [&](const StrandSeg &s) {
-                if (ns < segs.size()) segs[ns++] = s; else bad |= 2;
-            });
-        }
-        for (size_t s = 0; s < ns; ++s) {
-            const StrandSeg g = segs[s];
-            const int32_t a0 = g.r0 - anchor, a1 = a0 + st_seg_len(g);
-            if (a0 < 0 || a1 > ST_W) { bad |= 4; continue; }
-            for (int32_t p = a0; p < a1; ++p) {
-                if (st_seg_del(g)) {
-                    cell[(size_t)st_cell_rev(p, 5u)] += 1u;
-                } else {
-                    uint32_t col, qv;
-                    if (strand_base(seq, qual, g.q0 + (uint64_t)(p - a0), min_quality, col, qv)) {
-                        cell[(size_t)st_cell_qsum(p, col)] += qv;
-                        if (st_seg_rev(g)) cell[(size_t)st_cell_rev(p, col)] += 1u;
-                    }
-                }
-            }
-        }
-        for (int t = 0; t < m; ++t) {
-            if (!live[t] || win[t]) continue;
-            ++info[1];
-            const uint32_t rv = R[t].rev;
-            strand_walk(R[t], P, seq, qual, [&](int32_t r, uint32_t col, uint32_t qv) {
-                if (r < 0 || r >= ref_len || col > 5u) { bad |= 8; return; }
-                const int64_t w = (int64_t)r - (int64_t)anchor;
-                if (w >= 0 && w < ST_W) {
-                    ++info[3];
-                    if (rv) cell[(size_t)st_cell_rev((int32_t)w, col)] += 1u;
-                    if (col < (uint32_t)ST_QSUM_COLS) cell[(size_t)st_cell_qsum((int32_t)w, col)] += qv;
-                } else {
-                    if (rv) rev[(size_t)r * ST_REV_COLS + col] += 1u;
-                    if (col < (uint32_t)ST_QSUM_COLS) qsum[(size_t)r * ST_QSUM_COLS + col] += qv;
-                }
-            });
-        }
-    }
-    flush();
-    return bad;
+                int32_t force_serial, uint32_t *rev, unsigned long long *qsum, int64_t *info) {      // (qsum: 64 bits, as the kernel's atomics name them)
+    StrandTwin x;
+    return twin_poswin<StrandTally>(n, pos, flag, lseq, cig_off, cig, seq_off8, seq, qual, status, ref_len, min_quality, force_serial,
+                                    StrandTally::Out{rev, qsum}, info, x);
 }
 
 }  // extern "C"
 
 #ifdef STRAND_TWIN_MAIN
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static uint32_t rnd(uint32_t n) {      // xorshift64*, [0, n)
-    rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27;
-    return (uint32_t)(((rng_state * 0x2545F4914F6CDD1Dull) >> 33) % n);
-}
-
-#define CHECK(c)                                                             \
-    do {                                                                     \
-        if (!(c)) { printf("strand_twin: check failed at line %d: %s\n", __LINE__, #c); return 1; } \
-    } while (0)
-
-template <class T> static T *exact(const std::vector<T> &v) {      // a heap block of exactly the vector's size
-    T *p = (T *)malloc(v.size() ? v.size() * sizeof(T) : 1);
-    if (v.size()) memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
+#define TWIN_NAME "strand_twin"
+#include "twin_main.hpp"
 
 int main() {
-    static const uint32_t codes[5] = {1, 2, 4, 8, 15};
     int64_t windowed = 0, serial = 0;
     for (int round = 0; round < 300; ++round) {
-        const int32_t G = 1 + (int32_t)rnd(round % 5 == 0 ? 4 : 3000);
-        const int64_t n = rnd(round % 3 == 0 ? 700 : 40);
-        const int32_t mq = (int32_t)rnd(50);
-        std::vector<int32_t> pos;
-        std::vector<uint16_t> flag;
-        std::vector<uint32_t> lseq, coff(1, 0u), words, soff(1, 0u);
-        std::vector<uint8_t> seq, qual, status;
-        int32_t pile = (int32_t)rnd((uint32_t)G);
-        for (int64_t i = 0; i < n; ++i) {
-            std::vector<uint32_t> ops;
-            uint32_t L = 0;
-            const uint32_t kind = rnd(10);
-            if (kind < 6) {                       // regular: clips, a core of up to 9 ops, clips
-                if (rnd(4) == 0) ops.push_back((rnd(5) << 4) | ST_OP_H);
-                if (rnd(3) == 0) ops.push_back((rnd(9) << 4) | ST_OP_S);
-                const uint32_t core = 1 + rnd(kind == 0 ? 9 : 3);
-                for (uint32_t k = 0; k < core; ++k) {
-                    static const uint32_t pick[7] = {ST_OP_M, ST_OP_M, ST_OP_EQ, ST_OP_X, ST_OP_I, ST_OP_D, ST_OP_N};
-                    ops.push_back((rnd(k % 2 ? 6 : 90) << 4) | pick[rnd(k == 0 ? 4 : 7)]);
-                }
-                if (rnd(3) == 0) ops.push_back((rnd(9) << 4) | ST_OP_S);
-                if (rnd(4) == 0) ops.push_back((rnd(5) << 4) | ST_OP_H);
-            } else {                              // anything
-                const uint32_t k = rnd(8) == 0 ? 40 + rnd(10) : rnd(6);
-                for (uint32_t j = 0; j < k; ++j) ops.push_back((rnd(30) << 4) | rnd(10));
-            }
-            for (uint32_t v : ops) { const uint32_t op = v & 15u; if (op == ST_OP_M || op == ST_OP_I || op == ST_OP_S || op == ST_OP_EQ || op == ST_OP_X) L += v >> 4; }
-            if (rnd(12) == 0) L = rnd(2) ? L + 1 + rnd(5) : (L > 3 ? L - 1 - rnd(3) : 0);      // l_seq and the CIGAR disagree
-            for (uint32_t v : ops) words.push_back(v);
-            coff.push_back((uint32_t)words.size());
-            // a pile, a wide spread, and reads in front of and behind the reference
-            const uint32_t where = rnd(10);
-            pos.push_back(where < 6 ? pile + (int32_t)rnd(40) : where < 9 ? (int32_t)rnd((uint32_t)G + 30) - 15 : (int32_t)rnd(2) * (G - 1));
-            flag.push_back((uint16_t)((rnd(2) ? 0x10u : 0u) | (rnd(2) ? 0x1u : 0u)));
-            lseq.push_back(L);
-            status.push_back(rnd(25) == 0 ? (uint8_t)(1 + rnd(9)) : (uint8_t)0);
-            const uint32_t padded = (L + 7u) & ~7u;
-            const size_t q0 = qual.size();
-            for (uint32_t k = 0; k < padded; ++k) qual.push_back((uint8_t)rnd(60));
-            if (L && rnd(30) == 0) qual[q0] = 0xFF;
-            for (uint32_t k = 0; k < padded / 2; ++k) seq.push_back((uint8_t)((codes[rnd(5)] << 4) | codes[rnd(5)]));
-            soff.push_back((uint32_t)(qual.size() / 8));
-        }
-        int32_t *p_pos = exact(pos); uint16_t *p_flag = exact(flag); uint32_t *p_lseq = exact(lseq), *p_coff = exact(coff), *p_cig = exact(words), *p_soff = exact(soff);
-        uint8_t *p_seq = exact(seq), *p_qual = exact(qual), *p_st = exact(status);
+        TwinReads b;
+        b.draw(round);
+        const int32_t G = b.G, mq = b.mq;
         const size_t nr = (size_t)G * ST_REV_COLS, nq = (size_t)G * ST_QSUM_COLS;
-        uint32_t *rev[2]; uint64_t *qs[2];
+        uint32_t *rev[2]; unsigned long long *qs[2];
         int64_t info[2][4];
         for (int mode = 0; mode < 2; ++mode) {
-            rev[mode] = (uint32_t *)calloc(nr, 4); qs[mode] = (uint64_t *)calloc(nq, 8);
-            CHECK(twin_strand(n, p_pos, p_flag, p_lseq, p_coff, p_cig, p_soff, p_seq, p_qual, p_st, G, mq, mode, rev[mode], qs[mode], info[mode]) == 0);
+            rev[mode] = (uint32_t *)calloc(nr, 4); qs[mode] = (unsigned long long *)calloc(nq, 8);
+            CHECK(twin_strand(b.n, b.pos, b.flag, b.lseq, b.coff, b.cig, b.soff, b.seq, b.qual, b.status, G, mq, mode, rev[mode], qs[mode], info[mode]) == 0);
         }
         // the window and the walk agree on every read, and the all-serial run never touches the segments
         CHECK(memcmp(rev[0], rev[1], nr * 4) == 0 && memcmp(qs[0], qs[1], nq * 8) == 0);
@@ -206,7 +66,7 @@ int main() {
         // a quality sum is at least min_quality per reverse read that was counted there
         for (int32_t p = 0; p < G; ++p)
             for (int c = 0; c < ST_QSUM_COLS; ++c) CHECK(qs[0][(size_t)p * ST_QSUM_COLS + c] >= (uint64_t)mq * rev[0][(size_t)p * ST_REV_COLS + c]);
-        free(p_pos); free(p_flag); free(p_lseq); free(p_coff); free(p_cig); free(p_soff); free(p_seq); free(p_qual); free(p_st);
+        b.release();
         for (int mode = 0; mode < 2; ++mode) { free(rev[mode]); free(qs[mode]); }
     }
     CHECK(windowed > 1000 && serial > 1000);
