@@ -27,15 +27,15 @@ UNIT_DEPS = {"amplihip.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")
              "amp_ins.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_ins.hpp")],
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
              # (amp_hook.hpp: the host shell the nine hooks behind the read pass share; amp_tally.hpp: the device skeleton of the four
-             # windowed tally kernels, and the whole loop of k_strand and k_readpos)
+             # windowed tally kernels, and the whole loop of k_strand and k_readpos; amp_keyed.hpp: the keyed table of del and hap)
              "amp_qc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_qc.hpp")],
              "amp_strand.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_tally.hpp")],
              "amp_amplicon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_amplicon.hpp", "amp_tally.hpp")],
              "amp_codon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_codon.hpp", "amp_tally.hpp")],
-             "amp_del.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_del.hpp", "amp_tally.hpp")],
+             "amp_del.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_del.hpp", "amp_keyed.hpp", "amp_tally.hpp")],
              "amp_cooc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_cooc.hpp", "amp_tally.hpp")],
              "amp_errprof.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_errprof.hpp", "amp_tally.hpp")],
-             "amp_hap.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_hap.hpp", "amp_tally.hpp")],
+             "amp_hap.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_hap.hpp", "amp_keyed.hpp", "amp_tally.hpp")],
              "amp_readpos.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_readpos.hpp", "amp_tally.hpp")],
              "amp_sam.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in
                              ("amp_codec.hpp", "amp_bgzf.hpp", "amp_bamout.hpp", "amp_bamtail.hpp")],

@@ -84,7 +84,7 @@ k_amplicon(AmpliconArgs a) {
         StrandRead R;
         uint32_t qual0;
         tally_no_read(in, R, qual0);
-        StrandShape sh = {false, 0, 0};
+        StrandShape sh = ST_NO_READ;
         const bool live = tally_live(in, i);
         int32_t amp = -1, lo_a = 0, hi_a = 0;
         size_t row0 = 0;
@@ -112,18 +112,19 @@ k_amplicon(AmpliconArgs a) {
         // the wave's distinct amplicons that want a window, one request each: (amplicon, first position, last end)
         const bool want = live && amplicon_wants_slot(amp, sh, R.pos, lo_a, hi_a);
         {
-            unsigned long long pending = __ballot(want);
-            int nreq = 0;
-            while (pending) {                                      // (wave-uniform)
-                const int src = __ffsll((long long)pending) - 1;
-                const int32_t v = __shfl(amp, src);
-                const bool mine = want && amp == v;
+            int nreq = 0;                                          // (wave-uniform; the requests past AM_REQ_PER_WAVE are counted, not kept)
+            int32_t v = -1;                                        // the leader's amplicon, in every lane
+            const auto same_amp = [&](int src) {
+                v = __shfl(amp, src);
+                return want && amp == v;
+            };
+            wave_each_distinct(want, same_amp, [&](int src, unsigned long long same) {
+                const bool mine = ((same >> lane) & 1ull) != 0ull;
                 int32_t l = mine ? R.pos : SPAN_NO_LO, h = mine ? sh.ref_end : SPAN_NO_HI;
-                wave_span(l, h);
+                wave_span(l, h);                                   // (every lane)
                 if (lane == src && nreq < AM_REQ_PER_WAVE) s_req[wave * AM_REQ_PER_WAVE + nreq] = AmReq{v, l, h, lo_a};
                 ++nreq;
-                pending &= ~__ballot(mine);
-            }
+            });
             if (lane == 0) s_nreq[wave] = min(nreq, AM_REQ_PER_WAVE);
         }
         __syncthreads();
@@ -201,21 +202,7 @@ k_amplicon(AmpliconArgs a) {
     amplicon_flush(s_cell, s_slots, (1u << AM_SLOTS) - 1u, a);
 }
 
-static size_t count_bytes(const AmpliconState *s) { return (size_t)s->cells * AM_COLS * 4; }
-static size_t read_bytes(const AmpliconState *s) { return ((size_t)s->n_amp + 1) * 8; }
-
 static AmpliconState *amplicon_state(amp_ctx *c) { return hook_state<AmpliconState>(c, HOOK_AMPLICON); }
-
-static void amplicon_free(void *state) {
-    AmpliconState *s = hook_state_of<AmpliconState>(state);
-    if (!s) return;
-    if (s->d_lo) (void)hipFree(s->d_lo);
-    if (s->d_start) (void)hipFree(s->d_start);
-    if (s->d_counts) (void)hipFree(s->d_counts);
-    if (s->d_reads) (void)hipFree(s->d_reads);
-    s->timer.destroy();
-    delete s;
-}
 
 static int amplicon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
@@ -227,15 +214,7 @@ static int amplicon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_
     });
 }
 
-static int amplicon_reset(amp_ctx *c) {
-    const HookCtx q = ctx_hook(c);
-    AmpliconState *s = amplicon_state(c);
-    HOOKCHK(q, hipMemsetAsync(s->d_counts, 0, count_bytes(s), q.stream));
-    HOOKCHK(q, hipMemsetAsync(s->d_reads, 0, read_bytes(s), q.stream));
-    return AMP_OK;
-}
-
-HookOps amplicon_hook = {"the amplicon tables need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, amplicon_enqueue, amplicon_reset, amplicon_free};
+HookOps amplicon_hook = {"the amplicon tables need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, amplicon_enqueue, hook_free<AmpliconState>};
 
 }  // namespace amp
 
@@ -275,21 +254,23 @@ int amp_amplicon_enable(amp_ctx *c, int32_t n_amp, const int32_t *lo, const int3
     if (s && (s->n_amp != n_amp || s->cells != cells)) {
         // another amplicon set: the tables are laid out again (a kernel of the old one may still be in flight)
         HOOKCHK(q, hipStreamSynchronize(q.stream));
-        amplicon_free(s);
+        hook_free<AmpliconState>(s);
         s = nullptr; slot.state = nullptr; slot.on = false;
     }
     if (!s) {
-        const int rc = hook_new_state(q, slot, amplicon_hook, s, [&](AmpliconState &f) -> int {
+        HOOKTRY(hook_new_state(q, slot, amplicon_hook, s, [&](AmpliconState &f) -> int {
             f.n_amp = n_amp; f.cells = cells;
-            HOOKCHK(q, hipMalloc((void **)&f.d_lo, A * 12));
+            const size_t n_counts = (size_t)cells * AM_COLS;
+            HOOKTRY(hook_alloc(q, f, &f.d_lo, A * 12));
             f.d_hi = f.d_lo + A; f.d_off = (uint32_t *)(f.d_hi + A);
-            HOOKCHK(q, hipMalloc((void **)&f.d_start, std::max<size_t>(G * 8, 8)));
+            HOOKTRY(hook_alloc(q, f, &f.d_start, std::max<size_t>(G * 8, 8)));
             f.d_end = f.d_start + G;
-            HOOKCHK(q, hipMalloc((void **)&f.d_counts, count_bytes(&f)));
-            HOOKCHK(q, hipMalloc((void **)&f.d_reads, read_bytes(&f)));
+            HOOKTRY(hook_alloc(q, f, &f.d_counts, n_counts * 4, n_counts * 4));
+            HOOKTRY(hook_alloc(q, f, &f.d_reads, (A + 1) * 8, (A + 1) * 8));
+            hook_table(f, f.d_counts, n_counts);
+            hook_table(f, f.d_reads, A + 1);
             return AMP_OK;
-        });
-        if (rc != AMP_OK) return rc;
+        }));
     }
     slot.on = false;
     HOOKCHK(q, hipMemcpyAsync(s->d_lo, lo, A * 4, hipMemcpyHostToDevice, q.stream));
@@ -299,34 +280,15 @@ int amp_amplicon_enable(amp_ctx *c, int32_t n_amp, const int32_t *lo, const int3
         HOOKCHK(q, hipMemcpyAsync(s->d_start, amp_start, G * 4, hipMemcpyHostToDevice, q.stream));
         HOOKCHK(q, hipMemcpyAsync(s->d_end, amp_end, G * 4, hipMemcpyHostToDevice, q.stream));
     }
-    const int rc = amplicon_reset(c);
-    if (rc != AMP_OK) return rc;
+    HOOKTRY(hook_zero(q, *s));
     HOOKCHK(q, hipStreamSynchronize(q.stream));        // (the caller's arrays and `off` are free again)
     slot.on = true;
     return AMP_OK;
 }
 
-int amp_amplicon_get(amp_ctx *c, uint32_t *counts, uint64_t *reads) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    AmpliconState *s = amplicon_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    if (counts) HOOKCHK(q, hipMemcpyAsync(counts, s->d_counts, count_bytes(s), hipMemcpyDeviceToHost, q.stream));
-    if (reads) HOOKCHK(q, hipMemcpyAsync(reads, s->d_reads, read_bytes(s), hipMemcpyDeviceToHost, q.stream));
-    HOOKCHK(q, hipStreamSynchronize(q.stream));
-    return AMP_OK;
-}
+int amp_amplicon_get(amp_ctx *c, uint32_t *counts, uint64_t *reads) { return hook_get(c, HOOK_AMPLICON, {counts, reads}); }
 
-int amp_amplicon_add(amp_ctx *c, const uint32_t *counts, const uint64_t *reads) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    AmpliconState *s = amplicon_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    const int rc = hook_add(q, s->d_counts, counts, (size_t)s->cells * AM_COLS);
-    return rc != AMP_OK ? rc : hook_add(q, (uint64_t *)s->d_reads, reads, (size_t)s->n_amp + 1);
-}
+int amp_amplicon_add(amp_ctx *c, const uint32_t *counts, const uint64_t *reads) { return hook_add_tables(c, HOOK_AMPLICON, {counts, reads}); }
 
 int amp_amplicon_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_AMPLICON, ms); }
 

@@ -148,31 +148,10 @@ k_codon(CodonArgs a) {
         __syncthreads();
     }
     codon_flush(s_cell, win_at.a0, a);
-    // the block's reads: a sum per wave, one atomic each
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        n_tallied += __shfl_xor(n_tallied, d);
-        n_skipped += __shfl_xor(n_skipped, d);
-    }
-    if (lane == 0) {
-        if (n_tallied) atomicAdd(&a.reads[0], (unsigned long long)n_tallied);
-        if (n_skipped) atomicAdd(&a.reads[1], (unsigned long long)n_skipped);
-    }
+    tally_wave_add2(a.reads, n_tallied, n_skipped);            // the block's reads
 }
-
-static size_t codon_bytes(const CodonState *s) { return (size_t)s->n_slots * CD_CELLS * 4; }
 
 static CodonState *codon_state(amp_ctx *c) { return hook_state<CodonState>(c, HOOK_CODON); }
-
-static void codon_free(void *state) {
-    CodonState *s = hook_state_of<CodonState>(state);
-    if (!s) return;
-    if (s->d_starts) (void)hipFree(s->d_starts);
-    if (s->d_codon) (void)hipFree(s->d_codon);
-    if (s->d_reads) (void)hipFree(s->d_reads);
-    s->timer.destroy();
-    delete s;
-}
 
 static int codon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
@@ -183,15 +162,7 @@ static int codon_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out
     });
 }
 
-static int codon_reset(amp_ctx *c) {
-    const HookCtx q = ctx_hook(c);
-    CodonState *s = codon_state(c);
-    HOOKCHK(q, hipMemsetAsync(s->d_codon, 0, codon_bytes(s), q.stream));
-    HOOKCHK(q, hipMemsetAsync(s->d_reads, 0, 16, q.stream));
-    return AMP_OK;
-}
-
-HookOps codon_hook = {"the codon tallies need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, codon_enqueue, codon_reset, codon_free};
+HookOps codon_hook = {"the codon tallies need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, codon_enqueue, hook_free<CodonState>};
 
 }  // namespace amp
 
@@ -220,50 +191,32 @@ int amp_codon_enable(amp_ctx *c, int32_t n_slots, const int32_t *starts) {
     if (s && (s->n_slots != n_slots || memcmp(s->starts.data(), starts, N * 4) != 0)) {
         // another set: the tables are laid out again (a kernel of the old one may still be in flight)
         HOOKCHK(q, hipStreamSynchronize(q.stream));
-        codon_free(s);
+        hook_free<CodonState>(s);
         s = nullptr; slot.state = nullptr; slot.on = false;
     }
     if (!s) {
-        const int rc = hook_new_state(q, slot, codon_hook, s, [&](CodonState &f) -> int {
+        HOOKTRY(hook_new_state(q, slot, codon_hook, s, [&](CodonState &f) -> int {
             f.n_slots = n_slots;
             f.starts.assign(starts, starts + N);
-            HOOKCHK(q, hipMalloc((void **)&f.d_starts, N * 4));
-            HOOKCHK(q, hipMalloc((void **)&f.d_codon, codon_bytes(&f)));
-            HOOKCHK(q, hipMalloc((void **)&f.d_reads, 16));
+            HOOKTRY(hook_alloc(q, f, &f.d_starts, N * 4));
+            HOOKTRY(hook_alloc(q, f, &f.d_codon, N * CD_CELLS * 4, N * CD_CELLS * 4));
+            HOOKTRY(hook_alloc(q, f, &f.d_reads, 16, 16));
+            hook_table(f, f.d_codon, N * CD_CELLS);
+            hook_table(f, f.d_reads, 2);
             HOOKCHK(q, hipMemcpyAsync(f.d_starts, f.starts.data(), N * 4, hipMemcpyHostToDevice, q.stream));
             HOOKCHK(q, hipStreamSynchronize(q.stream));
             return AMP_OK;
-        });
-        if (rc != AMP_OK) return rc;
+        }));
     }
     slot.on = false;
-    const int rc = codon_reset(c);
-    if (rc != AMP_OK) return rc;
+    HOOKTRY(hook_zero(q, *s));
     slot.on = true;
     return AMP_OK;
 }
 
-int amp_codon_get(amp_ctx *c, uint32_t *codon, uint64_t *reads) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    CodonState *s = codon_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    if (codon) HOOKCHK(q, hipMemcpyAsync(codon, s->d_codon, codon_bytes(s), hipMemcpyDeviceToHost, q.stream));
-    if (reads) HOOKCHK(q, hipMemcpyAsync(reads, s->d_reads, 16, hipMemcpyDeviceToHost, q.stream));
-    HOOKCHK(q, hipStreamSynchronize(q.stream));
-    return AMP_OK;
-}
+int amp_codon_get(amp_ctx *c, uint32_t *codon, uint64_t *reads) { return hook_get(c, HOOK_CODON, {codon, reads}); }
 
-int amp_codon_add(amp_ctx *c, const uint32_t *codon, const uint64_t *reads) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    CodonState *s = codon_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    const int rc = hook_add(q, s->d_codon, codon, (size_t)s->n_slots * CD_CELLS);
-    return rc != AMP_OK ? rc : hook_add(q, (uint64_t *)s->d_reads, reads, 2);
-}
+int amp_codon_add(amp_ctx *c, const uint32_t *codon, const uint64_t *reads) { return hook_add_tables(c, HOOK_CODON, {codon, reads}); }
 
 int amp_codon_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_CODON, ms); }
 

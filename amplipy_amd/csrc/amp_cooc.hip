@@ -74,8 +74,7 @@ k_cooc(CoocArgs a) {
         StrandRead R;
         uint32_t qual0;
         tally_no_read(in, R, qual0);
-        StrandShape sh;
-        sh.regular = false; sh.n_seg = 0; sh.ref_end = 0;
+        StrandShape sh = ST_NO_READ;
         if (tally_live(in, i)) {
             tally_counted_read(in, i, R, qual0);
             sh = regular_scan(R, in.P, qual0, [](int32_t, uint64_t, uint32_t, bool) {});
@@ -101,48 +100,22 @@ k_cooc(CoocArgs a) {
                 ++s;
                 more = cooc_is_candidate(S, s, sh.ref_end);
             }
-            unsigned long long pending = __ballot(key != CO_NO_KEY);
-            while (pending) {
-                const int src = __ffsll((long long)pending) - 1;
-                const int32_t lk = __shfl(key, src);
-                const unsigned long long same = __ballot(key == lk);
-                if (lane == src) {
-                    const uint32_t cnt = (uint32_t)__popcll(same);
-                    const int32_t w = cooc_window_cell(win, lk);
-                    if (w >= 0) atomicAdd(&s_cell[w], cnt);
-                    else atomicAdd(&a.cooc[lk], cnt);
-                }
-                pending &= ~same;
-            }
+            int32_t lk = CO_NO_KEY;             // the leader's key, in every lane
+            wave_each_distinct(key != CO_NO_KEY, [&](int src) { lk = __shfl(key, src); return key == lk; }, [&](int src, unsigned long long same) {
+                if (lane != src) return;
+                const uint32_t cnt = (uint32_t)__popcll(same);
+                const int32_t w = cooc_window_cell(win, lk);
+                if (w >= 0) atomicAdd(&s_cell[w], cnt);
+                else atomicAdd(&a.cooc[lk], cnt);
+            });
         }
         __syncthreads();                       // the tile's adds are in the window before a flush; s_lo / s_hi are free again
     }
     cooc_flush(s_cell, win.a0, a);
-    // the block's reads: a sum per wave, one atomic each
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        n_tallied += __shfl_xor(n_tallied, d);
-        n_skipped += __shfl_xor(n_skipped, d);
-    }
-    if (lane == 0) {
-        if (n_tallied) atomicAdd(&a.reads[0], (unsigned long long)n_tallied);
-        if (n_skipped) atomicAdd(&a.reads[1], (unsigned long long)n_skipped);
-    }
+    tally_wave_add2(a.reads, n_tallied, n_skipped);            // the block's reads
 }
-
-static size_t cooc_bytes(const CoocState *s) { return (size_t)s->n_sets * CO_CELLS * 4; }
 
 static CoocState *cooc_state(amp_ctx *c) { return hook_state<CoocState>(c, HOOK_COOC); }
-
-static void cooc_free(void *state) {
-    CoocState *s = hook_state_of<CoocState>(state);
-    if (!s) return;
-    if (s->d_sets) (void)hipFree(s->d_sets);
-    if (s->d_cooc) (void)hipFree(s->d_cooc);
-    if (s->d_reads) (void)hipFree(s->d_reads);
-    s->timer.destroy();
-    delete s;
-}
 
 static int cooc_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
@@ -152,15 +125,7 @@ static int cooc_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out 
     });
 }
 
-static int cooc_reset(amp_ctx *c) {
-    const HookCtx q = ctx_hook(c);
-    CoocState *s = cooc_state(c);
-    HOOKCHK(q, hipMemsetAsync(s->d_cooc, 0, cooc_bytes(s), q.stream));
-    HOOKCHK(q, hipMemsetAsync(s->d_reads, 0, 16, q.stream));
-    return AMP_OK;
-}
-
-HookOps cooc_hook = {"the co-occurrence tallies need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, cooc_enqueue, cooc_reset, cooc_free};
+HookOps cooc_hook = {"the co-occurrence tallies need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, cooc_enqueue, hook_free<CoocState>};
 
 }  // namespace amp
 
@@ -237,57 +202,39 @@ int amp_cooc_enable(amp_ctx *c, int32_t n_sets, const int32_t *set_off, const in
     }
     std::vector<int32_t> packed;
     int32_t n_sites = 0, max_span = 0;
-    const int prc = cooc_pack(q, n_sets, set_off, site_pos, site_len, site_sym, packed, n_sites, max_span);
-    if (prc != AMP_OK) return prc;
+    HOOKTRY(cooc_pack(q, n_sets, set_off, site_pos, site_len, site_sym, packed, n_sites, max_span));
     Guard g(q.device);
     CoocState *s = cooc_state(c);
     if (s && s->packed != packed) {
         // other sets: the tables are laid out again (a kernel of the old ones may still be in flight)
         HOOKCHK(q, hipStreamSynchronize(q.stream));
-        cooc_free(s);
+        hook_free<CoocState>(s);
         s = nullptr; slot.state = nullptr; slot.on = false;
     }
     if (!s) {
-        const int rc = hook_new_state(q, slot, cooc_hook, s, [&](CoocState &f) -> int {
+        HOOKTRY(hook_new_state(q, slot, cooc_hook, s, [&](CoocState &f) -> int {
             f.n_sets = n_sets; f.n_sites = n_sites; f.max_span = max_span;
             f.packed = packed;
-            HOOKCHK(q, hipMalloc((void **)&f.d_sets, packed.size() * 4));
-            HOOKCHK(q, hipMalloc((void **)&f.d_cooc, cooc_bytes(&f)));
-            HOOKCHK(q, hipMalloc((void **)&f.d_reads, 16));
+            const size_t cells = (size_t)n_sets * CO_CELLS;
+            HOOKTRY(hook_alloc(q, f, &f.d_sets, packed.size() * 4));
+            HOOKTRY(hook_alloc(q, f, &f.d_cooc, cells * 4, cells * 4));
+            HOOKTRY(hook_alloc(q, f, &f.d_reads, 16, 16));
+            hook_table(f, f.d_cooc, cells);
+            hook_table(f, f.d_reads, 2);
             HOOKCHK(q, hipMemcpyAsync(f.d_sets, f.packed.data(), packed.size() * 4, hipMemcpyHostToDevice, q.stream));
             HOOKCHK(q, hipStreamSynchronize(q.stream));
             return AMP_OK;
-        });
-        if (rc != AMP_OK) return rc;
+        }));
     }
     slot.on = false;
-    const int rc = cooc_reset(c);
-    if (rc != AMP_OK) return rc;
+    HOOKTRY(hook_zero(q, *s));
     slot.on = true;
     return AMP_OK;
 }
 
-int amp_cooc_get(amp_ctx *c, uint32_t *cooc, uint64_t *reads) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    CoocState *s = cooc_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    if (cooc) HOOKCHK(q, hipMemcpyAsync(cooc, s->d_cooc, cooc_bytes(s), hipMemcpyDeviceToHost, q.stream));
-    if (reads) HOOKCHK(q, hipMemcpyAsync(reads, s->d_reads, 16, hipMemcpyDeviceToHost, q.stream));
-    HOOKCHK(q, hipStreamSynchronize(q.stream));
-    return AMP_OK;
-}
+int amp_cooc_get(amp_ctx *c, uint32_t *cooc, uint64_t *reads) { return hook_get(c, HOOK_COOC, {cooc, reads}); }
 
-int amp_cooc_add(amp_ctx *c, const uint32_t *cooc, const uint64_t *reads) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    CoocState *s = cooc_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    const int rc = hook_add(q, s->d_cooc, cooc, (size_t)s->n_sets * CO_CELLS);
-    return rc != AMP_OK ? rc : hook_add(q, (uint64_t *)s->d_reads, reads, 2);
-}
+int amp_cooc_add(amp_ctx *c, const uint32_t *cooc, const uint64_t *reads) { return hook_add_tables(c, HOOK_COOC, {cooc, reads}); }
 
 int amp_cooc_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_COOC, ms); }
 

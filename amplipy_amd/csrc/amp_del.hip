@@ -15,9 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-
-#include <algorithm>
-#include <vector>
+#include <stdio.h>
 
 #include "amp_del.hpp"
 #include "amp_hook.hpp"
@@ -26,15 +24,10 @@
 
 namespace amp {
 
-struct DelTable {                               // the global table as a kernel is handed it
-    unsigned long long *keys;                   // [capacity], DL_EMPTY: free
-    uint32_t *cnt;                              // [capacity][2]: count, rev
-    unsigned long long *info;                   // [2]: used slots, lost reads
-    uint32_t log2_capacity;
-};
+using DelTable = KeyedTable<unsigned long long, 1>;     // the global table (amp_keyed.hpp): a key is one word, DL_EMPTY: free
 
 struct DelState : HookState {
-    DelTable t = {nullptr, nullptr, nullptr, 0u};      // keys, cnt and info are one allocation
+    DelTable t = {nullptr, nullptr, nullptr, 0u};
 };
 
 struct DelArgs {
@@ -44,15 +37,32 @@ struct DelArgs {
 
 // (key, count, rev) into the global table: 64-bit compare-and-swap on the key, then the adds (agent scope: HIP's default)
 __device__ __forceinline__ void del_global_insert(const DelTable &t, uint64_t key, uint32_t count, uint32_t rev) {
+    bool fresh = false;
     const int64_t s = del_probe(key, del_slot_global(key, t.log2_capacity), (1u << t.log2_capacity) - 1u, del_probes_global(t.log2_capacity), [&](uint32_t slot) {
         const uint64_t prev = atomicCAS(&t.keys[slot], (unsigned long long)DL_EMPTY, (unsigned long long)key);
-        if (prev == DL_EMPTY) atomicAdd(&t.info[0], 1ull);
+        fresh = prev == DL_EMPTY;
         return prev;
     });
-    if (s < 0) { atomicAdd(&t.info[1], (unsigned long long)count); return; }
-    atomicAdd(&t.cnt[2 * (size_t)s], count);
-    if (rev) atomicAdd(&t.cnt[2 * (size_t)s + 1], rev);
+    keyed_tally(t, s, fresh, count, rev);
 }
+
+// What amp_keyed.hpp is told about the table
+struct DelKeys {
+    using Word = unsigned long long;
+    using Entry = amp_del_event;
+    static constexpr int WORDS = 1, LOG2_MIN = DL_LOG2_MIN, LOG2_MAX = DL_LOG2_MAX, LOG2_DEFAULT = DL_LOG2_DEFAULT;
+    static constexpr const char *NOUN = "the deletion events' table";
+    static __host__ __device__ void to_key(const Entry &e, Word *key) { key[0] = del_key(e.start, e.len); }
+    static __host__ __device__ Entry to_entry(const Word *key, uint32_t count, uint32_t rev) { return Entry{del_key_start(key[0]), del_key_len(key[0]), count, rev}; }
+    static __host__ __device__ bool whole(const Word *key) { return key[0] != DL_EMPTY; }
+    static bool less(const Entry &x, const Entry &y) { return x.start != y.start ? x.start < y.start : x.len < y.len; }
+    static bool check(const Entry &e, long long k, char *err, size_t cap) {
+        if (e.start >= 0 && e.len >= 1) return true;
+        snprintf(err, cap, "deletion event %lld: start %d, length %d", k, e.start, e.len);
+        return false;
+    }
+    static __device__ void insert(const DelTable &t, const Word *key, uint32_t count, uint32_t rev) { del_global_insert(t, key[0], count, rev); }
+};
 
 // ... into the block's table, or past it when it has no slot within its probe count
 __device__ __forceinline__ void del_lds_insert(unsigned long long *s_key, uint32_t *s_cnt, uint32_t *s_used, const DelTable &t, uint64_t key, uint32_t count,
@@ -133,14 +143,14 @@ k_del(DelArgs a) {
             const uint64_t e = have ? (uint64_t)s_list[s0 + (uint32_t)lane] : 0ull;
             const uint64_t key = e & ~DL_REV_BIT;
             const unsigned long long revs = __ballot(have && (e & DL_REV_BIT) != 0ull);
-            unsigned long long pending = __ballot(have);
-            while (pending) {
-                const int src = __ffsll((long long)pending) - 1;
-                const uint64_t lk = (uint64_t)__shfl((unsigned long long)key, src);
-                const unsigned long long same = __ballot(have && key == lk);
+            uint64_t lk = 0ull;                 // the leader's key, in every lane
+            const auto same_key = [&](int src) {
+                lk = (uint64_t)__shfl((unsigned long long)key, src);
+                return have && key == lk;
+            };
+            wave_each_distinct(have, same_key, [&](int src, unsigned long long same) {
                 if (lane == src) del_lds_insert(s_key, s_cnt, &s_used, a.t, lk, (uint32_t)__popcll(same), (uint32_t)__popcll(same & revs));
-                pending &= ~same;
-            }
+            });
         }
         __syncthreads();
         // ---- the tile boundary (s_used changes in phase B and below only: every lane reads the same value here)
@@ -155,55 +165,7 @@ k_del(DelArgs a) {
     del_flush(s_key, s_cnt, a.t);
 }
 
-// host entries through the same insert path
-__global__ void k_del_add(DelTable t, const amp_del_event *ev, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const amp_del_event e = ev[i];
-    del_global_insert(t, del_key(e.start, e.len), e.count, e.rev);
-}
-
-// the used slots, in no order
-__global__ void k_del_compact(DelTable t, amp_del_event *out, unsigned long long *n_out, uint64_t cap_out) {
-    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= (1ull << t.log2_capacity)) return;
-    const uint64_t key = t.keys[s];
-    if (key == DL_EMPTY) return;
-    const uint64_t at = atomicAdd(n_out, 1ull);
-    if (at < cap_out) out[at] = amp_del_event{del_key_start(key), del_key_len(key), t.cnt[2 * s], t.cnt[2 * s + 1]};
-}
-
-static size_t del_bytes(uint32_t log2_capacity) { return ((size_t)16 << log2_capacity) + 64; }      // keys, counts, info (and the compaction's counter)
-
 static DelState *del_state(amp_ctx *c) { return hook_state<DelState>(c, HOOK_DEL); }
-
-static void del_free(void *state) {
-    DelState *s = hook_state_of<DelState>(state);
-    if (!s) return;
-    if (s->t.keys) (void)hipFree(s->t.keys);
-    s->timer.destroy();
-    delete s;
-}
-
-static int del_layout(const HookCtx &q, DelTable &t, uint32_t log2_capacity) {
-    if (t.keys) (void)hipFree(t.keys);
-    t = DelTable{nullptr, nullptr, nullptr, 0u};
-    void *p = nullptr;
-    HOOKCHK(q, hipMalloc(&p, del_bytes(log2_capacity)));
-    const size_t cap = (size_t)1 << log2_capacity;
-    t.keys = (unsigned long long *)p;
-    t.cnt = (uint32_t *)(t.keys + cap);
-    t.info = t.keys + 2 * cap;
-    t.log2_capacity = log2_capacity;
-    return AMP_OK;
-}
-
-static int del_zero(const HookCtx &q, const DelTable &t) {
-    const size_t cap = (size_t)1 << t.log2_capacity;
-    HOOKCHK(q, hipMemsetAsync(t.keys, 0xFF, cap * 8, q.stream));
-    HOOKCHK(q, hipMemsetAsync(t.cnt, 0, cap * 8 + 64, q.stream));
-    return AMP_OK;
-}
 
 static int del_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
@@ -213,9 +175,7 @@ static int del_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *
     });
 }
 
-static int del_reset(amp_ctx *c) { return del_state(c)->t.keys ? del_zero(ctx_hook(c), del_state(c)->t) : AMP_OK; }
-
-HookOps del_hook = {"the deletion events need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, del_enqueue, del_reset, del_free};
+HookOps del_hook = {"the deletion events need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, del_enqueue, hook_free<DelState>};
 
 }  // namespace amp
 
@@ -228,86 +188,35 @@ int amp_del_enable(amp_ctx *c, int on, int log2_capacity) {
     const HookCtx q = ctx_hook(c);
     HookSlot &slot = hook_slot(c, HOOK_DEL);
     if (!on) { slot.on = false; return AMP_OK; }
-    if (log2_capacity == 0) log2_capacity = DL_LOG2_DEFAULT;
-    if (log2_capacity < DL_LOG2_MIN || log2_capacity > DL_LOG2_MAX) {
-        snprintf(q.err, q.err_cap, "the deletion events' table takes 2^%d to 2^%d slots (0: the default, 2^%d)", DL_LOG2_MIN, DL_LOG2_MAX, DL_LOG2_DEFAULT);
-        return AMP_EINVAL;
-    }
+    HOOKTRY(keyed_capacity<DelKeys>(q, log2_capacity));
     Guard g(q.device);
     DelState *s = del_state(c);
     if (!s) {
-        const int rc = hook_new_state(q, slot, del_hook, s, [&](DelState &f) -> int { return del_layout(q, f.t, (uint32_t)log2_capacity); });
-        if (rc != AMP_OK) return rc;
+        HOOKTRY(hook_new_state(q, slot, del_hook, s, [&](DelState &f) -> int { return keyed_layout(q, f, f.t, (uint32_t)log2_capacity); }));
     } else if (s->t.log2_capacity != (uint32_t)log2_capacity) {
+        // another capacity: the table is laid out again (a kernel on the old one may still be in flight)
         slot.on = false;
         HOOKCHK(q, hipStreamSynchronize(q.stream));
-        const int rc = del_layout(q, s->t, (uint32_t)log2_capacity);
-        if (rc != AMP_OK) return rc;
+        hook_release(*s);
+        HOOKTRY(keyed_layout(q, *s, s->t, (uint32_t)log2_capacity));
     }
-    const int rc = del_zero(q, s->t);
-    if (rc != AMP_OK) return rc;
+    HOOKTRY(hook_zero(q, *s));
     slot.on = true;
     return AMP_OK;
 }
 
 int amp_del_get(amp_ctx *c, amp_del_event *entries, int64_t cap, int64_t *n, amp_del_info *info) {
     if (!c || cap < 0) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
     DelState *s = del_state(c);
     if (!s || !s->t.keys) return AMP_ESTATE;
-    Guard g(q.device);
-    unsigned long long h[2] = {0ull, 0ull};
-    HOOKCHK(q, hipMemcpyAsync(h, s->t.info, sizeof(h), hipMemcpyDeviceToHost, q.stream));
-    HOOKCHK(q, hipStreamSynchronize(q.stream));
-    if (info) { info->used = h[0]; info->capacity = 1ull << s->t.log2_capacity; info->lost = h[1]; }
-    if (n) *n = (int64_t)h[0];
-    if ((uint64_t)cap < h[0] || (h[0] && !entries)) {
-        snprintf(q.err, q.err_cap, "the deletion events' table holds %llu entries, the array given %lld", h[0], (long long)cap);
-        return AMP_EINVAL;
-    }
-    if (!h[0]) return AMP_OK;
-    amp_del_event *d_out = nullptr;
-    HOOKCHK(q, hipMalloc((void **)&d_out, (size_t)h[0] * sizeof(amp_del_event)));
-    unsigned long long *d_n = s->t.info + 2;                       // (inside the allocation's last 64 bytes)
-    const int rc = [&]() -> int {
-        HOOKCHK(q, hipMemsetAsync(d_n, 0, 8, q.stream));
-        const uint64_t slots = 1ull << s->t.log2_capacity;
-        k_del_compact<<<(unsigned)((slots + 255) / 256), 256, 0, q.stream>>>(s->t, d_out, d_n, h[0]);
-        HOOKCHK(q, hipGetLastError());
-        HOOKCHK(q, hipMemcpyAsync(entries, d_out, (size_t)h[0] * sizeof(amp_del_event), hipMemcpyDeviceToHost, q.stream));
-        HOOKCHK(q, hipStreamSynchronize(q.stream));
-        return AMP_OK;
-    }();
-    (void)hipFree(d_out);
-    if (rc != AMP_OK) return rc;
-    std::sort(entries, entries + h[0], [](const amp_del_event &x, const amp_del_event &y) { return x.start != y.start ? x.start < y.start : x.len < y.len; });
-    return AMP_OK;
+    return keyed_get<DelKeys>(ctx_hook(c), s->t, entries, cap, n, info);
 }
 
 int amp_del_add(amp_ctx *c, const amp_del_event *entries, int64_t n) {
     if (!c || n < 0 || (n && !entries)) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
     DelState *s = del_state(c);
     if (!s || !s->t.keys) return AMP_ESTATE;
-    if (!n) return AMP_OK;
-    for (int64_t k = 0; k < n; ++k) {
-        if (entries[k].start < 0 || entries[k].len < 1) {
-            snprintf(q.err, q.err_cap, "deletion event %lld: start %d, length %d", (long long)k, entries[k].start, entries[k].len);
-            return AMP_EINVAL;
-        }
-    }
-    Guard g(q.device);
-    amp_del_event *d_in = nullptr;
-    HOOKCHK(q, hipMalloc((void **)&d_in, (size_t)n * sizeof(amp_del_event)));
-    const int rc = [&]() -> int {
-        HOOKCHK(q, hipMemcpyAsync(d_in, entries, (size_t)n * sizeof(amp_del_event), hipMemcpyHostToDevice, q.stream));
-        k_del_add<<<(unsigned)((n + 255) / 256), 256, 0, q.stream>>>(s->t, d_in, n);
-        HOOKCHK(q, hipGetLastError());
-        HOOKCHK(q, hipStreamSynchronize(q.stream));
-        return AMP_OK;
-    }();
-    (void)hipFree(d_in);
-    return rc;
+    return keyed_add(ctx_hook(c), s->t, DelKeys{}, entries, n);
 }
 
 int amp_del_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_DEL, ms); }

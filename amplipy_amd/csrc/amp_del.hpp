@@ -15,6 +15,7 @@
 
 #include <stdint.h>
 
+#include "amp_keyed.hpp"
 #include "amp_strand.hpp"
 
 namespace amp {
@@ -25,7 +26,7 @@ constexpr int DL_LDS_LOG2 = 10;
 constexpr int DL_LDS_SLOTS = 1 << DL_LDS_LOG2;           // slots of a block's table: a u64 key and two u32 counts each, 16 KB
 constexpr int DL_LDS_PROBES = 16;            // slots an insert into the block's table tries; then it goes straight to the global table
 constexpr int DL_LDS_FLUSH_AT = DL_LDS_SLOTS / 4 * 3;    // more used slots than this at a tile boundary: the block's table goes to the global one
-constexpr int DL_GLOBAL_PROBES = 4096;       // slots an insert into the global table tries (all of a smaller table); then the event is lost
+constexpr int DL_GLOBAL_PROBES = 4096;       // slots an insert into the global table tries (keyed_probes); then the event is lost
 constexpr int DL_TILES_PER_BLOCK = 2;        // a block takes at least this many tiles before another block is added ...
 constexpr int DL_BLOCKS_PER_CU = 6;          // ... and the grid stops growing here: six blocks' LDS (24.6 KB each) fit a CU
 constexpr int DL_MAX_TILES_PER_FLUSH = 1 << 23;          // a key takes at most one add per read: 2^23 tiles of 256 stay below 2^32
@@ -33,6 +34,7 @@ constexpr int DL_LOG2_DEFAULT = 20, DL_LOG2_MIN = 4, DL_LOG2_MAX = 28;      // t
 constexpr uint64_t DL_EMPTY = ~0ull;         // no key: a start is below 2^31
 constexpr uint64_t DL_REV_BIT = 1ull << 63;  // a list entry: the key, and this bit for a reverse read
 static_assert(DL_LDS_FLUSH_AT * 4 == DL_LDS_SLOTS * 3, "three quarters");
+static_assert(DL_GLOBAL_PROBES == KEYED_PROBES, "one probe rule (amp_keyed.hpp)");
 static_assert((uint64_t)DL_MAX_TILES_PER_FLUSH * DL_BLOCK < (1ull << 32), "a count of the block's table cannot overflow before its flush");
 
 // The key of an event: start in the high word, len in the low one -- keys order as (start, len) does.
@@ -50,10 +52,8 @@ AMP_ST_HD uint64_t del_hash(uint64_t key) {
     return x;
 }
 AMP_ST_HD uint32_t del_slot_lds(uint64_t key) { return (uint32_t)del_hash(key) & (uint32_t)(DL_LDS_SLOTS - 1); }
-AMP_ST_HD uint32_t del_slot_global(uint64_t key, uint32_t log2_capacity) { return (uint32_t)(del_hash(key) >> 32) & ((1u << log2_capacity) - 1u); }
-AMP_ST_HD uint32_t del_probes_global(uint32_t log2_capacity) {
-    return log2_capacity < 12u ? (1u << log2_capacity) : (uint32_t)DL_GLOBAL_PROBES;
-}
+AMP_ST_HD uint32_t del_slot_global(uint64_t key, uint32_t log2_capacity) { return keyed_slot(del_hash(key), log2_capacity); }
+AMP_ST_HD uint32_t del_probes_global(uint32_t log2_capacity) { return keyed_probes(log2_capacity); }
 
 // The probe rule of both tables: slots first, first + 1, ... (wrapping at the table's end), at most `probes` of them;
 // claim(slot) puts the key into an empty slot and says what the slot held before (DL_EMPTY: the key is new there).  -> the

@@ -46,15 +46,12 @@ struct ErrprofArgs {
 // cells[key] += the number of lanes with `have` and this key, one add per distinct key of the wave: the leaders' counts by a
 // ballot loop, then every leader's add in one instruction.  Whole waves call it.
 __device__ __forceinline__ void ep_combine_add(uint32_t *cells, bool have, int key, int lane) {
-    unsigned long long pending = __ballot(have);
     uint32_t mine = 0u;
-    while (pending) {
-        const int src = __ffsll((long long)pending) - 1;
+    const auto same_key = [&](int src) {
         const int lk = __shfl(key, src);
-        const unsigned long long same = __ballot(have && key == lk);
-        if (lane == src) mine = (uint32_t)__popcll(same);
-        pending &= ~same;
-    }
+        return have && key == lk;
+    };
+    wave_each_distinct(have, same_key, [&](int src, unsigned long long same) { if (lane == src) mine = (uint32_t)__popcll(same); });
     if (mine) atomicAdd(&cells[key], mine);
 }
 
@@ -141,28 +138,10 @@ k_errprof(ErrprofArgs a) {
         __syncthreads();
     }
     flush();
-    // the block's reads: a sum per wave, one atomic each
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        n_profiled += __shfl_xor(n_profiled, d);
-        n_skipped += __shfl_xor(n_skipped, d);
-    }
-    if (lane == 0) {
-        if (n_profiled) atomicAdd(&a.cells[EP_CELLS], (unsigned long long)n_profiled);
-        if (n_skipped) atomicAdd(&a.cells[EP_CELLS + 1], (unsigned long long)n_skipped);
-    }
+    tally_wave_add2(a.cells + EP_CELLS, n_profiled, n_skipped);        // the block's reads
 }
 
 static ErrprofState *errprof_state(amp_ctx *c) { return hook_state<ErrprofState>(c, HOOK_ERRPROF); }
-
-static void errprof_free(void *state) {
-    ErrprofState *s = hook_state_of<ErrprofState>(state);
-    if (!s) return;
-    if (s->d_cells) (void)hipFree(s->d_cells);
-    if (s->d_code) (void)hipFree(s->d_code);
-    s->timer.destroy();
-    delete s;
-}
 
 static int errprof_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
@@ -174,13 +153,7 @@ static int errprof_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_o
     });
 }
 
-static int errprof_reset(amp_ctx *c) {
-    const HookCtx q = ctx_hook(c);
-    HOOKCHK(q, hipMemsetAsync(errprof_state(c)->d_cells, 0, (size_t)(EP_CELLS + 2) * 8, q.stream));
-    return AMP_OK;
-}
-
-HookOps errprof_hook = {"the error profile needs", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, errprof_enqueue, errprof_reset, errprof_free};
+HookOps errprof_hook = {"the error profile needs", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, errprof_enqueue, hook_free<ErrprofState>};
 
 }  // namespace amp
 
@@ -202,48 +175,29 @@ int amp_errprof_enable(amp_ctx *c, int on, const uint8_t *ref_ascii, const uint3
     Guard g(q.device);
     ErrprofState *s = errprof_state(c);
     if (!s) {
-        const int rc = hook_new_state(q, slot, errprof_hook, s, [&](ErrprofState &f) -> int {
-            HOOKCHK(q, hipMalloc((void **)&f.d_cells, (size_t)(EP_CELLS + 2) * 8));
-            HOOKCHK(q, hipMalloc((void **)&f.d_code, code.size()));
+        HOOKTRY(hook_new_state(q, slot, errprof_hook, s, [&](ErrprofState &f) -> int {
+            HOOKTRY(hook_alloc(q, f, &f.d_cells, (size_t)(EP_CELLS + 2) * 8, (size_t)(EP_CELLS + 2) * 8));
+            HOOKTRY(hook_alloc(q, f, &f.d_code, code.size()));
+            hook_table(f, f.d_cells, EP_CYC_CELLS);
+            hook_table(f, f.d_cells + EP_QUAL_AT, EP_QUAL_CELLS);
+            hook_table(f, f.d_cells + EP_SUB_AT, EP_SUB_CELLS);
+            hook_table(f, f.d_cells + EP_CELLS, 2);
             return AMP_OK;
-        });
-        if (rc != AMP_OK) return rc;
+        }));
     }
     slot.on = false;
     HOOKCHK(q, hipStreamSynchronize(q.stream));            // (a kernel on the codes of the call before may still be in flight)
     HOOKCHK(q, hipMemcpyAsync(s->d_code, code.data(), code.size(), hipMemcpyHostToDevice, q.stream));
     HOOKCHK(q, hipStreamSynchronize(q.stream));
-    const int rc = errprof_reset(c);
-    if (rc != AMP_OK) return rc;
+    HOOKTRY(hook_zero(q, *s));
     slot.on = true;
     return AMP_OK;
 }
 
-int amp_errprof_get(amp_ctx *c, uint64_t *cyc, uint64_t *qualt, uint64_t *sub, uint64_t *reads) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    ErrprofState *s = errprof_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    if (cyc) HOOKCHK(q, hipMemcpyAsync(cyc, s->d_cells, (size_t)EP_CYC_CELLS * 8, hipMemcpyDeviceToHost, q.stream));
-    if (qualt) HOOKCHK(q, hipMemcpyAsync(qualt, s->d_cells + EP_QUAL_AT, (size_t)EP_QUAL_CELLS * 8, hipMemcpyDeviceToHost, q.stream));
-    if (sub) HOOKCHK(q, hipMemcpyAsync(sub, s->d_cells + EP_SUB_AT, (size_t)EP_SUB_CELLS * 8, hipMemcpyDeviceToHost, q.stream));
-    if (reads) HOOKCHK(q, hipMemcpyAsync(reads, s->d_cells + EP_CELLS, 16, hipMemcpyDeviceToHost, q.stream));
-    HOOKCHK(q, hipStreamSynchronize(q.stream));
-    return AMP_OK;
-}
+int amp_errprof_get(amp_ctx *c, uint64_t *cyc, uint64_t *qualt, uint64_t *sub, uint64_t *reads) { return hook_get(c, HOOK_ERRPROF, {cyc, qualt, sub, reads}); }
 
 int amp_errprof_add(amp_ctx *c, const uint64_t *cyc, const uint64_t *qualt, const uint64_t *sub, const uint64_t *reads) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    ErrprofState *s = errprof_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    uint64_t *d = (uint64_t *)s->d_cells;
-    int rc = hook_add(q, d, cyc, (size_t)EP_CYC_CELLS);
-    if (rc == AMP_OK) rc = hook_add(q, d + EP_QUAL_AT, qualt, (size_t)EP_QUAL_CELLS);
-    if (rc == AMP_OK) rc = hook_add(q, d + EP_SUB_AT, sub, (size_t)EP_SUB_CELLS);
-    return rc != AMP_OK ? rc : hook_add(q, d + EP_CELLS, reads, 2);
+    return hook_add_tables(c, HOOK_ERRPROF, {cyc, qualt, sub, reads});
 }
 
 int amp_errprof_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_ERRPROF, ms); }

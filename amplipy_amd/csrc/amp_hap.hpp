@@ -35,6 +35,7 @@
 
 #include <stdint.h>
 
+#include "amp_keyed.hpp"
 #include "amp_strand.hpp"
 
 namespace amp {
@@ -48,7 +49,7 @@ constexpr int32_t HP_MAX_REGIONS = 1 << 16;
 constexpr int HP_TALLY_COLS = 6;
 constexpr int HP_COVER = 0, HP_REF = 1, HP_REF_REV = 2, HP_LOWQ = 3, HP_OVERFLOW = 4, HP_EDGE = 5;       // the columns of tally
 constexpr int HP_KIND_N = 4, HP_KIND_DEL = 5;
-constexpr int HP_GLOBAL_PROBES = 4096;       // slots an insert tries (all of a smaller table); then the reads are lost (DL_GLOBAL_PROBES' rule)
+constexpr int HP_GLOBAL_PROBES = 4096;       // slots an insert tries (keyed_probes); then the reads are lost
 constexpr int HP_LOG2_DEFAULT = 20, HP_LOG2_MIN = 4, HP_LOG2_MAX = 28;      // the table's slots (64 bytes each)
 constexpr int HP_TILES_PER_BLOCK = 2;        // a block takes at least this many tiles before another block is added ...
 constexpr int HP_BLOCKS_PER_CU = 4;          // ... and the grid stops growing here (15 KB of LDS a block)
@@ -56,6 +57,7 @@ constexpr uint32_t HP_EMPTY = 0xFFFFFFFFu;   // no key word: a head has n_diffs 
 // what a trial comes to
 constexpr int HP_OUT_NONE = -1, HP_OUT_REF = 0, HP_OUT_LOWQ = 1, HP_OUT_OVERFLOW = 2, HP_OUT_EDGE = 3, HP_OUT_KEY = 4;
 static_assert(HP_MAX_DIFFS == AMP_HAP_MAX_DIFFS && HP_MAX_REGION == AMP_HAP_MAX_REGION && HP_TALLY_COLS == AMP_HAP_TALLY_COLS, "amplihip.h");
+static_assert(HP_GLOBAL_PROBES == KEYED_PROBES, "one probe rule (amp_keyed.hpp)");
 static_assert(HP_KEY_WORDS == HP_MAX_DIFFS + 1 && sizeof(amp_hap_entry) == 64 && (HP_KEY_STRIDE & 1), "a key is the first 14 words of an entry");
 static_assert(HP_MAX_REGION <= (1 << 12) && HP_MAX_REGION < (1 << 13), "offset and deletion length fit their bits");
 
@@ -216,8 +218,8 @@ AMP_ST_HD uint64_t hap_hash(const uint32_t *key) {
     h ^= h >> 33;
     return h;
 }
-AMP_ST_HD uint32_t hap_slot_global(uint64_t hash, uint32_t log2_capacity) { return (uint32_t)(hash >> 32) & ((1u << log2_capacity) - 1u); }
-AMP_ST_HD uint32_t hap_probes_global(uint32_t log2_capacity) { return log2_capacity < 12u ? (1u << log2_capacity) : (uint32_t)HP_GLOBAL_PROBES; }
+AMP_ST_HD uint32_t hap_slot_global(uint64_t hash, uint32_t log2_capacity) { return keyed_slot(hash, log2_capacity); }
+AMP_ST_HD uint32_t hap_probes_global(uint32_t log2_capacity) { return keyed_probes(log2_capacity); }
 AMP_ST_HD bool hap_key_equal(const uint32_t *x, const uint32_t *y) {
     bool same = true;
     for (int w = 0; w < HP_KEY_WORDS; ++w) same = same && x[w] == y[w];

@@ -2,7 +2,8 @@
 // report (amp_qc.hip), the strand tallies (amp_strand.hip), the per-amplicon counts (amp_amplicon.hip), the codon tallies
 // (amp_codon.hip), the deletion events (amp_del.hip), the co-occurrence tallies (amp_cooc.hip), the error profile (amp_errprof.hip), the read haplotypes (amp_hap.hip), the read-position tallies (amp_readpos.hip).  What a hook needs to know of a ctx, and what the hooks have in common -- the check macro, the device
 // guard, the timer round a launch, the grid rule, the merge of host tables, the check of a trimming pass's results, the common
-// part of a state and its construction, the frame of an enqueue, last_ms -- each once.  (What the three tally kernels share
+// part of a state and its construction, the record of what a state owns on the device with free, reset, get and add written
+// from it, the frame of an enqueue, last_ms -- each once.  (What the three tally kernels share
 // on the device is amp_tally.hpp.)  amp_ctx (amp_ctx.hpp) keeps one slot (switch, state) per hook and amplihip.hip walks the
 // table of HookOps; a unit keeps its state, its kernels and what it enables.
 #pragma once
@@ -14,6 +15,7 @@
 #include <stdio.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -29,6 +31,8 @@
         }                                                                                                                    \
     } while (0)
 #define HOOKCHK(q, call) AMP_HIPCHK((q).err, (q).err_cap, #call, call)       // q: a HookCtx
+// a step that gives an AMP_* code: anything but AMP_OK out of the enclosing function
+#define HOOKTRY(call) do { const int rc__ = (call); if (rc__ != AMP_OK) return rc__; } while (0)
 
 namespace amp {
 
@@ -68,8 +72,7 @@ struct HookOps {
     const char *name;           // as a refusal begins: "the QC report needs"
     uint32_t needs;             // OUT_* bits
     int (*enqueue)(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *dev_out);       // the kernel on the ctx stream; the state exists
-    int (*reset)(amp_ctx *c);   // amp_reset: the tables start over; the state exists
-    void (*free_state)(void *state);        // null: nothing to do
+    void (*free_state)(void *state);        // hook_free of the unit's state; a null state is nothing to do
 };
 // One per unit; amplihip.hip keeps them in enum order.  (Not const objects, though nothing writes them: hipcc emits a const
 // object with a constant initialiser into the device image as well, host function pointers and all.)
@@ -147,12 +150,99 @@ int hook_add(const HookCtx &q, T *dev, const T *host, size_t count) {
     return AMP_OK;
 }
 
-// What every hook's state begins with; a slot's `state` points at this part.
+// What every hook's state begins with; a slot's `state` points at this part.  Next to the timer it records what the state
+// owns on the device: its allocations (hook_alloc), each with what a reset does to it -- the first `ones` bytes to 0xFF (the
+// free keys of a keyed table, amp_keyed.hpp), the `zeros` bytes behind them to 0 -- and its result tables in the order of the
+// ABI's get / add arguments (hook_table).  A table may be a sub-range of an allocation.
 struct HookState {
+    struct Owned { void *p; size_t ones, zeros; };
+    struct Table { void *p; size_t count, elem; };       // elem: 4 or 8 bytes
     HookTimer timer;
+    Owned owned[8] = {};
+    Table table[4] = {};
+    int n_owned = 0, n_table = 0;
 };
 template <class S> S *hook_state_of(void *state) { return static_cast<S *>(static_cast<HookState *>(state)); }
 template <class S> S *hook_state(amp_ctx *c, int which) { return hook_state_of<S>(hook_slot(c, which).state); }
+
+// `bytes` of device memory that the state owns from here on, into *ptr
+template <class P>
+int hook_alloc(const HookCtx &q, HookState &s, P **ptr, size_t bytes, size_t zeros = 0, size_t ones = 0) {
+    if (s.n_owned == (int)(sizeof(s.owned) / sizeof(s.owned[0]))) return AMP_ESTATE;
+    void *p = nullptr;
+    HOOKCHK(q, hipMalloc(&p, bytes));
+    s.owned[s.n_owned++] = HookState::Owned{p, ones, zeros};
+    *ptr = (P *)p;
+    return AMP_OK;
+}
+// The next result table: `count` elements at p
+template <class T>
+void hook_table(HookState &s, T *p, size_t count) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "hook_add adds u32 or u64");
+    s.table[s.n_table++] = HookState::Table{p, count, sizeof(T)};
+}
+// What the state owns goes back; the record is empty afterwards.  (No kernel on it may be in flight.)
+inline void hook_release(HookState &s) {
+    for (int k = 0; k < s.n_owned; ++k) (void)hipFree(s.owned[k].p);
+    s.n_owned = s.n_table = 0;
+}
+// HookOps::free_state of a unit whose state is S (its host-only members go with the delete)
+template <class S>
+void hook_free(void *state) {
+    S *s = hook_state_of<S>(state);
+    if (!s) return;
+    hook_release(*s);
+    s->timer.destroy();
+    delete s;
+}
+// The tables start over (amp_reset, and the end of every enable): a memset per allocation that has something to clear, two
+// for a keyed table
+inline int hook_zero(const HookCtx &q, const HookState &s) {
+    for (int k = 0; k < s.n_owned; ++k) {
+        const HookState::Owned &o = s.owned[k];
+        if (o.ones) HOOKCHK(q, hipMemsetAsync(o.p, 0xFF, o.ones, q.stream));
+        if (o.zeros) HOOKCHK(q, hipMemsetAsync((char *)o.p + o.ones, 0, o.zeros, q.stream));
+    }
+    return AMP_OK;
+}
+
+// The state's tables to the host arrays given in the record's order, a null one left out; enqueued, not waited for
+inline int hook_tables_get(const HookCtx &q, const HookState &s, std::initializer_list<void *> host) {
+    int k = 0;
+    for (void *h : host) {
+        const HookState::Table &t = s.table[k++];
+        if (h && t.count) HOOKCHK(q, hipMemcpyAsync(h, t.p, t.count * t.elem, hipMemcpyDeviceToHost, q.stream));
+    }
+    return AMP_OK;
+}
+// ... and the host arrays added onto them (hook_add)
+inline int hook_tables_add(const HookCtx &q, const HookState &s, std::initializer_list<const void *> host) {
+    int k = 0;
+    for (const void *h : host) {
+        const HookState::Table &t = s.table[k++];
+        HOOKTRY(t.elem == 4 ? hook_add(q, (uint32_t *)t.p, (const uint32_t *)h, t.count) : hook_add(q, (uint64_t *)t.p, (const uint64_t *)h, t.count));
+    }
+    return AMP_OK;
+}
+// amp_*_get and amp_*_add of a hook whose results are its tables: AMP_ESTATE before the first enable
+inline int hook_get(amp_ctx *c, int which, std::initializer_list<void *> host) {
+    if (!c) return AMP_EINVAL;
+    const HookCtx q = ctx_hook(c);
+    const HookState *s = (const HookState *)hook_slot(c, which).state;
+    if (!s) return AMP_ESTATE;
+    Guard g(q.device);
+    HOOKTRY(hook_tables_get(q, *s, host));
+    HOOKCHK(q, hipStreamSynchronize(q.stream));
+    return AMP_OK;
+}
+inline int hook_add_tables(amp_ctx *c, int which, std::initializer_list<const void *> host) {
+    if (!c) return AMP_EINVAL;
+    const HookCtx q = ctx_hook(c);
+    const HookState *s = (const HookState *)hook_slot(c, which).state;
+    if (!s) return AMP_ESTATE;
+    Guard g(q.device);
+    return hook_tables_add(q, *s, host);
+}
 
 // A new state for the slot: fill(*s) allocates what the unit keeps (AMP_OK, or the code of what failed), then the timer;
 // the state is handed to the slot, or freed again when a step failed (s is null then).

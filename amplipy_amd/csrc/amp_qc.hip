@@ -176,15 +176,6 @@ k_qc_regions(const uint32_t *__restrict__ depth, int32_t n_regions, const int32_
 
 static QcState *qc_state(amp_ctx *c) { return hook_state<QcState>(c, HOOK_QC); }
 
-static void qc_free(void *state) {
-    QcState *s = hook_state_of<QcState>(state);
-    if (!s) return;
-    void *bufs[] = {s->d_left, s->d_right, s->d_tally, s->d_rstart, s->d_rend, s->d_regions, s->d_depth};
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    s->timer.destroy();
-    delete s;
-}
-
 static int qc_enqueue_reads(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
     QcState *s = qc_state(c);
@@ -201,14 +192,7 @@ static int qc_enqueue_reads(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_
     });
 }
 
-static int qc_reset(amp_ctx *c) {
-    const HookCtx q = ctx_hook(c);
-    QcState *s = qc_state(c);
-    HOOKCHK(q, hipMemsetAsync(s->d_tally, 0, s->tally_words() * sizeof(unsigned long long), q.stream));
-    return AMP_OK;
-}
-
-HookOps qc_hook = {"the QC report needs", OUT_NEW_POS | OUT_REF_LEN | OUT_TRIM_FLAGS | OUT_STATUS, qc_enqueue_reads, qc_reset, qc_free};
+HookOps qc_hook = {"the QC report needs", OUT_NEW_POS | OUT_REF_LEN | OUT_TRIM_FLAGS | OUT_STATUS, qc_enqueue_reads, hook_free<QcState>};
 
 }  // namespace amp
 
@@ -250,7 +234,7 @@ int amp_qc_enable(amp_ctx *c, const amp_qc_params *p) {
     if (q.do_trim && !q.have_primers) return AMP_ESTATE;
     Guard g(q.device);
     HOOKCHK(q, hipStreamSynchronize(q.stream));      // (a report that is replaced may still have a kernel in flight)
-    qc_free(slot.state);
+    hook_free<QcState>(slot.state);
     slot.state = nullptr; slot.on = false;
     QcState *made = nullptr;
     const int made_rc = hook_new_state(q, slot, qc_hook, made, [&](QcState &fresh) -> int {
@@ -265,14 +249,14 @@ int amp_qc_enable(amp_ctx *c, const amp_qc_params *p) {
             rs[r] = p->region_start[r]; re[r] = p->region_end[r];
             qc_region_clamp(q.ref_len, rs[r], re[r]);
         }
-        HOOKCHK(q, hipMalloc((void **)&s->d_left, G * 4));
-        HOOKCHK(q, hipMalloc((void **)&s->d_right, G * 4));
-        HOOKCHK(q, hipMalloc((void **)&s->d_depth, G * 4));
-        HOOKCHK(q, hipMalloc((void **)&s->d_tally, s->tally_words() * sizeof(unsigned long long)));
+        HOOKTRY(hook_alloc(q, fresh, &s->d_left, G * 4));
+        HOOKTRY(hook_alloc(q, fresh, &s->d_right, G * 4));
+        HOOKTRY(hook_alloc(q, fresh, &s->d_depth, G * 4));
+        HOOKTRY(hook_alloc(q, fresh, &s->d_tally, s->tally_words() * sizeof(unsigned long long), s->tally_words() * sizeof(unsigned long long)));
         if (R) {
-            HOOKCHK(q, hipMalloc((void **)&s->d_rstart, R * 4));
-            HOOKCHK(q, hipMalloc((void **)&s->d_rend, R * 4));
-            HOOKCHK(q, hipMalloc((void **)&s->d_regions, R * sizeof(amp_qc_region)));
+            HOOKTRY(hook_alloc(q, fresh, &s->d_rstart, R * 4));
+            HOOKTRY(hook_alloc(q, fresh, &s->d_rend, R * 4));
+            HOOKTRY(hook_alloc(q, fresh, &s->d_regions, R * sizeof(amp_qc_region)));
             HOOKCHK(q, hipMemcpyAsync(s->d_rstart, rs.data(), R * 4, hipMemcpyHostToDevice, q.stream));
             HOOKCHK(q, hipMemcpyAsync(s->d_rend, re.data(), R * 4, hipMemcpyHostToDevice, q.stream));
         }

@@ -33,17 +33,7 @@ struct ReadposArgs {
 __global__ void __launch_bounds__(RP_BLOCK)
 k_readpos(ReadposArgs a) { tally_poswin<ReadposTally>(a.in, a.out); }
 
-static size_t readpos_bytes(int32_t ref_len) { return (size_t)ref_len * RP_CELLS * sizeof(uint32_t); }
-
 static ReadposState *readpos_state(amp_ctx *c) { return hook_state<ReadposState>(c, HOOK_READPOS); }
-
-static void readpos_free(void *state) {
-    ReadposState *s = hook_state_of<ReadposState>(state);
-    if (!s) return;
-    if (s->d_hist) (void)hipFree(s->d_hist);
-    s->timer.destroy();
-    delete s;
-}
 
 static int readpos_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
@@ -53,13 +43,7 @@ static int readpos_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_o
     });
 }
 
-static int readpos_reset(amp_ctx *c) {
-    const HookCtx q = ctx_hook(c);
-    HOOKCHK(q, hipMemsetAsync(readpos_state(c)->d_hist, 0, readpos_bytes(q.ref_len), q.stream));
-    return AMP_OK;
-}
-
-HookOps readpos_hook = {"the read-position tallies need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, readpos_enqueue, readpos_reset, readpos_free};
+HookOps readpos_hook = {"the read-position tallies need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, readpos_enqueue, hook_free<ReadposState>};
 
 }  // namespace amp
 
@@ -75,36 +59,21 @@ int amp_readpos_enable(amp_ctx *c, int on) {
     Guard g(q.device);
     ReadposState *s = readpos_state(c);
     if (!s) {
-        const int rc = hook_new_state(q, slot, readpos_hook, s, [&](ReadposState &f) -> int {
-            HOOKCHK(q, hipMalloc((void **)&f.d_hist, std::max<size_t>(readpos_bytes(q.ref_len), 64)));
+        HOOKTRY(hook_new_state(q, slot, readpos_hook, s, [&](ReadposState &f) -> int {
+            const size_t cells = (size_t)q.ref_len * RP_CELLS;
+            HOOKTRY(hook_alloc(q, f, &f.d_hist, std::max<size_t>(cells * 4, 64), cells * 4));
+            hook_table(f, f.d_hist, cells);
             return AMP_OK;
-        });
-        if (rc != AMP_OK) return rc;
+        }));
     }
-    HOOKCHK(q, hipMemsetAsync(s->d_hist, 0, readpos_bytes(q.ref_len), q.stream));
+    HOOKTRY(hook_zero(q, *s));
     slot.on = true;
     return AMP_OK;
 }
 
-int amp_readpos_get(amp_ctx *c, uint32_t *hist) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    ReadposState *s = readpos_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    if (hist && q.ref_len) HOOKCHK(q, hipMemcpyAsync(hist, s->d_hist, readpos_bytes(q.ref_len), hipMemcpyDeviceToHost, q.stream));
-    HOOKCHK(q, hipStreamSynchronize(q.stream));
-    return AMP_OK;
-}
+int amp_readpos_get(amp_ctx *c, uint32_t *hist) { return hook_get(c, HOOK_READPOS, {hist}); }
 
-int amp_readpos_add(amp_ctx *c, const uint32_t *hist) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    ReadposState *s = readpos_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    return hook_add(q, s->d_hist, hist, (size_t)q.ref_len * RP_CELLS);
-}
+int amp_readpos_add(amp_ctx *c, const uint32_t *hist) { return hook_add_tables(c, HOOK_READPOS, {hist}); }
 
 int amp_readpos_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_READPOS, ms); }
 

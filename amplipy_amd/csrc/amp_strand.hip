@@ -36,17 +36,7 @@ struct StrandArgs {
 __global__ void __launch_bounds__(ST_BLOCK)
 k_strand(StrandArgs a) { tally_poswin<StrandTally>(a.in, a.out); }
 
-static size_t strand_bytes(int32_t ref_len) { return (size_t)ref_len * 64; }
-
 static StrandState *strand_state(amp_ctx *c) { return hook_state<StrandState>(c, HOOK_STRAND); }
-
-static void strand_free(void *state) {
-    StrandState *s = hook_state_of<StrandState>(state);
-    if (!s) return;
-    if (s->d_qsum) (void)hipFree(s->d_qsum);
-    s->timer.destroy();
-    delete s;
-}
 
 static int strand_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
@@ -57,13 +47,7 @@ static int strand_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_ou
     });
 }
 
-static int strand_reset(amp_ctx *c) {
-    const HookCtx q = ctx_hook(c);
-    HOOKCHK(q, hipMemsetAsync(strand_state(c)->d_qsum, 0, strand_bytes(q.ref_len), q.stream));
-    return AMP_OK;
-}
-
-HookOps strand_hook = {"the strand tallies need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, strand_enqueue, strand_reset, strand_free};
+HookOps strand_hook = {"the strand tallies need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, strand_enqueue, hook_free<StrandState>};
 
 }  // namespace amp
 
@@ -79,41 +63,23 @@ int amp_strand_enable(amp_ctx *c, int on) {
     Guard g(q.device);
     StrandState *s = strand_state(c);
     if (!s) {
-        const int rc = hook_new_state(q, slot, strand_hook, s, [&](StrandState &f) -> int {
-            HOOKCHK(q, hipMalloc((void **)&f.d_qsum, std::max<size_t>(strand_bytes(q.ref_len), 64)));
-            f.d_rev = (uint32_t *)(f.d_qsum + (size_t)q.ref_len * ST_QSUM_COLS);
+        HOOKTRY(hook_new_state(q, slot, strand_hook, s, [&](StrandState &f) -> int {
+            const size_t G = (size_t)q.ref_len;
+            HOOKTRY(hook_alloc(q, f, &f.d_qsum, std::max<size_t>(G * 64, 64), G * 64));
+            f.d_rev = (uint32_t *)(f.d_qsum + G * ST_QSUM_COLS);
+            hook_table(f, f.d_rev, G * ST_REV_COLS);
+            hook_table(f, f.d_qsum, G * ST_QSUM_COLS);
             return AMP_OK;
-        });
-        if (rc != AMP_OK) return rc;
+        }));
     }
-    HOOKCHK(q, hipMemsetAsync(s->d_qsum, 0, strand_bytes(q.ref_len), q.stream));
+    HOOKTRY(hook_zero(q, *s));
     slot.on = true;
     return AMP_OK;
 }
 
-int amp_strand_get(amp_ctx *c, uint32_t *rev, uint64_t *qsum) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    StrandState *s = strand_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    const size_t G = (size_t)q.ref_len;
-    if (rev && G) HOOKCHK(q, hipMemcpyAsync(rev, s->d_rev, G * ST_REV_COLS * 4, hipMemcpyDeviceToHost, q.stream));
-    if (qsum && G) HOOKCHK(q, hipMemcpyAsync(qsum, s->d_qsum, G * ST_QSUM_COLS * 8, hipMemcpyDeviceToHost, q.stream));
-    HOOKCHK(q, hipStreamSynchronize(q.stream));
-    return AMP_OK;
-}
+int amp_strand_get(amp_ctx *c, uint32_t *rev, uint64_t *qsum) { return hook_get(c, HOOK_STRAND, {rev, qsum}); }
 
-int amp_strand_add(amp_ctx *c, const uint32_t *rev, const uint64_t *qsum) {
-    if (!c) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
-    StrandState *s = strand_state(c);
-    if (!s) return AMP_ESTATE;
-    Guard g(q.device);
-    const size_t G = (size_t)q.ref_len;
-    const int rc = hook_add(q, s->d_rev, rev, G * ST_REV_COLS);
-    return rc != AMP_OK ? rc : hook_add(q, (uint64_t *)s->d_qsum, qsum, G * ST_QSUM_COLS);
-}
+int amp_strand_add(amp_ctx *c, const uint32_t *rev, const uint64_t *qsum) { return hook_add_tables(c, HOOK_STRAND, {rev, qsum}); }
 
 int amp_strand_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_STRAND, ms); }
 

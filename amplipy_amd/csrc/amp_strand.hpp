@@ -90,6 +90,7 @@ struct StrandShape {
     int32_t n_seg;         // segments handed out
     int32_t ref_end;       // pos + the reference bases of the CIGAR (regular reads)
 };
+constexpr StrandShape ST_NO_READ = {false, 0, 0};         // what a lane without a live read carries
 
 // The scan of a read's CIGAR, the one place where "regular" is decided: put(r0, q_index, len, is_del) for every non-empty
 // match and deletion segment in CIGAR order (q_index: the index in qual / seq of a match segment's first base), n_seg of

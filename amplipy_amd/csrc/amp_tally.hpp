@@ -104,6 +104,35 @@ __device__ __forceinline__ void block_span(int32_t &lo, int32_t &hi, int32_t *s_
     for (int w = 0; w < BLOCK / 64; ++w) { lo = min(lo, s_lo[w]); hi = max(hi, s_hi[w]); }
 }
 
+// The wave's lanes with `have` fall into groups that hold the same key; body(src, same) once per group, wave-uniformly: src is
+// the group's lowest lane, `same` the ballot of its lanes.  same_as(src) -- does this lane hold lane src's key -- is evaluated
+// by EVERY lane (its shuffles need them all) and is false in a lane without a key.  Whole waves call this; a body that wants
+// one actor tests lane == src itself, and one that wants the leader's key lets same_as leave it in a variable of the caller (a
+// scalar then, where the lane's own copy is a vector register).  (src is among `same`: the loop ends.)
+template <class Same, class Body>
+__device__ __forceinline__ void wave_each_distinct(bool have, Same same_as, Body body) {
+    unsigned long long pending = __ballot(have);
+    while (pending) {
+        const int src = __ffsll((long long)pending) - 1;
+        const unsigned long long same = __ballot(same_as(src));
+        body(src, same);
+        pending &= ~same;
+    }
+}
+
+// Two per-lane read counters summed over the wave, one atomic each onto reads[0] and reads[1]
+__device__ __forceinline__ void tally_wave_add2(unsigned long long *reads, uint32_t a, uint32_t b) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        a += __shfl_xor(a, d);
+        b += __shfl_xor(b, d);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (a) atomicAdd(&reads[0], (unsigned long long)a);
+        if (b) atomicAdd(&reads[1], (unsigned long long)b);
+    }
+}
+
 // Entry s0 + lane of a list of ns segments of type S; `have`: there is one (an all-zero entry otherwise)
 template <class S>
 __device__ __forceinline__ S seg_take(const S *list, uint32_t s0, uint32_t ns, int lane, bool &have) {
@@ -168,7 +197,7 @@ __device__ __forceinline__ void tally_poswin(const TallyReads &in, const typenam
         StrandRead R;
         uint32_t qual0;
         tally_no_read(in, R, qual0);
-        StrandShape sh = {false, 0, 0};
+        StrandShape sh = ST_NO_READ;
         const bool live = tally_live(in, i);
         if (live) {
             tally_counted_read(in, i, R, qual0);

@@ -756,7 +756,7 @@ int amp_reset(amp_ctx *c) {
     HIPCHK(c, hipGetLastError());
     for (int k = 0; k < N_HOOKS; ++k) {        // (... and the tables of every hook that has some, on or off)
         if (!c->hooks[k].state) continue;
-        const int rc = HOOKS[k]->reset(c);
+        const int rc = hook_zero(ctx_hook(c), *(const HookState *)c->hooks[k].state);
         if (rc != AMP_OK) return rc;
     }
     return AMP_OK;

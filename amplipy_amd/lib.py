@@ -323,6 +323,31 @@ class Engine:
         self._chk(getattr(self.L, entry)(self.h, C.byref(t)), entry)
         return float(t.value)
 
+    def _tables(self, entry, specs, arrays=None, head=()):
+        """The tables of a hook through ``entry``, one per (shape, dtype) of ``specs``, behind the arguments ``head``.
+        ``arrays`` None: an amp_*_get into new arrays (a first dimension of 0 is 1 for the call) -> the list of them.
+        Else an amp_*_add of ``arrays``, each made contiguous and held to the size of its shape; a None is left out."""
+        if arrays is None:
+            arrs = [np.zeros((max(shape[0], 1),) + tuple(shape[1:]), dt) for shape, dt in specs]
+        else:
+            arrs = [None if a is None else np.ascontiguousarray(a, dt) for a, (_, dt) in zip(arrays, specs)]
+            assert all(a is None or a.size == int(np.prod(shape)) for a, (shape, _) in zip(arrs, specs))
+        self._chk(getattr(self.L, entry)(self.h, *head, *[C.c_void_p(abi.ptr(a)) for a in arrs]), entry)
+        return arrs if arrays is not None else [a[:shape[0]] for a, (shape, _) in zip(arrs, specs)]
+
+    def _keyed_get(self, entry, dtype, info_fields, tail=()):
+        """The two calls of a keyed table's amp_*_get: without an array for the size, then -- the table is not empty -- with
+        one that holds it -> (dtype[used], the info dict).  ``tail``: the arguments behind info."""
+        n = C.c_int64(0)
+        info = np.zeros(len(info_fields), np.uint64)
+        args = (C.byref(n), C.c_void_p(abi.ptr(info))) + tuple(tail)
+        rc = getattr(self.L, entry)(self.h, None, C.c_int64(0), *args)
+        ev = np.zeros(max(int(n.value), 1), dtype)
+        if rc == -1 and n.value > 0:            # (AMP_EINVAL with the needed size: the table is not empty)
+            rc = getattr(self.L, entry)(self.h, C.c_void_p(abi.ptr(ev)), C.c_int64(ev.size), *args)
+        self._chk(rc, entry)
+        return ev[:int(n.value)], {k: int(v) for k, v in zip(info_fields, info)}
+
     def qc_last_ms(self):
         return self._hook_last_ms("amp_qc_last_ms")
 
@@ -334,18 +359,16 @@ class Engine:
     def strand_disable(self):
         self._chk(self.L.amp_strand_enable(self.h, C.c_int(0)), "amp_strand_enable")
 
+    def _strand_specs(self):
+        return [((self.ref_len, abi.NSYM), np.uint32), ((self.ref_len, abi.STRAND_QSUM_COLS), np.uint64)]
+
     def strand_tables(self):
         """amp_strand_get -> (rev uint32[ref_len][6], qsum uint64[ref_len][5]) as they stand."""
-        rev = np.zeros((self.ref_len, abi.NSYM), np.uint32)
-        qsum = np.zeros((self.ref_len, abi.STRAND_QSUM_COLS), np.uint64)
-        self._chk(self.L.amp_strand_get(self.h, C.c_void_p(abi.ptr(rev)), C.c_void_p(abi.ptr(qsum))), "amp_strand_get")
-        return rev, qsum
+        return tuple(self._tables("amp_strand_get", self._strand_specs()))
 
     def strand_add(self, rev, qsum):
         """amp_strand_add: host tables added element-wise (the merge of partial tables)."""
-        r = np.ascontiguousarray(rev, np.uint32); q = np.ascontiguousarray(qsum, np.uint64)
-        assert r.size == self.ref_len * abi.NSYM and q.size == self.ref_len * abi.STRAND_QSUM_COLS
-        self._chk(self.L.amp_strand_add(self.h, C.c_void_p(abi.ptr(r)), C.c_void_p(abi.ptr(q))), "amp_strand_add")
+        self._tables("amp_strand_add", self._strand_specs(), (rev, qsum))
 
     def strand_last_ms(self):
         return self._hook_last_ms("amp_strand_last_ms")
@@ -368,19 +391,17 @@ class Engine:
     def amplicon_disable(self):
         self._chk(self.L.amp_amplicon_enable(self.h, C.c_int32(0), None, None, None, None), "amp_amplicon_enable")
 
+    def _amplicon_specs(self):
+        n_amp, cells = getattr(self, "_amplicon_shape", (0, 0))
+        return [((cells, abi.NSYM), np.uint32), ((n_amp + 1,), np.uint64)]
+
     def amplicon_tables(self):
         """amp_amplicon_get -> (counts uint32[sum span][6], reads uint64[n_amp + 1]) as they stand."""
-        n_amp, cells = getattr(self, "_amplicon_shape", (0, 0))
-        counts = np.zeros((max(cells, 1), abi.NSYM), np.uint32); reads = np.zeros(n_amp + 1, np.uint64)
-        self._chk(self.L.amp_amplicon_get(self.h, C.c_void_p(abi.ptr(counts)), C.c_void_p(abi.ptr(reads))), "amp_amplicon_get")
-        return counts[:cells], reads
+        return tuple(self._tables("amp_amplicon_get", self._amplicon_specs()))
 
     def amplicon_add(self, counts, reads):
         """amp_amplicon_add: host tables added element-wise (the merge of partial tables)."""
-        n_amp, cells = getattr(self, "_amplicon_shape", (0, 0))
-        c = np.ascontiguousarray(counts, np.uint32); r = np.ascontiguousarray(reads, np.uint64)
-        assert c.size == cells * abi.NSYM and r.size == n_amp + 1
-        self._chk(self.L.amp_amplicon_add(self.h, C.c_void_p(abi.ptr(c)), C.c_void_p(abi.ptr(r))), "amp_amplicon_add")
+        self._tables("amp_amplicon_add", self._amplicon_specs(), (counts, reads))
 
     def amplicon_last_ms(self):
         return self._hook_last_ms("amp_amplicon_last_ms")
@@ -398,19 +419,16 @@ class Engine:
     def codon_disable(self):
         self._chk(self.L.amp_codon_enable(self.h, C.c_int32(0), None), "amp_codon_enable")
 
+    def _codon_specs(self):
+        return [((getattr(self, "_codon_slots", 0), abi.CODON_CELLS), np.uint32), ((2,), np.uint64)]
+
     def codon_tables(self):
         """amp_codon_get -> (codon uint32[n_slots][65], reads uint64[2]: tallied, skipped) as they stand."""
-        n = getattr(self, "_codon_slots", 0)
-        codon = np.zeros((max(n, 1), abi.CODON_CELLS), np.uint32); reads = np.zeros(2, np.uint64)
-        self._chk(self.L.amp_codon_get(self.h, C.c_void_p(abi.ptr(codon)), C.c_void_p(abi.ptr(reads))), "amp_codon_get")
-        return codon[:n], reads
+        return tuple(self._tables("amp_codon_get", self._codon_specs()))
 
     def codon_add(self, codon, reads):
         """amp_codon_add: host tables added element-wise (the merge of partial tables)."""
-        n = getattr(self, "_codon_slots", 0)
-        c = np.ascontiguousarray(codon, np.uint32); r = np.ascontiguousarray(reads, np.uint64)
-        assert c.size == n * abi.CODON_CELLS and r.size == 2
-        self._chk(self.L.amp_codon_add(self.h, C.c_void_p(abi.ptr(c)), C.c_void_p(abi.ptr(r))), "amp_codon_add")
+        self._tables("amp_codon_add", self._codon_specs(), (codon, reads))
 
     def codon_last_ms(self):
         return self._hook_last_ms("amp_codon_last_ms")
@@ -426,14 +444,7 @@ class Engine:
 
     def del_events(self):
         """amp_del_get -> (abi.DEL_EVENT_DTYPE[used] ordered by (start, len), {"used", "capacity", "lost"})."""
-        n = C.c_int64(0)
-        info = np.zeros(len(abi.DEL_INFO_FIELDS), np.uint64)
-        rc = self.L.amp_del_get(self.h, None, C.c_int64(0), C.byref(n), C.c_void_p(abi.ptr(info)))
-        ev = np.zeros(max(int(n.value), 1), abi.DEL_EVENT_DTYPE)
-        if rc == -1 and n.value > 0:            # (AMP_EINVAL with the needed size: the table is not empty)
-            rc = self.L.amp_del_get(self.h, C.c_void_p(abi.ptr(ev)), C.c_int64(ev.size), C.byref(n), C.c_void_p(abi.ptr(info)))
-        self._chk(rc, "amp_del_get")
-        return ev[:int(n.value)], {k: int(v) for k, v in zip(abi.DEL_INFO_FIELDS, info)}
+        return self._keyed_get("amp_del_get", abi.DEL_EVENT_DTYPE, abi.DEL_INFO_FIELDS)
 
     def del_add(self, events):
         """amp_del_add: host entries (abi.DEL_EVENT_DTYPE) through the kernel's insert path (the merge of partial tables)."""
@@ -464,19 +475,16 @@ class Engine:
     def cooc_disable(self):
         self._chk(self.L.amp_cooc_enable(self.h, C.c_int32(0), None, None, None, None), "amp_cooc_enable")
 
+    def _cooc_specs(self):
+        return [((getattr(self, "_cooc_sets", 0), abi.COOC_CELLS), np.uint32), ((2,), np.uint64)]
+
     def cooc_tables(self):
         """amp_cooc_get -> (cooc uint32[n_sets][65], reads uint64[2]: tallied, skipped) as they stand."""
-        n = getattr(self, "_cooc_sets", 0)
-        cooc = np.zeros((max(n, 1), abi.COOC_CELLS), np.uint32); reads = np.zeros(2, np.uint64)
-        self._chk(self.L.amp_cooc_get(self.h, C.c_void_p(abi.ptr(cooc)), C.c_void_p(abi.ptr(reads))), "amp_cooc_get")
-        return cooc[:n], reads
+        return tuple(self._tables("amp_cooc_get", self._cooc_specs()))
 
     def cooc_add(self, cooc, reads):
         """amp_cooc_add: host tables added element-wise (the merge of partial tables)."""
-        n = getattr(self, "_cooc_sets", 0)
-        c = np.ascontiguousarray(cooc, np.uint32); r = np.ascontiguousarray(reads, np.uint64)
-        assert c.size == n * abi.COOC_CELLS and r.size == 2
-        self._chk(self.L.amp_cooc_add(self.h, C.c_void_p(abi.ptr(c)), C.c_void_p(abi.ptr(r))), "amp_cooc_add")
+        self._tables("amp_cooc_add", self._cooc_specs(), (cooc, reads))
 
     def cooc_last_ms(self):
         return self._hook_last_ms("amp_cooc_last_ms")
@@ -503,20 +511,16 @@ class Engine:
     def errprof_disable(self):
         self._chk(self.L.amp_errprof_enable(self.h, C.c_int(0), None, None), "amp_errprof_enable")
 
+    _ERRPROF_SPECS = [(s, np.uint64) for s in (abi.EP_CYC_SHAPE, abi.EP_QUAL_SHAPE, abi.EP_SUB_SHAPE, (2,))]
+
     def errprof_tables(self):
         """amp_errprof_get -> (cyc uint64[2][512][2], qualt uint64[2][94][2], sub uint64[2][2][2][4][4], reads uint64[2]:
         profiled, skipped) as they stand."""
-        cyc = np.zeros(abi.EP_CYC_SHAPE, np.uint64); qualt = np.zeros(abi.EP_QUAL_SHAPE, np.uint64)
-        sub = np.zeros(abi.EP_SUB_SHAPE, np.uint64); reads = np.zeros(2, np.uint64)
-        self._chk(self.L.amp_errprof_get(self.h, C.c_void_p(abi.ptr(cyc)), C.c_void_p(abi.ptr(qualt)), C.c_void_p(abi.ptr(sub)),
-                                         C.c_void_p(abi.ptr(reads))), "amp_errprof_get")
-        return cyc, qualt, sub, reads
+        return tuple(self._tables("amp_errprof_get", self._ERRPROF_SPECS))
 
     def errprof_add(self, cyc, qualt, sub, reads):
         """amp_errprof_add: host tables added element-wise (the merge of partial tables)."""
-        arrs = [np.ascontiguousarray(a, np.uint64) for a in (cyc, qualt, sub, reads)]
-        assert [a.size for a in arrs] == [int(np.prod(s)) for s in (abi.EP_CYC_SHAPE, abi.EP_QUAL_SHAPE, abi.EP_SUB_SHAPE)] + [2]
-        self._chk(self.L.amp_errprof_add(self.h, *[C.c_void_p(abi.ptr(a)) for a in arrs]), "amp_errprof_add")
+        self._tables("amp_errprof_add", self._ERRPROF_SPECS, (cyc, qualt, sub, reads))
 
     def errprof_last_ms(self):
         return self._hook_last_ms("amp_errprof_last_ms")
@@ -540,31 +544,22 @@ class Engine:
     def hap_disable(self):
         self._chk(self.L.amp_hap_enable(self.h, C.c_int32(0), None, None, None, C.c_int(0)), "amp_hap_enable")
 
+    def _hap_specs(self):
+        return [((getattr(self, "_hap_regions", 0), abi.HAP_TALLY_COLS), np.uint64), ((2,), np.uint64)]
+
     def hap_tables(self):
         """amp_hap_get -> (abi.HAP_ENTRY_DTYPE[used] ordered by the 14 key words, {"used", "capacity", "lost"},
         tally uint64[n_regions][6]: COVER REF REF_REV LOWQ OVERFLOW EDGE, reads uint64[2]: covering, other) as they stand."""
-        nr = getattr(self, "_hap_regions", 0)
-        n = C.c_int64(0)
-        info = np.zeros(len(abi.HAP_INFO_FIELDS), np.uint64)
-        tally = np.zeros((max(nr, 1), abi.HAP_TALLY_COLS), np.uint64); reads = np.zeros(2, np.uint64)
-        args = (C.byref(n), C.c_void_p(abi.ptr(info)), C.c_void_p(abi.ptr(tally)), C.c_void_p(abi.ptr(reads)))
-        rc = self.L.amp_hap_get(self.h, None, C.c_int64(0), *args)
-        ev = np.zeros(max(int(n.value), 1), abi.HAP_ENTRY_DTYPE)
-        if rc == -1 and n.value > 0:            # (AMP_EINVAL with the needed size: the table is not empty)
-            rc = self.L.amp_hap_get(self.h, C.c_void_p(abi.ptr(ev)), C.c_int64(ev.size), *args)
-        self._chk(rc, "amp_hap_get")
-        return ev[:int(n.value)], {k: int(v) for k, v in zip(abi.HAP_INFO_FIELDS, info)}, tally[:nr], reads
+        specs = self._hap_specs()
+        tally, reads = (np.zeros((max(shape[0], 1),) + tuple(shape[1:]), dt) for shape, dt in specs)
+        ev, info = self._keyed_get("amp_hap_get", abi.HAP_ENTRY_DTYPE, abi.HAP_INFO_FIELDS, (C.c_void_p(abi.ptr(tally)), C.c_void_p(abi.ptr(reads))))
+        return ev, info, tally[:specs[0][0][0]], reads
 
     def hap_add(self, entries, tally=None, reads=None):
         """amp_hap_add: host entries (abi.HAP_ENTRY_DTYPE) through the kernel's insert path, tally and reads added element-wise
         (the merge of partial tables)."""
         ev = np.ascontiguousarray(entries, abi.HAP_ENTRY_DTYPE)
-        t = None if tally is None else np.ascontiguousarray(tally, np.uint64)
-        r = None if reads is None else np.ascontiguousarray(reads, np.uint64)
-        assert t is None or t.size == getattr(self, "_hap_regions", 0) * abi.HAP_TALLY_COLS
-        assert r is None or r.size == 2
-        self._chk(self.L.amp_hap_add(self.h, C.c_void_p(abi.ptr(ev)) if ev.size else None, C.c_int64(ev.size), C.c_void_p(abi.ptr(t)),
-                                     C.c_void_p(abi.ptr(r))), "amp_hap_add")
+        self._tables("amp_hap_add", self._hap_specs(), (tally, reads), head=(C.c_void_p(abi.ptr(ev)) if ev.size else None, C.c_int64(ev.size)))
 
     def hap_last_ms(self):
         return self._hook_last_ms("amp_hap_last_ms")
@@ -577,17 +572,16 @@ class Engine:
     def readpos_disable(self):
         self._chk(self.L.amp_readpos_enable(self.h, C.c_int(0)), "amp_readpos_enable")
 
+    def _readpos_specs(self):
+        return [((self.ref_len, abi.NSYM, abi.RP_BINS), np.uint32)]
+
     def readpos_tables(self):
         """amp_readpos_get -> hist uint32[ref_len][6][7] as it stands."""
-        hist = np.zeros((self.ref_len, abi.NSYM, abi.RP_BINS), np.uint32)
-        self._chk(self.L.amp_readpos_get(self.h, C.c_void_p(abi.ptr(hist))), "amp_readpos_get")
-        return hist
+        return self._tables("amp_readpos_get", self._readpos_specs())[0]
 
     def readpos_add(self, hist):
         """amp_readpos_add: a host table added element-wise (the merge of partial tables)."""
-        h = np.ascontiguousarray(hist, np.uint32)
-        assert h.size == self.ref_len * abi.RP_CELLS
-        self._chk(self.L.amp_readpos_add(self.h, C.c_void_p(abi.ptr(h))), "amp_readpos_add")
+        self._tables("amp_readpos_add", self._readpos_specs(), (hist,))
 
     def readpos_last_ms(self):
         return self._hook_last_ms("amp_readpos_last_ms")

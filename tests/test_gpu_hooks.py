@@ -4,7 +4,8 @@ test_gpu_amplicon.py; here: with all three on, each one's tables are bit for bit
 the same batch, and trim results, count table and events are what an engine with none on gives; the three windowed tally
 kernels (strand, amplicon, codon) on a batch whose last tile holds one read, with and without trimming; reset zeroes all three and a
 disabled one is left out; a trimming pass without its results is refused by the first hook in run order that is on, before
-anything ran; and every hook's timer answers after a batch and answers ESTATE after an empty one."""
+anything ran; every hook's timer answers after a batch and answers ESTATE after an empty one; and, for each of the eight hooks
+that keep tables, one life of its state: get before the first enable, add, reset, disable, and the next engine."""
 import numpy as np
 import pytest
 
@@ -196,3 +197,107 @@ def test_every_timer_answers_after_a_batch_and_not_after_an_empty_one():
         with pytest.raises(lib.AmpliHipError) as e:
             last_ms(eng, h)
         assert e.value.rc == -5, h
+
+
+# ---- the eight hooks that keep tables: one life of a state, the same for each ---------------------------------------------------
+TABLE_HOOKS = ("strand", "amplicon", "codon", "del", "cooc", "errprof", "hap", "readpos")
+
+
+def table_switches(eng):
+    """hook -> (enable on the example set, disable) for ``eng``; the sets and the batch -- batch(257) with its match bases set
+    onto a reference, so that the haplotype table gets keys -- are made once."""
+    st = state()
+    if "ref" not in st:
+        from tests import codon_util, cooc_util, hap_util
+        G = st["amps"].G
+        ref = hap_util.reference(G, seed=3)
+        st.update(ref=ref, cds=codon_util.overlapping(G), sets=cooc_util.mixed_sets(G), regions=hap_util.regions_near(st["primers"][:40], G),
+                  on_ref=hap_util.onto_reference(batch(257), ref, 5, rate=0.01, low_rate=0.02))
+    regions = st["regions"]
+    return {"strand": (eng.strand_enable, eng.strand_disable),
+            "amplicon": (lambda: st["amps"].enable(eng), eng.amplicon_disable),
+            "codon": (lambda: eng.codon_enable(st["cds"].starts), eng.codon_disable),
+            "del": (eng.del_enable, eng.del_disable),
+            "cooc": (lambda: eng.cooc_enable(*st["sets"].arrays()), eng.cooc_disable),
+            "errprof": (lambda: eng.errprof_enable(st["ref"]), eng.errprof_disable),
+            "hap": (lambda: eng.hap_enable([s for s, _ in regions], [e for _, e in regions], st["ref"]), eng.hap_disable),
+            "readpos": (eng.readpos_enable, eng.readpos_disable)}
+
+
+def tables_of(eng, hook):
+    """-> (the hook's arrays that add element-wise, its keyed records or None)"""
+    if hook == "del":
+        return (), eng.del_events()[0]
+    if hook == "hap":
+        ev, _, tally, reads = eng.hap_tables()
+        return (tally, reads), ev
+    t = getattr(eng, hook + "_tables")()
+    return (t if isinstance(t, tuple) else (t,)), None
+
+
+def same_tables(a, b):
+    return same(a[0], b[0]) and (a[1] is None) == (b[1] is None) and (a[1] is None or a[1].tobytes() == b[1].tobytes())
+
+
+def another_engine():
+    st = state()
+    e = lib.Engine(st["amps"].G)
+    e.set_primers(*oracle.find_overlapping_primers(st["amps"].G, st["primers"], 0))
+    e.set_params(MQ, WINDOW, True, True)
+    return e
+
+
+@pytest.mark.parametrize("hook", TABLE_HOOKS)
+def test_a_hook_s_tables_from_before_the_first_enable_to_the_next_engine(hook):
+    """Two tiles, the second with one live read.  Before the first enable a get answers ESTATE; after a batch every table holds
+    something; adding the tables just got doubles every cell, and every count and rev of a keyed table; reset zeroes them; a
+    disabled hook's tables stay readable and a further batch leaves them alone; an engine closed with every hook on takes
+    nothing with it: the next engine's tables are the first one's."""
+    other = another_engine()
+    with pytest.raises(lib.AmpliHipError) as e:
+        tables_of(other, hook)
+    assert e.value.rc == -5
+    eng = fresh(())
+    sw = table_switches(eng)
+    b = state()["on_ref"]
+    for h in TABLE_HOOKS:
+        sw[h][1]()
+    sw[hook][0]()
+    try:
+        eng.process(b)
+        once = tables_of(eng, hook)
+        assert all(x.any() for x in once[0]) and (once[1] is None or (once[1].size > 0 and once[1]["count"].all()))
+        if hook == "del":
+            eng.del_add(once[1])
+        elif hook == "hap":
+            eng.hap_add(once[1], *once[0])
+        else:
+            getattr(eng, hook + "_add")(*once[0])
+        twice = tables_of(eng, hook)
+        assert same(twice[0], added(once[0], once[0]))
+        if once[1] is not None:
+            want = once[1].copy()
+            want["count"] *= 2; want["rev"] *= 2
+            assert twice[1].tobytes() == want.tobytes()
+        eng.reset()
+        cleared = tables_of(eng, hook)
+        assert zero(cleared[0]) and (cleared[1] is None or cleared[1].size == 0)
+        eng.process(b)
+        assert same_tables(tables_of(eng, hook), once)
+        sw[hook][1]()
+        eng.process(b)
+        assert same_tables(tables_of(eng, hook), once)
+    finally:
+        sw[hook][1]()
+    sw_other = table_switches(other)
+    other.qc_enable(state()["primers"], 0, MIN_LENGTH)
+    for h in TABLE_HOOKS:
+        sw_other[h][0]()
+    other.process(b)
+    assert same_tables(tables_of(other, hook), once)
+    other.close()                               # ... with all nine states alive
+    other = another_engine()
+    table_switches(other)[hook][0]()
+    other.process(b)
+    assert same_tables(tables_of(other, hook), once)
+    other.close()
