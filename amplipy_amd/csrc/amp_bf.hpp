@@ -6,7 +6,12 @@
 // branchy forms costs a save / branch / restore of the execution mask even when it is not taken; the per-read logic was
 // a third of the fast kernel's instructions.  Here a read's whole trim is ~300 straight-line vector instructions.
 // tests/hostsim fuzzes these forms against the branchy ones and against the generic code on the CPU
-// (tests/test_hostsim_golden.py::test_branch_free_closed_forms).
+// (tests/test_hostsim_golden.py::test_branch_free_closed_forms), and walks them over the complete domain of reads of up to 12
+// bases (tests/hostsim/bf_forms_main.cpp, tests/test_bf_forms_exhaustive.py).
+//
+// A rule that is a clamp or a saturating difference is written as min / max arithmetic on the lengths, not as a chain of `bool's:
+// on the device a `bool' is a compare into a scalar register pair, every & | ! of two is a scalar mask operation and every field it
+// decides a select, and the fast kernel has no wave to spare for scalar instructions.
 #pragma once
 
 #include "amp_read.hpp"
@@ -94,49 +99,47 @@ AMP_HD int32_t bf_ref_offset(const Bf &s, int32_t qp) {
 // A:467-510, or quality_clip, A:597-622: QUALITY).  What the two differ in: a clip that ends exactly in front of the indel
 // keeps it when it is a quality clip (the op is copied behind the clip) and swallows it when it is a primer clip (an
 // insertion turns into soft clip, a deletion is dropped and the start jumps over it).  adv = the reference advance.
+// skip: the caller's `del == 0' (both clips return at once: nothing changes, nothing is punted); it passes d = 0 with it.
+//
+// Written as arithmetic on the lengths, with ONE lane condition for the outcome (a `bool' costs a compare into a scalar pair, the
+// mask operations that combine it and a select per field it decides):
+//   the indel survives (`keep') when the clip ends inside the first match op, inside the insertion or -- a quality clip -- exactly in
+//   front of the indel: d < m1 + kq with kq = the bases of the indel a clip may end in front of.  The clip then moves the start
+//   by d whatever it ate: a + d, and takes min(d, m1) from the first op and the rest from the insertion.
+//   otherwise the clip goes through the indel and eats t = min(d - m1 - kI, m2) of the second segment, which becomes the first.
 template <bool QUALITY>
-AMP_HD Bf bf_clip_left(const Bf &s, int32_t d, int32_t &adv) {
-    const bool r1 = (s.m1 > 0) & (d < s.m1);                                  // the clip ends inside the first match op
-    const int32_t d1 = d - s.m1, A = s.a + s.m1;
-    const bool stopI = !r1 & (s.kind == 1) & (d1 < s.k) & (QUALITY | (d1 > 0));     // ... inside the insertion (or right in front of it)
-    const bool stopD = !r1 & (s.kind == 2) & (d1 == 0) & QUALITY;                  // ... right in front of the deletion
-    const bool stop = stopI | stopD;
-    // the clip goes through the indel: what is left of the second segment
-    const int32_t d2 = s.kind == 1 ? bf_max(d1 - s.k, 0) : d1;
-    const int32_t m = s.kind ? s.m2 : 0;
-    const int32_t t = bf_min(d2, m);
-    const int32_t m_left = m - t;
-    const int32_t A4 = A + s.kI() + t;
+AMP_HD Bf bf_clip_left(const Bf &s, int32_t d, bool skip, int32_t &adv) {
+    const int32_t kI = s.kI(), kD = s.kD();
+    const int32_t e = bf_min(d, s.m1), d1 = d - e;                              // eaten from the first match op; what is left of the clip behind it
+    const int32_t kq = QUALITY ? (s.kind == 2 ? 1 : kI) : kI;
+    const bool keep = QUALITY ? ((d < s.m1 + kq) | skip) : (((d < s.m1 + kq) & (d != s.m1)) | skip);
+    // the clip goes through the indel: what is left of the second segment (m2 = 0 without an indel)
+    const int32_t t = bf_min(bf_max(d1 - kI, 0), s.m2);
+    const int32_t m_left = s.m2 - t;
+    const bool gone = m_left == 0;                                              // no match left: one soft clip (canon)
     Bf o;
     o.op = s.op;
-    o.punt = s.punt | ((!r1 & (s.kind != 0) & (s.m2 == 0)) ? 1u : 0u);          // an indel that already touches the far clip
-    o.a = r1 ? s.a + d : (stop ? A + (stopI ? d1 : 0) : A4 + (m_left == 0 ? s.c : 0));
-    o.m1 = r1 ? s.m1 - d : (stop ? 0 : m_left);
-    o.k = r1 ? s.k : (stop ? s.k - (stopI ? d1 : 0) : 0);
-    o.m2 = (r1 | stop) ? s.m2 : 0;
-    o.kind = (r1 | stop) ? s.kind : 0;
-    o.c = (r1 | stop) ? s.c : (m_left == 0 ? 0 : s.c);
-    adv = r1 ? d : (stop ? s.m1 : s.m1 + s.kD() + t);
+    o.punt = s.punt | (((d >= s.m1) & !skip & (s.kind != 0) & (s.m2 == 0)) ? 1u : 0u);      // an indel that already touches the far clip
+    o.a = keep ? s.a + d : s.a + s.m1 + kI + t + (gone ? s.c : 0);
+    o.m1 = keep ? s.m1 - e : m_left;
+    o.k = keep ? s.k - d1 : 0;
+    o.m2 = keep ? s.m2 : 0;
+    o.kind = keep ? s.kind : 0;
+    o.c = (keep | !gone) ? s.c : 0;
+    adv = keep ? e : s.m1 + kD + t;
     return o;
 }
 
 // primer_clip (A:467-510) of `del' query bases from the front; returns the reference advance
 AMP_HD Bf bf_primer_clip(const Bf &s, int32_t del, int32_t &adv) {
-    const int32_t d = s.a > 0 ? bf_max(del - s.a, 0) : del;                    // a soft clip stays one and eats its share
-    int32_t adv_c;
-    const Bf c = bf_clip_left<false>(s, bf_max(d, 0), adv_c);
     const bool neg = del < 0, zero = del == 0;
-    // del < 0: every query-consuming op falls into the "else" arm -- all soft clip; a deletion still advances
-    Bf o;
-    o.op = s.op;
-    o.punt = (neg | zero) ? s.punt : c.punt;
-    o.a = neg ? s.query_len() : (zero ? s.a : c.a);
-    o.m1 = neg ? 0 : (zero ? s.m1 : c.m1);
-    o.k = neg ? 0 : (zero ? s.k : c.k);
-    o.m2 = neg ? 0 : (zero ? s.m2 : c.m2);
-    o.c = neg ? 0 : (zero ? s.c : c.c);
-    o.kind = neg ? 0 : (zero ? s.kind : c.kind);
-    adv = neg ? s.kD() : (zero ? 0 : adv_c);
+    // a soft clip stays one and eats its share.  del < 0: every query-consuming op falls into the "else" arm -- all soft clip, which
+    // is what a clip longer than the read leaves; only a deletion still advances, and nothing is punted
+    const int32_t d = neg ? 0x3FFFFFFF : bf_max(del - s.a, 0);
+    int32_t adv_c;
+    Bf o = bf_clip_left<false>(s, d, zero, adv_c);
+    o.punt = neg ? s.punt : o.punt;
+    adv = neg ? s.kD() : adv_c;
     return o;
 }
 AMP_HD Bf bf_canon(const Bf &s) {         // no match left: one soft clip
@@ -146,49 +149,51 @@ AMP_HD Bf bf_canon(const Bf &s) {         // no match left: one soft clip
     o.c = all ? 0 : s.c;
     return o;
 }
+// bf_mirror where f, the shape as it is elsewhere
+AMP_HD Bf bf_mirror_if(bool f, const Bf &s) {
+    const bool sw = f & (s.kind != 0);
+    return Bf{f ? s.c : s.a, sw ? s.m2 : s.m1, s.k, sw ? s.m1 : s.m2, f ? s.a : s.c, s.kind, s.op, s.punt};
+}
 
 // Stage 1+2 of trim_read (A:450-558) on the shape, given the two table entries (-1 = None) and the outcome of the
-// template-length test of A:452: cig2_trim_primers_isize
+// template-length test of A:452: cig2_trim_primers_isize.  A clip that is not made is a clip of 0 bases, which leaves the shape as
+// it is (every shape here is canonical: bf_from_words5 gives m1 > 0, and both clips end in bf_canon or its like).
 AMP_HD Bf bf_trim_primers(const Bf &s0, int32_t &pos, uint32_t &flags, uint32_t flag, bool isize_flag, int32_t lseq,
                           int32_t left_max_end, int32_t right_min_start) {
     const bool is_paired = flag & 1u, is_reverse = (flag & 0x10u) != 0;
-    const bool do1 = !(is_paired & isize_flag & is_reverse) & (left_max_end >= 0);          // A:460
+    const bool far = is_paired & isize_flag;
+    const bool do1 = !(far & is_reverse) & (left_max_end >= 0);                             // A:460
     int32_t adv1;
-    const Bf c1 = bf_primer_clip(s0, bf_pos_on_query(s0, left_max_end + 1 - pos), adv1);   // A:463
-    Bf s = bf_pick(do1, c1, s0);
-    pos += do1 ? adv1 : 0;                                                                 // A:514
+    const Bf s = bf_primer_clip(s0, do1 ? bf_pos_on_query(s0, left_max_end + 1 - pos) : 0, adv1);   // A:463
+    pos += adv1;                                                                           // A:514
     flags |= do1 ? AMP_TRIM_PRIMER_START : 0u;
-    const bool do2 = !(is_paired & isize_flag & !is_reverse) & (right_min_start >= 0) & !s.punt;   // A:517
-    const int32_t del2 = lseq - bf_pos_on_query(s, right_min_start - pos);                 // A:520
+    const bool do2 = !(far & !is_reverse) & (right_min_start >= 0) & !s.punt;              // A:517
+    const int32_t del2 = do2 ? lseq - bf_pos_on_query(s, right_min_start - pos) : 0;       // A:520
     int32_t adv2;
-    const Bf c2 = bf_canon(bf_mirror(bf_primer_clip(bf_mirror(s), del2, adv2)));
     flags |= do2 ? AMP_TRIM_PRIMER_END : 0u;
-    return bf_pick(do2, c2, s);
+    return bf_canon(bf_mirror(bf_primer_clip(bf_mirror(s), del2, adv2)));
 }
 
-// aligned-quality window of the shape: [lo, lo + qlen) -- cig2_quality_window
+// aligned-quality window of the shape: [lo, lo + qlen) -- cig2_quality_window.  (One soft clip covering the read, whose end is not
+// examined, is written [S a]: c = 0.)
 AMP_HD void bf_quality_window(const Bf &s, int32_t lseq, int32_t &lo, int32_t &qlen) {
-    const bool single = (s.m1 == 0) & (s.kind == 0);        // one soft clip covering the read: its end is not examined
-    const int32_t qe = single ? lseq : lseq - s.c;
     lo = bf_min(s.a, lseq);
-    qlen = bf_max(qe, lo) - lo;
+    qlen = bf_max(lseq - s.c, lo) - lo;
 }
 
-// Stage 3 of trim_read given the scan result i (A:589-625, A:651-686) -- cig2_trim_quality
+// Stage 3 of trim_read given the scan result i (A:589-625, A:651-686) -- cig2_trim_quality.  A read is clipped at ONE end, its 5'
+// end in read direction: the forward read is mirrored, clipped like the reverse one and mirrored back.
 AMP_HD Bf bf_trim_quality(const Bf &s, int32_t pos, uint32_t &flags, bool is_reverse, int32_t i, int32_t qlen) {
     int32_t adv;
     // reverse strand: trimmed only if get_pos_on_ref(del + query_alignment_start - 1) > reference_start (A:591-594);
-    // reference_start is NOT advanced
-    const int32_t del_r = i;
-    const bool do_r = is_reverse & (bf_ref_offset(s, del_r + s.a - 1) > 0);
-    const Bf cr = bf_clip_left<true>(s, del_r, adv);
-    const Bf cr0 = bf_pick(del_r == 0, s, cr);                     // (quality_clip returns at once on del == 0)
-    const int32_t del_f = qlen - i;
-    const bool do_f = !is_reverse & (del_f != 0);                                          // A:656
-    const Bf cf = bf_canon(bf_mirror(bf_clip_left<true>(bf_mirror(s), del_f, adv)));
-    flags |= (do_r | do_f) ? AMP_TRIM_QUALITY : 0u;
+    // reference_start is NOT advanced.  Forward: if any base goes (A:656).  (quality_clip returns at once on del == 0)
+    const bool fwd = !is_reverse;
+    const int32_t del = fwd ? qlen - i : i;
+    const bool doit = fwd ? del != 0 : bf_ref_offset(s, del + s.a - 1) > 0;
+    flags |= doit ? AMP_TRIM_QUALITY : 0u;
+    const int32_t d = doit ? del : 0;
     (void)pos;
-    return bf_pick(do_r, cr0, bf_pick(do_f, cf, s));
+    return bf_canon(bf_mirror_if(fwd, bf_clip_left<true>(bf_mirror_if(fwd, s), d, d == 0, adv)));
 }
 
 }  // namespace amp

@@ -304,9 +304,11 @@ __device__ __forceinline__ uint32_t count_piece5(const uint2 &sq, uint32_t m16, 
 // second one, where ITS pairs are aligned.  The two halves of a pair come from two SDWA shifts into the FIXED registers v[252:253] / v[254:255] (an asm operand
 // cannot name the halves of a 64-bit register).  Counter bytes never carry (flush discipline), so the low word cannot spill over.
 __device__ __forceinline__ uint32_t count_piece5q(const uint2 &sq, uint32_t m16, int32_t d0, int32_t lim16, uint32_t wrep, uint32_t ooff) {
-    const bool inwin = (d0 >= 0) & (d0 <= lim16);
-    const bool redo = (m16 != 0u) & (!inwin | (nibbles_bad(sq.x, sq.y) != 0u));
-    const uint32_t m = redo ? 0u : m16;
+    // (ONE lane condition and selects on it: written with `bool's -- in the window, a bad code, any base counted -- the piece took three
+    //  compares and four mask operations on the scalar side, in every one of a tile's eleven pieces.  lim16 is the same for the whole wave)
+    const bool inwin = (uint32_t)d0 < (lim16 < 0 ? 0u : (uint32_t)lim16 + 1u);
+    const uint32_t defect = inwin ? nibbles_bad(sq.x, sq.y) : 1u;
+    const uint32_t m = defect ? 0u : m16;                               // nothing is added for a piece the careful loop redoes
     const uint32_t se0 = __builtin_amdgcn_perm(0x00000010u, 0x00080018u, (sq.x >> 4) & 0x07070707u);
     const uint32_t so0 = __builtin_amdgcn_perm(0x00000010u, 0x00080018u, sq.x & 0x07070707u);
     const uint32_t se1 = __builtin_amdgcn_perm(0x00000010u, 0x00080018u, (sq.y >> 4) & 0x07070707u);
@@ -326,7 +328,8 @@ __device__ __forceinline__ uint32_t count_piece5q(const uint2 &sq, uint32_t m16,
                  : : "v"(wb), "v"(se0), "v"(so0), "v"(se1), "v"(so1), "v"(f0), "v"(f1), "v"(f2), "v"(f3) : "memory", "v252", "v253", "v254", "v255");
 #undef F_SH
 #undef F_AQ
-    return redo ? 1u : 0u;
+    const uint32_t left = m16 ^ m;                                      // the counted bases that were not added: all of them or none
+    return left < 1u ? left : 1u;
 }
 // bits [klo, khi) of a 16-bit mask, klo / khi clamped to 0..16
 __device__ __forceinline__ uint32_t range_bits16(int32_t klo, int32_t khi) {
@@ -388,6 +391,8 @@ __device__ __forceinline__ uint32_t range_bits16(int32_t klo, int32_t khi) {
 enum : uint32_t { KA_MIN_START = 144, KA_MAX_END = 160, KA_NEW_POS = 176, KA_NEW_NCIG = 192, KA_NEW_CIG = 208, KA_O_REF_LEN = 224, KA_TRIM_FLAGS = 240,
                   KA_STATUS = 256, KA_COUNTS = 272, KA_EV = 288, KA_CTR = 304, KA_INS_AT = 320, KA_GLIST = 336, KA_GCNT = 352, KA_N_READS = 368,
                   KA_READ_BASE = 384, KA_EV_CAP = 400 };
+static_assert(KA_MAX_END == KA_MIN_START + 16 && KA_NEW_NCIG == KA_NEW_POS + 16 && KA_O_REF_LEN == KA_NEW_CIG + 16 && KA_STATUS == KA_TRIM_FLAGS + 16 &&
+              KA_CTR == KA_EV + 16, "karg_late2 reads two neighbours");
 template <typename T>
 __device__ __forceinline__ T karg_late(uint32_t off) {
     static_assert(sizeof(T) == 8, "the late-loaded arguments are pointers and 64-bit values");
@@ -396,11 +401,25 @@ __device__ __forceinline__ T karg_late(uint32_t off) {
         ((const __attribute__((address_space(4))) uint8_t *)__builtin_amdgcn_kernarg_segment_ptr() + off);
     return __builtin_bit_cast(T, v);
 }
+// ... two neighbours of the argument list that are used together, in ONE load with one wait (32 bytes from `off': the first value, its
+// 32-bit companion and pad, the second value, its companion and pad)
+struct KargPair { unsigned long long a, b; };
+__device__ __forceinline__ KargPair karg_late2(uint32_t off) {
+    typedef unsigned long long amp_u64x4 __attribute__((ext_vector_type(4), aligned(16)));
+    asm volatile("" : "+s"(off));
+    const amp_u64x4 v = *(const __attribute__((address_space(4))) amp_u64x4 *)
+        ((const __attribute__((address_space(4))) uint8_t *)__builtin_amdgcn_kernarg_segment_ptr() + off);
+    return KargPair{v.x, v.z};
+}
 // ... a pointer into global memory (the address space is stated: a pointer loaded from memory would otherwise be used with flat
 // instructions, which count in vmcnt AND lgkmcnt)
 template <typename T>
 __device__ __forceinline__ T *karg_late_ptr(uint32_t off) {
     return (T *)karg_late<__attribute__((address_space(1))) T *>(off);
+}
+template <typename T>
+__device__ __forceinline__ T *karg_ptr_of(unsigned long long v) {
+    return (T *)__builtin_bit_cast(__attribute__((address_space(1))) T *, v);
 }
 
 #if AMP_F_ADD64
@@ -415,7 +434,10 @@ k_fast(F_ARGS F_DBG_PARAM) {
     const KParams P{a_min_quality, a_window, a_do_trim, a_do_count, a_ref_len, a_max_primer_len, nullptr, nullptr, (uint32_t)a_epoch};
     const amp_dev_reads rd{a_n_reads, a_pos, a_flag, a_tlen, a_lseq, a_cig_off32, a_cig, a_seq_off8, a_seq, a_qual, 0, 0};
     auto late_ctr = [] { return karg_late_ptr<unsigned long long>(KA_CTR); };
-    auto late_eb = [] { return EventBuf{karg_late_ptr<amp_ins_event>(KA_EV), karg_late_ptr<unsigned long long>(KA_CTR), karg_late_ptr<uint32_t>(KA_INS_AT), karg_late<long long>(KA_EV_CAP)}; };
+    auto late_eb = [] {
+        const KargPair ec = karg_late2(KA_EV);                               // (ev, ctr)
+        return EventBuf{karg_ptr_of<amp_ins_event>(ec.a), karg_ptr_of<unsigned long long>(ec.b), karg_late_ptr<uint32_t>(KA_INS_AT), karg_late<long long>(KA_EV_CAP)};
+    };
     // THREE separate LDS objects, not one struct: the compiler orders every LDS access behind LDS-DMA loads in flight
     // (s_waitcnt vmcnt) unless alias scopes tell it that the access cannot touch the DMA's destination, and it only
     // builds those scopes per LDS variable.  With one struct every counter add waited for the next tile's bytes.
@@ -461,7 +483,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
         return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
     };
     const int64_t wend = re;                                        // (a tile's lanes past the block's reads are idle)
-    unsigned long long n_err = 0;
+    uint32_t n_err = 0;                                             // (per lane: a lane sees far fewer than 2^32 reads)
     // lane constants of the bank plan (see the head of this file)
 #ifndef AMP_F_REPSHIFT
 #define AMP_F_REPSHIFT 2
@@ -611,7 +633,10 @@ k_fast(F_ARGS F_DBG_PARAM) {
     auto load_tabs = [&](const HdrP &h, const Shape &sh, bool trim) {
         Tabs t{-1, -1};
         const bool in_ref = (uint32_t)h.pos < G && (uint32_t)(h.pos + sh.refspan - 1) < G;
-        if (trim && in_ref) { t.L = karg_late_ptr<const int32_t>(KA_MAX_END)[h.pos]; t.R = karg_late_ptr<const int32_t>(KA_MIN_START)[h.pos + sh.refspan - 1]; }
+        if (trim && in_ref) {
+            const KargPair tabs = karg_late2(KA_MIN_START);                    // (min_start, max_end)
+            t.L = karg_ptr_of<const int32_t>(tabs.b)[h.pos]; t.R = karg_ptr_of<const int32_t>(tabs.a)[h.pos + sh.refspan - 1];
+        }
         return t;
     };
     // the tile's quality bytes by LDS-DMA (lane l moves bytes [1024 s + 16 l, + 16) of the run to the same offset of
@@ -651,8 +676,10 @@ k_fast(F_ARGS F_DBG_PARAM) {
 #endif
         const uint32_t ncig = r.meta & 0xFFu;
         if (r.meta & P_STORED) {
-            const DevOut out{karg_late_ptr<int32_t>(KA_NEW_POS), karg_late_ptr<uint32_t>(KA_NEW_NCIG), karg_late_ptr<uint32_t>(KA_NEW_CIG),
-                             karg_late_ptr<int32_t>(KA_O_REF_LEN), karg_late_ptr<uint8_t>(KA_TRIM_FLAGS), karg_late_ptr<uint8_t>(KA_STATUS)};
+            // (the six output pointers, neighbours in the argument list, in three loads behind one wait)
+            const KargPair o01 = karg_late2(KA_NEW_POS), o23 = karg_late2(KA_NEW_CIG), o45 = karg_late2(KA_TRIM_FLAGS);
+            const DevOut out{karg_ptr_of<int32_t>(o01.a), karg_ptr_of<uint32_t>(o01.b), karg_ptr_of<uint32_t>(o23.a),
+                             karg_ptr_of<int32_t>(o23.b), karg_ptr_of<uint8_t>(o45.a), karg_ptr_of<uint8_t>(o45.b)};
             uint32_t *home = out.new_cig + ((size_t)r.slot_lo + 3 * (size_t)r.i);
             if (ncig > 0u) home[0] = r.cw0;
             if (ncig > 1u) home[1] = r.cw1;
@@ -880,62 +907,46 @@ k_fast(F_ARGS F_DBG_PARAM) {
 
         F_STAMP(3);          // window scan
         // ---- quality clip, results (A:589-686) ------------------------------------------------------------------
-        bool general = i < re && !shaped;               // (a lane whose bytes did not fit the run included)
-        bool stored = false;
-        uint32_t ncig = 0, cw[5] = {0u, 0u, 0u, 0u, 0u};
-        int32_t reflen = 0;
-        if (shaped) {
-            if (fb == 0xFFu || s.punt) {
-                general = true;                   // QUAL '*': the generic code reports it (A:561-562, A:718); a shape the closed forms leave
-            } else {
-                if (scan) {
-                    int32_t iq;
-                    if (!rev && ffmin != 0x7FFFFFFF) iq = ffmin - lo;
-                    else if (rev && lemax >= 0) iq = lemax - lo;
-                    else {
-                        // no full window failed: the shrinking windows at the 3' end decide
-                        iq = rev ? 0 : qlen;
-                        int32_t acc = 0;
-                        const uint64_t t_lo = (uint64_t)tw0.x | ((uint64_t)tw0.y << 32), t_hi = (uint64_t)tw1.x | ((uint64_t)tw1.y << 32);
-                        const int32_t kmax = qlen < W - 1 ? qlen : W - 1;
-                        const int32_t qlo = lo - (int32_t)phi, qhi = hi - (int32_t)phi;            // query indices
-                        for (int32_t k = 1; k <= kmax; ++k) {
-                            const uint32_t o = (uint32_t)((rev ? qlo + k - 1 : qhi - k) - tab);      // 0..15
-                            acc += (int32_t)(((o < 8u ? t_lo : t_hi) >> ((o & 7u) * 8u)) & 0xFFu);
-                            if ((int64_t)acc < (int64_t)mq * k) iq = rev ? k : qlen - k;
-                        }
-                    }
-#if AMP_F4_BF
-                    { uint32_t f2 = ts.flags; s = cig2_of(bf_trim_quality(bf_of(s), ts.pos, f2, rev, iq, qlen)); ts.flags = f2; }
-#else
-                    cig2_trim_quality(ts, rev, iq, qlen, s);
-#endif
-                }
-                if (s.punt) {
-                    general = true;
-                } else {
-                    if (!ts.err) {
-                        // [S a][op m1][I|D k][op m2][S c], absent parts left out: slot `ncig` takes the next part (part t can only land
-                        // in slots 0..t, and the second match op is never there without the indel in front of it)
-                        const uint32_t part[5] = {((uint32_t)s.a << 4) | OP_S, ((uint32_t)s.m1 << 4) | s.op,
-                                                  ((uint32_t)s.k << 4) | (s.kind == 1 ? OP_I : OP_D), ((uint32_t)s.m2 << 4) | s.op,
-                                                  ((uint32_t)s.c << 4) | OP_S};
-                        const bool has[5] = {s.a > 0, s.m1 > 0, s.kind != 0, s.kind != 0 && s.m2 > 0, s.c > 0};
-#pragma unroll
-                        for (int t = 0; t < 5; ++t) {
-                            if (has[t]) {
-#pragma unroll
-                                for (int j = (t == 3 ? 1 : 0); j <= t; ++j) cw[j] = ncig == (uint32_t)j ? part[t] : cw[j];
-                                ++ncig;
-                            }
-                        }
-                        reflen = s.ref_len();
-                    }
-                    stored = true;
-                    if (ts.err) ++n_err;
-                }
+        // Straight-line on purpose: every `if' on a lane condition here was a compare, a save / branch / restore of the execution mask and
+        // a merge of what it defined, for a handful of vector instructions the wave runs anyway.  What is left as a branch skips real work
+        // for the whole wave (the shrinking windows).  A lane that is not `scan' has lo = qlen = 0: its quality clip is a clip of 0 bases,
+        // which changes neither shape nor flags; a lane that is not `shaped' has the all-zero shape and no part to emit.
+        const bool star = fb == 0xFFu;                  // QUAL '*': the generic code reports it (A:561-562, A:718)
+        int32_t iq = rev ? (lemax >= 0 ? lemax - lo : 0) : (ffmin != 0x7FFFFFFF ? ffmin - lo : qlen);
+        const bool tail = scan & (rev ? lemax < 0 : ffmin == 0x7FFFFFFF);
+        if (tail) {
+            // no full window failed: the shrinking windows at the 3' end decide
+            int32_t acc = 0;
+            const uint64_t t_lo = (uint64_t)tw0.x | ((uint64_t)tw0.y << 32), t_hi = (uint64_t)tw1.x | ((uint64_t)tw1.y << 32);
+            const int32_t kmax = qlen < W - 1 ? qlen : W - 1;
+            const int32_t qlo = lo - (int32_t)phi, qhi = hi - (int32_t)phi;            // query indices
+            for (int32_t k = 1; k <= kmax; ++k) {
+                const uint32_t o = (uint32_t)((rev ? qlo + k - 1 : qhi - k) - tab);      // 0..15
+                acc += (int32_t)(((o < 8u ? t_lo : t_hi) >> ((o & 7u) * 8u)) & 0xFFu);
+                if ((int64_t)acc < (int64_t)mq * k) iq = rev ? k : qlen - k;
             }
         }
+#if AMP_F4_BF
+        { uint32_t f2 = ts.flags; s = cig2_of(bf_trim_quality(bf_of(s), ts.pos, f2, rev, iq, qlen)); ts.flags = f2; }
+#else
+        if (scan) cig2_trim_quality(ts, rev, iq, qlen, s);
+#endif
+        const bool stored = shaped & !star & !s.punt;   // (punt is sticky: a shape the primer clips left to the generic code stays one)
+        const bool general = i < re && !stored;         // a lane whose bytes did not fit the run, QUAL '*', a shape the closed forms leave
+        const bool emit = stored & (ts.err == 0);
+        // [S a][op m1][I|D k][op m2][S c]: the five parts in place, then the absent ones drop out from the back, so that no word moves
+        // twice (the second match op is never there without the indel in front of it)
+        const bool has0 = emit & (s.a > 0), has1 = emit & (s.m1 > 0), has2 = emit & (s.kind != 0), has3 = has2 & (s.m2 > 0), has4 = emit & (s.c > 0);
+        uint32_t cw[5] = {((uint32_t)s.a << 4) | OP_S, ((uint32_t)s.m1 << 4) | s.op, ((uint32_t)s.k << 4) | (s.kind == 1 ? OP_I : OP_D),
+                          ((uint32_t)s.m2 << 4) | s.op, ((uint32_t)s.c << 4) | OP_S};
+        cw[4] = has4 ? cw[4] : 0u;
+        cw[3] = has3 ? cw[3] : cw[4]; cw[4] = has3 ? cw[4] : 0u;
+        cw[2] = has2 ? cw[2] : cw[3]; cw[3] = has2 ? cw[3] : cw[4]; cw[4] = has2 ? cw[4] : 0u;
+        cw[1] = has1 ? cw[1] : cw[2]; cw[2] = has1 ? cw[2] : cw[3]; cw[3] = has1 ? cw[3] : cw[4]; cw[4] = has1 ? cw[4] : 0u;
+        cw[0] = has0 ? cw[0] : cw[1]; cw[1] = has0 ? cw[1] : cw[2]; cw[2] = has0 ? cw[2] : cw[3]; cw[3] = has0 ? cw[3] : cw[4]; cw[4] = has0 ? cw[4] : 0u;
+        const uint32_t ncig = (has0 ? 1u : 0u) + (has1 ? 1u : 0u) + (has2 ? 1u : 0u) + (has3 ? 1u : 0u) + (has4 ? 1u : 0u);
+        const int32_t reflen = emit ? s.ref_len() : 0;
+        n_err += (stored & (ts.err != 0)) ? 1u : 0u;
         const bool counted = stored && !ts.err && do_count_t;
         F_STAMP(4);          // quality clip, results
         // ---- counting (A:709-753): the counted query ranges [qa1, qb1) and [qa2, qb2) in piece coordinates, the window
@@ -1020,14 +1031,10 @@ k_fast(F_ARGS F_DBG_PARAM) {
         const uint32_t okB = ok_bits16(make_uint4(bq0.x, bq0.y, bq1.x, bq1.y), mqb);
 #endif
         // group B: the part of the second segment that shares a piece with the first
-        int32_t xbe = 0, jb = 0;
-        bool has_b = false;
-        if (two) {
-            const int32_t jstar = (qb1 - 1) & ~15;                   // the piece that holds the first segment's last base
-            has_b = jstar + 16 > qa2 && qb2 > qa2;
-            xbe = qb2 < jstar + 16 ? qb2 : jstar + 16;
-            jb = g_b + (int32_t)phi;
-        }
+        // (xbe and jb are looked at for lanes with has_b alone)
+        const int32_t jstar = (qb1 - 1) & ~15;                       // the piece that holds the first segment's last base
+        const bool has_b = two & (jstar + 16 > qa2) & (qb2 > qa2);
+        const int32_t xbe = qb2 < jstar + 16 ? qb2 : jstar + 16, jb = g_b + (int32_t)phi;
         // The bases go into the wave's packed window, F_PW positions from pw_base.  Reads of one tile usually lie within a
         // few positions of each other; where the batch steps from one pile of reads to the next they do not, and the
         // tile is counted in PASSES: every pass takes the lanes whose counted positions all lie inside the window, then the
@@ -1149,7 +1156,7 @@ k_fast(F_ARGS F_DBG_PARAM) {
             }
         }
     }
-    if (n_err) atomicAdd(&late_ctr()[CTR_ERROR_READS], n_err);
+    if (n_err) atomicAdd(&late_ctr()[CTR_ERROR_READS], (unsigned long long)n_err);
     F_STAMP_OUT;
     if (tid == 0) { karg_late_ptr<uint32_t>(KA_GCNT)[blockIdx.x] = s_gcur; if (s_gcur) late_ctr()[CTR_EPOCH] = (unsigned long long)P.epoch; }      // (every block writes the same value)
 }
