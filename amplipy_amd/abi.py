@@ -84,6 +84,14 @@ DEL_EVENT_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("count", "<u4"), 
 DEL_INFO_FIELDS = ("used", "capacity", "lost")                  # amp_del_info, uint64 each
 assert DEL_EVENT_DTYPE.itemsize == 16
 
+# ---- insertion evidence (amp_insev_*): amp_insev_entry[used], amp_insev_info = amp_del_info ----
+INSEV_LOG2_DEFAULT, INSEV_LOG2_MIN, INSEV_LOG2_MAX = 20, 4, 28  # slots of the device table (64 bytes each): 0 asks for the default
+INSEV_BINS = 7                                                  # rp_bin's: d < 2, 2-3, 4-7, 8-15, 16-31, 32-63, >= 64
+INSEV_STRIDE = 512 * 256                                        # AMP_INSEV_STRIDE: events the kernel's grid takes in one stride
+INSEV_ENTRY_DTYPE = np.dtype([("ref_pos", "<i4"), ("len", "<i4"), ("hash", "<u8"), ("count", "<u4"), ("rev", "<u4"), ("noqual", "<u4"),
+                              ("qsum", "<u8"), ("bin", "<u4", (INSEV_BINS,))], align=True)
+assert INSEV_ENTRY_DTYPE.itemsize == 72 and INSEV_ENTRY_DTYPE.fields["qsum"][1] == 32
+
 # ---- co-occurrence of listed mutations (amp_cooc_*): cooc uint32[n_sets][COOC_CELLS], reads uint64[2] ----
 COOC_CELLS = 65                # the 64 patterns (site 0 is bit 0), then partial
 COOC_SITES = 6                 # sites of a set at most

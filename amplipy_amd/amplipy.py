@@ -15,7 +15,7 @@ import sys
 import types
 from os.path import isfile
 
-from . import AMPLIPY_VERSION, calling, lib, parallel, qc, reports
+from . import AMPLIPY_VERSION, calling, insevidence, lib, parallel, qc, reports
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -79,9 +79,11 @@ def open_device_bam_text(input_fn, output_fn):
 class VcfWriter:
     """Text VCF with the header AmpliPy builds through pysam (AmpliPy.py:271-281)."""
 
-    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False, errprof=False, hap=False, readpos=False):
+    def __init__(self, fn, ref_id, strand=False, amplicon=False, codon=False, deletion=False, cooc=False, errprof=False, hap=False, readpos=False,
+                 insertions=False):
         """Each keyword of calling.INFO_ORDER: the header also declares the INFO keys of that report, in that order (``line``
-        appends them when given the report's tables)."""
+        appends them when given the report's tables).  insertions: the two keys of the indel unit's insertion half
+        (insevidence.py), behind the deletion keys' place -- the half has no report of its own."""
         if fn.lower() == "stdout":
             self.f = sys.stdout
         elif isfile(fn):
@@ -105,7 +107,7 @@ class VcfWriter:
         w("##INFO=<ID=REF_FREQ,Number=1,Type=Float,Description=\"Frequency of reference base\">\n")
         w("##INFO=<ID=ALT_FREQ,Number=1,Type=String,Description=\"Frequency of alternate base\">\n")
         on = dict(zip(calling.INFO_ORDER, (strand, amplicon, codon, deletion, cooc, errprof, hap, readpos)))
-        w("".join([R.HEADER_LINES for R in reports.REGISTRY if on[R.name]]))
+        w("".join([(R.HEADER_LINES if on[R.name] else "") + (insevidence.HEADER_LINES if insertions and R.name == "deletion" else "") for R in reports.REGISTRY]))
         w("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n")
 
     def line(self, r, strand=None, amplicon=None, codon=None, deletion=None, cooc=None, errprof=None, hap=None, readpos=None):
@@ -130,7 +132,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 qc_depth_fn=None, strand=False, strand_fn=None, amplicons_fn=None, amplicon_out_fn=None, codons_fn=None,
                 codon_out_fn=None, aa_out_fn=None, deletions=False, del_out_fn=None, indel_vcf_fn=None, del_capacity=None, cooc_fn=None,
                 cooc_out_fn=None, error_profile_fn=None, error_mask_fn=None, haplotypes_fn=None, hap_out_fn=None, hap_min_reads=None,
-                hap_min_freq=None, hap_capacity=None, readpos=False, readpos_end=None, readpos_fn=None):
+                hap_min_freq=None, hap_capacity=None, readpos=False, readpos_end=None, readpos_fn=None, insertions=False, ins_out_fn=None,
+                ins_capacity=None, ins_end=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -167,6 +170,13 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     indel_vcf_fn (runs that call variants): a second, spec-valid VCF of anchored indels -- the events and the call's insertion
     alleles at or above the variant thresholds.  del_capacity: log2 of the device table's slots (default 20).  Reads of events
     the table had no slot for end the run with an error.  With the first three off the engine's hook is never switched on.
+    insertions (default: off; runs that write a VCF): the insertion half of the same unit.  The device
+    tallies, behind every batch's read pass, the batch's insertion events per allele -- reads, reverse reads, quality sum, reads
+    without qualities and seven bins of the allele's distance to the nearer end of the read's kept bases -- and every VCF record
+    also carries INS_N and INS.  ins_out_fn: every allele as a TSV file (runs with a count table).  ins_capacity: log2 of the
+    device table's slots (default 20).  ins_end: the distance below which an allele counts as at a read end (one of 2, 4, 8, 16,
+    32, 64; default 8).  With the half on, the insertion rows of indel_vcf_fn carry RV.  The device entries are joined with the
+    run's allele texts as a check: a miss, a double hit or a count mismatch ends the run with an error that names the position.
     cooc_fn (default: off; runs with a count table): the mutation-set file -- a name and a comma-separated list of mutations per
     line, A23403G, del21765-21770 or del21991, POSITIONS 1-BASED as in the VCF.  The device tallies,
     behind every batch's read pass, per set the reads that show all its sites by the pattern of mutations they carry, and every
@@ -294,7 +304,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             print_log(route.note)
         if variants_fn is not None and rank == 0:
             print_log("Output variants VCF: %s" % variants_fn)
-            vcf = VcfWriter(variants_fn, ref_id, **{r.name: r.annotates(run) for r in on})
+            vcf = VcfWriter(variants_fn, ref_id, insertions=bool(insertions), **{r.name: r.annotates(run) for r in on})
         for r in on:
             r.open(run)
         if qc_on:
@@ -319,6 +329,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             r.enable(run, eng)
     print_log("Processing reads...")
     loop = ReadLoop(eng, min_length, include_no_primer, run_trim, do_count)
+    vars(run).update(ins_store=loop.ins_store)    # (the insertion evidence joins the device entries with the run's allele texts)
     if driver is not None:
         try:
             driver.run(loop)
@@ -503,6 +514,10 @@ def parse_args(argv=None):
         p.add_argument("--del_out", required=False, type=str, default=None, help="Every deletion event: start, length, reads, reverse reads, depth, frequency, deleted text (TSV or TSV.gz; variants, consensus, aio)")
         p.add_argument("--indel_vcf", required=False, type=str, default=None, help="A second VCF of anchored indels: deletion events and insertion alleles at or above the variant thresholds (VCF or VCF.gz; variants, aio)")
         p.add_argument("--del_capacity", required=False, type=int, default=None, help="log2 of the slots of the deletion events' table on the device, 4 to 28 (20 when omitted)")
+        p.add_argument("--insertions", action="store_true", help="Insertion alleles tallied with their evidence on the device; VCF records also carry INS_N and INS: the alleles anchored at the position with reads, reverse reads, mean base quality and reads near a read end; the insertion rows of --indel_vcf carry RV (variants, aio)")
+        p.add_argument("--ins_out", required=False, type=str, default=None, help="Every insertion allele: position, allele, reads, reverse reads, reads without qualities, mean base quality, seven distance-to-end bins, depth, frequency (TSV or TSV.gz; variants, consensus, aio)")
+        p.add_argument("--ins_capacity", required=False, type=int, default=None, help="log2 of the slots of the insertion evidence table on the device, 4 to 28 (20 when omitted)")
+        p.add_argument("--ins_end", required=False, type=int, default=None, help="Distance below which an insertion allele counts as at a read end in INS: one of 2, 4, 8, 16, 32, 64 (8 when omitted); needs --insertions or --ins_out")
         p.add_argument("--cooc", required=False, type=str, default=None, help="Mutation-set file (TSV: name, comma-separated mutations such as A23403G, del21765-21770, del21991; positions 1-BASED as in the VCF, unlike --codons): per set, the reads that carry its mutations together, tallied on the device, and COOC on every VCF record (variants, consensus, aio)")
         p.add_argument("--cooc_out", required=False, type=str, default=None, help="Reads per mutation set and pattern of mutations carried (TSV or TSV.gz; needs --cooc)")
         p.add_argument("--error_profile", required=False, type=str, default=None, help="Error profile (JSON): how often a base differs from the reference by sequencing cycle, by reported quality and by substitution class, tallied on the device over every match base; ERR_RATE and ERR_P on every VCF record. Without --error_mask the site's own bases are part of the rate (variants, consensus, aio)")
@@ -530,7 +545,8 @@ def main(argv=None):
                    del_out_fn=args.del_out, indel_vcf_fn=args.indel_vcf, del_capacity=args.del_capacity, cooc_fn=args.cooc, cooc_out_fn=args.cooc_out,
                    error_profile_fn=args.error_profile, error_mask_fn=args.error_mask, haplotypes_fn=args.haplotypes, hap_out_fn=args.hap_out,
                    hap_min_reads=args.hap_min_reads, hap_min_freq=args.hap_min_freq, hap_capacity=args.hap_capacity,
-                   readpos=args.readpos, readpos_end=args.readpos_end, readpos_fn=args.readpos_out)
+                   readpos=args.readpos, readpos_end=args.readpos_end, readpos_fn=args.readpos_out, insertions=args.insertions,
+                   ins_out_fn=args.ins_out, ins_capacity=args.ins_capacity, ins_end=args.ins_end)
     if args.command == "trim":
         run_amplipy(untrimmed_reads_fn=args.input, primer_fn=args.primer, reference_fn=args.reference,
                     trimmed_reads_fn=args.output, primer_pos_offset=args.primer_pos_offset, min_length=args.min_length,

@@ -13,9 +13,9 @@ CSRC = os.path.join(_HERE, "csrc")
 # host code beside it compiles none of them); the insertion-event aggregation (its sort headers triple the compile time of
 # whatever includes them, so it is built -- and cached -- on its own), the DEFLATE encoder of the BAM writer, and
 # the codecs for SAM text and for BAM (input, and trimmed records out), the QC report, the strand tallies, the per-amplicon counts, and
-# the codon tallies, the deletion events, the co-occurrence tallies, the error profile, the read haplotypes, the read-position tallies
+# the codon tallies, the deletion events, the insertion evidence, the co-occurrence tallies, the error profile, the read haplotypes, the read-position tallies
 UNITS = ["amplihip.hip", "amp_readpass.hip", "amp_ins.hip", "amp_deflate.hip", "amp_sam.hip", "amp_bgzf.hip", "amp_qc.hip", "amp_strand.hip", "amp_amplicon.hip",
-         "amp_codon.hip", "amp_del.hip", "amp_cooc.hip", "amp_errprof.hip", "amp_hap.hip", "amp_readpos.hip"]
+         "amp_codon.hip", "amp_del.hip", "amp_insev.hip", "amp_cooc.hip", "amp_errprof.hip", "amp_hap.hip", "amp_readpos.hip"]
 HEADERS = [os.path.join(_HERE, "..", "include", "amplihip.h")] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
 # what a unit includes, as `hipcc -MM` reports it (tests/test_build_deps.py holds every list to that): a unit is recompiled
 # when one of these is newer than its object.  amp_ctx.hpp (the context) is private to the first two.
@@ -33,6 +33,8 @@ UNIT_DEPS = {"amplihip.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")
              "amp_amplicon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_amplicon.hpp", "amp_tally.hpp")],
              "amp_codon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_codon.hpp", "amp_tally.hpp")],
              "amp_del.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_del.hpp", "amp_keyed.hpp", "amp_tally.hpp")],
+             # (the insertion half of the indel unit: it reads the event list -- amp_ins.hpp -- and takes rp_bin from amp_readpos.hpp)
+             "amp_insev.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_insev.hpp", "amp_keyed.hpp", "amp_ins.hpp", "amp_readpos.hpp", "amp_tally.hpp")],
              "amp_cooc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_cooc.hpp", "amp_tally.hpp")],
              "amp_errprof.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_errprof.hpp", "amp_tally.hpp")],
              "amp_hap.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_hap.hpp", "amp_keyed.hpp", "amp_tally.hpp")],

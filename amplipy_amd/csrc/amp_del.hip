@@ -167,15 +167,28 @@ k_del(DelArgs a) {
 
 static DelState *del_state(amp_ctx *c) { return hook_state<DelState>(c, HOOK_DEL); }
 
+// The slot's enqueue: k_del while the deletion half is on, then the insertion half's kernel (amp_insev.hip) while that is
 static int del_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
     DelState *s = del_state(c);
-    return hook_launch(q, s, del_hook, rd->n_reads, o, DL_BLOCK, DL_TILES_PER_BLOCK, DL_BLOCKS_PER_CU, [&](unsigned grid) {
-        k_del<<<grid, DL_BLOCK, 0, q.stream>>>(DelArgs{tally_reads(q, rd, o), s->t});
-    });
+    s->timer.timed = false;
+    if (hook_slot(c, HOOK_DEL).halves & 1u)
+        HOOKTRY(hook_launch(q, s, del_hook, rd->n_reads, o, DL_BLOCK, DL_TILES_PER_BLOCK, DL_BLOCKS_PER_CU, [&](unsigned grid) {
+            k_del<<<grid, DL_BLOCK, 0, q.stream>>>(DelArgs{tally_reads(q, rd, o), s->t});
+        }));
+    return insev_enqueue(c, s->more, rd, o);
 }
 
-HookOps del_hook = {"the deletion events need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, del_enqueue, hook_free<DelState>};
+// The slot's state for the insertion half to hang its own on: made here, without a table, when the deletion half was never
+// enabled (amp_del_get and amp_del_add answer AMP_ESTATE as before the first enable: the table has no keys)
+int indel_slot_state(amp_ctx *c, HookState **out) {
+    DelState *s = del_state(c);
+    if (!s) HOOKTRY(hook_new_state(ctx_hook(c), hook_slot(c, HOOK_DEL), del_hook, s, [](DelState &) -> int { return AMP_OK; }));
+    *out = s;
+    return AMP_OK;
+}
+
+HookOps del_hook = {"the deletion events need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, del_enqueue, hook_free<DelState>, insev_before_pass};
 
 }  // namespace amp
 
@@ -187,7 +200,7 @@ int amp_del_enable(amp_ctx *c, int on, int log2_capacity) {
     if (!c) return AMP_EINVAL;
     const HookCtx q = ctx_hook(c);
     HookSlot &slot = hook_slot(c, HOOK_DEL);
-    if (!on) { slot.on = false; return AMP_OK; }
+    if (!on) { hook_half(slot, 0, false); return AMP_OK; }
     HOOKTRY(keyed_capacity<DelKeys>(q, log2_capacity));
     Guard g(q.device);
     DelState *s = del_state(c);
@@ -195,13 +208,13 @@ int amp_del_enable(amp_ctx *c, int on, int log2_capacity) {
         HOOKTRY(hook_new_state(q, slot, del_hook, s, [&](DelState &f) -> int { return keyed_layout(q, f, f.t, (uint32_t)log2_capacity); }));
     } else if (s->t.log2_capacity != (uint32_t)log2_capacity) {
         // another capacity: the table is laid out again (a kernel on the old one may still be in flight)
-        slot.on = false;
+        hook_half(slot, 0, false);
         HOOKCHK(q, hipStreamSynchronize(q.stream));
         hook_release(*s);
         HOOKTRY(keyed_layout(q, *s, s->t, (uint32_t)log2_capacity));
     }
     HOOKTRY(hook_zero(q, *s));
-    slot.on = true;
+    hook_half(slot, 0, true);
     return AMP_OK;
 }
 

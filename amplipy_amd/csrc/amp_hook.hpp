@@ -54,6 +54,9 @@ struct HookCtx {
     const uint32_t *counts;     // the device table as it stands
     int do_trim, have_primers, min_quality, n_cu;
     char *err; size_t err_cap;
+    // the insertion-event list as the read pass leaves it (amp_insev.hip): EV_SHARDS regions of ev_cap entries, and the shards'
+    // slot counters on the device.  Valid until the next read pass, which may lay the regions out again.
+    const amp_ins_event *events; long long ev_cap; const unsigned long long *ev_n;
 };
 HookCtx ctx_hook(amp_ctx *c);
 
@@ -62,8 +65,14 @@ enum { HOOK_QC, HOOK_STRAND, HOOK_AMPLICON, HOOK_CODON, HOOK_DEL, HOOK_COOC, HOO
 struct HookSlot {
     bool on;                    // the switch amplihip.hip reads per batch
     void *state;                // the hook's device state, owned by its unit; it outlives the switch (tables stay readable)
+    uint8_t halves;             // a slot of two halves (HOOK_DEL: bit 0 the deletion events, bit 1 the insertion evidence): `on` is their OR
 };
 HookSlot &hook_slot(amp_ctx *c, int which);
+// One half's switch of a slot that carries two
+inline void hook_half(HookSlot &slot, int half, bool on) {
+    slot.halves = (uint8_t)(on ? slot.halves | (1u << half) : slot.halves & ~(1u << half));
+    slot.on = slot.halves != 0;
+}
 
 // The results of a trimming pass (the fields of amp_trim_out, in its order) a hook's kernel reads.
 enum : uint32_t { OUT_NEW_POS = 1u, OUT_NEW_NCIG = 2u, OUT_NEW_CIG = 4u, OUT_REF_LEN = 8u, OUT_TRIM_FLAGS = 16u, OUT_STATUS = 32u };
@@ -73,10 +82,23 @@ struct HookOps {
     uint32_t needs;             // OUT_* bits
     int (*enqueue)(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *dev_out);       // the kernel on the ctx stream; the state exists
     void (*free_state)(void *state);        // hook_free of the unit's state; a null state is nothing to do
+    // Optional (null in most units): in FRONT of a batch's read pass, on the ctx stream, while the hook is on -- what the unit has
+    // to note of the ctx's device state before the pass changes it.  read_base is the pass's own.
+    int (*before_pass)(amp_ctx *c, uint64_t read_base);
 };
 // One per unit; amplihip.hip keeps them in enum order.  (Not const objects, though nothing writes them: hipcc emits a const
 // object with a constant initialiser into the device image as well, host function pointers and all.)
 extern HookOps qc_hook, strand_hook, amplicon_hook, codon_hook, del_hook, cooc_hook, errprof_hook, hap_hook, readpos_hook;
+
+// What the two halves of HOOK_DEL's slot ask of each other.  amp_insev.hip: del_hook's before_pass -- while the insertion
+// half is on, the event list's slot counts as they stand become the half's cursor: what the pass appends behind them is this
+// batch's; nothing is enqueued while the half is off -- and its kernel behind the pass while its half is on (`more`: the
+// half's state, null before its first enable).  amp_del.hip: the slot's state, made without a table when the deletion half
+// was never enabled.
+struct HookState;
+int insev_before_pass(amp_ctx *c, uint64_t read_base);
+int insev_enqueue(amp_ctx *c, HookState *more, const amp_dev_reads *rd, const amp_trim_out *dev_out);
+int indel_slot_state(amp_ctx *c, HookState **state);
 
 // With trimming on, every result in `needs` must be there; otherwise the refusal is in q.err.  amplihip.hip asks in front of a
 // device batch's read pass, so that a refused call changes nothing; an enqueue asks again.
@@ -161,6 +183,8 @@ struct HookState {
     Owned owned[8] = {};
     Table table[4] = {};
     int n_owned = 0, n_table = 0;
+    HookState *more = nullptr;              // the state of the slot's second half (amp_insev.hip behind amp_del.hip), with what frees it:
+    void (*free_more)(void *) = nullptr;    // amp_reset zeroes it and the slot's free takes it along; nothing else follows the link
 };
 template <class S> S *hook_state_of(void *state) { return static_cast<S *>(static_cast<HookState *>(state)); }
 template <class S> S *hook_state(amp_ctx *c, int which) { return hook_state_of<S>(hook_slot(c, which).state); }
@@ -191,6 +215,7 @@ template <class S>
 void hook_free(void *state) {
     S *s = hook_state_of<S>(state);
     if (!s) return;
+    if (s->more) s->free_more(s->more);
     hook_release(*s);
     s->timer.destroy();
     delete s;

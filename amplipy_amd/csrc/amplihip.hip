@@ -269,12 +269,23 @@ hipStream_t ctx_stream(const amp_ctx *c) { return c->stream; }
 int ctx_device(const amp_ctx *c) { return c->device; }
 // ... and the hooks behind the read pass (amp_hook.hpp)
 HookCtx ctx_hook(amp_ctx *c) {
-    return HookCtx{c->device, c->ref_len, c->stream, c->d_counts, c->do_trim, c->have_primers ? 1 : 0, c->min_quality, c->n_cu, c->err, sizeof(c->err)};
+    return HookCtx{c->device, c->ref_len, c->stream, c->d_counts, c->do_trim, c->have_primers ? 1 : 0, c->min_quality, c->n_cu, c->err, sizeof(c->err),
+                   c->events.as<amp_ins_event>(), (long long)c->ev_cap, c->d_ctr + CTR_EV_SHARD0};
 }
 HookSlot &hook_slot(amp_ctx *c, int which) { return c->hooks[which]; }
 }  // namespace amp
 
 static const HookOps *const HOOKS[N_HOOKS] = {&qc_hook, &strand_hook, &amplicon_hook, &codon_hook, &del_hook, &cooc_hook, &errprof_hook, &hap_hook, &readpos_hook};      // in the enum's order: the run order
+
+// What the hooks that are on have to note in FRONT of the read pass (HookOps::before_pass, where a unit has one)
+static int hooks_before_pass(amp_ctx *c, uint64_t read_base) {
+    for (int k = 0; k < N_HOOKS; ++k) {
+        if (!c->hooks[k].on || !HOOKS[k]->before_pass) continue;
+        const int rc = HOOKS[k]->before_pass(c, read_base);
+        if (rc != AMP_OK) return rc;
+    }
+    return AMP_OK;
+}
 
 // The kernels of the hooks that are on, behind the read pass on the ctx stream, until one fails.
 static int enqueue_hooks(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *dev_out) {
@@ -416,7 +427,7 @@ void amp_ctx_destroy(amp_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (int k = 0; k < N_HOOKS; ++k) {
         HOOKS[k]->free_state(c->hooks[k].state);
-        c->hooks[k] = HookSlot{false, nullptr};
+        c->hooks[k] = HookSlot{false, nullptr, 0};
     }
     if (c->own_counts && c->d_counts) (void)hipFree(c->d_counts);
     if (c->d_min_start) (void)hipFree(c->d_min_start);
@@ -515,6 +526,12 @@ int amp_debug_last_second_grids(amp_ctx *c, int *gen_blocks, int *heavy_blocks) 
     return AMP_OK;
 }
 
+int amp_debug_event_capacity(amp_ctx *c, int64_t *per_shard) {
+    if (!c || !per_shard) return AMP_EINVAL;
+    *per_shard = c->ev_cap;
+    return AMP_OK;
+}
+
 int amp_set_timing(amp_ctx *c, int split) {
     if (!c) return AMP_EINVAL;
     c->split_timing = split != 0;
@@ -547,7 +564,8 @@ int amp_process_batch_device(amp_ctx *c, const amp_dev_reads *rd, uint64_t read_
         const int rc = hook_check_out(ctx_hook(c), dev_out, *HOOKS[k]);
         if (rc != AMP_OK) return rc;
     }
-    const int rc = launch_reads(c, rd, read_base, dev_out);
+    int rc = hooks_before_pass(c, read_base);
+    if (rc == AMP_OK) rc = launch_reads(c, rd, read_base, dev_out);
     return rc != AMP_OK ? rc : enqueue_hooks(c, rd, dev_out);
 }
 
@@ -584,7 +602,8 @@ int amp_process_batch(amp_ctx *c, const amp_reads *r, uint64_t read_base, const 
     const amp_dev_reads rd = staged_reads(c);
     amp_trim_out dout{c->o_pos.as<int32_t>(), c->o_ncig.as<uint32_t>(), c->o_cig.as<uint32_t>(), c->o_reflen.as<int32_t>(),
                       c->o_flags.as<uint8_t>(), c->o_status.as<uint8_t>()};
-    int rc = launch_reads(c, &rd, read_base, &dout);
+    int rc = hooks_before_pass(c, read_base);
+    if (rc == AMP_OK) rc = launch_reads(c, &rd, read_base, &dout);
     if (rc != AMP_OK) return rc;
     rc = enqueue_hooks(c, &rd, &dout);         // (no check in front of the pass here: dout is always complete)
     if (rc != AMP_OK) return rc;
@@ -755,9 +774,10 @@ int amp_reset(amp_ctx *c) {
     k_reset<<<std::min<unsigned>(RESET_BLOCKS, (unsigned)((words + ctr_words + 1023) / 1024)), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, ctr_words);
     HIPCHK(c, hipGetLastError());
     for (int k = 0; k < N_HOOKS; ++k) {        // (... and the tables of every hook that has some, on or off)
-        if (!c->hooks[k].state) continue;
-        const int rc = hook_zero(ctx_hook(c), *(const HookState *)c->hooks[k].state);
-        if (rc != AMP_OK) return rc;
+        for (const HookState *s = (const HookState *)c->hooks[k].state; s; s = s->more) {      // (a slot of two halves: both)
+            const int rc = hook_zero(ctx_hook(c), *s);
+            if (rc != AMP_OK) return rc;
+        }
     }
     return AMP_OK;
 }

@@ -10,7 +10,7 @@ import sys
 
 import numpy as np
 
-from . import abi, parallel
+from . import abi, insevidence, parallel
 from .readloop import error
 from .reports import Report
 
@@ -116,10 +116,11 @@ def insertion_rows(records):
     return out
 
 
-def indel_records(tables, insertions=()):
+def indel_records(tables, insertions=(), evidence=None):
     """[(POS, REF, ALT, INFO)] of the indel VCF, by position (at one position deletions first, shorter first, then
     insertions by allele).  A deletion is anchored at the base in front of it; one that starts at the first base of the
-    reference at the base behind it, as the VCF specification prescribes."""
+    reference at the base behind it, as the VCF specification prescribes.  evidence: the insertion alleles' insevidence.Tables
+    (--insertions, --ins_out) -- an insertion row then carries its reverse reads in RV."""
     ref = tables.ref
     rows = []
     for s, l, c, r, d in tables.called():
@@ -132,33 +133,55 @@ def indel_records(tables, insertions=()):
         rows.append((pos, 0, l, "", ref_text, alt, "DP=%d;AD=%d;RV=%d;AF=%.6g" % (d, c, r, c / d)))
     for p, allele, n, dp in insertions:
         if dp >= tables.min_depth and dp > 0 and n / dp >= tables.min_freq:
-            rows.append((p + 1, 1, 0, allele, ref[p], allele, "DP=%d;AD=%d;RV=.;AF=%.6g" % (dp, n, n / dp)))
+            rv = evidence.rev_of(p, allele) if evidence is not None else None
+            rows.append((p + 1, 1, 0, allele, ref[p], allele, "DP=%d;AD=%d;RV=%s;AF=%.6g" % (dp, n, "." if rv is None else "%d" % rv, n / dp)))
     rows.sort(key=lambda x: x[:4])
     return [(x[0], x[4], x[5], x[6]) for x in rows]
 
 
-def write_indel_vcf(f, ref_id, tables, insertions=(), source=""):
-    """The second VCF: spec-valid VCF 4.2 records of anchored indels, by position."""
+def write_indel_vcf(f, ref_id, tables, insertions=(), source="", evidence=None):
+    """The second VCF: spec-valid VCF 4.2 records of anchored indels, by position.  With ``evidence`` (the insertion half on)
+    RV is declared for both kinds of record."""
     f.write("##fileformat=VCFv4.2\n##FILTER=<ID=PASS,Description=\"All filters passed\">\n")
     if source:
         f.write("##source=%s\n" % source)
     f.write("##contig=<ID=%s,length=%d>\n" % (ref_id, len(tables.ref)))
-    f.write(INDEL_NOTE + INDEL_INFO_LINES)
+    f.write(INDEL_NOTE + (INDEL_INFO_LINES if evidence is None else INDEL_INFO_LINES.replace(" (deletions only)", "")))
     f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n")
-    f.write("".join(["%s\t%d\t.\t%s\t%s\t.\tPASS\t%s\n" % (ref_id, pos, r, a, info) for pos, r, a, info in indel_records(tables, insertions)]))
+    f.write("".join(["%s\t%d\t.\t%s\t%s\t.\tPASS\t%s\n" % (ref_id, pos, r, a, info) for pos, r, a, info in indel_records(tables, insertions, evidence)]))
+
+
+class IndelTables:
+    """The tables of the indel unit on rank 0 when the insertion half is on: the deletion events' Tables (None with that half
+    off) and the insertion alleles' insevidence.Tables (None when the device table lost events: no join)."""
+
+    def __init__(self, deletion, insertion):
+        self.deletion, self.insertion = deletion, insertion
 
 
 class DeletionReport(Report):
-    """--deletions puts the keys on the VCF; --del_out or --indel_vcf alone switch the hook on too.  The indel VCF takes the
-    call's insertion alleles, so both files are written beside the VCF."""
+    """The indel unit.  --deletions puts the deletion keys on the VCF; --del_out or --indel_vcf alone switch the deletion half
+    on too.  The indel VCF takes the call's insertion alleles, so both files are written beside the VCF.  --insertions puts the
+    insertion keys on the VCF and --ins_out writes the allele table: either switches the insertion half on (insevidence.py),
+    and with it on the insertion rows of the indel VCF carry RV.  With the insertion flags off nothing of that half is called."""
     name, HEADER_LINES, with_calls = "deletion", HEADER_LINES, True
-    outputs = (("indel_vcf_fn", "indel VCF", write_indel_vcf), ("del_out_fn", "deletion events", write_tsv))
+    outputs = (("indel_vcf_fn", "indel VCF", write_indel_vcf), ("del_out_fn", "deletion events", write_tsv),
+               ("ins_out_fn", "insertion alleles", insevidence.write_tsv))
+    ins_lost = 0
 
-    def active(self, run):
+    @staticmethod
+    def del_on(run):
         return bool(run.deletions) or run.del_out_fn is not None or run.indel_vcf_fn is not None
 
+    @staticmethod
+    def ins_on(run):
+        return bool(getattr(run, "insertions", False)) or getattr(run, "ins_out_fn", None) is not None
+
+    def active(self, run):
+        return self.del_on(run) or self.ins_on(run)
+
     def check(self, run):
-        on = self.active(run)
+        on = self.del_on(run)
         if on and not (run.run_variants or run.run_consensus):
             error("A run that only trims has no count table: no deletion events (--deletions, --del_out, --indel_vcf)")
         if run.deletions and not run.run_variants:
@@ -171,27 +194,85 @@ class DeletionReport(Report):
             error("--del_capacity is the log2 of the table's slots, %d to %d: %s" % (abi.DEL_LOG2_MIN, abi.DEL_LOG2_MAX, run.del_capacity))
         if run.indel_vcf_fn is not None and not run.indel_vcf_fn.lower().endswith((".vcf", ".vcf.gz")):
             error("Invalid indel VCF extension (should be .vcf or .vcf.gz): %s" % run.indel_vcf_fn)
+        ins, cap, end = self.ins_on(run), getattr(run, "ins_capacity", None), getattr(run, "ins_end", None)
+        if ins and not (run.run_variants or run.run_consensus):
+            error("A run that only trims has no insertion events: no insertion evidence (--insertions, --ins_out)")
+        if getattr(run, "insertions", False) and not run.run_variants:
+            error("The insertion INFO keys need a VCF (--insertions on variants or aio)")
+        if cap is not None and not ins:
+            error("The insertion evidence table's size (--ins_capacity) needs --insertions or --ins_out")
+        if cap is not None and not abi.INSEV_LOG2_MIN <= cap <= abi.INSEV_LOG2_MAX:
+            error("--ins_capacity is the log2 of the table's slots, %d to %d: %s" % (abi.INSEV_LOG2_MIN, abi.INSEV_LOG2_MAX, cap))
+        if end is not None and not ins:
+            error("The read-end distance of the insertion keys (--ins_end) needs --insertions or --ins_out")
+        if end is not None and end not in insevidence.END_EDGES:
+            error("--ins_end is one of %s: %s" % (", ".join("%d" % e for e in insevidence.END_EDGES), end))
 
     def enable(self, run, eng):
-        eng.del_enable(run.del_capacity or 0)
+        if self.del_on(run):
+            eng.del_enable(run.del_capacity or 0)
+        if self.ins_on(run):
+            eng.insev_enable(run.ins_capacity or 0)
 
     def collect(self, run, eng):
-        events, info = eng.del_events()
-        self.lost = info["lost"]
-        if run.dist is not None:              # every rank's events to rank 0, which sums them per key on the host
-            parts = parallel.gather_objects(run.dist, run.rank, run.world, (events, info))
+        del_tables = None
+        if self.del_on(run):
+            events, info = eng.del_events()
+            self.lost = info["lost"]
+            if run.dist is not None:              # every rank's events to rank 0, which sums them per key on the host
+                parts = parallel.gather_objects(run.dist, run.rank, run.world, (events, info))
+                if run.rank == 0:
+                    events = merge_events([part[0] for part in parts])
+                    self.lost = sum(part[1]["lost"] for part in parts)
             if run.rank == 0:
-                events = merge_events([part[0] for part in parts])
-                self.lost = sum(part[1]["lost"] for part in parts)
-        if run.rank == 0:
-            self.tables = Tables(events, eng.counts(), run.ref_seq, run.v_min_depth, run.v_min_freq)
+                del_tables = Tables(events, eng.counts(), run.ref_seq, run.v_min_depth, run.v_min_freq)
+        if not self.ins_on(run):
+            self.tables = del_tables
+            return
+        # the insertion half: one more gather, issued by every rank whenever the flags are on -- the entries and every allele text
+        # of the rank's share (the call exchanges the texts of the flagged positions only; the join wants them all)
+        entries, info = eng.insev_entries()
+        triples = run.ins_store.counted_pairs()
+        self.ins_lost = info["lost"]
+        if run.dist is not None:
+            parts = parallel.gather_objects(run.dist, run.rank, run.world, (entries, info, triples))
+            if run.rank == 0:
+                entries = insevidence.merge_entries([part[0] for part in parts])
+                self.ins_lost = sum(part[1]["lost"] for part in parts)
+                triples = [t for part in parts for t in part[2]]
+        if run.rank == 0 and not self.ins_lost:  # (a table that lost events cannot meet the store: after() says so)
+            ins_tables = insevidence.Tables(entries, triples, eng.counts(), run.v_min_freq, run.ins_end or insevidence.END_DEFAULT)
+            self.tables = IndelTables(del_tables, ins_tables)
+        elif run.rank == 0:
+            self.tables = IndelTables(del_tables, None)
 
     def annotates(self, run):
         return bool(run.deletions)
 
+    def vcf_tables(self, run):
+        t = self.tables
+        if run.insertions:                        # (in front of the VCF's records: a table that lost events has no keys to give, and
+            check_lost(self.lost)                 # a header that declares keys no record carries is not left behind)
+            insevidence.check_lost(self.ins_lost)
+        if not isinstance(t, IndelTables):
+            return super().vcf_tables(run)
+        d = t.deletion if self.annotates(run) else None
+        i = t.insertion if run.insertions else None
+        return d if i is None else insevidence.IndelInfo(d, i)
+
     def writer_args(self, arg, run, res):
-        more = (insertion_rows(res.records), " ".join(sys.argv)) if arg == "indel_vcf_fn" else ()
-        return (run.ref_id, self.tables) + more
+        t = self.tables
+        d, i = (t.deletion, t.insertion) if isinstance(t, IndelTables) else (t, None)
+        if arg == "indel_vcf_fn":
+            return (run.ref_id, d, insertion_rows(res.records), " ".join(sys.argv)) + ((i,) if i is not None else ())
+        return run.ref_id, (i if arg == "ins_out_fn" else d)
+
+    def write(self, run, res):
+        if self.ins_lost:                         # (no join: the files of the indel unit are not written; every rank's after() raises)
+            check_lost(self.lost)
+            insevidence.check_lost(self.ins_lost)
+        super().write(run, res)
 
     def after(self, run):
         check_lost(self.lost)                 # (behind the run's last collective: no rank is left waiting)
+        insevidence.check_lost(self.ins_lost)

@@ -26,7 +26,7 @@ EXPORTS = [
     "amp_process_batch_device", "amp_sync", "amp_last_kernel_ms", "amp_get_counts", "amp_add_counts",
     "amp_get_ins_events", "amp_counts_device_ptr", "amp_reduce", "amp_reset", "amp_error_reads",
     "amp_reserve_events", "amp_set_kernel_variant", "amp_set_reference", "amp_call_positions",
-    "amp_event_strings", "amp_debug_counters", "amp_call_compact", "amp_debug_blocks", "amp_call_compact_view", "amp_set_timing", "amp_call_compact_begin", "amp_coordinate_helpers", "amp_drain_ins_events", "amp_set_cu_share", "amp_debug_second_grids", "amp_debug_last_second_grids",
+    "amp_event_strings", "amp_debug_counters", "amp_call_compact", "amp_debug_blocks", "amp_call_compact_view", "amp_set_timing", "amp_call_compact_begin", "amp_coordinate_helpers", "amp_drain_ins_events", "amp_set_cu_share", "amp_debug_second_grids", "amp_debug_last_second_grids", "amp_debug_event_capacity",
     "amp_aggregate_ins_events", "amp_fast_path_active", "amp_last_kernel_variant",
     "amp_deflate_blocks", "amp_deflate_blocks_device", "amp_deflate_blocks_device_counted", "amp_deflate_sync", "amp_deflate_blocks_cb",
     "amp_sam_create", "amp_sam_destroy", "amp_sam_set_references", "amp_sam_parse", "amp_sam_reads", "amp_sam_batch_to_host",
@@ -42,6 +42,7 @@ EXPORTS = [
     "amp_amplicon_enable", "amp_amplicon_get", "amp_amplicon_add", "amp_amplicon_last_ms",
     "amp_codon_enable", "amp_codon_get", "amp_codon_add", "amp_codon_last_ms",
     "amp_del_enable", "amp_del_get", "amp_del_add", "amp_del_last_ms",
+    "amp_insev_enable", "amp_insev_get", "amp_insev_add", "amp_insev_last_ms",
     "amp_cooc_enable", "amp_cooc_get", "amp_cooc_add", "amp_cooc_last_ms",
     "amp_errprof_enable", "amp_errprof_get", "amp_errprof_add", "amp_errprof_last_ms",
     "amp_hap_enable", "amp_hap_get", "amp_hap_add", "amp_hap_last_ms",
@@ -187,6 +188,12 @@ class Engine:
 
     def set_timing(self, split):
         self._chk(self.L.amp_set_timing(self.h, C.c_int(1 if split else 0)), "amp_set_timing")
+
+    def debug_event_capacity(self):
+        """Slots per shard the insertion-event list has room for as it stands (amp_debug_event_capacity)."""
+        n = C.c_int64(0)
+        self._chk(self.L.amp_debug_event_capacity(self.h, C.byref(n)), "amp_debug_event_capacity")
+        return int(n.value)
 
     def reserve_events(self, cap):
         self._chk(self.L.amp_reserve_events(self.h, C.c_int64(cap)), "amp_reserve_events")
@@ -454,6 +461,28 @@ class Engine:
 
     def del_last_ms(self):
         return self._hook_last_ms("amp_del_last_ms")
+
+    # ---- insertion alleles: strand, quality and read-position evidence (the insertion half of the indel unit) ----
+    def insev_enable(self, log2_capacity=0):
+        """amp_insev_enable: the half on, the table zero, 2^log2_capacity slots (0: the default).
+        ``insev_disable`` turns it off; the table stays readable.  The deletion half (``del_enable``) is not touched."""
+        self._chk(self.L.amp_insev_enable(self.h, C.c_int(1), C.c_int(int(log2_capacity))), "amp_insev_enable")
+
+    def insev_disable(self):
+        self._chk(self.L.amp_insev_enable(self.h, C.c_int(0), C.c_int(0)), "amp_insev_enable")
+
+    def insev_entries(self):
+        """amp_insev_get -> (abi.INSEV_ENTRY_DTYPE[used] ordered by (ref_pos, len, hash), {"used", "capacity", "lost"})."""
+        return self._keyed_get("amp_insev_get", abi.INSEV_ENTRY_DTYPE, abi.DEL_INFO_FIELDS)
+
+    def insev_add(self, entries):
+        """amp_insev_add: host entries (abi.INSEV_ENTRY_DTYPE) through the kernel's insert path (the merge of partial tables)."""
+        ev = np.ascontiguousarray(entries, abi.INSEV_ENTRY_DTYPE)
+        if ev.size:
+            self._chk(self.L.amp_insev_add(self.h, C.c_void_p(abi.ptr(ev)), C.c_int64(ev.size)), "amp_insev_add")
+
+    def insev_last_ms(self):
+        return self._hook_last_ms("amp_insev_last_ms")
 
     # ---- co-occurrence of listed mutations ---------------------------------------------
     def cooc_enable(self, set_off, site_pos, site_len, site_sym):

@@ -252,6 +252,9 @@ int amp_debug_blocks(amp_ctx *ctx, uint32_t *out, int cap_blocks, int *n_blocks)
 int amp_debug_second_grids(amp_ctx *ctx, int gen_blocks, int heavy_blocks);
 /* ... and the blocks the two were launched with in the ctx's last pass behind a fast kernel (0 before the first). */
 int amp_debug_last_second_grids(amp_ctx *ctx, int *gen_blocks, int *heavy_blocks);
+/* Slots per shard the insertion-event list has room for as it stands (development aid: the tests look at it to see the list
+ * grow between batches). */
+int amp_debug_event_capacity(amp_ctx *ctx, int64_t *per_shard);
 /* Pre-size the insertion-event buffer.  Without it every amp_process_batch* call first runs
  * a small bound kernel and synchronises to size the buffer; with it the call is fully
  * asynchronous and amp_get_ins_events reports AMP_EOVERFLOW if the reservation was short.
@@ -808,6 +811,37 @@ int amp_del_get(amp_ctx *ctx, amp_del_event *entries, int64_t cap, int64_t *n, a
 int amp_del_add(amp_ctx *ctx, const amp_del_event *entries, int64_t n);
 /* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_del_last_ms(amp_ctx *ctx, float *ms);
+
+/* ---- insertion alleles: strand, quality and read-position evidence (opt-in) ---------------------------
+ * The insertion half of the indel unit: it shares the deletion events' place behind the read pass, and either half may be on
+ * alone (amp_del_enable(ctx, 0, ...) switches the deletion half off only).  While it is on, one more kernel behind every
+ * batch's read pass reads the insertion events that THIS batch's pass appended to the event list (whatever the caller's drain
+ * pattern: the list's slot counts are noted in front of the pass) and tallies them per allele: key (ref_pos, len, hash) --
+ * the two values amp_aggregate_ins_events sorts by, so one key is one allele of one position.  Per key: count (events), rev
+ * (those of reads whose FLAG has 0x10), noqual (those of reads with QUAL '*', first byte 0xFF), qsum (the sum of the allele's
+ * quality bytes over the other events) and bin[7]: the events by rp_bin(d) of the read-position tallies, d = max(0,
+ * min(q_from - qs, qe - q_to)) with [qs, qe) the query span of the counted alignment (the trimmed one with do_trim).  The
+ * table is an open-addressed hash table on the device that persists across batches; a key that finds no slot (every probe loop
+ * is bounded) adds its events to `lost` and is dropped -- never merged into another key.  amp_reset zeroes the table. */
+typedef struct amp_insev_entry {
+    int32_t ref_pos, len;       /* the event's position, the allele's bases */
+    uint64_t hash;              /* of the allele's base codes (63 bits) */
+    uint32_t count, rev, noqual;
+    uint64_t qsum;              /* (8-byte aligned: four bytes of padding in front) */
+    uint32_t bin[7];
+} amp_insev_entry;              /* 72 bytes */
+typedef amp_del_info amp_insev_info;        /* used: distinct alleles; lost: EVENTS of keys that found no slot */
+#define AMP_INSEV_STRIDE (512 * 256) /* events the kernel's fixed grid takes in one stride of its loop */
+/* on != 0: the half on, the table zero; 2^log2_capacity slots of 64 bytes (0: the default, 20; else 4 to 28, AMP_EINVAL
+ * otherwise), laid out again only when the capacity changed.  on == 0: off; the table stays readable.  The refusals of
+ * amp_process_batch_device are the deletion half's. */
+int amp_insev_enable(amp_ctx *ctx, int on, int log2_capacity);
+/* The used entries as they stand (waits for the stream), ordered by (ref_pos, len, hash); the rest as amp_del_get. */
+int amp_insev_get(amp_ctx *ctx, amp_insev_entry *entries, int64_t cap, int64_t *n, amp_insev_info *info);
+/* Host entries inserted through the kernel's own insert path (the merge of partial tables): a call per job, not per batch. */
+int amp_insev_add(amp_ctx *ctx, const amp_insev_entry *entries, int64_t n);
+/* Time of the half's kernel behind the last batch; AMP_ESTATE when none ran.  (amp_del_last_ms stays k_del's.) */
+int amp_insev_last_ms(amp_ctx *ctx, float *ms);
 
 /* ---- co-occurrence of listed mutations on single reads (opt-in) ----------------------------------------------
  * Do these listed mutations stand together on the SAME reads?  A set has 1 to 6 sites in strictly increasing position that do not
