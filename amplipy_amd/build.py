@@ -26,14 +26,14 @@ UNIT_DEPS = {"amplihip.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")
                                    "amp_fast5.hpp", "amp_fast6.hpp", "amp_fast7.hpp", "amp_wave.hpp", "amp_heavy.hpp")],
              "amp_ins.hip": [os.path.join(_HERE, "..", "include", "amplihip.h"), os.path.join(CSRC, "amp_ins.hpp")],
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
-             # (amp_hook.hpp: the host shell the nine hooks behind the read pass share; amp_tally.hpp: the device skeleton of the four
-             # windowed tally kernels, and the whole loop of k_strand and k_readpos; amp_keyed.hpp: the keyed table of del and hap)
+             # (amp_hook.hpp: the host shell the ten hooks behind the read pass share; amp_tally.hpp: the device skeleton of the four
+             # windowed tally kernels, and the whole loop of k_strand and k_readpos; amp_keyed.hpp: the keyed table of del, insev and hap)
              "amp_qc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_qc.hpp")],
              "amp_strand.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_tally.hpp")],
              "amp_amplicon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_amplicon.hpp", "amp_tally.hpp")],
              "amp_codon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_codon.hpp", "amp_tally.hpp")],
              "amp_del.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_del.hpp", "amp_keyed.hpp", "amp_tally.hpp")],
-             # (the insertion half of the indel unit: it reads the event list -- amp_ins.hpp -- and takes rp_bin from amp_readpos.hpp)
+             # (the insertion evidence: it reads the event list -- amp_ins.hpp -- and takes rp_bin from amp_readpos.hpp)
              "amp_insev.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_insev.hpp", "amp_keyed.hpp", "amp_ins.hpp", "amp_readpos.hpp", "amp_tally.hpp")],
              "amp_cooc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_cooc.hpp", "amp_tally.hpp")],
              "amp_errprof.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_errprof.hpp", "amp_tally.hpp")],

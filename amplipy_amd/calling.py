@@ -16,7 +16,7 @@ from . import abi
 
 SYMS = abi.SYMBOLS
 # the reports that annotate a VCF record, in the order of their INFO keys on a line and of their header lines: the keywords of
-# vcf_line, CallResult.vcf_text and amplipy.VcfWriter, the names of reports.REGISTRY, HOOK_STRAND .. HOOK_READPOS of amp_hook.hpp
+# vcf_line, CallResult.vcf_text and amplipy.VcfWriter, the names of reports.REGISTRY, HOOK_STRAND .. HOOK_READPOS of amp_hook.hpp (without HOOK_INSEV, which has no report of its own)
 INFO_ORDER = ("strand", "amplicon", "codon", "deletion", "cooc", "errprof", "hap", "readpos")
 
 

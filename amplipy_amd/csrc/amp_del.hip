@@ -50,10 +50,11 @@ __device__ __forceinline__ void del_global_insert(const DelTable &t, uint64_t ke
 struct DelKeys {
     using Word = unsigned long long;
     using Entry = amp_del_event;
+    using Table = DelTable;
     static constexpr int WORDS = 1, LOG2_MIN = DL_LOG2_MIN, LOG2_MAX = DL_LOG2_MAX, LOG2_DEFAULT = DL_LOG2_DEFAULT;
     static constexpr const char *NOUN = "the deletion events' table";
-    static __host__ __device__ void to_key(const Entry &e, Word *key) { key[0] = del_key(e.start, e.len); }
-    static __host__ __device__ Entry to_entry(const Word *key, uint32_t count, uint32_t rev) { return Entry{del_key_start(key[0]), del_key_len(key[0]), count, rev}; }
+    static __device__ void insert(const Table &t, const Entry &e) { del_global_insert(t, del_key(e.start, e.len), e.count, e.rev); }
+    static __device__ void to_entry(const Table &t, uint64_t s, Entry &e) { e = Entry{del_key_start(t.keys[s]), del_key_len(t.keys[s]), t.cnt[2 * s], t.cnt[2 * s + 1]}; }
     static __host__ __device__ bool whole(const Word *key) { return key[0] != DL_EMPTY; }
     static bool less(const Entry &x, const Entry &y) { return x.start != y.start ? x.start < y.start : x.len < y.len; }
     static bool check(const Entry &e, long long k, char *err, size_t cap) {
@@ -61,7 +62,6 @@ struct DelKeys {
         snprintf(err, cap, "deletion event %lld: start %d, length %d", k, e.start, e.len);
         return false;
     }
-    static __device__ void insert(const DelTable &t, const Word *key, uint32_t count, uint32_t rev) { del_global_insert(t, key[0], count, rev); }
 };
 
 // ... into the block's table, or past it when it has no slot within its probe count
@@ -167,28 +167,15 @@ k_del(DelArgs a) {
 
 static DelState *del_state(amp_ctx *c) { return hook_state<DelState>(c, HOOK_DEL); }
 
-// The slot's enqueue: k_del while the deletion half is on, then the insertion half's kernel (amp_insev.hip) while that is
 static int del_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);
     DelState *s = del_state(c);
-    s->timer.timed = false;
-    if (hook_slot(c, HOOK_DEL).halves & 1u)
-        HOOKTRY(hook_launch(q, s, del_hook, rd->n_reads, o, DL_BLOCK, DL_TILES_PER_BLOCK, DL_BLOCKS_PER_CU, [&](unsigned grid) {
-            k_del<<<grid, DL_BLOCK, 0, q.stream>>>(DelArgs{tally_reads(q, rd, o), s->t});
-        }));
-    return insev_enqueue(c, s->more, rd, o);
+    return hook_launch(q, s, del_hook, rd->n_reads, o, DL_BLOCK, DL_TILES_PER_BLOCK, DL_BLOCKS_PER_CU, [&](unsigned grid) {
+        k_del<<<grid, DL_BLOCK, 0, q.stream>>>(DelArgs{tally_reads(q, rd, o), s->t});
+    });
 }
 
-// The slot's state for the insertion half to hang its own on: made here, without a table, when the deletion half was never
-// enabled (amp_del_get and amp_del_add answer AMP_ESTATE as before the first enable: the table has no keys)
-int indel_slot_state(amp_ctx *c, HookState **out) {
-    DelState *s = del_state(c);
-    if (!s) HOOKTRY(hook_new_state(ctx_hook(c), hook_slot(c, HOOK_DEL), del_hook, s, [](DelState &) -> int { return AMP_OK; }));
-    *out = s;
-    return AMP_OK;
-}
-
-HookOps del_hook = {"the deletion events need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, del_enqueue, hook_free<DelState>, insev_before_pass};
+HookOps del_hook = {"the deletion events need", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, del_enqueue, hook_free<DelState>};
 
 }  // namespace amp
 
@@ -200,21 +187,18 @@ int amp_del_enable(amp_ctx *c, int on, int log2_capacity) {
     if (!c) return AMP_EINVAL;
     const HookCtx q = ctx_hook(c);
     HookSlot &slot = hook_slot(c, HOOK_DEL);
-    if (!on) { hook_half(slot, 0, false); return AMP_OK; }
+    if (!on) { slot.on = false; return AMP_OK; }
     HOOKTRY(keyed_capacity<DelKeys>(q, log2_capacity));
     Guard g(q.device);
     DelState *s = del_state(c);
+    const auto layout = [&](DelState &f) -> int { return keyed_layout(q, f, f.t, (uint32_t)log2_capacity); };
     if (!s) {
-        HOOKTRY(hook_new_state(q, slot, del_hook, s, [&](DelState &f) -> int { return keyed_layout(q, f, f.t, (uint32_t)log2_capacity); }));
+        HOOKTRY(hook_new_state(q, slot, del_hook, s, layout));
     } else if (s->t.log2_capacity != (uint32_t)log2_capacity) {
-        // another capacity: the table is laid out again (a kernel on the old one may still be in flight)
-        hook_half(slot, 0, false);
-        HOOKCHK(q, hipStreamSynchronize(q.stream));
-        hook_release(*s);
-        HOOKTRY(keyed_layout(q, *s, s->t, (uint32_t)log2_capacity));
+        HOOKTRY(keyed_relayout(q, slot, *s, layout));
     }
     HOOKTRY(hook_zero(q, *s));
-    hook_half(slot, 0, true);
+    slot.on = true;
     return AMP_OK;
 }
 

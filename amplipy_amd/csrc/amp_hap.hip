@@ -60,21 +60,17 @@ __device__ __forceinline__ void hap_global_insert(const HapTable &t, const uint3
 struct HapKeys {
     using Word = uint32_t;
     using Entry = amp_hap_entry;
+    using Table = HapTable;
     static constexpr int WORDS = HP_KEY_WORDS, LOG2_MIN = HP_LOG2_MIN, LOG2_MAX = HP_LOG2_MAX, LOG2_DEFAULT = HP_LOG2_DEFAULT;
     static constexpr const char *NOUN = "the haplotype table";
     int32_t n_regions;                          // (of the state: what check holds an entry's region to)
-    static __host__ __device__ void to_key(const Entry &e, Word *key) {
-        key[0] = e.head;
-#pragma unroll
-        for (int w = 1; w < HP_KEY_WORDS; ++w) key[w] = e.diff[w - 1];
-    }
-    static __host__ __device__ Entry to_entry(const Word *key, uint32_t count, uint32_t rev) {
-        Entry e;
+    static __device__ void insert(const Table &t, const Entry &e) { hap_global_insert(t, &e.head, hap_hash(&e.head), e.count, e.rev); }
+    static __device__ void to_entry(const Table &t, uint64_t s, Entry &e) {
+        const Word *key = t.keys + (size_t)s * HP_KEY_WORDS;
         e.head = key[0];
 #pragma unroll
         for (int w = 1; w < HP_KEY_WORDS; ++w) e.diff[w - 1] = key[w];
-        e.count = count; e.rev = rev;
-        return e;
+        e.count = t.cnt[2 * s]; e.rev = t.cnt[2 * s + 1];
     }
     static __host__ __device__ bool whole(const Word *key) { return key[HP_KEY_WORDS - 1] != HP_EMPTY; }     // (the last word is written last)
     static bool less(const Entry &x, const Entry &y) { return hap_key_less(&x.head, &y.head); }
@@ -84,7 +80,6 @@ struct HapKeys {
         snprintf(err, cap, "haplotype entry %lld: region %u of %d, %u differences", k, region, n_regions, nd);
         return false;
     }
-    static __device__ void insert(const HapTable &t, const Word *key, uint32_t count, uint32_t rev) { hap_global_insert(t, key, hap_hash(key), count, rev); }
 };
 
 __global__ void __launch_bounds__(HP_BLOCK)

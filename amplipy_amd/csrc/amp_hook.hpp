@@ -1,11 +1,12 @@
 // amp_hook.hpp -- the host shell of the opt-in kernels that run behind every batch's read pass: the QC
 // report (amp_qc.hip), the strand tallies (amp_strand.hip), the per-amplicon counts (amp_amplicon.hip), the codon tallies
-// (amp_codon.hip), the deletion events (amp_del.hip), the co-occurrence tallies (amp_cooc.hip), the error profile (amp_errprof.hip), the read haplotypes (amp_hap.hip), the read-position tallies (amp_readpos.hip).  What a hook needs to know of a ctx, and what the hooks have in common -- the check macro, the device
+// (amp_codon.hip), the deletion events (amp_del.hip), the insertion evidence (amp_insev.hip), the co-occurrence tallies (amp_cooc.hip), the error profile (amp_errprof.hip), the read haplotypes (amp_hap.hip), the read-position tallies (amp_readpos.hip).  What a hook needs to know of a ctx, and what the hooks have in common -- the check macro, the device
 // guard, the timer round a launch, the grid rule, the merge of host tables, the check of a trimming pass's results, the common
 // part of a state and its construction, the record of what a state owns on the device with free, reset, get and add written
 // from it, the frame of an enqueue, last_ms -- each once.  (What the three tally kernels share
 // on the device is amp_tally.hpp.)  amp_ctx (amp_ctx.hpp) keeps one slot (switch, state) per hook and amplihip.hip walks the
-// table of HookOps; a unit keeps its state, its kernels and what it enables.
+// table of HookOps; a unit keeps its state, its kernels and what it enables, and no unit knows of another: nothing of one
+// unit's is declared here but its HookOps.
 #pragma once
 
 #ifdef __HIPCC__
@@ -61,18 +62,12 @@ struct HookCtx {
 HookCtx ctx_hook(amp_ctx *c);
 
 // The hooks; the numeric order is the order their kernels run in behind the read pass.
-enum { HOOK_QC, HOOK_STRAND, HOOK_AMPLICON, HOOK_CODON, HOOK_DEL, HOOK_COOC, HOOK_ERRPROF, HOOK_HAP, HOOK_READPOS, N_HOOKS };
+enum { HOOK_QC, HOOK_STRAND, HOOK_AMPLICON, HOOK_CODON, HOOK_DEL, HOOK_INSEV, HOOK_COOC, HOOK_ERRPROF, HOOK_HAP, HOOK_READPOS, N_HOOKS };
 struct HookSlot {
     bool on;                    // the switch amplihip.hip reads per batch
     void *state;                // the hook's device state, owned by its unit; it outlives the switch (tables stay readable)
-    uint8_t halves;             // a slot of two halves (HOOK_DEL: bit 0 the deletion events, bit 1 the insertion evidence): `on` is their OR
 };
 HookSlot &hook_slot(amp_ctx *c, int which);
-// One half's switch of a slot that carries two
-inline void hook_half(HookSlot &slot, int half, bool on) {
-    slot.halves = (uint8_t)(on ? slot.halves | (1u << half) : slot.halves & ~(1u << half));
-    slot.on = slot.halves != 0;
-}
 
 // The results of a trimming pass (the fields of amp_trim_out, in its order) a hook's kernel reads.
 enum : uint32_t { OUT_NEW_POS = 1u, OUT_NEW_NCIG = 2u, OUT_NEW_CIG = 4u, OUT_REF_LEN = 8u, OUT_TRIM_FLAGS = 16u, OUT_STATUS = 32u };
@@ -88,17 +83,7 @@ struct HookOps {
 };
 // One per unit; amplihip.hip keeps them in enum order.  (Not const objects, though nothing writes them: hipcc emits a const
 // object with a constant initialiser into the device image as well, host function pointers and all.)
-extern HookOps qc_hook, strand_hook, amplicon_hook, codon_hook, del_hook, cooc_hook, errprof_hook, hap_hook, readpos_hook;
-
-// What the two halves of HOOK_DEL's slot ask of each other.  amp_insev.hip: del_hook's before_pass -- while the insertion
-// half is on, the event list's slot counts as they stand become the half's cursor: what the pass appends behind them is this
-// batch's; nothing is enqueued while the half is off -- and its kernel behind the pass while its half is on (`more`: the
-// half's state, null before its first enable).  amp_del.hip: the slot's state, made without a table when the deletion half
-// was never enabled.
-struct HookState;
-int insev_before_pass(amp_ctx *c, uint64_t read_base);
-int insev_enqueue(amp_ctx *c, HookState *more, const amp_dev_reads *rd, const amp_trim_out *dev_out);
-int indel_slot_state(amp_ctx *c, HookState **state);
+extern HookOps qc_hook, strand_hook, amplicon_hook, codon_hook, del_hook, insev_hook, cooc_hook, errprof_hook, hap_hook, readpos_hook;
 
 // With trimming on, every result in `needs` must be there; otherwise the refusal is in q.err.  amplihip.hip asks in front of a
 // device batch's read pass, so that a refused call changes nothing; an enqueue asks again.
@@ -183,8 +168,6 @@ struct HookState {
     Owned owned[8] = {};
     Table table[4] = {};
     int n_owned = 0, n_table = 0;
-    HookState *more = nullptr;              // the state of the slot's second half (amp_insev.hip behind amp_del.hip), with what frees it:
-    void (*free_more)(void *) = nullptr;    // amp_reset zeroes it and the slot's free takes it along; nothing else follows the link
 };
 template <class S> S *hook_state_of(void *state) { return static_cast<S *>(static_cast<HookState *>(state)); }
 template <class S> S *hook_state(amp_ctx *c, int which) { return hook_state_of<S>(hook_slot(c, which).state); }
@@ -215,7 +198,6 @@ template <class S>
 void hook_free(void *state) {
     S *s = hook_state_of<S>(state);
     if (!s) return;
-    if (s->more) s->free_more(s->more);
     hook_release(*s);
     s->timer.destroy();
     delete s;

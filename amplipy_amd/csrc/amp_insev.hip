@@ -1,10 +1,10 @@
 // amp_insev.hip -- insertion alleles: strand, quality and read-position evidence, tallied on the device (DESIGN.md section 19b;
 // C ABI: the amp_insev_* entry points of amplihip.h; what one event contributes: amp_insev.hpp).
 //
-// The insertion half of the indel unit: it has no slot of its own behind the read pass but shares HOOK_DEL's (amp_hook.hpp:
-// hook_half), and del_hook's enqueue (amp_del.hip) calls insev_enqueue behind k_del.  k_insev reads the entries that THIS
-// batch's read pass appended to the event list.  Which ones: in front of every pass, while the half is on, k_insev_mark copies
-// the eight shards' slot counters into the half's cursor (insev_before_pass, del_hook's before_pass); behind the pass the entries between cursor and
+// A hook like the others (amp_hook.hpp), in the slot directly behind the deletion events': k_insev runs behind k_del and in
+// front of k_cooc, and the two units know nothing of each other (the host report drives both: deletion.py).  k_insev reads the
+// entries that THIS batch's read pass appended to the event list.  Which ones: in front of every pass, while the hook is on,
+// k_insev_mark copies the eight shards' slot counters into the state's cursor (insev_before_pass, the one before_pass among the hooks); behind the pass the entries between cursor and
 // counter are the batch's -- whether the caller drains per batch or never, whether amp_reset came in between, and wherever
 // grow_events has moved the regions (the cursor holds indices, and the list is taken from the ctx behind the pass).  The
 // number of events is known on the device only, so the grid is fixed (IE_GRID blocks) and every wave strides over the slots, an
@@ -17,19 +17,18 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include <algorithm>
-
 #include "amp_hook.hpp"
 #include "amp_insev.hpp"
 #include "amp_tally.hpp"
 
 namespace amp {
 
-using InsevTable = KeyedTable<unsigned long long, 2>;       // the keys, (count, rev) and info (amp_keyed.hpp); the other cells: InsevSide[slot]
+struct InsevTable : KeyedTable<unsigned long long, 2> {     // the keys, (count, rev) and info (amp_keyed.hpp), and a slot's other cells:
+    InsevSide *side;                                        // [capacity], an allocation of its own
+};
 
 struct InsevState : HookState {
-    InsevTable t = {nullptr, nullptr, nullptr, 0u};
-    InsevSide *side = nullptr;                  // [capacity]
+    InsevTable t = {};
     unsigned long long *cursor = nullptr;       // [8]: the shards' slot counts in front of the batch's read pass
     uint64_t read_base = 0;                     // of that pass
     bool marked = false;                        // the cursor is this batch's
@@ -42,7 +41,6 @@ struct InsevArgs {
     long long cap;
     const unsigned long long *ev_n, *cursor;
     InsevTable t;
-    InsevSide *side;
 };
 
 __global__ void k_insev_mark(unsigned long long *cursor, const unsigned long long *ev_n) {
@@ -51,8 +49,8 @@ __global__ void k_insev_mark(unsigned long long *cursor, const unsigned long lon
 
 // One key's cells into the table: the slot claimed word by word, then the adds (agent scope: HIP's default).  `count` events
 // are lost when no slot takes the key.
-__device__ __forceinline__ void insev_insert(const InsevTable &t, InsevSide *side, const uint64_t *key, uint32_t count, uint32_t rev, uint32_t noqual,
-                                             unsigned long long qsum, const uint32_t *bin) {
+__device__ __forceinline__ void insev_insert(const InsevTable &t, const uint64_t *key, uint32_t count, uint32_t rev, uint32_t noqual, unsigned long long qsum,
+                                             const uint32_t *bin) {
     bool fresh;
     const int64_t s = insev_probe(key, keyed_slot(insev_hash(key), t.log2_capacity), (1u << t.log2_capacity) - 1u, keyed_probes(t.log2_capacity),
                                   [&](uint32_t slot, int w, uint64_t v) {
@@ -60,7 +58,7 @@ __device__ __forceinline__ void insev_insert(const InsevTable &t, InsevSide *sid
                                   }, fresh);
     keyed_tally(t, s, fresh, count, rev);
     if (s < 0) return;
-    InsevSide &c = side[s];
+    InsevSide &c = t.side[s];
     if (noqual) atomicAdd(&c.noqual, noqual);
     if (qsum) atomicAdd(&c.qsum, qsum);
 #pragma unroll
@@ -119,53 +117,49 @@ k_insev(InsevArgs a) {
 #pragma unroll
             for (int b = 0; b < IE_BINS; ++b) g_bin[b] = (uint32_t)__popcll(same & bins[b]);
         });
-        if (leader) insev_insert(a.t, a.side, key, g_count, g_rev, g_noqual, g_qsum, g_bin);       // (a leader's own key is its group's)
+        if (leader) insev_insert(a.t, key, g_count, g_rev, g_noqual, g_qsum, g_bin);       // (a leader's own key is its group's)
     }
 }
 
-// host entries through the kernel's insert
-__global__ void k_insev_add(InsevTable t, InsevSide *side, const amp_insev_entry *ev, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const amp_insev_entry e = ev[i];
-    const uint64_t key[2] = {((uint64_t)(uint32_t)e.ref_pos << 32) | (uint64_t)(uint32_t)e.len, e.hash};
-    insev_insert(t, side, key, e.count, e.rev, e.noqual, (unsigned long long)e.qsum, e.bin);
-}
-
-// the used slots, in no order
-__global__ void k_insev_compact(InsevTable t, const InsevSide *side, amp_insev_entry *out, unsigned long long *n_out, uint64_t cap_out) {
-    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= (1ull << t.log2_capacity)) return;
-    const unsigned long long *key = t.keys + (size_t)s * 2;
-    if (key[1] == IE_EMPTY) return;             // (the last word is written last: the slot holds all of a key)
-    const uint64_t at = atomicAdd(n_out, 1ull);
-    if (at >= cap_out) return;
-    amp_insev_entry &e = out[at];               // (field by field into the zeroed array: the entry's padding stays zero)
-    e.ref_pos = (int32_t)(uint32_t)(key[0] >> 32); e.len = (int32_t)(uint32_t)key[0]; e.hash = key[1];
-    e.count = t.cnt[2 * s]; e.rev = t.cnt[2 * s + 1]; e.noqual = side[s].noqual; e.qsum = side[s].qsum;
-    for (int b = 0; b < IE_BINS; ++b) e.bin[b] = side[s].bin[b];
-}
-
-struct InsevKeys {      // (what keyed_capacity is told)
-    static constexpr int LOG2_MIN = IE_LOG2_MIN, LOG2_MAX = IE_LOG2_MAX, LOG2_DEFAULT = IE_LOG2_DEFAULT;
+// What amp_keyed.hpp is told about the table: an entry carries the side array's cells next to (count, rev)
+struct InsevKeys {
+    using Word = unsigned long long;
+    using Entry = amp_insev_entry;
+    using Table = InsevTable;
+    static constexpr int WORDS = 2, LOG2_MIN = IE_LOG2_MIN, LOG2_MAX = IE_LOG2_MAX, LOG2_DEFAULT = IE_LOG2_DEFAULT;
     static constexpr const char *NOUN = "the insertion evidence table";
+    static __device__ void insert(const Table &t, const Entry &e) {
+        const uint64_t key[2] = {((uint64_t)(uint32_t)e.ref_pos << 32) | (uint64_t)(uint32_t)e.len, e.hash};
+        insev_insert(t, key, e.count, e.rev, e.noqual, (unsigned long long)e.qsum, e.bin);
+    }
+    static __device__ void to_entry(const Table &t, uint64_t s, Entry &e) {       // (field by field: the zeroed entry's padding stays zero)
+        const Word *key = t.keys + (size_t)s * 2;
+        e.ref_pos = (int32_t)(uint32_t)(key[0] >> 32); e.len = (int32_t)(uint32_t)key[0]; e.hash = key[1];
+        e.count = t.cnt[2 * s]; e.rev = t.cnt[2 * s + 1]; e.noqual = t.side[s].noqual; e.qsum = t.side[s].qsum;
+        for (int b = 0; b < IE_BINS; ++b) e.bin[b] = t.side[s].bin[b];
+    }
+    static __host__ __device__ bool whole(const Word *key) { return key[1] != IE_EMPTY; }       // (the last word is written last)
+    static bool less(const Entry &x, const Entry &y) { return x.ref_pos != y.ref_pos ? x.ref_pos < y.ref_pos : x.len != y.len ? x.len < y.len : x.hash < y.hash; }
+    static bool check(const Entry &e, long long k, char *err, size_t cap) {
+        if (e.ref_pos >= 0 && e.len >= 0 && !(e.hash >> 63)) return true;
+        snprintf(err, cap, "insertion evidence entry %lld: position %d, length %d, hash %llx", k, e.ref_pos, e.len, (unsigned long long)e.hash);
+        return false;
+    }
 };
 
-static HookSlot &insev_slot(amp_ctx *c) { return hook_slot(c, HOOK_DEL); }
-static InsevState *insev_state(amp_ctx *c) {
-    HookState *s = (HookState *)insev_slot(c).state;
-    return s ? static_cast<InsevState *>(s->more) : nullptr;
-}
+static InsevState *insev_state(amp_ctx *c) { return hook_state<InsevState>(c, HOOK_INSEV); }
 
 static int insev_layout(const HookCtx &q, InsevState &f, uint32_t log2_capacity) {
     const size_t cap = (size_t)1 << log2_capacity;
+    f.t.side = nullptr; f.cursor = nullptr;
     HOOKTRY(keyed_layout(q, f, f.t, log2_capacity));
-    HOOKTRY(hook_alloc(q, f, &f.side, cap * sizeof(InsevSide), cap * sizeof(InsevSide)));
+    HOOKTRY(hook_alloc(q, f, &f.t.side, cap * sizeof(InsevSide), cap * sizeof(InsevSide)));
     return hook_alloc(q, f, &f.cursor, 64, 64);
 }
 
-int insev_before_pass(amp_ctx *c, uint64_t read_base) {
-    if (!(insev_slot(c).halves & 2u)) return AMP_OK;
+// In FRONT of the read pass, while the hook is on: the event list's slot counts as they stand become the cursor -- what the
+// pass appends behind them is this batch's
+static int insev_before_pass(amp_ctx *c, uint64_t read_base) {
     const HookCtx q = ctx_hook(c);
     InsevState *s = insev_state(c);
     if (!s) return AMP_ESTATE;
@@ -176,24 +170,20 @@ int insev_before_pass(amp_ctx *c, uint64_t read_base) {
     return AMP_OK;
 }
 
-int insev_enqueue(amp_ctx *c, HookState *more, const amp_dev_reads *rd, const amp_trim_out *o) {
-    InsevState *s = static_cast<InsevState *>(more);
-    if (s) s->timer.timed = false;
-    if (!(insev_slot(c).halves & 2u)) return AMP_OK;
-    if (!s) return AMP_ESTATE;
-    const bool marked = s->marked;
-    s->marked = false;
-    if (rd->n_reads <= 0) return AMP_OK;
+static int insev_enqueue(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_out *o) {
     const HookCtx q = ctx_hook(c);              // (behind the pass: the list where grow_events has left it)
-    if (!marked) { snprintf(q.err, q.err_cap, "the insertion evidence: no mark in front of this read pass"); return AMP_ESTATE; }
-    HOOKTRY(hook_check_out(q, o, del_hook));
-    HOOKCHK(q, s->timer.begin(q.stream));
-    if (q.events && q.ev_cap > 0)
-        k_insev<<<IE_GRID, IE_BLOCK, 0, q.stream>>>(InsevArgs{tally_reads(q, rd, o), s->read_base, q.events, q.ev_cap, q.ev_n, s->cursor, s->t, s->side});
-    HOOKCHK(q, hipGetLastError());
-    HOOKCHK(q, s->timer.end(q.stream));
-    return AMP_OK;
+    InsevState *s = insev_state(c);
+    const bool marked = s->marked;
+    s->marked = s->timer.timed = false;
+    if (rd->n_reads > 0 && !marked) { snprintf(q.err, q.err_cap, "the insertion evidence: no mark in front of this read pass"); return AMP_ESTATE; }
+    // (the grid is fixed, whatever the batch: the number of events is known on the device only)
+    return hook_launch(q, s, insev_hook, rd->n_reads, o, IE_BLOCK, 1, 1, [&](unsigned) {
+        if (q.events && q.ev_cap > 0)
+            k_insev<<<IE_GRID, IE_BLOCK, 0, q.stream>>>(InsevArgs{tally_reads(q, rd, o), s->read_base, q.events, q.ev_cap, q.ev_n, s->cursor, s->t});
+    });
 }
+
+HookOps insev_hook = {"the insertion evidence needs", OUT_NEW_POS | OUT_NEW_NCIG | OUT_NEW_CIG | OUT_STATUS, insev_enqueue, hook_free<InsevState>, insev_before_pass};
 
 }  // namespace amp
 
@@ -204,101 +194,37 @@ extern "C" {
 int amp_insev_enable(amp_ctx *c, int on, int log2_capacity) {
     if (!c) return AMP_EINVAL;
     const HookCtx q = ctx_hook(c);
-    HookSlot &slot = insev_slot(c);
-    if (!on) { hook_half(slot, 1, false); return AMP_OK; }
+    HookSlot &slot = hook_slot(c, HOOK_INSEV);
+    if (!on) { slot.on = false; return AMP_OK; }
     HOOKTRY(keyed_capacity<InsevKeys>(q, log2_capacity));
     Guard g(q.device);
-    HookState *shell = nullptr;
-    HOOKTRY(indel_slot_state(c, &shell));
-    InsevState *s = static_cast<InsevState *>(shell->more);
+    InsevState *s = insev_state(c);
+    const auto layout = [&](InsevState &f) -> int { return insev_layout(q, f, (uint32_t)log2_capacity); };
     if (!s) {
-        // (the half's state hangs on the slot's; hook_new_state wants a slot to hand it to: one of its own, for the call)
-        HookSlot mine = {false, nullptr, 0};
-        static HookOps ops = {"the insertion evidence needs", 0u, nullptr, hook_free<InsevState>, nullptr};
-        HOOKTRY(hook_new_state(q, mine, ops, s, [&](InsevState &f) -> int { return insev_layout(q, f, (uint32_t)log2_capacity); }));
-        shell->more = s; shell->free_more = hook_free<InsevState>;
+        HOOKTRY(hook_new_state(q, slot, insev_hook, s, layout));
     } else if (s->t.log2_capacity != (uint32_t)log2_capacity) {
-        // another capacity: the table is laid out again (a kernel on the old one may still be in flight)
-        hook_half(slot, 1, false);
-        HOOKCHK(q, hipStreamSynchronize(q.stream));
-        hook_release(*s);
-        s->t = InsevTable{nullptr, nullptr, nullptr, 0u}; s->side = nullptr; s->cursor = nullptr;
-        HOOKTRY(insev_layout(q, *s, (uint32_t)log2_capacity));
+        HOOKTRY(keyed_relayout(q, slot, *s, layout));
     }
     HOOKTRY(hook_zero(q, *s));
     s->marked = false;
-    hook_half(slot, 1, true);
+    slot.on = true;
     return AMP_OK;
 }
 
 int amp_insev_get(amp_ctx *c, amp_insev_entry *entries, int64_t cap, int64_t *n, amp_insev_info *info) {
     if (!c || cap < 0) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
     InsevState *s = insev_state(c);
     if (!s || !s->t.keys) return AMP_ESTATE;
-    const InsevTable &t = s->t;
-    Guard g(q.device);
-    unsigned long long h[2] = {0ull, 0ull};
-    HOOKCHK(q, hipMemcpyAsync(h, t.info, sizeof(h), hipMemcpyDeviceToHost, q.stream));
-    HOOKCHK(q, hipStreamSynchronize(q.stream));
-    if (info) { info->used = h[0]; info->capacity = 1ull << t.log2_capacity; info->lost = h[1]; }
-    if (n) *n = (int64_t)h[0];
-    if ((uint64_t)cap < h[0] || (h[0] && !entries)) {
-        snprintf(q.err, q.err_cap, "%s holds %llu entries, the array given %lld", InsevKeys::NOUN, h[0], (long long)cap);
-        return AMP_EINVAL;
-    }
-    if (!h[0]) return AMP_OK;
-    amp_insev_entry *d_out = nullptr;
-    HOOKCHK(q, hipMalloc((void **)&d_out, (size_t)h[0] * sizeof(amp_insev_entry)));
-    unsigned long long *d_n = t.info + 2;                          // (inside the allocation's last 64 bytes)
-    const int rc = [&]() -> int {
-        HOOKCHK(q, hipMemsetAsync(d_out, 0, (size_t)h[0] * sizeof(amp_insev_entry), q.stream));      // (the entries' padding, too)
-        HOOKCHK(q, hipMemsetAsync(d_n, 0, 8, q.stream));
-        const uint64_t slots = 1ull << t.log2_capacity;
-        k_insev_compact<<<(unsigned)((slots + 255) / 256), 256, 0, q.stream>>>(t, s->side, d_out, d_n, h[0]);
-        HOOKCHK(q, hipGetLastError());
-        HOOKCHK(q, hipMemcpyAsync(entries, d_out, (size_t)h[0] * sizeof(amp_insev_entry), hipMemcpyDeviceToHost, q.stream));
-        HOOKCHK(q, hipStreamSynchronize(q.stream));
-        return AMP_OK;
-    }();
-    (void)hipFree(d_out);
-    if (rc == AMP_OK)
-        std::sort(entries, entries + h[0], [](const amp_insev_entry &x, const amp_insev_entry &y) {
-            return x.ref_pos != y.ref_pos ? x.ref_pos < y.ref_pos : x.len != y.len ? x.len < y.len : x.hash < y.hash;
-        });
-    return rc;
+    return keyed_get<InsevKeys>(ctx_hook(c), s->t, entries, cap, n, info);
 }
 
 int amp_insev_add(amp_ctx *c, const amp_insev_entry *entries, int64_t n) {
     if (!c || n < 0 || (n && !entries)) return AMP_EINVAL;
-    const HookCtx q = ctx_hook(c);
     InsevState *s = insev_state(c);
     if (!s || !s->t.keys) return AMP_ESTATE;
-    for (int64_t k = 0; k < n; ++k) {
-        const amp_insev_entry &e = entries[k];
-        if (e.ref_pos >= 0 && e.len >= 0 && !(e.hash >> 63)) continue;
-        snprintf(q.err, q.err_cap, "insertion evidence entry %lld: position %d, length %d, hash %llx", (long long)k, e.ref_pos, e.len, (unsigned long long)e.hash);
-        return AMP_EINVAL;
-    }
-    if (!n) return AMP_OK;
-    Guard g(q.device);
-    amp_insev_entry *d_in = nullptr;
-    HOOKCHK(q, hipMalloc((void **)&d_in, (size_t)n * sizeof(amp_insev_entry)));
-    const int rc = [&]() -> int {
-        HOOKCHK(q, hipMemcpyAsync(d_in, entries, (size_t)n * sizeof(amp_insev_entry), hipMemcpyHostToDevice, q.stream));
-        k_insev_add<<<(unsigned)((n + 255) / 256), 256, 0, q.stream>>>(s->t, s->side, d_in, n);
-        HOOKCHK(q, hipGetLastError());
-        HOOKCHK(q, hipStreamSynchronize(q.stream));
-        return AMP_OK;
-    }();
-    (void)hipFree(d_in);
-    return rc;
+    return keyed_add(ctx_hook(c), s->t, InsevKeys{}, entries, n);
 }
 
-int amp_insev_last_ms(amp_ctx *c, float *ms) {
-    if (!c) return AMP_EINVAL;
-    InsevState *s = insev_state(c);
-    return s ? s->timer.last_ms(ctx_hook(c), ms) : AMP_ESTATE;
-}
+int amp_insev_last_ms(amp_ctx *c, float *ms) { return hook_last_ms(c, HOOK_INSEV, ms); }
 
 }  // extern "C"

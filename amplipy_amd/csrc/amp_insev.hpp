@@ -154,4 +154,4 @@ AMP_ST_HD size_t insev_span_at(const InsevSpan &M, int64_t j) {
 }
 
 }  // namespace amp
-// (the kernel is part of del_hook's enqueue, amp_del.hip: the insertion half of the indel unit, declared in amp_hook.hpp)
+// (the hook amplihip.hip runs behind the read pass is insev_hook of amp_insev.hip, declared in amp_hook.hpp)

@@ -1,13 +1,16 @@
-// amp_keyed.hpp -- the keyed table in HBM that the deletion events (amp_del.hip) and the read haplotypes (amp_hap.hip) tally
-// into: open addressing, linear probing, a bounded probe count.  One allocation: keys[capacity] of N
-// words of type W (all ones: free), then cnt[capacity][2] (count, rev), then info[2] (used slots, lost reads), then the rest of
-// a 64-byte tail, where the compaction keeps its counter.  Which slot a hash starts at and how many slots an insert tries are
-// plain functions (the hostsim twins call them); the table, its layout, the two helper kernels and the host halves of get and
-// add are written once over a unit's traits type T:
-//   Word, WORDS, Entry (of the ABI)     to_key(entry, key)  to_entry(key, count, rev)  whole(key): the slot holds all of a key
+// amp_keyed.hpp -- the keyed table in HBM that the deletion events (amp_del.hip), the insertion evidence (amp_insev.hip) and the
+// read haplotypes (amp_hap.hip) tally into: open addressing, linear probing, a bounded probe count.  One
+// allocation: keys[capacity] of N words of type W (all ones: free), then cnt[capacity][2] (count, rev), then info[2] (used slots,
+// lost reads), then the rest of a 64-byte tail, where the compaction keeps its counter.  Which slot a hash starts at and how
+// many slots an insert tries are plain functions (the hostsim twins call them); the table, its layout, the two helper kernels,
+// the host side of get and add and the way to another capacity are written once over a unit's traits type T:
+//   Word, WORDS, Entry (of the ABI)     Table: what the kernels are handed -- KeyedTable<Word, WORDS>, or a struct that derives from
+//   it and adds what a slot carries beside (count, rev)                          whole(key): the slot holds all of a key
+//   insert(table, entry): the unit's device insert of a host entry     to_entry(table, slot, entry): a used slot into a zeroed entry
 //   less(entry, entry): the order get returns       check(entry, k, err, cap): a host entry of add, false with its message
-//   NOUN, LOG2_MIN, LOG2_MAX, LOG2_DEFAULT          insert(table, key, count, rev): the unit's device insert
-// The probe loops stay with their units: del_probe claims a key with one 64-bit compare-and-swap, hap_probe word by word.
+//   NOUN, LOG2_MIN, LOG2_MAX, LOG2_DEFAULT
+// The probe loops stay with their units: del_probe claims a key with one 64-bit compare-and-swap, hap_probe and insev_probe
+// word by word.
 #pragma once
 
 #include <stdint.h>
@@ -36,7 +39,6 @@ struct KeyedTable {                             // the table as a kernel is hand
     unsigned long long *info;                   // [2]: used slots, lost reads
     uint32_t log2_capacity;
 };
-template <class T> using KeyedTableOf = KeyedTable<typename T::Word, T::WORDS>;
 
 // The end of an insert into the table: s is the key's slot (fresh: this insert took it), or negative when it found none
 template <class W, int N>
@@ -49,24 +51,19 @@ __device__ __forceinline__ void keyed_tally(const KeyedTable<W, N> &t, int64_t s
 
 // host entries through the unit's insert path
 template <class T>
-__global__ void k_keyed_add(KeyedTableOf<T> t, const typename T::Entry *ev, int64_t n) {
+__global__ void k_keyed_add(typename T::Table t, const typename T::Entry *ev, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const typename T::Entry e = ev[i];
-    typename T::Word key[T::WORDS];
-    T::to_key(e, key);
-    T::insert(t, key, e.count, e.rev);
+    if (i < n) T::insert(t, ev[i]);
 }
 
-// the used slots, in no order
+// the used slots, in no order, into a zeroed array (the unit fills an entry field by field: its padding stays zero)
 template <class T>
-__global__ void k_keyed_compact(KeyedTableOf<T> t, typename T::Entry *out, unsigned long long *n_out, uint64_t cap_out) {
+__global__ void k_keyed_compact(typename T::Table t, typename T::Entry *out, unsigned long long *n_out, uint64_t cap_out) {
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= (1ull << t.log2_capacity)) return;
-    const typename T::Word *key = t.keys + (size_t)s * T::WORDS;
-    if (!T::whole(key)) return;
+    if (!T::whole(t.keys + (size_t)s * T::WORDS)) return;
     const uint64_t at = atomicAdd(n_out, 1ull);
-    if (at < cap_out) out[at] = T::to_entry(key, t.cnt[2 * s], t.cnt[2 * s + 1]);
+    if (at < cap_out) T::to_entry(t, s, out[at]);
 }
 
 // log2_capacity as enable was given it: 0 is the default; outside the range the refusal is in q.err
@@ -90,10 +87,20 @@ int keyed_layout(const HookCtx &q, HookState &s, KeyedTable<W, N> &t, uint32_t l
     return AMP_OK;
 }
 
+// amp_*_enable at another capacity than the state's: the hook is switched off, what is in flight on the old tables ends, they
+// go back, and layout(s) -- the unit's, as at its first enable -- lays them out again
+template <class S, class Layout>
+int keyed_relayout(const HookCtx &q, HookSlot &slot, S &s, Layout layout) {
+    slot.on = false;
+    HOOKCHK(q, hipStreamSynchronize(q.stream));
+    hook_release(s);
+    return layout(s);
+}
+
 // amp_*_get's entries: info and n as the table stands, then -- when the caller's array holds them -- the used slots,
 // compacted on the device and sorted here
 template <class T, class Info>
-int keyed_get(const HookCtx &q, const KeyedTableOf<T> &t, typename T::Entry *entries, int64_t cap, int64_t *n, Info *info) {
+int keyed_get(const HookCtx &q, const typename T::Table &t, typename T::Entry *entries, int64_t cap, int64_t *n, Info *info) {
     using Entry = typename T::Entry;
     Guard g(q.device);
     unsigned long long h[2] = {0ull, 0ull};
@@ -110,6 +117,7 @@ int keyed_get(const HookCtx &q, const KeyedTableOf<T> &t, typename T::Entry *ent
     HOOKCHK(q, hipMalloc((void **)&d_out, (size_t)h[0] * sizeof(Entry)));
     unsigned long long *d_n = t.info + 2;                          // (inside the allocation's last 64 bytes)
     const int rc = [&]() -> int {
+        HOOKCHK(q, hipMemsetAsync(d_out, 0, (size_t)h[0] * sizeof(Entry), q.stream));      // (the entries' padding, too)
         HOOKCHK(q, hipMemsetAsync(d_n, 0, 8, q.stream));
         const uint64_t slots = 1ull << t.log2_capacity;
         k_keyed_compact<T><<<(unsigned)((slots + 255) / 256), 256, 0, q.stream>>>(t, d_out, d_n, h[0]);
@@ -125,7 +133,7 @@ int keyed_get(const HookCtx &q, const KeyedTableOf<T> &t, typename T::Entry *ent
 
 // amp_*_add's entries: each checked by `traits`, then all of them through k_keyed_add
 template <class T>
-int keyed_add(const HookCtx &q, const KeyedTableOf<T> &t, const T &traits, const typename T::Entry *entries, int64_t n) {
+int keyed_add(const HookCtx &q, const typename T::Table &t, const T &traits, const typename T::Entry *entries, int64_t n) {
     using Entry = typename T::Entry;
     for (int64_t k = 0; k < n; ++k)
         if (!traits.check(entries[k], (long long)k, q.err, q.err_cap)) return AMP_EINVAL;

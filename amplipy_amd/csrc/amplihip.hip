@@ -275,7 +275,7 @@ HookCtx ctx_hook(amp_ctx *c) {
 HookSlot &hook_slot(amp_ctx *c, int which) { return c->hooks[which]; }
 }  // namespace amp
 
-static const HookOps *const HOOKS[N_HOOKS] = {&qc_hook, &strand_hook, &amplicon_hook, &codon_hook, &del_hook, &cooc_hook, &errprof_hook, &hap_hook, &readpos_hook};      // in the enum's order: the run order
+static const HookOps *const HOOKS[N_HOOKS] = {&qc_hook, &strand_hook, &amplicon_hook, &codon_hook, &del_hook, &insev_hook, &cooc_hook, &errprof_hook, &hap_hook, &readpos_hook};      // in the enum's order: the run order
 
 // What the hooks that are on have to note in FRONT of the read pass (HookOps::before_pass, where a unit has one)
 static int hooks_before_pass(amp_ctx *c, uint64_t read_base) {
@@ -427,7 +427,7 @@ void amp_ctx_destroy(amp_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (int k = 0; k < N_HOOKS; ++k) {
         HOOKS[k]->free_state(c->hooks[k].state);
-        c->hooks[k] = HookSlot{false, nullptr, 0};
+        c->hooks[k] = HookSlot{false, nullptr};
     }
     if (c->own_counts && c->d_counts) (void)hipFree(c->d_counts);
     if (c->d_min_start) (void)hipFree(c->d_min_start);
@@ -774,10 +774,9 @@ int amp_reset(amp_ctx *c) {
     k_reset<<<std::min<unsigned>(RESET_BLOCKS, (unsigned)((words + ctr_words + 1023) / 1024)), 256, 0, c->stream>>>(c->d_counts, words, (uint32_t *)c->d_ctr, ctr_words);
     HIPCHK(c, hipGetLastError());
     for (int k = 0; k < N_HOOKS; ++k) {        // (... and the tables of every hook that has some, on or off)
-        for (const HookState *s = (const HookState *)c->hooks[k].state; s; s = s->more) {      // (a slot of two halves: both)
-            const int rc = hook_zero(ctx_hook(c), *s);
-            if (rc != AMP_OK) return rc;
-        }
+        if (!c->hooks[k].state) continue;
+        const int rc = hook_zero(ctx_hook(c), *(const HookState *)c->hooks[k].state);
+        if (rc != AMP_OK) return rc;
     }
     return AMP_OK;
 }

@@ -92,5 +92,5 @@ def __getattr__(name):
     from . import amplicon, codon, cooc, deletion, errprof, haplotype, readpos, strand
     global REGISTRY
     REGISTRY = (strand.StrandReport, amplicon.AmpliconReport, codon.CodonReport, deletion.DeletionReport, cooc.CoocReport,
-                errprof.ErrprofReport, haplotype.HapReport, readpos.ReadposReport)      # HOOK_STRAND .. HOOK_READPOS of amp_hook.hpp
+                errprof.ErrprofReport, haplotype.HapReport, readpos.ReadposReport)      # HOOK_STRAND .. HOOK_READPOS of amp_hook.hpp (HOOK_INSEV aside: DeletionReport drives it)
     return REGISTRY

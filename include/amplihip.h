@@ -809,12 +809,14 @@ int amp_del_enable(amp_ctx *ctx, int on, int log2_capacity);
 int amp_del_get(amp_ctx *ctx, amp_del_event *entries, int64_t cap, int64_t *n, amp_del_info *info);
 /* Host entries inserted through the kernel's own insert path (the merge of partial tables): a call per job, not per batch. */
 int amp_del_add(amp_ctx *ctx, const amp_del_event *entries, int64_t n);
-/* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
+/* Time of the hook's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran.  Behind a batch
+ * that ran with the hook off it answers what every switched-off hook answers: the time of the last batch that ran with it on
+ * (AMP_ESTATE when there was none), whether the insertion evidence is on or not. */
 int amp_del_last_ms(amp_ctx *ctx, float *ms);
 
 /* ---- insertion alleles: strand, quality and read-position evidence (opt-in) ---------------------------
- * The insertion half of the indel unit: it shares the deletion events' place behind the read pass, and either half may be on
- * alone (amp_del_enable(ctx, 0, ...) switches the deletion half off only).  While it is on, one more kernel behind every
+ * The insertion half of the indel unit: a hook of its own directly behind the deletion events', and either may be on alone
+ * (amp_del_enable(ctx, 0, ...) switches the deletion events off only).  While it is on, one more kernel behind every
  * batch's read pass reads the insertion events that THIS batch's pass appended to the event list (whatever the caller's drain
  * pattern: the list's slot counts are noted in front of the pass) and tallies them per allele: key (ref_pos, len, hash) --
  * the two values amp_aggregate_ins_events sorts by, so one key is one allele of one position.  Per key: count (events), rev
@@ -833,14 +835,15 @@ typedef struct amp_insev_entry {
 typedef amp_del_info amp_insev_info;        /* used: distinct alleles; lost: EVENTS of keys that found no slot */
 #define AMP_INSEV_STRIDE (512 * 256) /* events the kernel's fixed grid takes in one stride of its loop */
 /* on != 0: the half on, the table zero; 2^log2_capacity slots of 64 bytes (0: the default, 20; else 4 to 28, AMP_EINVAL
- * otherwise), laid out again only when the capacity changed.  on == 0: off; the table stays readable.  The refusals of
- * amp_process_batch_device are the deletion half's. */
+ * otherwise), laid out again only when the capacity changed.  on == 0: off; the table stays readable.  With the hook on and
+ * do_trim set, amp_process_batch_device refuses a dev_out without new_pos, new_ncig, new_cig or status (AMP_EINVAL) before
+ * anything runs, in this hook's name. */
 int amp_insev_enable(amp_ctx *ctx, int on, int log2_capacity);
 /* The used entries as they stand (waits for the stream), ordered by (ref_pos, len, hash); the rest as amp_del_get. */
 int amp_insev_get(amp_ctx *ctx, amp_insev_entry *entries, int64_t cap, int64_t *n, amp_insev_info *info);
 /* Host entries inserted through the kernel's own insert path (the merge of partial tables): a call per job, not per batch. */
 int amp_insev_add(amp_ctx *ctx, const amp_insev_entry *entries, int64_t n);
-/* Time of the half's kernel behind the last batch; AMP_ESTATE when none ran.  (amp_del_last_ms stays k_del's.) */
+/* Time of the hook's kernel (k_insev) behind the last batch, as amp_del_last_ms is k_del's; AMP_ESTATE when none ran. */
 int amp_insev_last_ms(amp_ctx *ctx, float *ms);
 
 /* ---- co-occurrence of listed mutations on single reads (opt-in) ----------------------------------------------

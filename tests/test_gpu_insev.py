@@ -247,12 +247,17 @@ def test_insev_add_of_a_table_onto_itself_doubles_every_cell():
 
 
 # ---- 5. the two halves of the indel unit ---------------------------------------------------------------------------------------------
+def indel_case():
+    """540 reads: 300 with a deletion on both strands, 40 with insertions of their own, 200 with one and the same."""
+    rng = np.random.default_rng(3)
+    dels = [U.read(100 + k % 7, [(M, 20), (K.D, 3 + k % 2), (M, 30)], rng=rng, flag=16 * (k & 1)) for k in range(300)]
+    return simple(K.by_pos(dels + U.distinct(40, pos=104) + U.copies(200, pos=103)))
+
+
 def test_either_half_alone_and_both():
     """The deletion table's bytes are the same with the insertion half on beside it; the insertion table is the same with the
     deletion half beside it; amp_del_enable(0) switches the deletion half off only."""
-    rng = np.random.default_rng(3)
-    dels = [U.read(100 + k % 7, [(M, 20), (K.D, 3 + k % 2), (M, 30)], rng=rng, flag=16 * (k & 1)) for k in range(300)]
-    case = simple(K.by_pos(dels + U.distinct(40, pos=104) + U.copies(200, pos=103)))
+    case = indel_case()
     snaps = {}
     for halves in ("del", "ins", "both"):
         eng = engine(case.G, case.tabs, insev=halves != "del")
@@ -274,6 +279,41 @@ def test_either_half_alone_and_both():
     assert snaps["del"][0] == snaps["both"][0] and len(snaps["del"][0]) >= 2 * abi.DEL_EVENT_DTYPE.itemsize
     assert snaps["ins"][1] == snaps["both"][1] == U.by_key(case.want())
     assert snaps["del"][2] == snaps["ins"][2] == snaps["both"][2]
+
+
+@pytest.mark.parametrize("first", ["insev", "del"])
+def test_the_two_slots_are_independent(first):
+    """In either enable order and with both tables filled: an enable of one unit at another capacity empties its own table and
+    leaves the other's bytes; amp_reset empties both; a batch behind all that fills both to the restatements' values."""
+    from tests import del_util
+    case = indel_case()
+    b = case.batch
+    dels = del_util.table([b.segment(i) for i in range(b.n)], MQ, case.G)
+    want_ins, want_del, want_del2 = U.by_key(case.want()), del_util.as_array(dels).tobytes(), del_util.as_array(del_util.add_tables(dels, dels)).tobytes()
+    assert len(dels) >= 2 and len(want_ins) >= 41
+    eng = engine(case.G, case.tabs, insev=False)
+    try:
+        for unit in (first, "del" if first == "insev" else "insev"):
+            getattr(eng, unit + "_enable")()
+        ins_bytes = lambda: eng.insev_entries()[0].tobytes()
+        del_bytes = lambda: eng.del_events()[0].tobytes()
+        eng.process(b)
+        filled = ins_bytes()
+        assert got(eng) == want_ins and del_bytes() == want_del
+        eng.del_enable(12)                      # another capacity: the deletion table alone starts over
+        assert del_bytes() == b"" and eng.del_events()[1]["capacity"] == 1 << 12 and ins_bytes() == filled
+        eng.process(b, read_base=b.n)
+        assert del_bytes() == want_del and got(eng) == U.by_key(U.scaled(case.want(), 2))
+        eng.insev_enable(12)                    # ... and the converse
+        assert ins_bytes() == b"" and eng.insev_entries()[1]["capacity"] == 1 << 12 and del_bytes() == want_del
+        eng.process(b, read_base=2 * b.n)
+        assert got(eng) == want_ins and del_bytes() == want_del2
+        eng.reset()
+        assert ins_bytes() == b"" and del_bytes() == b""
+        eng.process(b)
+        assert got(eng) == want_ins and ins_bytes() == filled and del_bytes() == want_del
+    finally:
+        eng.close()
 
 
 def test_all_nine_hooks_beside_the_new_kernel():

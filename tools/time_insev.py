@@ -2,15 +2,18 @@
 
   * the benchmark's 10k x batch (1,993,533 reads of 150 bases, built on the device by synth_torch) through process_device with
     every per-read output -- the SPARSE load: the insertion events that batch happens to hold.  The read pass with every hook
-    off (amp_last_kernel_ms), then k_del alone (amp_del_last_ms), then k_insev alone (amp_insev_last_ms), then both halves of
-    the indel unit together;
+    off (amp_last_kernel_ms), then k_del alone (amp_del_last_ms), then k_insev alone (amp_insev_last_ms), then both hooks of
+    the indel unit (HOOK_DEL and HOOK_INSEV, amp_hook.hpp) together;
   * the HOT-SPOT load: as many reads as the batch has, all on one amplicon, every one with the same four-base insertion, through
     process (the host form): every slot of the list holds one and the same key.  k_insev, k_del and the read pass itself
     (which piles the same reads onto one stretch of the count table) in the same launches.
 
-20 launches per figure after 5 warm-up launches (8 after 2 on the hot spot, whose batch is staged anew every time), medians.  With --parent-lib the read pass with every switch off is timed on
-both builds, which take turns, a fresh process each (tools/time_hooks.py's child): `hook_off_ratio` is this build's median over
-the parent's, next to the parent's own run-to-run spread (max / min over its rounds) from the same session.
+20 launches per figure after 5 warm-up launches (8 after 2 on the hot spot, whose batch is staged anew every time), medians.  With --parent-lib both builds are
+timed, taking turns, a fresh process each (tools/time_hooks.py's child): the read pass with every switch off and -- when the
+parent has the unit -- the same figures as this build.  `hook_off_ratio` is this build's median over the parent's, next to the
+parent's own run-to-run spread (max / min over its rounds) from the same session; `vs_parent` holds the same for k_insev
+(sparse and hot spot) and k_del: both medians, the ratio, the parent's spread, and whether this build's median lies inside the
+parent's range.
 
   python tools/time_insev.py [--parent-lib PATH/libamplihip.so] [--rounds 5] [--out profiles/insev.json]
 """
@@ -42,9 +45,11 @@ def hot_batch(n, pos):
                                   cig, np.broadcast_to(codes, (n, codes.size)), np.full((n, codes.size), 37, np.uint8))
 
 
-def leg(with_insev):
+def leg(this):
+    from amplipy_amd import lib
+    with open(lib.LIB_PATH, "rb") as f:        # (looked for in the file: loading the library here would bring HIP up in front of torch)
+        with_insev = this or b"amp_insev_enable" in f.read()
     if not with_insev:             # (a build from before the unit has none of its entry points, nor the getter that came with it)
-        from amplipy_amd import lib
         lib.EXPORTS[:] = [n for n in lib.EXPORTS if not n.startswith("amp_insev_") and n != "amp_debug_event_capacity"]
     s = time_hooks.Setup()
     e, med = s.eng, statistics.median
@@ -96,6 +101,12 @@ def main():
         res["hook_off_ratio"] = res["pass_off_ms"] / med(p)
         res["parent_spread_ratio"] = max(p) / min(p)
         res["hook_off_within_parent_spread"] = min(p) / med(p) <= res["hook_off_ratio"] <= max(p) / med(p)
+        res["vs_parent"] = {}
+        for key in ("sparse_insev_ms", "hot_insev_ms", "sparse_del_ms"):
+            p = [r[key] for r in res["rounds"]["parent"] if key in r]
+            if p:
+                res["vs_parent"][key] = {"this": res[key], "parent": med(p), "parent_min": min(p), "parent_max": max(p), "ratio": res[key] / med(p),
+                                         "parent_spread_ratio": max(p) / min(p), "within_parent_range": min(p) <= res[key] <= max(p)}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
