@@ -138,6 +138,15 @@ QC_REGION_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("depth_sum", "<u8
                             ("covered", "<u4", (QC_MAX_DEPTHS,))])
 assert QC_REGION_DTYPE.itemsize == 40
 
+# ---- QC report, soft-clip sites (amp_qc_clips_*): table uint32[ref_len + 1][2][CLIP_CELLS], scalars uint64[CLIP_SCALARS] ----
+CLIP_K = 16                    # clipped bases kept per site, nearest the junction first
+CLIP_COLS = 5                  # A C G T other
+CLIP_CELLS = 2 + CLIP_K * CLIP_COLS      # reads, rev, comp[j][c]
+CLIP_LEFT, CLIP_RIGHT = 0, 1
+CLIP_SCALARS = 4
+CLIP_SCALAR_FIELDS = ("scanned", "skipped", "left", "right")
+CLIP_MIN_MAX = 64              # clip_min: 1..64
+
 
 def ptr(a):
     """Address of a contiguous numpy array (or None)."""

@@ -15,7 +15,7 @@ import sys
 import types
 from os.path import isfile
 
-from . import AMPLIPY_VERSION, calling, insevidence, lib, parallel, qc, reports
+from . import AMPLIPY_VERSION, abi, calling, clips, insevidence, lib, parallel, qc, reports
 from .drivers import (NATIVE_BATCH_READS, DeviceBamDriver, NativeDriver, NativeInput, native_parts, open_driver,  # noqa: F401
                       select)
 from .readloop import BATCH_READS, PROGRESS_NUM_READS, ReadLoop, error, print_log  # noqa: F401
@@ -133,7 +133,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 codon_out_fn=None, aa_out_fn=None, deletions=False, del_out_fn=None, indel_vcf_fn=None, del_capacity=None, cooc_fn=None,
                 cooc_out_fn=None, error_profile_fn=None, error_mask_fn=None, haplotypes_fn=None, hap_out_fn=None, hap_min_reads=None,
                 hap_min_freq=None, hap_capacity=None, readpos=False, readpos_end=None, readpos_fn=None, insertions=False, ins_out_fn=None,
-                ins_capacity=None, ins_end=None):
+                ins_capacity=None, ins_end=None, qc_clips=False, qc_clip_fn=None, qc_junction_fn=None, qc_clip_min=None, qc_clip_reads=None):
     """The reference's run_amplipy (AmpliPy.py:774-963) on the MI355X engine.
 
     gpu_sam (default: AMPLIPY_GPU_SAM, off): SAM text in (and SAM text or nothing out) goes through the device codec of
@@ -150,6 +150,12 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     per region -- tallied on the device behind every batch's read pass, whichever codec feeds it.  qc_regions_fn: a BED of further
     regions (ref, start, end, name); qc_depths: up to 4 depth thresholds (1, 10, 100); qc_depth_fn: depth of every position as a
     TSV file (runs with a count table).  With all four None the engine's report is never switched on.
+    qc_clips (default: off; needs qc_fn): the report gains the section "clips"  -- soft-clip sites and the
+    junctions they place: deletions and duplications the aligner clipped instead of opening a gap for them.  A second kernel of
+    the QC unit tallies, per reference position and side, the reads clipped there by at least qc_clip_min bases (1..64, default
+    10) and their first 16 clipped bases; the host builds a consensus per site with at least qc_clip_reads reads (default 2),
+    holds it against the reference and reports what lands elsewhere.  qc_clip_fn: every such site as a TSV file; qc_junction_fn:
+    the junctions as a TSV file; either switches the report's hook on by itself.  With all three off the kernel never runs.
     strand (default: off; runs that write a VCF): every VCF record also carries REF_RV, ALT_RV, REF_QUAL, ALT_QUAL and SB
      -- reverse-strand depth, mean base quality and a strand-bias p-value per allele -- from two more tables
     the device tallies behind every batch's read pass.  strand_fn: the tables of every position as a TSV file (runs with a count
@@ -242,11 +248,23 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         error("QC regions and QC depth thresholds need a QC report (--qc)")
     if qc_depth_fn is not None and not (run_variants or run_consensus):
         error("A run that only trims has no count table: no per-position depth (--qc_depth_out)")
+    clips_on = bool(qc_clips) or qc_clip_fn is not None or qc_junction_fn is not None       # (the run's arguments alone: every rank agrees)
+    if qc_clips and qc_fn is None:
+        error("The clip section is part of the QC report: it needs one (--qc_clips needs --qc)")
+    if not clips_on and (qc_clip_min is not None or qc_clip_reads is not None):
+        error("A clip length or a read threshold without clip sites (--qc_clip_min and --qc_clip_reads need --qc_clips, --qc_clip_out or --qc_junction_out)")
+    if clips_on:
+        qc_clip_min = clips.DEFAULT_CLIP_MIN if qc_clip_min is None else qc_clip_min
+        qc_clip_reads = clips.DEFAULT_MIN_READS if qc_clip_reads is None else qc_clip_reads
+        if not 1 <= qc_clip_min <= abi.CLIP_MIN_MAX:
+            error("Minimum clip length must be between 1 and %d: %s" % (abi.CLIP_MIN_MAX, qc_clip_min))
+        if qc_clip_reads < 1:
+            error("Minimum reads of a clip site must be >= 1: %s" % qc_clip_reads)
     every = [R() for R in reports.REGISTRY]
     for r in every:
         r.check(run)
     on = [r for r in every if r.active(run)]
-    qc_on = qc_fn is not None or qc_depth_fn is not None
+    qc_on = qc_fn is not None or qc_depth_fn is not None or clips_on
     if qc_on:
         qc_depths = list(qc.DEFAULT_DEPTHS) if qc_depths is None else list(qc_depths)
         if len(qc_depths) > 4 or any(d < 0 for d in qc_depths):
@@ -287,7 +305,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     # Opening the files can fail on ONE rank of a multi-rank run (a missing share, an output that exists): the other ranks must
     # not be left waiting in the collective, so with several ranks the failure is carried to the exchange in front of it
     driver = vcf = rank_error = None
-    qc_files, qc_regions, qc_primers = [None, None], [], []
+    qc_files, qc_regions, qc_primers = [None, None, None, None], [], []
     reads_in, reads_out = (untrimmed_reads_fn, trimmed_reads_fn) if run_trim else (trimmed_reads_fn, None)
     try:
         if rank == 0 and final_trimmed_fn is not None and final_trimmed_fn.lower() != "stdout" and isfile(final_trimmed_fn):
@@ -311,7 +329,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             qc_regions = [(0, G, qc.WHOLE)] + (qc.load_regions(qc_regions_fn) if qc_regions_fn is not None else [])
             qc_primers = qc.load_primer_rows(primer_fn) if run_trim else []
             if rank == 0:
-                qc_files = [qc.open_new(fn) if fn is not None else None for fn in (qc_fn, qc_depth_fn)]
+                qc_files = [qc.open_new(fn) if fn is not None else None for fn in (qc_fn, qc_depth_fn, qc_clip_fn, qc_junction_fn)]
     except (Exception, SystemExit) as e:
         if dist is None:
             raise
@@ -324,6 +342,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
     if qc_on and rank_error is None:
         eng.qc_enable([(s, e) for s, e, _ in qc_primers], primer_pos_offset or 0, min_length if min_length is not None else 0,
                       include_no_primer, [(s, e) for s, e, _ in qc_regions], qc_depths)
+        if clips_on:
+            eng.qc_clips_enable(qc_clip_min)
     if rank_error is None:
         for r in on:
             r.enable(run, eng)
@@ -358,6 +378,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                                                                                         ", ".join("%.1f" % (100.0 * b_ / tot) for _, b_ in shares)))
         if qc_on:                        # every rank's tallies to rank 0, which adds them up
             qc_parts = parallel.gather_objects(dist, rank, world, eng.qc_read_tallies())
+        if clips_on:                     # ... and the clip sites, summed on every rank; rank 0 uses them
+            clip_tables = clips.from_wire(parallel.allreduce_numpy(dist, device, clips.to_wire(*eng.qc_clips_tables())), G)
         if final_trimmed_fn is not None and driver.part_writer is not None:
             # the ranks' files (all closed by now: the writer threads were joined in run()) become the one trimmed BAM
             parts = parallel.gather_objects(dist, rank, world, (driver.part_writer.path, driver.part_writer.header_bytes))
@@ -373,6 +395,8 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
         qc_depth = qc_region_recs = None
         if qc_on and rank == 0:
             qc_tallies = qc.merge_read_tallies(qc_parts) if dist is not None else eng.qc_read_tallies()
+            if clips_on and dist is None:
+                clip_tables = eng.qc_clips_tables()
         if do_count:
             cp = calling.call_params(min_depth_consensus if min_depth_consensus is not None else 0,
                                      min_freq_consensus if min_freq_consensus is not None else 0,
@@ -384,7 +408,7 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                 eng.sync()
                 parallel.allreduce_table(dist, table)      # the ONE collective of the run: every rank now holds the job's table
             if qc_on and rank == 0:                        # depth from the job's table
-                qc_depth, qc_region_recs = eng.qc_depth(want_depth=qc_depth_fn is not None)
+                qc_depth, qc_region_recs = eng.qc_depth(want_depth=qc_depth_fn is not None or clips_on)      # (a junction's flank depths)
             for r in on:                                   # one more all-reduce or gather per report, in the same order on every rank
                 r.collect(run, eng)
 
@@ -409,6 +433,9 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
             for r in on:                                   # (a report is on only in a run with a count table)
                 if not r.with_calls:
                     r.write(run, res)
+        if clips_on and rank == 0:
+            clip_sites = clips.find_sites(clip_tables[0], ref_seq, qc_clip_reads)
+            clip_junctions = clips.find_junctions(clip_sites, G, qc_depth)
         if qc_on and rank == 0:
             if qc_fn is not None:
                 report = qc.build_report(
@@ -418,11 +445,19 @@ def run_amplipy(untrimmed_reads_fn=None, primer_fn=None, reference_fn=None, trim
                     [name for _, _, name in qc_regions], qc_region_recs, qc_depths)
                 for r in on:
                     r.add_to_qc(report)
+                if qc_clips:
+                    report["clips"] = clips.section(qc_clip_min, qc_clip_reads, clip_tables[1], clip_sites, clip_junctions)
                 qc.write_json(qc_files[0], report)
                 print_log("Output QC report: %s" % qc_fn)
                 print_log(qc.summary_line(report))
             if qc_depth_fn is not None:
                 qc.write_depth(qc_files[1], ref_id, qc_depth)
+            if qc_clip_fn is not None:
+                clips.write_sites(qc_files[2], ref_id, clip_sites)
+            if qc_junction_fn is not None:
+                clips.write_junctions(qc_files[3], ref_id, clip_junctions)
+            if clips_on:
+                print_log("Clip sites: %d with at least %d reads, %d junctions" % (len(clip_sites), qc_clip_reads, len(clip_junctions)))
         for r in on:
             r.summary(run)
         for r in on:
@@ -504,6 +539,11 @@ def parse_args(argv=None):
         p.add_argument("--qc_regions", required=False, type=str, default=None, help="Further regions of the QC report (BED: ref, start, end, name); needs --qc")
         p.add_argument("--qc_depths", required=False, type=str, default=None, help="Depth thresholds of the QC report, at most 4 (1,10,100 when omitted); needs --qc")
         p.add_argument("--qc_depth_out", required=False, type=str, default=None, help="Depth of every position (TSV or TSV.gz: ref, position, depth)")
+        p.add_argument("--qc_clips", action="store_true", help="The QC report gains the section \"clips\": soft-clip sites and the junctions they place, deletions and duplications the aligner clipped instead of opening a gap; needs --qc")
+        p.add_argument("--qc_clip_out", required=False, type=str, default=None, help="Every soft-clip site with at least --qc_clip_reads reads: position, side, reads, reverse reads, consensus of the clipped bases, class, partner (TSV or TSV.gz)")
+        p.add_argument("--qc_junction_out", required=False, type=str, default=None, help="Junctions placed from soft-clip sites: kind, start, end, length, reads and reverse reads of either side, depth of the flanks (TSV or TSV.gz)")
+        p.add_argument("--qc_clip_min", required=False, type=int, default=None, help="Clipped bases a read needs at a site, 1 to 64 (10 when omitted); needs --qc_clips, --qc_clip_out or --qc_junction_out")
+        p.add_argument("--qc_clip_reads", required=False, type=int, default=None, help="Reads a site needs to be written (2 when omitted); needs --qc_clips, --qc_clip_out or --qc_junction_out")
         p.add_argument("--strand", action="store_true", help="VCF records also carry REF_RV, ALT_RV, REF_QUAL, ALT_QUAL and SB: reverse-strand depth, mean base quality and strand bias per allele (variants, aio)")
         p.add_argument("--amplicons", required=False, type=str, default=None, help="Amplicon file (TSV: left primer, right primer[, amplicon name]): per-amplicon allele counts on the device, and AMP, AMP_DP, AMP_REF_DP, AMP_ALT_DP, AMP_NA_DP, AMP_P and PRIMER on every VCF record (aio)")
         p.add_argument("--amplicon_out", required=False, type=str, default=None, help="Count of every symbol per amplicon and position of its span (TSV or TSV.gz; aio, needs --amplicons)")
@@ -538,7 +578,13 @@ def main(argv=None):
     args = parse_args(argv)
     if args.qc is None and (args.qc_regions is not None or args.qc_depths is not None):
         error("--qc_regions and --qc_depths need --qc")
-    qc_args = dict(qc_fn=args.qc, qc_regions_fn=args.qc_regions, qc_depth_fn=args.qc_depth_out,
+    if args.qc_clips and args.qc is None:
+        error("--qc_clips needs --qc")
+    if (args.qc_clip_min is not None or args.qc_clip_reads is not None) and not (args.qc_clips or args.qc_clip_out is not None or args.qc_junction_out is not None):
+        error("--qc_clip_min and --qc_clip_reads need --qc_clips, --qc_clip_out or --qc_junction_out")
+    qc_args = dict(qc_clips=args.qc_clips, qc_clip_fn=args.qc_clip_out, qc_junction_fn=args.qc_junction_out, qc_clip_min=args.qc_clip_min,
+                   qc_clip_reads=args.qc_clip_reads)
+    qc_args.update(qc_fn=args.qc, qc_regions_fn=args.qc_regions, qc_depth_fn=args.qc_depth_out,
                    qc_depths=qc.parse_depths(args.qc_depths) if args.qc_depths is not None else None)
     qc_args.update(strand=args.strand, strand_fn=args.strand_out, amplicons_fn=args.amplicons, amplicon_out_fn=args.amplicon_out,
                    codons_fn=args.codons, codon_out_fn=args.codon_out, aa_out_fn=args.aa_out, deletions=args.deletions,

@@ -28,7 +28,8 @@ UNIT_DEPS = {"amplihip.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")
              "amp_deflate.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")],
              # (amp_hook.hpp: the host shell the ten hooks behind the read pass share; amp_tally.hpp: the device skeleton of the four
              # windowed tally kernels, and the whole loop of k_strand and k_readpos; amp_keyed.hpp: the keyed table of del, insev and hap)
-             "amp_qc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_qc.hpp")],
+             # (amp_clip.hpp: the clip sites of the QC report; amp_tally.hpp for the wave combine its kernel shares with the tally kernels)
+             "amp_qc.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_qc.hpp", "amp_clip.hpp", "amp_strand.hpp", "amp_tally.hpp")],
              "amp_strand.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_tally.hpp")],
              "amp_amplicon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_amplicon.hpp", "amp_tally.hpp")],
              "amp_codon.hip": [os.path.join(_HERE, "..", "include", "amplihip.h")] + [os.path.join(CSRC, f) for f in ("amp_hook.hpp", "amp_strand.hpp", "amp_codon.hpp", "amp_tally.hpp")],

@@ -10,6 +10,8 @@
 // No step relies on the reads being sorted: an unsorted batch only makes shorter runs.
 // k_qc_depth and k_qc_regions turn the count table as it stands into depth per position and per-region figures, without
 // atomics: the output does not depend on the order anything ran in.
+// k_qc_clips (section 15b) is the report's second per-batch kernel, behind k_qc_reads while its own sub-switch is on: soft-clip
+// sites per reference position and side, from the reads as they came in (amp_clip.hpp).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -20,8 +22,10 @@
 #include <new>
 #include <vector>
 
+#include "amp_clip.hpp"
 #include "amp_hook.hpp"
 #include "amp_qc.hpp"
+#include "amp_tally.hpp"
 
 namespace amp {
 
@@ -32,7 +36,12 @@ struct QcState : HookState {
     int32_t *d_rstart = nullptr, *d_rend = nullptr;       // [n_regions], clamped
     amp_qc_region *d_regions = nullptr;                   // [n_regions]
     uint32_t *d_depth = nullptr;                          // [ref_len]
+    // the clip sites (amp_qc_clips_enable): the table and, behind it in the same allocation, the CL_N_SCALARS 64-bit scalars
+    uint32_t *d_clip = nullptr;
+    int32_t clip_min = 0;                                 // 0: the sub-switch is off
+    HookTimer clip_timer;                                 // k_qc_clips' own: `timer` stays k_qc_reads'
     size_t tally_words() const { return (size_t)QC_N_TALLIES + 2 * (size_t)p.n_primers; }
+    ~QcState() { clip_timer.destroy(); }
 };
 
 struct QcReadsArgs {
@@ -132,6 +141,98 @@ k_qc_reads(QcReadsArgs a) {
     }
 }
 
+struct QcClipsArgs {
+    int64_t n;
+    const int32_t *pos;
+    const uint16_t *flag;
+    const uint32_t *lseq, *cig_off32, *cig, *seq_off8;
+    const uint8_t *seq, *status;
+    uint32_t *table;                    // [(ref_len + 1)][2][CL_CELLS]
+    unsigned long long *scalars;        // [CL_N_SCALARS]
+    int32_t ref_len, clip_min;
+};
+
+// What one read adds to its site, cell by cell (a lane whose site no other lane of the wave shares)
+__device__ __forceinline__ void qc_clip_add_alone(uint32_t *cells, uint32_t rev, uint64_t cols) {
+    atomicAdd(&cells[0], 1u);
+    if (rev) atomicAdd(&cells[1], 1u);
+    for (int j = 0; j < CL_K; ++j) {
+        const uint32_t f = clip_field(cols, j);
+        if (f == CL_NO_COL) break;
+        atomicAdd(&cells[2 + j * CL_COLS + (int)f], 1u);
+    }
+}
+
+// One lane per read.  The normal input is a pile -- thousands of neighbouring reads with one pos, hence one LEFT site; with
+// pre-trimmed input nearly every read has a primer-length clip at one of a few hundred sites -- so nothing is added per read:
+// per side the wave's lanes fall into groups with the same site (wave_each_distinct), a group's reads and reverse reads are
+// popcounts of ballots, and per clipped-base offset five ballots give the group's count of every column, which lanes 0..4 add,
+// one atomic each where the count is not zero.  The atomics a wave issues grow with its distinct sites, not with its reads.  A
+// lane that is alone on its site is only noted in the loop and adds its own cells behind it, all such lanes at once.  A wave
+// without a site of a side leaves that side at wave_each_distinct's first ballot.  Nothing relies on the batch being sorted.
+__global__ void __launch_bounds__(QC_BLOCK)
+k_qc_clips(QcClipsArgs a) {
+    const int tid = (int)threadIdx.x, lane = qc_lane();
+    uint32_t cnt[CL_N_SCALARS] = {0u, 0u, 0u, 0u};      // wave-uniform
+    // (the bound is the same for every lane of the block: the ballots and shuffles below always see whole waves)
+    for (int64_t base = (int64_t)blockIdx.x * QC_BLOCK; base < a.n; base += (int64_t)gridDim.x * QC_BLOCK) {
+        const int64_t i = base + tid;
+        const bool live = i < a.n && (a.status ? a.status[i] == 0 : true);
+        ClipRead r;
+        r.skipped = 0; r.L[0] = r.L[1] = 0; r.p[0] = r.p[1] = -1;
+        int32_t lseq = 0;
+        uint32_t rev = 0u;
+        uint64_t sbase = 0ull;
+        if (live) {
+            const uint32_t c0 = a.cig_off32[i], c1 = a.cig_off32[i + 1];
+            lseq = (int32_t)a.lseq[i];
+            r = clip_scan(a.pos[i], a.cig + c0, c1 - c0, lseq, a.ref_len, a.clip_min);
+            rev = (a.flag[i] & 0x10u) ? 1u : 0u;
+            sbase = (uint64_t)a.seq_off8[i] * 8ull;
+        }
+        cnt[CL_SCANNED] += (uint32_t)__popcll(__ballot(live && !r.skipped));
+        cnt[CL_SKIPPED] += (uint32_t)__popcll(__ballot(live && r.skipped));
+        cnt[CL_N_LEFT] += (uint32_t)__popcll(__ballot(r.p[CL_LEFT] >= 0));
+        cnt[CL_N_RIGHT] += (uint32_t)__popcll(__ballot(r.p[CL_RIGHT] >= 0));
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            const int32_t key = r.p[side];                // in [0, ref_len] (clip_scan), or -1
+            const bool have = key >= 0;
+            const uint64_t cols = have ? clip_cols(a.seq, sbase, lseq, side, r.L[side]) : ~0ull;
+            bool alone = false;
+            int32_t site = 0;                             // the group's key: a scalar
+            wave_each_distinct(have, [&](int src) { site = __shfl(key, src); return have && key == site; },
+                               [&](int src, unsigned long long same) {
+                const uint32_t n_in = (uint32_t)__popcll(same);
+                if (n_in == 1u) { alone = alone || lane == src; return; }
+                const bool in = (same >> lane) & 1ull;
+                uint32_t *const cells = a.table + clip_site_word(site, side);
+                const uint32_t n_rev = (uint32_t)__popcll(__ballot(in && rev));
+                if (lane == 0) atomicAdd(&cells[0], n_in);
+                if (lane == 1 && n_rev) atomicAdd(&cells[1], n_rev);
+                for (int j = 0; j < CL_K; ++j) {
+                    const uint32_t f = in ? clip_field(cols, j) : CL_NO_COL;
+                    if (!__ballot(f != CL_NO_COL)) break;      // (no read of the group is clipped this far)
+                    uint32_t mine = 0u;
+#pragma unroll
+                    for (int c = 0; c < CL_COLS; ++c) {
+                        const uint32_t v = (uint32_t)__popcll(__ballot(f == (uint32_t)c));
+                        mine = lane == c ? v : mine;
+                    }
+                    if (lane < CL_COLS && mine) atomicAdd(&cells[2 + j * CL_COLS + lane], mine);
+                }
+            });
+            if (alone) qc_clip_add_alone(a.table + clip_site_word(key, side), rev, cols);
+        }
+    }
+    if (lane < CL_N_SCALARS) {
+        uint32_t mine = 0u;
+#pragma unroll
+        for (int k = 0; k < CL_N_SCALARS; ++k) mine = lane == k ? cnt[k] : mine;
+        if (mine) atomicAdd(&a.scalars[lane], (unsigned long long)mine);
+    }
+}
+
 __global__ void __launch_bounds__(QC_BLOCK)
 k_qc_depth(const uint32_t *__restrict__ counts, int32_t ref_len, uint32_t *__restrict__ depth) {
     for (int64_t p = (int64_t)blockIdx.x * QC_BLOCK + threadIdx.x; p < ref_len; p += (int64_t)gridDim.x * QC_BLOCK)
@@ -186,10 +287,24 @@ static int qc_enqueue_reads(amp_ctx *c, const amp_dev_reads *rd, const amp_trim_
     a.tally = s->d_tally; a.n_primers = s->p.n_primers;
     a.P = QcReadParams{q.ref_len, q.do_trim ? 1 : 0, s->p.min_length, s->p.include_no_primer};
     // (paid once per block: its LDS histogram and its twelve adds)
-    return hook_launch(q, s, qc_hook, a.n, o, QC_BLOCK, QC_TILES_PER_BLOCK, QC_BLOCKS_PER_CU, [&](unsigned grid) {
+    HOOKTRY(hook_launch(q, s, qc_hook, a.n, o, QC_BLOCK, QC_TILES_PER_BLOCK, QC_BLOCKS_PER_CU, [&](unsigned grid) {
         if (2 * (int64_t)s->p.n_primers <= QC_LDS_COUNTERS) k_qc_reads<true><<<grid, QC_BLOCK, 0, q.stream>>>(a);
         else k_qc_reads<false><<<grid, QC_BLOCK, 0, q.stream>>>(a);
-    });
+    }));
+    if (s->clip_min <= 0 || !s->d_clip) return AMP_OK;
+    // the clip sites, behind it on the same stream, between the events of a timer of their own
+    s->clip_timer.timed = false;
+    if (a.n <= 0) return AMP_OK;
+    QcClipsArgs k;
+    k.n = rd->n_reads; k.pos = rd->pos; k.flag = rd->flag; k.lseq = rd->lseq; k.cig_off32 = rd->cig_off32; k.cig = rd->cig;
+    k.seq_off8 = rd->seq_off8; k.seq = rd->seq; k.status = a.status;
+    k.table = s->d_clip; k.scalars = (unsigned long long *)(s->d_clip + clip_table_words(q.ref_len));
+    k.ref_len = q.ref_len; k.clip_min = s->clip_min;
+    HOOKCHK(q, s->clip_timer.begin(q.stream));
+    k_qc_clips<<<hook_grid(k.n, QC_BLOCK, QC_TILES_PER_BLOCK, QC_BLOCKS_PER_CU, q.n_cu), QC_BLOCK, 0, q.stream>>>(k);
+    HOOKCHK(q, hipGetLastError());
+    HOOKCHK(q, s->clip_timer.end(q.stream));
+    return AMP_OK;
 }
 
 HookOps qc_hook = {"the QC report needs", OUT_NEW_POS | OUT_REF_LEN | OUT_TRIM_FLAGS | OUT_STATUS, qc_enqueue_reads, hook_free<QcState>};
@@ -308,5 +423,73 @@ int amp_qc_depth(amp_ctx *c, uint32_t *depth, amp_qc_region *regions) {
 }
 
 int amp_qc_last_ms(amp_ctx *c, float *reads_ms) { return hook_last_ms(c, HOOK_QC, reads_ms); }
+
+// ---- clip sites: the sub-switch of the report ----
+static size_t qc_clip_bytes(int32_t ref_len) { return clip_table_words(ref_len) * 4 + CL_N_SCALARS * sizeof(uint64_t); }
+
+// The state with a clip table, or the refusal's code with its message in the ctx error text
+static int qc_clip_state(amp_ctx *c, const HookCtx &q, const char *who, QcState *&s) {
+    s = qc_state(c);
+    if (s && s->d_clip) return AMP_OK;
+    snprintf(q.err, q.err_cap, "%s: %s", who, s ? "the clip sites were not enabled since the last amp_qc_enable (amp_qc_clips_enable)" : "no QC report (amp_qc_enable)");
+    return AMP_ESTATE;
+}
+
+int amp_qc_clips_enable(amp_ctx *c, int32_t clip_min) {
+    if (!c) return AMP_EINVAL;
+    const HookCtx q = ctx_hook(c);
+    QcState *s = qc_state(c);
+    if (clip_min < 0 || clip_min > CL_MIN_MAX) {
+        snprintf(q.err, q.err_cap, "amp_qc_clips_enable: clip_min %d is not in 0..%d", (int)clip_min, CL_MIN_MAX);
+        return AMP_EINVAL;
+    }
+    if (!s) {
+        snprintf(q.err, q.err_cap, "amp_qc_clips_enable: no QC report (amp_qc_enable)");
+        return AMP_ESTATE;
+    }
+    if (clip_min == 0) { s->clip_min = 0; return AMP_OK; }       // off; a table read so far stays readable
+    Guard g(q.device);
+    const size_t bytes = qc_clip_bytes(q.ref_len);
+    if (!s->d_clip) {
+        HOOKCHK(q, s->clip_timer.create());
+        HOOKTRY(hook_alloc(q, *s, &s->d_clip, bytes, bytes));     // (zeros: all of it, so amp_reset clears it)
+    }
+    HOOKCHK(q, hipStreamSynchronize(q.stream));      // (a kernel of the last setting may be in flight)
+    HOOKCHK(q, hipMemsetAsync(s->d_clip, 0, bytes, q.stream));
+    s->clip_min = clip_min;
+    return AMP_OK;
+}
+
+int amp_qc_clips_get(amp_ctx *c, uint32_t *table, uint64_t *scalars) {
+    if (!c) return AMP_EINVAL;
+    const HookCtx q = ctx_hook(c);
+    QcState *s;
+    HOOKTRY(qc_clip_state(c, q, "amp_qc_clips_get", s));
+    Guard g(q.device);
+    const size_t words = clip_table_words(q.ref_len);
+    if (table) HOOKCHK(q, hipMemcpyAsync(table, s->d_clip, words * 4, hipMemcpyDeviceToHost, q.stream));
+    if (scalars) HOOKCHK(q, hipMemcpyAsync(scalars, s->d_clip + words, CL_N_SCALARS * sizeof(uint64_t), hipMemcpyDeviceToHost, q.stream));
+    HOOKCHK(q, hipStreamSynchronize(q.stream));
+    return AMP_OK;
+}
+
+int amp_qc_clips_add(amp_ctx *c, const uint32_t *table, const uint64_t *scalars) {
+    if (!c) return AMP_EINVAL;
+    const HookCtx q = ctx_hook(c);
+    QcState *s;
+    HOOKTRY(qc_clip_state(c, q, "amp_qc_clips_add", s));
+    Guard g(q.device);
+    const size_t words = clip_table_words(q.ref_len);
+    HOOKTRY(hook_add(q, s->d_clip, table, words));
+    return hook_add(q, (uint64_t *)(s->d_clip + words), scalars, (size_t)CL_N_SCALARS);
+}
+
+int amp_qc_clips_last_ms(amp_ctx *c, float *ms) {
+    if (!c) return AMP_EINVAL;
+    const HookCtx q = ctx_hook(c);
+    QcState *s;
+    HOOKTRY(qc_clip_state(c, q, "amp_qc_clips_last_ms", s));
+    return s->clip_timer.last_ms(q, ms);
+}
 
 }  // extern "C"

@@ -38,6 +38,7 @@ EXPORTS = [
     "amp_sam_first_bad", "amp_sam_waits",
     "amp_bam_set_references", "amp_bam_text_check", "amp_bam_format",
     "amp_qc_find_primer_owners", "amp_qc_enable", "amp_qc_read_tallies", "amp_qc_depth", "amp_qc_last_ms",
+    "amp_qc_clips_enable", "amp_qc_clips_get", "amp_qc_clips_add", "amp_qc_clips_last_ms",
     "amp_strand_enable", "amp_strand_get", "amp_strand_add", "amp_strand_last_ms",
     "amp_amplicon_enable", "amp_amplicon_get", "amp_amplicon_add", "amp_amplicon_last_ms",
     "amp_codon_enable", "amp_codon_get", "amp_codon_add", "amp_codon_last_ms",
@@ -357,6 +358,26 @@ class Engine:
 
     def qc_last_ms(self):
         return self._hook_last_ms("amp_qc_last_ms")
+
+    # ---- QC report: soft-clip sites ----------------------------------------------------
+    def qc_clips_enable(self, clip_min):
+        """amp_qc_clips_enable: the clip sites of the QC report on (clip_min 1..64), their table zero; 0: off.  Needs a QC
+        report, and has to be called again after every ``qc_enable``."""
+        self._chk(self.L.amp_qc_clips_enable(self.h, C.c_int32(int(clip_min))), "amp_qc_clips_enable")
+
+    def _clip_specs(self):
+        return [((self.ref_len + 1, 2, abi.CLIP_CELLS), np.uint32), ((abi.CLIP_SCALARS,), np.uint64)]
+
+    def qc_clips_tables(self):
+        """amp_qc_clips_get -> (table uint32[ref_len + 1][2][CLIP_CELLS], scalars uint64[4]: abi.CLIP_SCALAR_FIELDS)."""
+        return tuple(self._tables("amp_qc_clips_get", self._clip_specs()))
+
+    def qc_clips_add(self, table, scalars):
+        """amp_qc_clips_add: a host table and its scalars added element-wise (the merge of partial tables)."""
+        self._tables("amp_qc_clips_add", self._clip_specs(), (table, scalars))
+
+    def qc_clips_last_ms(self):
+        return self._hook_last_ms("amp_qc_clips_last_ms")
 
     # ---- strand and base-quality tallies ---------------------------------------------
     def strand_enable(self):

@@ -713,6 +713,34 @@ int amp_qc_depth(amp_ctx *ctx, uint32_t *depth /* [ref_len] or NULL */, amp_qc_r
 /* Time of the report's kernel behind the last batch (HIP events on the ctx stream); AMP_ESTATE when none ran. */
 int amp_qc_last_ms(amp_ctx *ctx, float *reads_ms);
 
+/* ---- QC report: soft-clip sites (opt-in sub-switch of the report) --------------------------------------------
+ * A large deletion leaves no gap in an alignment: the aligner aligns one side and soft-clips the rest.  With the sub-switch on, a
+ * second kernel behind the report's tallies, per reference position and side, the reads that are clipped there and their first
+ * AMP_CLIP_K clipped bases, from every row with status 0 as it CAME IN (original pos, CIGAR, l_seq, FLAG, SEQ; no quality test):
+ *   L_left / L_right: the S ops summed from the front (leading H ops skipped) up to the first other op / from the back down to
+ *   element 1.  A read is skipped -- it adds to `skipped` and to nothing else -- when l_seq <= 0, when it has no op other than H and S,
+ *   when L_left + L_right > l_seq, when pos < 0 or when pos + the CIGAR's reference length > ref_len.  Every other read is scanned.
+ *   L_left >= clip_min: a LEFT site at p = pos, its clipped base at offset j the query base L_left - 1 - j (nearest the junction first);
+ *   L_right >= clip_min: a RIGHT site at p = pos + the reference length, in [0, ref_len], offset j the query base l_seq - L_right + j.
+ *   Per site: reads += 1, rev += 1 with FLAG 0x10, comp[j][col] += 1 for j < min(L, AMP_CLIP_K); col 0..3 for the BAM codes 1 2 4 8
+ *   (A C G T), 4 for anything else.
+ * table: uint32 [(ref_len + 1)][2][AMP_CLIP_CELLS], position-major, side 0 = left; a site's cells are reads, rev, comp[j][c].
+ * scalars: scanned, skipped, left, right -- reads that were scanned / skipped / have a site of that side. */
+#define AMP_CLIP_K 16
+#define AMP_CLIP_COLS 5
+#define AMP_CLIP_CELLS (2 + AMP_CLIP_K * AMP_CLIP_COLS)
+#define AMP_CLIP_SCALARS 4
+/* clip_min 1..64: on, the table zero; 0: off (a table read so far stays readable); anything else AMP_EINVAL.  AMP_ESTATE unless a QC
+ * report exists; amp_qc_enable builds a new report, so this has to be called again after every amp_qc_enable. */
+int amp_qc_clips_enable(amp_ctx *ctx, int32_t clip_min);
+/* Host copies as they stand (waits for the stream); either pointer may be NULL.  AMP_ESTATE unless the clip sites were enabled
+ * since the last amp_qc_enable. */
+int amp_qc_clips_get(amp_ctx *ctx, uint32_t *table, uint64_t scalars[AMP_CLIP_SCALARS]);
+/* Host table and scalars added element-wise onto the device's (the merge of partial tables); either pointer may be NULL. */
+int amp_qc_clips_add(amp_ctx *ctx, const uint32_t *table, const uint64_t *scalars);
+/* Time of the clip kernel behind the last batch; AMP_ESTATE when none ran.  amp_qc_last_ms stays the report's first kernel. */
+int amp_qc_clips_last_ms(amp_ctx *ctx, float *ms);
+
 /* ---- per-allele strand and base-quality tallies (opt-in) ----------------------------------------------------
  * The evidence behind a call that the count table forgets.  For every read with status 0, each increment update_base_counts
  * (AmpliPy.py:690-753) makes to one of the six fixed keys A C G T N '-' of position r (columns 0..5 as in the count table) also adds
